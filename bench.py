@@ -46,6 +46,8 @@ METRIC = "audio-sec separated / wall-sec (RTF), UVR-MDX-NET 44.1kHz stereo, 1/2/
 PMC_FILES = ("r05_pmc_conv3x3.json", "r03_pmc_conv3x3.json", "r02_pmc_conv3x3.json", "r01_pmc_conv3x3.json")
 PMC_FILES_WINO = ("r05_pmc_wino3.json", "r04_pmc_wino3.json", "r03_pmc_wino3.json")
 PMC_FILES_3H = ("r06_pmc_conv3h.json",)
+DUMP_BYTES = 64 * 10**6 - 64 * 1024  # --dump-outputs: all .npy files together, headers included, stay under 64 MB
+DUMP_SEED = 0
 
 
 def cpu_baseline(seconds: float, seed: int):
@@ -82,6 +84,29 @@ def cpu_baseline(seconds: float, seed: int):
                                 f"{dt:.1f} s wall" + note}
 
 
+def dump_outputs(directory, arrays):
+    """Write each float32 tensor of ``arrays`` ({name: tensor}) as ``directory/<name>.npy``.  Arrays that together exceed DUMP_BYTES
+    are sampled: the same DUMP_SEED-seeded, sorted set of flat element indices for a given shape, so that two builds given the same
+    arguments write element-for-element comparable files."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    total = sum(int(t.numel()) for t in arrays.values())
+    budget = DUMP_BYTES // 4
+    written = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = int(flat.numel())
+        k = n if total <= budget else n * budget // total
+        if k < n:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float32).cpu().numpy()
+        a = a if k < n else a.reshape(tuple(t.shape))
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written[name] = {"shape": list(t.shape), "elements_written": int(a.size), "sampled": k < n}
+    print(f"bench.py: --dump-outputs {directory}: {written}", file=sys.stderr)
+
+
 _JSON_FD = None
 
 
@@ -114,7 +139,12 @@ def parse_args(argv=None):
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dry-gloo", action="store_true")
     ap.add_argument("--master-port", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32; an output larger "
+                         f"than {DUMP_BYTES // 10**6} MB is written as a fixed seeded sample of its elements (dump_outputs())")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.config5:
         args.mode, args.songs_per_rank = "files", 8
     return args
@@ -336,8 +366,10 @@ def main():
         adapter = HipEngineAdapter(eng)
         shard_ws = ShardWorkspace(graph=not args.no_graph)   # local / slab / out allocated once: the loop times compute + gather + fold; the rank's chunk-range compute replays a captured hipGraph from its third call on
 
+        last = {}
+
         def step(k):
-            sharded_demix(adapter, mix, workspace=shard_ws)
+            last["out"] = sharded_demix(adapter, mix, workspace=shard_ws)
 
         def drain():
             pass
@@ -364,6 +396,15 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = songs_per_step * args.seconds * args.steps / dt
+
+    # ---- what the last timed step handed its caller on rank 0, before anything below reuses the buffers ----
+    if args.dump_outputs and rank == 0:
+        if args.mode == "files":
+            b = (args.steps - 1) & 1                    # FilesPipeline.step(k) demixes into outs[k & 1]
+            stems = torch.cat(pipe.gathered[b]) if use_dist else pipe.outs[b]     # [ranks x songs, 2, N], the primary stem of each song
+        else:
+            stems = last["out"].unsqueeze(0)            # [1, 2, N]
+        dump_outputs(args.dump_outputs, {"stems": stems})
 
     # ---- the same K steps on the fp32-EXACT arithmetic (gemm_f16x3 = 0: every split-operand kernel multiplies exact three-way bf16 splits, six
     # products per multiply-add; conv3h_kernel's level falls back to conv_wino3_kernel), outside the timed region: both headlines are driver-timed

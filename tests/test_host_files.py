@@ -1,12 +1,11 @@
 """CPU tests of the file edges and model-file readers above the C ABI: the WAV codec, the Demucs package / bag reader
 (restricted unpickling, checksums, error behaviour of repo.py), the Roformer configuration mirror against the reference's
-own normaliser (build container only for that part), CommonSeparator's naming rules."""
-import importlib
-import importlib.machinery
+own normaliser (stored outputs), CommonSeparator's naming rules."""
+import ast
+import json
 import logging
 import os
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -14,9 +13,6 @@ import pytest
 import audio_separator_amd as A
 from audio_separator_amd import audio_io, model_files as MF, roformer_config as RC
 from tests import separate_cases as SC
-
-REF = "/root/reference"
-
 
 # ---- WAV codec ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("subtype,tol", [("PCM_16", 2 / 32767), ("PCM_24", 2 / 8388607), ("PCM_32", 1e-6), ("FLOAT", 0.0), ("DOUBLE", 1e-7)])
@@ -197,31 +193,27 @@ YAMLS = {
 }
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/audio_separator"), reason="reference tree not present")
+ROFORMER_PATHS = ("/m/model_bs_roformer_x.ckpt", "/m/mel_band_roformer_y.ckpt", "/m/plain.ckpt")
+
+
 @pytest.mark.parametrize("name", sorted(YAMLS))
-def test_roformer_config_matches_reference_normaliser(name, monkeypatch):
-    for n, path in (("audio_separator", REF + "/audio_separator"), ("audio_separator.separator", REF + "/audio_separator/separator")):
-        pkg = types.ModuleType(n)
-        pkg.__path__ = [path]
-        pkg.__spec__ = importlib.machinery.ModuleSpec(n, None, is_package=True)
-        monkeypatch.setitem(sys.modules, n, pkg)
-    norm_mod = importlib.import_module("audio_separator.separator.roformer.configuration_normalizer")
-    ref = norm_mod.ConfigurationNormalizer()
+def test_roformer_config_matches_reference_normaliser(name, golden_dir):
+    """Against what the reference's ConfigurationNormalizer returned for the same YAML and path (tests/golden/make_golden_reference_tables.py)."""
+    with open(os.path.join(golden_dir, "reference_tables.json")) as fh:
+        table = json.load(fh)["roformer_normaliser"]
     cfg = YAMLS[name]
-    for path in ("/m/model_bs_roformer_x.ckpt", "/m/mel_band_roformer_y.ckpt", "/m/plain.ckpt"):
+    for path in ROFORMER_PATHS:
         mine_type = RC.model_type_from_path(cfg, path)
-        try:
-            want = ref.normalize_from_file_path(cfg, path, apply_defaults=True, validate=True)
-        except Exception as e:                                  # reference refuses -> so must the mirror
+        rec = table[f"{name}|{path}"]
+        if "error" in rec:                                      # reference refuses -> so must the mirror
+            assert "ParameterValidationError" in rec["error"]
             with pytest.raises(RC.ParameterValidationError):
                 RC.normalize_config(cfg, mine_type)
-            assert "ParameterValidationError" in type(e).__name__
             continue
+        want = ast.literal_eval(rec["config"])
         got = RC.normalize_config(cfg, mine_type)
         assert got == want, (name, path, {k: (got.get(k), want.get(k)) for k in set(got) | set(want) if got.get(k) != want.get(k)})
-        assert RC.detect_model_type(got) == ref.detect_model_type(want)
-    for k in [k for k in sys.modules if k.startswith("audio_separator.separator.roformer")]:
-        sys.modules.pop(k, None)
+        assert RC.detect_model_type(got) == rec["model_type"]
 
 
 def test_roformer_constructor_args_quirks():
@@ -273,3 +265,14 @@ def test_install_registers_reference_module_names():
     finally:
         A.uninstall()
     assert not any(n in sys.modules for n in names)
+
+
+def test_stem_vocabulary_equals_the_references(golden_dir):
+    """Every upper-case class constant of the reference's CommonSeparator (stem names, STEM_PAIR_MAPPER, NON_ACCOM_STEMS,
+    common_separator.py:19-53; stored by tests/golden/make_golden_reference_tables.py) has the same value here: the
+    orchestrator, the presets and the file names rely on them."""
+    with open(os.path.join(golden_dir, "reference_tables.json")) as fh:
+        consts = {k: ast.literal_eval(v) for k, v in json.load(fh)["stem_constants"].items()}
+    assert len(consts) >= 30
+    for k, v in consts.items():
+        assert getattr(A.CommonSeparator, k) == v, k
