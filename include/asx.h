@@ -197,8 +197,16 @@ int asx_separate_dev(asx_engine *e, float *mix_dev, int64_t n_samples, float max
 /* ---- MDXC / TFC-TDF v3 (MDX23C): uvr_lib_v5/tfc_tdf_v3.py + the TFC branch of MDXCSeparator.demix ----
  * The engine's n_fft / hop_length / dim_f / segment_size (asx_mdx_config) are config.audio.* and
  * inference.dim_t (or the overridden segment size, mdxc_separator.py:354-359).
- *   norm: 0 = None, 1 = InstanceNorm (affine)          tfc_tdf_v3.py:55-69
- *   act:  0 = relu, 1 = gelu                            tfc_tdf_v3.py:72-80
+ *   norm (tfc_tdf_v3.py:55-69, model.norm):
+ *         0       = None / Identity (also any unrecognised norm string)
+ *         1       = InstanceNorm (affine)
+ *         2       = BatchNorm (eval: running statistics; needs "<prefix>.running_mean" / ".running_var",
+ *                   num_batches_tracked is ignored)
+ *         256 + G = GroupNorm<G> (G >= 1 groups; G must divide every normalised channel count, else
+ *                   asx_v3_commit fails)
+ *   act (tfc_tdf_v3.py:72-80, model.act):
+ *         0 = relu, 1 = gelu, 2 = elu<alpha>: alpha is the one-element tensor "__act_alpha__", set with
+ *         asx_net_set_tensor() between asx_v3_begin() and asx_v3_commit()
  * Weights are handed over with asx_net_set_tensor() under the reference's own state_dict keys
  * (e.g. "encoder_blocks.0.tfc_tdf.blocks.1.tfc1.2.weight"); scale is fixed to [2, 2]. */
 typedef struct asx_v3_config {

@@ -1106,8 +1106,10 @@ int asx_v3_begin(asx_engine *e, const asx_v3_config *cfg) {
   REQUIRE(cfg->num_scales >= 1 && cfg->num_blocks_per_scale >= 1 && cfg->num_channels_model > 0 && cfg->growth >= 0 &&
               cfg->bottleneck_factor >= 1 && cfg->num_targets >= 1,
           "bad TFC-TDF v3 hyper-parameters");
-  REQUIRE(cfg->norm == 0 || cfg->norm == 1, "norm must be None (0) or InstanceNorm (1)");
-  REQUIRE(cfg->act == 0 || cfg->act == 1, "act must be relu (0) or gelu (1)");
+  REQUIRE(v3_norm_valid(cfg->norm), "norm must be None (0), InstanceNorm (1), BatchNorm (2) or 256 + G for GroupNorm(G), got %d",
+          cfg->norm);
+  REQUIRE(cfg->act == V3_ACT_RELU || cfg->act == V3_ACT_GELU || cfg->act == V3_ACT_ELU,
+          "act must be relu (0), gelu (1) or elu (2), got %d", cfg->act);
   const int fs = e->cfg.dim_f / cfg->num_subbands;
   REQUIRE(fs % (1 << cfg->num_scales) == 0 && e->cfg.segment_size % (1 << cfg->num_scales) == 0,
           "dim_f / num_subbands and segment_size must be divisible by 2^num_scales");
@@ -1134,6 +1136,13 @@ int asx_v3_commit(asx_engine *e) {
   const asx_v3_config &cf = n.cfg;
   const int k = cf.num_subbands, dim_c = k * cf.num_channels * 2;
   int c = cf.num_channels_model, f = e->cfg.dim_f / k;
+  n.act_alpha = 1.f;
+  if (cf.act == V3_ACT_ELU) {
+    const float *al;
+    CHK(get_tensor(e, V3_ACT_ALPHA_TENSOR, 1, &al));
+    REQUIRE(std::isfinite(*al), "elu alpha must be finite");
+    n.act_alpha = *al;
+  }
   CHK(v3_load_conv(e, n.first, CK_1X1, "first_conv.weight", dim_c, c, 1));
   n.enc.assign(cf.num_scales, {});
   n.dec.assign(cf.num_scales, {});

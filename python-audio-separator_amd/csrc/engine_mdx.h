@@ -258,6 +258,7 @@ struct ConvView {
   const float *res = nullptr;
   int64_t aux_bstride = 0;  // of skip / res; 0 = dense
   int act = -1;             // -1 = the layer's own activation
+  float alpha = 1.f;        // act == ACT_ELU (CK_1X1 layers only)
 };
 
 // x [B,cin,T,F] -> y
@@ -277,6 +278,8 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
   a.T = T;
   a.F = F;
   a.act = v.act >= 0 ? v.act : (L.relu ? ACT_RELU : ACT_NONE);
+  a.alpha = v.alpha;
+  REQUIRE(a.act != ACT_ELU || L.kind == CK_1X1, "ELU epilogue: 1x1 convolutions only");
   a.CG = L.cg;
   a.NCI = L.nci;
   static const int nt_mode = getenv("ASX_NT") ? atoi(getenv("ASX_NT")) : 0;   // bit 0: conv stores, bit 1: TDF stores, bit 2: TDF residual loads

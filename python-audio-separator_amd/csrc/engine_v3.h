@@ -6,10 +6,14 @@
 // (instnorm_stats_kernel + norm_act_kernel) that writes the activated tensor the MFMA kernels
 // then DMA; shortcut adds, the TDF residual, the decoder concat (written in place through
 // channel-slice views) and the final `x * first_conv_out` are fused or zero-copy.
+// GroupNorm runs a split statistics pass (v3_gn_partial_kernel + v3_gn_finish_kernel) into the same
+// per-(b, c) (mean, rstd) table; BatchNorm (eval) is folded into a per-channel scale / shift at load
+// time and needs no statistics.  All norms share norm_act_kernel.
 #pragma once
+#include "v3_norm.h"
 
 struct V3Norm {
-  DevBuf g, b;
+  DevBuf g, b;  // affine weight / bias; BatchNorm: the folded scale / shift
   int c = 0;
 };
 
@@ -22,6 +26,7 @@ struct V3Block {
 
 struct V3Net {
   asx_v3_config cfg{};
+  float act_alpha = 1.f;  // cfg.act == V3_ACT_ELU
   bool begun = false, ready = false;
   ConvLayer first, final0, final1;
   std::vector<std::vector<V3Block>> enc, dec;
@@ -30,7 +35,7 @@ struct V3Net {
   std::vector<V3Norm> ds_n, us_n;
   // workspace (sized for ws_batch chunks)
   int ws_batch = 0;
-  DevBuf cat0, firstout, S, A, X1, X2, XB, CUR, H, HA, stats, out_spec, frames, chunk_out, d_starts;
+  DevBuf cat0, firstout, S, A, X1, X2, XB, CUR, H, HA, stats, gn_part, out_spec, frames, chunk_out, d_starts;
   std::vector<DevBuf> lvl;
 };
 
@@ -62,7 +67,7 @@ static void v3_free(V3Net &n) {
   for (auto &c : n.us) free_conv(c);
   for (auto &x : n.ds_n) v3_free_norm(x);
   for (auto &x : n.us_n) v3_free_norm(x);
-  DevBuf *bufs[] = {&n.cat0, &n.firstout, &n.S, &n.A, &n.X1, &n.X2, &n.XB, &n.CUR, &n.H, &n.HA, &n.stats,
+  DevBuf *bufs[] = {&n.cat0, &n.firstout, &n.S, &n.A, &n.X1, &n.X2, &n.XB, &n.CUR, &n.H, &n.HA, &n.stats, &n.gn_part,
                     &n.out_spec, &n.frames, &n.chunk_out, &n.d_starts};
   for (auto *b : bufs) b->release();
   for (auto &l : n.lvl) l.release();
@@ -79,10 +84,26 @@ static void v3_destroy(V3Net *n) {
 // ---------------------------------------------------------------------------
 static int v3_load_norm(asx_engine *e, V3Norm &n, const std::string &prefix, int c) {
   n.c = c;
-  if (e->v3->cfg.norm == 0) return ASX_OK;
+  const int norm = e->v3->cfg.norm;
+  if (norm == V3_NORM_NONE) return ASX_OK;
+  const int G = v3_norm_groups(norm);
+  // nn.GroupNorm refuses these at construction (tfc_tdf_v3.py:55-69)
+  REQUIRE(G == 0 || c % G == 0, "%s: GroupNorm%d needs the channel count to be divisible by the number of groups, got %d channels",
+          prefix.c_str(), G, c);
   const float *g, *b;
   CHK(get_tensor(e, prefix + ".weight", c, &g));
   CHK(get_tensor(e, prefix + ".bias", c, &b));
+  std::vector<float> sc, sh;
+  if (norm == V3_NORM_BATCH) {  // eval(): running statistics, folded (num_batches_tracked is not used)
+    const float *rm, *rv;
+    CHK(get_tensor(e, prefix + ".running_mean", c, &rm));
+    CHK(get_tensor(e, prefix + ".running_var", c, &rv));
+    sc.resize(c);
+    sh.resize(c);
+    v3_bn_fold(c, g, b, rm, rv, 1e-5, sc.data(), sh.data());
+    g = sc.data();
+    b = sh.data();
+  }
   CHK(n.g.ensure((size_t)c * 4));
   CHK(n.b.ensure((size_t)c * 4));
   HIPCHK(hipMemcpy(n.g.p, g, (size_t)c * 4, hipMemcpyHostToDevice));
@@ -136,20 +157,33 @@ struct V3View {
 
 static int v3_norm_act(asx_engine *e, const V3Norm &n, V3View x, int C, int64_t P, int B, float *y, hipStream_t s) {
   V3Net &net = *e->v3;
-  const bool has_norm = net.cfg.norm != 0;
+  const int norm = net.cfg.norm;
   float2 *st = reinterpret_cast<float2 *>(net.stats.p);
-  const int act = net.cfg.act == 1 ? 2 : 1;  // cfg.act: 0 relu, 1 gelu -> kernel enum 1 relu, 2 gelu
+  // cfg.act: 0 relu, 1 gelu, 2 elu -> kernel enum (ACT_*) 1 relu, 2 gelu, 3 elu
+  const int act = net.cfg.act == V3_ACT_GELU ? ACT_GELU : net.cfg.act == V3_ACT_ELU ? ACT_ELU : ACT_RELU;
   const double bytes_r = 4.0 * B * C * (double)P;
-  if (has_norm) {
+  if (norm == V3_NORM_INSTANCE) {
     CHK(timed(e, ASX_PROF_MISC, 0.0, bytes_r, s, [&]() {
       hipLaunchKernelGGL(instnorm_stats_kernel, dim3(C, B), dim3(256), 0, s, x.p, x.bstride, C, P, 1e-5f, st);
     }));
+  } else if (norm > V3_NORM_GROUP) {
+    const int G = v3_norm_groups(norm);
+    const int64_t len = (int64_t)(C / G) * P;
+    const int ns = v3_gn_splits(B, G, len);
+    REQUIRE(C % G == 0 && net.gn_part.bytes >= (size_t)B * G * ns * sizeof(double2), "GroupNorm%d over %d channels: workspace", G, C);
+    double2 *part = reinterpret_cast<double2 *>(net.gn_part.p);
+    CHK(timed(e, ASX_PROF_MISC, 0.0, bytes_r, s, [&]() {
+      hipLaunchKernelGGL(v3_gn_partial_kernel, dim3((unsigned)ns, (unsigned)G, (unsigned)B), dim3(256), 0, s, x.p, x.bstride, C, G, P,
+                         ns, part);
+      hipLaunchKernelGGL(v3_gn_finish_kernel, dim3((unsigned)G, (unsigned)B), dim3(256), 0, s, part, C, G, P, ns, 1e-5f, st);
+    }));
   }
+  const bool has_stats = norm == V3_NORM_INSTANCE || norm > V3_NORM_GROUP;
   const unsigned gx = (unsigned)std::min<int64_t>((P / 4 + 255) / 256 + 1, 64);
-  const float *gp = n.g.f(), *bp = n.b.f();
+  const float *gp = norm == V3_NORM_NONE ? nullptr : n.g.f(), *bp = norm == V3_NORM_NONE ? nullptr : n.b.f();
   CHK(timed(e, ASX_PROF_MISC, 0.0, 2.0 * bytes_r, s, [&]() {
     hipLaunchKernelGGL(norm_act_kernel, dim3(gx, C, B), dim3(256), 0, s, x.p, x.bstride, C, P,
-                       has_norm ? st : nullptr, gp, bp, act, y);
+                       has_stats ? st : nullptr, gp, bp, act, net.act_alpha, y);
   }));
   return ASX_OK;
 }
@@ -206,6 +240,7 @@ static int v3_ensure_workspace(asx_engine *e, int B) {
   CHK(n.HA.ensure(big / 2 / cf.bottleneck_factor + 256));
   int cmax = c0 + cf.growth * cf.num_scales;
   CHK(n.stats.ensure((size_t)B * 2 * cmax * sizeof(float2)));
+  if (cf.norm > V3_NORM_GROUP) CHK(n.gn_part.ensure((size_t)B * v3_norm_groups(cf.norm) * V3_GN_MAX_SPLIT * sizeof(double2)));
   n.lvl.resize(cf.num_scales);
   int c = c0;
   int64_t P = P0;
@@ -275,7 +310,8 @@ static int v3_core_dev(asx_engine *e, int B, hipStream_t s) {
     }));
   }
   ConvView vf;
-  vf.act = cf.act == 1 ? ACT_GELU : ACT_RELU;
+  vf.act = cf.act == V3_ACT_GELU ? ACT_GELU : cf.act == V3_ACT_ELU ? ACT_ELU : ACT_RELU;  // final_conv.1 is the same act module
+  vf.alpha = n.act_alpha;
   CHK(conv_launch(e, n.final0, n.cat0.f(), nullptr, n.X1.f(), B, T, Fs, s, vf));
   CHK(conv_launch(e, n.final1, n.X1.f(), nullptr, n.out_spec.f(), B, T, Fs, s));
   return ASX_OK;

@@ -701,7 +701,7 @@ __global__ __launch_bounds__(256) void mdxc_finalize_kernel(const float *__restr
 }
 
 // ---------------------------------------------------------------------------
-// TFC-TDF v3 pre-activation blocks: InstanceNorm2d(affine) statistics and norm -> act.
+// TFC-TDF v3 pre-activation blocks: InstanceNorm2d(affine) / GroupNorm statistics and norm -> act.
 // x is a channel-slice view [B, C, P] (P = T*F) with batch stride x_bstride.
 // stats[b*C + c] = (mean, 1/sqrt(var + eps)), biased variance, accumulated in float64.
 // ---------------------------------------------------------------------------
@@ -745,16 +745,107 @@ __global__ __launch_bounds__(256) void instnorm_stats_kernel(const float *__rest
   }
 }
 
-__device__ __forceinline__ float v3_act(float v, int act) {
+// GroupNorm(G, C) statistics on the same channel-slice views: group g is the contiguous run of (C/G)*P floats that starts at
+// channel g*C/G.  Split reduction: v3_gn_partial_kernel sums slice k of nsplit of every (group, batch item) into
+// part[(b*G + g)*nsplit + k] (float64 sum, sum of squares); v3_gn_finish_kernel adds the slices of a group in a fixed order and
+// writes the group's (mean, rstd) to stats[b*C + c] for every channel c of the group -- the layout norm_act_kernel reads.
+// Fixed summation order, no atomics: two runs are bit-identical.
+__global__ __launch_bounds__(256) void v3_gn_partial_kernel(const float *__restrict__ x, int64_t x_bstride, int C, int G,
+                                                            int64_t P, int nsplit, double2 *__restrict__ part) {
+  const int k = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
+  const int64_t len = (int64_t)(C / G) * P;
+  const float *xp = x + (int64_t)b * x_bstride + (int64_t)g * len;
+  double s = 0.0, q = 0.0;
+  if ((P & 3) == 0 && (x_bstride & 3) == 0) {
+    const int64_t n4 = len / 4, i0 = n4 * k / nsplit, i1 = n4 * (k + 1) / nsplit;
+    const float4 *x4 = reinterpret_cast<const float4 *>(xp);
+    int64_t i = i0 + threadIdx.x;
+    for (; i + 3 * 256 < i1; i += 4 * 256) {       // four independent 16-B loads in flight per thread
+      float4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = x4[i + u * 256];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        s += (double)v[u].x + (double)v[u].y + (double)v[u].z + (double)v[u].w;
+        q += (double)v[u].x * v[u].x + (double)v[u].y * v[u].y + (double)v[u].z * v[u].z + (double)v[u].w * v[u].w;
+      }
+    }
+    for (; i < i1; i += 256) {
+      const float4 v = x4[i];
+      s += (double)v.x + (double)v.y + (double)v.z + (double)v.w;
+      q += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+    }
+  } else {
+    const int64_t i0 = len * k / nsplit, i1 = len * (k + 1) / nsplit;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+      const double v = xp[i];
+      s += v;
+      q += v * v;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    s += __shfl_xor(s, off);
+    q += __shfl_xor(q, off);
+  }
+  __shared__ double ws[4], wq[4];
+  if ((threadIdx.x & 63) == 0) {
+    ws[threadIdx.x >> 6] = s;
+    wq[threadIdx.x >> 6] = q;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    part[((int64_t)b * G + g) * nsplit + k] = make_double2(ws[0] + ws[1] + ws[2] + ws[3], wq[0] + wq[1] + wq[2] + wq[3]);
+}
+
+// one workgroup per (group, batch item): the group's slices are added in a fixed tree order (thread t takes slices
+// t, t + 256, ...; then the wave and workgroup reductions); biased variance over the group's (C/G)*P elements
+__global__ __launch_bounds__(256) void v3_gn_finish_kernel(const double2 *__restrict__ part, int C, int G, int64_t P, int nsplit,
+                                                           float eps, float2 *__restrict__ stats) {
+  const int g = blockIdx.x, b = blockIdx.y, cpg = C / G;
+  const double2 *pp = part + ((int64_t)b * G + g) * nsplit;
+  double s = 0.0, q = 0.0;
+  for (int k = threadIdx.x; k < nsplit; k += 256) {
+    s += pp[k].x;
+    q += pp[k].y;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    s += __shfl_xor(s, off);
+    q += __shfl_xor(q, off);
+  }
+  __shared__ double ws[4], wq[4];
+  __shared__ float2 st;
+  if ((threadIdx.x & 63) == 0) {
+    ws[threadIdx.x >> 6] = s;
+    wq[threadIdx.x >> 6] = q;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double n = (double)cpg * (double)P;
+    const double mean = (ws[0] + ws[1] + ws[2] + ws[3]) / n;
+    double var = (wq[0] + wq[1] + wq[2] + wq[3]) / n - mean * mean;
+    if (var < 0.0) var = 0.0;
+    st = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < cpg; c += 256) stats[(int64_t)b * C + g * cpg + c] = st;
+}
+
+// act: 1 relu, 2 gelu (erf), 3 elu(alpha) -- the ACT_* values of kernels_net.h; anything else: identity
+__device__ __forceinline__ float v3_act(float v, int act, float alpha) {
   if (act == 1) return fmaxf(v, 0.f);
   if (act == 2) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+  if (act == 3) return v > 0.f ? v : alpha * expm1f(v);
   return v;
 }
 
-// y[b,c,:] = act((x - mean) * rstd * gamma[c] + beta[c]); stats == nullptr -> act only (norm = None).
+// y[b,c,:] = act((x - mean) * rstd * gamma[c] + beta[c]) with (mean, rstd) = stats[b*C + c] (InstanceNorm / GroupNorm);
+// stats == nullptr: act(x * gamma[c] + beta[c]) (BatchNorm in eval, folded into a per-channel scale / shift at load time),
+// or act(x) when gamma is nullptr too (norm = None / Identity).
 __global__ __launch_bounds__(256) void norm_act_kernel(const float *__restrict__ x, int64_t x_bstride, int C, int64_t P,
                                                        const float2 *__restrict__ stats, const float *__restrict__ gamma,
-                                                       const float *__restrict__ beta, int act, float *__restrict__ y) {
+                                                       const float *__restrict__ beta, int act, float alpha, float *__restrict__ y) {
   const int c = blockIdx.y, b = blockIdx.z;
   const float *xp = x + (int64_t)b * x_bstride + (int64_t)c * P;
   float *yp = y + ((int64_t)b * C + c) * P;
@@ -764,21 +855,24 @@ __global__ __launch_bounds__(256) void norm_act_kernel(const float *__restrict__
     mean = st.x;
     sc = st.y * gamma[c];
     sh = beta[c];
+  } else if (gamma != nullptr) {
+    sc = gamma[c];
+    sh = beta[c];
   }
   if ((P & 3) == 0) {
     const float4 *x4 = reinterpret_cast<const float4 *>(xp);
     float4 *y4 = reinterpret_cast<float4 *>(yp);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P / 4; i += (int64_t)gridDim.x * blockDim.x) {
       float4 v = x4[i];
-      v.x = v3_act((v.x - mean) * sc + sh, act);
-      v.y = v3_act((v.y - mean) * sc + sh, act);
-      v.z = v3_act((v.z - mean) * sc + sh, act);
-      v.w = v3_act((v.w - mean) * sc + sh, act);
+      v.x = v3_act((v.x - mean) * sc + sh, act, alpha);
+      v.y = v3_act((v.y - mean) * sc + sh, act, alpha);
+      v.z = v3_act((v.z - mean) * sc + sh, act, alpha);
+      v.w = v3_act((v.w - mean) * sc + sh, act, alpha);
       y4[i] = v;
     }
   } else {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (int64_t)gridDim.x * blockDim.x)
-      yp[i] = v3_act((xp[i] - mean) * sc + sh, act);
+      yp[i] = v3_act((xp[i] - mean) * sc + sh, act, alpha);
   }
 }
 

@@ -60,7 +60,7 @@ struct ConvCfg {
   static constexpr int NWV = (W_ROWS * NWP / 4 + 255) / 256;   // weight float4 per thread per stage
 };
 
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2 };
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_ELU = 3 };  // ACT_ELU (alpha = ConvArgs::alpha): 1x1 convs only
 
 __device__ __forceinline__ float act_fn(float v, int act) {
   if (act == ACT_RELU) return fmaxf(v, 0.f);
@@ -85,7 +85,18 @@ struct ConvArgs {
   int act;
   int nt;              // 1: non-temporal output stores of the full-tile epilogue (A/B switch ASX_NT)
   int64_t x_bstride, y_bstride, aux_bstride;
+  float alpha;         // ACT_ELU: nn.ELU(alpha)
 };
+
+// Activation of the EPI_BIAS_ACT epilogue.  ELU is compiled into the 1x1 kernels only (final_conv of TFC-TDF v3 built with
+// act = elu<alpha>, tfc_tdf_v3.py:72-80); every other kernel keeps act_fn as it is.
+template <class CFG>
+__device__ __forceinline__ float conv_act(float v, const ConvArgs &a) {
+  if constexpr (CFG::KH == 1 && CFG::KW == 1) {
+    if (a.act == ACT_ELU) return v > 0.f ? v : a.alpha * expm1f(v);
+  }
+  return act_fn(v, a.act);
+}
 
 // Shared epilogue of both conv kernel families.
 template <class CFG>
@@ -114,10 +125,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &a, f32x4 (&acc)[CF
         for (int m = 0; m < MREP; ++m) {
           const int t = to0 + wave * RPW + (m >> 2), f = fo0 + (m & 3) * 16 + lk * 4;
           f32x4 v = acc[m][n];
-          v.x = act_fn(v.x + bv, a.act);
-          v.y = act_fn(v.y + bv, a.act);
-          v.z = act_fn(v.z + bv, a.act);
-          v.w = act_fn(v.w + bv, a.act);
+          v.x = conv_act<CFG>(v.x + bv, a);
+          v.y = conv_act<CFG>(v.y + bv, a);
+          v.z = conv_act<CFG>(v.z + bv, a);
+          v.w = conv_act<CFG>(v.w + bv, a);
           if (rb != nullptr) v += rs[m];
           if (a.nt) __builtin_nontemporal_store(v, reinterpret_cast<f32x4 *>(yb + ((int64_t)co * a.To + t) * a.Fo + f));
           else *reinterpret_cast<f32x4 *>(yb + ((int64_t)co * a.To + t) * a.Fo + f) = v;
@@ -132,7 +143,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &a, f32x4 (&acc)[CF
           const int64_t off = ((int64_t)co * a.To + t) * a.Fo + f;
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            if (f + r < a.Fo) yb[off + r] = act_fn(o[r] + bv, a.act) + (rb != nullptr ? rb[off + r] : 0.f);
+            if (f + r < a.Fo) yb[off + r] = conv_act<CFG>(o[r] + bv, a) + (rb != nullptr ? rb[off + r] : 0.f);
         }
       }
     }

@@ -138,6 +138,43 @@ class V3Config:
     num_targets: int = 2
 
 
+# asx_v3_config.norm / act codes (include/asx.h)
+V3_NORM_NONE, V3_NORM_INSTANCE, V3_NORM_BATCH, V3_NORM_GROUP = 0, 1, 2, 256
+V3_ACT_RELU, V3_ACT_GELU, V3_ACT_ELU = 0, 1, 2
+V3_ACT_ALPHA_TENSOR = "__act_alpha__"
+
+
+def v3_norm_act_codes(norm, act) -> tuple:
+    """model.norm / model.act of an MDX23C YAML -> (norm code, act code, elu alpha), with the rules of the reference's
+    get_norm / get_act (uvr_lib_v5/tfc_tdf_v3.py:55-80): norm None / BatchNorm / InstanceNorm / any string containing
+    "GroupNorm" (the rest must be an int, ValueError otherwise); any other norm is Identity.  act gelu / relu / elu<float>;
+    anything else raises ValueError."""
+    if norm is None:
+        n = V3_NORM_NONE
+    elif norm == "BatchNorm":
+        n = V3_NORM_BATCH
+    elif norm == "InstanceNorm":
+        n = V3_NORM_INSTANCE
+    elif "GroupNorm" in norm:
+        g = int(norm.replace("GroupNorm", ""))
+        if g < 1:
+            raise ValueError(f"GroupNorm needs at least one group, got {norm!r}")
+        n = V3_NORM_GROUP + g
+    else:
+        n = V3_NORM_NONE                                  # nn.Identity
+    alpha = 1.0
+    if act == "gelu":
+        a = V3_ACT_GELU
+    elif act == "relu":
+        a = V3_ACT_RELU
+    elif isinstance(act, str) and act[:3] == "elu":
+        alpha = float(act.replace("elu", ""))
+        a = V3_ACT_ELU
+    else:
+        raise ValueError(f"unsupported act {act!r} (gelu, relu or elu<alpha>)")
+    return n, a, alpha
+
+
 @dataclass
 class RofConfig:
     """BSRoformer constructor arguments (roformer_loader.py:123-150); n_fft / hop / dim_t live in MDXConfig."""
@@ -487,11 +524,9 @@ class Engine:
 
     # -- MDXC / TFC-TDF v3 ------------------------------------------------------
     def load_v3(self, v3: V3Config, state_dict: dict):
-        """state_dict: the reference TFC_TDF_net's own keys -> float32 arrays / torch tensors."""
-        norm = {None: 0, "": 0, "None": 0, "InstanceNorm": 1}.get(v3.norm)
-        act = {"relu": 0, "gelu": 1}.get(v3.act)
-        if norm is None or act is None:
-            raise ValueError(f"unsupported norm/act for the HIP path: {v3.norm!r}/{v3.act!r}")
+        """state_dict: the reference TFC_TDF_net's own keys -> float32 arrays / torch tensors (BatchNorm running statistics
+        included).  norm / act as the YAML names them (v3_norm_act_codes)."""
+        norm, act, alpha = v3_norm_act_codes(v3.norm, v3.act)
         c = _V3Cfg(v3.num_channels, v3.num_subbands, v3.num_scales, v3.num_blocks_per_scale, v3.num_channels_model,
                    v3.growth, v3.bottleneck_factor, norm, act, v3.num_targets)
         self._check(self._lib.asx_v3_begin(self._h, C.byref(c)))
@@ -500,6 +535,9 @@ class Engine:
                 t = t.detach().cpu().numpy()
             a = _f32(t).reshape(-1)
             self._check(self._lib.asx_net_set_tensor(self._h, name.encode(), _ptr(a), a.size))
+        if act == V3_ACT_ELU:
+            a = np.array([alpha], np.float32)
+            self._check(self._lib.asx_net_set_tensor(self._h, V3_ACT_ALPHA_TENSOR.encode(), _ptr(a), 1))
         self._check(self._lib.asx_v3_commit(self._h))
         self.v3_cfg = v3
 
