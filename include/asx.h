@@ -548,6 +548,34 @@ int asx_op_tdf(asx_engine *e, const float *x_host, int32_t batch, int32_t c, int
 int asx_op_tdf_block(asx_engine *e, const float *x_host, int32_t batch, int32_t c, int32_t t, int32_t f, const float *w0_host,
                      const float *scale0_host, const float *shift0_host, int32_t n8, const float *w1_host, const float *scale1_host,
                      const float *shift1_host, float *y_host, float *h_host);
+/* (ABI 7) One attention launch of the Roformer transformers (bs_roformer.py: Attention.forward -- softmax(q k^T / 8) v, times sigmoid(gate)
+ * per (token, head); dim_head 64), through the engine's own launch code (csrc/engine_attn.h) -- single-op test hook like asx_op_tdf.
+ * qkv [M, 3 * heads * 64] (q | k | v, head h owning columns [h * 64, h * 64 + 64) of each part, rotary already applied), gate [M, gate_ld]
+ * (pre-sigmoid, column h), out [M, heads * 64].  The tokens are the matrix [B, T, Fb] (row (b * T + t) * Fb + f); axis 0 attends along time
+ * (one sequence of length T per (b, f)), axis 1 along frequency (one of length Fb per (b, t)).  Rows M > B * T * Fb are padding that no
+ * sequence touches.  `exact` 1: libm expf in the softmax; 0: the hardware exp unit.  `out` is read as well as written: its contents are
+ * uploaded first, so elements the kernel does not own keep them.
+ * variant: "attn2" / "attn2_qw2" / "attn2_db" (attention2_kernel: fp32 MFMA; 64 or 128 queries per workgroup; double-buffered K / V),
+ * "attn6" / "attn6_qw2" (attention6_kernel on the bf16 x 6 arithmetic), "attn6h" / "attn6h_qw2" (on the fp16 x 3 arithmetic), or "auto":
+ * the kernel the engine picks for this sequence length under its options and environment.  resolved (optional): the index of the variant
+ * that ran in the list "auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
+ * "mha6_wide", "mha6h", "mha6h_wide", "hd_local".  ASX_ERR_INVALID for an unknown variant or one of the other family. */
+int asx_op_attention(asx_engine *e, const float *qkv_host, const float *gate_host, int64_t m, int32_t batch, int32_t t, int32_t fb,
+                     int32_t axis, int32_t heads, int32_t gate_ld, int32_t exact, const char *variant, float *out_host, int32_t *resolved);
+/* (ABI 7) One multi-head attention launch of the HTDemucs transformer (self and cross attention, nq != nk allowed) or of the LocalState
+ * of HDemucs / Demucs v3 (decay_host set; demucs.py:197-221) -- through the engine's own launch code, single-op test hook like asx_op_tdf.
+ * q [batch * nq, ldq], k [batch * nk, ldk], v [batch * nk, ldv], out [batch * nq, ldo]; head h owns columns [h * dh, h * dh + dh).
+ * Scores are q . k / sqrt(dh); with decay logits [batch * nq, ldd] (4 per head, nq == nk) every query gets the slope
+ * D = 1/4 sum_f (f + 1) sigmoid(logit_f), the score loses |key - query| * D and the diagonal is set to -100.  `out` is read as well as
+ * written (its padding columns beyond heads * dh keep what the caller put there).  variant: "mha" (mha_kernel: fp32 MFMA; dh 48 / 64,
+ * with decay 16 / 32 / 48 / 64 / 96), "mha_db" (its double-buffered build, dh 48), "mha6" / "mha6_wide" (mha6_kernel on the bf16 x 6
+ * arithmetic, 64 / 128 queries per workgroup; dh 48 / 64, no decay), "mha6h" / "mha6h_wide" (on the fp16 x 3 arithmetic), "hd_local"
+ * (hd_local_attn_kernel: decay, 4 heads of dh 4 / 8 / 12 / 24, ldo == heads * dh), or "auto": the engine's rule (the HTDemucs one
+ * without decay, the LocalState one with it).  All but "hd_local" need leading dimensions that are multiples of 4.  A variant that is
+ * not built for the arguments is ASX_ERR_INVALID, never a launch.  resolved: as in asx_op_attention. */
+int asx_op_mha(asx_engine *e, const float *q_host, int64_t ldq, const float *k_host, int64_t ldk, const float *v_host, int64_t ldv,
+               const float *decay_host, int64_t ldd, int32_t batch, int32_t nq, int32_t nk, int32_t heads, int32_t dh, int32_t exact,
+               const char *variant, float *out_host, int64_t ldo, int32_t *resolved);
 
 /* ---- options ------------------------------------------------------------ */
 /* "winograd": kernel of the 3x3 / pad-1 TFC convolutions.  3 (default; also ASX_WINOGRAD in the environment) = Winograd

@@ -436,6 +436,7 @@ double asx_net_flops(const asx_engine *e, int32_t batch) {
 
 }  // extern "C" (the engine headers below define templates)
 #include "engine_v3.h"
+#include "engine_attn.h"
 #include "engine_rof.h"
 #include "engine_ht.h"
 #include "engine_hd.h"
@@ -1095,6 +1096,108 @@ int asx_op_tdf_block(asx_engine *e, const float *x_host, int32_t B, int32_t c, i
   w3_drop(e, L0.w.p);
   w3_drop(e, L1.w.p);
   return rc;
+}
+
+// single attention launches through the engines' launch code (engine_attn.h); the output is uploaded first, so the caller sees exactly which
+// elements the kernel wrote
+int asx_op_attention(asx_engine *e, const float *qkv_host, const float *gate_host, int64_t M, int32_t B, int32_t T, int32_t Fb, int32_t axis,
+                     int32_t heads, int32_t gate_ld, int32_t exact, const char *variant, float *out_host, int32_t *resolved) {
+  REQUIRE(e && qkv_host && gate_host && out_host && B > 0 && T > 0 && Fb > 0 && (axis == 0 || axis == 1) && heads > 0 && gate_ld >= heads &&
+              M >= (int64_t)B * T * Fb,
+          "asx_op_attention: bad argument");
+  int v;
+  CHK(attn_variant_parse(variant, &v));
+  HIPCHK(hipSetDevice(e->device));
+  AttnArgs a{};
+  const int64_t nseq = rof_attn_geometry(a, B, T, Fb, axis == 0);
+  if (v == AV_AUTO) v = rof_attn_variant(e, a.len);
+  REQUIRE(v >= AV_ATTN2 && v <= AV_ATTN6H_QW2, "asx_op_attention: '%s' is not a Roformer attention variant", k_attn_variant_names[v]);
+  const int inner = heads * 64;
+  DevBuf dqkv, dgate, dout;
+  BufGuard g{{&dqkv, &dgate, &dout}};
+  CHK(to_dev(dqkv, qkv_host, (size_t)M * 3 * inner));
+  CHK(to_dev(dgate, gate_host, (size_t)M * gate_ld));
+  CHK(to_dev(dout, out_host, (size_t)M * inner));
+  a.qkv = dqkv.f();
+  a.gate = dgate.f();
+  a.out = dout.f();
+  a.heads = heads;
+  a.gate_ld = gate_ld;
+  a.scale = 1.0f / sqrtf(64.0f);
+  a.exact = exact ? 1 : 0;
+  CHK(rof_attn_launch(e, v, a, nseq, nullptr));
+  HIPCHK(hipGetLastError());
+  CHK(to_host(out_host, dout, (size_t)M * inner));
+  if (resolved) *resolved = v;
+  return ASX_OK;
+}
+
+int asx_op_mha(asx_engine *e, const float *q_host, int64_t ldq, const float *k_host, int64_t ldk, const float *v_host, int64_t ldv,
+               const float *decay_host, int64_t ldd, int32_t B, int32_t nq, int32_t nk, int32_t heads, int32_t dh, int32_t exact, const char *variant,
+               float *out_host, int64_t ldo, int32_t *resolved) {
+  REQUIRE(e && q_host && k_host && v_host && out_host && B > 0 && nq > 0 && nk > 0 && heads > 0 && dh > 0,
+          "asx_op_mha: bad argument");
+  const int64_t hd = (int64_t)heads * dh;
+  REQUIRE(ldq >= hd && ldk >= hd && ldv >= hd && ldo >= hd, "asx_op_mha: leading dimensions must be at least heads * dh = %lld", (long long)hd);
+  REQUIRE(!decay_host || (ldd >= 4 * (int64_t)heads && nq == nk), "asx_op_mha: decay logits need nq == nk and ldd >= 4 * heads");
+  int v;
+  CHK(attn_variant_parse(variant, &v));
+  HIPCHK(hipSetDevice(e->device));
+  MhaArgs a{};
+  a.ldq = ldq;
+  a.ldk = ldk;
+  a.ldv = ldv;
+  a.ldo = ldo;
+  a.ldd = ldd;
+  a.nq = nq;
+  a.nk = nk;
+  a.scale = 1.0f / sqrtf((float)dh);
+  a.exact = exact ? 1 : 0;
+  static const float dummy = 0.f;
+  a.decay = decay_host ? &dummy : nullptr;   // the rules and checks below look only at whether it is set
+  if (v == AV_AUTO) {
+    v = decay_host ? hd_attn_variant(a, dh) : ht_mha_variant(e, a, nq, dh);
+    REQUIRE(v != AV_AUTO, "asx_op_mha: no attention kernel is built for dh %d", dh);
+  }
+  if (v == AV_HD_LOCAL)
+    REQUIRE(decay_host && heads == 4 && hd_local_ok(dh) && ldo == hd,
+            "asx_op_mha: 'hd_local' takes decay logits, 4 heads, dh 4 / 8 / 12 / 24 and ldo == heads * dh");
+  else
+    REQUIRE(v >= AV_MHA && v <= AV_MHA6H_WIDE && mha_variant_ok(v, a, dh), "asx_op_mha: variant '%s' is not built for these arguments (dh %d)",
+            k_attn_variant_names[v], dh);
+  DevBuf dq, dk, dv, dd, dout;
+  BufGuard g{{&dq, &dk, &dv, &dd, &dout}};
+  CHK(to_dev(dout, out_host, (size_t)B * nq * ldo));
+  if (v == AV_HD_LOCAL) {
+    // the engine's LocalState layout: one matrix [B * T, 3 H + 16] of query | key | content | decay logits
+    const int H = (int)hd, ld = 3 * H + 16;
+    const int64_t rows = (int64_t)B * nq;
+    std::vector<float> qkvd((size_t)rows * ld, 0.f);
+    for (int64_t r = 0; r < rows; ++r) {
+      float *dst = qkvd.data() + r * ld;
+      memcpy(dst, q_host + r * ldq, H * 4);
+      memcpy(dst + H, k_host + r * ldk, H * 4);
+      memcpy(dst + 2 * H, v_host + r * ldv, H * 4);
+      memcpy(dst + 3 * H, decay_host + r * ldd, 16 * 4);
+    }
+    CHK(to_dev(dq, qkvd.data(), qkvd.size()));
+    hd_local_launch(dq.f(), ld, nq, H, dout.f(), B, nullptr);
+  } else {
+    CHK(to_dev(dq, q_host, (size_t)B * nq * ldq));
+    CHK(to_dev(dk, k_host, (size_t)B * nk * ldk));
+    CHK(to_dev(dv, v_host, (size_t)B * nk * ldv));
+    if (decay_host) CHK(to_dev(dd, decay_host, (size_t)B * nq * ldd));
+    a.q = dq.f();
+    a.k = dk.f();
+    a.v = dv.f();
+    a.out = dout.f();
+    a.decay = decay_host ? dd.f() : nullptr;
+    mha_launch(e, v, a, B, heads, dh, nullptr);
+  }
+  HIPCHK(hipGetLastError());
+  CHK(to_host(out_host, dout, (size_t)B * nq * ldo));
+  if (resolved) *resolved = v;
+  return ASX_OK;
 }
 
 // ---- MDXC / TFC-TDF v3 --------------------------------------------------------------

@@ -459,9 +459,15 @@ static int hd_blstm_joint(asx_engine *e, std::vector<HdGroup> &G, bool levelZ, s
   return ASX_OK;
 }
 
-template <int DH>
-static void hd_launch_attn(const float *qkvd, int ld, int T, int H, float *out, int B, hipStream_t s) {
-  hipLaunchKernelGGL((hd_local_attn_kernel<DH>), dim3((unsigned)((T + 63) / 64), 4, (unsigned)B), dim3(64), 0, s, qkvd, ld, T, H, out);
+// the LocalState kernel hd_local_state runs (the variant asx_op_mha calls "auto" with decay logits); AV_AUTO: none is built for dh
+static int hd_attn_variant(const MhaArgs &a, int dh) {
+  if (dh % 16 == 0 && (dh <= 64 || dh == 96)) {
+    // the flash attention of the v4 transformer (kernels_ht.h) with the per-query decay slope and the -100 diagonal
+    static const bool hd_mha_db = !(getenv("ASX_MHA_DB") && atoi(getenv("ASX_MHA_DB")) == 0);
+    const int v = (dh == 48 && hd_mha_db) ? AV_MHA_DB : AV_MHA;
+    return mha_variant_ok(v, a, dh) ? v : AV_AUTO;
+  }
+  return hd_local_ok(dh) ? AV_HD_LOCAL : AV_AUTO;
 }
 
 // LocalState in place on hbuf [B, T, H] (demucs.py:197-221)
@@ -470,48 +476,25 @@ static int hd_local_state(asx_engine *e, const HdAttn &A, float *hbuf, int B, in
   const int ld = 3 * H + 16, dh = H / 4;
   const int64_t M = (int64_t)B * T;
   CHK(ht_linear(e, A.qkvd, hbuf, H, M, b.qkvd, ld, 0, nullptr, 0, s));
-  int bad = 0;
+  MhaArgs a{};
+  a.q = b.qkvd;
+  a.k = b.qkvd + H;
+  a.v = b.qkvd + 2 * H;
+  a.out = b.att;
+  a.ldq = a.ldk = a.ldv = ld;
+  a.ldo = H;
+  a.nq = a.nk = T;
+  a.scale = 1.0f / sqrtf((float)dh);
+  static const int attn_exact = getenv("ASX_ATTN_EXACT") != nullptr;
+  a.exact = attn_exact;
+  a.decay = b.qkvd + 3 * H;
+  a.ldd = ld;
+  const int v = hd_attn_variant(a, dh);
+  REQUIRE(v != AV_AUTO, "LocalState head dim %d is not built (4, 8, 12, 24 and multiples of 16 up to 64, 96)", dh);
   CHK(timed(e, ASX_PROF_CONV1X1, 4.0 * B * 4.0 * (double)T * T * dh, 4.0 * (double)M * (ld + H), s, [&]() {
-    if (dh % 16 == 0 && (dh <= 64 || dh == 96)) {
-      // the flash attention of the v4 transformer (kernels_ht.h) with the per-query decay slope and the -100 diagonal
-      MhaArgs a{};
-      a.q = b.qkvd;
-      a.k = b.qkvd + H;
-      a.v = b.qkvd + 2 * H;
-      a.out = b.att;
-      a.ldq = a.ldk = a.ldv = ld;
-      a.ldo = H;
-      a.nq = a.nk = T;
-      a.scale = 1.0f / sqrtf((float)dh);
-      static const int attn_exact = getenv("ASX_ATTN_EXACT") != nullptr;
-      a.exact = attn_exact;
-      a.decay = b.qkvd + 3 * H;
-      a.ldd = ld;
-      a.nqt = (T + 63) / 64;
-      a.heads = 4;
-      const dim3 grid((unsigned)(a.nqt * 4 * B));   // 1-D, XCD-aware (kernels_ht.h)
-      static const bool hd_mha_db = !(getenv("ASX_MHA_DB") && atoi(getenv("ASX_MHA_DB")) == 0);
-      switch (dh / 16) {
-        case 1: hipLaunchKernelGGL((mha_kernel<1, true>), grid, dim3(256), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((mha_kernel<2, true>), grid, dim3(256), 0, s, a); break;
-        case 3:
-          if (hd_mha_db) hipLaunchKernelGGL((mha_kernel<3, true, true>), grid, dim3(256), 0, s, a);
-          else hipLaunchKernelGGL((mha_kernel<3, true>), grid, dim3(256), 0, s, a);
-          break;
-        case 4: hipLaunchKernelGGL((mha_kernel<4, true>), grid, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((mha_kernel<6, true>), grid, dim3(256), 0, s, a); break;
-      }
-      return;
-    }
-    switch (dh) {   // narrow heads: one thread per query
-      case 4: hd_launch_attn<4>(b.qkvd, ld, T, H, b.att, B, s); break;
-      case 8: hd_launch_attn<8>(b.qkvd, ld, T, H, b.att, B, s); break;
-      case 12: hd_launch_attn<12>(b.qkvd, ld, T, H, b.att, B, s); break;
-      case 24: hd_launch_attn<24>(b.qkvd, ld, T, H, b.att, B, s); break;
-      default: bad = 1;
-    }
+    if (v == AV_HD_LOCAL) hd_local_launch(b.qkvd, ld, T, H, b.att, B, s);   // narrow heads: one thread per query (engine_attn.h)
+    else mha_launch(e, v, a, B, 4, dh, s);
   }));
-  REQUIRE(!bad, "LocalState head dim %d is not built (4, 8, 12, 24 and multiples of 16 up to 64, 96)", dh);
   return ht_linear(e, A.proj, b.att, H, M, hbuf, H, 0, hbuf, H, s);
 }
 

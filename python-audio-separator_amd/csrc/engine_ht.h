@@ -736,6 +736,22 @@ static int ht_gn(asx_engine *e, float *x, int G1, int64_t R, int G2, int ld, int
   });
 }
 
+// the attention kernel ht_mha runs (the variant asx_op_mha calls "auto" without decay logits)
+static int ht_mha_variant(const asx_engine *e, const MhaArgs &a, int nq, int dh) {
+  // dh = 48: the single-buffered build runs FOUR workgroups per CU (118 registers, 26 KB of LDS): 55.0 -> 51.5 ms per song
+  // against the double-buffered, one-barrier build with three (ASX_MHA_DB=1: A/B) -- occupancy, not the barrier count
+  static const bool mha_db = getenv("ASX_MHA_DB") && atoi(getenv("ASX_MHA_DB")) != 0;
+  // bf16 x 6 form (kernels_ht.h: mha6_kernel) under the process-wide switch of the row GEMM; ASX_MHA6=0: A/B
+  static const bool mha6 = !(getenv("ASX_MHA6") && atoi(getenv("ASX_MHA6")) == 0);
+  if (mha6 && e->gemm_bf16x6 > 0 && a.decay == nullptr && (dh == 48 || dh == 64) && (a.ldq & 3) == 0 && (a.ldk & 3) == 0 &&
+      (a.ldv & 3) == 0 && (a.ldo & 3) == 0) {
+    const bool wide = nq > 128;                      // 128 queries per workgroup on long sequences
+    if (e->gemm_f16x3 > 0) return wide ? AV_MHA6H_WIDE : AV_MHA6H;   // fp16 x 3 arithmetic (kernels_ht.h: template parameter H)
+    return wide ? AV_MHA6_WIDE : AV_MHA6;
+  }
+  return (dh == 48 && mha_db) ? AV_MHA_DB : AV_MHA;
+}
+
 static int ht_mha(asx_engine *e, const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv, float *out,
                   int64_t ldo, int B, int nq, int nk, int heads, int dh, hipStream_t s) {
   MhaArgs a{};
@@ -754,44 +770,9 @@ static int ht_mha(asx_engine *e, const float *q, int64_t ldq, const float *k, co
   a.exact = attn_exact;
   const double flops = 4.0 * (double)B * heads * (double)nq * nk * dh;
   const double bytes = 4.0 * (double)B * heads * dh * (2.0 * nq + 2.0 * nk);
-  a.nqt = (nq + 63) / 64;
-  a.heads = heads;
-  const dim3 grid((unsigned)(a.nqt * heads * B));   // 1-D, XCD-aware (kernels_ht.h)
+  const int variant = ht_mha_variant(e, a, nq, dh);
   return timed(e, ASX_PROF_CONV1X1, flops, bytes, s, [&]() {   // profile class shared with the Roformer attention
-    // dh = 48: the single-buffered build runs FOUR workgroups per CU (118 registers, 26 KB of LDS): 55.0 -> 51.5 ms per song
-    // against the double-buffered, one-barrier build with three (ASX_MHA_DB=1: A/B) -- occupancy, not the barrier count
-    static const bool mha_db = getenv("ASX_MHA_DB") && atoi(getenv("ASX_MHA_DB")) != 0;
-    // bf16 x 6 form (kernels_ht.h: mha6_kernel) under the process-wide switch of the row GEMM; ASX_MHA6=0: A/B
-    static const bool mha6 = !(getenv("ASX_MHA6") && atoi(getenv("ASX_MHA6")) == 0);
-    if (mha6 && e->gemm_bf16x6 > 0 && a.decay == nullptr && (dh == 48 || dh == 64) && (ldq & 3) == 0 && (ldkv & 3) == 0 &&
-        (ldo & 3) == 0) {
-      MhaArgs a6 = a;
-      const bool wide = nq > 128;                      // 128 queries per workgroup on long sequences
-      a6.nqt = wide ? (nq + 127) / 128 : (nq + 63) / 64;
-      const dim3 grid6((unsigned)(a6.nqt * heads * B));
-      if (e->gemm_f16x3 > 0) {                         // fp16 x 3 arithmetic (kernels_ht.h: template parameter H)
-        if (dh == 48) {
-          if (wide) hipLaunchKernelGGL((mha6_kernel<3, 2, true>), grid6, dim3(256), 0, s, a6);
-          else hipLaunchKernelGGL((mha6_kernel<3, 1, true>), grid6, dim3(256), 0, s, a6);
-        } else {
-          if (wide) hipLaunchKernelGGL((mha6_kernel<4, 2, true>), grid6, dim3(256), 0, s, a6);
-          else hipLaunchKernelGGL((mha6_kernel<4, 1, true>), grid6, dim3(256), 0, s, a6);
-        }
-        g_attn6h_launches.fetch_add(1);
-      } else if (dh == 48) {
-        if (wide) hipLaunchKernelGGL((mha6_kernel<3, 2>), grid6, dim3(256), 0, s, a6);
-        else hipLaunchKernelGGL((mha6_kernel<3, 1>), grid6, dim3(256), 0, s, a6);
-      } else {
-        if (wide) hipLaunchKernelGGL((mha6_kernel<4, 2>), grid6, dim3(256), 0, s, a6);
-        else hipLaunchKernelGGL((mha6_kernel<4, 1>), grid6, dim3(256), 0, s, a6);
-      }
-      g_attn6_launches.fetch_add(1);
-      e->prof_nprod = e->gemm_f16x3 > 0 ? 3 : 6;
-      return;
-    }
-    if (dh == 48 && mha_db) hipLaunchKernelGGL((mha_kernel<3, false, true>), grid, dim3(256), 0, s, a);
-    else if (dh == 48) hipLaunchKernelGGL((mha_kernel<3>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((mha_kernel<4>), grid, dim3(256), 0, s, a);
+    mha_launch(e, variant, a, B, heads, dh, s);   // engine_attn.h
   });
 }
 

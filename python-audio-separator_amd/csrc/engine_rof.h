@@ -257,6 +257,23 @@ static int rof_rownorm(asx_engine *e, const float *x, int64_t lda, int d, float 
   });
 }
 
+// the attention kernel the engine runs on sequences of length len (the variant asx_op_attention calls "auto")
+static int rof_attn_variant(const asx_engine *e, int len) {
+  static const bool attn_db = getenv("ASX_ATTN_DB") && atoi(getenv("ASX_ATTN_DB")) != 0;   // A/B (default off until measured)
+  static const int qw = getenv("ASX_ATTN_QW") ? atoi(getenv("ASX_ATTN_QW")) : 1;   // 2: 128 queries per workgroup (measured slower: 357 vs 328 ms)
+  // bf16 x 6 form (kernels_rof.h: attention6_kernel) under the process-wide switch of the row GEMM; ASX_ATTN6=0: A/B
+  static const bool attn6 = !(getenv("ASX_ATTN6") && atoi(getenv("ASX_ATTN6")) == 0);
+  if (attn6 && e->gemm_bf16x6 > 0) {
+    static const int qw6 = getenv("ASX_ATTN6_QW") ? atoi(getenv("ASX_ATTN6_QW")) : 2;   // 128 queries per workgroup on long sequences
+    const bool h3 = e->gemm_f16x3 > 0;           // fp16 x 3 arithmetic (kernels_rof.h: template parameter H)
+    if (qw6 >= 2 && len > 128) return h3 ? AV_ATTN6H_QW2 : AV_ATTN6_QW2;
+    return h3 ? AV_ATTN6H : AV_ATTN6;
+  }
+  if (qw >= 2 && len > 64) return AV_ATTN2_QW2;
+  if (attn_db && len > 128) return AV_ATTN2_DB;   // several key tiles: one barrier per tile (double-buffered K / V)
+  return AV_ATTN2;
+}
+
 // one Transformer (bs_roformer.py:136-160, norm_output = False) over the token matrix TOK [M, D]
 static int rof_transformer(asx_engine *e, std::vector<RofLayer> &layers, bool time_axis, int B, hipStream_t s,
                            const DevBuf *out_norm = nullptr) {
@@ -334,69 +351,17 @@ static int rof_transformer(asx_engine *e, std::vector<RofLayer> &layers, bool ti
       aa.scale = 1.0f / sqrtf((float)c.dim_head);
       static const int attn_exact = getenv("ASX_ATTN_EXACT") != nullptr;
       aa.exact = attn_exact;
-      int64_t nseq;
-      if (time_axis) {
-        aa.len = T;
-        aa.row_stride = Fb;
-        aa.inner_cnt = Fb;
-        aa.outer_stride = (int64_t)T * Fb;
-        aa.inner_stride = 1;
-        nseq = (int64_t)B * Fb;
-      } else {
-        aa.len = Fb;
-        aa.row_stride = 1;
-        aa.inner_cnt = 1;
-        aa.outer_stride = Fb;
-        aa.inner_stride = 0;
-        nseq = (int64_t)B * T;
-      }
-      const int qtiles = (aa.len + 63) / 64;
+      const int64_t nseq = rof_attn_geometry(aa, B, T, Fb, time_axis);
       const double fl = 4.0 * (double)nseq * H * (double)aa.len * aa.len * c.dim_head;
       CHK(timed(e, ASX_PROF_CONV1X1, fl, 4.0 * M * 4 * inner, s, [&]() {
 #ifdef ASX_EXPERIMENTAL_KERNELS
         static const bool v1 = getenv("ASX_ATTN_V1") && atoi(getenv("ASX_ATTN_V1")) != 0;   // the 4-byte-fragment kernel (A/B)
-#else
-        constexpr bool v1 = false;
-#endif
-        static const bool attn_db = getenv("ASX_ATTN_DB") && atoi(getenv("ASX_ATTN_DB")) != 0;   // A/B (default off until measured)
-        static const int qw = getenv("ASX_ATTN_QW") ? atoi(getenv("ASX_ATTN_QW")) : 1;   // 2: 128 queries per workgroup (measured slower: 357 vs 328 ms)
-        // bf16 x 6 form (kernels_rof.h: attention6_kernel) under the process-wide switch of the row GEMM; ASX_ATTN6=0: A/B
-        static const bool attn6 = !(getenv("ASX_ATTN6") && atoi(getenv("ASX_ATTN6")) == 0);
-        if (attn6 && e->gemm_bf16x6 > 0 && !v1) {
-          AttnArgs a2 = aa;
-          static const int qw6 = getenv("ASX_ATTN6_QW") ? atoi(getenv("ASX_ATTN6_QW")) : 2;   // 128 queries per workgroup on long sequences
-          const bool h3 = e->gemm_f16x3 > 0;           // fp16 x 3 arithmetic (kernels_rof.h: template parameter H)
-          if (qw6 >= 2 && aa.len > 128) {
-            a2.nqt = (aa.len + 127) / 128;
-            const dim3 g2((unsigned)((int64_t)a2.nqt * H * nseq));
-            if (h3) hipLaunchKernelGGL((attention6_kernel<2, true>), g2, dim3(256), 0, s, a2);
-            else hipLaunchKernelGGL(attention6_kernel<2>, g2, dim3(256), 0, s, a2);
-          } else {
-            a2.nqt = qtiles;
-            const dim3 g1((unsigned)((int64_t)qtiles * H * nseq));
-            if (h3) hipLaunchKernelGGL((attention6_kernel<1, true>), g1, dim3(256), 0, s, a2);
-            else hipLaunchKernelGGL(attention6_kernel<1>, g1, dim3(256), 0, s, a2);
-          }
-          g_attn6_launches.fetch_add(1);
-          if (h3) g_attn6h_launches.fetch_add(1);
-          e->prof_nprod = h3 ? 3 : 6;
-        } else
-#ifdef ASX_EXPERIMENTAL_KERNELS
-        if (v1) hipLaunchKernelGGL(attention_kernel, dim3(qtiles, H, (unsigned)nseq), dim3(256), 0, s, aa);
-        else
-#endif
-        if (qw >= 2 && aa.len > 64) {
-          AttnArgs a2 = aa;
-          a2.nqt = (aa.len + 127) / 128;
-          hipLaunchKernelGGL(attention2_kernel<2>, dim3((unsigned)(a2.nqt * H * nseq)), dim3(256), 0, s, a2);
-        } else {
-          AttnArgs a2 = aa;
-          a2.nqt = qtiles;
-          const dim3 grid((unsigned)((int64_t)qtiles * H * nseq));   // 1-D, XCD-aware (kernels_rof.h)
-          if (attn_db && aa.len > 128)   // several key tiles: one barrier per tile (double-buffered K / V)
-            hipLaunchKernelGGL((attention2_kernel<1, true>), grid, dim3(256), 0, s, a2);
-          else hipLaunchKernelGGL(attention2_kernel<1>, grid, dim3(256), 0, s, a2);
+        if (v1) {
+          hipLaunchKernelGGL(attention_kernel, dim3((aa.len + 63) / 64, H, (unsigned)nseq), dim3(256), 0, s, aa);
+          return;
         }
+#endif
+        rof_attn_launch(e, rof_attn_variant(e, aa.len), aa, nseq, s);   // engine_attn.h
       }));
     }
     CHK(rof_gemm(e, L.attn.out, n.ATT.f(), inner, Mg, n.TOK.f(), D, 0, n.TOK.f(), D, s));   // + x (in place: each

@@ -274,7 +274,11 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_ht_standardize_dev", "asx_ht_bag_accumulate_dev", "asx_ht_bag_finish_dev", "asx_ensemble",
            "asx_ensemble_dev", "asx_invert_stem", "asx_normalize", "asx_normalize_dev", "asx_residual_dev",
            "asx_profile_launches", "asx_debug_trace", "asx_resample_sinc", "asx_resample_sinc_dev", "asx_counter",
-           "asx_set_stft_window", "asx_op_tdf_block"]
+           "asx_set_stft_window", "asx_op_tdf_block", "asx_op_attention", "asx_op_mha"]
+
+# the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
+ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
+                 "mha6_wide", "mha6h", "mha6h_wide", "hd_local")
 
 
 class _LaunchRec(C.Structure):     # struct asx_launch_rec
@@ -327,6 +331,9 @@ def load_library():
     lib.asx_op_conv.argtypes = [vp, C.c_char_p, _FP, i32, i32, i32, i32, _FP, _FP, i32, _FP, i32, _FP]
     lib.asx_op_tdf.argtypes = [vp, _FP, i32, i32, i32, i32, _FP, _FP, i32, _FP, _FP, _FP, _FP]
     lib.asx_op_tdf_block.argtypes = [vp, _FP, i32, i32, i32, i32, _FP, _FP, _FP, i32, _FP, _FP, _FP, _FP, _FP]
+    lib.asx_op_attention.argtypes = [vp, _FP, _FP, i64, i32, i32, i32, i32, i32, i32, i32, C.c_char_p, _FP, C.POINTER(i32)]
+    lib.asx_op_mha.argtypes = [vp, _FP, i64, _FP, i64, _FP, i64, _FP, i64, i32, i32, i32, i32, i32, i32, C.c_char_p, _FP, i64,
+                               C.POINTER(i32)]
     lib.asx_v3_begin.argtypes = [vp, C.POINTER(_V3Cfg)]
     lib.asx_v3_commit.argtypes = [vp]
     lib.asx_v3_flops.argtypes = [vp, i32]
@@ -1116,6 +1123,44 @@ class Engine:
         self._check(self._lib.asx_op_tdf_block(self._h, _ptr(x), B, c, t, f, _ptr(w0), _ptr(scale0), _ptr(shift0), n8, _ptr(w1),
                                                _ptr(scale1), _ptr(shift1), _ptr(y), _optptr(h)))
         return (y, h) if return_hidden else y
+
+    def op_attention(self, qkv, gate, B, T, Fb, axis="time", exact=False, variant="auto", out=None):
+        """One Roformer attention launch (asx_op_attention): qkv [M, 3 * heads * 64], gate [M, gate_ld] (gate_ld >= heads), tokens
+        [B, T, Fb] along `axis` ("time" or "freq").  `out` [M, heads * 64] is uploaded before the launch (elements the kernel does not
+        own keep their contents); default NaN.  Returns (out, name of the variant that ran)."""
+        qkv, gate = _f32(qkv), _f32(gate)
+        M, w = qkv.shape
+        if w % 192 != 0 or gate.ndim != 2 or gate.shape[0] != M:
+            raise AsxError(f"op_attention: qkv {qkv.shape} / gate {gate.shape} are not [M, 3 * heads * 64] / [M, gate_ld]")
+        heads = w // 192
+        if axis not in ("time", "freq"):
+            raise AsxError(f"op_attention: axis must be 'time' or 'freq', got {axis!r}")
+        out = np.full((M, heads * 64), np.nan, np.float32) if out is None else np.array(out, np.float32, order="C")
+        if out.shape != (M, heads * 64):
+            raise AsxError(f"op_attention: out {out.shape} is not [{M}, {heads * 64}]")
+        res = C.c_int32(-1)
+        self._check(self._lib.asx_op_attention(self._h, _ptr(qkv), _ptr(gate), M, B, T, Fb, 0 if axis == "time" else 1, heads,
+                                               gate.shape[1], int(exact), variant.encode(), _ptr(out), C.byref(res)))
+        return out, ATTN_VARIANTS[res.value]
+
+    def op_mha(self, q, k, v, B, nq, nk, heads, dh, decay=None, exact=False, variant="auto", out=None):
+        """One multi-head attention launch (asx_op_mha): q [B * nq, ldq], k / v [B * nk, ld], optional LocalState decay logits
+        [B * nq, ldd]; head h owns columns [h * dh, (h + 1) * dh).  `out` [B * nq, ldo] (ldo >= heads * dh) is uploaded before the
+        launch; default NaN of width heads * dh.  Returns (out, name of the variant that ran)."""
+        q, k, v = _f32(q), _f32(k), _f32(v)
+        if q.shape[0] != B * nq or k.shape[0] != B * nk or v.shape[0] != B * nk:
+            raise AsxError(f"op_mha: q {q.shape} / k {k.shape} / v {v.shape} do not hold {B} x {nq} queries and {B} x {nk} keys")
+        decay = _f32(decay) if decay is not None else None
+        if decay is not None and decay.shape[0] != B * nq:
+            raise AsxError(f"op_mha: decay {decay.shape} does not have {B * nq} rows")
+        out = np.full((B * nq, heads * dh), np.nan, np.float32) if out is None else np.array(out, np.float32, order="C")
+        if out.ndim != 2 or out.shape[0] != B * nq:
+            raise AsxError(f"op_mha: out {out.shape} does not have {B * nq} rows")
+        res = C.c_int32(-1)
+        self._check(self._lib.asx_op_mha(self._h, _ptr(q), q.shape[1], _ptr(k), k.shape[1], _ptr(v), v.shape[1], _optptr(decay),
+                                         decay.shape[1] if decay is not None else 0, B, nq, nk, heads, dh, int(exact),
+                                         variant.encode(), _ptr(out), out.shape[1], C.byref(res)))
+        return out, ATTN_VARIANTS[res.value]
 
     # -- profiling --------------------------------------------------------------
     def profile_enable(self, on: bool = True):
