@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the demix hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode files|chunks] [--songs-per-rank S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode files|chunks] [--songs-per-rank S] [--full]
 
 A "step" = one pass of the hot path (asx_demix_dev: chunking -> STFT -> ConvTDFNet -> iSTFT -> Hann fold ->
 result/divider) over 4-minute 44.1 kHz stereo songs that are already resident in HBM, on the UVR-MDX-NET-Inst_HQ_3
@@ -22,6 +22,13 @@ which case WORLD_SIZE must equal N -- anything else is an error, never a silent 
 
 ``--dry-gloo`` replaces the GPU work by a copy and RCCL by gloo so that the launcher / rendezvous / collective plumbing
 can be exercised on a CPU-only box (tests/test_bench_launcher.py); its line says ``"dry": true`` and carries no rate.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, ``--dump-outputs`` and the line.  ``--full`` adds,
+after the timed region, everything else the line can carry: the fp32-exact A/B (``arithmetic_ab``), the event-timed gather / fold
+(``rccl.gather_ms`` ...), the profiled pass with its roofline, per-level table, live PMC traffic and direct-kernel leg (``roofline``,
+``kernel_ms``, ``stage_roofline``), the CPU oracle baseline and parity (``cpu_baseline``), the plugin's file-level rate
+(``file_level``) and the sibling nets (``siblings``).  ``--cpu-seconds``, ``--siblings``, ``--file-level``, ``--traffic`` and
+``--no-arith-ab`` tune what ``--full`` runs; without it they have no effect.  The line's ``full`` field says which kind of run it is.
 
 Prints ONE JSON line on rank 0 (field notes in DESIGN.md 4).
 """
@@ -125,15 +132,18 @@ def parse_args(argv=None):
     ap.add_argument("--songs-per-rank", type=int, default=1)
     ap.add_argument("--max-batch", type=int, default=0)
     ap.add_argument("--seconds", type=float, default=SONG_SECONDS)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="length of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--siblings", type=int, default=1, help="1: append short htdemucs / BS-Roformer / VR / hdemucs lines (N = 1 only)")
-    ap.add_argument("--file-level", type=int, default=1, help="1: time Separator-level separate(wav) -> stem files after the timed region (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the A/Bs, the profiled roofline pass, the CPU baseline, the file-level and the "
+                         "sibling measurements (off: the run does only what the headline needs)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: length of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--siblings", type=int, default=1, help="--full, 1: append short htdemucs / BS-Roformer / VR / hdemucs lines (N = 1 only)")
+    ap.add_argument("--file-level", type=int, default=1, help="--full, 1: time Separator-level separate(wav) -> stem files after the timed region (N = 1 only)")
     ap.add_argument("--no-graph", action="store_true", help="--mode chunks: launch the rank's chunk range eagerly instead of replaying a captured hipGraph")
-    ap.add_argument("--no-arith-ab", action="store_true", help="skip the fp32-exact arithmetic A/B after the timed region (N = 1 only)")
+    ap.add_argument("--no-arith-ab", action="store_true", help="--full: skip the fp32-exact arithmetic A/B after the timed region (N = 1 only)")
     ap.add_argument("--no-overlap", action="store_true", help="blocking gather (A/B of the gather / compute overlap)")
     ap.add_argument("--config5", action="store_true", help="BASELINE config 5 preset: --mode files --songs-per-rank 8 (64 songs on 8 GPUs)")
     ap.add_argument("--traffic", choices=("live", "stored"), default="live",
-                    help="roofline.traffic: 'live' = two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of a one-song child of this "
+                    help="--full, roofline.traffic: 'live' = two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of a one-song child of this "
                          "script, inside this run (N = 1 only; falls back to 'stored' when rocprofv3 is missing or fails); "
                          "'stored' = the ratio kept under profiles/")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
@@ -409,7 +419,7 @@ def main():
     # ---- the same K steps on the fp32-EXACT arithmetic (gemm_f16x3 = 0: every split-operand kernel multiplies exact three-way bf16 splits, six
     # products per multiply-add; conv3h_kernel's level falls back to conv_wino3_kernel), outside the timed region: both headlines are driver-timed
     arithmetic_ab = None
-    if world == 1 and eng.option("gemm_bf16x6") > 0 and eng.option("gemm_f16x3") > 0 and not args.no_arith_ab:
+    if args.full and world == 1 and eng.option("gemm_bf16x6") > 0 and eng.option("gemm_f16x3") > 0 and not args.no_arith_ab:
         eng.set_option("gemm_f16x3", 0)
         for k in range(2):
             step(k)
@@ -432,7 +442,7 @@ def main():
     comm = {"gather_bytes_per_step": 0, "gather_ms": None, "fold_ms": None}
     if args.mode == "files":
         comm["gather_bytes_per_step"] = pipe.gather_bytes_per_step
-        if use_dist:
+        if use_dist and args.full:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
             dist.barrier()
             torch.cuda.synchronize()
@@ -444,13 +454,14 @@ def main():
             comm["gather_ms"] = round(ev[0].elapsed_time(ev[1]) / 3, 3)
             comm["gather_ms_note"] = "one blocking dist.gather of a step's stems, hipEvents on the current stream, mean of 3; in the timed loop it overlaps the next step"
     else:
-        shard_ws.timed = True
-        sharded_demix(adapter, mix, workspace=shard_ws)
-        shard_ws.timed = False
-        if shard_ws.timings:
-            comm["gather_ms"] = round(shard_ws.timings["gather_ms"], 3)
-            comm["fold_ms"] = round(shard_ws.timings["fold_ms"], 3)
-            comm["compute_ms"] = round(shard_ws.timings["compute_ms"], 3)
+        if args.full:
+            shard_ws.timed = True
+            sharded_demix(adapter, mix, workspace=shard_ws)
+            shard_ws.timed = False
+            if shard_ws.timings:
+                comm["gather_ms"] = round(shard_ws.timings["gather_ms"], 3)
+                comm["fold_ms"] = round(shard_ws.timings["fold_ms"], 3)
+                comm["compute_ms"] = round(shard_ws.timings["compute_ms"], 3)
         comm["graph"] = {"enabled": shard_ws.graph, "replays": shard_ws.graph_replays, "error": shard_ws.graph_error}
         cs = plan["chunk_size"]
         # local fold: (world - 1) seam chunks point-to-point + the folded slabs of the other ranks to rank 0
@@ -461,7 +472,7 @@ def main():
     # ---- roofline of the dominant kernel (3x3 TFC conv, MFMA bound), HIP events on the launch stream ----
     roofline = None
     prof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         m0 = mixes[0] if args.mode == "files" else mix
         o0 = torch.empty_like(m0)
         eng.profile_enable(True)
@@ -559,7 +570,7 @@ def main():
     # ---- CPU baseline + on-the-fly parity of the same workload (rank 0, N = 1 only) ----
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         ref, cmix, cpu = cpu_baseline(args.cpu_seconds, seed=0)
         g = eng.demix(cmix)
         parity = float(np.sqrt(np.mean((g.astype(np.float64) - ref) ** 2)) / np.sqrt(np.mean(ref.astype(np.float64) ** 2)))
@@ -572,7 +583,7 @@ def main():
         res = {
             "metric": METRIC, "value": round(value, 2), "unit": "audio-s/wall-s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "full": args.full,
             "dtype": ("f32 (I/O and accumulators; matrix products on the 16-bit pipe from block-scaled two-part fp16 operands, 22-bit products -- see arithmetic; "
                       "fp32-exact setting timed in arithmetic_ab)" if (eng.option("gemm_bf16x6") > 0 and eng.option("gemm_f16x3") > 0) else
                       "f32 (I/O and accumulators; matrix products from exactly split bf16 operands or fp32 MFMA -- see arithmetic)"),
@@ -662,14 +673,14 @@ def main():
                     stages[k] = {"bound": "hbm", "achieved": round(gb, 1), "unit": "GB/s", "frac": round(gb / 8000.0, 4),
                                  "frac_vs_copy": round(gb / 6290.0, 4)}
             res["stage_roofline"] = stages
-        if world == 1 and (args.siblings or args.file_level):
+        if args.full and world == 1 and (args.siblings or args.file_level):
             eng.close()
-        if world == 1 and args.file_level:
+        if args.full and world == 1 and args.file_level:
             try:
                 res["file_level"] = file_level_line(args, sd)
             except Exception as e:                  # never take the headline line down
                 res["file_level"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and args.siblings:
+        if args.full and world == 1 and args.siblings:
             res["siblings"] = sibling_lines(args)
         emit(res)
     if use_dist:
