@@ -578,22 +578,27 @@ int asx_op_mha(asx_engine *e, const float *q_host, int64_t ldq, const float *k_h
                const char *variant, float *out_host, int64_t ldo, int32_t *resolved);
 
 /* ---- options ------------------------------------------------------------ */
-/* "winograd": kernel of the 3x3 / pad-1 TFC convolutions.  3 (default; also ASX_WINOGRAD in the environment) = Winograd
+/* Engine options.  Each engine takes its defaults from the environment variable named beside the option when it is created (values go
+ * through the same normalisation as asx_set_option); asx_set_option changes one for this engine only.
+ * "winograd": kernel of the 3x3 / pad-1 TFC convolutions.  3 (default; also ASX_WINOGRAD in the environment) = Winograd
  * F(2x2,3x3) in fp32 (2.25x fewer multiply-accumulates; results differ from the direct kernel by a few float32 ulps per
  * layer, whole-song deviation from the CPU oracle stays below 1e-5 relative RMS, profiles/r03_fullsong_parity.json);
- * 0 = the direct MFMA kernel; 1 / 2 = earlier Winograd generations kept for A/B measurements.
- * "winograd_stationary": 1 (also ASX_WINOS) = layers with at most 96 input channels run the weight-stationary form of the same
+ * 0 = the direct MFMA kernel; 1 / 2 = earlier Winograd generations kept for A/B measurements, in experimental builds only (the default
+ * library refuses them from asx_set_option, and reads any positive ASX_WINOGRAD as 3).
+ * "winograd_stationary" (experimental builds only -- the default library accepts 0 and refuses 1): 1 (also ASX_WINOS) = layers with at most 96 input channels run the weight-stationary form of the same
  * transform (csrc/kernels_winos.h: the transformed weights stay in registers, positions split over eight waves) when "winograd"
  * is 3; 0 (default: the stationary form measured slower, profiles/NOTES.md) = conv_wino3_kernel for every layer.
  * "winograd_bf16x6" (ABI 6; also ASX_WINO6): minimum input-channel count from which a 3x3 TFC convolution runs Winograd F(2x2,3x3) on the
  * bf16 matrix pipe (conv_wino6_kernel, csrc/kernels_wino6.h: the sixteen transform-domain GEMMs as six bf16 MFMA products on exactly
  * split operands -- the arithmetic of "gemm_bf16x6", which must be on) instead of conv_wino3_kernel; needs "winograd" = 3.  Default 144
  * (levels 2 .. 5 of the HQ_3 net: measured 1.08-1.24x faster there, equal at 96 channels, slower at 48); 0 = never.
- * "conv_direct_f16x3" (ABI 7; also ASX_CONV3H): 1 (default) = a 3x3 TFC convolution of 48 -> 48 channels on planes whose width is a multiple of
- * 32 (level 0 of the HQ_3 geometry, the widest planes of the net) runs conv3h_kernel (csrc/kernels_conv3h.h): a DIRECT implicit GEMM on the fp16
+ * "conv_direct_f16x3" (ABI 7; also ASX_CONV3H): a channel-count threshold.  N > 0 (default 144) = a 3x3 TFC convolution of 48n -> 48n channels
+ * with 48n <= N (at most 144: the weight image is packed up to 144 channels) on planes whose width is a multiple of 32 (levels 0, 1 and 2 of
+ * the HQ_3 geometry) runs conv3h_kernel (csrc/kernels_conv3h.h): a DIRECT implicit GEMM on the fp16
  * matrix pipe with the arithmetic of "gemm_f16x3" (which must be on, as "gemm_bf16x6" and "winograd" = 3) -- the two-part weight image stays in
  * LDS for the whole launch, producer waves fetch four input rows per step into a ring walked down T and split them under one running
- * power-of-two exponent per walk, consumer waves multiply; 5.3-5.8 ms per launch of 55 chunks against 8.5-8.9 on conv_wino3_kernel.  0 = conv_wino3_kernel.
+ * power-of-two exponent per walk, consumer waves multiply; n x n launches over 48-channel slices; 5.3-5.8 ms per launch of 55 chunks against
+ * 8.5-8.9 on conv_wino3_kernel at 48 channels.  0 = never (conv_wino3_kernel / conv_wino6_kernel).
  * "conv_down_bf16x6" / "conv_up_bf16x6" (ABI 7; also ASX_DOWN6 / ASX_UP6): 1 (default) = the 2 x 2 / stride-2 convolutions between the levels
  * (mdxnet.py:66-72) and the transposed ones of the decoder with their `x *= skip` (mdxnet.py:80-86, 113) run conv_down6_kernel / conv_up6_kernel
  * (csrc/kernels_updown6.h) while "gemm_bf16x6" is on: the arithmetic of that option -- both fp32 operands split EXACTLY into three bf16 parts, six
@@ -629,6 +634,9 @@ int asx_op_mha(asx_engine *e, const float *q_host, int64_t ldq, const float *k_h
  * in a GEMM row makes that row's accumulators NaN under 1 (h = Inf, v - h = NaN) and +-Inf / NaN under 0; the ReLU epilogues then
  * return 0 for NaN (maxNum).  No other row is affected (tests/test_gpu_parity.py::test_rowgemm_bf16x6_nonfinite_rows). */
 int asx_set_option(asx_engine *e, const char *key, int32_t value);
+/* The value an option of this engine has now, after normalisation ("gemm_*" / "conv_*_bf16x6": 0 / 1; the others: >= 0) -- the
+ * environment's default or the last asx_set_option.  Unknown key: ASX_ERR_INVALID.  (ABI 7, additive) */
+int asx_get_option(const asx_engine *e, const char *key, int32_t *value);
 
 /* ---- profiling ---------------------------------------------------------- */
 int asx_profile_enable(asx_engine *e, int32_t on); /* clears the counters */

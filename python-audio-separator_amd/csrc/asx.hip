@@ -18,10 +18,26 @@
 #include <map>
 #include <string>
 #include <mutex>
-#include <set>
 #include <vector>
 
 #include "../../include/asx.h"
+#include "knobs.h"
+
+// Raise a kernel's dynamic-LDS limit to `bytes` unless an earlier call granted as much.  Engines are driven from several host threads
+// (one per bag member / rank): one lock covers the record and the attribute call, so no launch can overtake the grant it needs.
+static void grant_lds(const void *kernel, int bytes) {
+  static std::mutex mu;
+  static std::map<const void *, int> granted;
+  std::lock_guard<std::mutex> lock(mu);
+  int &g = granted[kernel];
+  if (bytes > g) {
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    g = bytes;
+  }
+}
+template <class K>
+static void grant_lds(K *kernel, int bytes) { grant_lds(reinterpret_cast<const void *>(kernel), bytes); }
+
 #include "kernels_fft.h"
 #include "kernels_fft3.h"
 #include "kernels_net.h"
@@ -34,9 +50,6 @@
 #include "kernels_wino6.h"
 #include "kernels_conv3h.h"
 #include "kernels_updown6.h"
-#ifndef ASX_TDF2_DEFAULT
-#define ASX_TDF2_DEFAULT 1
-#endif
 #include "kernels_rof.h"
 #include "kernels_ht.h"
 #include "kernels_halo.h"
@@ -48,6 +61,46 @@ using namespace asx;
 
 #include "engine_core.h"
 #include "engine_mdx.h"
+
+// ----------------------------------------------------------------------------
+// engine options (asx_set_option / asx_get_option)
+// ----------------------------------------------------------------------------
+static int opt_nonneg(int32_t v) { return v < 0 ? 0 : (int)v; }
+static int opt_onoff(int32_t v) { return v > 0 ? 1 : 0; }
+
+// One entry per option: where the engine keeps it, its default from the environment (knobs.h; asx_engine_create puts it through the same
+// normaliser as asx_set_option) and, for an option that selects kernels only an experimental build carries, the refusal of the default
+// build for positive values other than `shipped` (a printf format of the refused value).
+static const struct EngineOption {
+  const char *key;
+  int asx_engine::*field;
+  int EngineKnobs::*knob;
+  int (*norm)(int32_t);
+  const char *refusal = nullptr;
+  int shipped = 0;
+} kOptions[] = {
+    {"winograd", &asx_engine::winograd, &EngineKnobs::winograd, opt_nonneg,
+     "asx_set_option: winograd = %d names a superseded kernel generation that only an experimental build carries "
+     "(python build.py --experimental); this library has 0 (direct kernel) and 3 (the default)", 3},
+    {"winograd_stationary", &asx_engine::winos, &EngineKnobs::winos, opt_nonneg,
+     "asx_set_option: the weight-stationary Winograd kernel (measured slower) is in experimental builds only (python build.py --experimental)"},
+    {"winograd_bf16x6", &asx_engine::wino6, &EngineKnobs::wino6, opt_nonneg},
+    {"gemm_bf16x6", &asx_engine::gemm_bf16x6, &EngineKnobs::gemm_bf16x6, opt_onoff},   // this engine only (round 5; it was process-wide before)
+    {"gemm_f16x3", &asx_engine::gemm_f16x3, &EngineKnobs::gemm_f16x3, opt_onoff},
+    {"conv_direct_f16x3", &asx_engine::conv3h, &EngineKnobs::conv3h, opt_nonneg},
+    {"conv_down_bf16x6", &asx_engine::down6, &EngineKnobs::down6, opt_onoff},
+    {"conv_up_bf16x6", &asx_engine::up6, &EngineKnobs::up6, opt_onoff},
+    {"gemm_pair_images", &asx_engine::pair_images, &EngineKnobs::pair_images, opt_onoff,
+     "asx_set_option: gemm_pair_images = 1 needs an experimental build (python build.py --experimental): the pair-image reader measured no "
+     "faster in the nets and is not in the default library"},
+};
+
+static const EngineOption *find_option(const char *fn, const char *key) {
+  for (const EngineOption &o : kOptions)
+    if (!strcmp(key, o.key)) return &o;
+  set_err("%s: unknown option '%s'", fn, key);
+  return nullptr;
+}
 
 // ----------------------------------------------------------------------------
 // C ABI
@@ -80,7 +133,10 @@ int asx_engine_create(int device, const asx_mdx_config *cfg, asx_engine **out) {
   HIPCHK(hipGetDeviceCount(&ndev));
   REQUIRE(device >= 0 && device < ndev, "device %d not available (%d visible)", device, ndev);
   HIPCHK(hipSetDevice(device));
+  (void)knobs();                                       // the process-wide knobs: read once, here at the first engine
+  const EngineKnobs opts;                              // this engine's option defaults: read again for every engine
   asx_engine *e = new asx_engine();
+  for (const EngineOption &o : kOptions) e->*o.field = o.norm(opts.*o.knob);
   e->device = device;
   e->cfg = *cfg;
   e->plan = plan;
@@ -104,7 +160,7 @@ int asx_engine_create(int device, const asx_mdx_config *cfg, asx_engine **out) {
       rc = ASX_ERR_HIP;
     }
   }
-  if (rc == ASX_OK && cfg->n_fft == f3::NFFT && cfg->hop_length == f3::HOP && !(getenv("ASX_FFT3") && atoi(getenv("ASX_FFT3")) == 0)) {
+  if (rc == ASX_OK && cfg->n_fft == f3::NFFT && cfg->hop_length == f3::HOP && opts.fft3) {
     std::vector<float> t3((size_t)(16 * 12 + 16 * f3::NB) * 2);
     for (int r = 0; r < 16; ++r)
       for (int k = 0; k < 12; ++k) {
@@ -138,7 +194,7 @@ int asx_engine_create(int device, const asx_mdx_config *cfg, asx_engine **out) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&f3::stft3p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   f3::STFT3P_LDS_BYTES);
         e->fft3 = true;
-        e->fft3p = !(getenv("ASX_FFT3P") && atoi(getenv("ASX_FFT3P")) == 0);
+        e->fft3p = opts.fft3p;
         if ((rc = e->d_hann3.ensure((size_t)C * 8)) == ASX_OK) {
           hipLaunchKernelGGL(f3::hann3_table_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, nullptr, C,
                              reinterpret_cast<double *>(e->d_hann3.p));
@@ -563,7 +619,7 @@ int asx_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t N, float
   const int win = windowed_mode(e, flags) ? 1 : 0;
   const double bytes = 4.0 * ((double)p.n_chunks * 2 * p.chunk_size + 2.0 * N);
   const double *hann = (e->fft3 && e->d_hann3.p) ? reinterpret_cast<const double *>(e->d_hann3.p) : nullptr;
-  static const bool fin4 = !(getenv("ASX_FINALIZE4") && atoi(getenv("ASX_FINALIZE4")) == 0);
+  const bool fin4 = knobs().finalize4;
   // vector path: the divider (input-independent) comes from a table built once per plan; needs 4-sample alignment of the
   // chunk geometry and 16-byte aligned buffers
   if (fin4 && p.chunk_size % 4 == 0 && p.step % 4 == 0 && p.trim % 4 == 0 && N % 4 == 0 && p.chunk_size + (int64_t)p.trim >= 0 &&
@@ -2238,57 +2294,21 @@ int asx_ht_bag_finish_dev(asx_engine *e, const float *est_dev, const float *tota
 
 int asx_set_option(asx_engine *e, const char *key, int32_t value) {
   REQUIRE(e && key, "asx_set_option: null argument");
-  if (!strcmp(key, "winograd")) {
+  const EngineOption *o = find_option("asx_set_option", key);
+  if (!o) return ASX_ERR_INVALID;
 #ifndef ASX_EXPERIMENTAL_KERNELS
-    REQUIRE(value <= 0 || value == 3, "asx_set_option: winograd = %d names a superseded kernel generation that only an experimental build carries "
-            "(python build.py --experimental); this library has 0 (direct kernel) and 3 (the default)", (int)value);
+  REQUIRE(!o->refusal || value <= 0 || value == o->shipped, o->refusal, (int)value);
 #endif
-    e->winograd = value < 0 ? 0 : (int)value;
-    return ASX_OK;
-  }
-  if (!strcmp(key, "winograd_stationary")) {
-#ifndef ASX_EXPERIMENTAL_KERNELS
-    REQUIRE(value <= 0, "asx_set_option: the weight-stationary Winograd kernel (measured slower) is in experimental builds only (python build.py --experimental)");
-#endif
-    e->winos = value < 0 ? 0 : (int)value;
-    return ASX_OK;
-  }
-  if (!strcmp(key, "winograd_bf16x6")) {
-    e->wino6 = value < 0 ? 0 : (int)value;
-    return ASX_OK;
-  }
-  if (!strcmp(key, "gemm_bf16x6")) {                 // this engine only (round 5; it was process-wide before)
-    e->gemm_bf16x6 = value > 0 ? 1 : 0;
-    return ASX_OK;
-  }
-  if (!strcmp(key, "gemm_f16x3")) {
-    e->gemm_f16x3 = value > 0 ? 1 : 0;
-    return ASX_OK;
-  }
-  if (!strcmp(key, "conv_direct_f16x3")) {
-    e->conv3h = value < 0 ? 0 : (int)value;
-    return ASX_OK;
-  }
-  if (!strcmp(key, "conv_down_bf16x6")) {
-    e->down6 = value > 0 ? 1 : 0;
-    return ASX_OK;
-  }
-  if (!strcmp(key, "conv_up_bf16x6")) {
-    e->up6 = value > 0 ? 1 : 0;
-    return ASX_OK;
-  }
-  if (!strcmp(key, "gemm_pair_images")) {
-#ifndef ASX_EXPERIMENTAL_KERNELS
-    if (value > 0) {
-      set_err("asx_set_option: gemm_pair_images = 1 needs an experimental build (python build.py --experimental): the pair-image reader measured no faster in the nets and is not in the default library");
-      return ASX_ERR_INVALID;
-    }
-#endif
-    e->pair_images = value > 0 ? 1 : 0;
-    return ASX_OK;
-  }
-  set_err("asx_set_option: unknown option '%s'", key);
-  return ASX_ERR_INVALID;
+  e->*o->field = o->norm(value);
+  return ASX_OK;
+}
+
+int asx_get_option(const asx_engine *e, const char *key, int32_t *value) {
+  REQUIRE(e && key && value, "asx_get_option: null argument");
+  const EngineOption *o = find_option("asx_get_option", key);
+  if (!o) return ASX_ERR_INVALID;
+  *value = e->*o->field;
+  return ASX_OK;
 }
 
 // ---- profiling -------------------------------------------------------------------
@@ -2308,7 +2328,7 @@ int asx_profile_read(asx_engine *e, asx_profile *out) {
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipDeviceSynchronize());
   memset(out, 0, sizeof(*out));
-  static const bool dump = getenv("ASX_PROF_DUMP") != nullptr;   // one line per launch on stderr (tuning aid)
+  const bool dump = knobs().prof_dump;
   for (auto &r : e->recs) {
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));

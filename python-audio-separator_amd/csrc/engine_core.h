@@ -47,11 +47,9 @@ struct DevBuf {
     bytes = 0;
     HIPCHK(hipMalloc(&p, n));
     bytes = n;
-    // ASX_POISON=<byte 0..255>: fill every fresh allocation with that byte (255 = NaN, 127 = 3.39e38 floats) -- a debugging aid that
-    // makes any read of memory the engine never wrote show up in the results, instead of depending on what the allocation held
-    // before (round 5: a first forward on the bf16 x 6 kernels differed from later ones on some boxes and not on others)
-    static const int poison = getenv("ASX_POISON") ? atoi(getenv("ASX_POISON")) : -1;
-    if (poison >= 0) HIPCHK(hipMemset(p, poison & 255, n));
+    // ASX_POISON: a debugging aid that makes any read of memory the engine never wrote show up in the results, instead of depending on
+    // what the allocation held before (round 5: a first forward on the bf16 x 6 kernels differed from later ones on some boxes and not on others)
+    if (knobs().poison >= 0) HIPCHK(hipMemset(p, knobs().poison & 255, n));
     return ASX_OK;
   }
   void release() {
@@ -177,48 +175,41 @@ struct asx_engine {
   hipEvent_t div_ev = nullptr;       // recorded behind the kernel that built d_div; a call on ANOTHER stream waits for it
   hipStream_t div_stream = nullptr;
   std::vector<DevBuf> skip;
+  // The nine engine options (asx_set_option / asx_get_option; asx_engine_create sets them from EngineKnobs, knobs.h).
   // 3x3 / pad-1 convs of the ConvTDFNet and TFC-TDF-v3 nets: 3 = Winograd F(2x2,3x3) (conv_wino3_kernel, the default), 0 = the
-  // direct kernel (conv_dma_kernel), 1 / 2 = the earlier Winograd generations (kept for A/B runs).  ASX_WINOGRAD or
-  // asx_set_option("winograd", n).
-#ifdef ASX_EXPERIMENTAL_KERNELS
-  int winograd = getenv("ASX_WINOGRAD") ? std::max(0, atoi(getenv("ASX_WINOGRAD"))) : 3;
-#else   // generations 1 / 2 are not in this build: anything but 0 means the default
-  int winograd = getenv("ASX_WINOGRAD") ? (atoi(getenv("ASX_WINOGRAD")) <= 0 ? 0 : 3) : 3;
-#endif
+  // direct kernel (conv_dma_kernel), 1 / 2 = the earlier Winograd generations (kept for A/B runs; experimental builds only).
+  // ASX_WINOGRAD or asx_set_option("winograd", n).
+  int winograd = 3;
   // 1: layers with Cin <= 96 run the weight-stationary Winograd kernel (conv_winos_kernel, kernels_winos.h) when the option above
   // is 3; 0 (default -- the stationary form measured 3-8 % slower, profiles/NOTES.md round 4): conv_wino3_kernel everywhere.
   // ASX_WINOS or asx_set_option("winograd_stationary", n).
-#ifdef ASX_EXPERIMENTAL_KERNELS
-  int winos = getenv("ASX_WINOS") ? std::max(0, atoi(getenv("ASX_WINOS"))) : 0;
-#else
   int winos = 0;
-#endif
   // 1 (default): row GEMMs, channels-last convolutions (GATHER mode) and attention of THIS engine run the bf16 x 6 kernels when their
   // shapes allow (kernels_gemm3.h); 0: the fp32-MFMA kernels.  ASX_GEMM_BF16X6 or asx_set_option("gemm_bf16x6", n).
-  int gemm_bf16x6 = getenv("ASX_GEMM_BF16X6") ? atoi(getenv("ASX_GEMM_BF16X6")) : 1;
+  int gemm_bf16x6 = 1;
   // 1 (default): every kernel "gemm_bf16x6" sends to the 16-bit matrix pipe -- tdf3_kernel (row GEMMs, GATHER-mode convolutions),
   // attention6_kernel / mha6_kernel, conv_wino6_kernel -- runs the fp16 x 3 arithmetic: operands scaled by power-of-two block exponents and
   // split into two fp16 parts, three MFMAs per product instead of six (kernels_gemm3.h); 4-30 % faster per launch, as close to float64 as the
   // bf16 x 6 form on finite data (profiles/r05_gemm_f16x3.txt, r05_attention_f16x3.txt, r05_wino6_f16x3.txt).  0: bf16 x 6 (exact
   // three-way split) everywhere.  ASX_GEMM_F16X3 or asx_set_option("gemm_f16x3", n).
-  int gemm_f16x3 = getenv("ASX_GEMM_F16X3") ? atoi(getenv("ASX_GEMM_F16X3")) : 1;
+  int gemm_f16x3 = 1;
   // 3x3 TFC convs with at least this many input channels run Winograd F(2x2,3x3) on the bf16 pipe (conv_wino6_kernel, kernels_wino6.h)
   // when "winograd" is 3 and "gemm_bf16x6" is on; 0 = never.  Default 144: measured faster than conv_wino3_kernel from level 2 of the
   // HQ_3 net down, equal on level 1, slower on level 0 (profiles/r05_wino6_forms.txt).  ASX_WINO6 or asx_set_option("winograd_bf16x6", n).
-  int wino6 = getenv("ASX_WINO6") ? std::max(0, atoi(getenv("ASX_WINO6"))) : 144;
+  int wino6 = 144;
   // 3x3 TFC convs of 48 n -> 48 n channels with at most this many channels run the DIRECT implicit GEMM on the fp16 x 3 arithmetic (conv3h_kernel,
   // kernels_conv3h.h: 48 x 48 weight slices resident in LDS, no Winograd transforms; n x n launches per layer, the input slices summed through
   // the output) while "winograd" is 3 and "gemm_bf16x6" / "gemm_f16x3" are on; 0: never.  Default 144: levels 0, 1 and 2 of the HQ_3 geometry --
   // 5.2-5.5 ms per launch of 55 chunks against 8.5-8.9 on conv_wino3_kernel at 48 channels, 6.0 against 8.0-8.2 at 96, 3.76 against 4.0-4.1
   // (conv_wino6_kernel) at 144; the image is packed up to 144 channels.
   // ASX_CONV3H or asx_set_option("conv_direct_f16x3", n).
-  int conv3h = getenv("ASX_CONV3H") ? std::max(0, atoi(getenv("ASX_CONV3H"))) : 144;
+  int conv3h = 144;
   // 1 (default): the 2 x 2 / stride-2 convolutions between the levels run conv_down6_kernel (kernels_updown6.h: bf16 x 6 -- exact three-way split
   // operands on the 16-bit matrix pipe, fp32 accumulation) while "gemm_bf16x6" is on; 0: the fp32-MFMA kernel conv_dma_kernel<2, 2, 2, 0, ...>.
   // ASX_DOWN6 or asx_set_option("conv_down_bf16x6", n).
-  int down6 = getenv("ASX_DOWN6") ? atoi(getenv("ASX_DOWN6")) : 1;
+  int down6 = 1;
   // the same for the transposed 2 x 2 / stride-2 convolutions of the decoder (conv_up6_kernel).  ASX_UP6 or asx_set_option("conv_up_bf16x6", n).
-  int up6 = getenv("ASX_UP6") ? atoi(getenv("ASX_UP6")) : 1;
+  int up6 = 1;
   // EXPERIMENTAL builds only (`python build.py --experimental`; the default library refuses the option).  1: a matrix whose only reader is a row
   // GEMM on the fp16 x 3 arithmetic is written by its producer as a PAIR IMAGE -- the two fp16 parts the GEMM multiplies, in the bytes of the
   // fp32 values, one exponent per (row, column tile) beside it (kernels_net.h TdfDmaArgs::xexp; kernels_gemm3.h) -- so the reader splits
@@ -226,11 +217,7 @@ struct asx_engine {
   // is 3-17 % faster (profiles/r06_tdf3h_abl.txt, r06_tdf_pair_image_chain.txt), the whole nets are not (MDX TDF class 33.3 vs 33.2 ms,
   // BS-Roformer row GEMMs 940 vs 932 ms per step: profiles/NOTES.md) -- retired with the other measured-and-lost variants.  Default 0.
   // ASX_PAIR_IMAGES or asx_set_option("gemm_pair_images", n).
-#ifdef ASX_EXPERIMENTAL_KERNELS
-  int pair_images = getenv("ASX_PAIR_IMAGES") ? atoi(getenv("ASX_PAIR_IMAGES")) : 0;
-#else
   int pair_images = 0;
-#endif
   // split (bf16 x 3) images of this engine's weight matrices, built on first use and freed only with the engine or when the engine's
   // own weights are re-loaded: another engine of the process can never invalidate a pointer a captured graph of this one holds
   std::vector<W3Entry> w3;
@@ -281,9 +268,8 @@ static bool make_plan(int n_fft, FftPlan *p) {
   p->n_stage = 0;
   int n = p->nh;
   // large radices first: a 2048-point transform is 16 x 16 x 8 -- three barrier-separated LDS passes instead of six radix-4 / 2
-  // ones (the generic kernels are bound by their passes, not by memory: profiles/NOTES.md).  ASX_FFT_RADIX4=1: the old plans.
-  static const bool r4only = getenv("ASX_FFT_RADIX4") && atoi(getenv("ASX_FFT_RADIX4")) != 0;
-  if (!r4only) {
+  // ones (the generic kernels are bound by their passes, not by memory: profiles/NOTES.md).  ASX_FFT_RADIX4: the old plans.
+  if (!knobs().fft_radix4) {
     while (n % 16 == 0) {
       p->radix[p->n_stage++] = 16;
       n /= 16;

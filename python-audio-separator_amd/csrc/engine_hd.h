@@ -463,8 +463,7 @@ static int hd_blstm_joint(asx_engine *e, std::vector<HdGroup> &G, bool levelZ, s
 static int hd_attn_variant(const MhaArgs &a, int dh) {
   if (dh % 16 == 0 && (dh <= 64 || dh == 96)) {
     // the flash attention of the v4 transformer (kernels_ht.h) with the per-query decay slope and the -100 diagonal
-    static const bool hd_mha_db = !(getenv("ASX_MHA_DB") && atoi(getenv("ASX_MHA_DB")) == 0);
-    const int v = (dh == 48 && hd_mha_db) ? AV_MHA_DB : AV_MHA;
+    const int v = (dh == 48 && knobs().hd_mha_db) ? AV_MHA_DB : AV_MHA;
     return mha_variant_ok(v, a, dh) ? v : AV_AUTO;
   }
   return hd_local_ok(dh) ? AV_HD_LOCAL : AV_AUTO;
@@ -485,8 +484,7 @@ static int hd_local_state(asx_engine *e, const HdAttn &A, float *hbuf, int B, in
   a.ldo = H;
   a.nq = a.nk = T;
   a.scale = 1.0f / sqrtf((float)dh);
-  static const int attn_exact = getenv("ASX_ATTN_EXACT") != nullptr;
-  a.exact = attn_exact;
+  a.exact = knobs().attn_exact;
   a.decay = b.qkvd + 3 * H;
   a.ldd = ld;
   const int v = hd_attn_variant(a, dh);
@@ -782,9 +780,8 @@ static int hd_plan(const asx_engine *e, int64_t N, int32_t shifts, const int64_t
 
 // chunk forwards [k0, k1) -> chunk_out [k1-k0, S, 2, segment] (each row holds clen valid samples).  Chunks of equal
 // length form one group (up to max_batch of them); up to HD_MAX_GROUPS groups advance together and share their BLSTM
-// launches (hd_forward_groups).  (Running the tail groups on a second stream instead was measured and gave nothing: the
-// two HSA queues never had kernels in flight together)
-constexpr int HD_MAX_GROUPS = 6;
+// launches (hd_forward_groups; HD_MAX_GROUPS is in knobs.h beside ASX_HD_GROUPS).  (Running the tail groups on a second stream instead was
+// measured and gave nothing: the two HSA queues never had kernels in flight together)
 
 static int hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const HdPlan &p, uint32_t flags, int k0, int k1, float *chunk_out,
                            hipStream_t s) {
@@ -803,7 +800,7 @@ static int hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const
   const int nk = (int)order.size();
   std::vector<int64_t> st(nk);
   for (int i = 0; i < nk; ++i) st[i] = p.starts[order[i]];
-  static const int max_groups = getenv("ASX_HD_GROUPS") ? std::max(1, std::min(HD_MAX_GROUPS, atoi(getenv("ASX_HD_GROUPS")))) : HD_MAX_GROUPS;
+  const int max_groups = knobs().hd_groups;
   int i = 0;
   while (i < nk) {
     std::vector<HdGroup> G;

@@ -123,8 +123,7 @@ static int ht_up_named(asx_engine *e, DevBuf &d, const std::string &name, int64_
 
 // second packing of a stride-1 k3 / 3x3 conv for the halo-tile kernel (pw = [N, taps*cinp] as uploaded to g.w)
 static int ht_halo_pack(HtGemm &g, const std::vector<float> &pw, int taps, int cinp) {
-  static const bool off = getenv("ASX_HALO") != nullptr && atoi(getenv("ASX_HALO")) == 0;
-  if (off || (taps != 3 && taps != 9) || (cinp % HG_KC) != 0 || (g.n & 3)) return ASX_OK;
+  if (!knobs().halo || (taps != 3 && taps != 9) || (cinp % HG_KC) != 0 || (g.n & 3)) return ASX_OK;
   std::vector<float> ph;
   g.wh_nt = hg_tile_n(g.n);
   g.wh_taps = taps;
@@ -553,9 +552,9 @@ static int ht_gg(asx_engine *e, const HtGemm &g, const float *x, const HtGeom &q
   // are HBM-bound (algorithmic flop / byte under ASX_GG_LOWAI) or whose 128-row grid would not fill the chip twice
   // (ASX_GG_SMALLGRID workgroups: the inner Demucs levels).  Measured (profiles/NOTES.md): threshold 0 / 40 / 90 / 200 / inf ->
   // htdemucs 956 / 965 / 975 / 974 / 976x, hdemucs_mmi 1120 / 1130 / 1148 / 1163 / 1181x, VR 522 / 520 / 521 / 517 / 516x.
-  static const double lowai_thr = getenv("ASX_GG_LOWAI") ? atof(getenv("ASX_GG_LOWAI")) : 90.0;
-  static const int64_t small_grid = getenv("ASX_GG_SMALLGRID") ? atoll(getenv("ASX_GG_SMALLGRID")) : 1024;
   {
+    const double lowai_thr = knobs().gg_lowai;
+    const int64_t small_grid = knobs().gg_smallgrid;
     const int tn = gg_tile_n(a.N, g.glu_c != 0);
     const int64_t blocks128 = ((a.M + 127) / 128) * ((a.N + tn - 1) / tn);
     a.lowai = ((bytes > 0.0 && flops / bytes < lowai_thr) || blocks128 < small_grid) ? 1 : 0;
@@ -563,19 +562,15 @@ static int ht_gg(asx_engine *e, const HtGemm &g, const float *x, const HtGeom &q
   // stride-1 dense convs with 32-aligned channel counts: the bf16 x 6 row GEMM in GATHER mode (kernels_gemm3.h) -- an implicit GEMM
   // whose A rows are the pixels of the channels-last image, one (tap, 32-channel chunk) per stage.  ASX_GATHER6=0: A/B.
   {
-    static const bool gather6 = !(getenv("ASX_GATHER6") && atoi(getenv("ASX_GATHER6")) == 0);
+    const Knobs &k = knobs();
     auto a16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    static const int gather_minn = getenv("ASX_GATHER6_MINN") ? atoi(getenv("ASX_GATHER6_MINN")) : 48;   // narrowest dense layer routed here
-    static const bool gather_glu = !(getenv("ASX_GATHER6_GLU") && atoi(getenv("ASX_GATHER6_GLU")) == 0);
-    const bool glu = mode == GG_GLU && gather_glu && g.glu_c > 0 && g.n % 32 == 0;
-    static const bool gather_strided = !(getenv("ASX_GATHER6_STRIDED") && atoi(getenv("ASX_GATHER6_STRIDED")) == 0);
+    const bool glu = mode == GG_GLU && k.gather6_glu && g.glu_c > 0 && g.n % 32 == 0;
     const bool unit = q.SI == 1 && q.SO == 1 && q.IR == q.I && a.OR == q.O;
     // channel counts off the 32-grid (48, 80, ...): the last chunk of every tap is zero padded -- worth it from 70 % chunk use
     // (ASX_GATHER6_PARTIAL=0: only multiples of 32)
-    static const bool gather_partial = !(getenv("ASX_GATHER6_PARTIAL") && atoi(getenv("ASX_GATHER6_PARTIAL")) == 0);
-    const bool cin_ok = q.Cin % 32 == 0 || (gather_partial && q.Cin % 8 == 0 && q.Cin > 32 && 10 * q.Cin >= 7 * 32 * ((q.Cin + 31) / 32));
-    if (gather6 && e->gemm_bf16x6 > 0 && (mode == GG_DENSE || glu) && res == nullptr && fz == nullptr && (unit || gather_strided) &&
-        q.SI >= 1 && q.SO >= 1 && q.KO <= 3 && q.KO * q.KI > 1 && cin_ok && g.n % 8 == 0 && g.n >= (glu ? 65 : gather_minn) && (q.ldc & 3) == 0 && (ldy & 3) == 0 &&
+    const bool cin_ok = q.Cin % 32 == 0 || (k.gather6_partial && q.Cin % 8 == 0 && q.Cin > 32 && 10 * q.Cin >= 7 * 32 * ((q.Cin + 31) / 32));
+    if (k.gather6 && e->gemm_bf16x6 > 0 && (mode == GG_DENSE || glu) && res == nullptr && fz == nullptr && (unit || k.gather6_strided) &&
+        q.SI >= 1 && q.SO >= 1 && q.KO <= 3 && q.KO * q.KI > 1 && cin_ok && g.n % 8 == 0 && g.n >= (glu ? 65 : k.gather6_minn) && (q.ldc & 3) == 0 && (ldy & 3) == 0 &&
         a.y_bs == (int64_t)a.OR * q.IR * ldy && a16(x) && a16(y) && a16(g.w.p) && a16(g.b.p) && a.M < (1ll << 31) &&
         (int64_t)(q.KO * q.DO + q.PO + 1) * q.I * q.ldc < (1ll << 31) && (uint64_t)16 * (uint64_t)ldy * 4 < (1ull << 31)) {
       TdfDmaArgs d{};
@@ -616,7 +611,7 @@ static int ht_gg(asx_engine *e, const HtGemm &g, const float *x, const HtGeom &q
   // stride-1 k3 / 3x3 convs with a halo packing run on the halo-tile kernel (the input block enters LDS once for all taps)
   HgGeom hgm;
   // A/B knob: launches whose halo grid would be smaller than ASX_HALO_MINBLK workgroups stay on gg_kernel (128-row tiles)
-  static const int64_t halo_minblk = getenv("ASX_HALO_MINBLK") ? atoll(getenv("ASX_HALO_MINBLK")) : 0;
+  const int64_t halo_minblk = knobs().halo_minblk;
   if (g.wh.p != nullptr && q.SI == 1 && q.SO == 1 && q.KI == 3 && (q.KO == 1 || q.KO == 3) && q.KO * q.KI == g.wh_taps &&
       (mode == GG_DENSE || mode == GG_GLU) && res == nullptr && a.row_stat == nullptr && q.IR == q.I && a.OR == q.O &&
       (q.KO == 3 || q.O == 1) && (((uintptr_t)x | (uintptr_t)y) & 15) == 0 && hg_geometry(q.O, q.I, q.KO, q.DO, q.DI, &hgm) && (int64_t)q.O * q.I * q.ldc < (1ll << 31) &&   // 32-bit lane offsets inside an image
@@ -680,8 +675,7 @@ static int ht_linear(asx_engine *e, const HtGemm &g, const float *x, int64_t lda
   d.ldy = ldy;
   d.ldr = ldr;
   // 64 x 128 tiles, three workgroups per CU: 56.2 -> 53.7 ms per song on the transformer linears (ASX_HT_LINEAR_SMALL=0: A/B)
-  static const bool lin_small = !(getenv("ASX_HT_LINEAR_SMALL") && atoi(getenv("ASX_HT_LINEAR_SMALL")) == 0);
-  d.prefer_small = lin_small ? 1 : 0;
+  d.prefer_small = knobs().ht_linear_small ? 1 : 0;
   if ((g.k & 3) || (lda & 3) || (ldy & 3) || (g.n & 3) || (res && (ldr & 3))) {
     set_err("ht_linear: K, N and row strides must be multiples of 4 floats");
     return ASX_ERR_INVALID;
@@ -740,16 +734,14 @@ static int ht_gn(asx_engine *e, float *x, int G1, int64_t R, int G2, int ld, int
 static int ht_mha_variant(const asx_engine *e, const MhaArgs &a, int nq, int dh) {
   // dh = 48: the single-buffered build runs FOUR workgroups per CU (118 registers, 26 KB of LDS): 55.0 -> 51.5 ms per song
   // against the double-buffered, one-barrier build with three (ASX_MHA_DB=1: A/B) -- occupancy, not the barrier count
-  static const bool mha_db = getenv("ASX_MHA_DB") && atoi(getenv("ASX_MHA_DB")) != 0;
   // bf16 x 6 form (kernels_ht.h: mha6_kernel) under the process-wide switch of the row GEMM; ASX_MHA6=0: A/B
-  static const bool mha6 = !(getenv("ASX_MHA6") && atoi(getenv("ASX_MHA6")) == 0);
-  if (mha6 && e->gemm_bf16x6 > 0 && a.decay == nullptr && (dh == 48 || dh == 64) && (a.ldq & 3) == 0 && (a.ldk & 3) == 0 &&
+  if (knobs().mha6 && e->gemm_bf16x6 > 0 && a.decay == nullptr && (dh == 48 || dh == 64) && (a.ldq & 3) == 0 && (a.ldk & 3) == 0 &&
       (a.ldv & 3) == 0 && (a.ldo & 3) == 0) {
     const bool wide = nq > 128;                      // 128 queries per workgroup on long sequences
     if (e->gemm_f16x3 > 0) return wide ? AV_MHA6H_WIDE : AV_MHA6H;   // fp16 x 3 arithmetic (kernels_ht.h: template parameter H)
     return wide ? AV_MHA6_WIDE : AV_MHA6;
   }
-  return (dh == 48 && mha_db) ? AV_MHA_DB : AV_MHA;
+  return (dh == 48 && knobs().ht_mha_db) ? AV_MHA_DB : AV_MHA;
 }
 
 static int ht_mha(asx_engine *e, const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv, float *out,
@@ -766,8 +758,7 @@ static int ht_mha(asx_engine *e, const float *q, int64_t ldq, const float *k, co
   a.nq = nq;
   a.nk = nk;
   a.scale = 1.0f / sqrtf((float)dh);
-  static const int attn_exact = getenv("ASX_ATTN_EXACT") != nullptr;
-  a.exact = attn_exact;
+  a.exact = knobs().attn_exact;
   const double flops = 4.0 * (double)B * heads * (double)nq * nk * dh;
   const double bytes = 4.0 * (double)B * heads * dh * (2.0 * nq + 2.0 * nk);
   const int variant = ht_mha_variant(e, a, nq, dh);

@@ -9,12 +9,7 @@
 // ----------------------------------------------------------------------------
 template <class CFG>
 static void launch_conv_t(const ConvArgs &a, int nblk, hipStream_t s) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma_kernel<CFG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, CFG::LDS_BYTES);
-    attr_done = true;
-  }
+  grant_lds(&conv_mfma_kernel<CFG>, CFG::LDS_BYTES);
   hipLaunchKernelGGL(conv_mfma_kernel<CFG>, dim3(nblk), dim3(256), CFG::LDS_BYTES, s, a);
 }
 
@@ -34,8 +29,7 @@ static int pick_nrep_conv(int cout) {
 }
 static int pick_nrep_up(int cout) {
   const int ct = (cout + 15) / 16;  // virtual tiles = 4*ct, pairs must stay together
-  static const int force = getenv("ASX_UP_NREP") ? atoi(getenv("ASX_UP_NREP")) : 0;   // A/B: 4 = four virtual tiles per workgroup wherever they divide
-  if (force == 4 && (4 * ct) % 4 == 0) return 4;
+  if (knobs().up_nrep == 4 && (4 * ct) % 4 == 0) return 4;
   if ((4 * ct) % 6 == 0) return 6;
   if ((4 * ct) % 4 == 0) return 4;
   return 2;
@@ -57,14 +51,11 @@ static int conv_setup(ConvLayer &L, int kind, int cin, int cout, int relu) {
     // 3x3 convs stage FOUR channels at a time (37 KB of LDS instead of 75 KB at eight): a third co-resident workgroup
     // per CU covers the prologue / epilogue / barrier gaps of the other two.  Measured on the bench configuration: 3x3 class
     // 234.9 -> 224.0 ms (85.1 -> 89.4 % of the fp32-MFMA peak), every level gains.  ASX_CONV_KC4=<cin threshold> for the
-    // A/B (0 = eight channels everywhere).
-    static const int kc4 = getenv("ASX_CONV_KC4") ? atoi(getenv("ASX_CONV_KC4")) : (1 << 30);
-    // (also for the two-tile channel groups of the MDX23C widths: ASX_CONV_KC4_N2=0 keeps their eight-channel stages)
-    static const int kc4_n2 = getenv("ASX_CONV_KC4_N2") ? atoi(getenv("ASX_CONV_KC4_N2")) : 1;
-    if (kind == CK_3X3 && cin <= kc4 && cin % 4 == 0 && (pick_nrep_conv(cout) == 3 || (kc4_n2 && pick_nrep_conv(cout) == 2))) L.kc = 4;
+    // A/B (0 = eight channels everywhere).  Also for the two-tile channel groups of the MDX23C widths (ASX_CONV_KC4_N2).
+    const Knobs &k = knobs();
+    if (kind == CK_3X3 && cin <= k.conv_kc4 && cin % 4 == 0 && (pick_nrep_conv(cout) == 3 || (k.conv_kc4_n2 && pick_nrep_conv(cout) == 2))) L.kc = 4;
     // 2x2 / stride-2 conv: two-channel stages (four workgroups per CU); ASX_DOWN_KC2=0 keeps the four-channel stages
-    static const int down_kc2 = getenv("ASX_DOWN_KC2") ? atoi(getenv("ASX_DOWN_KC2")) : 1;
-    if (kind == CK_DOWN && down_kc2 && cin % 2 == 0 && pick_nrep_conv(cout) == 3) L.kc = 2;
+    if (kind == CK_DOWN && k.down_kc2 && cin % 2 == 0 && pick_nrep_conv(cout) == 3) L.kc = 2;
     L.cg = ((cout + 15) / 16 + L.nrep - 1) / L.nrep;
   }
   L.nci = (cin + L.kc - 1) / L.kc;
@@ -208,8 +199,7 @@ static int conv_pack(ConvLayer &L, const float *w, const float *b, int wino_mode
   if (L.kind == CK_DOWN) {
     // bf16 x 6 image of the 2 x 2 / stride-2 conv (kernels_updown6.h); which kernel RUNS is the engine's "gemm_bf16x6" option at launch time
     std::vector<uint32_t> w6;
-    static const int wide = getenv("ASX_DOWN6_WIDE") ? atoi(getenv("ASX_DOWN6_WIDE")) : 1;   // A/B: 96-channel workgroups where Cout % 96 == 0
-    L.wd6_nrep = (wide && L.cout % 96 == 0) ? 6 : 3;
+    L.wd6_nrep = (knobs().down6_wide && L.cout % 96 == 0) ? 6 : 3;
     if (L.wd6_nrep == 6) down6_pack<6>(w, L.cout, L.cin, w6, &L.wd6_cg, &L.wd6_nst);
     else down6_pack<3>(w, L.cout, L.cin, w6, &L.wd6_cg, &L.wd6_nst);
     CHK(L.wd6.ensure(w6.size() * 4));
@@ -236,12 +226,7 @@ static int conv_pack(ConvLayer &L, const float *w, const float *b, int wino_mode
 
 template <class CFG>
 static void launch_conv_dma_t(const ConvArgs &a, int nblk, hipStream_t s) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_dma_kernel<CFG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, CFG::LDS_BYTES);
-    attr_done = true;
-  }
+  grant_lds(&conv_dma_kernel<CFG>, CFG::LDS_BYTES);
   hipLaunchKernelGGL(conv_dma_kernel<CFG>, dim3(nblk), dim3(256), CFG::LDS_BYTES, s, a);
 }
 
@@ -282,8 +267,7 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
   REQUIRE(a.act != ACT_ELU || L.kind == CK_1X1, "ELU epilogue: 1x1 convolutions only");
   a.CG = L.cg;
   a.NCI = L.nci;
-  static const int nt_mode = getenv("ASX_NT") ? atoi(getenv("ASX_NT")) : 0;   // bit 0: conv stores, bit 1: TDF stores, bit 2: TDF residual loads
-  a.nt = nt_mode & 1;
+  a.nt = knobs().nt & 1;
   int cls = ASX_PROF_CONV3X3;
   double taps = 9;
   int64_t out_plane;
@@ -320,8 +304,7 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
   if (L.kind == CK_UP && skip) bytes += 4.0 * (double)L.cout * outpix * 4;  // skip read
   if (v.res) bytes += 4.0 * (double)L.cout * outpix;
   int bad = 0;
-  const bool dma = (F % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && (a.x_bstride % 4 == 0) &&
-                   getenv("ASX_NO_DMA") == nullptr;
+  const bool dma = (F % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && (a.x_bstride % 4 == 0) && !knobs().no_dma;
   const ConvArgs &d = a;
 #ifdef ASX_EXPERIMENTAL_KERNELS   // measured-and-rejected generations (profiles/NOTES.md): python build.py --experimental, or ASX_EXPERIMENTAL=1 in the environment of the build
   if (L.kind == CK_3X3 && e->winograd == 3 && e->winos == 1 && dma && L.wus.p != nullptr && a.Fo % 32 == 0 && v.res == nullptr &&
@@ -341,16 +324,10 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     wa.NCI = SPB;
     const int nb = base * RB;
     auto gos = [&](auto kern, int lds) {
-      {
-        static std::mutex attr_mutex;
-        static std::set<const void *> attr_done;
-        std::lock_guard<std::mutex> lock(attr_mutex);
-        if (attr_done.insert(reinterpret_cast<const void *>(kern)).second)
-          (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      }
+      grant_lds(kern, lds);
       return timed(e, cls, flops, bytes, s, [&]() { hipLaunchKernelGGL(kern, dim3(nb), dim3(512), lds, s, wa); });
     };
-    static const int abls = getenv("ASX_WINOS_ABL") ? atoi(getenv("ASX_WINOS_ABL")) : 0;   // timing probes (results invalid)
+    const int abls = knobs().winos_abl;
     const bool k12 = L.wus_ks == 12;
     const bool ragged = (a.To & 1) || (L.cout % 48) != 0;
     if (abls && !ragged) {
@@ -390,16 +367,8 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
       }
     }
     if (best > 1e29) bw = 32;                          // (tilesT not divisible: one segment)
-    {
-      static std::mutex attr_mutex;
-      static bool attr_done = false;
-      std::lock_guard<std::mutex> lock(attr_mutex);
-      if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3h_kernel<0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, Conv3hCfg::LDS_BYTES);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3h_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, Conv3hCfg::LDS_BYTES);
-        attr_done = true;
-      }
-    }
+    grant_lds(&conv3h_kernel<0, false>, Conv3hCfg::LDS_BYTES);
+    grant_lds(&conv3h_kernel<0, true>, Conv3hCfg::LDS_BYTES);
     const int64_t plane = (int64_t)T * F;
     return timed(e, cls, flops, bytes, s, [&]() {
       e->prof_nprod = 3;
@@ -440,18 +409,8 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     const int64_t S = (int64_t)wa.tilesT * wa.tilesF * B;
     const int64_t nb = ((S + 7) / 8) * 8 * wa.CG;
     if (nb < ((int64_t)1 << 31)) {
-      {
-        static std::mutex attr_mutex;
-        static bool attr_done = false;
-        std::lock_guard<std::mutex> lock(attr_mutex);
-        if (!attr_done) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wino6_kernel<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    Wino6Cfg::LDS_BYTES);
-          (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wino6_kernel<0, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    Wino6Cfg::LDS_BYTES);
-          attr_done = true;
-        }
-      }
+      grant_lds(&conv_wino6_kernel<0, 1>, Wino6Cfg::LDS_BYTES);
+      grant_lds(&conv_wino6_kernel<0, 1, true>, Wino6Cfg::LDS_BYTES);
       g_wino6_launches.fetch_add(1);
       if (h3) g_wino6h_launches.fetch_add(1);
       return timed(e, cls, flops, bytes, s, [&]() {
@@ -470,21 +429,15 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     wa.tilesF = (a.Fo + Wino3Cfg::TW - 1) / Wino3Cfg::TW;
     const int nb = wa.CG * wa.tilesT * wa.tilesF * B;
     auto go = [&](auto kern, int lds, int stages) {
-      {
-        static std::mutex attr_mutex;            // engines may be driven from several host threads (one per bag member / rank)
-        static std::set<const void *> attr_done;
-        std::lock_guard<std::mutex> lock(attr_mutex);
-        if (attr_done.insert(reinterpret_cast<const void *>(kern)).second)
-          (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      }
+      grant_lds(kern, lds);
       wa.NCI = stages;
       return timed(e, cls, flops, bytes, s, [&]() { hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, s, wa); });
     };
 #ifdef ASX_EXPERIMENTAL_KERNELS
-    static const int abl3 = getenv("ASX_WINO_ABL") ? atoi(getenv("ASX_WINO_ABL")) : 0;   // timing probes (results invalid)
-    // A/B builds: 6 (default): 4-channel stages x 2 LDS buffers, raw planes at an odd float stride; 5 / 4: rings of 3 / 4 buffers
+    const int abl3 = knobs().wino_abl;
+    // A/B builds (ASX_WINO_CFG): 6 (default): 4-channel stages x 2 LDS buffers, raw planes at an odd float stride; 5 / 4: rings of 3 / 4 buffers
     // (two / three stages of DMA in flight, counted vmcnt); 0 / 2: 4 / 3 buffers at the even stride; 1: 8-channel stages x 2 buffers
-    static const int wcfg = getenv("ASX_WINO_CFG") ? atoi(getenv("ASX_WINO_CFG")) : 6;
+    const int wcfg = knobs().wino_cfg;
     if (abl3) {
       switch (abl3) {
         case 1: return go(&conv_wino3_kernel<1>, Wino3Cfg::LDS_BYTES, L.wu3_nci);
@@ -511,12 +464,7 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     wa.tilesT = (a.To + 7) / 8;
     wa.tilesF = (a.Fo + 31) / 32;
     const int nb = wa.CG * wa.tilesT * wa.tilesF * B;
-    static bool attr_done = false;
-    if (!attr_done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wino2_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                Wino2Cfg<4>::LDS_BYTES);
-      attr_done = true;
-    }
+    grant_lds(&conv_wino2_kernel<4>, Wino2Cfg<4>::LDS_BYTES);
     return timed(e, cls, flops, bytes, s, [&]() {
       hipLaunchKernelGGL(conv_wino2_kernel<4>, dim3(nb), dim3(256), Wino2Cfg<4>::LDS_BYTES, s, wa);
     });
@@ -529,12 +477,7 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     wa.tilesT = (a.To + WinoCfg::TH - 1) / WinoCfg::TH;
     wa.tilesF = (a.Fo + WinoCfg::TW - 1) / WinoCfg::TW;
     const int nb = wa.CG * wa.tilesT * wa.tilesF * B;
-    static bool attr_done = false;
-    if (!attr_done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_wino_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, WinoCfg::LDS_BYTES);
-      attr_done = true;
-    }
+    grant_lds(&conv_wino_kernel, WinoCfg::LDS_BYTES);
     return timed(e, cls, flops, bytes, s, [&]() {
       hipLaunchKernelGGL(conv_wino_kernel, dim3(nb), dim3(256), WinoCfg::LDS_BYTES, s, wa);
     });
@@ -552,12 +495,8 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     da.tilesT = (a.To + Down6Cfg::TH - 1) / Down6Cfg::TH;
     da.tilesF = (a.Fo + Down6Cfg::TW - 1) / Down6Cfg::TW;
     const int nb6 = da.CG * da.tilesT * da.tilesF * B;
-    static bool attr6 = false;
-    if (!attr6) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_down6_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, Down6CfgT<3>::LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_down6_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize, Down6CfgT<6>::LDS_BYTES);
-      attr6 = true;
-    }
+    grant_lds(&conv_down6_kernel<3>, Down6CfgT<3>::LDS_BYTES);
+    grant_lds(&conv_down6_kernel<6>, Down6CfgT<6>::LDS_BYTES);
     g_down6_launches.fetch_add(1);
     return timed(e, cls, flops, bytes, s, [&]() {
       e->prof_nprod = 6;
@@ -575,13 +514,9 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     ua.tilesT = (T + 1) / 2;
     ua.tilesF = (F + 63) / 64;
     const int nbu = ua.CG * ua.tilesT * ua.tilesF * B;
-    static bool attru = false;
-    if (!attru) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_up6_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize, Up6CfgT<6>::LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_up6_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, Up6CfgT<4>::LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_up6_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, Up6CfgT<2>::LDS_BYTES);
-      attru = true;
-    }
+    grant_lds(&conv_up6_kernel<6>, Up6CfgT<6>::LDS_BYTES);
+    grant_lds(&conv_up6_kernel<4>, Up6CfgT<4>::LDS_BYTES);
+    grant_lds(&conv_up6_kernel<2>, Up6CfgT<2>::LDS_BYTES);
     g_up6_launches.fetch_add(1);
     return timed(e, cls, flops, bytes, s, [&]() {
       e->prof_nprod = 6;
@@ -640,12 +575,7 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
 template <int NREP, int MREP, bool KVEC>
 static void launch_tdf_tt(const TdfArgs &a, hipStream_t s) {
   using CFG = TdfCfg<NREP, MREP>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&tdf_mfma_kernel<NREP, MREP, KVEC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, CFG::LDS_BYTES);
-    attr_done = true;
-  }
+  grant_lds(&tdf_mfma_kernel<NREP, MREP, KVEC>, CFG::LDS_BYTES);
   const int64_t nbm = (a.M + CFG::BM - 1) / CFG::BM;
   const int nbn = (a.N + CFG::BN - 1) / CFG::BN;
   hipLaunchKernelGGL((tdf_mfma_kernel<NREP, MREP, KVEC>), dim3((unsigned)(nbm * nbn)), dim3(256), CFG::LDS_BYTES, s,
@@ -660,20 +590,14 @@ static void launch_tdf_t(const TdfArgs &a, hipStream_t s) {
 template <int NREP, int MREP, int BK>
 static void launch_tdf_dma_tt(const TdfDmaArgs &a, hipStream_t s) {
   using CFG = TdfDmaCfg<NREP, MREP, BK>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&tdf_dma_kernel<NREP, MREP, BK>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, CFG::LDS_BYTES);
-    attr_done = true;
-  }
+  grant_lds(&tdf_dma_kernel<NREP, MREP, BK>, CFG::LDS_BYTES);
   const int64_t nbm = (a.M + CFG::BM - 1) / CFG::BM;
   const int nbn = (a.N + CFG::BN - 1) / CFG::BN;
   hipLaunchKernelGGL((tdf_dma_kernel<NREP, MREP, BK>), dim3((unsigned)(nbm * nbn)), dim3(256), CFG::LDS_BYTES, s, a);
 }
 template <int NREP, int MREP>
 static void launch_tdf_dma_t(const TdfDmaArgs &a, hipStream_t s) {
-  static const bool bk64 = getenv("ASX_GEMM_BK64") != nullptr;
-  if (bk64 && NREP == 3 && MREP == 8 && a.K >= 128) launch_tdf_dma_tt<3, 8, 64>(a, s);
+  if (knobs().gemm_bk64 && NREP == 3 && MREP == 8 && a.K >= 128) launch_tdf_dma_tt<3, 8, 64>(a, s);
   else launch_tdf_dma_tt<NREP, MREP, 32>(a, s);
 }
 
@@ -684,10 +608,7 @@ static void launch_tdf_dma_t(const TdfDmaArgs &a, hipStream_t s) {
 // ASX_GEMM_T128=0 forces 128 x 192, =2 forces 128 x 128 (tuning aid).
 // second-generation row GEMM (kernels_gemm2.h).  ASX_TDF2: 0 = tdf_dma_kernel only, 1 = tdf2 one tile per workgroup,
 // 2 = + persistent over the column tiles of a row tile on short-K layers, 3 = + start stagger (ASX_TDF2_SBIT: block-id bit).
-static int tdf2_mode() {
-  static const int m = getenv("ASX_TDF2") ? atoi(getenv("ASX_TDF2")) : ASX_TDF2_DEFAULT;
-  return m;
-}
+static int tdf2_mode() { return knobs().tdf2; }
 static bool tdf2_ok(const TdfDmaArgs &d) {
   auto a16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const int64_t lda = d.lda ? d.lda : d.K, ldy = d.ldy ? d.ldy : d.N, ldr = d.ldr ? d.ldr : d.N;
@@ -700,13 +621,7 @@ static bool tdf2_ok(const TdfDmaArgs &d) {
 template <int NREP, int MREP, int ABL, int BK = 32>
 static void launch_tdf2_abl(const TdfDmaArgs &a, hipStream_t s) {
   constexpr int BM = 16 * MREP, BN = 64 * NREP, LDS_BYTES = 2 * (BM + BN) * BK * 4;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&tdf2_kernel<NREP, MREP, ABL, BK>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr_done = true;
-  }
-  static const int sbit = getenv("ASX_TDF2_SBIT") ? atoi(getenv("ASX_TDF2_SBIT")) : 8;
+  grant_lds(&tdf2_kernel<NREP, MREP, ABL, BK>, LDS_BYTES);
   const int64_t nbm = (a.M + BM - 1) / BM;
   const int nbn = (a.N + BN - 1) / BN;
   const int mode = tdf2_mode();
@@ -715,14 +630,13 @@ static void launch_tdf2_abl(const TdfDmaArgs &a, hipStream_t s) {
   const bool persist = mode >= 2 && nbn >= 2 && a.K <= 768 && nbm >= 2048;
   const int tiles = persist ? nbn : 1;
   hipLaunchKernelGGL((tdf2_kernel<NREP, MREP, ABL, BK>), dim3((unsigned)(nbm * (nbn / tiles))), dim3(256), LDS_BYTES, s, a, tiles,
-                     (mode >= 3 && persist) ? sbit : -1);
+                     (mode >= 3 && persist) ? knobs().tdf2_sbit : -1);
 }
 template <int NREP, int MREP>
 static void launch_tdf2(const TdfDmaArgs &a, hipStream_t s) {
 #ifdef ASX_EXPERIMENTAL_KERNELS
-  static const int abl = getenv("ASX_TDF2_ABL") ? atoi(getenv("ASX_TDF2_ABL")) : 0;   // ablation builds exist for the 128 x 192 tile only
-  if constexpr (NREP == 3 && MREP == 8) {
-    switch (abl) {
+  if constexpr (NREP == 3 && MREP == 8) {   // ablation builds exist for the 128 x 192 tile only
+    switch (knobs().tdf2_abl) {
       case 1: return launch_tdf2_abl<3, 8, 1>(a, s);
       case 2: return launch_tdf2_abl<3, 8, 2>(a, s);
       case 3: return launch_tdf2_abl<3, 8, 3>(a, s);
@@ -735,7 +649,7 @@ static void launch_tdf2(const TdfDmaArgs &a, hipStream_t s) {
     }
   }
   // ASX_TDF2_BK16: 16-float stages (40 KB of LDS, launch bound 3) -- 1: on the 128 x 192 tile, 2: on a 64 x 192 tile
-  static const int bk16 = getenv("ASX_TDF2_BK16") ? atoi(getenv("ASX_TDF2_BK16")) : 0;
+  const int bk16 = knobs().tdf2_bk16;
   if constexpr (NREP == 3 && MREP == 8) {
     if (a.M % 16 == 0 && a.N % 16 == 0 && a.relu == 1 && a.K % 16 == 0) {
       if (bk16 == 1) return launch_tdf2_abl<3, 8, 0, 16>(a, s);
@@ -829,13 +743,12 @@ static void launch_tdf3_abl(const TdfDmaArgs &a0, const u32x4 *w3, hipStream_t s
   // Default (round 5, profiles/r05_tdf3_tile_map_ab.txt + r05_pmc_tdf3.json): fewer than 8 column tiles -> map 1 (the column tiles of a
   // row block are neighbours on one XCD, so x crosses the fabric once instead of twice: level-0 first TDF linear 6.86 -> 6.69 ms,
   // fabric traffic 2.0x -> ~1.0x algorithmic); 8 or more -> map 0 (column tiles partitioned over the XCDs; maps 1 / 2 measure the same).
-  static const int map_env = getenv("ASX_TDF3_MAP") ? atoi(getenv("ASX_TDF3_MAP")) : -1;
+  const int map_env = knobs().tdf3_map;
   a.tile_map = map_env >= 0 ? (nbn >= 8 ? map_env % 10 : map_env / 10) : (nbn < 8 ? 1 : 0);
   // N = 384 exactly (the first TDF linear of level 0): ONE 8-wave workgroup per row block computes both 192-column halves from one x tile -- half the
   // x loads, splits and LDS stores per MFMA (kernels_gemm3.h, template parameter NW).  ASX_TDF3_NW8=0: A/B
   if constexpr (H && !PS && ABL == 0 && NREP == 3 && MREP == 8) {
-    static const bool nw8 = !(getenv("ASX_TDF3_NW8") && atoi(getenv("ASX_TDF3_NW8")) == 0);
-    if (nw8 && a.N == 384 && a.yexp == nullptr) {        // (a pair-image producer writes one exponent span per 192-column tile: the 4-wave form)
+    if (knobs().tdf3_nw8 && a.N == 384 && a.yexp == nullptr) {        // (a pair-image producer writes one exponent span per 192-column tile: the 4-wave form)
       hipLaunchKernelGGL((tdf3_kernel<3, 8, 0, false, true, false, 8>), dim3((unsigned)nbm), dim3(512), LDS_BYTES, s, a, w3, RowGather{});
       g_tdf3_launches.fetch_add(1);
       g_tdf3h_launches.fetch_add(1);
@@ -882,9 +795,8 @@ static bool launch_tdf3_gather_auto(asx_engine *e, const TdfDmaArgs &d, const Ro
 }
 template <int NREP, int MREP>
 static bool launch_tdf3(asx_engine *e, const TdfDmaArgs &a, hipStream_t s) {
-  static const int abl0 = getenv("ASX_TDF3_ABL") ? atoi(getenv("ASX_TDF3_ABL")) : 0;
-  // ASX_F16X3_N (bisection aid, kept: tools/debug_rof_race.py found the rotary-epilogue anomaly with it): fp16 x 3 on the launches with this N only (< 0: all but)
-  static const int only_n = getenv("ASX_F16X3_N") ? atoi(getenv("ASX_F16X3_N")) : 0;
+  // ASX_F16X3_N: a bisection aid, kept (tools/debug_rof_race.py found the rotary-epilogue anomaly with it)
+  const int abl0 = knobs().tdf3_abl, only_n = knobs().f16x3_n;
   const bool h = e->gemm_f16x3 > 0 && abl0 == 0 && (only_n == 0 || (only_n > 0 ? a.N == only_n : a.N != -only_n));
   const u32x4 *w3 = w3_image(e, a.w, a.N, a.K, s, 0, h ? 1 : 0);
   if (!w3) return false;                               // out of memory for the image: the caller falls back to the fp32 kernels
@@ -908,9 +820,8 @@ static bool launch_tdf3(asx_engine *e, const TdfDmaArgs &a, hipStream_t s) {
     return true;
   }
 #ifdef ASX_EXPERIMENTAL_KERNELS
-  static const int abl = getenv("ASX_TDF3_ABL") ? atoi(getenv("ASX_TDF3_ABL")) : 0;   // ablation builds exist for the 128 x 192 tile only
-  if constexpr (NREP == 3 && MREP == 8) {
-    switch (abl) {
+  if constexpr (NREP == 3 && MREP == 8) {   // ablation builds exist for the 128 x 192 tile only
+    switch (knobs().tdf3_abl) {
       case 1: launch_tdf3_abl<3, 8, 1>(a, w3, s); return true;
       case 2: launch_tdf3_abl<3, 8, 2>(a, w3, s); return true;
       case 4: launch_tdf3_abl<3, 8, 4>(a, w3, s); return true;
@@ -926,8 +837,8 @@ static bool launch_tdf3(asx_engine *e, const TdfDmaArgs &a, hipStream_t s) {
 
 // which tile form launch_tdf_dma_auto gives a layer on tdf3_kernel: 0 = not tdf3's (N <= 64 or tdf3_ok says no), 1 = 64 x 128, 2 = 128 x 128, 3 = 128 x 192
 static int tdf3_tile_form(const asx_engine *e, const TdfDmaArgs &d) {
-  static const int t128 = getenv("ASX_GEMM_T128") ? atoi(getenv("ASX_GEMM_T128")) : 1;
-  static const int small = getenv("ASX_TDF2_SMALL") ? atoi(getenv("ASX_TDF2_SMALL")) : 0;   // A/B: 64 x 128 tiles (3+ workgroups per CU) on short-K layers
+  const int t128 = knobs().gemm_t128;
+  const int small = knobs().tdf2_small;   // A/B: 64 x 128 tiles (3+ workgroups per CU) on short-K layers
   if (!tdf3_ok(e, d) || d.N <= 64) return 0;
   if (d.N <= 128) return 1;
   if ((small && d.K <= small) || d.prefer_small) return 1;
@@ -939,12 +850,12 @@ static int tdf3_tile_form(const asx_engine *e, const TdfDmaArgs &d) {
   // ASX_TDF3_EFF128: relative efficiency charged to the 128-column tile of the bf16 x 6 kernel.  Measured on the BS-Roformer and
   // HTDemucs linears: 0.96 / 0.85 / 0.75 -> 1251 / 1262 / 1262 ms and 30.5 / 30.4 / 30.5 ms per song -- no reason to move off
   // the fp32 kernel's figure (N = 512 stays on four 128-column tiles).
-  static const double eff128 = getenv("ASX_TDF3_EFF128") ? atof(getenv("ASX_TDF3_EFF128")) : 0.96;
+  const double eff128 = knobs().tdf3_eff128;
   // fp16 x 3: the 128-column tile needs 166 registers -- three workgroups per CU -- and measures as fast per MAC as the 192-column
   // one or faster on the SHORT-K shapes (BS-Roformer FF1 4.45 vs 4.74 ms, qkv 2.85 vs 3.28, HTDemucs linear 0.266 vs 0.328:
   // profiles/r05_gemm_f16x3.txt, "tile forms"): no handicap there.  Long K keeps it: the level-0 / level-1 first TDF linears
   // (K = 3072 / 1536) are 3 % / 35 % slower on the narrow tile.
-  const double e128 = (e->gemm_f16x3 > 0 && d.K <= 512 && !getenv("ASX_TDF3_EFF128")) ? 1.0 : eff128;
+  const double e128 = (e->gemm_f16x3 > 0 && d.K <= 512 && !knobs().tdf3_eff128_set) ? 1.0 : eff128;
   const bool narrow3 = t128 == 2 || (t128 == 1 && cost(128, e128) < cost(192, 1.0));
   return narrow3 ? 2 : 3;
 }
@@ -952,7 +863,7 @@ static int tdf3_tile_form(const asx_engine *e, const TdfDmaArgs &d) {
 // Will launch_tdf_dma_auto run this layer on the fp16 x 3 form of tdf3_kernel?  Only then may its x be a pair image, or its y be written as
 // one (TdfDmaArgs::xexp / yexp).  Builds (and caches) the layer's split weight image, so that the launch itself cannot fall back.
 static bool tdf3h_will_run(asx_engine *e, const TdfDmaArgs &d, hipStream_t s) {
-  static const bool dbg = getenv("ASX_TDF3_ABL") != nullptr || getenv("ASX_F16X3_N") != nullptr;   // bisection aids of launch_tdf3: no pair images with them
+  const bool dbg = knobs().tdf3_abl_set || knobs().f16x3_n_set;   // bisection aids of launch_tdf3: no pair images with them
   if (dbg || e->gemm_f16x3 <= 0 || e->pair_images <= 0 || tdf3_tile_form(e, d) == 0) return false;
   return w3_image(e, d.w, d.N, d.K, s, 0, 1) != nullptr;
 }
@@ -967,9 +878,9 @@ static void tdf3_set_xexp(TdfDmaArgs &d, const int *tab, int cols) {
 }
 
 static void launch_tdf_dma_auto(asx_engine *e, const TdfDmaArgs &d, hipStream_t s) {
-  static const int t128 = getenv("ASX_GEMM_T128") ? atoi(getenv("ASX_GEMM_T128")) : 1;
+  const int t128 = knobs().gemm_t128;
   const bool v2 = tdf2_ok(d);
-  static const int small = getenv("ASX_TDF2_SMALL") ? atoi(getenv("ASX_TDF2_SMALL")) : 0;
+  const int small = knobs().tdf2_small;
   const int form = tdf3_tile_form(e, d);
   if (form == 1 && d.N > 128 && launch_tdf3<2, 4>(e, d, s)) return;
   if (v2 && ((small && d.K <= small) || d.prefer_small) && d.N > 128) return launch_tdf2<2, 4>(d, s);
@@ -1009,7 +920,7 @@ static void tdf_fill_args(asx_engine *e, const TdfLayer &L, const float *x, cons
   d.C = L.c;
   d.T = T;
   d.relu = relu;
-  static const int nt_mode = getenv("ASX_NT") ? atoi(getenv("ASX_NT")) : 0;
+  const int nt_mode = knobs().nt;
   d.nt = ((nt_mode >> 1) & 1) | ((nt_mode >> 2) & 1) << 1;
 }
 
@@ -1032,7 +943,7 @@ static int tdf_launch(asx_engine *e, const TdfLayer &L, const float *x, const fl
   if (M <= 0) return ASX_OK;
   const double flops = 2.0 * (double)M * L.n * L.k;
   const double bytes = 4.0 * ((double)M * L.k + (double)M * L.n * (res ? 2 : 1) + (double)L.n * L.k);
-  const bool dma = (L.k % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && getenv("ASX_NO_DMA") == nullptr;
+  const bool dma = (L.k % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && !knobs().no_dma;
   TdfDmaArgs d;
   tdf_fill_args(e, L, x, res, y, M, T, relu, d);
   if (pair_out) {
@@ -1066,7 +977,7 @@ static int tdf_pair_launch(asx_engine *e, const TdfLayer &L0, const TdfLayer &L1
     TdfDmaArgs d0, d1;
     tdf_fill_args(e, L0, x, nullptr, H, M, T, 1, d0);
     tdf_fill_args(e, L1, H, x, out, M, T, 1, d1);
-    const bool al = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(H)) & 15) == 0 && getenv("ASX_NO_DMA") == nullptr;
+    const bool al = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(H)) & 15) == 0 && !knobs().no_dma;
     if (al && L0.n % 32 == 0 && L0.k % 4 == 0 && L1.k % 4 == 0 && tdf3h_will_run(e, d0, s) && tdf3h_will_run(e, d1, s)) {
       pair_cols = tdf3_tile_cols(e, d0);
       pair_tab = HE;
@@ -1138,8 +1049,7 @@ static int stft_launch(asx_engine *e, const float *wave, const int64_t *d_starts
     f.sign = sign;
     // ~16 frames per workgroup, in even shares: many short workgroups balance better over the CUs than two or three rounds
     // of long ones (measured: 8 / 16 frames 0.257 / 0.253 ms, 20 frames in exactly two rounds 0.368 ms)
-    static const int GS = getenv("ASX_FFT3_GS") ? std::max(1, atoi(getenv("ASX_FFT3_GS"))) : 16;
-    f.n_groups = std::max(1, T / GS);
+    f.n_groups = std::max(1, T / knobs().fft3_gs);
     return timed(e, ASX_PROF_STFT, 0.0, bytes, s, [&]() {
       if (e->fft3p)
         hipLaunchKernelGGL(f3::stft3p_kernel, dim3(f.n_groups, 2, B), dim3(256), f3::STFT3P_LDS_BYTES, s, f);
@@ -1191,8 +1101,7 @@ static int istft_ola_launch(asx_engine *e, const float *spec, int B, int T, int 
   }
   // >= 16 frames per workgroup, in even shares.  The grouping depends on T only: a hop on a seam is summed as
   // (tail partial) + (head partial), so results stay bit-identical whatever the batch size.
-  static const int G = getenv("ASX_FFT3_G") ? std::max(5, atoi(getenv("ASX_FFT3_G"))) : 16;
-  const int ng = std::max(1, T / G);
+  const int ng = std::max(1, T / knobs().fft3_g);
   CHK(e->seam3.ensure((size_t)B * 2 * ng * 2 * 5 * f3::HOP * 4));
   f3::Istft3Args f{};
   f.spec = spec;
@@ -1216,7 +1125,7 @@ static int istft_ola_launch(asx_engine *e, const float *spec, int B, int T, int 
     const bool aligned = e->cfg.dim_f % 4 == 0 && (reinterpret_cast<uintptr_t>(spec) & 15) == 0;
     if (e->fft3p && combine == 0 && aligned)
     {
-      static const int abl = getenv("ASX_ISTFT_ABL") ? atoi(getenv("ASX_ISTFT_ABL")) : 0;   // timing probes (results invalid)
+      const int abl = knobs().istft_abl;
       if (abl == 1) hipLaunchKernelGGL(f3::istft3p_kernel<1>, dim3(ng, 2, B), dim3(256), f3::ISTFT3P_LDS_BYTES, s, f);
       else if (abl == 2) hipLaunchKernelGGL(f3::istft3p_kernel<2>, dim3(ng, 2, B), dim3(256), f3::ISTFT3P_LDS_BYTES, s, f);
       else if (abl == 3) hipLaunchKernelGGL(f3::istft3p_kernel<3>, dim3(ng, 2, B), dim3(256), f3::ISTFT3P_LDS_BYTES, s, f);
@@ -1297,8 +1206,7 @@ static int block_forward(asx_engine *e, const Block &blk, float *&cur, float *de
   }
   // (A/B ASX_TDF_INPLACE=1: x + tdf(x) written over x where no skip copy is needed -- every output element depends on the
   // same element of x only)
-  static const bool inplace = getenv("ASX_TDF_INPLACE") && atoi(getenv("ASX_TDF_INPLACE")) != 0;
-  float *out = dest ? dest : (inplace ? cur : next_free(cur, nullptr));
+  float *out = dest ? dest : (knobs().tdf_inplace ? cur : next_free(cur, nullptr));
   CHK(tdf_pair_launch(e, blk.tdf0, blk.tdf1, cur, e->H.f(), reinterpret_cast<int *>(e->HE.p), out, M, blk.t, s));
   cur = out;
   return ASX_OK;

@@ -121,10 +121,7 @@ static int rof_load_lin_folded(asx_engine *e, RofLin &l, const std::string &name
 }
 
 // RMSNorms folded into the projections behind them (default; ASX_ROF_NORMFUSE=0 keeps the separate normalisation pass)
-static bool rof_norm_fuse() {
-  static const bool on = !(getenv("ASX_ROF_NORMFUSE") && atoi(getenv("ASX_ROF_NORMFUSE")) == 0);
-  return on;
-}
+static bool rof_norm_fuse() { return knobs().rof_normfuse; }
 
 // cos/sin table exactly as torch builds it: angle = float32(pos) * float32(freq) (one float32
 // rounding), then cos/sin of that float32 angle.
@@ -176,10 +173,7 @@ struct RofRot {
 
 // activation code of the feed-forward GELU: 2 = libm erff, 6 = fast_erf (kernels_net.h); ASX_ROF_GELU overrides (1 = ReLU: a timing
 // probe with wrong results)
-static int rof_gelu_act() {
-  static const int v = getenv("ASX_ROF_GELU") ? atoi(getenv("ASX_ROF_GELU")) : 2;
-  return v;
-}
+static int rof_gelu_act() { return knobs().rof_gelu; }
 
 static int rof_gemm_args(asx_engine *e, const RofLin &L, const float *x, int64_t lda, int64_t M, float *y, int64_t ldy,
                          int act, const float *res, int64_t ldr, const RofRot *rot, const float *rscale, TdfDmaArgs &d) {
@@ -259,18 +253,15 @@ static int rof_rownorm(asx_engine *e, const float *x, int64_t lda, int d, float 
 
 // the attention kernel the engine runs on sequences of length len (the variant asx_op_attention calls "auto")
 static int rof_attn_variant(const asx_engine *e, int len) {
-  static const bool attn_db = getenv("ASX_ATTN_DB") && atoi(getenv("ASX_ATTN_DB")) != 0;   // A/B (default off until measured)
-  static const int qw = getenv("ASX_ATTN_QW") ? atoi(getenv("ASX_ATTN_QW")) : 1;   // 2: 128 queries per workgroup (measured slower: 357 vs 328 ms)
+  const Knobs &k = knobs();
   // bf16 x 6 form (kernels_rof.h: attention6_kernel) under the process-wide switch of the row GEMM; ASX_ATTN6=0: A/B
-  static const bool attn6 = !(getenv("ASX_ATTN6") && atoi(getenv("ASX_ATTN6")) == 0);
-  if (attn6 && e->gemm_bf16x6 > 0) {
-    static const int qw6 = getenv("ASX_ATTN6_QW") ? atoi(getenv("ASX_ATTN6_QW")) : 2;   // 128 queries per workgroup on long sequences
+  if (k.attn6 && e->gemm_bf16x6 > 0) {
     const bool h3 = e->gemm_f16x3 > 0;           // fp16 x 3 arithmetic (kernels_rof.h: template parameter H)
-    if (qw6 >= 2 && len > 128) return h3 ? AV_ATTN6H_QW2 : AV_ATTN6_QW2;
+    if (k.attn6_qw >= 2 && len > 128) return h3 ? AV_ATTN6H_QW2 : AV_ATTN6_QW2;
     return h3 ? AV_ATTN6H : AV_ATTN6;
   }
-  if (qw >= 2 && len > 64) return AV_ATTN2_QW2;
-  if (attn_db && len > 128) return AV_ATTN2_DB;   // several key tiles: one barrier per tile (double-buffered K / V)
+  if (k.attn_qw >= 2 && len > 64) return AV_ATTN2_QW2;   // (measured slower: 357 vs 328 ms)
+  if (k.attn_db && len > 128) return AV_ATTN2_DB;   // several key tiles: one barrier per tile (double-buffered K / V)
   return AV_ATTN2;
 }
 
@@ -298,9 +289,8 @@ static int rof_transformer(asx_engine *e, std::vector<RofLayer> &layers, bool ti
       ain = n.XN.f();
     }
     // rotary on q and k: in the projection's epilogue (default), or as a separate in-place pass (ASX_ROF_FUSE=0)
-    static const bool fuse_rot = !(getenv("ASX_ROF_FUSE") && atoi(getenv("ASX_ROF_FUSE")) == 0);
     RofRot rr;
-    if (fuse_rot && c.dim_head % 4 == 0 && M < (1ll << 31)) {
+    if (knobs().rof_fuse && c.dim_head % 4 == 0 && M < (1ll << 31)) {
       rr.tab = reinterpret_cast<const float2 *>(L.attn.rot_tab.p);
       rr.cols = 2 * inner;
       rr.half = c.dim_head / 2;
@@ -349,14 +339,12 @@ static int rof_transformer(asx_engine *e, std::vector<RofLayer> &layers, bool ti
       aa.heads = H;
       aa.gate_ld = (H % 4 == 0) ? gl : H;
       aa.scale = 1.0f / sqrtf((float)c.dim_head);
-      static const int attn_exact = getenv("ASX_ATTN_EXACT") != nullptr;
-      aa.exact = attn_exact;
+      aa.exact = knobs().attn_exact;
       const int64_t nseq = rof_attn_geometry(aa, B, T, Fb, time_axis);
       const double fl = 4.0 * (double)nseq * H * (double)aa.len * aa.len * c.dim_head;
       CHK(timed(e, ASX_PROF_CONV1X1, fl, 4.0 * M * 4 * inner, s, [&]() {
 #ifdef ASX_EXPERIMENTAL_KERNELS
-        static const bool v1 = getenv("ASX_ATTN_V1") && atoi(getenv("ASX_ATTN_V1")) != 0;   // the 4-byte-fragment kernel (A/B)
-        if (v1) {
+        if (knobs().attn_v1) {
           hipLaunchKernelGGL(attention_kernel, dim3((aa.len + 63) / 64, H, (unsigned)nseq), dim3(256), 0, s, aa);
           return;
         }

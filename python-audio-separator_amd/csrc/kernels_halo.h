@@ -201,12 +201,11 @@ __global__ __launch_bounds__(256, (NREP <= 6 ? 3 : 2)) void hg_kernel(HgArgs a) 
 
 // N tile the halo kernel uses for n output columns (fewest padded columns; wider on ties)
 static inline int hg_tile_n(int n) {
-  static const int force = getenv("ASX_HALO_NT") ? atoi(getenv("ASX_HALO_NT")) : 0;
+  const int force = knobs().halo_nt;
   if (force == 32 || force == 64 || force == 96 || force == 128) return force;
   if (n <= 32) return 32;
   if (n <= 64) return 64;
-  static const bool split128 = getenv("ASX_HALO_SPLIT128") && atoi(getenv("ASX_HALO_SPLIT128")) != 0;   // A/B: 64-column tiles (3 workgroups per CU) where 128 would fit
-  if (split128 && n % 128 == 0) return 64;
+  if (knobs().halo_split128 && n % 128 == 0) return 64;   // A/B: three workgroups per CU
   const int p96 = (n + 95) / 96 * 96, p128 = (n + 127) / 128 * 128;
   return p96 <= p128 ? 96 : 128;
 }
@@ -260,11 +259,7 @@ template <int NREP, int KO>
 static void hg_launch(const HgArgs &a, int64_t nblocks, hipStream_t s) {
   const int WSUB = hg_wsub(16 * NREP);
   const int lds = (2 * a.inb + 2 * WSUB) * 4;
-  static int granted = 0;
-  if (lds > granted) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&hg_kernel<NREP, KO>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    granted = lds;
-  }
+  grant_lds(&hg_kernel<NREP, KO>, lds);
   hipLaunchKernelGGL((hg_kernel<NREP, KO>), dim3((unsigned)nblocks), dim3(256), lds, s, a);
 }
 

@@ -451,12 +451,7 @@ template <int NREP, int MREP, bool MS = false>
 static void ht_launch_gg(const GgArgs &a, hipStream_t s) {
   constexpr int BM = MS ? 64 * MREP : 16 * MREP, BN = MS ? 16 * NREP : 64 * NREP;
   constexpr int lds = 2 * (BM + BN) * 32 * 4;
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gg_kernel<NREP, MREP, MS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    once = true;
-  }
+  grant_lds(&gg_kernel<NREP, MREP, MS>, lds);
   const int64_t nbm = (a.M + BM - 1) / BM;
   const int nbn = (a.N + BN - 1) / BN;
   // a single-stage K loop (K <= 32: the DConv 1x1 -> 2C GEMMs of the outer levels) only ever touches LDS buffer 0: ask for half
@@ -469,8 +464,7 @@ static void ht_launch_gg(const GgArgs &a, hipStream_t s) {
 // glu: the launch runs a GLU epilogue (value / gate fragment pairs must sit in ONE wave: no 16- or 48-column tiles, and not
 // the 64-column tile whose four waves own 16 columns each)
 static inline int gg_tile_n(int n, bool glu = false) {
-  static const bool legacy = getenv("ASX_GG_LEGACY") != nullptr;
-  if (legacy && !glu) return n > 64 ? 128 : 64;
+  if (knobs().gg_legacy && !glu) return n > 64 ? 128 : 64;
   if (glu) {
     if (n <= 32) return 32;
     if (n <= 64) return 32;
@@ -486,7 +480,7 @@ static inline int gg_tile_n(int n, bool glu = false) {
 static void ht_gg_dispatch(const GgArgs &a, hipStream_t s) {
   // narrow outputs (N <= 48: DConv k3 -> C/8, small VR / encoder layers) are HBM-bound: 128-row tiles (37-45 KB of LDS, three to
   // four workgroups per CU) instead of 256-row tiles (70-78 KB, two) keep more loads in flight (ASX_GG_M128=0: the 256-row tiles)
-  static const bool m128 = !(getenv("ASX_GG_M128") && atoi(getenv("ASX_GG_M128")) == 0);
+  const bool m128 = knobs().gg_m128;
   switch (gg_tile_n(a.N, a.glu_rows != 0)) {
     case 16: m128 ? ht_launch_gg<1, 2, true>(a, s) : ht_launch_gg<1, 4, true>(a, s); break;
     case 32: m128 ? ht_launch_gg<2, 2, true>(a, s) : ht_launch_gg<2, 4, true>(a, s); break;

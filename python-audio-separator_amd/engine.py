@@ -274,7 +274,7 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_ht_standardize_dev", "asx_ht_bag_accumulate_dev", "asx_ht_bag_finish_dev", "asx_ensemble",
            "asx_ensemble_dev", "asx_invert_stem", "asx_normalize", "asx_normalize_dev", "asx_residual_dev",
            "asx_profile_launches", "asx_debug_trace", "asx_resample_sinc", "asx_resample_sinc_dev", "asx_counter",
-           "asx_set_stft_window", "asx_op_tdf_block", "asx_op_attention", "asx_op_mha"]
+           "asx_set_stft_window", "asx_op_tdf_block", "asx_op_attention", "asx_op_mha", "asx_get_option"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -350,6 +350,7 @@ def load_library():
     lib.asx_rof_demix.argtypes = [vp, _FP, i64, i64, _FP]
     lib.asx_rof_demix_dev.argtypes = [vp, vp, i64, i64, vp, vp]
     lib.asx_set_option.argtypes = [vp, C.c_char_p, i32]
+    lib.asx_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
     lib.asx_counter.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
     lib.asx_set_stft_window.argtypes = [vp, _FP, i32]
     lib.asx_ht_begin.argtypes = [vp, C.POINTER(_HtCfg)]
@@ -460,7 +461,6 @@ class Engine:
     def __init__(self, cfg: MDXConfig, device: int = 0):
         self._lib = load_library()
         self._h = C.c_void_p()
-        self._options = {}
         self.cfg = cfg
         self.device = device
         self.net_cfg = None
@@ -489,22 +489,12 @@ class Engine:
 
     def set_option(self, key: str, value: int):
         self._check(self._lib.asx_set_option(self._h, key.encode(), int(value)))
-        self._options[key] = (1 if int(value) > 0 else 0) if key in ("gemm_bf16x6", "gemm_f16x3", "gemm_pair_images", "conv_down_bf16x6", "conv_up_bf16x6") else max(0, int(value)) if key == "conv_direct_f16x3" else int(value)
 
     def option(self, key: str) -> int:
-        """Current value of an engine option (the library default when it was never set here)."""
-        defaults = {"winograd": max(0, int(os.environ.get("ASX_WINOGRAD", "3"))),
-                    "winograd_stationary": max(0, int(os.environ.get("ASX_WINOS", "0"))),
-                    "gemm_bf16x6": 1 if int(os.environ.get("ASX_GEMM_BF16X6", "1")) > 0 else 0,
-                    "gemm_f16x3": 1 if int(os.environ.get("ASX_GEMM_F16X3", "1")) > 0 else 0,
-                    "winograd_bf16x6": max(0, int(os.environ.get("ASX_WINO6", "144"))),
-                    "conv_direct_f16x3": max(0, int(os.environ.get("ASX_CONV3H", "144"))),
-                    "gemm_pair_images": 0,
-                    "conv_down_bf16x6": 1 if int(os.environ.get("ASX_DOWN6", "1")) > 0 else 0,
-                    "conv_up_bf16x6": 1 if int(os.environ.get("ASX_UP6", "1")) > 0 else 0}
-        if key not in defaults:
-            raise AsxError(f"unknown engine option {key!r} (known: {sorted(defaults)})")
-        return self._options.get(key, defaults[key])
+        """Current value of an engine option, as the library holds it (asx_get_option)."""
+        out = C.c_int32(0)
+        self._check(self._lib.asx_get_option(self._h, key.encode(), C.byref(out)))
+        return int(out.value)
 
     def counter(self, name: str) -> int:
         """A library launch counter (asx_counter): "tdf3_launches" = bf16x6 row-GEMM launches of this process, ..."""

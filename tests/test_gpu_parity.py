@@ -950,6 +950,41 @@ def test_separate_on_device_bit_exact_algebra(A):
         assert np.array_equal(secondary, ref_secondary)
 
 
+ONOFF_OPTIONS = ("gemm_bf16x6", "gemm_f16x3", "gemm_pair_images", "conv_down_bf16x6", "conv_up_bf16x6")
+COUNT_OPTIONS = ("winograd", "winograd_stationary", "winograd_bf16x6", "conv_direct_f16x3")
+
+
+def test_option_reads_the_library(A, monkeypatch):
+    """Engine.option is asx_get_option: the value the library holds after every set_option (normalised: on / off options to 0 / 1, the
+    others to >= 0; what only an experimental build carries is refused and changes nothing), and for an engine created with option
+    variables in the environment, which go through the same normaliser (in the default build a positive ASX_WINOGRAD means 3)."""
+    eng = A.Engine(small_cfg(A))
+    try:
+        eng.set_option("winograd", 1)
+        experimental = True
+    except A.AsxError:
+        experimental = False
+    for key in ONOFF_OPTIONS + COUNT_OPTIONS:
+        for v in (-1, 0, 1, 2, 144, 200):
+            before = eng.option(key)
+            if not experimental and v > 0 and (key in ("winograd_stationary", "gemm_pair_images") or key == "winograd" and v != 3):
+                with pytest.raises(A.AsxError, match="experimental"):
+                    eng.set_option(key, v)
+                assert eng.option(key) == before, (key, v)
+            else:
+                eng.set_option(key, v)
+                assert eng.option(key) == ((1 if v > 0 else 0) if key in ONOFF_OPTIONS else max(0, v)), (key, v)
+    with pytest.raises(A.AsxError, match="unknown option"):
+        eng.option("no_such_option")
+    eng.close()
+    monkeypatch.setenv("ASX_GEMM_F16X3", "0")
+    monkeypatch.setenv("ASX_WINOGRAD", "1")
+    fresh = A.Engine(small_cfg(A))
+    assert fresh.option("gemm_f16x3") == 0 and fresh.option("gemm_bf16x6") == 1
+    assert fresh.option("winograd") == (1 if experimental else 3)
+    fresh.close()
+
+
 def _set_or_skip(eng, key, value):
     """Options that name a superseded kernel generation exist in experimental builds only (python build.py --experimental): skip elsewhere."""
     import audio_separator_amd as A_
