@@ -194,6 +194,32 @@ int asx_separate(asx_engine *e, float *mix_host, int64_t n_samples, float max_pe
 int asx_separate_dev(asx_engine *e, float *mix_dev, int64_t n_samples, float max_peak, float min_peak,
                      int32_t has_min_peak, float compensate, float *primary_dev, float *secondary_dev, void *stream);
 
+/* A batch of songs in one call.  The chunks of all songs form one list that runs through the STFT / net / iSTFT launches in
+ * batches of up to max_batch chunks, whichever song a chunk belongs to: the launch count depends on the total chunk count, not on
+ * the number of songs (64 clips of 20 s are 6 net passes of 64 chunks, not 64 passes of 6).  One segmented fold then writes every
+ * song's out [2, n_samples]; each equals what asx_demix_dev writes for that song alone, bit for bit.  `songs` is a HOST array,
+ * read during the call; the mixes may have different lengths.  flags as for asx_demix_dev.  The chunk tables are built on the
+ * device from launch arguments: like asx_demix_chunks_dev the call only enqueues work on `stream`.  Nothing is enqueued when any
+ * song is invalid (null pointer, n_samples < 1); n_songs == 0 is ASX_OK.  The engine's chunk buffer grows to the pool's total
+ * chunk count (2 * chunk_size floats per chunk).  (Added within ABI 7: new functions and structs only.) */
+typedef struct asx_song {
+  const float *mix_dev;   /* [2, n_samples] */
+  float *out_dev;         /* [2, n_samples] */
+  int64_t n_samples;
+} asx_song;
+int asx_demix_batch_dev(asx_engine *e, const asx_song *songs, int32_t n_songs, uint32_t flags, void *stream);
+
+/* asx_separate_dev for a batch: per song its own peak, in-place normalise of mix_dev, primary = demix * peak,
+ * secondary = mix - compensate * primary ([n_samples, 2] each); all songs share ONE pooled demix as above. */
+typedef struct asx_song_stems {
+  float *mix_dev;         /* [2, n_samples], normalised in place */
+  float *primary_dev;     /* [n_samples, 2] */
+  float *secondary_dev;   /* [n_samples, 2] */
+  int64_t n_samples;
+} asx_song_stems;
+int asx_separate_batch_dev(asx_engine *e, const asx_song_stems *songs, int32_t n_songs, float max_peak, float min_peak,
+                           int32_t has_min_peak, float compensate, void *stream);
+
 /* ---- MDXC / TFC-TDF v3 (MDX23C): uvr_lib_v5/tfc_tdf_v3.py + the TFC branch of MDXCSeparator.demix ----
  * The engine's n_fft / hop_length / dim_f / segment_size (asx_mdx_config) are config.audio.* and
  * inference.dim_t (or the overridden segment size, mdxc_separator.py:354-359).

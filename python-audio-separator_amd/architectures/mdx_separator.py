@@ -132,3 +132,85 @@ class MDXSeparator(CommonSeparator):
             self.secondary_source = secondary
 
         return self._emit_pair(custom_output_names)
+
+    # ---- a batch of files in one pooled engine call -----------------------------------------------------------------
+    _PER_FILE = ("audio_file_path", "audio_file_base", "input_bit_depth", "input_subtype", "_file_seconds")
+
+    def _load_for_batch(self, path):
+        """One file as ``separate`` would load it: (device mix [2, N] or None, host mix or None) -- the device decoder when the
+        file allows it, else ``prepare_mix`` with the same refusals."""
+        self._reset_file_state()
+        self._begin_file(path)
+        if not self.invert_using_spec:
+            mix = self._device_mix(self.audio_file_path)
+            if mix is not None:
+                return mix, None
+        mix = self.prepare_mix(self.audio_file_path)
+        if mix.shape[0] != 2:
+            msg = f"Expected a 2-channel audio signal, but got {mix.shape[0]} channels"
+            self.logger.error(msg)
+            raise ValueError(msg)
+        return None, np.ascontiguousarray(mix, np.float32)
+
+    def separate_many(self, paths, custom_output_names=None):
+        """``separate`` for a list of files with ONE pooled engine call: every file is loaded as ``separate`` loads it, the
+        chunks of all of them share the net passes (``asx_separate_batch_dev``), then each file's stems go through the same
+        writer and naming code.  Returns one list of output names per input, in order; the files are byte-identical to those of
+        ``separate(path)`` called per path.
+
+        A file that cannot be used (unreadable, empty or silent, not stereo) fails alone, like the orchestrator's per-file
+        ``try``: its entry in the result is an empty list, the exception is logged and kept in ``self.batch_errors[index]``;
+        the other files are processed.  ``custom_output_names`` applies to every file, as it does in ``separate``."""
+        import torch
+        paths = list(paths)
+        self.batch_errors = {}
+        loaded = []                                       # (index, per-file state, device mix, host mix)
+        for i, path in enumerate(paths):
+            try:
+                dev_mix, host_mix = self._load_for_batch(path)
+            except Exception as e:                        # this file only
+                self.logger.error(f"{path}: {e}")
+                self.batch_errors[i] = e
+                continue
+            loaded.append((i, {k: getattr(self, k) for k in self._PER_FILE}, dev_mix, host_mix))
+        results = [[] for _ in paths]
+        if not loaded:
+            self._reset_file_state()
+            return results
+        self.initialize_model_settings()
+        if self.invert_using_spec:
+            stems = self._dm.separate_stems_many([h for _, _, _, h in loaded])
+        else:
+            dev = self._torch_device()
+            mixes = [d if d is not None else torch.from_numpy(h).to(dev) for _, _, d, h in loaded]
+            prim = [torch.empty((m.shape[1], 2), dtype=torch.float32, device=dev) for m in mixes]
+            sec = [torch.empty((m.shape[1], 2), dtype=torch.float32, device=dev) for m in mixes]
+            self.engine.separate_batch_dev([(m.data_ptr(), p.data_ptr(), s.data_ptr(), m.shape[1]) for m, p, s in zip(mixes, prim, sec)],
+                                           self.normalization_threshold, self.amplification_threshold, self.compensate,
+                                           stream=self._stream())
+            stems = list(zip(prim, sec))
+        self._in_separate = True
+        try:
+            for (i, state, dev_mix, _), (primary, secondary) in zip(loaded, stems):
+                self._reset_file_state()
+                for k, v in state.items():
+                    setattr(self, k, v)
+                if isinstance(primary, np.ndarray):
+                    self.primary_source, self.secondary_source = primary, secondary
+                elif dev_mix is not None:                 # decoded on the device: the stems stay there for the writer, as in separate()
+                    self.primary_source, self.secondary_source = self._host_stem(primary), self._host_stem(secondary)
+                    self._sync()
+                else:                                     # decoded on the host: host stems and the host writer, as in separate()
+                    self.primary_source, self.secondary_source = primary.cpu().numpy(), secondary.cpu().numpy()
+                try:
+                    results[i] = self._emit_pair(custom_output_names)
+                except Exception as e:
+                    self.logger.error(f"{state['audio_file_path']}: {e}")
+                    self.batch_errors[i] = e
+        except BaseException:
+            self._in_separate = False
+            self._drain_writes(raise_errors=False)
+            raise
+        self._in_separate = False
+        self._drain_writes()
+        return results

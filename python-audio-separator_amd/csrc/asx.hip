@@ -193,6 +193,10 @@ int asx_engine_create(int device, const asx_mdx_config *cfg, asx_engine **out) {
                                   f3::ISTFT3P_LDS_BYTES);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&f3::stft3p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   f3::STFT3P_LDS_BYTES);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&f3::stft3_pool_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  f3::STFT3_LDS_BYTES);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&f3::stft3p_pool_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  f3::STFT3P_LDS_BYTES);
         e->fft3 = true;
         e->fft3p = opts.fft3p;
         if ((rc = e->d_hann3.ensure((size_t)C * 8)) == ASX_OK) {
@@ -213,6 +217,8 @@ int asx_engine_create(int device, const asx_mdx_config *cfg, asx_engine **out) {
   }
   if (rc == ASX_OK) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)stft_lds(plan));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&stft_pool_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)stft_lds(plan));
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)istft_lds(plan));
@@ -296,6 +302,7 @@ void asx_engine_destroy(asx_engine *e) {
   e->d_peak.release();
   e->d_demixed.release();
   e->d_div.release();
+  for (DevBuf *b : {&e->pool_wave, &e->pool_nsong, &e->pool_songs, &e->pool_div, &e->pool_peak}) b->release();
   for (auto &sk : e->skip) sk.release();
   if (e->v3) v3_destroy(e->v3);
   if (e->rof) rof_destroy(e->rof);
@@ -667,6 +674,138 @@ int asx_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, float *out_dev
   return ASX_OK;
 }
 
+// ---- a batch of songs, their chunks pooled per launch ---------------------------------------------------------
+// The demix of n songs (validated by the caller) on device buffers: one chunk list over all songs, walked in batches of up to
+// pick_batch(e) chunks that may straddle songs -- the STFT / net / iSTFT launch count depends on the total chunk count only --
+// then one divider build per distinct length and ONE segmented fold.  Every buffer is sized before the first launch.
+static int demix_pool_dev(asx_engine *e, const float *const *mix, float *const *out, const int64_t *Ns, int n, uint32_t flags,
+                          hipStream_t s) {
+  const bool match = (flags & ASX_FLAG_MATCH_MIX) != 0;
+  const bool need_net = !match;
+  if (need_net && !e->net_ready) {
+    set_err("asx_demix: net weights not committed");
+    return ASX_ERR_STATE;
+  }
+  std::vector<asx_plan> plans((size_t)n);
+  std::vector<int> chunk0((size_t)n + 1, 0);
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    CHK(asx_plan_query(e, Ns[i], flags, &plans[i]));
+    total += plans[i].n_chunks;
+    REQUIRE(total < ((int64_t)1 << 30), "asx_demix_batch_dev: %lld chunks in one pool", (long long)total);
+    chunk0[i + 1] = (int)total;
+  }
+  const int nk = (int)total;
+  const asx_plan &p0 = plans[0];                       // chunk geometry (everything but N, pad, padded_len, n_chunks) is the engine's
+  const int64_t C = p0.chunk_size;
+  const int T = e->cfg.segment_size;
+  const bool win = windowed_mode(e, flags);
+  const double *hann = (e->fft3 && e->d_hann3.p) ? reinterpret_cast<const double *>(e->d_hann3.p) : nullptr;
+  const int maxB = pick_batch(e);
+  const int nbatch = (nk + maxB - 1) / maxB;
+  const int per = (nk + nbatch - 1) / nbatch;
+  // dividers: one table per distinct length, 16-byte aligned slots
+  std::map<int64_t, int64_t> div_off;                  // N -> floats into pool_div
+  int64_t div_floats = 0;
+  for (int i = 0; i < n; ++i)
+    if (div_off.emplace(Ns[i], div_floats).second) div_floats += (Ns[i] + 3) / 4 * 4;
+  CHK(ensure_workspace(e, per, need_net));
+  CHK(e->d_starts.ensure((size_t)nk * 8));
+  CHK(e->d_nact.ensure((size_t)nk * 8));
+  CHK(e->pool_wave.ensure((size_t)nk * 8));
+  CHK(e->pool_nsong.ensure((size_t)nk * 8));
+  CHK(e->pool_songs.ensure((size_t)n * sizeof(PoolSong)));
+  CHK(e->pool_div.ensure((size_t)div_floats * 4));
+  CHK(e->chunk_out.ensure((size_t)nk * 2 * C * 4));
+  if (e->fft3) CHK(e->seam3.ensure((size_t)per * 2 * std::max(1, T / knobs().fft3_g) * 2 * 5 * f3::HOP * 4));   // istft_ola_launch's, for the largest batch
+  float *chunks = e->chunk_out.f();
+  const bool geom4 = knobs().finalize4 && C % 4 == 0 && p0.step % 4 == 0 && p0.trim % 4 == 0;
+  // tables
+  int64_t blk = 0;
+  for (int g0 = 0; g0 < n; g0 += POOL_GROUP) {
+    PoolGroup g{};
+    g.n_songs = std::min(POOL_GROUP, n - g0);
+    g.song0 = g0;
+    for (int i = 0; i < g.n_songs; ++i) {
+      const int sidx = g0 + i;
+      g.mix[i] = mix[sidx];
+      g.out[i] = out[sidx];
+      g.n[i] = Ns[sidx];
+      g.div_off[i] = div_off[Ns[sidx]];
+      g.chunk0[i] = chunk0[sidx];
+      // the vector path of asx_finalize_dev, under its conditions, per song
+      g.vec[i] = (geom4 && Ns[sidx] % 4 == 0 && (((uintptr_t)(chunks + (size_t)chunk0[sidx] * 2 * C) | (uintptr_t)out[sidx]) & 15) == 0) ? 1 : 0;
+      g.blk0[i] = blk;
+      blk += ((g.vec[i] ? Ns[sidx] / 4 : Ns[sidx]) + 255) / 256;
+    }
+    g.chunk0[g.n_songs] = chunk0[g0 + g.n_songs];
+    const int nthr = g.chunk0[g.n_songs] - g.chunk0[0];
+    hipLaunchKernelGGL(pool_table_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, g, p0.step, C, (int)p0.trim, p0.gen_size,
+                       win ? 1 : 0, chunks, e->pool_div.f(), reinterpret_cast<const float **>(e->pool_wave.p),
+                       reinterpret_cast<int64_t *>(e->pool_nsong.p), reinterpret_cast<int64_t *>(e->d_starts.p),
+                       reinterpret_cast<int64_t *>(e->d_nact.p), reinterpret_cast<PoolSong *>(e->pool_songs.p));
+    HIPCHK(hipGetLastError());
+  }
+  REQUIRE(blk < ((int64_t)1 << 31), "asx_demix_batch_dev: %lld samples in one pool", (long long)blk * 256);
+  // chunks
+  const size_t spec_elems = (size_t)4 * T * e->cfg.dim_f;
+  for (int b0 = 0; b0 < nk; b0 += per) {
+    const int B = std::min(per, nk - b0);
+    const int64_t *ds = reinterpret_cast<const int64_t *>(e->d_starts.p) + b0;
+    const int64_t *dn = reinterpret_cast<const int64_t *>(e->d_nact.p) + b0;
+    const PoolChunks pc{reinterpret_cast<const float *const *>(e->pool_wave.p) + b0, reinterpret_cast<const int64_t *>(e->pool_nsong.p) + b0};
+    CHK(stft_launch(e, nullptr, ds, 0, B, C, T, e->spec_in.f(), 1, 3, 1.0f, s, &pc));
+    const float *spec_final = e->spec_in.f();
+    int combine = 0;
+    if (need_net) {
+      int Bn = B;
+      if (e->cfg.enable_denoise) {
+        CHK(stft_launch(e, nullptr, ds, 0, B, C, T, e->spec_in.f() + (size_t)B * spec_elems, 1, 3, -1.0f, s, &pc));
+        Bn = 2 * B;
+        combine = B;
+      }
+      CHK(net_forward_dev(e, e->spec_in.f(), e->spec_out.f(), Bn, s));
+      spec_final = e->spec_out.f();
+    }
+    CHK(istft_ola_launch(e, spec_final, B, T, combine, dn, C, chunks + (size_t)b0 * 2 * C, s));
+  }
+  // fold
+  for (int i = 0; i < n; ++i) {
+    const auto it = div_off.find(Ns[i]);
+    if (it->second < 0) continue;                      // built for an earlier song of this length
+    const asx_plan &p = plans[i];
+    float *dv = e->pool_div.f() + it->second;
+    CHK(timed(e, ASX_PROF_MISC, 0.0, 4.0 * p.n_samples, s, [&]() {
+      hipLaunchKernelGGL(finalize_div_kernel, dim3((unsigned)((p.n_samples + 255) / 256)), dim3(256), 0, s, p.n_chunks, p.chunk_size, p.step,
+                         p.padded_len, p.trim, p.n_samples, win ? 1 : 0, dv, hann);
+    }));
+    it->second = -1;
+  }
+  double bytes = 0.0;
+  for (int i = 0; i < n; ++i) bytes += 4.0 * ((double)plans[i].n_chunks * 2 * C + 3.0 * Ns[i]);
+  return timed(e, ASX_PROF_FINALIZE, 0.0, bytes, s, [&]() {
+    hipLaunchKernelGGL(finalize_pool_kernel, dim3((unsigned)blk, 2), dim3(256), 0, s, reinterpret_cast<const PoolSong *>(e->pool_songs.p), n, C,
+                       p0.step, (int)p0.trim);
+  });
+}
+
+int asx_demix_batch_dev(asx_engine *e, const asx_song *songs, int32_t n_songs, uint32_t flags, void *stream) {
+  REQUIRE(e && n_songs >= 0 && (songs || n_songs == 0), "asx_demix_batch_dev: null argument");
+  if (n_songs == 0) return ASX_OK;
+  std::vector<const float *> mix((size_t)n_songs);
+  std::vector<float *> out((size_t)n_songs);
+  std::vector<int64_t> Ns((size_t)n_songs);
+  for (int i = 0; i < n_songs; ++i) {                  // nothing is enqueued unless every song is valid
+    REQUIRE(songs[i].mix_dev && songs[i].out_dev, "asx_demix_batch_dev: null pointer in song %d", i);
+    REQUIRE(songs[i].n_samples >= 1, "asx_demix_batch_dev: song %d: n_samples must be >= 1", i);
+    mix[i] = songs[i].mix_dev;
+    out[i] = songs[i].out_dev;
+    Ns[i] = songs[i].n_samples;
+  }
+  HIPCHK(hipSetDevice(e->device));
+  return demix_pool_dev(e, mix.data(), out.data(), Ns.data(), n_songs, flags, reinterpret_cast<hipStream_t>(stream));
+}
+
 int asx_demix(asx_engine *e, const float *mix_host, int64_t N, float *out_host, uint32_t flags) {
   REQUIRE(e && mix_host && out_host, "asx_demix: null argument");
   REQUIRE(N >= 1, "n_samples must be >= 1");
@@ -716,6 +855,54 @@ int asx_separate_dev(asx_engine *e, float *mix_dev, int64_t N, float max_peak, f
     hipLaunchKernelGGL(stems_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, e->d_demixed.f(), mix_dev, N,
                        pk, compensate, primary_dev, secondary_dev);
   }));
+  return ASX_OK;
+}
+
+// asx_separate_dev per song around ONE pooled demix: each song's own peak word, in-place normalise and stem algebra
+int asx_separate_batch_dev(asx_engine *e, const asx_song_stems *songs, int32_t n_songs, float max_peak, float min_peak,
+                           int32_t has_min, float compensate, void *stream) {
+  REQUIRE(e && n_songs >= 0 && (songs || n_songs == 0), "asx_separate_batch_dev: null argument");
+  if (n_songs == 0) return ASX_OK;
+  std::vector<const float *> mix((size_t)n_songs);
+  std::vector<float *> dem((size_t)n_songs);
+  std::vector<int64_t> Ns((size_t)n_songs), off((size_t)n_songs);
+  int64_t floats = 0;
+  for (int i = 0; i < n_songs; ++i) {
+    REQUIRE(songs[i].mix_dev && songs[i].primary_dev && songs[i].secondary_dev, "asx_separate_batch_dev: null pointer in song %d", i);
+    REQUIRE(songs[i].n_samples >= 1, "asx_separate_batch_dev: song %d: n_samples must be >= 1", i);
+    Ns[i] = songs[i].n_samples;
+    off[i] = floats;
+    floats += (2 * Ns[i] + 3) / 4 * 4;                 // 16-byte aligned slots, like a buffer of its own
+  }
+  if (!e->net_ready) {
+    set_err("asx_demix: net weights not committed");
+    return ASX_ERR_STATE;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  CHK(e->pool_peak.ensure((size_t)n_songs * 4));
+  CHK(e->d_demixed.ensure((size_t)floats * 4));
+  unsigned int *pk = reinterpret_cast<unsigned int *>(e->pool_peak.p);
+  HIPCHK(hipMemsetAsync(pk, 0, (size_t)n_songs * 4, s));
+  for (int i = 0; i < n_songs; ++i) {
+    const int64_t n2 = 2 * Ns[i];
+    const unsigned nb = (unsigned)std::min<int64_t>((n2 + 255) / 256, 2048);
+    float *m = songs[i].mix_dev;
+    CHK(timed(e, ASX_PROF_MISC, 0.0, 4.0 * n2, s, [&]() { hipLaunchKernelGGL(absmax_kernel, dim3(nb), dim3(256), 0, s, m, n2, pk + i); }));
+    CHK(timed(e, ASX_PROF_MISC, 0.0, 8.0 * n2, s, [&]() {
+      hipLaunchKernelGGL(normalize_kernel, dim3(nb), dim3(256), 0, s, m, n2, pk + i, max_peak, min_peak, has_min);
+    }));
+    mix[i] = m;
+    dem[i] = e->d_demixed.f() + off[i];
+  }
+  CHK(demix_pool_dev(e, mix.data(), dem.data(), Ns.data(), n_songs, 0, s));
+  for (int i = 0; i < n_songs; ++i) {
+    const int64_t N = Ns[i];
+    CHK(timed(e, ASX_PROF_MISC, 0.0, 4.0 * 4 * 2 * N, s, [&]() {
+      hipLaunchKernelGGL(stems_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, dem[i], songs[i].mix_dev, N, pk + i, compensate,
+                         songs[i].primary_dev, songs[i].secondary_dev);
+    }));
+  }
   return ASX_OK;
 }
 

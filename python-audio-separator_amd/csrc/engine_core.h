@@ -168,6 +168,9 @@ struct asx_engine {
   // workspace
   int ws_batch = 0;  // chunks the workspace is sized for
   DevBuf spec_in, spec_out, R[3], H, HE, frames, chunk_out, d_starts, d_nact, d_peak, d_demixed;
+  // a pool of songs (asx_demix_batch_dev / asx_separate_batch_dev): per-chunk song table (base pointer, length) beside d_starts / d_nact,
+  // the per-song fold table (PoolSong), the dividers of the distinct song lengths, one peak word per song
+  DevBuf pool_wave, pool_nsong, pool_songs, pool_div, pool_peak;
   DevBuf gn_part;    // per-plane float64 (sum, sum of squares) of the GroupNorm variant of the net (asx_net_config.norm == 1)
   DevBuf d_div;      // divider of the chunk fold for div_key's plan (input-independent: built once, asx_finalize_dev)
   DivKey div_key;

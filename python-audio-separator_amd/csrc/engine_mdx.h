@@ -1011,8 +1011,9 @@ static int tdf_pack(TdfLayer &L, int n, int k, int c, const float *w, const floa
 // ----------------------------------------------------------------------------
 // STFT / iSTFT launch helpers (device buffers)
 // ----------------------------------------------------------------------------
+// pc != nullptr: a pool of songs -- chunk b reads the song pc->wave[b] / pc->n_song[b] (`wave` / `n_song` unused; the *_pool_kernel twins)
 static int stft_launch(asx_engine *e, const float *wave, const int64_t *d_starts, int64_t n_song, int B, int64_t C,
-                       int T, float *spec, int tf_layout, int zero_low, float sign, hipStream_t s) {
+                       int T, float *spec, int tf_layout, int zero_low, float sign, hipStream_t s, const PoolChunks *pc = nullptr) {
   StftArgs a{};
   a.wave = wave;
   a.chunk_start = d_starts;
@@ -1051,14 +1052,19 @@ static int stft_launch(asx_engine *e, const float *wave, const int64_t *d_starts
     // of long ones (measured: 8 / 16 frames 0.257 / 0.253 ms, 20 frames in exactly two rounds 0.368 ms)
     f.n_groups = std::max(1, T / knobs().fft3_gs);
     return timed(e, ASX_PROF_STFT, 0.0, bytes, s, [&]() {
-      if (e->fft3p)
+      if (pc && e->fft3p)
+        hipLaunchKernelGGL(f3::stft3p_pool_kernel, dim3(f.n_groups, 2, B), dim3(256), f3::STFT3P_LDS_BYTES, s, f, *pc);
+      else if (pc)
+        hipLaunchKernelGGL(f3::stft3_pool_kernel, dim3(T, 2, B), dim3(256), f3::STFT3_LDS_BYTES, s, f, *pc);
+      else if (e->fft3p)
         hipLaunchKernelGGL(f3::stft3p_kernel, dim3(f.n_groups, 2, B), dim3(256), f3::STFT3P_LDS_BYTES, s, f);
       else
         hipLaunchKernelGGL(f3::stft3_kernel, dim3(T, 2, B), dim3(256), f3::STFT3_LDS_BYTES, s, f);
     });
   }
   return timed(e, ASX_PROF_STFT, 0.0, bytes, s, [&]() {
-    hipLaunchKernelGGL(stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p);
+    if (pc) hipLaunchKernelGGL(stft_pool_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p, *pc);
+    else hipLaunchKernelGGL(stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p);
   });
 }
 

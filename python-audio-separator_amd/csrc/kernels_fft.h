@@ -202,70 +202,21 @@ struct StftArgs {
   int64_t out_bstride;        // floats between batch items of spec (tf_layout only); 0 = dense
 };
 
+// A pool of songs (asx_demix_batch_dev): chunk b of a launch reads ITS song -- base pointer and length per chunk, beside the
+// chunk_start table (the *_pool_kernel twins of the three STFT kernels put them in place of the launch's `wave` / `n_song`).
+struct PoolChunks {
+  const float *const *wave;   // [B] the [2, N_s] mix of the song chunk b belongs to
+  const int64_t *n_song;      // [B] N_s
+};
+
 __global__ __launch_bounds__(256) void stft_kernel(StftArgs a, FftPlan p) {
-  extern __shared__ float2 lds[];
-  float2 *bufA = lds;
-  float2 *bufB = lds + p.nh;
-  const int t = blockIdx.x, ch = blockIdx.y, b = blockIdx.z;
-  const int half = p.nh;  // n_fft / 2
-  const int64_t C = a.C;
-  const float *src;
-  int64_t cstart = 0;
-  if (a.n_song >= 0) {
-    src = a.wave + (int64_t)ch * a.n_song;
-    cstart = a.chunk_start[b];
-  } else {
-    src = a.wave + ((int64_t)b * 2 + ch) * C;
-  }
-  // load + window; LDS float pairs (x[2m], x[2m+1]) are the packed complex input
-  float *fa = reinterpret_cast<float *>(bufA);
-  for (int e = threadIdx.x; e < p.n_fft; e += blockDim.x) {
-    int64_t q = (int64_t)t * a.hop + e - half;
-    if (q < 0) q = -q;
-    if (q >= C) q = 2 * (C - 1) - q;
-    float v;
-    if (a.n_song >= 0) {
-      const int64_t j = cstart + q - a.trim;  // index into the un-padded mix
-      v = (j >= 0 && j < a.n_song) ? src[j] : 0.0f;
-    } else {
-      v = src[q];
-    }
-    fa[e] = v * a.window[e];
-  }
-  float2 *Z = fft_lds<-1>(bufA, bufB, p, a.tw);
-  // split: X[k] = E + e^{-2 pi i k / n} * O,  E = (Z[k] + conj Z[Nh-k]) / 2,  O = -i (Z[k] - conj Z[Nh-k]) / 2
-  const int nh = p.nh;
-  for (int k = threadIdx.x; k < a.dim_f; k += blockDim.x) {
-    float re = 0.f, im = 0.f;
-    if (k >= a.zero_low) {
-      const float2 zk = Z[k == nh ? 0 : k];
-      float2 zc = Z[(k == 0 || k == nh) ? 0 : nh - k];
-      zc.y = -zc.y;
-      const float2 E = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y));
-      const float2 D = make_float2(0.5f * (zk.x - zc.x), 0.5f * (zk.y - zc.y));
-      const float2 O = make_float2(D.y, -D.x);
-      float2 w = (k == nh) ? make_float2(-1.f, 0.f) : a.tw[k];
-      const float2 X = cadd(E, cmul(w, O));
-      re = X.x * a.sign;
-      im = X.y * a.sign;
-    }
-    if (a.tf_layout == 2) {
-      // BS-Roformer: b t (f s c) -- frequency-major with the stereo channel interleaved (bs_roformer.py:455-459)
-      reinterpret_cast<float2 *>(a.spec)[(((int64_t)b * a.T + t) * a.dim_f + k) * 2 + ch] = make_float2(re, im);
-    } else if (a.tf_layout) {
-      const int kb = a.subbands > 1 ? a.subbands : 1;
-      const int fs = a.dim_f / kb;
-      const int j = k / fs, fp = k - j * fs;
-      const int64_t bst = a.out_bstride ? a.out_bstride : (int64_t)4 * a.T * a.dim_f;
-      const int64_t base = (int64_t)b * bst + (((int64_t)(ch * 2) * kb + j) * a.T + t) * fs + fp;
-      a.spec[base] = re;
-      a.spec[base + (int64_t)kb * a.T * fs] = im;
-    } else {
-      const int64_t base = (((int64_t)b * 4 + ch * 2) * a.dim_f + k) * a.T + t;
-      a.spec[base] = re;
-      a.spec[base + (int64_t)a.dim_f * a.T] = im;
-    }
-  }
+#include "stft_body.inc.h"
+}
+// (the body is a textual include, not a device function: the one-song kernel must stay the code object it was -- an inlined body compiles to other registers and schedules)
+__global__ __launch_bounds__(256) void stft_pool_kernel(StftArgs a, FftPlan p, PoolChunks pc) {
+  a.wave = pc.wave[blockIdx.z];
+  a.n_song = pc.n_song[blockIdx.z];
+#include "stft_body.inc.h"
 }
 
 // ---------------------------------------------------------------------------
@@ -499,6 +450,127 @@ __global__ __launch_bounds__(256) void finalize4_kernel(const float *__restrict_
     *reinterpret_cast<float4 *>(o) = r;
   } else {
     for (int e = 0; e < 4 && i + e < N; ++e) o[e] = acc[e] / divider[i + e];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// A pool of songs (asx_demix_batch_dev): the chunks of all songs stand one after the other in one chunk buffer and go
+// through the STFT / net / iSTFT launches in batches that may straddle songs.  Per-song are only the tables below, built
+// on the device from launch arguments (no host copy: the call stays stream-ordered and capturable), and the fold.
+// ---------------------------------------------------------------------------
+struct PoolSong {             // fold table, one entry per song
+  const float *chunks;        // the song's windowed chunks [n_chunks, 2, C] inside the pooled chunk buffer
+  float *out;                 // [2, N]
+  const float *divider;       // [N] built by finalize_div_kernel for this song's plan
+  int64_t N, L;               // samples, padded length
+  int64_t blk0;               // first workgroup (x) of the song in finalize_pool_kernel's grid
+  int n_chunks;
+  int vec;                    // 1: four samples per thread (finalize4_kernel's conditions hold for this song)
+};
+
+constexpr int POOL_GROUP = 32;
+struct PoolGroup {            // up to POOL_GROUP songs, by value in the launch arguments
+  const float *mix[POOL_GROUP];
+  float *out[POOL_GROUP];
+  int64_t n[POOL_GROUP];
+  int64_t div_off[POOL_GROUP];     // floats into the divider buffer
+  int64_t blk0[POOL_GROUP];
+  int chunk0[POOL_GROUP + 1];      // first pooled chunk of each song (+ the end of the last)
+  int vec[POOL_GROUP];
+  int n_songs, song0;              // songs in this group, pool index of its first
+};
+
+// chunk j of the pool: its song (base pointer, length), its start inside that song's padded domain, its active length
+// (chunk_table_kernel's values per song); thread i < n_songs also writes the fold entry of song song0 + i.
+__global__ __launch_bounds__(256) void pool_table_kernel(PoolGroup g, int64_t step, int64_t C, int trim, int64_t gen, int win,
+                                                         const float *chunk_buf, const float *div_buf,
+                                                         const float **__restrict__ wave, int64_t *__restrict__ n_song,
+                                                         int64_t *__restrict__ starts, int64_t *__restrict__ nact,
+                                                         PoolSong *__restrict__ songs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < g.n_songs) {
+    PoolSong ps;
+    const int64_t N = g.n[i];
+    ps.chunks = chunk_buf + (int64_t)g.chunk0[i] * 2 * C;
+    ps.out = g.out[i];
+    ps.divider = div_buf + g.div_off[i];
+    ps.N = N;
+    ps.L = trim + N + (gen + trim - N % gen);
+    ps.blk0 = g.blk0[i];
+    ps.n_chunks = g.chunk0[i + 1] - g.chunk0[i];
+    ps.vec = g.vec[i];
+    songs[g.song0 + i] = ps;
+  }
+  const int j = g.chunk0[0] + i;
+  if (j >= g.chunk0[g.n_songs]) return;
+  int sg = 0;
+  while (sg + 1 < g.n_songs && g.chunk0[sg + 1] <= j) ++sg;
+  const int64_t N = g.n[sg];
+  const int64_t L = trim + N + (gen + trim - N % gen);
+  const int64_t st = (int64_t)(j - g.chunk0[sg]) * step;
+  const int64_t na = C < L - st ? C : L - st;
+  wave[j] = g.mix[sg];
+  n_song[j] = N;
+  starts[j] = st;
+  nact[j] = win ? na : -1;
+}
+
+// K4/K5 for every song of a pool in one launch: grid.x = the songs' workgroups one after the other (PoolSong::blk0), grid.y = channel.
+// Per sample the sums of finalize_kernel / finalize4_kernel (covering chunks in increasing k) divided by the song's table
+// value (finalize_div_kernel: finalize_kernel's own accumulation) -> what asx_finalize_dev writes for the song alone.
+__global__ __launch_bounds__(256) void finalize_pool_kernel(const PoolSong *__restrict__ songs, int n_songs, int64_t C, int64_t step,
+                                                            int trim) {
+  int lo = 0, hi = n_songs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (songs[mid].blk0 <= (int64_t)blockIdx.x) lo = mid;
+    else hi = mid - 1;
+  }
+  const PoolSong sg = songs[lo];
+  const int ch = blockIdx.y;
+  const int64_t N = sg.N, L = sg.L;
+  const float *__restrict__ chunk_out = sg.chunks;
+  const int64_t t = ((int64_t)blockIdx.x - sg.blk0) * blockDim.x + threadIdx.x;
+  const int64_t i = sg.vec ? t * 4 : t;
+  if (i >= N) return;
+  const int64_t m = i + trim;
+  int64_t k_hi = m / step;
+  if (k_hi > sg.n_chunks - 1) k_hi = sg.n_chunks - 1;
+  int64_t k_lo = 0;
+  if (m - C >= 0) k_lo = (m - C) / step + 1;
+  float *o = sg.out + (int64_t)ch * N + i;
+  if (sg.vec) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t k = k_lo; k <= k_hi; ++k) {
+      const int64_t s = k * step;
+      const int64_t j = m - s;
+      int64_t na = L - s;
+      if (na > C) na = C;
+      if (j >= na) continue;
+      const float4 v = *reinterpret_cast<const float4 *>(chunk_out + (k * 2 + ch) * C + j);
+      acc[0] += v.x;
+      if (j + 1 < na) acc[1] += v.y;
+      if (j + 2 < na) acc[2] += v.z;
+      if (j + 3 < na) acc[3] += v.w;
+    }
+    const float4 d = *reinterpret_cast<const float4 *>(sg.divider + i);   // vec: N % 4 == 0, so i + 4 <= N
+    float4 r;
+    r.x = acc[0] / d.x;
+    r.y = acc[1] / d.y;
+    r.z = acc[2] / d.z;
+    r.w = acc[3] / d.w;
+    *reinterpret_cast<float4 *>(o) = r;
+  } else {
+    float acc = 0.f;
+    for (int64_t k = k_lo; k <= k_hi; ++k) {
+      const int64_t s = k * step;
+      const int64_t j = m - s;
+      int64_t na = L - s;
+      if (na > C) na = C;
+      if (j >= na) continue;
+      acc += chunk_out[(k * 2 + ch) * C + j];
+    }
+    *o = acc / sg.divider[i];
   }
 }
 

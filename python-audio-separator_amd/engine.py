@@ -274,7 +274,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_ht_standardize_dev", "asx_ht_bag_accumulate_dev", "asx_ht_bag_finish_dev", "asx_ensemble",
            "asx_ensemble_dev", "asx_invert_stem", "asx_normalize", "asx_normalize_dev", "asx_residual_dev",
            "asx_profile_launches", "asx_debug_trace", "asx_resample_sinc", "asx_resample_sinc_dev", "asx_counter",
-           "asx_set_stft_window", "asx_op_tdf_block", "asx_op_attention", "asx_op_mha", "asx_get_option"]
+           "asx_set_stft_window", "asx_op_tdf_block", "asx_op_attention", "asx_op_mha", "asx_get_option",
+           "asx_demix_batch_dev", "asx_separate_batch_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -283,6 +284,14 @@ ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2",
 
 class _LaunchRec(C.Structure):     # struct asx_launch_rec
     _fields_ = [("cls", C.c_int32), ("ms", C.c_float), ("flops", C.c_double), ("bytes", C.c_double)]
+
+
+class _Song(C.Structure):          # struct asx_song
+    _fields_ = [("mix_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_samples", C.c_int64)]
+
+
+class _SongStems(C.Structure):     # struct asx_song_stems
+    _fields_ = [("mix_dev", C.c_void_p), ("primary_dev", C.c_void_p), ("secondary_dev", C.c_void_p), ("n_samples", C.c_int64)]
 
 
 def load_library():
@@ -324,6 +333,8 @@ def load_library():
     f32 = C.c_float
     lib.asx_separate.argtypes = [vp, _FP, i64, f32, f32, i32, f32, _FP, _FP]
     lib.asx_separate_dev.argtypes = [vp, vp, i64, f32, f32, i32, f32, vp, vp, vp]
+    lib.asx_demix_batch_dev.argtypes = [vp, C.POINTER(_Song), i32, u32, vp]
+    lib.asx_separate_batch_dev.argtypes = [vp, C.POINTER(_SongStems), i32, f32, f32, i32, f32, vp]
     lib.asx_stft.argtypes = [vp, _FP, i32, i64, _FP]
     lib.asx_istft.argtypes = [vp, _FP, i32, i32, _FP]
     lib.asx_net_forward.argtypes = [vp, _FP, i32, _FP]
@@ -1038,6 +1049,75 @@ class Engine:
                                                float(min_peak) if min_peak is not None else 0.0,
                                                int(min_peak is not None), float(compensate), primary_ptr,
                                                secondary_ptr, stream or None))
+
+    # -- a batch of songs in one call: the chunks of all of them pooled per launch ------------------------------------
+    def demix_batch_dev(self, songs, is_match_mix: bool = False, stream: int = 0):
+        """``songs``: a list of ``(mix_ptr, out_ptr, n_samples)`` -- device pointers to float32 [2, n_samples] each.  Every
+        ``out`` equals what ``demix_dev`` writes for that song alone, bit for bit (asx_demix_batch_dev)."""
+        songs = list(songs)
+        arr = (_Song * max(1, len(songs)))()
+        for i, (mix_ptr, out_ptr, n) in enumerate(songs):
+            arr[i] = _Song(mix_ptr or None, out_ptr or None, int(n))
+        self._check(self._lib.asx_demix_batch_dev(self._h, arr, len(songs), ASX_FLAG_MATCH_MIX if is_match_mix else 0,
+                                                  stream or None))
+
+    def separate_batch_dev(self, songs, max_peak: float, min_peak, compensate: float, stream: int = 0):
+        """``songs``: a list of ``(mix_ptr, primary_ptr, secondary_ptr, n_samples)``; per song what ``separate_dev`` does
+        (mix [2, n] normalised in place, stems [n, 2]), all songs through one pooled demix (asx_separate_batch_dev)."""
+        songs = list(songs)
+        arr = (_SongStems * max(1, len(songs)))()
+        for i, (mix_ptr, p_ptr, s_ptr, n) in enumerate(songs):
+            arr[i] = _SongStems(mix_ptr or None, p_ptr or None, s_ptr or None, int(n))
+        self._check(self._lib.asx_separate_batch_dev(self._h, arr, len(songs), float(max_peak),
+                                                     float(min_peak) if min_peak is not None else 0.0,
+                                                     int(min_peak is not None), float(compensate), stream or None))
+
+    def _torch_stream(self):
+        import torch
+        dev = torch.device("cuda", self.device)
+        return torch, dev, torch.cuda.current_stream(dev)
+
+    def demix_batch(self, mixes, is_match_mix: bool = False) -> list:
+        """``demix`` for a list of float32 [2, N_i] arrays in one pooled call; returns the list of [2, N_i] results.  Device
+        staging buffers come from torch (the plumbing layer), as in the file-level path."""
+        host = []
+        for mix in mixes:
+            mix = _f32(mix)
+            if mix.ndim != 2 or mix.shape[0] != 2:
+                raise ValueError(f"Expected a 2-channel audio signal, but got shape {mix.shape}")
+            host.append(mix)
+        if not host:
+            return []
+        torch, dev, st = self._torch_stream()
+        with torch.cuda.stream(st):
+            d_mix = [torch.from_numpy(m).to(dev) for m in host]
+            d_out = [torch.empty_like(m) for m in d_mix]
+            self.demix_batch_dev([(m.data_ptr() if m.numel() else 0, o.data_ptr() if o.numel() else 0, m.shape[1])
+                                  for m, o in zip(d_mix, d_out)], is_match_mix, st.cuda_stream)
+            outs = [o.cpu().numpy() for o in d_out]
+        return outs
+
+    def separate_batch(self, mixes, max_peak: float, min_peak, compensate: float) -> list:
+        """``separate`` for a list of mixes (each float32 [2, N_i], C-contiguous, normalised IN PLACE) in one pooled call;
+        returns ``[(primary [N_i, 2], secondary [N_i, 2]), ...]``."""
+        for mix in mixes:
+            if not isinstance(mix, np.ndarray) or mix.dtype != np.float32 or not mix.flags.c_contiguous or mix.ndim != 2 or mix.shape[0] != 2:
+                raise ValueError("mix must be a C-contiguous float32 array of shape [2, N]")
+        if not len(mixes):
+            return []
+        torch, dev, st = self._torch_stream()
+        with torch.cuda.stream(st):
+            d_mix = [torch.from_numpy(m).to(dev) for m in mixes]
+            d_p = [torch.empty((m.shape[1], 2), dtype=torch.float32, device=dev) for m in mixes]
+            d_s = [torch.empty((m.shape[1], 2), dtype=torch.float32, device=dev) for m in mixes]
+            ptr = lambda t: t.data_ptr() if t.numel() else 0  # noqa: E731
+            self.separate_batch_dev([(ptr(m), ptr(p), ptr(s), m.shape[1]) for m, p, s in zip(d_mix, d_p, d_s)],
+                                    max_peak, min_peak, compensate, st.cuda_stream)
+            res = []
+            for m, dm, p, s in zip(mixes, d_mix, d_p, d_s):
+                m[...] = dm.cpu().numpy()
+                res.append((p.cpu().numpy(), s.cpu().numpy()))
+        return res
 
     # -- stage hooks ----------------------------------------------------------
     def stft(self, wave: np.ndarray) -> np.ndarray:

@@ -175,6 +175,37 @@ class MDXDemixer:
             raise ValueError("Audio file is empty or not valid")
         return self.engine.demix(mix.astype(np.float32, copy=False), is_match_mix=is_match_mix)
 
+    @staticmethod
+    def _check_mix(mix):
+        if mix.ndim != 2 or mix.shape[0] != 2:
+            raise ValueError(f"Expected a 2-channel audio signal, but got {mix.shape[0] if mix.ndim else 0} channels")
+        if mix.shape[1] == 0:
+            raise ValueError("Audio file is empty or not valid")
+
+    def demix_many(self, mixes, is_match_mix=False):
+        """``demix`` for a list of float32 [2, N_i] mixes in ONE engine call: the chunks of all songs are pooled per net
+        pass (Engine.demix_batch).  Result i is bit-identical to ``demix(mixes[i])``."""
+        self.initialize_model_settings()
+        mixes = [np.asarray(m) for m in mixes]
+        for m in mixes:
+            self._check_mix(m)
+        return self.engine.demix_batch([m.astype(np.float32, copy=False) for m in mixes], is_match_mix=is_match_mix)
+
+    def separate_stems_many(self, mixes):
+        """``separate_stems`` for a list of mixes in one pooled call: every mix is normalised in place, the result is
+        ``[(primary [N_i, 2], secondary [N_i, 2]), ...]``.  ``primary_source`` / ``secondary_source`` are left as the last
+        song's stems."""
+        self.initialize_model_settings()
+        for m in mixes:
+            self._check_mix(m)
+        stems = self.engine.separate_batch(mixes, self.normalization_threshold, self.amplification_threshold, self.compensate)
+        if self.invert_using_spec:
+            raws = self.engine.demix_batch(mixes, is_match_mix=True)
+            stems = [(p, self.engine.invert_stem(raw, (p * self.compensate).T)) for (p, _), raw in zip(stems, raws)]
+        if stems:
+            self.primary_source, self.secondary_source = stems[-1]
+        return stems
+
     def run_model(self, mix, is_match_mix=False):
         """mdx_separator.py:414-450: [B, 2, chunk_size] -> [B, 2, chunk_size] (numpy)."""
         x, _ = _to_numpy(mix)

@@ -173,11 +173,17 @@ class FilesPipeline:
 
     ``demix(mix, out)`` is the per-song hot path (libasx.so's ``demix_dev`` on the GPU; any callable in the CPU tests).
     ``on_gathered(step, slabs)`` (rank ``dst`` only) is called when the gather of ``step`` has completed, before its buffers
-    are reused: ``slabs[r]`` is rank r's [S, 2, N] stems of that step.  With ``overlap=False`` the gather blocks."""
+    are reused: ``slabs[r]`` is rank r's [S, 2, N] stems of that step.  With ``overlap=False`` the gather blocks.
 
-    def __init__(self, demix, mixes, world: int, rank: int, use_dist: bool, dst: int = 0, overlap: bool = True, on_gathered=None):
+    ``demix_many(mixes, outs)`` (optional) replaces the per-song loop of a step by ONE call over all of the rank's songs
+    (``outs`` is the step's [S, 2, N] stem buffer): libasx.so's ``demix_batch_dev``, which pools the chunks of all songs per
+    launch (``batch_demix_many`` below builds the callable)."""
+
+    def __init__(self, demix, mixes, world: int, rank: int, use_dist: bool, dst: int = 0, overlap: bool = True, on_gathered=None,
+                 demix_many=None):
         import torch
         self.demix, self.mixes, self.world, self.rank, self.dst = demix, mixes, world, rank, dst
+        self.demix_many = demix_many
         self.use_dist, self.overlap, self.on_gathered = use_dist, overlap, on_gathered
         S, shape = len(mixes), tuple(mixes[0].shape)
         mk = lambda: torch.empty((S,) + shape, dtype=mixes[0].dtype, device=mixes[0].device)  # noqa: E731
@@ -200,8 +206,11 @@ class FilesPipeline:
         import torch.distributed as dist
         b = k & 1
         self._complete(b)                 # the stems buffer is free again once its gather has drained
-        for s, mix in enumerate(self.mixes):
-            self.demix(mix, self.outs[b][s])
+        if self.demix_many is not None:
+            self.demix_many(self.mixes, self.outs[b])
+        else:
+            for s, mix in enumerate(self.mixes):
+                self.demix(mix, self.outs[b][s])
         if self.use_dist:
             if self.overlap:
                 self.pending[b] = (dist.gather(self.outs[b], self.gathered[b], dst=self.dst, async_op=True), k)
@@ -215,6 +224,16 @@ class FilesPipeline:
         order = sorted((b for b in (0, 1) if self.pending[b] is not None), key=lambda b: self.pending[b][1])
         for b in order:
             self._complete(b)
+
+
+def batch_demix_many(engine, is_match_mix: bool = False, stream=None):
+    """The ``demix_many`` callable of FilesPipeline over an MDX engine: one ``demix_batch_dev`` call for all songs of a step.
+    ``stream`` is a callable returning the raw stream handle (default: torch's current stream on the engine's GPU)."""
+    def run(mixes, outs):
+        import torch
+        st = stream() if stream is not None else torch.cuda.current_stream(torch.device("cuda", engine.device)).cuda_stream
+        engine.demix_batch_dev([(m.data_ptr(), outs[i].data_ptr(), m.shape[-1]) for i, m in enumerate(mixes)], is_match_mix, st)
+    return run
 
 
 class ShardWorkspace:
