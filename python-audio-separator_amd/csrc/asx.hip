@@ -577,9 +577,7 @@ int asx_demix_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t
   }
   const int nk = k1 - k0;
   if (nk == 0) return ASX_OK;
-  const int maxB = pick_batch(e);
-  const int nbatch = (nk + maxB - 1) / maxB;
-  const int per = (nk + nbatch - 1) / nbatch;
+  const int per = even_batches(nk, pick_batch(e));
   CHK(ensure_workspace(e, per, need_net));
   // chunk tables, built on the device: start of chunk k = k * step, active length = min(chunk, L - start), or negative
   // for "no chunk window" (overlap == 0, mdx_separator.py:389-390).  No host copy, no host synchronisation: the call
@@ -1005,23 +1003,6 @@ int asx_resample_sinc_dev(asx_engine *e, const float *x_dev, int32_t channels, i
 }
 
 // ---- stage hooks -------------------------------------------------------------
-static int to_dev(DevBuf &d, const float *h, size_t n) {
-  CHK(d.ensure(n * 4));
-  HIPCHK(hipMemcpy(d.p, h, n * 4, hipMemcpyHostToDevice));
-  return ASX_OK;
-}
-static int to_host(float *h, const DevBuf &d, size_t n) {
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(h, d.p, n * 4, hipMemcpyDeviceToHost));
-  return ASX_OK;
-}
-struct BufGuard {
-  std::vector<DevBuf *> v;
-  ~BufGuard() {
-    for (auto *b : v) b->release();
-  }
-};
-
 static int transpose_launch(const float *in, float *out, int planes, int rows, int cols, hipStream_t s) {
   hipLaunchKernelGGL(transpose_last2_kernel, dim3((cols + 31) / 32, (rows + 31) / 32, planes), dim3(32, 8), 0, s, in,
                      out, rows, cols);
@@ -1127,12 +1108,9 @@ int asx_resample_sinc(asx_engine *e, const float *x_host, int32_t channels, int6
                       float *y_host, int64_t n_out) {
   REQUIRE(e && x_host && y_host && channels >= 1 && n_in >= 1 && n_out >= 1, "asx_resample_sinc: bad argument");
   HIPCHK(hipSetDevice(e->device));
-  DevBuf dx, dy;
-  BufGuard g{{&dx, &dy}};
-  CHK(to_dev(dx, x_host, (size_t)channels * n_in));
-  CHK(dy.ensure((size_t)channels * n_out * 4));
-  CHK(asx_resample_sinc_dev(e, dx.f(), channels, n_in, ratio, mono_calls, dy.f(), n_out, nullptr));
-  return to_host(y_host, dy, (size_t)channels * n_out);
+  return host_round_trip(x_host, (size_t)channels * n_in, y_host, (size_t)channels * n_out, [&](const float *x, float *y) {
+    return asx_resample_sinc_dev(e, x, channels, n_in, ratio, mono_calls, y, n_out, nullptr);
+  });
 }
 
 int asx_stft(asx_engine *e, const float *wave_host, int32_t B, int64_t C, float *spec_host) {
@@ -1141,13 +1119,9 @@ int asx_stft(asx_engine *e, const float *wave_host, int32_t B, int64_t C, float 
   HIPCHK(hipSetDevice(e->device));
   const int T = (int)(C / e->cfg.hop_length) + 1;
   const size_t ns = (size_t)B * 4 * e->cfg.dim_f * T;
-  DevBuf dw, ds;
-  BufGuard g{{&dw, &ds}};
-  CHK(to_dev(dw, wave_host, (size_t)B * 2 * C));
-  CHK(ds.ensure(ns * 4));
-  CHK(stft_launch(e, dw.f(), nullptr, -1, B, C, T, ds.f(), 0, 0, 1.0f, nullptr));
-  CHK(to_host(spec_host, ds, ns));
-  return ASX_OK;
+  return host_round_trip(wave_host, (size_t)B * 2 * C, spec_host, ns, [&](const float *w, float *spec) {
+    return stft_launch(e, w, nullptr, -1, B, C, T, spec, 0, 0, 1.0f, nullptr);
+  });
 }
 
 int asx_istft(asx_engine *e, const float *spec_host, int32_t B, int32_t T, float *wave_host) {
@@ -1186,16 +1160,12 @@ int asx_net_forward(asx_engine *e, const float *spec_host, int32_t B, float *out
   e->cfg.enable_denoise = den;
   CHK(rc);
   const size_t ns = (size_t)B * dc * Fq * T;
-  DevBuf din, dout;
-  BufGuard g{{&din, &dout}};
-  CHK(to_dev(din, spec_host, ns));
-  CHK(dout.ensure(ns * 4));
-  // reference layout [B,4,F,T] -> engine layout [B,4,T,F]
-  CHK(transpose_launch(din.f(), e->spec_in.f(), B * dc, Fq, T, nullptr));
-  CHK(net_forward_dev(e, e->spec_in.f(), e->spec_out.f(), B, nullptr));
-  CHK(transpose_launch(e->spec_out.f(), dout.f(), B * dc, T, Fq, nullptr));
-  CHK(to_host(out_host, dout, ns));
-  return ASX_OK;
+  return host_round_trip(spec_host, ns, out_host, ns, [&](const float *in, float *out) -> int {
+    // reference layout [B,4,F,T] -> engine layout [B,4,T,F]
+    CHK(transpose_launch(in, e->spec_in.f(), B * dc, Fq, T, nullptr));
+    CHK(net_forward_dev(e, e->spec_in.f(), e->spec_out.f(), B, nullptr));
+    return transpose_launch(e->spec_out.f(), out, B * dc, T, Fq, nullptr);
+  });
 }
 
 int asx_run_model(asx_engine *e, const float *wave_host, int32_t B, float *out_host, uint32_t flags) {
@@ -1524,20 +1494,12 @@ double asx_v3_flops(const asx_engine *e, int32_t batch) { return e ? v3_flops(e,
 
 int asx_v3_forward(asx_engine *e, const float *wave_host, int32_t B, float *out_host) {
   REQUIRE(e && wave_host && out_host && B > 0, "asx_v3_forward: bad argument");
-  if (!e->v3 || !e->v3->ready) {
-    set_err("asx_v3_forward: weights not committed");
-    return ASX_ERR_STATE;
-  }
+  READY(e->v3, "asx_v3_forward");
   HIPCHK(hipSetDevice(e->device));
   const int64_t C = (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1);
   const int S = e->v3->cfg.num_targets;
-  DevBuf dw, dout;
-  BufGuard g{{&dw, &dout}};
-  CHK(to_dev(dw, wave_host, (size_t)B * 2 * C));
-  CHK(dout.ensure((size_t)B * S * 2 * C * 4));
-  CHK(v3_chunks_dev(e, dw.f(), nullptr, -1, 0, B, dout.f(), nullptr));
-  CHK(to_host(out_host, dout, (size_t)B * S * 2 * C));
-  return ASX_OK;
+  return host_round_trip(wave_host, (size_t)B * 2 * C, out_host, (size_t)B * S * 2 * C,
+                         [&](const float *w, float *out) { return v3_chunks_dev(e, w, nullptr, -1, 0, B, out, nullptr); });
 }
 
 int asx_mdxc_plan(const asx_engine *e, int64_t N, int32_t overlap, asx_plan *out) {
@@ -1564,10 +1526,7 @@ int asx_mdxc_plan(const asx_engine *e, int64_t N, int32_t overlap, asx_plan *out
 int asx_mdxc_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t overlap, int32_t k0, int32_t k1, float *chunk_out_dev,
                         void *stream) {
   REQUIRE(e && mix_dev && chunk_out_dev, "asx_mdxc_chunks_dev: null argument");
-  if (!e->v3 || !e->v3->ready) {
-    set_err("asx_mdxc_demix: weights not committed");
-    return ASX_ERR_STATE;
-  }
+  READY(e->v3, "asx_mdxc_chunks_dev");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   HIPCHK(hipSetDevice(e->device));
   asx_plan p;
@@ -1582,9 +1541,7 @@ int asx_mdxc_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t 
   hipLaunchKernelGGL(chunk_table_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, k0, nk, p.step, p.chunk_size,
                      p.padded_len, 0, reinterpret_cast<int64_t *>(n.d_starts.p), reinterpret_cast<int64_t *>(n.d_starts.p) + nk);
   HIPCHK(hipGetLastError());
-  const int maxB = e->cfg.max_batch > 0 ? e->cfg.max_batch : 8;
-  const int nbatch = (nk + maxB - 1) / maxB;
-  const int per = (nk + nbatch - 1) / nbatch;
+  const int per = even_batches(nk, e->cfg.max_batch > 0 ? e->cfg.max_batch : 8);
   for (int j = 0; j < nk; j += per) {
     const int B = std::min(per, nk - j);
     CHK(v3_chunks_dev(e, mix_dev, reinterpret_cast<const int64_t *>(n.d_starts.p) + j, N, p.trim, B,
@@ -1596,10 +1553,7 @@ int asx_mdxc_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t 
 // uniform fold of ALL chunks, / overlap (mdxc_separator.py:246-255, 394-404): chunk_out [n_chunks, S, 2, chunk] -> out [S, 2, N]
 int asx_mdxc_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t N, int32_t overlap, float *out_dev, void *stream) {
   REQUIRE(e && chunk_out_dev && out_dev, "asx_mdxc_finalize_dev: null argument");
-  if (!e->v3 || !e->v3->ready) {
-    set_err("asx_mdxc_demix: weights not committed");
-    return ASX_ERR_STATE;
-  }
+  READY(e->v3, "asx_mdxc_finalize_dev");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   HIPCHK(hipSetDevice(e->device));
   asx_plan p;
@@ -1615,10 +1569,7 @@ int asx_mdxc_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t N, 
 
 int asx_mdxc_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t overlap, float *out_dev, void *stream) {
   REQUIRE(e && mix_dev && out_dev, "asx_mdxc_demix_dev: null argument");
-  if (!e->v3 || !e->v3->ready) {
-    set_err("asx_mdxc_demix: weights not committed");
-    return ASX_ERR_STATE;
-  }
+  READY(e->v3, "asx_mdxc_demix_dev");
   asx_plan p;
   CHK(asx_mdxc_plan(e, N, overlap, &p));
   V3Net &n = *e->v3;
@@ -1630,19 +1581,11 @@ int asx_mdxc_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t o
 int asx_mdxc_demix(asx_engine *e, const float *mix_host, int64_t N, int32_t overlap, float *out_host) {
   REQUIRE(e && mix_host && out_host, "asx_mdxc_demix: null argument");
   REQUIRE(N >= 1, "n_samples must be >= 1");
-  if (!e->v3 || !e->v3->ready) {
-    set_err("asx_mdxc_demix: weights not committed");
-    return ASX_ERR_STATE;
-  }
+  READY(e->v3, "asx_mdxc_demix");
   HIPCHK(hipSetDevice(e->device));
   const int S = e->v3->cfg.num_targets;
-  DevBuf dmix, dout;
-  BufGuard g{{&dmix, &dout}};
-  CHK(to_dev(dmix, mix_host, (size_t)2 * N));
-  CHK(dout.ensure((size_t)S * 2 * N * 4));
-  CHK(asx_mdxc_demix_dev(e, dmix.f(), N, overlap, dout.f(), nullptr));
-  CHK(to_host(out_host, dout, (size_t)S * 2 * N));
-  return ASX_OK;
+  return host_round_trip(mix_host, (size_t)2 * N, out_host, (size_t)S * 2 * N,
+                         [&](const float *mix, float *out) { return asx_mdxc_demix_dev(e, mix, N, overlap, out, nullptr); });
 }
 
 // ---- BS-Roformer ------------------------------------------------------------------
@@ -1791,20 +1734,12 @@ double asx_rof_flops(const asx_engine *e, int32_t batch) { return e ? rof_flops(
 
 int asx_rof_forward(asx_engine *e, const float *wave_host, int32_t B, float *out_host) {
   REQUIRE(e && wave_host && out_host && B > 0, "asx_rof_forward: bad argument");
-  if (!e->rof || !e->rof->ready) {
-    set_err("asx_rof_forward: weights not committed");
-    return ASX_ERR_STATE;
-  }
+  READY(e->rof, "asx_rof_forward");
   HIPCHK(hipSetDevice(e->device));
   const int64_t C = (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1);
   const int S = e->rof->cfg.num_stems;
-  DevBuf dw, dout;
-  BufGuard g{{&dw, &dout}};
-  CHK(to_dev(dw, wave_host, (size_t)B * 2 * C));
-  CHK(dout.ensure((size_t)B * S * 2 * C * 4));
-  CHK(rof_chunks_dev(e, dw.f(), nullptr, -1, B, dout.f(), nullptr));
-  CHK(to_host(out_host, dout, (size_t)B * S * 2 * C));
-  return ASX_OK;
+  return host_round_trip(wave_host, (size_t)B * 2 * C, out_host, (size_t)B * S * 2 * C,
+                         [&](const float *w, float *out) { return rof_chunks_dev(e, w, nullptr, -1, B, out, nullptr); });
 }
 
 // start of Roformer chunk k0 + t: t * step, the last one re-anchored to N - C (mdxc_separator.py:323-336)
@@ -1837,10 +1772,7 @@ int asx_rof_plan(const asx_engine *e, int64_t N, int64_t step, int32_t *n_chunks
 int asx_rof_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int64_t step, int32_t k0, int32_t k1, float *chunk_out_dev,
                        void *stream) {
   REQUIRE(e && mix_dev && chunk_out_dev, "asx_rof_chunks_dev: null argument");
-  if (!e->rof || !e->rof->ready) {
-    set_err("asx_rof_demix: weights not committed");
-    return ASX_ERR_STATE;
-  }
+  READY(e->rof, "asx_rof_chunks_dev");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   HIPCHK(hipSetDevice(e->device));
   RofNet &n = *e->rof;
@@ -1856,9 +1788,7 @@ int asx_rof_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int64_t s
   hipLaunchKernelGGL(rof_starts_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, k0, nk, step, N, C,
                      reinterpret_cast<int64_t *>(n.d_starts.p));
   HIPCHK(hipGetLastError());
-  const int maxB = e->cfg.max_batch > 0 ? e->cfg.max_batch : 8;
-  const int nbatch = (nk + maxB - 1) / maxB;
-  const int per = (nk + nbatch - 1) / nbatch;
+  const int per = even_batches(nk, e->cfg.max_batch > 0 ? e->cfg.max_batch : 8);
   for (int j = 0; j < nk; j += per) {
     const int B = std::min(per, nk - j);
     CHK(rof_chunks_dev(e, mix_dev, reinterpret_cast<const int64_t *>(n.d_starts.p) + j, N, B, chunk_out_dev + (size_t)j * S * 2 * C, s));
@@ -1869,10 +1799,7 @@ int asx_rof_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int64_t s
 // Hamming-weighted fold of ALL chunks / counter.clamp(1e-10) (mdxc_separator.py:310-343)
 int asx_rof_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t N, int64_t step, float *out_dev, void *stream) {
   REQUIRE(e && chunk_out_dev && out_dev, "asx_rof_finalize_dev: null argument");
-  if (!e->rof || !e->rof->ready) {
-    set_err("asx_rof_demix: weights not committed");
-    return ASX_ERR_STATE;
-  }
+  READY(e->rof, "asx_rof_finalize_dev");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   HIPCHK(hipSetDevice(e->device));
   RofNet &n = *e->rof;
@@ -1894,10 +1821,7 @@ int asx_rof_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t N, i
 
 int asx_rof_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int64_t step, float *out_dev, void *stream) {
   REQUIRE(e && mix_dev && out_dev, "asx_rof_demix_dev: null argument");
-  if (!e->rof || !e->rof->ready) {
-    set_err("asx_rof_demix: weights not committed");
-    return ASX_ERR_STATE;
-  }
+  READY(e->rof, "asx_rof_demix_dev");
   RofNet &n = *e->rof;
   std::vector<int64_t> starts;
   CHK(rof_starts(e, N, step, starts));
@@ -1909,19 +1833,11 @@ int asx_rof_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int64_t st
 
 int asx_rof_demix(asx_engine *e, const float *mix_host, int64_t N, int64_t step, float *out_host) {
   REQUIRE(e && mix_host && out_host, "asx_rof_demix: null argument");
-  if (!e->rof || !e->rof->ready) {
-    set_err("asx_rof_demix: weights not committed");
-    return ASX_ERR_STATE;
-  }
+  READY(e->rof, "asx_rof_demix");
   HIPCHK(hipSetDevice(e->device));
   const int n_out = e->rof->cfg.n_out;
-  DevBuf dmix, dout;
-  BufGuard g{{&dmix, &dout}};
-  CHK(to_dev(dmix, mix_host, (size_t)2 * N));
-  CHK(dout.ensure((size_t)n_out * 2 * N * 4));
-  CHK(asx_rof_demix_dev(e, dmix.f(), N, step, dout.f(), nullptr));
-  CHK(to_host(out_host, dout, (size_t)n_out * 2 * N));
-  return ASX_OK;
+  return host_round_trip(mix_host, (size_t)2 * N, out_host, (size_t)n_out * 2 * N,
+                         [&](const float *mix, float *out) { return asx_rof_demix_dev(e, mix, N, step, out, nullptr); });
 }
 
 // ---- options -----------------------------------------------------------------------
@@ -1967,10 +1883,7 @@ double asx_ht_flops(const asx_engine *e) { return (e && e->ht && e->ht->ready) ?
 
 int asx_ht_forward(asx_engine *e, const float *mix_host, int32_t B, int64_t length, float *out_host) {
   REQUIRE(e && mix_host && out_host && B > 0, "asx_ht_forward: bad argument");
-  if (!e->ht || !e->ht->ready) {
-    set_err("asx_ht_forward: weights not committed");
-    return ASX_ERR_STATE;
-  }
+  READY(e->ht, "asx_ht_forward");
   HIPCHK(hipSetDevice(e->device));
   const int64_t TL = e->ht->L[0];
   const int S = e->ht->cfg.n_sources;
@@ -1986,77 +1899,6 @@ int asx_ht_forward(asx_engine *e, const float *mix_host, int32_t B, int64_t leng
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy2D(out_host, (size_t)length * 4, dout.p, (size_t)TL * 4, (size_t)length * 4, (size_t)B * S * 2,
                      hipMemcpyDeviceToHost));
-  return ASX_OK;
-}
-
-int asx_ht_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
-                     uint32_t flags, float *out_dev, void *stream) {
-  REQUIRE(e && mix_dev && out_dev && N >= 2, "asx_ht_demix_dev: bad argument");
-  REQUIRE(shifts >= 0 && (shifts == 0 || offsets), "shifts > 0 needs the offsets array");
-  REQUIRE(overlap >= 0.0 && overlap < 1.0, "overlap must be in [0, 1)");
-  if (!e->ht || !e->ht->ready) {
-    set_err("asx_ht_demix: weights not committed");
-    return ASX_ERR_STATE;
-  }
-  HIPCHK(hipSetDevice(e->device));
-  return ht_demix_dev(e, mix_dev, N, shifts, offsets, overlap, flags, out_dev, reinterpret_cast<hipStream_t>(stream));
-}
-
-#define HT_READY(fn)                                   \
-  do {                                                 \
-    if (!e->ht || !e->ht->ready) {                     \
-      set_err(fn ": weights not committed");           \
-      return ASX_ERR_STATE;                            \
-    }                                                  \
-  } while (0)
-
-int asx_ht_plan(const asx_engine *e, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, int32_t *n_segments,
-                int64_t *segment_samples) {
-  REQUIRE(e && n_segments && segment_samples && N >= 2 && shifts >= 0 && (shifts == 0 || offsets), "asx_ht_plan: bad argument");
-  HT_READY("asx_ht_plan");
-  HtPlan p;
-  CHK(ht_plan(e, N, shifts, offsets, overlap, p));
-  *n_segments = (int32_t)p.starts.size();
-  *segment_samples = p.segment;
-  return ASX_OK;
-}
-
-int asx_ht_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
-                        uint32_t flags, int32_t k0, int32_t k1, float *chunk_out_dev, void *stream) {
-  REQUIRE(e && mix_dev && chunk_out_dev && N >= 2 && shifts >= 0 && (shifts == 0 || offsets), "asx_ht_segments_dev: bad argument");
-  HT_READY("asx_ht_segments_dev");
-  HIPCHK(hipSetDevice(e->device));
-  HtPlan p;
-  CHK(ht_plan(e, N, shifts, offsets, overlap, p));
-  REQUIRE(k0 >= 0 && k0 <= k1 && k1 <= (int)p.starts.size(), "segment range [%d, %d) outside [0, %d)", k0, k1, (int)p.starts.size());
-  return ht_segments_dev(e, mix_dev, N, p, flags, k0, k1, chunk_out_dev, reinterpret_cast<hipStream_t>(stream));
-}
-
-int asx_ht_fold_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, uint32_t flags,
-                    const float *chunk_out_dev, float *out_dev, void *stream) {
-  REQUIRE(e && mix_dev && chunk_out_dev && out_dev && N >= 2 && shifts >= 0 && (shifts == 0 || offsets), "asx_ht_fold_dev: bad argument");
-  HT_READY("asx_ht_fold_dev");
-  HIPCHK(hipSetDevice(e->device));
-  HtPlan p;
-  CHK(ht_plan(e, N, shifts, offsets, overlap, p));
-  return ht_fold_dev(e, mix_dev, N, p, flags, chunk_out_dev, out_dev, reinterpret_cast<hipStream_t>(stream));
-}
-
-int asx_ht_demix(asx_engine *e, const float *mix_host, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
-                 uint32_t flags, float *out_host) {
-  REQUIRE(e && mix_host && out_host && N >= 2, "asx_ht_demix: bad argument");
-  if (!e->ht || !e->ht->ready) {
-    set_err("asx_ht_demix: weights not committed");
-    return ASX_ERR_STATE;
-  }
-  HIPCHK(hipSetDevice(e->device));
-  const int S = e->ht->cfg.n_sources;
-  DevBuf dm, dout;
-  BufGuard g{{&dm, &dout}};
-  CHK(to_dev(dm, mix_host, (size_t)2 * N));
-  CHK(dout.ensure((size_t)S * 2 * N * 4));
-  CHK(asx_ht_demix_dev(e, dm.f(), N, shifts, offsets, overlap, flags, dout.f(), nullptr));
-  CHK(to_host(out_host, dout, (size_t)S * 2 * N));
   return ASX_OK;
 }
 
@@ -2114,84 +1956,122 @@ int asx_hd_commit(asx_engine *e) {
   return rc;
 }
 
-#define HD_READY(fn)                                   \
-  do {                                                 \
-    if (!e->hd || !e->hd->ready) {                     \
-      set_err(fn ": weights not committed");           \
-      return ASX_ERR_STATE;                            \
-    }                                                  \
-  } while (0)
-
 double asx_hd_flops(const asx_engine *e, int64_t length) { return (e && e->hd && e->hd->ready && length > 0) ? hd_flops(e, length) : 0.0; }
 
 int asx_hd_forward(asx_engine *e, const float *mix_host, int32_t B, int64_t length, float *out_host) {
   REQUIRE(e && mix_host && out_host && B > 0 && length > 0, "asx_hd_forward: bad argument");
-  HD_READY("asx_hd_forward");
+  READY(e->hd, "asx_hd_forward");
   HIPCHK(hipSetDevice(e->device));
   const int S = e->hd->cfg.n_sources;
-  DevBuf din, dout;
-  BufGuard g{{&din, &dout}};
-  CHK(to_dev(din, mix_host, (size_t)B * 2 * length));
-  CHK(dout.ensure((size_t)B * S * 2 * length * 4));
-  CHK(hd_forward_dev(e, din.f(), B, length, dout.f(), nullptr));
-  HIPCHK(hipDeviceSynchronize());
-  return to_host(out_host, dout, (size_t)B * S * 2 * length);
+  return host_round_trip(mix_host, (size_t)B * 2 * length, out_host, (size_t)B * S * 2 * length, [&](const float *mix, float *out) -> int {
+    CHK(hd_forward_dev(e, mix, B, length, out, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    return ASX_OK;
+  });
 }
 
-int asx_hd_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, uint32_t flags,
-                     float *out_dev, void *stream) {
-  REQUIRE(e && mix_dev && out_dev && N >= 2, "asx_hd_demix_dev: bad argument");
-  REQUIRE(shifts >= 0 && (shifts == 0 || offsets), "shifts > 0 needs the offsets array");
-  REQUIRE(overlap >= 0.0 && overlap < 1.0, "overlap must be in [0, 1)");
-  HD_READY("asx_hd_demix_dev");
-  HIPCHK(hipSetDevice(e->device));
-  return hd_demix_dev(e, mix_dev, N, shifts, offsets, overlap, flags, out_dev, reinterpret_cast<hipStream_t>(stream));
+// ---- Demucs v4 and v3: the apply_model loop ------------------------------------------------------------------------
+// One implementation per verb behind asx_ht_* (v3 = false) and asx_hd_* (v3 = true); `fn` is the entry point that was called.
+static int demucs_ready(const asx_engine *e, bool v3, const char *fn) {
+  if (v3) READY(e->hd, fn);
+  else READY(e->ht, fn);
+  return ASX_OK;
 }
 
-int asx_hd_demix(asx_engine *e, const float *mix_host, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, uint32_t flags,
-                 float *out_host) {
-  REQUIRE(e && mix_host && out_host && N >= 2, "asx_hd_demix: bad argument");
-  HD_READY("asx_hd_demix");
-  HIPCHK(hipSetDevice(e->device));
-  const int S = e->hd->cfg.n_sources;
-  DevBuf dm, dout;
-  BufGuard g{{&dm, &dout}};
-  CHK(to_dev(dm, mix_host, (size_t)2 * N));
-  CHK(dout.ensure((size_t)S * 2 * N * 4));
-  CHK(asx_hd_demix_dev(e, dm.f(), N, shifts, offsets, overlap, flags, dout.f(), nullptr));
-  return to_host(out_host, dout, (size_t)S * 2 * N);
-}
-
-int asx_hd_plan(const asx_engine *e, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, int32_t *n_segments,
-                int64_t *segment_samples) {
-  REQUIRE(e && n_segments && segment_samples && N >= 2 && shifts >= 0 && (shifts == 0 || offsets), "asx_hd_plan: bad argument");
-  HD_READY("asx_hd_plan");
-  HdPlan p;
-  CHK(hd_plan(e, N, shifts, offsets, overlap, p));
+static int demucs_plan(const asx_engine *e, bool v3, const char *fn, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
+                       int32_t *n_segments, int64_t *segment_samples) {
+  REQUIRE(e && n_segments && segment_samples && N >= 2 && shifts >= 0 && (shifts == 0 || offsets), "%s: bad argument", fn);
+  CHK(demucs_ready(e, v3, fn));
+  ApplyPlan p;
+  CHK(apply_plan(apply_net(e, v3), N, shifts, offsets, overlap, p));
   *n_segments = (int32_t)p.starts.size();
   *segment_samples = p.segment;
   return ASX_OK;
 }
 
-int asx_hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, uint32_t flags,
-                        int32_t k0, int32_t k1, float *chunk_out_dev, void *stream) {
-  REQUIRE(e && mix_dev && chunk_out_dev && N >= 2 && shifts >= 0 && (shifts == 0 || offsets), "asx_hd_segments_dev: bad argument");
-  HD_READY("asx_hd_segments_dev");
+static int demucs_segments_dev(asx_engine *e, bool v3, const char *fn, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets,
+                               double overlap, uint32_t flags, int32_t k0, int32_t k1, float *chunk_out_dev, void *stream) {
+  REQUIRE(e && mix_dev && chunk_out_dev && N >= 2 && shifts >= 0 && (shifts == 0 || offsets), "%s: bad argument", fn);
+  CHK(demucs_ready(e, v3, fn));
   HIPCHK(hipSetDevice(e->device));
-  HdPlan p;
-  CHK(hd_plan(e, N, shifts, offsets, overlap, p));
+  const ApplyNet a = apply_net(e, v3);
+  ApplyPlan p;
+  CHK(apply_plan(a, N, shifts, offsets, overlap, p));
   REQUIRE(k0 >= 0 && k0 <= k1 && k1 <= (int)p.starts.size(), "segment range [%d, %d) outside [0, %d)", k0, k1, (int)p.starts.size());
-  return hd_segments_dev(e, mix_dev, N, p, flags, k0, k1, chunk_out_dev, reinterpret_cast<hipStream_t>(stream));
+  return a.segments(e, mix_dev, N, p, flags, k0, k1, chunk_out_dev, reinterpret_cast<hipStream_t>(stream));
 }
 
+static int demucs_fold_dev(asx_engine *e, bool v3, const char *fn, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets,
+                           double overlap, uint32_t flags, const float *chunk_out_dev, float *out_dev, void *stream) {
+  REQUIRE(e && mix_dev && chunk_out_dev && out_dev && N >= 2 && shifts >= 0 && (shifts == 0 || offsets), "%s: bad argument", fn);
+  CHK(demucs_ready(e, v3, fn));
+  HIPCHK(hipSetDevice(e->device));
+  const ApplyNet a = apply_net(e, v3);
+  ApplyPlan p;
+  CHK(apply_plan(a, N, shifts, offsets, overlap, p));
+  return apply_fold_dev(e, a, mix_dev, N, p, flags, chunk_out_dev, out_dev, reinterpret_cast<hipStream_t>(stream));
+}
+
+static int demucs_demix_dev(asx_engine *e, bool v3, const char *fn, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets,
+                            double overlap, uint32_t flags, float *out_dev, void *stream) {
+  REQUIRE(e && mix_dev && out_dev && N >= 2, "%s: bad argument", fn);
+  REQUIRE(shifts >= 0 && (shifts == 0 || offsets), "shifts > 0 needs the offsets array");
+  REQUIRE(overlap >= 0.0 && overlap < 1.0, "overlap must be in [0, 1)");
+  CHK(demucs_ready(e, v3, fn));
+  HIPCHK(hipSetDevice(e->device));
+  return apply_demix_dev(e, apply_net(e, v3), mix_dev, N, shifts, offsets, overlap, flags, out_dev, reinterpret_cast<hipStream_t>(stream));
+}
+
+static int demucs_demix(asx_engine *e, bool v3, const char *fn, const float *mix_host, int64_t N, int32_t shifts, const int64_t *offsets,
+                        double overlap, uint32_t flags, float *out_host) {
+  REQUIRE(e && mix_host && out_host && N >= 2, "%s: bad argument", fn);
+  CHK(demucs_ready(e, v3, fn));
+  HIPCHK(hipSetDevice(e->device));
+  const int S = apply_net(e, v3).S;
+  return host_round_trip(mix_host, (size_t)2 * N, out_host, (size_t)S * 2 * N, [&](const float *mix, float *out) {
+    return demucs_demix_dev(e, v3, fn, mix, N, shifts, offsets, overlap, flags, out, nullptr);
+  });
+}
+
+int asx_ht_plan(const asx_engine *e, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, int32_t *n_segments,
+                int64_t *segment_samples) {
+  return demucs_plan(e, false, "asx_ht_plan", N, shifts, offsets, overlap, n_segments, segment_samples);
+}
+int asx_hd_plan(const asx_engine *e, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, int32_t *n_segments,
+                int64_t *segment_samples) {
+  return demucs_plan(e, true, "asx_hd_plan", N, shifts, offsets, overlap, n_segments, segment_samples);
+}
+int asx_ht_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
+                        uint32_t flags, int32_t k0, int32_t k1, float *chunk_out_dev, void *stream) {
+  return demucs_segments_dev(e, false, "asx_ht_segments_dev", mix_dev, N, shifts, offsets, overlap, flags, k0, k1, chunk_out_dev, stream);
+}
+int asx_hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
+                        uint32_t flags, int32_t k0, int32_t k1, float *chunk_out_dev, void *stream) {
+  return demucs_segments_dev(e, true, "asx_hd_segments_dev", mix_dev, N, shifts, offsets, overlap, flags, k0, k1, chunk_out_dev, stream);
+}
+int asx_ht_fold_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, uint32_t flags,
+                    const float *chunk_out_dev, float *out_dev, void *stream) {
+  return demucs_fold_dev(e, false, "asx_ht_fold_dev", mix_dev, N, shifts, offsets, overlap, flags, chunk_out_dev, out_dev, stream);
+}
 int asx_hd_fold_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, uint32_t flags,
                     const float *chunk_out_dev, float *out_dev, void *stream) {
-  REQUIRE(e && mix_dev && chunk_out_dev && out_dev && N >= 2 && shifts >= 0 && (shifts == 0 || offsets), "asx_hd_fold_dev: bad argument");
-  HD_READY("asx_hd_fold_dev");
-  HIPCHK(hipSetDevice(e->device));
-  HdPlan p;
-  CHK(hd_plan(e, N, shifts, offsets, overlap, p));
-  return hd_fold_dev(e, mix_dev, N, p, flags, chunk_out_dev, out_dev, reinterpret_cast<hipStream_t>(stream));
+  return demucs_fold_dev(e, true, "asx_hd_fold_dev", mix_dev, N, shifts, offsets, overlap, flags, chunk_out_dev, out_dev, stream);
+}
+int asx_ht_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
+                     uint32_t flags, float *out_dev, void *stream) {
+  return demucs_demix_dev(e, false, "asx_ht_demix_dev", mix_dev, N, shifts, offsets, overlap, flags, out_dev, stream);
+}
+int asx_hd_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
+                     uint32_t flags, float *out_dev, void *stream) {
+  return demucs_demix_dev(e, true, "asx_hd_demix_dev", mix_dev, N, shifts, offsets, overlap, flags, out_dev, stream);
+}
+int asx_ht_demix(asx_engine *e, const float *mix_host, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
+                 uint32_t flags, float *out_host) {
+  return demucs_demix(e, false, "asx_ht_demix", mix_host, N, shifts, offsets, overlap, flags, out_host);
+}
+int asx_hd_demix(asx_engine *e, const float *mix_host, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
+                 uint32_t flags, float *out_host) {
+  return demucs_demix(e, true, "asx_hd_demix", mix_host, N, shifts, offsets, overlap, flags, out_host);
 }
 
 // ---- VR ------------------------------------------------------------------------------
@@ -2229,17 +2109,9 @@ int asx_vr_commit(asx_engine *e) {
 
 double asx_vr_flops(const asx_engine *e) { return (e && e->vr && e->vr->ready) ? vr_flops_patch(e) : 0.0; }
 
-#define VR_READY(fn)                                   \
-  do {                                                 \
-    if (!e->vr || !e->vr->ready) {                     \
-      set_err(fn ": weights not committed");           \
-      return ASX_ERR_STATE;                            \
-    }                                                  \
-  } while (0)
-
 int asx_vr_plan(const asx_engine *e, int64_t n_samples, int32_t *n_frames, int64_t *n_out) {
   REQUIRE(e && n_frames && n_out && n_samples > 0, "asx_vr_plan: bad argument");
-  VR_READY("asx_vr_plan");
+  READY(e->vr, "asx_vr_plan");
   int T;
   CHK(vr_plan(*e->vr, n_samples, &T, n_out));
   *n_frames = T;
@@ -2248,31 +2120,27 @@ int asx_vr_plan(const asx_engine *e, int64_t n_samples, int32_t *n_frames, int64
 
 int asx_vr_forward(asx_engine *e, const float *x_host, int32_t B, float *out_host) {
   REQUIRE(e && x_host && out_host && B > 0, "asx_vr_forward: bad argument");
-  VR_READY("asx_vr_forward");
+  READY(e->vr, "asx_vr_forward");
   HIPCHK(hipSetDevice(e->device));
   VrNet &n = *e->vr;
   const int W = n.cfg.window_size;
   const size_t numel = (size_t)B * 2 * n.nb1 * W;
-  DevBuf dx, dy;
-  BufGuard g{{&dx, &dy}};
-  CHK(to_dev(dx, x_host, numel));
-  CHK(dy.ensure(numel * 4));
-  CHK(n.cfg.v51 ? vr51_ensure_workspace(e, B) : vr_ensure_workspace(e, B));
-  const int64_t P = (int64_t)B * n.max_bin * W;
-  hipLaunchKernelGGL(vr_from_nchw_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, nullptr, dx.f(), n.nb1, n.max_bin, W, n.ctot,
-                     n.b.hc, P);
-  HIPCHK(hipGetLastError());
-  CHK(n.cfg.v51 ? vr51_net_dev(e, B, nullptr) : vr_net_dev(e, B, nullptr));
-  hipLaunchKernelGGL(vr_to_nchw_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, nullptr, n.b.mk, n.nb1, n.max_bin, W, dy.f(),
-                     (int64_t)numel);
-  HIPCHK(hipGetLastError());
-  CHK(to_host(out_host, dy, numel));
-  return ASX_OK;
+  return host_round_trip(x_host, numel, out_host, numel, [&](const float *x, float *y) -> int {
+    CHK(n.cfg.v51 ? vr51_ensure_workspace(e, B) : vr_ensure_workspace(e, B));
+    const int64_t P = (int64_t)B * n.max_bin * W;
+    hipLaunchKernelGGL(vr_from_nchw_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, nullptr, x, n.nb1, n.max_bin, W, n.ctot, n.b.hc, P);
+    HIPCHK(hipGetLastError());
+    CHK(n.cfg.v51 ? vr51_net_dev(e, B, nullptr) : vr_net_dev(e, B, nullptr));
+    hipLaunchKernelGGL(vr_to_nchw_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, nullptr, n.b.mk, n.nb1, n.max_bin, W, y,
+                       (int64_t)numel);
+    HIPCHK(hipGetLastError());
+    return ASX_OK;
+  });
 }
 
 int asx_vr_analysis(asx_engine *e, const float *wave_host, int64_t n_samples, float *spec_host) {
   REQUIRE(e && wave_host && spec_host && n_samples > 0, "asx_vr_analysis: bad argument");
-  VR_READY("asx_vr_analysis");
+  READY(e->vr, "asx_vr_analysis");
   HIPCHK(hipSetDevice(e->device));
   VrNet &n = *e->vr;
   int T;
@@ -2290,7 +2158,7 @@ int asx_vr_analysis(asx_engine *e, const float *wave_host, int64_t n_samples, fl
 int asx_vr_separate_dev(asx_engine *e, const float *wave_dev, int64_t n_samples, const asx_vr_params *params, float *primary_dev,
                         float *secondary_dev, void *stream) {
   REQUIRE(e && wave_dev && params && n_samples > 0, "asx_vr_separate_dev: bad argument");
-  VR_READY("asx_vr_separate");
+  READY(e->vr, "asx_vr_separate_dev");
   HIPCHK(hipSetDevice(e->device));
   return vr_separate_dev(e, wave_dev, n_samples, params, primary_dev, secondary_dev, reinterpret_cast<hipStream_t>(stream));
 }
@@ -2298,7 +2166,7 @@ int asx_vr_separate_dev(asx_engine *e, const float *wave_dev, int64_t n_samples,
 int asx_vr_separate(asx_engine *e, const float *wave_host, int64_t n_samples, const asx_vr_params *params, float *primary_host,
                     float *secondary_host) {
   REQUIRE(e && wave_host && params && n_samples > 0, "asx_vr_separate: bad argument");
-  VR_READY("asx_vr_separate");
+  READY(e->vr, "asx_vr_separate");
   HIPCHK(hipSetDevice(e->device));
   int T;
   int64_t n_out;

@@ -33,6 +33,14 @@ static void set_err(const char *fmt, ...) {
       return ASX_ERR_INVALID;     \
     }                             \
   } while (0)
+// every entry point of a net family but begin / commit: ASX_ERR_STATE until the family's commit has succeeded
+#define READY(net, fn)                                 \
+  do {                                                 \
+    if (!(net) || !(net)->ready) {                     \
+      set_err("%s: weights not committed", fn);        \
+      return ASX_ERR_STATE;                            \
+    }                                                  \
+  } while (0)
 
 // ----------------------------------------------------------------------------
 // device buffer helper
@@ -59,6 +67,35 @@ struct DevBuf {
   }
   float *f() const { return reinterpret_cast<float *>(p); }
 };
+
+// host <-> device copies of the entry points that take host arrays (to_host waits for the device first)
+static int to_dev(DevBuf &d, const float *h, size_t n) {
+  CHK(d.ensure(n * 4));
+  HIPCHK(hipMemcpy(d.p, h, n * 4, hipMemcpyHostToDevice));
+  return ASX_OK;
+}
+static int to_host(float *h, const DevBuf &d, size_t n) {
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(h, d.p, n * 4, hipMemcpyDeviceToHost));
+  return ASX_OK;
+}
+struct BufGuard {
+  std::vector<DevBuf *> v;
+  ~BufGuard() {
+    for (auto *b : v) b->release();
+  }
+};
+// The host round trip of an entry point that takes and returns host arrays: n_in floats to the device, run(in_dev, out_dev)
+// enqueues the work on the default stream, n_out floats back; both buffers are freed on every way out.
+template <class F>
+static int host_round_trip(const float *in_host, size_t n_in, float *out_host, size_t n_out, F &&run) {
+  DevBuf din, dout;
+  BufGuard g{{&din, &dout}};
+  CHK(to_dev(din, in_host, n_in));
+  CHK(dout.ensure(n_out * 4));
+  CHK(run(din.f(), dout.f()));
+  return to_host(out_host, dout, n_out);
+}
 
 // ----------------------------------------------------------------------------
 // packed layers
@@ -234,6 +271,13 @@ struct asx_engine {
 // default: a whole 4-minute song (55 chunks, ~45 GB of the 288 GB) in one batch -- deep U-Net levels then
 // launch enough workgroups to fill 256 CUs (measured 328 vs 337 ms per song against batches of 8)
 static int pick_batch(const asx_engine *e) { return e->cfg.max_batch > 0 ? e->cfg.max_batch : 64; }
+
+// Items per launch when nk >= 1 items run in the fewest batches of at most maxB: evened out, so that no short tail batch runs
+// alone (85 items at maxB 32: 29 + 29 + 27, not 32 + 32 + 21).  The callers walk `for (j = 0; j < nk; j += per)`.
+static int even_batches(int nk, int maxB) {
+  const int nbatch = (nk + maxB - 1) / maxB;
+  return (nk + nbatch - 1) / nbatch;
+}
 
 // ----------------------------------------------------------------------------
 // profiling wrapper

@@ -746,44 +746,12 @@ static double hd_flops(const asx_engine *e, int64_t L) {
 }
 
 // ---- apply_model around it (apply.py:195-260) ---------------------------------------------------------------------
-struct HdPlan {
-  int64_t stride, segment, max_shift;
-  std::vector<HtShift> shifts;
-  std::vector<int64_t> starts, clen;   // per chunk: song index of its first sample, its length
-};
-
-static int hd_plan(const asx_engine *e, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, HdPlan &p) {
-  const asx_hd_config &c = e->hd->cfg;
-  p.segment = c.segment_samples;
-  p.stride = (int64_t)((1.0 - overlap) * (double)p.segment);
-  REQUIRE(p.stride >= 1 && p.stride <= p.segment, "overlap %g gives a bad stride", overlap);
-  p.max_shift = shifts > 0 ? c.samplerate / 2 : 0;
-  p.shifts.clear();
-  p.starts.clear();
-  p.clen.clear();
-  const int nsh = shifts > 0 ? shifts : 1;
-  for (int si = 0; si < nsh; ++si) {
-    HtShift sh;
-    sh.offset = shifts > 0 ? offsets[si] : 0;
-    REQUIRE(sh.offset >= 0 && sh.offset <= p.max_shift, "shift offset %lld outside [0, %lld]", (long long)sh.offset, (long long)p.max_shift);
-    sh.VL = N + p.max_shift - sh.offset;
-    sh.first = (int)p.starts.size();
-    for (int64_t off = 0; off < sh.VL; off += p.stride) {
-      p.starts.push_back(sh.offset + off - p.max_shift);   // no padding: the chunk itself is the model input
-      p.clen.push_back(std::min(sh.VL - off, p.segment));
-    }
-    sh.nk = (int)p.starts.size() - sh.first;
-    p.shifts.push_back(sh);
-  }
-  return ASX_OK;
-}
-
 // chunk forwards [k0, k1) -> chunk_out [k1-k0, S, 2, segment] (each row holds clen valid samples).  Chunks of equal
 // length form one group (up to max_batch of them); up to HD_MAX_GROUPS groups advance together and share their BLSTM
 // launches (hd_forward_groups; HD_MAX_GROUPS is in knobs.h beside ASX_HD_GROUPS).  (Running the tail groups on a second stream instead was
 // measured and gave nothing: the two HSA queues never had kernels in flight together)
 
-static int hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const HdPlan &p, uint32_t flags, int k0, int k1, float *chunk_out,
+static int hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const ApplyPlan &p, uint32_t flags, int k0, int k1, float *chunk_out,
                            hipStream_t s) {
   HdNet &h = *e->hd;
   HtNet &n = *e->ht;
@@ -835,32 +803,8 @@ static int hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const
   return ASX_OK;
 }
 
-static int hd_fold_dev(asx_engine *e, const float *mix_dev, int64_t N, const HdPlan &p, uint32_t flags, const float *chunk_out, float *out_dev,
-                       hipStream_t s) {
-  HtNet &n = *e->ht;
-  const int S = e->hd->cfg.n_sources;
-  const int standardize = (flags & ASX_HT_STANDARDIZE) ? 1 : 0;
-  const int swap01 = (flags & ASX_HT_SWAP01) ? 1 : 0;
-  if (standardize) CHK(ht_ref_stats(e, mix_dev, N, s));
-  const int nsh = (int)p.shifts.size();
-  for (int si = 0; si < nsh; ++si) {
-    const HtShift &sh = p.shifts[si];
-    CHK(timed(e, ASX_PROF_FINALIZE, 0.0, 4.0 * ((double)sh.nk * S * 2 * p.segment + 2.0 * S * 2 * N), s, [&]() {
-      hipLaunchKernelGGL(ht_fold_kernel, dim3((unsigned)((N + 255) / 256), S * 2), dim3(256), 0, s, chunk_out + (size_t)sh.first * S * 2 * p.segment,
-                         sh.nk, S * 2, p.segment, p.stride, p.segment, sh.VL, p.max_shift - sh.offset, n.fold_w.f(), si == 0 ? 1 : 0,
-                         si == nsh - 1 ? 1 : 0, nsh, reinterpret_cast<const double *>(n.ref_acc.p), standardize, swap01, 0, N, out_dev);
-    }));
-  }
-  return ASX_OK;
-}
-
-static int hd_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, uint32_t flags,
-                        float *out_dev, hipStream_t s) {
-  HtNet &n = *e->ht;
-  HdPlan p;
-  CHK(hd_plan(e, N, shifts, offsets, overlap, p));
-  const int nseg = (int)p.starts.size();
-  CHK(n.chunk_out.ensure((size_t)nseg * e->hd->cfg.n_sources * 2 * p.segment * 4));
-  CHK(hd_segments_dev(e, mix_dev, N, p, flags, 0, nseg, n.chunk_out.f(), s));
-  return hd_fold_dev(e, mix_dev, N, p, flags, n.chunk_out.f(), out_dev, s);
+// what apply_plan / apply_fold_dev / apply_demix_dev (engine_ht.h) need to know about the net the caller means
+static ApplyNet apply_net(const asx_engine *e, bool v3) {
+  if (v3) return ApplyNet{e->hd->cfg.n_sources, false, e->hd->cfg.segment_samples, e->hd->cfg.samplerate, hd_segments_dev};
+  return ApplyNet{e->ht->cfg.n_sources, true, e->ht->L[0], e->ht->cfg.samplerate, ht_segments_dev};
 }

@@ -10,6 +10,7 @@
 //   decoder i : (x + skip fused into the producer) rewrite 3x3 / k3 + GLU | ConvTranspose k8/s4 as a 2-tap GEMM with
 //               a 4-position scatter epilogue (+ GELU + next skip)
 #pragma once
+#include "apply_plan.h"
 
 struct HtGemm {
   DevBuf w, b;
@@ -1201,41 +1202,20 @@ static double ht_flops(const asx_engine *e) {
 }
 
 // ---- apply_model + demix_demucs ---------------------------------------------------------------------------------------
-// The segment-forwards of one call, in the reference's order: shift 0's chunks, shift 1's chunks, ...
-struct HtShift {
-  int64_t offset, VL;
-  int first, nk;          // range inside the global segment list
-};
-struct HtPlan {
-  int64_t stride, segment, max_shift;
-  std::vector<HtShift> shifts;
-  std::vector<int64_t> starts;   // song index of model-input sample 0 of every segment
+// One shell for both generations (apply.py:195-260, demucs_separator.py:162-194).  What differs between them is in ApplyNet:
+// v4 (HTDemucs) runs every chunk as a full training segment with the chunk centred inside it, in fixed-length batches
+// (ht_segments_dev); v3 (HDemucs, engine_hd.h) runs the chunk at its own length, grouped by length (hd_segments_dev).
+using ApplySegments = int (*)(asx_engine *, const float *, int64_t, const ApplyPlan &, uint32_t, int, int, float *, hipStream_t);
+struct ApplyNet {
+  int S;                         // sources
+  bool centered;                 // v4: chunks centred in a full segment (ApplyPlan::starts, the fold's `center`)
+  int64_t segment, samplerate;   // rows of the chunk slab are `segment` long
+  ApplySegments segments;
 };
 
-static int ht_plan(const asx_engine *e, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, HtPlan &p) {
-  const HtNet &n = *e->ht;
-  const int64_t TL = n.L[0];
-  p.segment = TL;
-  p.stride = (int64_t)((1.0 - overlap) * (double)TL);   // int((1 - overlap) * segment), apply.py:220
-  REQUIRE(p.stride >= 1 && p.stride <= TL, "overlap %g gives a bad stride", overlap);
-  p.max_shift = shifts > 0 ? n.cfg.samplerate / 2 : 0;
-  p.shifts.clear();
-  p.starts.clear();
-  const int nsh = shifts > 0 ? shifts : 1;
-  for (int si = 0; si < nsh; ++si) {
-    HtShift sh;
-    sh.offset = shifts > 0 ? offsets[si] : 0;
-    REQUIRE(sh.offset >= 0 && sh.offset <= p.max_shift, "shift offset %lld outside [0, %lld]", (long long)sh.offset, (long long)p.max_shift);
-    // view = padded_mix[offset : offset + N + max_shift - offset]; padded index q <-> song index q - max_shift
-    sh.VL = N + p.max_shift - sh.offset;
-    sh.first = (int)p.starts.size();
-    for (int64_t off = 0; off < sh.VL; off += p.stride) {
-      const int64_t clen = std::min(sh.VL - off, TL);
-      p.starts.push_back(sh.offset + off - (TL - clen) / 2 - p.max_shift);
-    }
-    sh.nk = (int)p.starts.size() - sh.first;
-    p.shifts.push_back(sh);
-  }
+static int apply_plan(const ApplyNet &a, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, ApplyPlan &p) {
+  std::string err;
+  REQUIRE(apply_plan_build(N, a.segment, a.samplerate, shifts, offsets, overlap, a.centered, p, err), "%s", err.c_str());
   return ASX_OK;
 }
 
@@ -1250,7 +1230,7 @@ static int ht_ref_stats(asx_engine *e, const float *mix_dev, int64_t N, hipStrea
 }
 
 // segment-forwards [k0, k1) of the global list -> chunk_out [k1-k0, S, 2, TL]
-static int ht_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const HtPlan &p, uint32_t flags, int k0, int k1, float *chunk_out,
+static int ht_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const ApplyPlan &p, uint32_t flags, int k0, int k1, float *chunk_out,
                            hipStream_t s) {
   HtNet &n = *e->ht;
   const asx_ht_config &c = n.cfg;
@@ -1263,9 +1243,7 @@ static int ht_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const
   // segments per forward: an engine knob (results do not depend on it).  4-minute song, 84 segments: 14 / 21 / 28 / 42 per batch
   // -> 871 / 899 / 926 / 928x real time (round 3; round 1: 611 vs 536x for 16 vs 8) -- the inner levels and the transformer fill
   // the chip only with many segments.
-  const int maxB = c.max_batch > 0 ? c.max_batch : 32;
-  const int nbatch = (nk + maxB - 1) / maxB;
-  const int per = (nk + nbatch - 1) / nbatch;
+  const int per = even_batches(nk, c.max_batch > 0 ? c.max_batch : 32);
   CHK(n.seg.ensure((size_t)per * 2 * TL * 4));
   for (int j = 0; j < nk; j += per) {
     const int B = std::min(per, nk - j);
@@ -1276,36 +1254,36 @@ static int ht_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const
   return ASX_OK;
 }
 
-// triangular fold per shift, mean over shifts, de-standardise, stem swap: chunk_out [all segments, S, 2, TL] -> out [S, 2, N]
-static int ht_fold_dev(asx_engine *e, const float *mix_dev, int64_t N, const HtPlan &p, uint32_t flags, const float *chunk_out, float *out_dev,
-                       hipStream_t s) {
+// triangular fold per shift, mean over shifts, de-standardise, stem swap: chunk_out [all chunks, S, 2, segment] -> out [S, 2, N]
+static int apply_fold_dev(asx_engine *e, const ApplyNet &a, const float *mix_dev, int64_t N, const ApplyPlan &p, uint32_t flags,
+                          const float *chunk_out, float *out_dev, hipStream_t s) {
   HtNet &n = *e->ht;
-  const int S = n.cfg.n_sources;
-  const int64_t TL = n.L[0];
+  const int S = a.S;
+  const int64_t TL = p.segment;
   const int standardize = (flags & ASX_HT_STANDARDIZE) ? 1 : 0;
   const int swap01 = (flags & ASX_HT_SWAP01) ? 1 : 0;
   if (standardize) CHK(ht_ref_stats(e, mix_dev, N, s));
   const int nsh = (int)p.shifts.size();
   for (int si = 0; si < nsh; ++si) {
-    const HtShift &sh = p.shifts[si];
+    const ApplyShift &sh = p.shifts[si];
     CHK(timed(e, ASX_PROF_FINALIZE, 0.0, 4.0 * ((double)sh.nk * S * 2 * TL + 2.0 * S * 2 * N), s, [&]() {
       hipLaunchKernelGGL(ht_fold_kernel, dim3((unsigned)((N + 255) / 256), S * 2), dim3(256), 0, s, chunk_out + (size_t)sh.first * S * 2 * TL,
                          sh.nk, S * 2, TL, p.stride, p.segment, sh.VL, p.max_shift - sh.offset, n.fold_w.f(), si == 0 ? 1 : 0,
-                         si == nsh - 1 ? 1 : 0, nsh, reinterpret_cast<const double *>(n.ref_acc.p), standardize, swap01, 1, N, out_dev);
+                         si == nsh - 1 ? 1 : 0, nsh, reinterpret_cast<const double *>(n.ref_acc.p), standardize, swap01, a.centered ? 1 : 0, N,
+                         out_dev);
     }));
   }
   return ASX_OK;
 }
 
-// mix_dev [2, N] -> out_dev [S, 2, N].  offsets: `shifts` draws of random.randint(0, samplerate/2) made by the host
-// (apply.py:209); shifts == 0 runs the plain split path.
-static int ht_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
-                        uint32_t flags, float *out_dev, hipStream_t s) {
+// mix_dev [2, N] -> out_dev [S, 2, N]: plan, every chunk-forward, fold
+static int apply_demix_dev(asx_engine *e, const ApplyNet &a, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets,
+                           double overlap, uint32_t flags, float *out_dev, hipStream_t s) {
   HtNet &n = *e->ht;
-  HtPlan p;
-  CHK(ht_plan(e, N, shifts, offsets, overlap, p));
+  ApplyPlan p;
+  CHK(apply_plan(a, N, shifts, offsets, overlap, p));
   const int nseg = (int)p.starts.size();
-  CHK(n.chunk_out.ensure((size_t)nseg * n.cfg.n_sources * 2 * n.L[0] * 4));
-  CHK(ht_segments_dev(e, mix_dev, N, p, flags, 0, nseg, n.chunk_out.f(), s));
-  return ht_fold_dev(e, mix_dev, N, p, flags, n.chunk_out.f(), out_dev, s);
+  CHK(n.chunk_out.ensure((size_t)nseg * a.S * 2 * p.segment * 4));
+  CHK(a.segments(e, mix_dev, N, p, flags, 0, nseg, n.chunk_out.f(), s));
+  return apply_fold_dev(e, a, mix_dev, N, p, flags, n.chunk_out.f(), out_dev, s);
 }

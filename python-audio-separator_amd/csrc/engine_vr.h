@@ -984,9 +984,7 @@ static int vr_mask_pass(asx_engine *e, int T, int pad_l, int shift, int patches,
   // patches per net pass: an engine knob (results do not depend on it).  4-minute song, 84 patches: 8 / 21 / 28 / 42 / 84 per pass
   // -> 476 / 507 / 489 / 509 / 513x real time (the deep levels of the cascade fill the chip only with many patches); batches are
   // evened out so that no short tail batch runs alone.  ~1 GB of workspace per patch at the 4band_44100 layout (vr.py asks for 48).
-  const int maxB0 = c.max_batch > 0 ? c.max_batch : 4;
-  const int nbatch = (patches + maxB0 - 1) / maxB0;
-  const int maxB = (patches + nbatch - 1) / nbatch;
+  const int maxB = even_batches(patches, c.max_batch > 0 ? c.max_batch : 4);
   CHK(c.v51 ? vr51_ensure_workspace(e, maxB) : vr_ensure_workspace(e, maxB));
   for (int k0 = 0; k0 < patches; k0 += maxB) {
     const int B = std::min(maxB, patches - k0);

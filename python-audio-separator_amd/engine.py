@@ -514,6 +514,14 @@ class Engine:
         return int(out.value)
 
     # -- weights ------------------------------------------------------------
+    def _set_tensors(self, tensors: dict):
+        """name -> float32 array / torch tensor, handed to the net that the last asx_*_begin opened"""
+        for name, t in tensors.items():
+            if hasattr(t, "detach"):
+                t = t.detach().cpu().numpy()
+            a = _f32(t).reshape(-1)
+            self._check(self._lib.asx_net_set_tensor(self._h, name.encode(), _ptr(a), a.size))
+
     def load_net(self, net_cfg: NetConfig, tensors: dict):
         """tensors: canonical name -> float32 array (see include/asx.h)."""
         if net_cfg.norm not in ("batch", "group"):
@@ -521,9 +529,7 @@ class Engine:
         n = _NetCfg(net_cfg.dim_c, net_cfg.dim_f, net_cfg.dim_t, net_cfg.g, net_cfg.l, net_cfg.num_blocks, net_cfg.k,
                     -1 if net_cfg.bn is None else net_cfg.bn, int(bool(net_cfg.tdf_bias)), 1 if net_cfg.norm == "group" else 0)
         self._check(self._lib.asx_net_begin(self._h, C.byref(n)))
-        for name, arr in tensors.items():
-            a = _f32(arr).reshape(-1)
-            self._check(self._lib.asx_net_set_tensor(self._h, name.encode(), _ptr(a), a.size))
+        self._set_tensors(tensors)
         self._check(self._lib.asx_net_commit(self._h))
         self.net_cfg = net_cfg
 
@@ -538,14 +544,9 @@ class Engine:
         c = _V3Cfg(v3.num_channels, v3.num_subbands, v3.num_scales, v3.num_blocks_per_scale, v3.num_channels_model,
                    v3.growth, v3.bottleneck_factor, norm, act, v3.num_targets)
         self._check(self._lib.asx_v3_begin(self._h, C.byref(c)))
-        for name, t in state_dict.items():
-            if hasattr(t, "detach"):
-                t = t.detach().cpu().numpy()
-            a = _f32(t).reshape(-1)
-            self._check(self._lib.asx_net_set_tensor(self._h, name.encode(), _ptr(a), a.size))
+        self._set_tensors(state_dict)
         if act == V3_ACT_ELU:
-            a = np.array([alpha], np.float32)
-            self._check(self._lib.asx_net_set_tensor(self._h, V3_ACT_ALPHA_TENSOR.encode(), _ptr(a), 1))
+            self._set_tensors({V3_ACT_ALPHA_TENSOR: np.array([alpha], np.float32)})
         self._check(self._lib.asx_v3_commit(self._h))
         self.v3_cfg = v3
 
@@ -592,11 +593,7 @@ class Engine:
             for i, f in enumerate(rc.band_starts):
                 c.band_start[i] = int(f)
         self._check(self._lib.asx_rof_begin(self._h, C.byref(c)))
-        for name, t in state_dict.items():
-            if hasattr(t, "detach"):
-                t = t.detach().cpu().numpy()
-            a = _f32(t).reshape(-1)
-            self._check(self._lib.asx_net_set_tensor(self._h, name.encode(), _ptr(a), a.size))
+        self._set_tensors(state_dict)
         self._check(self._lib.asx_rof_commit(self._h))
         self.rof_cfg = rc
 
@@ -638,11 +635,7 @@ class Engine:
         tensors = dict(state_dict)
         if pos_tables and hc.t_layers > 0:
             tensors.update(ht_pos_tables(hc))
-        for name, t in tensors.items():
-            if hasattr(t, "detach"):
-                t = t.detach().cpu().numpy()
-            a = _f32(t).reshape(-1)
-            self._check(self._lib.asx_net_set_tensor(self._h, name.encode(), _ptr(a), a.size))
+        self._set_tensors(tensors)
         self._check(self._lib.asx_ht_commit(self._h))
         self.ht_cfg = hc
 
@@ -660,25 +653,11 @@ class Engine:
 
     def ht_demix(self, mix: np.ndarray, shifts: int = 0, offsets=None, overlap: float = 0.25, standardize: bool = False,
                  swap01: bool = False) -> np.ndarray:
-        mix = _f32(mix)
-        if mix.ndim != 2 or mix.shape[0] != 2:
-            raise ValueError(f"Expected a 2-channel audio signal, but got shape {mix.shape}")
-        out = np.empty((len(self.ht_cfg.sources), 2, mix.shape[1]), np.float32)
-        offs = None
-        if shifts:
-            if offsets is None or len(offsets) != shifts:
-                raise ValueError("shifts > 0 needs one offset per shift")
-            offs = (C.c_int64 * shifts)(*[int(o) for o in offsets])
-        flags = (1 if standardize else 0) | (2 if swap01 else 0)
-        self._check(self._lib.asx_ht_demix(self._h, _ptr(mix), mix.shape[1], int(shifts), offs, float(overlap), flags,
-                                           _ptr(out)))
-        return out
+        return self._apply_demix("ht", len(self.ht_cfg.sources), mix, shifts, offsets, overlap, standardize, swap01)
 
     def ht_demix_dev(self, mix_ptr: int, n_samples: int, out_ptr: int, shifts: int = 0, offsets=None,
                      overlap: float = 0.25, flags: int = 0, stream: int = 0):
-        offs = (C.c_int64 * shifts)(*[int(o) for o in offsets]) if shifts else None
-        self._check(self._lib.asx_ht_demix_dev(self._h, mix_ptr, n_samples, int(shifts), offs, float(overlap), flags,
-                                               out_ptr, stream or None))
+        self._apply_demix_dev("ht", mix_ptr, n_samples, out_ptr, shifts, offsets, overlap, flags, stream)
 
     # -- BagOfModels combine on the device -----------------------------------------
     def ht_standardize_dev(self, mix_ptr: int, n_samples: int, out_ptr: int, stream: int = 0):
@@ -702,11 +681,7 @@ class Engine:
                    hc.norm_starts, hc.norm_groups, hc.dconv_depth, hc.dconv_comp, hc.dconv_attn, hc.dconv_lstm, hc.samplerate,
                    hc.segment_samples, float(hc.freq_emb), hc.max_batch)
         self._check(self._lib.asx_hd_begin(self._h, C.byref(c)))
-        for name, t in state_dict.items():
-            if hasattr(t, "detach"):
-                t = t.detach().cpu().numpy()
-            a = _f32(t).reshape(-1)
-            self._check(self._lib.asx_net_set_tensor(self._h, name.encode(), _ptr(a), a.size))
+        self._set_tensors(state_dict)
         self._check(self._lib.asx_hd_commit(self._h))
         self.hd_cfg = hc
 
@@ -725,34 +700,11 @@ class Engine:
 
     def hd_demix(self, mix: np.ndarray, shifts: int = 0, offsets=None, overlap: float = 0.25, standardize: bool = False,
                  swap01: bool = False) -> np.ndarray:
-        mix = _f32(mix)
-        if mix.ndim != 2 or mix.shape[0] != 2:
-            raise ValueError(f"Expected a 2-channel audio signal, but got shape {mix.shape}")
-        out = np.empty((len(self.hd_cfg.sources), 2, mix.shape[1]), np.float32)
-        if shifts and (offsets is None or len(offsets) != shifts):
-            raise ValueError("shifts > 0 needs one offset per shift")
-        flags = (1 if standardize else 0) | (2 if swap01 else 0)
-        self._check(self._lib.asx_hd_demix(self._h, _ptr(mix), mix.shape[1], int(shifts), self._offs(shifts, offsets), float(overlap),
-                                           flags, _ptr(out)))
-        return out
+        return self._apply_demix("hd", len(self.hd_cfg.sources), mix, shifts, offsets, overlap, standardize, swap01)
 
     def hd_demix_dev(self, mix_ptr: int, n_samples: int, out_ptr: int, shifts: int = 0, offsets=None, overlap: float = 0.25,
                      flags: int = 0, stream: int = 0):
-        self._check(self._lib.asx_hd_demix_dev(self._h, mix_ptr, n_samples, int(shifts), self._offs(shifts, offsets), float(overlap),
-                                               flags, out_ptr, stream or None))
-
-    def hd_plan(self, n, shifts=0, offsets=None, overlap=0.25):
-        k, c = C.c_int32(), C.c_int64()
-        self._check(self._lib.asx_hd_plan(self._h, n, int(shifts), self._offs(shifts, offsets), float(overlap), C.byref(k), C.byref(c)))
-        return {"n_chunks": k.value, "chunk_size": c.value}
-
-    def hd_segments_dev(self, mix_ptr, n, k0, k1, out_ptr, shifts=0, offsets=None, overlap=0.25, flags=0, stream=0):
-        self._check(self._lib.asx_hd_segments_dev(self._h, mix_ptr, n, int(shifts), self._offs(shifts, offsets), float(overlap), flags,
-                                                  k0, k1, out_ptr, stream or None))
-
-    def hd_fold_dev(self, mix_ptr, n, chunks_ptr, out_ptr, shifts=0, offsets=None, overlap=0.25, flags=0, stream=0):
-        self._check(self._lib.asx_hd_fold_dev(self._h, mix_ptr, n, int(shifts), self._offs(shifts, offsets), float(overlap), flags,
-                                              chunks_ptr, out_ptr, stream or None))
+        self._apply_demix_dev("hd", mix_ptr, n_samples, out_ptr, shifts, offsets, overlap, flags, stream)
 
     # -- VR -----------------------------------------------------------------------
     def load_vr(self, model_params: dict, arch: int, capacity, state_dict: dict, window_size: int = 512, offset: int = 128,
@@ -783,11 +735,7 @@ class Engine:
                                     bp.get("hpf_stop", 0), bp.get("lpf_start", 0), bp.get("lpf_stop", 0), conv[cc],
                                     VR_RES_TYPES.get(bp.get("res_type", "polyphase"), 0))
         self._check(self._lib.asx_vr_begin(self._h, C.byref(c)))
-        for name, t in state_dict.items():
-            if hasattr(t, "detach"):
-                t = t.detach().cpu().numpy()
-            a = _f32(t).reshape(-1)
-            self._check(self._lib.asx_net_set_tensor(self._h, name.encode(), _ptr(a), a.size))
+        self._set_tensors(state_dict)
         self._check(self._lib.asx_vr_commit(self._h))
         self.vr_bins = mp["bins"]
         self.vr_window = int(window_size)
@@ -878,22 +826,58 @@ class Engine:
     def rof_finalize_dev(self, chunks_ptr, n, step, out_ptr, stream=0):
         self._check(self._lib.asx_rof_finalize_dev(self._h, chunks_ptr, n, int(step), out_ptr, stream or None))
 
+    # -- apply_model of Demucs v4 ("ht") and v3 ("hd"): one body per verb, the generation picks the asx_<gen>_* entry point ------
     @staticmethod
     def _offs(shifts, offsets):
         return (C.c_int64 * shifts)(*[int(o) for o in offsets]) if shifts else None
 
-    def ht_plan(self, n, shifts=0, offsets=None, overlap=0.25):
+    def _apply_demix(self, gen, n_sources, mix, shifts, offsets, overlap, standardize, swap01):
+        mix = _f32(mix)
+        if mix.ndim != 2 or mix.shape[0] != 2:
+            raise ValueError(f"Expected a 2-channel audio signal, but got shape {mix.shape}")
+        if shifts and (offsets is None or len(offsets) != shifts):
+            raise ValueError("shifts > 0 needs one offset per shift")
+        out = np.empty((n_sources, 2, mix.shape[1]), np.float32)
+        flags = (1 if standardize else 0) | (2 if swap01 else 0)
+        self._check(getattr(self._lib, f"asx_{gen}_demix")(self._h, _ptr(mix), mix.shape[1], int(shifts), self._offs(shifts, offsets),
+                                                          float(overlap), flags, _ptr(out)))
+        return out
+
+    def _apply_demix_dev(self, gen, mix_ptr, n, out_ptr, shifts, offsets, overlap, flags, stream):
+        self._check(getattr(self._lib, f"asx_{gen}_demix_dev")(self._h, mix_ptr, n, int(shifts), self._offs(shifts, offsets),
+                                                              float(overlap), flags, out_ptr, stream or None))
+
+    def _apply_plan(self, gen, n, shifts, offsets, overlap):
         k, c = C.c_int32(), C.c_int64()
-        self._check(self._lib.asx_ht_plan(self._h, n, int(shifts), self._offs(shifts, offsets), float(overlap), C.byref(k), C.byref(c)))
+        self._check(getattr(self._lib, f"asx_{gen}_plan")(self._h, n, int(shifts), self._offs(shifts, offsets), float(overlap),
+                                                         C.byref(k), C.byref(c)))
         return {"n_chunks": k.value, "chunk_size": c.value}
 
+    def _apply_segments_dev(self, gen, mix_ptr, n, k0, k1, out_ptr, shifts, offsets, overlap, flags, stream):
+        self._check(getattr(self._lib, f"asx_{gen}_segments_dev")(self._h, mix_ptr, n, int(shifts), self._offs(shifts, offsets),
+                                                                 float(overlap), flags, k0, k1, out_ptr, stream or None))
+
+    def _apply_fold_dev(self, gen, mix_ptr, n, chunks_ptr, out_ptr, shifts, offsets, overlap, flags, stream):
+        self._check(getattr(self._lib, f"asx_{gen}_fold_dev")(self._h, mix_ptr, n, int(shifts), self._offs(shifts, offsets),
+                                                             float(overlap), flags, chunks_ptr, out_ptr, stream or None))
+
+    def ht_plan(self, n, shifts=0, offsets=None, overlap=0.25):
+        return self._apply_plan("ht", n, shifts, offsets, overlap)
+
     def ht_segments_dev(self, mix_ptr, n, k0, k1, out_ptr, shifts=0, offsets=None, overlap=0.25, flags=0, stream=0):
-        self._check(self._lib.asx_ht_segments_dev(self._h, mix_ptr, n, int(shifts), self._offs(shifts, offsets), float(overlap), flags,
-                                                  k0, k1, out_ptr, stream or None))
+        self._apply_segments_dev("ht", mix_ptr, n, k0, k1, out_ptr, shifts, offsets, overlap, flags, stream)
 
     def ht_fold_dev(self, mix_ptr, n, chunks_ptr, out_ptr, shifts=0, offsets=None, overlap=0.25, flags=0, stream=0):
-        self._check(self._lib.asx_ht_fold_dev(self._h, mix_ptr, n, int(shifts), self._offs(shifts, offsets), float(overlap), flags,
-                                              chunks_ptr, out_ptr, stream or None))
+        self._apply_fold_dev("ht", mix_ptr, n, chunks_ptr, out_ptr, shifts, offsets, overlap, flags, stream)
+
+    def hd_plan(self, n, shifts=0, offsets=None, overlap=0.25):
+        return self._apply_plan("hd", n, shifts, offsets, overlap)
+
+    def hd_segments_dev(self, mix_ptr, n, k0, k1, out_ptr, shifts=0, offsets=None, overlap=0.25, flags=0, stream=0):
+        self._apply_segments_dev("hd", mix_ptr, n, k0, k1, out_ptr, shifts, offsets, overlap, flags, stream)
+
+    def hd_fold_dev(self, mix_ptr, n, chunks_ptr, out_ptr, shifts=0, offsets=None, overlap=0.25, flags=0, stream=0):
+        self._apply_fold_dev("hd", mix_ptr, n, chunks_ptr, out_ptr, shifts, offsets, overlap, flags, stream)
 
     def pcm16(self, stem: np.ndarray, max_peak: float = 1.0, min_peak=None):
         """write_audio_pydub's array work: stem [N, 2] (or [2, N] planar with planar=True semantics when shape[0] == 2)

@@ -149,8 +149,8 @@ class DemucsAdapter(_SiblingAdapter):
         self.kw = dict(shifts=shifts, offsets=offsets, overlap=overlap)
         self.flags = flags
         self.stems = self.out_stems = len((engine.hd_cfg if v3 else engine.ht_cfg).sources)
-        self._plan, self._segments, self._fold = ((engine.hd_plan, engine.hd_segments_dev, engine.hd_fold_dev) if v3 else
-                                                  (engine.ht_plan, engine.ht_segments_dev, engine.ht_fold_dev))
+        gen = "hd" if v3 else "ht"
+        self._plan, self._segments, self._fold = (getattr(engine, f"{gen}_{verb}") for verb in ("plan", "segments_dev", "fold_dev"))
 
     def plan(self, n):
         return self._plan(n, **self.kw)
