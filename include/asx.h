@@ -390,6 +390,32 @@ int asx_hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t n_samples, 
 int asx_hd_fold_dev(asx_engine *e, const float *mix_dev, int64_t n_samples, int32_t shifts, const int64_t *offsets, double overlap,
                     uint32_t flags, const float *chunk_out_dev, float *out_dev, void *stream);
 
+/* ---- Demucs v4 / v3: a batch of songs in one call (the sibling of asx_demix_batch_dev) ----
+ * The segments of ALL songs form one list (song-major, each song's in the order of asx_ht_plan) and share the forwards: v4 runs
+ * the list in batches of up to max_batch (default 32) segments whichever song a segment belongs to; v3 groups equal chunk
+ * lengths across songs (up to max_batch per group).  Every song keeps its own standardisation statistics; one segmented fold per
+ * shift index (and 32 songs) writes every song's out [S, 2, n_samples], which equals what asx_ht_demix_dev / asx_hd_demix_dev
+ * writes for that song alone, bit for bit.  `songs` and every `offsets` array are HOST memory, read during the call; shifts,
+ * overlap and flags (ASX_HT_*) hold for all songs.  The call only enqueues work on `stream`.  Nothing is enqueued when any song
+ * is invalid (null pointer, n_samples < 2 as for the single-song calls, an offset outside [0, samplerate / 2], offsets == NULL
+ * with shifts > 0); n_songs == 0 is ASX_OK.  Memory: the engine's chunk slab grows to the pool's TOTAL segment count (S * 2 *
+ * segment_samples floats per segment): a caller with more songs than that allows splits them over several calls.  v3 also
+ * grows its group workspaces: the chunk groups that advance together are full-length ones here, where one song has a single
+ * full-length group and short tails, so the groups of one round are bounded to 2 * max_batch segments' worth of samples
+ * (about 70 GB of workspace for 44-s chunks at the default max_batch of 16, against about 30 GB for one 4-minute song).  With
+ * more than 32 songs the fold takes one launch per shift index and 32 songs.  (Added within ABI 7: new functions and a new
+ * struct only.) */
+typedef struct asx_apply_song {
+  const float *mix_dev;     /* [2, n_samples] */
+  float *out_dev;           /* [S, 2, n_samples] */
+  int64_t n_samples;
+  const int64_t *offsets;   /* HOST: `shifts` draws for this song; NULL iff shifts == 0 */
+} asx_apply_song;
+int asx_ht_demix_batch_dev(asx_engine *e, const asx_apply_song *songs, int32_t n_songs, int32_t shifts, double overlap, uint32_t flags,
+                           void *stream);
+int asx_hd_demix_batch_dev(asx_engine *e, const asx_apply_song *songs, int32_t n_songs, int32_t shifts, double overlap, uint32_t flags,
+                           void *stream);
+
 /* ---- VR architecture -----------------------------------------------------------------
  * Replaces nets.determine_model_capacity(...) + load_state_dict (architectures/vr_separator.py:168-176,
  * uvr_lib_v5/vr_network/nets.py:65-93), VRSeparator.loading_mix (:255-291), inference_vr (:293-366) and spec_to_wav
@@ -531,6 +557,7 @@ int asx_invert_stem(asx_engine *e, const float *mix_host, const float *stem_host
  * "wino6_launches" (conv_wino6_kernel: Winograd F(2x2,3x3) on the 16-bit pipe), "wino6h_launches" (those on the fp16 x 3 arithmetic),
  * "conv3h_launches" (ABI 7: conv3h_kernel, the direct fp16 x 3 convolution of the 48-channel level),
  * "down6_launches" / "up6_launches" (ABI 7: conv_down6_kernel / conv_up6_kernel, the level-change convs on the 16-bit matrix pipe),
+ * "hd_rounds" (ABI 7: rounds of chunk groups the Demucs v3 forward has run -- the groups of a round share the BLSTM launches),
  * "tdf3_pair_image_launches" (ABI 7: the tdf3_kernel launches that read their x operand as a pair image -- option "gemm_pair_images", experimental builds).
  * ASX_ERR_INVALID for an unknown name. */
 int asx_counter(const asx_engine *e, const char *name, int64_t *out);

@@ -84,6 +84,9 @@ class DemucsSeparator(CommonSeparator):
             source = self.demix_demucs(mix)
             self.clear_gpu_cache()
 
+        return self._emit_stems(source, views, custom_output_names)
+
+    def _emit_stems(self, source, views, custom_output_names):
         n = len(source)
         self.demucs_source_map = {2: DEMUCS_2_SOURCE_MAPPER, 6: DEMUCS_6_SOURCE_MAPPER}.get(n, DEMUCS_4_SOURCE_MAPPER)
         files = []
@@ -95,3 +98,76 @@ class DemucsSeparator(CommonSeparator):
             self.final_process(path, views[index] if views is not None else source[index].T, stem_name)
             files.append(path)
         return files
+
+    # ---- a batch of files in one pooled engine call -----------------------------------------------------------------
+    _PER_FILE = ("audio_file_path", "audio_file_base", "input_bit_depth", "input_subtype", "_file_seconds")
+
+    def _load_for_batch(self, path):
+        """One file as ``separate`` would load it: (device mix [2, N] or None, host mix or None)."""
+        self._reset_file_state()
+        self._begin_file(path)
+        mix = self._device_mix(self.audio_file_path)
+        if mix is not None:
+            return mix, None
+        mix = np.ascontiguousarray(self.prepare_mix(self.audio_file_path), np.float32)
+        if mix.ndim != 2 or mix.shape[0] != 2:
+            raise ValueError(f"Expected a 2-channel audio signal, but got shape {mix.shape}")
+        return None, mix
+
+    def separate_many(self, paths, custom_output_names=None):
+        """``separate`` for a list of files with ONE pooled demix (``DemucsDemixer.demix_many_dev``: the segments of all files
+        share the forwards), then each file's stems go through the same writer and naming code.  Returns one list of output
+        names per input, in order.  The shift offsets are drawn in file order, so under one ``random.seed`` the files equal
+        those of ``separate(path)`` called per path.
+
+        A file that cannot be used fails alone: its entry is an empty list, the exception is logged and kept in
+        ``self.batch_errors[index]``.  ``custom_output_names`` applies to every file, as it does in ``separate``."""
+        from ..demucs import _cuda_ready
+        paths = list(paths)
+        self.batch_errors = {}
+        dm = self.load_model()
+        dm.shifts, dm.overlap, dm.segments_enabled = self.shifts, self.overlap, self.segments_enabled
+        loaded = []                                       # (index, per-file state, device mix, host mix)
+        for i, path in enumerate(paths):
+            try:
+                dev_mix, host_mix = self._load_for_batch(path)
+            except Exception as e:                        # this file only
+                self.logger.error(f"{path}: {e}")
+                self.batch_errors[i] = e
+                continue
+            loaded.append((i, {k: getattr(self, k) for k in self._PER_FILE}, dev_mix, host_mix))
+        results = [[] for _ in paths]
+        if not loaded:
+            self._reset_file_state()
+            return results
+        on_device = self.segments_enabled and _cuda_ready()
+        if on_device:
+            import torch
+            dev = torch.device("cuda", dm.device)
+            stems = dm.demix_many_dev([d if d is not None else torch.from_numpy(h).to(dev) for _, _, d, h in loaded])
+        else:                                             # segments_enabled=False windows on the host; so does an engine double
+            stems = dm.demix_many([h if h is not None else d.cpu().numpy() for _, _, d, h in loaded])
+        self.engine = dm.engine
+        self._in_separate = True
+        try:
+            for (i, state, dev_mix, _), out in zip(loaded, stems):
+                self._reset_file_state()
+                for k, v in state.items():
+                    setattr(self, k, v)
+                try:
+                    if on_device and dev_mix is not None:   # decoded on the device: the stems stay there for the writer, as in separate()
+                        source, views = self._host_planar_stems(out)
+                        self._sync()
+                    else:
+                        source, views = (out.cpu().numpy() if on_device else out), None
+                    results[i] = self._emit_stems(source, views, custom_output_names)
+                except Exception as e:
+                    self.logger.error(f"{state['audio_file_path']}: {e}")
+                    self.batch_errors[i] = e
+        except BaseException:
+            self._in_separate = False
+            self._drain_writes(raise_errors=False)
+            raise
+        self._in_separate = False
+        self._drain_writes()
+        return results

@@ -57,3 +57,49 @@ static inline bool apply_plan_build(int64_t N, int64_t segment, int64_t samplera
   }
   return true;
 }
+
+// ---- a pool of songs (asx_ht_demix_batch_dev / asx_hd_demix_batch_dev) -------------------------------------------------
+// One global segment list, song-major; inside a song the order of its own ApplyPlan.  `shifts[song * nsh + si]` is that song's
+// shift si with `first` moved into the global list (what the fold needs); stride / segment / max_shift are the same for every
+// song of a call.
+struct ApplyPoolSong {
+  int64_t N;
+  const int64_t *offsets;   // `shifts` draws of this song (unused when shifts == 0)
+};
+struct ApplyPoolPlan {
+  int64_t stride = 0, segment = 0, max_shift = 0;
+  int nsh = 1;                            // shift passes per song: max(shifts, 1)
+  std::vector<int> song;                  // per segment: its song
+  std::vector<int64_t> starts, clen;      // per segment, as ApplyPlan
+  std::vector<ApplyShift> shifts;         // [n_songs * nsh]
+};
+
+// false (and `err`, naming the song) when the plan of any one song is rejected: the caller then enqueues nothing.
+static inline bool apply_pool_build(const ApplyPoolSong *songs, int n_songs, int64_t segment, int64_t samplerate, int32_t shifts,
+                                    double overlap, bool centered, ApplyPoolPlan &pp, std::string &err) {
+  pp = ApplyPoolPlan();
+  pp.nsh = shifts > 0 ? shifts : 1;
+  pp.segment = segment;
+  ApplyPlan p;
+  for (int i = 0; i < n_songs; ++i) {
+    std::string why;
+    if (songs[i].N < 2) why = "n_samples must be >= 2";   // as the single-song entry points: the unbiased std needs two samples
+    else if (shifts > 0 && !songs[i].offsets) why = "shifts > 0 needs the offsets array";
+    else apply_plan_build(songs[i].N, segment, samplerate, shifts, songs[i].offsets, overlap, centered, p, why);
+    if (!why.empty()) {
+      err = "song " + std::to_string(i) + ": " + why;
+      return false;
+    }
+    pp.stride = p.stride;
+    pp.max_shift = p.max_shift;
+    const int base = (int)pp.starts.size();
+    for (ApplyShift sh : p.shifts) {
+      sh.first += base;
+      pp.shifts.push_back(sh);
+    }
+    pp.starts.insert(pp.starts.end(), p.starts.begin(), p.starts.end());
+    pp.clen.insert(pp.clen.end(), p.clen.begin(), p.clen.end());
+    pp.song.insert(pp.song.end(), p.starts.size(), i);
+  }
+  return true;
+}

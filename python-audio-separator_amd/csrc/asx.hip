@@ -2022,6 +2022,17 @@ static int demucs_demix_dev(asx_engine *e, bool v3, const char *fn, const float 
   return apply_demix_dev(e, apply_net(e, v3), mix_dev, N, shifts, offsets, overlap, flags, out_dev, reinterpret_cast<hipStream_t>(stream));
 }
 
+static int demucs_demix_batch_dev(asx_engine *e, bool v3, const char *fn, const asx_apply_song *songs, int32_t n_songs, int32_t shifts,
+                                  double overlap, uint32_t flags, void *stream) {
+  REQUIRE(e && n_songs >= 0 && (songs || n_songs == 0), "%s: null argument", fn);
+  REQUIRE(shifts >= 0, "%s: shifts must be >= 0", fn);
+  REQUIRE(overlap >= 0.0 && overlap < 1.0, "overlap must be in [0, 1)");
+  CHK(demucs_ready(e, v3, fn));
+  if (n_songs == 0) return ASX_OK;
+  HIPCHK(hipSetDevice(e->device));
+  return apply_demix_pool_dev(e, apply_net(e, v3), songs, n_songs, shifts, overlap, flags, reinterpret_cast<hipStream_t>(stream));
+}
+
 static int demucs_demix(asx_engine *e, bool v3, const char *fn, const float *mix_host, int64_t N, int32_t shifts, const int64_t *offsets,
                         double overlap, uint32_t flags, float *out_host) {
   REQUIRE(e && mix_host && out_host && N >= 2, "%s: bad argument", fn);
@@ -2064,6 +2075,14 @@ int asx_ht_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shi
 int asx_hd_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
                      uint32_t flags, float *out_dev, void *stream) {
   return demucs_demix_dev(e, true, "asx_hd_demix_dev", mix_dev, N, shifts, offsets, overlap, flags, out_dev, stream);
+}
+int asx_ht_demix_batch_dev(asx_engine *e, const asx_apply_song *songs, int32_t n_songs, int32_t shifts, double overlap, uint32_t flags,
+                           void *stream) {
+  return demucs_demix_batch_dev(e, false, "asx_ht_demix_batch_dev", songs, n_songs, shifts, overlap, flags, stream);
+}
+int asx_hd_demix_batch_dev(asx_engine *e, const asx_apply_song *songs, int32_t n_songs, int32_t shifts, double overlap, uint32_t flags,
+                           void *stream) {
+  return demucs_demix_batch_dev(e, true, "asx_hd_demix_batch_dev", songs, n_songs, shifts, overlap, flags, stream);
 }
 int asx_ht_demix(asx_engine *e, const float *mix_host, int64_t N, int32_t shifts, const int64_t *offsets, double overlap,
                  uint32_t flags, float *out_host) {
@@ -2197,6 +2216,7 @@ int asx_counter(const asx_engine *e, const char *name, int64_t *out) {
   else if (nm == "tdf3_pair_image_launches") *out = (int64_t)g_tdf3ps_launches.load();
   else if (nm == "down6_launches") *out = (int64_t)g_down6_launches.load();
   else if (nm == "up6_launches") *out = (int64_t)g_up6_launches.load();
+  else if (nm == "hd_rounds") *out = (int64_t)g_hd_rounds.load();
   else {
     set_err("asx_counter: unknown counter '%s'", name);
     return ASX_ERR_INVALID;

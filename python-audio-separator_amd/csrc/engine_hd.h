@@ -671,7 +671,9 @@ static int hd_phase_after(asx_engine *e, const HdGroup &gr, bool levelZ, size_t 
 }
 
 // all groups, phase by phase (G[0] must be the engine's own nets)
+static std::atomic<long long> g_hd_rounds{0};   // calls of hd_forward_groups since the process started (asx_counter "hd_rounds")
 static int hd_forward_groups(asx_engine *e, std::vector<HdGroup> &G, hipStream_t s) {
+  g_hd_rounds.fetch_add(1);
   HtNet *const ht0 = e->ht;
   HdNet *const hd0 = e->hd;
   int rc = ASX_OK;
@@ -751,32 +753,36 @@ static double hd_flops(const asx_engine *e, int64_t L) {
 // launches (hd_forward_groups; HD_MAX_GROUPS is in knobs.h beside ASX_HD_GROUPS).  (Running the tail groups on a second stream instead was
 // measured and gave nothing: the two HSA queues never had kernels in flight together)
 
-static int hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const ApplyPlan &p, uint32_t flags, int k0, int k1, float *chunk_out,
-                           hipStream_t s) {
+// `clen[k]`: the length of listed chunk k, whose result goes to row k of chunk_out; gather(idx, B, L, seg) fills seg [B, 2, L] from the
+// listed chunks idx[0 .. B).  `budget` (samples, 0 = none) bounds what the groups of one round hold together: every group after
+// the first runs on an engine clone with a workspace of its own (~2.2 GB per 44-s chunk), and a round whose groups are ALL full
+// (which one song never forms: it has one full-length group and short tails) would take hd_groups x max_batch chunks of it.
+template <class Gather>
+static int hd_run_chunks(asx_engine *e, const std::vector<int64_t> &clen, int64_t segment, int64_t budget, float *chunk_out, hipStream_t s,
+                         Gather gather) {
   HdNet &h = *e->hd;
   HtNet &n = *e->ht;
   const int S = h.cfg.n_sources;
-  const int standardize = (flags & ASX_HT_STANDARDIZE) ? 1 : 0;
-  if (k1 <= k0) return ASX_OK;
-  if (standardize) CHK(ht_ref_stats(e, mix_dev, N, s));
+  const int nk = (int)clen.size();
   std::vector<int> order;
-  for (int k = k0; k < k1; ++k) order.push_back(k);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return p.clen[a] > p.clen[b]; });
+  for (int k = 0; k < nk; ++k) order.push_back(k);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return clen[a] > clen[b]; });
   // 16: the BLSTM recurrences cost the same 200 steps whatever the batch, so the equal-length chunks of a song go together
   // (4-min song, 44-s chunks: 730 -> 789x real time against batches of 4; ~2.2 GB of workspace per 44-s chunk)
   const int maxB = h.cfg.max_batch > 0 ? h.cfg.max_batch : 16;
-  const int nk = (int)order.size();
-  std::vector<int64_t> st(nk);
-  for (int i = 0; i < nk; ++i) st[i] = p.starts[order[i]];
   const int max_groups = knobs().hd_groups;
   int i = 0;
   while (i < nk) {
     std::vector<HdGroup> G;
     std::vector<int> first;
+    int64_t held = 0;
     while (i < nk && (int)G.size() < max_groups) {
-      const int64_t L = p.clen[order[i]];
+      const int64_t L = clen[order[i]];
       int j = i;
-      while (j < nk && p.clen[order[j]] == L && j - i < maxB) ++j;
+      while (j < nk && clen[order[j]] == L && j - i < maxB) ++j;
+      const int B = j - i;
+      if (budget > 0 && !G.empty() && held + (int64_t)B * L > budget) break;
+      held += (int64_t)B * L;
       HtNet *gn = &n;
       HdNet *gh = &h;
       if (!G.empty()) {
@@ -784,10 +790,9 @@ static int hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const
         gn = e->ht_cl[G.size() - 1];
         gh = e->hd_cl[G.size() - 1];
       }
-      const int B = j - i;
       CHK(gn->seg.ensure((size_t)B * 2 * L * 4));
       CHK(gh->tmp_out.ensure((size_t)B * S * 2 * L * 4));
-      ht_gather_launch(mix_dev, N, st.data() + i, B, L, reinterpret_cast<const double *>(n.ref_acc.p), standardize, gn->seg.f(), s);
+      gather(order.data() + i, B, L, gn->seg.f());
       HIPCHK(hipGetLastError());
       G.push_back(HdGroup{gn, gh, B, L, gn->seg.f(), gh->tmp_out.f(), HdDims{}});
       first.push_back(i);
@@ -796,15 +801,49 @@ static int hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const
     CHK(hd_forward_groups(e, G, s));
     for (size_t gi = 0; gi < G.size(); ++gi)
       for (int bi = 0; bi < G[gi].B; ++bi)
-        HIPCHK(hipMemcpy2DAsync(chunk_out + (size_t)(order[first[gi] + bi] - k0) * S * 2 * p.segment, (size_t)p.segment * 4,
+        HIPCHK(hipMemcpy2DAsync(chunk_out + (size_t)order[first[gi] + bi] * S * 2 * segment, (size_t)segment * 4,
                                 G[gi].out + (size_t)bi * S * 2 * G[gi].L, (size_t)G[gi].L * 4, (size_t)G[gi].L * 4, (size_t)S * 2,
                                 hipMemcpyDeviceToDevice, s));
   }
   return ASX_OK;
 }
 
-// what apply_plan / apply_fold_dev / apply_demix_dev (engine_ht.h) need to know about the net the caller means
+static int hd_segments_dev(asx_engine *e, const float *mix_dev, int64_t N, const ApplyPlan &p, uint32_t flags, int k0, int k1, float *chunk_out,
+                           hipStream_t s) {
+  HtNet &n = *e->ht;
+  const int standardize = (flags & ASX_HT_STANDARDIZE) ? 1 : 0;
+  if (k1 <= k0) return ASX_OK;
+  if (standardize) CHK(ht_ref_stats(e, mix_dev, N, s));
+  const std::vector<int64_t> clen(p.clen.begin() + k0, p.clen.begin() + k1);
+  std::vector<int64_t> st;
+  return hd_run_chunks(e, clen, p.segment, 0, chunk_out, s, [&](const int *idx, int B, int64_t L, float *seg) {
+    st.resize((size_t)B);
+    for (int b = 0; b < B; ++b) st[b] = p.starts[k0 + idx[b]];
+    ht_gather_launch(mix_dev, N, st.data(), B, L, reinterpret_cast<const double *>(n.ref_acc.p), standardize, seg, s);
+  });
+}
+
+// The same over the pooled segment list of several songs (apply_demix_pool_dev, engine_ht.h): sorted by length, stably and
+// descending, so the full-length chunks of ALL songs fill groups of max_batch and equal tails of different songs share a group.
+// The groups of one round hold at most 2 x max_batch segments' worth of samples (hd_run_chunks: the clone workspaces; 32 44-s
+// chunks, ~70 GB, at the default max_batch, where one song peaks at about half of that).
+static int hd_segments_pool_dev(asx_engine *e, const ApplyPoolPlan &pp, const HtPoolRow *rows, uint32_t flags, float *chunk_out,
+                                hipStream_t s) {
+  HtNet &n = *e->ht;
+  const int standardize = (flags & ASX_HT_STANDARDIZE) ? 1 : 0;
+  if (pp.starts.empty()) return ASX_OK;
+  const int maxB = e->hd->cfg.max_batch > 0 ? e->hd->cfg.max_batch : 16;
+  std::vector<HtPoolRow> st;
+  return hd_run_chunks(e, pp.clen, pp.segment, 2 * (int64_t)maxB * pp.segment, chunk_out, s, [&](const int *idx, int B, int64_t L, float *seg) {
+    st.resize((size_t)B);
+    for (int b = 0; b < B; ++b) st[b] = rows[idx[b]];
+    ht_gather_pool_launch(st.data(), B, L, reinterpret_cast<const double *>(n.ref_acc.p), standardize, seg, s);
+  });
+}
+
+// what apply_plan / apply_fold_dev / apply_demix_dev / apply_demix_pool_dev (engine_ht.h) need to know about the net the caller means
 static ApplyNet apply_net(const asx_engine *e, bool v3) {
-  if (v3) return ApplyNet{e->hd->cfg.n_sources, false, e->hd->cfg.segment_samples, e->hd->cfg.samplerate, hd_segments_dev};
-  return ApplyNet{e->ht->cfg.n_sources, true, e->ht->L[0], e->ht->cfg.samplerate, ht_segments_dev};
+  if (v3)
+    return ApplyNet{e->hd->cfg.n_sources, false, e->hd->cfg.segment_samples, e->hd->cfg.samplerate, hd_segments_dev, hd_segments_pool_dev};
+  return ApplyNet{e->ht->cfg.n_sources, true, e->ht->L[0], e->ht->cfg.samplerate, ht_segments_dev, ht_segments_pool_dev};
 }

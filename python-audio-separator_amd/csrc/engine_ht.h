@@ -1206,11 +1206,14 @@ static double ht_flops(const asx_engine *e) {
 // v4 (HTDemucs) runs every chunk as a full training segment with the chunk centred inside it, in fixed-length batches
 // (ht_segments_dev); v3 (HDemucs, engine_hd.h) runs the chunk at its own length, grouped by length (hd_segments_dev).
 using ApplySegments = int (*)(asx_engine *, const float *, int64_t, const ApplyPlan &, uint32_t, int, int, float *, hipStream_t);
+// every segment of a pool of songs (rows[k] = where segment k of the pooled list reads) -> chunk_out [all segments, S, 2, segment]
+using ApplyPoolSegments = int (*)(asx_engine *, const ApplyPoolPlan &, const HtPoolRow *, uint32_t, float *, hipStream_t);
 struct ApplyNet {
   int S;                         // sources
   bool centered;                 // v4: chunks centred in a full segment (ApplyPlan::starts, the fold's `center`)
   int64_t segment, samplerate;   // rows of the chunk slab are `segment` long
   ApplySegments segments;
+  ApplyPoolSegments pool_segments;
 };
 
 static int apply_plan(const ApplyNet &a, int64_t N, int32_t shifts, const int64_t *offsets, double overlap, ApplyPlan &p) {
@@ -1286,4 +1289,86 @@ static int apply_demix_dev(asx_engine *e, const ApplyNet &a, const float *mix_de
   CHK(n.chunk_out.ensure((size_t)nseg * a.S * 2 * p.segment * 4));
   CHK(a.segments(e, mix_dev, N, p, flags, 0, nseg, n.chunk_out.f(), s));
   return apply_fold_dev(e, a, mix_dev, N, p, flags, n.chunk_out.f(), out_dev, s);
+}
+
+// ---- the same for a pool of songs: the segments of all of them share the forwards ---------------------------------------------
+// v4: the pooled list in forwards of even_batches(total, max_batch or 32) segments, whichever song a segment belongs to
+static int ht_segments_pool_dev(asx_engine *e, const ApplyPoolPlan &pp, const HtPoolRow *rows, uint32_t flags, float *chunk_out,
+                                hipStream_t s) {
+  HtNet &n = *e->ht;
+  const int S = n.cfg.n_sources;
+  const int64_t TL = n.L[0];
+  const int standardize = (flags & ASX_HT_STANDARDIZE) ? 1 : 0;
+  const int nk = (int)pp.starts.size();
+  if (nk == 0) return ASX_OK;
+  const int per = even_batches(nk, n.cfg.max_batch > 0 ? n.cfg.max_batch : 32);
+  CHK(n.seg.ensure((size_t)per * 2 * TL * 4));
+  for (int j = 0; j < nk; j += per) {
+    const int B = std::min(per, nk - j);
+    ht_gather_pool_launch(rows + j, B, TL, reinterpret_cast<const double *>(n.ref_acc.p), standardize, n.seg.f(), s);
+    HIPCHK(hipGetLastError());
+    CHK(ht_forward_dev(e, n.seg.f(), B, chunk_out + (size_t)j * S * 2 * TL, s));
+  }
+  return ASX_OK;
+}
+
+// songs[i].mix_dev [2, N_i] -> songs[i].out_dev [S, 2, N_i], each what apply_demix_dev writes for that song alone.  Every song is
+// checked and planned before anything is enqueued.  The chunk slab holds ALL segments of the pool at once (n_segments * S * 2 *
+// segment floats): walking a large pool in waves is left to the caller.  Song i keeps its standardisation statistics in slot i
+// of ref_acc, computed by the launches of ht_ref_stats (one mono + one reduction per song).  The fold takes one launch per shift
+// index and 32 songs (their arguments travel by value, like the gather's).
+static int apply_demix_pool_dev(asx_engine *e, const ApplyNet &a, const asx_apply_song *songs, int n_songs, int32_t shifts, double overlap,
+                                uint32_t flags, hipStream_t s) {
+  HtNet &n = *e->ht;
+  std::vector<ApplyPoolSong> ps((size_t)n_songs);
+  for (int i = 0; i < n_songs; ++i) {
+    REQUIRE(songs[i].mix_dev && songs[i].out_dev, "song %d: null pointer", i);
+    ps[i] = ApplyPoolSong{songs[i].n_samples, songs[i].offsets};
+  }
+  ApplyPoolPlan pp;
+  std::string err;
+  REQUIRE(apply_pool_build(ps.data(), n_songs, a.segment, a.samplerate, shifts, overlap, a.centered, pp, err), "%s", err.c_str());
+  const int S = a.S;
+  const int64_t TL = pp.segment;
+  const int standardize = (flags & ASX_HT_STANDARDIZE) ? 1 : 0;
+  const int swap01 = (flags & ASX_HT_SWAP01) ? 1 : 0;
+  const int nseg = (int)pp.starts.size();
+  CHK(n.chunk_out.ensure((size_t)nseg * S * 2 * TL * 4));
+  if (standardize) {
+    int64_t maxN = 0;
+    for (int i = 0; i < n_songs; ++i) maxN = std::max(maxN, songs[i].n_samples);
+    CHK(n.ref.ensure((size_t)maxN * 4));
+    CHK(n.ref_acc.ensure((size_t)n_songs * 16));
+    for (int i = 0; i < n_songs; ++i) {
+      const int64_t N = songs[i].n_samples;
+      hipLaunchKernelGGL(ht_mono_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, songs[i].mix_dev, N, n.ref.f());
+      HIPCHK(hipGetLastError());
+      CHK(ht_stats(e, n.ref.f(), 1, 1, N, N, 1, 1, 1, reinterpret_cast<double *>(n.ref_acc.p) + 2 * i, s));
+    }
+  }
+  std::vector<HtPoolRow> rows((size_t)nseg);
+  for (int k = 0; k < nseg; ++k) {
+    const int i = pp.song[k];
+    rows[k] = HtPoolRow{songs[i].mix_dev, songs[i].n_samples, pp.starts[k], i, 0};
+  }
+  CHK(a.pool_segments(e, pp, rows.data(), flags, n.chunk_out.f(), s));
+  for (int si = 0; si < pp.nsh; ++si)
+    for (int i0 = 0; i0 < n_songs; i0 += 32) {
+      HtFoldSongs fs{};
+      fs.n = std::min(32, n_songs - i0);
+      double bytes = 0.0;
+      for (int j = 0; j < fs.n; ++j) {
+        const ApplyShift &sh = pp.shifts[(size_t)(i0 + j) * pp.nsh + si];
+        const int64_t N = songs[i0 + j].n_samples;
+        fs.v[j] = HtFoldSong{songs[i0 + j].out_dev, N, sh.VL, pp.max_shift - sh.offset, sh.first, sh.nk, i0 + j, fs.blocks};
+        fs.blocks += (int)((N + 255) / 256);
+        bytes += 4.0 * ((double)sh.nk * S * 2 * TL + 2.0 * S * 2 * N);
+      }
+      CHK(timed(e, ASX_PROF_FINALIZE, 0.0, bytes, s, [&]() {
+        hipLaunchKernelGGL(ht_fold_pool_kernel, dim3((unsigned)fs.blocks, S * 2), dim3(256), 0, s, n.chunk_out.f(), fs, S * 2, TL, pp.stride,
+                           pp.segment, n.fold_w.f(), si == 0 ? 1 : 0, si == pp.nsh - 1 ? 1 : 0, pp.nsh, reinterpret_cast<const double *>(n.ref_acc.p),
+                           standardize, swap01, a.centered ? 1 : 0);
+      }));
+    }
+  return ASX_OK;
 }

@@ -1112,6 +1112,106 @@ __global__ __launch_bounds__(256) void ht_fold_kernel(const float *__restrict__ 
   *op = v;
 }
 
+// ---- a pool of songs (asx_ht_demix_batch_dev / asx_hd_demix_batch_dev): twins of ht_gather_kernel and ht_fold_kernel ----------
+// Every row of a forward batch may come from another song: song pointer, length, start and the song's slot of ref_acc travel BY
+// VALUE like HtStarts (up to 32 rows per launch, 32 bytes each).  Per element the arithmetic of ht_gather_kernel.
+struct HtPoolRow {
+  const float *song;   // [2, N]
+  int64_t N, start;
+  int slot, pad_;
+};
+struct HtPoolRows {
+  HtPoolRow v[32];
+};
+__global__ __launch_bounds__(256) void ht_gather_pool_kernel(HtPoolRows rows, int64_t L, const double *__restrict__ ref_acc, int standardize,
+                                                             float *__restrict__ seg) {
+  const int b = blockIdx.z, ch = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= L) return;
+  const float *__restrict__ song = rows.v[b].song;
+  const int64_t N = rows.v[b].N;
+  const int64_t j = rows.v[b].start + i;
+  float v = 0.f;
+  if (j >= 0 && j < N) {
+    v = song[(int64_t)ch * N + j];
+    if (standardize) {
+      float mean, stdv;
+      sample_mean_std(ref_acc, rows.v[b].slot, (double)N, mean, stdv);
+      v = (v - mean) / stdv;
+    }
+  }
+  seg[((int64_t)b * 2 + ch) * L + i] = v;
+}
+
+static inline void ht_gather_pool_launch(const HtPoolRow *host_rows, int B, int64_t L, const double *ref_acc, int standardize, float *seg,
+                                         hipStream_t s) {
+  for (int b0 = 0; b0 < B; b0 += 32) {
+    const int nb = B - b0 < 32 ? B - b0 : 32;
+    HtPoolRows r{};
+    for (int i = 0; i < nb; ++i) r.v[i] = host_rows[b0 + i];
+    hipLaunchKernelGGL(ht_gather_pool_kernel, dim3((unsigned)((L + 255) / 256), 2, nb), dim3(256), 0, s, r, L, ref_acc, standardize,
+                       seg + (size_t)b0 * 2 * L);
+  }
+}
+
+// The fold of ONE shift index for up to 32 songs in one launch.  blockIdx.x runs over the songs' sample ranges laid end to end,
+// each rounded up to whole blocks (`block0` = the song's first block; songs past `n` are never reached), so a block belongs to
+// one song and finds it with a scan of launch arguments.  From there on it is ht_fold_kernel per sample: the same k loop, first /
+// last / shifts handling, de-standardisation (the song's own ref_acc slot), swap01 and centre trim, on that song's rows of the
+// pooled chunk slab and that song's out [S, 2, N].
+struct HtFoldSong {
+  float *out;                    // [S, 2, N]
+  int64_t N, VL, lead;
+  int first, nk, slot, block0;   // rows [first, first + nk) of the pooled slab
+};
+struct HtFoldSongs {
+  HtFoldSong v[32];
+  int n, blocks;                 // songs in this launch, blocks they take together
+};
+__global__ __launch_bounds__(256) void ht_fold_pool_kernel(const float *__restrict__ chunk_all, HtFoldSongs songs, int SC, int64_t TL,
+                                                           int64_t stride, int64_t segment, const float *__restrict__ weight, int first,
+                                                           int last, int shifts, const double *__restrict__ ref_acc, int standardize,
+                                                           int swap01, int center) {
+  const int sc_ = blockIdx.y;
+  int si = 0;
+  while (si + 1 < songs.n && (int)blockIdx.x >= songs.v[si + 1].block0) ++si;
+  const int64_t N = songs.v[si].N, VL = songs.v[si].VL;
+  const int n_chunks = songs.v[si].nk;
+  const float *__restrict__ chunk_out = chunk_all + (int64_t)songs.v[si].first * SC * TL;
+  const int64_t n = (int64_t)((int)blockIdx.x - songs.v[si].block0) * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const int64_t u = n + songs.v[si].lead;
+  int64_t k_hi = u / stride;
+  if (k_hi > n_chunks - 1) k_hi = n_chunks - 1;
+  int64_t k_lo = (u - segment + stride) / stride;
+  if (u - segment + 1 <= 0) k_lo = 0;
+  float num = 0.f, den = 0.f;
+  for (int64_t k = k_lo; k <= k_hi; ++k) {
+    const int64_t off = k * stride;
+    const int64_t clen = (VL - off < segment) ? VL - off : segment;
+    const int64_t j = u - off;
+    if (j < 0 || j >= clen) continue;
+    const int64_t trim = center ? (TL - clen) / 2 : 0;
+    const float w = weight[j];
+    num += w * chunk_out[((int64_t)k * SC + sc_) * TL + trim + j];
+    den += w;
+  }
+  int so_ = sc_;
+  if (swap01 && (sc_ >> 1) < 2) so_ = ((1 - (sc_ >> 1)) << 1) | (sc_ & 1);
+  float *op = songs.v[si].out + (int64_t)so_ * N + n;
+  float v = num / den;
+  if (!first) v = *op + v;
+  if (last) {
+    v = v / (float)shifts;
+    if (standardize) {
+      float mean, stdv;
+      sample_mean_std(ref_acc, songs.v[si].slot, (double)N, mean, stdv);
+      v = v * stdv + mean;
+    }
+  }
+  *op = v;
+}
+
 // ---------------------------------------------------------------------------
 // mha6_kernel: mha_kernel on the bf16 matrix pipe with fp32 results (kernels_rof.h: attention6_kernel has the scheme -- six bf16
 // MFMA products on exactly split operands, Q split in registers, K and the transposed V split by the staging threads, P split

@@ -243,16 +243,123 @@ class DemucsDemixer:
             if single:
                 return out
             w = np.asarray(self.weights[i], np.float32)
-            out *= w[:, None, None]
             totals += w
-            est = out if est is None else est + out
-        est /= totals.astype(np.float32)[:, None, None]
-        ref = mix.mean(0)
+            est = self._bag_add(est, out, w)
+        return self._bag_finish(mix, est, totals)
+
+    @staticmethod
+    def _bag_finish(mix, est, totals):
+        """estimates /= totals; * ref.std() + ref.mean(); stems 0 / 1 swapped (apply.py:186-196, demucs_separator.py:186-189)"""
         import torch
-        rt = torch.from_numpy(ref)
+        est /= totals.astype(np.float32)[:, None, None]
+        rt = torch.from_numpy(mix.mean(0))
         est = est * float(rt.std()) + float(rt.mean())
         est[[0, 1]] = est[[1, 0]]
         return est
+
+    @staticmethod
+    def _bag_add(est, out, w):
+        """one member's weighted result onto the running sum (the first member starts it)"""
+        out *= w[:, None, None]
+        return out if est is None else est + out
+
+    # ---- a batch of songs: the segments of all of them pooled per forward (asx_ht_demix_batch_dev / asx_hd_demix_batch_dev) ------
+    def _draw_many(self, n_songs: int, offsets):
+        """[song][model] -> the shift draws.  Drawn in song order, then model order: the sequence a loop of single ``demix`` calls
+        consumes from ``random``, so under one ``random.seed`` the batch and the loop see the same offsets."""
+        if offsets is not None and len(offsets) != n_songs:
+            raise ValueError("offsets must give one entry per song")
+        return [[self._draw_offsets(i, offsets[s] if offsets is not None else None) for i in range(len(self.models))]
+                for s in range(n_songs)]
+
+    def _batch_run(self, i):
+        return self.engine.hd_demix_batch_dev if isinstance(self.models[i][0], HDConfig) else self.engine.ht_demix_batch_dev
+
+    def demix_many_dev(self, mix_tensors, offsets=None):
+        """``demix_dev`` for a list of CUDA tensors [2, N_i] in one pooled call per model: returns the list of [S, 2, N_i] CUDA
+        tensors (each equal to ``demix_dev`` of that song with the same offsets), or None when this configuration has no
+        device-resident path (``segments_enabled=False``).  ``offsets[i]`` is what ``demix(..., offsets=...)`` takes for song i.
+        A bag standardises each song once, runs ONE pooled demix of all standardised songs per member on that member's resident
+        engine, and accumulates / finishes per song with asx_ht_bag_*.  Only enqueues work on the current stream."""
+        import torch
+        if not self.segments_enabled:
+            return None
+        mixes = list(mix_tensors)
+        draws = self._draw_many(len(mixes), offsets)
+        if not mixes:
+            return []
+        dev = mixes[0].device
+        st = torch.cuda.current_stream(dev).cuda_stream
+        S = len(self.models[0][0].sources)
+        outs = [torch.empty((S, 2, m.shape[1]), dtype=torch.float32, device=dev) for m in mixes]
+        if len(self.models) == 1:
+            self._load(0)
+            self._batch_run(0)([(m.data_ptr(), o.data_ptr(), m.shape[1], draws[s][0]) for s, (m, o) in enumerate(zip(mixes, outs))],
+                               shifts=self.shifts, overlap=self.overlap, flags=3, stream=st)
+            return outs
+        std = [torch.empty_like(m) for m in mixes]
+        est = [torch.empty_like(o) for o in outs]
+        mem = [torch.empty_like(o) for o in outs]
+        totals = np.zeros(S, np.float64)
+        for i in range(len(self.models)):
+            self._load(i)
+            eng = self.engine
+            if i == 0:
+                for m, sd in zip(mixes, std):
+                    eng.ht_standardize_dev(m.data_ptr(), m.shape[1], sd.data_ptr(), stream=st)
+            self._batch_run(i)([(sd.data_ptr(), me.data_ptr(), sd.shape[1], draws[s][i]) for s, (sd, me) in enumerate(zip(std, mem))],
+                               shifts=self.shifts, overlap=self.overlap, flags=0, stream=st)
+            for es, me in zip(est, mem):
+                eng.ht_bag_accumulate_dev(es.data_ptr(), me.data_ptr(), self.weights[i], me.shape[2], first=(i == 0), stream=st)
+            totals += np.asarray(self.weights[i], np.float64)
+        for m, es, o in zip(mixes, est, outs):
+            self.engine.ht_bag_finish_dev(es.data_ptr(), totals.astype(np.float32), m.data_ptr(), m.shape[1], o.data_ptr(),
+                                          standardize=True, swap01=True, stream=st)
+        return outs
+
+    def demix_many(self, mixes, offsets=None) -> list:
+        """``demix`` for a list of [2, N_i] arrays -> the list of [S, 2, N_i] arrays, each equal to ``demix`` of that song.
+        ``segments_enabled=False`` has no pooled path: it runs the per-song loop."""
+        host = []
+        for mix in mixes:
+            mix = np.ascontiguousarray(mix, np.float32)
+            if mix.ndim != 2 or mix.shape[0] != 2:
+                raise ValueError(f"Expected a 2-channel audio signal, but got shape {mix.shape}")
+            host.append(mix)
+        if offsets is not None and len(offsets) != len(host):
+            raise ValueError("offsets must give one entry per song")
+        if not self.segments_enabled:
+            return [self.demix(m, offsets[s] if offsets is not None else None) for s, m in enumerate(host)]
+        if (self._own or self.engine is None) and _cuda_ready():
+            import torch
+            dev = torch.device("cuda", self.device)
+            return [o.cpu().numpy() for o in self.demix_many_dev([torch.from_numpy(m).to(dev) for m in host], offsets)]
+        # an engine handed in from outside: its host-array batch call, combined like ``demix`` combines a bag
+        draws = self._draw_many(len(host), offsets)
+        if not host:
+            return []
+        single = len(self.models) == 1
+        est = [None] * len(host)
+        totals = np.zeros(len(self.models[0][0].sources), np.float64)
+        for i in range(len(self.models)):
+            self._load(i)
+            run = self.engine.hd_demix_batch if isinstance(self.models[i][0], HDConfig) else self.engine.ht_demix_batch
+            offs = [d[i] for d in draws] if self.shifts else None
+            if single:
+                return run(host, shifts=self.shifts, offsets=offs, overlap=self.overlap, standardize=True, swap01=True)
+            outs = run([self._standardized(m) for m in host], shifts=self.shifts, offsets=offs, overlap=self.overlap)
+            w = np.asarray(self.weights[i], np.float32)
+            totals += w
+            for s, out in enumerate(outs):
+                est[s] = self._bag_add(est[s], out, w)
+        return [self._bag_finish(m, e, totals) for m, e in zip(host, est)]
+
+    @staticmethod
+    def _standardized(mix):
+        import torch
+        t = torch.from_numpy(mix)
+        ref = t.mean(0)
+        return ((t - ref.mean()) / ref.std()).numpy()
 
     def _apply_whole(self, std_mix: np.ndarray, hc, offs) -> np.ndarray:
         """apply_model(..., split=False) (apply.py:198-214, 251-260): one forward per shift over the whole (shifted) track.
@@ -282,10 +389,7 @@ class DemucsDemixer:
         return out / max(self.shifts, 1)
 
     def _bag_member(self, mix, offs):
-        import torch
-        t = torch.from_numpy(mix)
-        ref = t.mean(0)
-        std_mix = ((t - ref.mean()) / ref.std()).numpy()
+        std_mix = self._standardized(mix)
         if not self.segments_enabled:
             return self._apply_whole(std_mix, self.models[self._loaded][0], offs)
         return self._demix(std_mix, shifts=self.shifts, offsets=offs, overlap=self.overlap)

@@ -269,7 +269,7 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_vr_analysis", "asx_vr_separate", "asx_vr_separate_dev", "asx_debug_fetch", "asx_mdxc_chunks_dev",
            "asx_mdxc_finalize_dev", "asx_rof_plan", "asx_rof_chunks_dev", "asx_rof_finalize_dev", "asx_ht_plan",
            "asx_ht_segments_dev", "asx_ht_fold_dev", "asx_hd_begin", "asx_hd_commit", "asx_hd_flops",
-           "asx_hd_forward", "asx_hd_demix", "asx_hd_demix_dev", "asx_hd_plan", "asx_hd_segments_dev",
+           "asx_hd_forward", "asx_hd_demix", "asx_hd_demix_dev", "asx_ht_demix_batch_dev", "asx_hd_demix_batch_dev", "asx_hd_plan", "asx_hd_segments_dev",
            "asx_hd_fold_dev", "asx_pcm16", "asx_pcm16_dev", "asx_pcm16_rows_dev", "asx_pcm_decode_dev",
            "asx_ht_standardize_dev", "asx_ht_bag_accumulate_dev", "asx_ht_bag_finish_dev", "asx_ensemble",
            "asx_ensemble_dev", "asx_invert_stem", "asx_normalize", "asx_normalize_dev", "asx_residual_dev",
@@ -288,6 +288,10 @@ class _LaunchRec(C.Structure):     # struct asx_launch_rec
 
 class _Song(C.Structure):          # struct asx_song
     _fields_ = [("mix_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_samples", C.c_int64)]
+
+
+class _ApplySong(C.Structure):     # struct asx_apply_song
+    _fields_ = [("mix_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_samples", C.c_int64), ("offsets", C.POINTER(C.c_int64))]
 
 
 class _SongStems(C.Structure):     # struct asx_song_stems
@@ -415,6 +419,8 @@ def load_library():
     lib.asx_hd_plan.argtypes = [vp, i64, i32, C.POINTER(C.c_int64), C.c_double, C.POINTER(i32), C.POINTER(i64)]
     lib.asx_hd_segments_dev.argtypes = [vp, vp, i64, i32, C.POINTER(C.c_int64), C.c_double, u32, i32, i32, vp, vp]
     lib.asx_hd_fold_dev.argtypes = [vp, vp, i64, i32, C.POINTER(C.c_int64), C.c_double, u32, vp, vp, vp]
+    lib.asx_ht_demix_batch_dev.argtypes = [vp, C.POINTER(_ApplySong), i32, i32, C.c_double, u32, vp]
+    lib.asx_hd_demix_batch_dev.argtypes = [vp, C.POINTER(_ApplySong), i32, i32, C.c_double, u32, vp]
     lib.asx_profile_enable.argtypes = [vp, i32]
     lib.asx_profile_read.argtypes = [vp, C.POINTER(_Profile)]
     for name in SYMBOLS:
@@ -860,6 +866,60 @@ class Engine:
     def _apply_fold_dev(self, gen, mix_ptr, n, chunks_ptr, out_ptr, shifts, offsets, overlap, flags, stream):
         self._check(getattr(self._lib, f"asx_{gen}_fold_dev")(self._h, mix_ptr, n, int(shifts), self._offs(shifts, offsets),
                                                              float(overlap), flags, chunks_ptr, out_ptr, stream or None))
+
+    def _apply_demix_batch_dev(self, gen, songs, shifts, overlap, flags, stream):
+        """``songs``: a list of ``(mix_ptr, out_ptr, n_samples, offsets)`` -- mix [2, n] and out [S, 2, n] in HBM, ``offsets`` the
+        ``shifts`` draws of that song (None when shifts == 0).  The segments of all songs share the forwards; every ``out`` equals
+        what ``<gen>_demix_dev`` writes for that song alone, bit for bit (asx_<gen>_demix_batch_dev)."""
+        songs = list(songs)
+        arr = (_ApplySong * max(1, len(songs)))()
+        keep = []                                          # the offset arrays live until the call returns
+        for i, (mix_ptr, out_ptr, n, offsets) in enumerate(songs):
+            offs = None
+            if shifts and offsets is not None:
+                if len(offsets) != shifts:
+                    raise ValueError(f"song {i}: shifts > 0 needs one offset per shift")
+                offs = self._offs(shifts, offsets)
+                keep.append(offs)
+            arr[i] = _ApplySong(mix_ptr or None, out_ptr or None, int(n), offs)
+        self._check(getattr(self._lib, f"asx_{gen}_demix_batch_dev")(self._h, arr, len(songs), int(shifts), float(overlap), flags,
+                                                                    stream or None))
+
+    def ht_demix_batch_dev(self, songs, shifts=0, overlap=0.25, flags=0, stream=0):
+        self._apply_demix_batch_dev("ht", songs, shifts, overlap, flags, stream)
+
+    def hd_demix_batch_dev(self, songs, shifts=0, overlap=0.25, flags=0, stream=0):
+        self._apply_demix_batch_dev("hd", songs, shifts, overlap, flags, stream)
+
+    def _apply_demix_batch(self, gen, n_sources, mixes, shifts, offsets, overlap, standardize, swap01):
+        """``<gen>_demix`` for a list of float32 [2, N_i] arrays in one pooled call; ``offsets[i]`` are song i's draws.  Returns the
+        list of [S, 2, N_i] results.  Device staging buffers come from torch (the plumbing layer), as in ``demix_batch``."""
+        host = []
+        for mix in mixes:
+            mix = _f32(mix)
+            if mix.ndim != 2 or mix.shape[0] != 2:
+                raise ValueError(f"Expected a 2-channel audio signal, but got shape {mix.shape}")
+            host.append(mix)
+        if shifts and (offsets is None or len(offsets) != len(host)):
+            raise ValueError("shifts > 0 needs one list of offsets per song")
+        if not host:
+            return []
+        torch, dev, st = self._torch_stream()
+        flags = (1 if standardize else 0) | (2 if swap01 else 0)
+        with torch.cuda.stream(st):
+            d_mix = [torch.from_numpy(m).to(dev) for m in host]
+            d_out = [torch.empty((n_sources, 2, m.shape[1]), dtype=torch.float32, device=dev) for m in host]
+            self._apply_demix_batch_dev(gen, [(m.data_ptr() if m.numel() else 0, o.data_ptr() if o.numel() else 0, m.shape[1],
+                                               offsets[i] if shifts else None) for i, (m, o) in enumerate(zip(d_mix, d_out))],
+                                        shifts, overlap, flags, st.cuda_stream)
+            outs = [o.cpu().numpy() for o in d_out]
+        return outs
+
+    def ht_demix_batch(self, mixes, shifts=0, offsets=None, overlap=0.25, standardize=False, swap01=False) -> list:
+        return self._apply_demix_batch("ht", len(self.ht_cfg.sources), mixes, shifts, offsets, overlap, standardize, swap01)
+
+    def hd_demix_batch(self, mixes, shifts=0, offsets=None, overlap=0.25, standardize=False, swap01=False) -> list:
+        return self._apply_demix_batch("hd", len(self.hd_cfg.sources), mixes, shifts, offsets, overlap, standardize, swap01)
 
     def ht_plan(self, n, shifts=0, offsets=None, overlap=0.25):
         return self._apply_plan("ht", n, shifts, offsets, overlap)

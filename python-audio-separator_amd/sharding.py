@@ -177,15 +177,16 @@ class FilesPipeline:
 
     ``demix_many(mixes, outs)`` (optional) replaces the per-song loop of a step by ONE call over all of the rank's songs
     (``outs`` is the step's [S, 2, N] stem buffer): libasx.so's ``demix_batch_dev``, which pools the chunks of all songs per
-    launch (``batch_demix_many`` below builds the callable)."""
+    launch (``batch_demix_many`` below builds the callable; ``demucs_demix_many`` the one for a Demucs net, whose songs come back
+    as [sources, 2, N] each: pass that as ``stem_shape``, the per-song shape of the stem buffers, which defaults to the mix's)."""
 
     def __init__(self, demix, mixes, world: int, rank: int, use_dist: bool, dst: int = 0, overlap: bool = True, on_gathered=None,
-                 demix_many=None):
+                 demix_many=None, stem_shape=None):
         import torch
         self.demix, self.mixes, self.world, self.rank, self.dst = demix, mixes, world, rank, dst
         self.demix_many = demix_many
         self.use_dist, self.overlap, self.on_gathered = use_dist, overlap, on_gathered
-        S, shape = len(mixes), tuple(mixes[0].shape)
+        S, shape = len(mixes), tuple(stem_shape if stem_shape is not None else mixes[0].shape)
         mk = lambda: torch.empty((S,) + shape, dtype=mixes[0].dtype, device=mixes[0].device)  # noqa: E731
         self.outs = [mk(), mk()]
         self.gathered = [[mk() for _ in range(world)] for _ in range(2)] if (use_dist and rank == dst) else [None, None]
@@ -233,6 +234,20 @@ def batch_demix_many(engine, is_match_mix: bool = False, stream=None):
         import torch
         st = stream() if stream is not None else torch.cuda.current_stream(torch.device("cuda", engine.device)).cuda_stream
         engine.demix_batch_dev([(m.data_ptr(), outs[i].data_ptr(), m.shape[-1]) for i, m in enumerate(mixes)], is_match_mix, st)
+    return run
+
+
+def demucs_demix_many(engine, gen: str = "ht", shifts: int = 0, offsets=None, overlap: float = 0.25, flags: int = 3, stream=None):
+    """The ``demix_many`` callable of FilesPipeline over a Demucs engine (``gen`` "ht" = v4, "hd" = v3): one
+    ``<gen>_demix_batch_dev`` call pools the segments of all songs of a step.  ``offsets[s]`` are the ``shifts`` draws of song s
+    (fixed for the pipeline's life: the caller draws them); ``outs[s]`` is that song's [sources, 2, N] stems."""
+    run_batch = engine.hd_demix_batch_dev if gen == "hd" else engine.ht_demix_batch_dev
+
+    def run(mixes, outs):
+        import torch
+        st = stream() if stream is not None else torch.cuda.current_stream(torch.device("cuda", engine.device)).cuda_stream
+        run_batch([(m.data_ptr(), outs[i].data_ptr(), m.shape[-1], offsets[i] if shifts else None) for i, m in enumerate(mixes)],
+                  shifts=shifts, overlap=overlap, flags=flags, stream=st)
     return run
 
 
