@@ -556,6 +556,7 @@ int asx_invert_stem(asx_engine *e, const float *mix_host, const float *stem_host
  * "attn6h_launches" (those of them on the fp16 x 3 arithmetic),
  * "wino6_launches" (conv_wino6_kernel: Winograd F(2x2,3x3) on the 16-bit pipe), "wino6h_launches" (those on the fp16 x 3 arithmetic),
  * "conv3h_launches" (ABI 7: conv3h_kernel, the direct fp16 x 3 convolution of the 48-channel level),
+ * "conv3h_fin_launches" (those of them in the fused-input form, option "conv_fuse_input": one per net pass where it applies),
  * "down6_launches" / "up6_launches" (ABI 7: conv_down6_kernel / conv_up6_kernel, the level-change convs on the 16-bit matrix pipe),
  * "hd_rounds" (ABI 7: rounds of chunk groups the Demucs v3 forward has run -- the groups of a round share the BLSTM launches),
  * "tdf3_pair_image_launches" (ABI 7: the tdf3_kernel launches that read their x operand as a pair image -- option "gemm_pair_images", experimental builds).
@@ -652,6 +653,10 @@ int asx_op_mha(asx_engine *e, const float *q_host, int64_t ldq, const float *k_h
  * LDS for the whole launch, producer waves fetch four input rows per step into a ring walked down T and split them under one running
  * power-of-two exponent per walk, consumer waves multiply; n x n launches over 48-channel slices; 5.3-5.8 ms per launch of 55 chunks against
  * 8.5-8.9 on conv_wino3_kernel at 48 channels.  0 = never (conv_wino3_kernel / conv_wino6_kernel).
+ * "conv_fuse_input" (an option only, no environment variable): 1 (default) = where the first 3x3 TFC convolution of a BatchNorm ConvTDFNet runs
+ * conv3h_kernel at 48 channels, its producer waves compute the net's 1x1 input convolution (4 -> 48 channels, folded BatchNorm, ReLU) themselves
+ * from the four spectrogram planes: no launch of its own, no 48-channel activation written to memory and read back.  0 = two launches.  A
+ * GroupNorm net, another width or another 3x3 kernel: two launches either way.
  * "conv_down_bf16x6" / "conv_up_bf16x6" (ABI 7; also ASX_DOWN6 / ASX_UP6): 1 (default) = the 2 x 2 / stride-2 convolutions between the levels
  * (mdxnet.py:66-72) and the transposed ones of the decoder with their `x *= skip` (mdxnet.py:80-86, 113) run conv_down6_kernel / conv_up6_kernel
  * (csrc/kernels_updown6.h) while "gemm_bf16x6" is on: the arithmetic of that option -- both fp32 operands split EXACTLY into three bf16 parts, six

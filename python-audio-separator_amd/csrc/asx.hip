@@ -88,6 +88,7 @@ static const struct EngineOption {
     {"gemm_bf16x6", &asx_engine::gemm_bf16x6, &EngineKnobs::gemm_bf16x6, opt_onoff},   // this engine only (round 5; it was process-wide before)
     {"gemm_f16x3", &asx_engine::gemm_f16x3, &EngineKnobs::gemm_f16x3, opt_onoff},
     {"conv_direct_f16x3", &asx_engine::conv3h, &EngineKnobs::conv3h, opt_nonneg},
+    {"conv_fuse_input", &asx_engine::conv_fuse_input, &EngineKnobs::conv_fuse_input, opt_onoff},
     {"conv_down_bf16x6", &asx_engine::down6, &EngineKnobs::down6, opt_onoff},
     {"conv_up_bf16x6", &asx_engine::up6, &EngineKnobs::up6, opt_onoff},
     {"gemm_pair_images", &asx_engine::pair_images, &EngineKnobs::pair_images, opt_onoff,
@@ -248,6 +249,7 @@ static void free_conv(ConvLayer &L) {
   L.wu6.release();
   L.wu6h.release();
   L.w3h.release();
+  L.w1f.release();
   L.wd6.release();
   L.wup6.release();
   L.gn_w.release();
@@ -2213,6 +2215,7 @@ int asx_counter(const asx_engine *e, const char *name, int64_t *out) {
   else if (nm == "wino6_launches") *out = (int64_t)g_wino6_launches.load();
   else if (nm == "wino6h_launches") *out = (int64_t)g_wino6h_launches.load();
   else if (nm == "conv3h_launches") *out = (int64_t)g_conv3h_launches.load();
+  else if (nm == "conv3h_fin_launches") *out = (int64_t)g_conv3h_fin_launches.load();
   else if (nm == "tdf3_pair_image_launches") *out = (int64_t)g_tdf3ps_launches.load();
   else if (nm == "down6_launches") *out = (int64_t)g_down6_launches.load();
   else if (nm == "up6_launches") *out = (int64_t)g_up6_launches.load();

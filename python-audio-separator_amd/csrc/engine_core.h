@@ -119,6 +119,7 @@ struct ConvLayer {
   int wu6_nci = 0; // 32-channel stages of that image (0 = not packed: Cin < 64)
   DevBuf wu6h;     // the same for the fp16 x 3 arithmetic (wino6_pack_h): two fp16 parts per U, scaled per (position, cout); exponents behind the fragments
   DevBuf w3h;      // conv3h_kernel (kernels_conv3h.h): the 48 -> 48 layers' two-part fp16 weights in fragment order, one exponent per output channel
+  DevBuf w1f;      // CK_1X1 of 4 -> 48 channels: w [48][4] then b [48] as plain fp32, for the fused-input form of conv3h_kernel (the 3x3 conv behind it computes this layer in its producer)
   DevBuf wd6;      // CK_DOWN: conv_down6_kernel (kernels_updown6.h): the weights split three ways into bf16, fragment order [CG48][stage of 8 channels][part][n][lane][8]
   int wd6_cg = 0, wd6_nst = 0, wd6_nrep = 3;
   DevBuf wup6;     // CK_UP: conv_up6_kernel (kernels_updown6.h): [CG][stage of 32 channels][part][n][lane][8 bf16] over the 4 Cout virtual channels
@@ -215,7 +216,7 @@ struct asx_engine {
   hipEvent_t div_ev = nullptr;       // recorded behind the kernel that built d_div; a call on ANOTHER stream waits for it
   hipStream_t div_stream = nullptr;
   std::vector<DevBuf> skip;
-  // The nine engine options (asx_set_option / asx_get_option; asx_engine_create sets them from EngineKnobs, knobs.h).
+  // The ten engine options (asx_set_option / asx_get_option; asx_engine_create sets them from EngineKnobs, knobs.h).
   // 3x3 / pad-1 convs of the ConvTDFNet and TFC-TDF-v3 nets: 3 = Winograd F(2x2,3x3) (conv_wino3_kernel, the default), 0 = the
   // direct kernel (conv_dma_kernel), 1 / 2 = the earlier Winograd generations (kept for A/B runs; experimental builds only).
   // ASX_WINOGRAD or asx_set_option("winograd", n).
@@ -244,6 +245,11 @@ struct asx_engine {
   // (conv_wino6_kernel) at 144; the image is packed up to 144 channels.
   // ASX_CONV3H or asx_set_option("conv_direct_f16x3", n).
   int conv3h = 144;
+  // 1 (default): the net's 1x1 input conv (4 -> 48 channels, folded BatchNorm, ReLU) is computed by the producer waves of the first TFC conv's
+  // conv3h_kernel launch (its fused-input form) instead of in a launch of its own: the 48-channel level-0 activation is never written to
+  // memory and read back.  0: two launches.  Only where the first 3x3 layer runs conv3h_kernel at 48 channels and the net uses BatchNorm.
+  // asx_set_option("conv_fuse_input", n).
+  int conv_fuse_input = 1;
   // 1 (default): the 2 x 2 / stride-2 convolutions between the levels run conv_down6_kernel (kernels_updown6.h: bf16 x 6 -- exact three-way split
   // operands on the 16-bit matrix pipe, fp32 accumulation) while "gemm_bf16x6" is on; 0: the fp32-MFMA kernel conv_dma_kernel<2, 2, 2, 0, ...>.
   // ASX_DOWN6 or asx_set_option("conv_down_bf16x6", n).

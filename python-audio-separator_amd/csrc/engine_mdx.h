@@ -196,6 +196,14 @@ static int conv_pack(ConvLayer &L, const float *w, const float *b, int wino_mode
     }
 #endif
   }
+  if (L.kind == CK_1X1 && L.cin == 4 && L.cout == Conv3hCfg::C) {
+    // any 1x1 layer of 4 -> 48 channels (240 floats; only a ConvTDFNet's input conv is ever fused) as conv3h_kernel's fused-input form reads it: w [48][4], then b [48]
+    std::vector<float> w1((size_t)Conv3hCfg::C * 5, 0.f);
+    memcpy(w1.data(), w, (size_t)Conv3hCfg::C * 4 * 4);
+    if (b) memcpy(w1.data() + Conv3hCfg::C * 4, b, (size_t)Conv3hCfg::C * 4);
+    CHK(L.w1f.ensure(w1.size() * 4));
+    HIPCHK(hipMemcpy(L.w1f.p, w1.data(), w1.size() * 4, hipMemcpyHostToDevice));
+  }
   if (L.kind == CK_DOWN) {
     // bf16 x 6 image of the 2 x 2 / stride-2 conv (kernels_updown6.h); which kernel RUNS is the engine's "gemm_bf16x6" option at launch time
     std::vector<uint32_t> w6;
@@ -233,6 +241,7 @@ static void launch_conv_dma_t(const ConvArgs &a, int nblk, hipStream_t s) {
 static std::atomic<long long> g_wino6_launches{0};   // launches of conv_wino6_kernel (kernels_wino6.h) since the process started
 static std::atomic<long long> g_wino6h_launches{0};  // ... of which on the fp16 x 3 arithmetic
 static std::atomic<long long> g_conv3h_launches{0};  // launches of conv3h_kernel (kernels_conv3h.h)
+static std::atomic<long long> g_conv3h_fin_launches{0};   // ... of which in the fused-input form (the net's 1x1 input conv computed by the producers)
 static std::atomic<long long> g_down6_launches{0};   // launches of conv_down6_kernel (kernels_updown6.h)
 static std::atomic<long long> g_up6_launches{0};     // launches of conv_up6_kernel
 
@@ -244,7 +253,22 @@ struct ConvView {
   int64_t aux_bstride = 0;  // of skip / res; 0 = dense
   int act = -1;             // -1 = the layer's own activation
   float alpha = 1.f;        // act == ACT_ELU (CK_1X1 layers only)
+  // fused input (conv3h_kernel<0, false, true>): x is ignored; the layer's 48 input channels are `fin` (a 4 -> 48 1x1 conv with ReLU) of
+  // fin_x [B, 4, T, F] (dense), formed in the kernel's producer waves.  The caller has asked conv3h_takes first: no other kernel has the form.
+  const ConvLayer *fin = nullptr;
+  const float *fin_x = nullptr;
 };
+
+// does conv_launch run this 3x3 layer on conv3h_kernel?  (`dma`: F % 4 == 0, the input 16-byte aligned with a batch stride of whole float4, LDS-DMA not switched off)
+static bool conv3h_takes(const asx_engine *e, const ConvLayer &L, bool dma, const float *res, int act, int T, int F, int64_t y_bstride, const float *y) {
+#ifdef ASX_EXPERIMENTAL_KERNELS
+  // "winograd_stationary" = 1 sends every layer with a stationary image to conv_winos_kernel first (its other conditions are implied by the ones below)
+  if (e->winos == 1 && L.wus.p != nullptr) return false;
+#endif
+  return L.kind == CK_3X3 && e->winograd == 3 && e->gemm_bf16x6 > 0 && e->gemm_f16x3 > 0 && e->conv3h > 0 && L.cin <= e->conv3h && L.w3h.p != nullptr && dma &&
+         res == nullptr && (act == ACT_RELU || act == ACT_NONE) && F % 32 == 0 && (int64_t)Conv3hCfg::C * T * F < ((int64_t)1 << 29) &&
+         y_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+}
 
 // x [B,cin,T,F] -> y
 static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const float *skip, float *y, int B, int T,
@@ -304,7 +328,9 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
   if (L.kind == CK_UP && skip) bytes += 4.0 * (double)L.cout * outpix * 4;  // skip read
   if (v.res) bytes += 4.0 * (double)L.cout * outpix;
   int bad = 0;
-  const bool dma = (F % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && (a.x_bstride % 4 == 0) && !knobs().no_dma;
+  const bool dma = (F % 4 == 0) && ((reinterpret_cast<uintptr_t>(v.fin ? v.fin_x : x) & 15) == 0) && (a.x_bstride % 4 == 0) && !knobs().no_dma;
+  REQUIRE(!v.fin || (v.fin->w1f.p != nullptr && L.cin == Conv3hCfg::C && conv3h_takes(e, L, dma, v.res, a.act, T, F, a.y_bstride, y)),
+          "fused-input 3x3 conv: the layer does not run conv3h_kernel");
   const ConvArgs &d = a;
 #ifdef ASX_EXPERIMENTAL_KERNELS   // measured-and-rejected generations (profiles/NOTES.md): python build.py --experimental, or ASX_EXPERIMENTAL=1 in the environment of the build
   if (L.kind == CK_3X3 && e->winograd == 3 && e->winos == 1 && dma && L.wus.p != nullptr && a.Fo % 32 == 0 && v.res == nullptr &&
@@ -344,9 +370,7 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     return k12 ? gos(&conv_winos_kernel<12, 0, false>, WinoSCfg<12>::LDS_BYTES) : gos(&conv_winos_kernel<24, 0, false>, WinoSCfg<24>::LDS_BYTES);
   }
 #endif
-  if (L.kind == CK_3X3 && e->winograd == 3 && e->gemm_bf16x6 > 0 && e->gemm_f16x3 > 0 && e->conv3h > 0 && L.cin <= e->conv3h && L.w3h.p != nullptr && dma &&
-      v.res == nullptr && (a.act == ACT_RELU || a.act == ACT_NONE) && F % 32 == 0 && (int64_t)Conv3hCfg::C * T * F < ((int64_t)1 << 29) &&
-      a.y_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) {
+  if (conv3h_takes(e, L, dma, v.res, a.act, T, F, a.y_bstride, y)) {
     // direct implicit GEMM on the fp16 pipe, weights resident in LDS: one persistent 512-thread workgroup per CU (the walk assumes 8 XCDs x 32).
     // A layer of 48 n channels runs as n x n launches: for every 48-channel slice of the OUTPUT, the input slices one after the other, each
     // added to the sum of those before it (a.prev = the output itself), bias with the first, activation with the last.
@@ -369,6 +393,7 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     if (best > 1e29) bw = 32;                          // (tilesT not divisible: one segment)
     grant_lds(&conv3h_kernel<0, false>, Conv3hCfg::LDS_BYTES);
     grant_lds(&conv3h_kernel<0, true>, Conv3hCfg::LDS_BYTES);
+    grant_lds(&conv3h_kernel<0, false, true>, Conv3hCfg::LDS_BYTES);
     const int64_t plane = (int64_t)T * F;
     return timed(e, cls, flops, bytes, s, [&]() {
       e->prof_nprod = 3;
@@ -390,7 +415,13 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
           ca.tilesF = tilesF;
           ca.bw = bw;
           ca.tps = (tilesT * bw) % 32 == 0 ? tilesT * bw / 32 : tilesT;
-          if (ib > 0) hipLaunchKernelGGL((conv3h_kernel<0, true>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
+          if (v.fin) {                                 // (nb == 1) the algorithmic flops / bytes of the record stay the 3x3 layer's own
+            ca.xin = v.fin_x;
+            ca.xin_bstride = 4 * plane;
+            ca.w1 = v.fin->w1f.f();
+            hipLaunchKernelGGL((conv3h_kernel<0, false, true>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
+            g_conv3h_fin_launches.fetch_add(1);
+          } else if (ib > 0) hipLaunchKernelGGL((conv3h_kernel<0, true>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
           else hipLaunchKernelGGL((conv3h_kernel<0, false>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
           g_conv3h_launches.fetch_add(1);
         }
@@ -1164,7 +1195,9 @@ static int gn_launch(asx_engine *e, const float *x, int B, int C, int64_t P, con
   });
 }
 
-static int block_forward(asx_engine *e, const Block &blk, float *&cur, float *dest, int B, hipStream_t s) {
+// fin_x != nullptr (the net's first block only): `cur` holds nothing yet -- the first TFC conv computes the net's input conv e->first of fin_x
+// itself (conv3h_kernel's fused-input form) and writes where it would have written: the rotation through e->R is the same either way
+static int block_forward(asx_engine *e, const Block &blk, float *&cur, float *dest, int B, hipStream_t s, const float *fin_x = nullptr) {
   // TFC convs rotate through e->R; the TDF output goes to `dest` (or a free R buffer when dest == nullptr)
   auto next_free = [&](const float *a, const float *b) -> float * {
     for (int i = 0; i < 3; ++i)
@@ -1175,7 +1208,12 @@ static int block_forward(asx_engine *e, const Block &blk, float *&cur, float *de
   const int64_t plane = (int64_t)blk.t * blk.f;
   for (size_t j = 0; j < blk.tfc.size(); ++j) {
     float *out = next_free(cur, nullptr);
-    CHK(conv_launch(e, blk.tfc[j], cur, nullptr, out, B, blk.t, blk.f, s));
+    ConvView v;
+    if (j == 0 && fin_x) {
+      v.fin = &e->first;
+      v.fin_x = fin_x;
+    }
+    CHK(conv_launch(e, blk.tfc[j], cur, nullptr, out, B, blk.t, blk.f, s, v));
     if (gn) CHK(gn_launch(e, out, B, blk.c, plane, blk.tfc[j].gn_w, blk.tfc[j].gn_b, nullptr, nullptr, out, s));
     cur = out;
   }
@@ -1227,17 +1265,28 @@ static int net_forward_dev(asx_engine *e, const float *spec_in, float *spec_out,
   const int n = e->net.num_blocks / 2;
   const bool gn = e->net.norm == 1;
   float *cur = e->R[0].f();
-  CHK(conv_launch(e, e->first, spec_in, nullptr, cur, B, T, F, s));
-  if (gn) CHK(gn_launch(e, cur, B, e->net.g, (int64_t)T * F, e->first.gn_w, e->first.gn_b, nullptr, nullptr, cur, s));
+  // The input conv (4 -> 48 channels, folded BatchNorm, ReLU) is a pointwise function of four planes: where the first TFC conv runs conv3h_kernel,
+  // its producers compute it (option "conv_fuse_input") and the 48-channel activation never makes the round trip through memory.  With GroupNorm
+  // a norm pass stands between the two convs: no fusion.
+  const Block &blk0 = n > 0 ? e->enc[0] : e->mid;
+  const bool fuse = e->conv_fuse_input > 0 && !gn && e->first.kind == CK_1X1 && e->first.cin == 4 && e->first.cout == Conv3hCfg::C && e->first.relu &&
+                    e->first.w1f.p != nullptr && !blk0.tfc.empty() && blk0.tfc[0].cin == Conv3hCfg::C && blk0.tfc[0].cout == Conv3hCfg::C &&
+                    conv3h_takes(e, blk0.tfc[0], F % 4 == 0 && (reinterpret_cast<uintptr_t>(spec_in) & 15) == 0 && !knobs().no_dma, nullptr,
+                                 blk0.tfc[0].relu ? ACT_RELU : ACT_NONE, T, F, (int64_t)Conv3hCfg::C * T * F, e->R[1].f());
+  if (!fuse) {
+    CHK(conv_launch(e, e->first, spec_in, nullptr, cur, B, T, F, s));
+    if (gn) CHK(gn_launch(e, cur, B, e->net.g, (int64_t)T * F, e->first.gn_w, e->first.gn_b, nullptr, nullptr, cur, s));
+  }
+  const float *fin_x = fuse ? spec_in : nullptr;
   for (int i = 0; i < n; ++i) {
-    CHK(block_forward(e, e->enc[i], cur, e->skip[i].f(), B, s));
+    CHK(block_forward(e, e->enc[i], cur, e->skip[i].f(), B, s, i == 0 ? fin_x : nullptr));
     float *out = e->R[0].f();
     CHK(conv_launch(e, e->ds[i], cur, nullptr, out, B, e->enc[i].t, e->enc[i].f, s));
     if (gn)
       CHK(gn_launch(e, out, B, e->ds[i].cout, (int64_t)(e->enc[i].t / 2) * (e->enc[i].f / 2), e->ds[i].gn_w, e->ds[i].gn_b, nullptr, nullptr, out, s));
     cur = out;
   }
-  CHK(block_forward(e, e->mid, cur, nullptr, B, s));
+  CHK(block_forward(e, e->mid, cur, nullptr, B, s, n == 0 ? fin_x : nullptr));
   for (int i = 0; i < n; ++i) {
     const Block &blk = e->dec[i];
     float *out = nullptr;

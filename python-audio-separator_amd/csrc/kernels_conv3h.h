@@ -2,6 +2,10 @@
 // matrix pipe with the fp16 x 3 arithmetic of kernels_gemm3.h (two-part operands, three products, fp32 accumulation) -- no Winograd
 // transforms, no cross-wave exchange.  One kernel for 48 -> 48 channels; layers of 96 / 144 channels run as 4 / 9 launches over 48-channel
 // slices (accumulate mode).  DESIGN.md 6k has the design record and the measurements behind every choice below.
+// Fused-input form (template flag FIN, engine option "conv_fuse_input"): for the net's FIRST 3x3 layer, x is relu(b1 + w1 xin), the 4 -> 48 1x1
+// input conv of the net -- the producers fetch the four planes of xin (four loads per item instead of eight) and form their eight channels in
+// registers in a fixed fma order; pixels outside the plane enter the ring as 0 (the padding is of the 48-channel activation).  The 1x1 conv's
+// launch, its 48-channel write and this kernel's read of it are gone.
 //
 //   y[b, co, t, f] = act(bias[co] + prev[b, co, t, f] + sum_{ci, ky, kx} w[co, ci, ky, kx] x[b, ci, t + ky - 1, f + kx - 1])        [B, C, T, F] fp32, F fastest
 //
@@ -45,6 +49,10 @@ struct Conv3hArgs {
   int bw, tps;               // walk geometry: strips per band (32, 16 or 8: an XCD's 32 workgroups take bw strips x 32 / bw segments of T), tiles per segment (tilesT * bw / 32)
   const float *prev;         // nullptr, or a [B, 48, T, F] view (y's strides) ADDED in front of the activation: the partial sum of another 48-channel slice of the input
   long long *dbg;            // ABL & 32 (timeline build): [64 steps][8] s_memtime stamps of workgroup 0, then [4 workgroups][2048] step starts
+  // fused-input form (FIN): x is unused; the 48 input channels are relu(b1 + w1 xin), the net's 1x1 input conv, formed by the producers
+  const float *xin;          // [B, 4, T, F] view (xin_bstride floats between batch items)
+  const float *w1;           // w1 [48][4], then b1 [48] (BatchNorm folded)
+  int64_t xin_bstride;
 };
 
 struct Conv3hCfg {
@@ -219,10 +227,25 @@ __device__ __forceinline__ float ror8m(float keep, float from) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, keep), __builtin_bit_cast(int, from), 0x128, 0xf, BM, false));   // row_ror:8
 }
 
+// the producer registers only the fused-input form has
+template <bool FIN>
+struct Conv3hFinRegs {};
+template <>
+struct Conv3hFinRegs<true> {
+  f32x4 rin[4][4];           // the four fetched sets (block m in set m % 4): four input planes each
+  bool ok[4];                // the item of set m % 4 lies inside the plane
+  float w1[8][4], b1[8];     // the 1x1 weights and biases of the lane's eight channels, loaded once
+};
+
 // ABL (measurement-only builds, results are garbage): 2 = no global loads, 4 = no stores, 8 = no split / LDS writes, 32 = timeline stamps
 // ACC: accumulate mode (a.prev != nullptr): its own instantiation -- a run-time test in front of the six loads ended the MFMA scheduling region
 // and cost the plain launches a dozen register moves per tile
-template <int ABL = 0, bool ACC = false>
+// FIN: fused input (never with ACC).  The layer's 48 input channels are a pointwise function of FOUR planes -- the net's 1x1 input conv with
+// its folded BatchNorm and ReLU -- so a producer item fetches four lines instead of eight and forms its eight channels in registers,
+// v = max(0, fma(w3, in3, fma(w2, in2, fma(w1, in1, fma(w0, in0, b))))) in this fixed order (a halo pixel is computed by two tiles: same bits),
+// at the step that first consumes the block (the maximum); a pixel outside the plane enters the ring as 0 -- the 3x3 conv pads the 48-channel
+// activation, not the four planes, so relu(b) must not leak in -- through the item's in-image predicate, kept beside the raw set.
+template <int ABL = 0, bool ACC = false, bool FIN = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3h_kernel(Conv3hArgs a) {
   using CFG = Conv3hCfg;
   extern __shared__ float lds_f[];
@@ -268,8 +291,25 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     const bool item_ok = ptid < 240;
     const int loff = (row * CFG::IW + 4 * q - 3) * CFG::PSTR + cig * 16;   // pixel 0 of the quad inside a block slot (window column 4 q - 3: never written for quad 0)
-    const int goff = (int)(((int64_t)cig * 8 * a.T + row) * a.F + 4 * q);  // floats from (channel 0, row 4 j + 1, column f0 - 4); < 2^29 (launcher)
-    f32x4 raw[4][8];                                   // four register sets: block m lives in set m % 4 (fetched in step m - 4, its maximum taken in step m - 2, split in step m - 1)
+    const int goff = FIN ? (int)((int64_t)row * a.F + 4 * q)              // FIN: the four planes are shared by the channel groups
+                         : (int)(((int64_t)cig * 8 * a.T + row) * a.F + 4 * q);  // floats from (channel 0, row 4 j + 1, column f0 - 4); < 2^29 (launcher)
+    // four register sets: block m lives in set m % 4 (fetched in step m - 4, its maximum taken in step m - 2, split in step m - 1).
+    // FIN: the four fetched sets are fr.rin; the 48-channel values exist from the maximum to the split: two sets, m % 2
+    constexpr int NSET = FIN ? 2 : 4;
+    f32x4 raw[NSET][8];
+    Conv3hFinRegs<FIN> fr;
+    const unsigned in_bytes = (unsigned)(4 * TF * 4);
+    if constexpr (FIN) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const f32x4 wv = *reinterpret_cast<const f32x4 *>(a.w1 + (cig * 8 + c) * 4);
+        fr.w1[c][0] = wv.x;
+        fr.w1[c][1] = wv.y;
+        fr.w1[c][2] = wv.z;
+        fr.w1[c][3] = wv.w;
+        fr.b1[c] = a.w1[CFG::C * 4 + cig * 8 + c];
+      }
+    }
 
     Conv3hWalk wk;
     conv3h_walk_init(a, wg, wk);
@@ -280,19 +320,37 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int t1 = nf < NB ? row0 + wk.j * 4 + 1 : -(1 << 20);
       ++nf;
       conv3h_walk_next(a, wg, wk);
-      __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x + (int64_t)tb * a.x_bstride), 0, plane_bytes, 0x00020000);
+      __amdgpu_buffer_rsrc_t rs = FIN ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.xin + (int64_t)tb * a.xin_bstride), 0, in_bytes, 0x00020000)
+                                      : __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x + (int64_t)tb * a.x_bstride), 0, plane_bytes, 0x00020000);
       const int org = t1 * a.F + (f0 - 4);
       // F % 4 == 0 and the quad is aligned: inside the row or outside as a whole
       const bool ok = item_ok && (unsigned)(t1 + row) < (unsigned)a.T && (unsigned)(f0 - 4 + 4 * q) < (unsigned)a.F;
       const unsigned vo = ok ? (unsigned)(goff + org) * 4u : 0xfffffff0u;   // past num_records: the load returns 0
+      if constexpr (FIN) {
+        fr.ok[S] = ok;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if constexpr ((ABL & 2) != 0) raw[S][j] = (f32x4){0.25f, 0.5f, 0.75f, 1.f};
-        else raw[S][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, (int)(j * TF * 4), 0));
+        for (int j = 0; j < 4; ++j) fr.rin[S][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, (int)(j * TF * 4), 0));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if constexpr ((ABL & 2) != 0) raw[S][j] = (f32x4){0.25f, 0.5f, 0.75f, 1.f};
+          else raw[S][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, (int)(j * TF * 4), 0));
+        }
       }
     };
     auto tile_max = [&](auto setc, int slot) {         // largest finite |x| of the block held in set S -> maxtab[slot][pw]
-      constexpr int S = decltype(setc)::value;
+      constexpr int S = decltype(setc)::value % NSET;
+      if constexpr (FIN) {                             // the block's 48-channel values, first needed here
+        constexpr int SI = decltype(setc)::value;
+        const bool ok = fr.ok[SI];
+        auto px = [&](float i0, float i1, float i2, float i3, int c) {
+          const float v = __builtin_fmaf(fr.w1[c][3], i3, __builtin_fmaf(fr.w1[c][2], i2, __builtin_fmaf(fr.w1[c][1], i1, __builtin_fmaf(fr.w1[c][0], i0, fr.b1[c]))));
+          return ok ? __builtin_fmaxf(v, 0.f) : 0.f;   // outside the plane: the 3x3 conv's zero padding, not relu(b1)
+        };
+        const f32x4 i0 = fr.rin[SI][0], i1 = fr.rin[SI][1], i2 = fr.rin[SI][2], i3 = fr.rin[SI][3];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) raw[S][c] = (f32x4){px(i0.x, i1.x, i2.x, i3.x, c), px(i0.y, i1.y, i2.y, i3.y, c), px(i0.z, i1.z, i2.z, i3.z, c), px(i0.w, i1.w, i2.w, i3.w, c)};
+      }
       float m = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -312,7 +370,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     };
     int e_prev = 0, js = -1;                           // exponent of the block split last, position of the next block to split inside its item
     auto split_store = [&](auto setc, int par, int slot3) {   // set S -> ring rows of block slot `slot3` under the block's exponent
-      constexpr int S = decltype(setc)::value;
+      constexpr int S = decltype(setc)::value % NSET;
       const f32x4 mv = *reinterpret_cast<const f32x4 *>(maxtab + par * 4);
       const float m = fmaxf(fmaxf(mv.x, mv.y), fmaxf(mv.z, mv.w));
       // Running exponent of the walk down T: it follows a block's need (largest |x| 2^need in [2^14, 2^15)) only when the block would
