@@ -549,6 +549,22 @@ int asx_ensemble_dev(asx_engine *e, const float *waves_dev, int32_t k, int64_t n
                      float *out_dev, int64_t *n_out, void *stream);
 int asx_invert_stem(asx_engine *e, const float *mix_host, const float *stem_host, int64_t n_samples, float *out_host, int64_t *n_out);
 
+/* The edge between one ensemble member and asx_ensemble_dev (separator.py:1286, :1335; ensembler.py:29-30): what the member's
+ * stem becomes on its way through write_audio and librosa.load, written into slot k of a device stack [K, 2, n_max].
+ *   stem_dev   the stem as a plugin leaves it: planar [2, n] (ASX_STEM_PLANAR) or rows [n, 2] (ASX_STEM_ROWS), float32
+ *   mode       ASX_SLOT_PCM16:   slot[c, i] = (float)q[i, c] / 32768 with q the int16 asx_pcm16_dev / asx_pcm16_rows_dev write
+ *                                for the same stem and thresholds (bit for bit); *peak_after as those calls return it
+ *              ASX_SLOT_FLOAT32: slot[c, i] = stem value, no normalisation, no quantisation; *peak_after = max |stem|
+ *   padding    slot[c, i] = 0 for n <= i < n_max, written by this call: the stack need not be cleared
+ * Requires 0 <= n <= n_max (stem_dev may be NULL when n == 0), n_max >= 1, k >= 0; the caller owns a stack of at least
+ * (k + 1) * 2 * n_max floats.  peak_after may be NULL (then the call only enqueues work).  Additive to ABI 7. */
+#define ASX_STEM_PLANAR 0
+#define ASX_STEM_ROWS 1
+#define ASX_SLOT_PCM16 0
+#define ASX_SLOT_FLOAT32 1
+int asx_ensemble_slot_dev(asx_engine *e, const float *stem_dev, int64_t n_samples, int32_t layout, float max_peak, float min_peak,
+                          int32_t has_min, int32_t mode, float *stack_dev, int32_t k, int64_t n_max, float *peak_after, void *stream);
+
 /* Launch counters of this process (tests use them to prove which kernel family ran; ABI 6 -- until ABI 5 they travelled through a
  * float of asx_debug_fetch, which stops resolving single launches past 2^24): "tdf3_launches" (split-operand row GEMM, either arithmetic),
  * "tdf3h_launches" (those of them, plain or GATHER mode, that ran the fp16 x 3 arithmetic),

@@ -53,22 +53,48 @@ class DemucsSeparator(CommonSeparator):
         self.engine = dm.engine
         return out
 
-    def _demix_on_device(self):
+    def _device_stems(self):
         """RIFF/WAVE input at the model's rate: data chunk -> pinned -> HBM -> asx_pcm_decode_dev -> the demix (single model or
-        bag) -> stems [S, 2, N] that STAY in HBM; ``source`` is their pinned host mirror and every ``source[i].T`` view handed to
-        write_audio is registered against its device tensor, so the int16 pass runs on the device (asx_pcm16_dev) without a
-        second upload.  (None, None) when the file needs the host decoder or the configuration the host combine."""
+        bag) -> stems [S, 2, N] that STAY in HBM.  None when the file needs the host decoder or the configuration the host
+        combine."""
         dm = self.load_model()                      # binds self.engine, which the device decode needs
         mix_d = self._device_mix(self.audio_file_path)
         if mix_d is None:
-            return None, None
+            return None
         t0 = self._now()
         dm.shifts, dm.overlap, dm.segments_enabled = self.shifts, self.overlap, self.segments_enabled
         out_d = dm.demix_dev(mix_d) if hasattr(dm, "demix_dev") else None
         self.engine = dm.engine
+        if out_d is not None:
+            self._tick("demix", t0)
+        return out_d
+
+    def _source_map(self, n_sources):
+        self.demucs_source_map = {2: DEMUCS_2_SOURCE_MAPPER, 6: DEMUCS_6_SOURCE_MAPPER}.get(n_sources, DEMUCS_4_SOURCE_MAPPER)
+        return self.demucs_source_map
+
+    def _single_stem_skips(self, stem_name):
+        return self.output_single_stem is not None and stem_name.lower() != self.output_single_stem.lower()
+
+    def stems_dev(self, audio_file_path):
+        """The stems ``separate(audio_file_path)`` would hand to write_audio, in the order of the source map, left on the device:
+        [(stem name, CUDA tensor [2, N], "planar")]; honours ``output_single_stem``.  None when the file needs the host decoder
+        or the configuration the host combine.  Writes nothing."""
+        self._begin_file(audio_file_path)
+        out_d = self._device_stems()
+        if out_d is None:
+            return None
+        return [(name, out_d[index], "planar") for name, index in self._source_map(len(out_d)).items()
+                if not self._single_stem_skips(name)]
+
+    def _demix_on_device(self):
+        """``_device_stems``; ``source`` is the pinned host mirror of the stems and every ``source[i].T`` view handed to
+        write_audio is registered against its device tensor, so the int16 pass runs on the device (asx_pcm16_dev) without a
+        second upload.  (None, None) when there is no device-resident path for this file."""
+        out_d = self._device_stems()
         if out_d is None:
             return None, None
-        t0 = self._tick("demix", t0)
+        t0 = self._now()
         source, views = self._host_planar_stems(out_d)
         self._sync()
         self._tick("stems_d2h", t0)
@@ -87,11 +113,9 @@ class DemucsSeparator(CommonSeparator):
         return self._emit_stems(source, views, custom_output_names)
 
     def _emit_stems(self, source, views, custom_output_names):
-        n = len(source)
-        self.demucs_source_map = {2: DEMUCS_2_SOURCE_MAPPER, 6: DEMUCS_6_SOURCE_MAPPER}.get(n, DEMUCS_4_SOURCE_MAPPER)
         files = []
-        for stem_name, index in self.demucs_source_map.items():
-            if self.output_single_stem is not None and stem_name.lower() != self.output_single_stem.lower():
+        for stem_name, index in self._source_map(len(source)).items():
+            if self._single_stem_skips(stem_name):
                 self.logger.debug(f"{stem_name}: not written (output_single_stem = {self.output_single_stem})")
                 continue
             path = self.get_stem_output_path(stem_name, custom_output_names)

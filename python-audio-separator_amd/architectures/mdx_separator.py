@@ -83,11 +83,12 @@ class MDXSeparator(CommonSeparator):
         """mdx_separator.py:414-450."""
         return self._dm.run_model(mix, is_match_mix=is_match_mix)
 
-    def _separate_on_device(self, custom_output_names):
-        """The same steps with every array in HBM (RIFF/WAVE input at the model's rate): data chunk -> pinned -> device ->
-        asx_pcm_decode_dev -> asx_separate_dev -> [host mirrors of the float stems, pinned, for ``primary_source`` /
-        ``secondary_source``] -> asx_pcm16_rows_dev per written stem -> int16 back -> container.  The float stems are never
-        uploaded again.  Returns None when the file needs the host decoder (the caller continues on the generic path)."""
+    def _device_stems(self):
+        """The stems of the current file with every array in HBM (RIFF/WAVE input at the model's rate): data chunk -> pinned ->
+        device -> asx_pcm_decode_dev -> asx_separate_dev.  Returns (primary, secondary), CUDA tensors [N, 2], or None when the
+        file needs the host decoder or ``invert_using_spec`` the host path."""
+        if self.invert_using_spec:
+            return None
         mix = self._device_mix(self.audio_file_path)
         if mix is None:
             return None
@@ -99,7 +100,30 @@ class MDXSeparator(CommonSeparator):
         secondary = torch.empty((n, 2), dtype=torch.float32, device=mix.device)
         self.engine.separate_dev(mix.data_ptr(), n, self.normalization_threshold, self.amplification_threshold, self.compensate,
                                  primary.data_ptr(), secondary.data_ptr(), stream=self._stream())
-        t0 = self._tick("demix", t0)
+        self._tick("demix", t0)
+        return primary, secondary
+
+    def stems_dev(self, audio_file_path):
+        """The stems ``separate(audio_file_path)`` would hand to write_audio, in its order (secondary first), left on the device:
+        [(stem name, CUDA tensor [N, 2], "rows")]; honours ``output_single_stem``.  None when the file needs the host decoder
+        (the condition under which ``_device_mix`` returns None).  Writes nothing."""
+        self._begin_file(audio_file_path)
+        stems = self._device_stems()
+        if stems is None:
+            return None
+        primary, secondary = stems
+        return [(name, t, "rows") for name, t in ((self.secondary_stem_name, secondary), (self.primary_stem_name, primary))
+                if self._wanted(name)]
+
+    def _separate_on_device(self, custom_output_names):
+        """``_device_stems`` -> [host mirrors of the float stems, pinned, for ``primary_source`` / ``secondary_source``] ->
+        asx_pcm16_rows_dev per written stem -> int16 back -> container.  The float stems are never uploaded again.  Returns
+        None when the file needs the host decoder (the caller continues on the generic path)."""
+        stems = self._device_stems()
+        if stems is None:
+            return None
+        primary, secondary = stems
+        t0 = self._now()
         if not isinstance(self.primary_source, np.ndarray):
             self.primary_source = self._host_stem(primary)
         if not isinstance(self.secondary_source, np.ndarray):
@@ -111,10 +135,9 @@ class MDXSeparator(CommonSeparator):
     def separate(self, audio_file_path, custom_output_names=None):
         """mdx_separator.py:135-203."""
         self._begin_file(audio_file_path)
-        if not self.invert_using_spec:
-            files = self._separate_on_device(custom_output_names)
-            if files is not None:
-                return files
+        files = self._separate_on_device(custom_output_names)
+        if files is not None:
+            return files
         mix = self.prepare_mix(self.audio_file_path)
         if mix.shape[0] != 2:
             msg = f"Expected a 2-channel audio signal, but got {mix.shape[0]} channels"

@@ -72,10 +72,12 @@ class MDXCSeparator(CommonSeparator):
         """mdxc_separator.py:257-468: dict of stems, or the primary array for a single-target model without residual."""
         return self._demixer().demix(mix)
 
-    def _separate_on_device(self, custom_output_names):
-        """The same steps with every array in HBM (RIFF/WAVE input at the model's rate): decode on the device, normalise the mix in
-        place (asx_normalize_dev), demix, residual stem, normalise every stem in place, host mirrors (pinned) for
-        ``primary_source`` / ``secondary_source``, int16 pass on the device per written stem.  None: take the generic path."""
+    def _device_stems(self):
+        """The stems of the current file with every array in HBM (RIFF/WAVE input at the model's rate): decode on the device,
+        normalise the mix in place (asx_normalize_dev), demix, residual stem, normalise every stem in place.  Returns
+        (stems [S, 2, N] CUDA tensor, kind, [(stem name, row of ``stems``)] in the order ``separate`` writes them) with kind
+        "single" (single-target model without residual), "all" (every stem of a multi-stem model, ``output_single_stem`` does
+        not apply) or "pair" (secondary first).  None: take the generic path."""
         if self.pitch_shift != 0:
             return None               # the pitch round trip runs through demix() on host arrays (mdxc.py _demix_pitched)
         if self.engine is None:
@@ -98,36 +100,59 @@ class MDXCSeparator(CommonSeparator):
         eng.normalize_dev(mix_d.data_ptr(), 2 * n, thr, amp, stream=st)
         names, stems_d = dm.demix_dev(mix_d)
         training = self.model_data.get("training", {}) or {}
-        single = names == [None]
-        if single:
-            wanted = [0]
+        if names == [None]:
+            kind, entries = "single", [(self.primary_stem_name, 0)]
         else:
             order = [training["target_instrument"]] if training.get("target_instrument") else list(training.get("instruments") or [])
             if self.process_all_stems and len(order) > 2:
-                wanted = [names.index(k) for k in order]
+                kind, entries = "all", [(k, names.index(k)) for k in order]
             else:
-                wanted = [names.index(self.primary_stem_name), names.index(self.secondary_stem_name)]
-            for i in sorted(set(wanted)):           # norm(source[name]) of the reference, once per stem, in place
+                kind = "pair"
+                entries = [(self.secondary_stem_name, names.index(self.secondary_stem_name)),
+                           (self.primary_stem_name, names.index(self.primary_stem_name))]
+            for i in sorted({i for _, i in entries}):     # norm(source[name]) of the reference, once per stem, in place
                 eng.normalize_dev(stems_d[i].data_ptr(), 2 * n, thr, amp, stream=st)
-        t0 = self._tick("demix", t0)
+        self._tick("demix", t0)
+        return stems_d, kind, entries
+
+    def stems_dev(self, audio_file_path):
+        """The stems ``separate(audio_file_path)`` would hand to write_audio, in its order, left on the device:
+        [(stem name, CUDA tensor [2, N], "planar")]; honours ``output_single_stem`` where ``separate`` does and carries the
+        residual stem of a single-target model.  None when the file needs the host decoder.  Writes nothing."""
+        self._reset_file_state()
+        self._begin_file(audio_file_path)
+        got = self._device_stems()
+        if got is None:
+            return None
+        stems_d, kind, entries = got
+        return [(name, stems_d[i], "planar") for name, i in entries if kind == "all" or self._wanted(name)]
+
+    def _separate_on_device(self, custom_output_names):
+        """``_device_stems``, host mirrors (pinned) for ``primary_source`` / ``secondary_source``, int16 pass on the device per
+        written stem.  None: take the generic path."""
+        got = self._device_stems()
+        if got is None:
+            return None
+        stems_d, kind, entries = got
+        t0 = self._now()
         _, views = self._host_planar_stems(stems_d)
         self._sync()
         self._tick("stems_d2h", t0)
         files = []
-        if single:
+        if kind == "single":
             if self._wanted(self.primary_stem_name):
                 if not isinstance(self.primary_source, np.ndarray):
                     self.primary_source = views[0]
                 self.primary_stem_output_path = self._emit_stem(self.primary_stem_name, self.primary_source, custom_output_names, files)
             return files
-        if self.process_all_stems and len(wanted) > 2:
-            for k, i in zip(order, wanted):
+        if kind == "all":
+            for k, i in entries:
                 self._emit_stem(k, views[i], custom_output_names, files)
             return files
         if not isinstance(self.primary_source, np.ndarray):
-            self.primary_source = views[wanted[0]]
+            self.primary_source = views[entries[1][1]]
         if not isinstance(self.secondary_source, np.ndarray):
-            self.secondary_source = views[wanted[1]]
+            self.secondary_source = views[entries[0][1]]
         return self._emit_pair(custom_output_names)
 
     def separate(self, audio_file_path, custom_output_names=None):

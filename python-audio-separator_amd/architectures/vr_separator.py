@@ -86,8 +86,9 @@ class VRSeparator(CommonSeparator):
         self._warn_resampler()
         return self._dm
 
-    def separate(self, audio_file_path, custom_output_names=None):
-        """vr_separator.py:115-253."""
+    def _begin_vr_file(self, audio_file_path):
+        """What ``separate`` does before any sample is touched (vr_separator.py:115-156): per-file state, the input's sample
+        format for the writer, the model, the ``output_single_stem`` check.  Returns (demixer, want primary, want secondary)."""
         self._reset_file_state()
         self._begin_file(audio_file_path)
         try:
@@ -106,26 +107,51 @@ class VRSeparator(CommonSeparator):
         self.input_subtype = None
 
         dm = self.load_model()
-        bands = self.model_params["band"]
-        top = bands[len(bands)]
 
         if self.output_single_stem and self.output_single_stem.lower() not in (self.primary_stem_name.lower(),
                                                                                self.secondary_stem_name.lower()):
             self.logger.warning(f"output_single_stem = '{self.output_single_stem}' names neither '{self.primary_stem_name}' nor "
                                 f"'{self.secondary_stem_name}' (model {self.model_name}): ignored, both stems are written")
             self.output_single_stem = None
-        want_p, want_s = self._wanted(self.primary_stem_name), self._wanted(self.secondary_stem_name)
+        return dm, self._wanted(self.primary_stem_name), self._wanted(self.secondary_stem_name)
 
-        primary = secondary = None
-        # device-resident path (RIFF/WAVE at the top band's rate, which is also the rate the stems are written at): the data
-        # chunk is decoded on the device and both stems stay in HBM until the writer's int16 pass
+    def _device_stems(self, dm, audio_file_path):
+        """Device-resident path (RIFF/WAVE at the top band's rate, which is also the rate the stems are written at): the data
+        chunk is decoded on the device and both stems stay in HBM -- one CUDA tensor [2 (primary, secondary), 2, N'].  None when
+        the file needs the host decoder."""
+        bands = self.model_params["band"]
+        top = bands[len(bands)]
         keep = (self.input_subtype, self.input_bit_depth)
         wave_d = self._device_mix(audio_file_path, check_silent=False) if (top["sr"] == self.sample_rate and self.model_samplerate == 44100) else None
-        self.input_subtype, self.input_bit_depth = keep          # _device_mix records prepare_mix's fields; VR keeps its own (above)
-        if wave_d is not None:
+        self.input_subtype, self.input_bit_depth = keep          # _device_mix records prepare_mix's fields; VR keeps its own
+        if wave_d is None:
+            return None
+        t0 = self._now()
+        stems_d = dm.separate_stems_dev(wave_d)
+        self._tick("demix", t0)
+        return stems_d
+
+    def stems_dev(self, audio_file_path):
+        """The stems ``separate(audio_file_path)`` would hand to write_audio, primary first, left on the device:
+        [(stem name, CUDA tensor [2, N'], "planar")]; honours ``output_single_stem``.  None when the file needs the host
+        decoder.  Writes nothing."""
+        dm, want_p, want_s = self._begin_vr_file(audio_file_path)
+        stems_d = self._device_stems(dm, audio_file_path)
+        if stems_d is None:
+            return None
+        return [(name, stems_d[i], "planar") for i, (name, want) in enumerate(((self.primary_stem_name, want_p),
+                                                                              (self.secondary_stem_name, want_s))) if want]
+
+    def separate(self, audio_file_path, custom_output_names=None):
+        """vr_separator.py:115-253."""
+        dm, want_p, want_s = self._begin_vr_file(audio_file_path)
+        bands = self.model_params["band"]
+        top = bands[len(bands)]
+
+        primary = secondary = None
+        stems_d = self._device_stems(dm, audio_file_path)
+        if stems_d is not None:
             t0 = self._now()
-            stems_d = dm.separate_stems_dev(wave_d)
-            t0 = self._tick("demix", t0)
             _, views = self._host_planar_stems(stems_d)
             self._sync()
             self._tick("stems_d2h", t0)

@@ -2306,6 +2306,45 @@ int asx_ensemble_dev(asx_engine *e, const float *waves_dev, int32_t K, int64_t N
   return ens_ensemble_dev(e, waves_dev, K, N, algorithm, weights, out_dev, n_out, reinterpret_cast<hipStream_t>(stream));
 }
 
+// One member stem -> slot k of the [K, 2, n_max] stack asx_ensemble_dev reads, through the member's file round trip
+// (write_audio's normalise + int16, librosa.load's / 32768, the Ensembler's zero padding): ens_slot_kernel.
+int asx_ensemble_slot_dev(asx_engine *e, const float *stem_dev, int64_t n, int32_t layout, float max_peak, float min_peak,
+                          int32_t has_min, int32_t mode, float *stack_dev, int32_t k, int64_t n_max, float *peak_after, void *stream) {
+  REQUIRE(e && stack_dev && (stem_dev || n == 0), "asx_ensemble_slot_dev: bad argument");
+  REQUIRE(n >= 0 && n <= n_max && n_max >= 1 && n_max <= ((int64_t)1 << 38) && k >= 0,
+          "asx_ensemble_slot_dev: need 0 <= n <= n_max, 1 <= n_max <= 2^38 and k >= 0 (n %lld, n_max %lld, k %d)",
+          (long long)n, (long long)n_max, (int)k);
+  REQUIRE(layout == ASX_STEM_PLANAR || layout == ASX_STEM_ROWS, "asx_ensemble_slot_dev: layout %d (0 planar [2, n], 1 rows [n, 2])", (int)layout);
+  REQUIRE(mode == ASX_SLOT_PCM16 || mode == ASX_SLOT_FLOAT32, "asx_ensemble_slot_dev: mode %d (0 pcm16 round trip, 1 float32 copy)", (int)mode);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  CHK(e->d_peak.ensure(256));
+  unsigned int *pk = reinterpret_cast<unsigned int *>(e->d_peak.p) + 3;   // its own word (0: separate / pcm16, 1: decode, 2: normalize_dev)
+  HIPCHK(hipMemsetAsync(pk, 0, 4, s));
+  const int64_t n2 = 2 * n;
+  if (n2 > 0) {
+    const unsigned nb = (unsigned)std::min<int64_t>((n2 + 255) / 256, 2048);
+    CHK(timed(e, ASX_PROF_MISC, 0.0, 4.0 * n2, s, [&]() { hipLaunchKernelGGL(absmax_kernel, dim3(nb), dim3(256), 0, s, stem_dev, n2, pk); }));
+  }
+  float *slot = stack_dev + (size_t)k * 2 * (size_t)n_max;
+  CHK(timed(e, ASX_PROF_MISC, 0.0, 4.0 * (n2 + 2.0 * n_max), s, [&]() {
+    hipLaunchKernelGGL(ens_slot_kernel, dim3((unsigned)((n_max + 255) / 256)), dim3(256), 0, s, stem_dev, n, (int)(layout == ASX_STEM_ROWS), pk,
+                       max_peak, min_peak, (int)has_min, (int)(mode == ASX_SLOT_PCM16), slot, n_max);
+  }));
+  if (peak_after) {
+    float maxv = 0.f;
+    HIPCHK(hipMemcpyAsync(&maxv, pk, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    float scale = 1.0f;
+    if (mode == ASX_SLOT_PCM16) {
+      if (maxv > max_peak) scale = max_peak / maxv;
+      else if (has_min && maxv < min_peak) scale = min_peak / maxv;
+    }
+    *peak_after = maxv * scale;
+  }
+  return ASX_OK;
+}
+
 int asx_invert_stem(asx_engine *e, const float *mix_host, const float *stem_host, int64_t N, float *out_host, int64_t *n_out) {
   REQUIRE(e && mix_host && stem_host && out_host && n_out && N >= 1, "asx_invert_stem: bad argument");
   HIPCHK(hipSetDevice(e->device));

@@ -94,6 +94,47 @@ __global__ __launch_bounds__(256) void ens_take_kernel(const float *__restrict__
   if (i < N) out[(int64_t)ch * N + i] = waves[((int64_t)sel[ch] * 2 + ch) * N + i];
 }
 
+// The edge between an ensemble member and the Ensembler (separator.py:1286, :1335): the member's stem goes through write_audio
+// (spec_utils.normalize, (x * 32767).astype(int16), common_separator.py:309-337) and comes back through librosa.load
+// (int16 / 32768 as float32), and Ensembler.ensemble zero-pads it to the longest wave (ensembler.py:29-30).  One pass, no
+// int16 array: stem = planar [2, n] or rows [n, 2] -> slot [2, n_max] of the stack ens_*_kernel read.  The quantiser is
+// pcm16_kernel's, operation for operation (float32, one rounding each, C truncation), so slot * 32768 IS the int16 that
+// kernel writes; int16 -> float and the division by 2^15 are exact.  quantise == 0: plain copy (+ transpose) and pad.
+// Every element of the slot is written: the stack needs no clearing.
+__global__ __launch_bounds__(256) void ens_slot_kernel(const float *__restrict__ stem, int64_t n, int rows,
+                                                       const unsigned int *peak_bits, float max_peak, float min_peak, int has_min,
+                                                       int quantise, float *__restrict__ slot, int64_t n_max) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_max) return;
+  float l = 0.f, r = 0.f;
+  if (i < n) {
+    l = rows ? stem[2 * i] : stem[i];
+    r = rows ? stem[2 * i + 1] : stem[n + i];
+    if (quantise) {
+      const float maxv = __uint_as_float(*peak_bits);
+      float scale = 1.0f;
+      bool scaled = false;
+      if (maxv > max_peak) {
+        scale = __fdiv_rn(max_peak, maxv);
+        scaled = true;
+      } else if (has_min && maxv < min_peak) {
+        scale = __fdiv_rn(min_peak, maxv);
+        scaled = true;
+      }
+      if (scaled) {
+        l = l * scale;
+        r = r * scale;
+      }
+      const float lq = l * 32767.0f, rq = r * 32767.0f;
+      l = (float)(short)(int)lq * (1.0f / 32768.0f);
+      r = (float)(short)(int)rq * (1.0f / 32768.0f);
+    }
+  }
+  slot[i] = l;
+  slot[n_max + i] = r;
+}
+
 // librosa.stft frame t of channel ch of wave [2, n] (centre, zero padding) -> X[0 .. nh] in LDS
 __device__ __forceinline__ void ens_frame_spectrum(const float *__restrict__ wave, int64_t n, int ch, int t, int hop,
                                                    const float *__restrict__ window, const float2 *__restrict__ tw,

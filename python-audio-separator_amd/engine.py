@@ -275,7 +275,7 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_ensemble_dev", "asx_invert_stem", "asx_normalize", "asx_normalize_dev", "asx_residual_dev",
            "asx_profile_launches", "asx_debug_trace", "asx_resample_sinc", "asx_resample_sinc_dev", "asx_counter",
            "asx_set_stft_window", "asx_op_tdf_block", "asx_op_attention", "asx_op_mha", "asx_get_option",
-           "asx_demix_batch_dev", "asx_separate_batch_dev"]
+           "asx_demix_batch_dev", "asx_separate_batch_dev", "asx_ensemble_slot_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -390,6 +390,7 @@ def load_library():
     lib.asx_ensemble.argtypes = [vp, _FP, i32, i64, i32, C.POINTER(C.c_double), _FP, C.POINTER(i64)]
     lib.asx_ensemble_dev.argtypes = [vp, vp, i32, i64, i32, C.POINTER(C.c_double), vp, C.POINTER(i64), vp]
     lib.asx_invert_stem.argtypes = [vp, _FP, _FP, i64, _FP, C.POINTER(i64)]
+    lib.asx_ensemble_slot_dev.argtypes = [vp, vp, i64, i32, C.c_float, C.c_float, i32, i32, vp, i32, i64, _FP, vp]
     lib.asx_pcm16.argtypes = [vp, _FP, i64, C.c_float, C.c_float, i32, C.POINTER(C.c_int16), _FP]
     lib.asx_normalize.argtypes = [vp, _FP, i64, C.c_float, C.c_float, i32, _FP]
     lib.asx_pcm16_dev.argtypes = [vp, vp, i64, C.c_float, C.c_float, i32, vp, _FP, vp]
@@ -1026,6 +1027,45 @@ class Engine:
         self._check(self._lib.asx_ensemble(self._h, _ptr(stack), len(ws), n, self.ENSEMBLE_ALGORITHMS.index(algorithm), wt, _ptr(out),
                                            C.byref(n_out)))
         return out.reshape(-1)[: 2 * n_out.value].reshape(2, n_out.value).copy()     # the engine writes planar [2, n_out]
+
+    @staticmethod
+    def ensemble_weights(weights, k: int):
+        """The weights Ensembler.ensemble ends up using (ensembler.py:32-44), as a list of k floats, or None for equal weights:
+        a length mismatch, a non-finite value or a zero sum falls back to equal weights."""
+        if weights is None or len(weights) != k:
+            return None
+        w = np.asarray(weights, np.float64)
+        total = np.sum(w)
+        if not np.all(np.isfinite(w)) or not np.isfinite(total) or total == 0:
+            return None
+        return [float(v) for v in w]
+
+    SLOT_LAYOUTS = {"planar": 0, "rows": 1}
+    SLOT_MODES = {"pcm16": 0, "float32": 1}
+
+    def ensemble_slot_dev(self, stem_ptr: int, n_samples: int, layout: str, max_peak: float, min_peak, stack_ptr: int, k: int,
+                          n_max: int, mode: str = "pcm16", stream: int = 0, want_peak: bool = True):
+        """asx_ensemble_slot_dev: a device stem (``layout`` "planar" [2, n] or "rows" [n, 2]) -> slot ``k`` of the device stack
+        [K, 2, n_max] through the member's file round trip (``mode`` "pcm16": normalise, int16, / 32768 -- bit-exact to
+        pcm16_*_dev followed by librosa.load) or as it is ("float32"); zero padded to ``n_max``.  Returns the peak after
+        normalisation (the raw peak for "float32"; synchronises the stream) or None."""
+        pk = C.c_float()
+        self._check(self._lib.asx_ensemble_slot_dev(self._h, stem_ptr or None, n_samples, self.SLOT_LAYOUTS[layout], float(max_peak),
+                                                    float(min_peak or 0.0), int(min_peak is not None), self.SLOT_MODES[mode],
+                                                    stack_ptr or None, k, n_max, C.byref(pk) if want_peak else None, stream or None))
+        return pk.value if want_peak else None
+
+    def ensemble_dev(self, stack_ptr: int, k: int, n_samples: int, algorithm: str, weights, out_ptr: int, stream: int = 0) -> int:
+        """asx_ensemble_dev: a device stack [k, 2, n] -> ``out`` [2, n_out] on the device (room for [2, n]); returns n_out
+        (n, or 1024 * (n // 1024) for the uvr_* algorithms).  ``weights`` as Ensembler.ensemble treats them."""
+        if algorithm not in self.ENSEMBLE_ALGORITHMS:
+            raise ValueError(f"Unknown ensemble algorithm: {algorithm}")
+        w = self.ensemble_weights(weights, k)
+        wt = (C.c_double * k)(*w) if w is not None else None
+        n_out = C.c_int64()
+        self._check(self._lib.asx_ensemble_dev(self._h, stack_ptr or None, k, n_samples, self.ENSEMBLE_ALGORITHMS.index(algorithm), wt,
+                                               out_ptr or None, C.byref(n_out), stream or None))
+        return int(n_out.value)
 
     def invert_stem(self, mixture: np.ndarray, stem: np.ndarray) -> np.ndarray:
         """spec_utils.invert_stem(mixture [2, N], stem [2, N]) -> [N', 2]."""

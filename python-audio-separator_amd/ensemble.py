@@ -1,0 +1,361 @@
+"""Multi-model ensembles with resident members: ``Separator._separate_ensemble`` (audio_separator/separator/separator.py:1242-1392)
+and ``Ensembler`` (audio_separator/separator/ensembler.py) on the HIP engine.
+
+The reference runs K models on one song by reloading each model, writing every stem of every model to a temporary
+directory as a 16-bit file, reading the files back with librosa and combining equal-named stems in numpy.
+``EnsembleSeparator`` keeps the K plugin instances (and their engines) loaded and offers two paths in one class:
+
+* ``via_files=True`` -- that literal flow, minus the reloads: ``member.separate`` into a temporary directory, the files read
+  back (audio_io), ``Engine.ensemble`` on the host arrays, ``write_audio``.  Every piece of it is pinned to reference goldens.
+* the default -- the same result without a file or a host float array between the members and the combine: each member's
+  ``stems_dev`` leaves its stems in HBM, ``asx_ensemble_slot_dev`` applies what the file round trip does to the samples
+  (spec_utils.normalize, ``* 32767 -> int16``, ``/ 32768``, zero padding to the longest contributor) while filling the stack
+  ``asx_ensemble_dev`` reads, and the result is registered as a device stem so that ``write_audio`` quantises it there.
+  Outputs are byte-identical to the file path.
+
+``Ensembler`` is the drop-in for the reference class of that name (``plugin.install(ensembler=True)``).
+"""
+from __future__ import annotations
+
+import logging
+import os
+import re
+import shutil
+import tempfile
+
+import numpy as np
+
+from . import audio_io
+
+# separator.py:29-49, restated: lower-cased stem label -> the group it is ensembled in
+STEM_NAME_MAP = {
+    "vocals": "Vocals", "instrumental": "Instrumental", "inst": "Instrumental", "karaoke": "Instrumental", "other": "Other",
+    "no_vocals": "Instrumental", "drums": "Drums", "bass": "Bass", "guitar": "Guitar", "piano": "Piano",
+    "synthesizer": "Synthesizer", "strings": "Strings", "woodwinds": "Woodwinds", "brass": "Brass", "wind inst": "Wind Inst",
+    "lead vocals": "Lead Vocals", "backing vocals": "Backing Vocals", "primary stem": "Primary Stem",
+    "secondary stem": "Secondary Stem",
+}
+# separator.py:1362: prefixes dropped from a model file name before it is cut to 12 characters (the first match only)
+_SLUG_PREFIXES = ("mel_band_roformer_", "melband_roformer_", "bs_roformer_", "model_bs_roformer_", "UVR-MDX-NET-", "UVR_MDXNET_")
+_SILENT = 1e-6          # write_audio writes no file for a stem whose peak after normalisation is below this
+_LOSSLESS_16 = ("wav", "flac")
+
+
+def raw_stem_name(stem_file_name: str) -> str:
+    """separator.py:1291-1293: the stem label is whatever the FIRST ``_(...)`` of the intermediate file's basename holds -- for an
+    input called ``song_(live).wav`` that is ``live`` for every stem; kept, the files the reference writes depend on it."""
+    match = re.search(r"_\(([^)]+)\)", os.path.basename(stem_file_name))
+    return match.group(1) if match else "Unknown"
+
+
+def canonical_stem_names(raw_names) -> list:
+    """separator.py:1296-1315 for the stems ONE model produced: the group name of each."""
+    has_vocal_stem = any("vocal" in s.lower() for s in raw_names)
+    out = []
+    for raw in raw_names:
+        lower = raw.lower()
+        if "vocal" in lower and "lead" not in lower and "backing" not in lower:
+            out.append("Vocals")
+        elif lower == "other" and len(raw_names) == 2 and has_vocal_stem:
+            out.append("Instrumental")            # the complement of the vocals in a 2-stem model
+        elif lower in STEM_NAME_MAP:
+            out.append(STEM_NAME_MAP[lower])
+        else:
+            out.append(raw.title())
+    return out
+
+
+def model_slugs(model_filenames) -> str:
+    """separator.py:1357-1367."""
+    slugs = []
+    for mf in model_filenames:
+        name = os.path.splitext(mf)[0]
+        for prefix in _SLUG_PREFIXES:
+            if name.startswith(prefix):
+                name = name[len(prefix):]
+                break
+        slugs.append(name[:12])
+    return "_".join(slugs)
+
+
+def ensemble_output_name(base_name, stem_name, custom_output_names=None, preset=None, model_filenames=()) -> str:
+    """separator.py:1350-1368 (without the extension)."""
+    if custom_output_names and stem_name in custom_output_names:
+        return custom_output_names[stem_name]
+    if preset:
+        return f"{base_name}_({stem_name})_preset_{preset}"
+    return f"{base_name}_({stem_name})_custom_ensemble_{model_slugs(model_filenames)}"
+
+
+def effective_weights(weights, k: int, logger=None):
+    """ensembler.py:32-44: the weights a combine of ``k`` waves really uses, as float64 -- ones for None, a length mismatch,
+    a non-finite value or a zero sum."""
+    if weights is None:
+        return np.ones(k)
+    w = np.array(weights, dtype=np.float64)
+    if len(w) != k:
+        if logger:
+            logger.warning(f"Number of weights ({len(w)}) does not match number of waveforms ({k}). Using equal weights.")
+        return np.ones(k)
+    total = np.sum(w)
+    if not np.all(np.isfinite(w)) or not np.isfinite(total) or total == 0:
+        if logger:
+            logger.warning(f"Weights {weights} contain non-finite values or sum to zero. Falling back to equal weights.")
+        return np.ones(k)
+    return w
+
+
+class EnsembleSeparator:
+    ALGORITHMS = ("avg_wave", "median_wave", "min_wave", "max_wave", "avg_fft", "median_fft", "min_fft", "max_fft",
+                  "uvr_max_spec", "uvr_min_spec", "ensemble_wav")
+
+    def __init__(self, members, algorithm="avg_wave", weights=None, preset=None, model_filenames=None, intermediate="pcm16",
+                 via_files=False, logger=None):
+        """``members``: loaded plugin instances (MDXSeparator / MDXCSeparator / DemucsSeparator / VRSeparator, any mix); they
+        and their engines stay resident across files.  ``algorithm`` / ``weights``: Ensembler's.  ``preset`` only names the
+        outputs (``..._preset_<preset>``); ``model_filenames`` (default: each member's model file basename) name them
+        otherwise.  ``intermediate``: "pcm16" (what the reference's 16-bit intermediate files carry, the default) or
+        "float32" (unquantised stems between members and combine; device path only).  ``via_files``: the literal flow."""
+        self.members = list(members)
+        if not self.members:
+            raise ValueError("an ensemble needs at least one member")
+        if algorithm not in self.ALGORITHMS:
+            raise ValueError(f"Unknown ensemble algorithm: {algorithm}")
+        if intermediate not in ("pcm16", "float32"):
+            raise ValueError(f"intermediate must be 'pcm16' or 'float32', not {intermediate!r}")
+        if intermediate == "float32" and via_files:
+            raise ValueError("intermediate='float32' is an option of the device path (via_files=False): the file path's "
+                             "intermediates are the 16-bit files")
+        first = self.members[0]
+        for key in ("sample_rate", "normalization_threshold", "amplification_threshold"):
+            values = [getattr(m, key) for m in self.members]
+            if any(v != values[0] for v in values):
+                # the orchestrator hands every model the same values; intermediates are not resampled between rates
+                raise ValueError(f"ensemble members differ in {key}: {values}")
+        if model_filenames is not None and len(model_filenames) != len(self.members):
+            raise ValueError(f"{len(model_filenames)} model file names for {len(self.members)} members")
+        self.algorithm, self.weights, self.preset = algorithm, weights, preset
+        self.intermediate, self.via_files = intermediate, bool(via_files)
+        self.model_filenames = list(model_filenames) if model_filenames is not None else [
+            os.path.basename(m.model_path) if m.model_path else str(m.model_name) for m in self.members]
+        self.logger = logger or first.logger or logging.getLogger("audio_separator_amd")
+        self.sample_rate = first.sample_rate
+        writer = self.members[-1]                   # separator.py:1372-1379: the model loaded last writes the result
+        self.output_dir, self.output_format = writer.output_dir, writer.output_format
+        self.last_path_taken = None                 # "device" | "files": the path the last input took
+
+    # ---- shared pieces ---------------------------------------------------------------------------------------------
+    def _group_names(self, member, stem_names):
+        """The ensemble group of each stem ``member`` produced for the current file, from the file names it gives them."""
+        return canonical_stem_names([raw_stem_name(member.get_stem_output_path(n, None)) for n in stem_names])
+
+    def _write(self, path, stem_name, source, custom_output_names):
+        """separator.py:1350-1381: name the result, let the last member write it; ``source`` is [N, 2]."""
+        writer = self.members[-1]
+        base_name = os.path.splitext(os.path.basename(path))[0]
+        name = ensemble_output_name(base_name, stem_name, custom_output_names, self.preset, self.model_filenames)
+        output_path = f"{name}.{self.output_format.lower()}"
+        writer.audio_file_path = path
+        writer.output_dir = self.output_dir
+        writer.write_audio(output_path, source)
+        return os.path.join(self.output_dir, output_path) if self.output_dir else output_path
+
+    def _device_path_refusal(self):
+        """Why an input cannot take the device path, or None."""
+        if self.via_files:
+            return "via_files=True"
+        if any(m.use_soundfile for m in self.members):
+            return "a member writes with soundfile (float intermediates, not the 16-bit round trip)"
+        if str(self.output_format).lower() not in _LOSSLESS_16:
+            return f"output_format {self.output_format} is not one of {_LOSSLESS_16} (the intermediates would not be lossless 16-bit)"
+        if any(not hasattr(m, "stems_dev") for m in self.members):
+            return "a member has no device-stem hook"
+        return None
+
+    # ---- the public call ---------------------------------------------------------------------------------------------
+    def separate(self, audio_file_path, custom_output_names=None):
+        """``Separator._separate_ensemble``: a path or a list of paths -> the output files of all of them, in order."""
+        paths = [audio_file_path] if isinstance(audio_file_path, str) else list(audio_file_path)
+        output_files = []
+        for path in paths:
+            self.logger.info(f"Ensemble processing for file: {path}")
+            files = None
+            why = self._device_path_refusal()
+            if why is None:
+                files = self._separate_on_device(path, custom_output_names)
+            elif not self.via_files:
+                self.logger.info(f"{path}: ensemble through intermediate files ({why})")
+            if files is None:
+                files = self._separate_via_files(path, custom_output_names)
+                self.last_path_taken = "files"
+            else:
+                self.last_path_taken = "device"
+            output_files.extend(files)
+        return output_files
+
+    # ---- the literal flow ----------------------------------------------------------------------------------------------
+    def _separate_via_files(self, path, custom_output_names):
+        temp_dir = tempfile.mkdtemp(prefix="audio-separator-ensemble-")
+        try:
+            stems_by_type = {}
+            for member in self.members:
+                saved = member.output_dir
+                member.output_dir = temp_dir
+                try:
+                    # no custom names for the intermediates: their default names carry the stem labels (separator.py:1282-1286)
+                    model_stems = member.separate(path, None)
+                    member.clear_gpu_cache()
+                    member.clear_file_specific_paths()
+                finally:
+                    member.output_dir = saved
+                groups = canonical_stem_names([raw_stem_name(p) for p in model_stems])
+                for stem_path, group in zip(model_stems, groups):
+                    full = stem_path if os.path.isabs(stem_path) else os.path.join(temp_dir, stem_path)
+                    stems_by_type.setdefault(group, []).append(full)
+            engine = self.members[-1].engine
+            outputs = []
+            for stem_name, stem_paths in stems_by_type.items():
+                waveforms, original_channels = [], None
+                for sp in stem_paths:
+                    if not os.path.isfile(sp):
+                        # the member's writer left a silent stem out (peak < 1e-6); the reference would fail on loading it
+                        self.logger.warning(f"{stem_name}: {os.path.basename(sp)} was not written (silent stem), left out of the ensemble")
+                        continue
+                    wav, _ = audio_io.load(sp, mono=False, sr=self.sample_rate)
+                    if wav.ndim == 1:
+                        if original_channels is None:
+                            original_channels = 1
+                        wav = np.asfortranarray([wav, wav])
+                    elif original_channels is None:
+                        original_channels = wav.shape[0]
+                    waveforms.append(wav)
+                if not waveforms:
+                    continue
+                self.logger.info(f"Ensembling {len(waveforms)} stems for type: {stem_name}")
+                ensembled = engine.ensemble(waveforms, self.algorithm, self.weights)
+                if original_channels == 1 and ensembled.shape[0] > 1:
+                    ensembled = ensembled[:1, :]
+                outputs.append(self._write(path, stem_name, ensembled.T, custom_output_names))
+            return outputs
+        finally:
+            shutil.rmtree(temp_dir, ignore_errors=True)
+
+    # ---- the same without files ----------------------------------------------------------------------------------------
+    def _separate_on_device(self, path, custom_output_names):
+        """None: this input needs the file path (a member could not keep its stems on the device)."""
+        import torch
+        writer = self.members[-1]
+        groups = {}                                  # group name -> [(member index, device stem, layout)], first-seen order
+        for index, member in enumerate(self.members):
+            stems = member.stems_dev(path)
+            if stems is None:
+                self.logger.info(f"{path}: ensemble through intermediate files (member {index}, {member.model_name}, needs the host decoder)")
+                member.clear_file_specific_paths()
+                return None
+            names = self._group_names(member, [name for name, _, _ in stems])
+            member.clear_file_specific_paths()
+            for (_, tensor, layout), group in zip(stems, names):
+                groups.setdefault(group, []).append((index, tensor, layout))
+        engine = writer.engine
+        if any(t.device.index != engine.device for contributors in groups.values() for _, t, _ in contributors):
+            self.logger.info(f"{path}: ensemble through intermediate files (members sit on different devices)")
+            return None
+        thr, amp = writer.normalization_threshold, writer.amplification_threshold
+        stream = writer._stream()
+        outputs = []
+        for stem_name, contributors in groups.items():
+            live = list(contributors)
+            stack = None
+            while live:
+                # Ensembler.ensemble pads to the longest wave it is GIVEN: a silent stem (no file in the reference) counts for neither
+                n_max = max(t.shape[1] if layout == "planar" else t.shape[0] for _, t, layout in live)
+                stack = torch.empty((len(live), 2, n_max), dtype=torch.float32, device=live[0][1].device)
+                peaks = []
+                for k, (_, t, layout) in enumerate(live):
+                    if not t.is_contiguous():
+                        t = t.contiguous()
+                    n = t.shape[1] if layout == "planar" else t.shape[0]
+                    peaks.append(engine.ensemble_slot_dev(t.data_ptr(), n, layout, thr, amp, stack.data_ptr(), k, n_max,
+                                                          mode=self.intermediate, stream=stream))
+                silent = [c for c, p in zip(live, peaks) if p < _SILENT]
+                if not silent:
+                    break
+                for index, _, _ in silent:
+                    self.logger.warning(f"{stem_name}: the stem of member {index} ({self.members[index].model_name}) is silent, left out of the ensemble")
+                live = [c for c, p in zip(live, peaks) if not p < _SILENT]
+            if not live:
+                continue
+            self.logger.info(f"Ensembling {len(live)} stems for type: {stem_name}")
+            k, n_max = stack.shape[0], stack.shape[2]
+            if k == 1:
+                result = stack                       # a lone contributor comes out as its round-tripped wave
+            else:
+                out = torch.empty((2 * n_max,), dtype=torch.float32, device=stack.device)
+                n_out = engine.ensemble_dev(stack.data_ptr(), k, n_max, self.algorithm, self.weights, out.data_ptr(), stream=stream)
+                result = out[: 2 * n_out].view(1, 2, n_out)
+            _, views = writer._host_planar_stems(result)
+            writer._sync()
+            outputs.append(self._write(path, stem_name, views[0], custom_output_names))
+        return outputs
+
+
+class Ensembler:
+    """Drop-in for audio_separator.separator.ensembler.Ensembler: same constructor, same ``ensemble(waveforms)``.  Stereo inputs
+    are combined on the device (``Engine.ensemble``); anything else -- mono waves -- takes the numpy restatement of the
+    wave-domain algorithms, and mismatched channel counts raise the reference's ValueError."""
+
+    _engine = None           # one small engine for every instance that is not given one
+
+    def __init__(self, logger, algorithm="avg_wave", weights=None, engine=None):
+        self.logger = logger or logging.getLogger("audio_separator_amd")
+        self.algorithm = algorithm
+        self.weights = weights
+        self.engine = engine
+
+    def _get_engine(self):
+        if self.engine is not None:
+            return self.engine
+        if Ensembler._engine is None:
+            from .engine import Engine, MDXConfig
+            Ensembler._engine = Engine(MDXConfig(n_fft=64, hop_length=16, dim_f=32, segment_size=8))   # the spectral edges need no net
+        return Ensembler._engine
+
+    def ensemble(self, waveforms):
+        """ensembler.py:12-74."""
+        if not waveforms:
+            return None
+        if len(waveforms) == 1:
+            return waveforms[0]
+        waveforms = [np.asarray(w) for w in waveforms]
+        num_channels = waveforms[0].shape[0]
+        if any(w.shape[0] != num_channels for w in waveforms):
+            raise ValueError("All waveforms must have the same number of channels for ensembling.")
+        if all(w.ndim == 2 for w in waveforms) and num_channels == 2:
+            weights = effective_weights(self.weights, len(waveforms), self.logger)
+            if self.weights is not None and not self.algorithm.startswith("avg_") and not np.all(weights == weights[0]):
+                self.logger.warning(f"Weights are ignored for algorithm {self.algorithm}")
+            self.logger.debug(f"Ensembling {len(waveforms)} waveforms using algorithm {self.algorithm}")
+            return self._get_engine().ensemble(waveforms, self.algorithm, list(weights))
+        return self._ensemble_numpy(waveforms)
+
+    def _ensemble_numpy(self, waveforms):
+        """The wave-domain algorithms as the reference computes them (ensembler.py:28-64), for inputs the engine does not take."""
+        max_length = max(w.shape[1] for w in waveforms)
+        waveforms = [np.pad(w, ((0, 0), (0, max_length - w.shape[1]))) if w.shape[1] < max_length else w for w in waveforms]
+        weights = effective_weights(self.weights, len(waveforms), self.logger)
+        if self.algorithm == "avg_wave":
+            ensembled = np.zeros_like(waveforms[0])
+            for w, weight in zip(waveforms, weights):
+                ensembled += w * weight
+            return ensembled / np.sum(weights)
+        stacked = np.array(waveforms)
+        if self.algorithm == "median_wave":
+            return np.median(stacked, axis=0)
+        if self.algorithm in ("min_wave", "max_wave"):
+            pick = np.argmin if self.algorithm == "min_wave" else np.argmax
+            idxs = np.expand_dims(pick(np.abs(stacked), 0), 0)
+            return np.squeeze(np.take_along_axis(stacked, idxs, 0), axis=0)
+        if self.algorithm in EnsembleSeparator.ALGORITHMS:
+            raise ValueError(f"{self.algorithm} of {waveforms[0].shape[0]}-channel waves: the spectral ensembles run on the engine, "
+                             "which takes stereo [2, N] waves")
+        raise ValueError(f"Unknown ensemble algorithm: {self.algorithm}")
