@@ -25,9 +25,7 @@ class MDXSeparator(CommonSeparator):
         self.compensate, self.dim_f, self.n_fft = md["compensate"], md["mdx_dim_f_set"], md["mdx_n_fft_scale_set"]
         self.dim_t = 2 ** md["mdx_dim_t_set"]
         self.config_yaml = md.get("config_yaml")
-        # engine knob, not a reference option: chunks per device batch (results do not depend on it)
-        self._max_batch = int(arch_config.get("asx_max_batch", 0))
-        self._common, self._arch = dict(common_config), dict(arch_config)
+        self._keep_configs(common_config, arch_config)
 
         self.load_model()
 
@@ -83,15 +81,19 @@ class MDXSeparator(CommonSeparator):
         """mdx_separator.py:414-450."""
         return self._dm.run_model(mix, is_match_mix=is_match_mix)
 
-    def _device_stems(self):
-        """The stems of the current file with every array in HBM (RIFF/WAVE input at the model's rate): data chunk -> pinned ->
-        device -> asx_pcm_decode_dev -> asx_separate_dev.  Returns (primary, secondary), CUDA tensors [N, 2], or None when the
-        file needs the host decoder or ``invert_using_spec`` the host path."""
-        if self.invert_using_spec:
-            return None
-        mix = self._device_mix(self.audio_file_path)
-        if mix is None:
-            return None
+    # ---- one file: load (base ``_load_mix``), stems, ``_emit_file`` ---------------------------------------------------------
+    def _device_decode(self, path):
+        return None if self.invert_using_spec else self._device_mix(path)     # invert_stem runs on host arrays
+
+    def _require_stereo(self, mix):
+        if mix.shape[0] != 2:
+            msg = f"Expected a 2-channel audio signal, but got {mix.shape[0]} channels"
+            self.logger.error(msg)
+            raise ValueError(msg)
+
+    def _device_stems(self, mix):
+        """The stems of a mix decoded on the device (CUDA tensor [2, N]) with every array in HBM: asx_separate_dev.  Returns
+        (primary, secondary), CUDA tensors [N, 2]."""
         import torch
         t0 = self._now()
         self.initialize_model_settings()
@@ -106,134 +108,55 @@ class MDXSeparator(CommonSeparator):
     def stems_dev(self, audio_file_path):
         """The stems ``separate(audio_file_path)`` would hand to write_audio, in its order (secondary first), left on the device:
         [(stem name, CUDA tensor [N, 2], "rows")]; honours ``output_single_stem``.  None when the file needs the host decoder
-        (the condition under which ``_device_mix`` returns None).  Writes nothing."""
+        (the condition under which ``_device_decode`` returns None).  Writes nothing."""
         self._begin_file(audio_file_path)
-        stems = self._device_stems()
-        if stems is None:
+        mix = self._device_decode(self.audio_file_path)
+        if mix is None:
             return None
-        primary, secondary = stems
-        return [(name, t, "rows") for name, t in ((self.secondary_stem_name, secondary), (self.primary_stem_name, primary))
-                if self._wanted(name)]
+        stems = dict(zip(("primary", "secondary"), self._device_stems(mix)))
+        return [(name, stems[which], "rows") for name, which in self._wanted_pair()]
 
-    def _separate_on_device(self, custom_output_names):
-        """``_device_stems`` -> [host mirrors of the float stems, pinned, for ``primary_source`` / ``secondary_source``] ->
-        asx_pcm16_rows_dev per written stem -> int16 back -> container.  The float stems are never uploaded again.  Returns
-        None when the file needs the host decoder (the caller continues on the generic path)."""
-        stems = self._device_stems()
-        if stems is None:
-            return None
-        primary, secondary = stems
+    def _emit_file(self, stems, on_device, custom_output_names):
+        """(primary, secondary) of the current file -> its output files.  Decoded on the device: the float stems stay there, the
+        sources are their pinned host mirrors and asx_pcm16_rows_dev quantises each written stem without a second upload.
+        Decoded on the host: host stems and the host writer."""
         t0 = self._now()
-        if not isinstance(self.primary_source, np.ndarray):
-            self.primary_source = self._host_stem(primary)
-        if not isinstance(self.secondary_source, np.ndarray):
-            self.secondary_source = self._host_stem(secondary)
-        self._sync()                     # the host mirrors are complete before anyone can read primary_source / secondary_source
-        self._tick("stems_d2h", t0)
+        mirror = self._host_stem if on_device else self._to_host
+        # a primary_source / secondary_source set before separate() is honoured: unlike MDXC and VR, separate() here does not
+        # reset the file state first (separate_many does, per file)
+        for which, stem in zip(("primary", "secondary"), stems):
+            if not isinstance(getattr(self, f"{which}_source"), np.ndarray):
+                setattr(self, f"{which}_source", mirror(stem))
+        if on_device:
+            self._sync()                 # the host mirrors are complete before anyone can read primary_source / secondary_source
+            self._tick("stems_d2h", t0)
         return self._emit_pair(custom_output_names)
 
     def separate(self, audio_file_path, custom_output_names=None):
         """mdx_separator.py:135-203."""
         self._begin_file(audio_file_path)
-        files = self._separate_on_device(custom_output_names)
-        if files is not None:
-            return files
-        mix = self.prepare_mix(self.audio_file_path)
-        if mix.shape[0] != 2:
-            msg = f"Expected a 2-channel audio signal, but got {mix.shape[0]} channels"
-            self.logger.error(msg)
-            raise ValueError(msg)
-        mix = np.ascontiguousarray(mix, np.float32)
-        self.initialize_model_settings()
-        need_primary = not isinstance(self.primary_source, np.ndarray)
-        need_secondary = not isinstance(self.secondary_source, np.ndarray)
-        # peak / normalise(mix) in place / demix * peak / mix.T - compensate * primary (or invert_stem): MDXDemixer.separate_stems
-        primary, secondary = self._dm.separate_stems(mix)
-        if need_primary:
-            self.primary_source = primary
-        if need_secondary:
-            self.secondary_source = secondary
-
-        return self._emit_pair(custom_output_names)
-
-    # ---- a batch of files in one pooled engine call -----------------------------------------------------------------
-    _PER_FILE = ("audio_file_path", "audio_file_base", "input_bit_depth", "input_subtype", "_file_seconds")
-
-    def _load_for_batch(self, path):
-        """One file as ``separate`` would load it: (device mix [2, N] or None, host mix or None) -- the device decoder when the
-        file allows it, else ``prepare_mix`` with the same refusals."""
-        self._reset_file_state()
-        self._begin_file(path)
-        if not self.invert_using_spec:
-            mix = self._device_mix(self.audio_file_path)
-            if mix is not None:
-                return mix, None
-        mix = self.prepare_mix(self.audio_file_path)
-        if mix.shape[0] != 2:
-            msg = f"Expected a 2-channel audio signal, but got {mix.shape[0]} channels"
-            self.logger.error(msg)
-            raise ValueError(msg)
-        return None, np.ascontiguousarray(mix, np.float32)
-
-    def separate_many(self, paths, custom_output_names=None):
-        """``separate`` for a list of files with ONE pooled engine call: every file is loaded as ``separate`` loads it, the
-        chunks of all of them share the net passes (``asx_separate_batch_dev``), then each file's stems go through the same
-        writer and naming code.  Returns one list of output names per input, in order; the files are byte-identical to those of
-        ``separate(path)`` called per path.
-
-        A file that cannot be used (unreadable, empty or silent, not stereo) fails alone, like the orchestrator's per-file
-        ``try``: its entry in the result is an empty list, the exception is logged and kept in ``self.batch_errors[index]``;
-        the other files are processed.  ``custom_output_names`` applies to every file, as it does in ``separate``."""
-        import torch
-        paths = list(paths)
-        self.batch_errors = {}
-        loaded = []                                       # (index, per-file state, device mix, host mix)
-        for i, path in enumerate(paths):
-            try:
-                dev_mix, host_mix = self._load_for_batch(path)
-            except Exception as e:                        # this file only
-                self.logger.error(f"{path}: {e}")
-                self.batch_errors[i] = e
-                continue
-            loaded.append((i, {k: getattr(self, k) for k in self._PER_FILE}, dev_mix, host_mix))
-        results = [[] for _ in paths]
-        if not loaded:
-            self._reset_file_state()
-            return results
-        self.initialize_model_settings()
-        if self.invert_using_spec:
-            stems = self._dm.separate_stems_many([h for _, _, _, h in loaded])
+        dev_mix, host_mix = self._load_mix(self.audio_file_path)
+        if dev_mix is not None:
+            stems = self._device_stems(dev_mix)
         else:
-            dev = self._torch_device()
-            mixes = [d if d is not None else torch.from_numpy(h).to(dev) for _, _, d, h in loaded]
-            prim = [torch.empty((m.shape[1], 2), dtype=torch.float32, device=dev) for m in mixes]
-            sec = [torch.empty((m.shape[1], 2), dtype=torch.float32, device=dev) for m in mixes]
-            self.engine.separate_batch_dev([(m.data_ptr(), p.data_ptr(), s.data_ptr(), m.shape[1]) for m, p, s in zip(mixes, prim, sec)],
-                                           self.normalization_threshold, self.amplification_threshold, self.compensate,
-                                           stream=self._stream())
-            stems = list(zip(prim, sec))
-        self._in_separate = True
-        try:
-            for (i, state, dev_mix, _), (primary, secondary) in zip(loaded, stems):
-                self._reset_file_state()
-                for k, v in state.items():
-                    setattr(self, k, v)
-                if isinstance(primary, np.ndarray):
-                    self.primary_source, self.secondary_source = primary, secondary
-                elif dev_mix is not None:                 # decoded on the device: the stems stay there for the writer, as in separate()
-                    self.primary_source, self.secondary_source = self._host_stem(primary), self._host_stem(secondary)
-                    self._sync()
-                else:                                     # decoded on the host: host stems and the host writer, as in separate()
-                    self.primary_source, self.secondary_source = primary.cpu().numpy(), secondary.cpu().numpy()
-                try:
-                    results[i] = self._emit_pair(custom_output_names)
-                except Exception as e:
-                    self.logger.error(f"{state['audio_file_path']}: {e}")
-                    self.batch_errors[i] = e
-        except BaseException:
-            self._in_separate = False
-            self._drain_writes(raise_errors=False)
-            raise
-        self._in_separate = False
-        self._drain_writes()
-        return results
+            self.initialize_model_settings()
+            # peak / normalise(mix) in place / demix * peak / mix.T - compensate * primary (or invert_stem): MDXDemixer.separate_stems
+            stems = self._dm.separate_stems(host_mix)
+        return self._emit_file(stems, dev_mix is not None, custom_output_names)
+
+    # ---- a batch of files: the hooks of CommonSeparator._separate_many ------------------------------------------------------
+    separate_many = CommonSeparator._separate_many
+
+    def _pooled_stems(self, mixes):
+        """asx_separate_batch_dev: the chunks of all files share the net passes."""
+        self.initialize_model_settings()                  # after the files are loaded, where separate() runs it
+        if self.invert_using_spec:                        # every file was decoded on the host
+            return self._dm.separate_stems_many([h for _, h in mixes])
+        import torch
+        mixes = self._device_mixes(mixes)
+        prim = [torch.empty((m.shape[1], 2), dtype=torch.float32, device=m.device) for m in mixes]
+        sec = [torch.empty_like(p) for p in prim]
+        self.engine.separate_batch_dev([(m.data_ptr(), p.data_ptr(), s.data_ptr(), m.shape[1]) for m, p, s in zip(mixes, prim, sec)],
+                                       self.normalization_threshold, self.amplification_threshold, self.compensate,
+                                       stream=self._stream())
+        return list(zip(prim, sec))

@@ -22,8 +22,7 @@ class MDXCSeparator(CommonSeparator):
         self.logger.debug(f"MDXC arch params: batch_size={self.batch_size}, segment_size={self.segment_size}, overlap={self.overlap}, "
                           f"override_model_segment_size={self.override_model_segment_size}, pitch_shift={self.pitch_shift}")
         self.is_roformer = getattr(self, "is_roformer_model", False)
-        self._common, self._arch = dict(common_config), dict(arch_config)
-        self._max_batch = int(arch_config.get("asx_max_batch", 0))
+        self._keep_configs(common_config, arch_config)
         self._demixers = {}                 # one engine per chunk geometry (override_model_segment_size may flip per file)
 
         self.load_model()
@@ -72,12 +71,30 @@ class MDXCSeparator(CommonSeparator):
         """mdxc_separator.py:257-468: dict of stems, or the primary array for a single-target model without residual."""
         return self._demixer().demix(mix)
 
+    def _short_file_rule(self, seconds):
+        """mdxc_separator.py:131-138."""
+        if seconds < 10.0 and not self.override_model_segment_size:
+            self.override_model_segment_size = True
+            self.logger.warning(f"{seconds:.2f} s of audio (< 10 s): switching to the configured segment size "
+                                "(override_model_segment_size), as the reference does for short files")
+
+    def _stem_plan(self, names):
+        """What ``separate`` writes of a demix that produced the stems ``names`` (``[None]``: the one array of a single-target
+        model without residual): (kind, [(stem name, key into the demix)]) in the order written.  "single": the primary stem;
+        "all": every stem of a multi-stem model, ``output_single_stem`` does not apply; "pair": secondary first."""
+        if names == [None]:
+            return "single", [(self.primary_stem_name, None)]
+        training = self.model_data.get("training", {}) or {}
+        order = [training["target_instrument"]] if training.get("target_instrument") else list(training.get("instruments") or [])
+        if self.process_all_stems and len(order) > 2:
+            return "all", [(k, k) for k in order]
+        return "pair", [(k, k) for k in (self.secondary_stem_name, self.primary_stem_name)]
+
     def _device_stems(self):
         """The stems of the current file with every array in HBM (RIFF/WAVE input at the model's rate): decode on the device,
         normalise the mix in place (asx_normalize_dev), demix, residual stem, normalise every stem in place.  Returns
-        (stems [S, 2, N] CUDA tensor, kind, [(stem name, row of ``stems``)] in the order ``separate`` writes them) with kind
-        "single" (single-target model without residual), "all" (every stem of a multi-stem model, ``output_single_stem`` does
-        not apply) or "pair" (secondary first).  None: take the generic path."""
+        (stems [S, 2, N] CUDA tensor, kind, [(stem name, row of ``stems``)]) as ``_stem_plan`` has them.  None: take the
+        generic path."""
         if self.pitch_shift != 0:
             return None               # the pitch round trip runs through demix() on host arrays (mdxc.py _demix_pitched)
         if self.engine is None:
@@ -86,11 +103,7 @@ class MDXCSeparator(CommonSeparator):
         if mix_d is None:
             return None
         n = mix_d.shape[1]
-        seconds = n / self.sample_rate
-        if seconds < 10.0 and not self.override_model_segment_size:
-            self.override_model_segment_size = True
-            self.logger.warning(f"{seconds:.2f} s of audio (< 10 s): switching to the configured segment size "
-                                "(override_model_segment_size), as the reference does for short files")
+        self._short_file_rule(n / self.sample_rate)
         dm = self._demixer()
         if dm.engine.device != mix_d.device.index:
             return None
@@ -99,17 +112,9 @@ class MDXCSeparator(CommonSeparator):
         thr, amp = self.normalization_threshold, self.amplification_threshold
         eng.normalize_dev(mix_d.data_ptr(), 2 * n, thr, amp, stream=st)
         names, stems_d = dm.demix_dev(mix_d)
-        training = self.model_data.get("training", {}) or {}
-        if names == [None]:
-            kind, entries = "single", [(self.primary_stem_name, 0)]
-        else:
-            order = [training["target_instrument"]] if training.get("target_instrument") else list(training.get("instruments") or [])
-            if self.process_all_stems and len(order) > 2:
-                kind, entries = "all", [(k, names.index(k)) for k in order]
-            else:
-                kind = "pair"
-                entries = [(self.secondary_stem_name, names.index(self.secondary_stem_name)),
-                           (self.primary_stem_name, names.index(self.primary_stem_name))]
+        kind, entries = self._stem_plan(names)
+        entries = [(name, names.index(key)) for name, key in entries]
+        if kind != "single":
             for i in sorted({i for _, i in entries}):     # norm(source[name]) of the reference, once per stem, in place
                 eng.normalize_dev(stems_d[i].data_ptr(), 2 * n, thr, amp, stream=st)
         self._tick("demix", t0)
@@ -127,72 +132,39 @@ class MDXCSeparator(CommonSeparator):
         stems_d, kind, entries = got
         return [(name, stems_d[i], "planar") for name, i in entries if kind == "all" or self._wanted(name)]
 
-    def _separate_on_device(self, custom_output_names):
-        """``_device_stems``, host mirrors (pinned) for ``primary_source`` / ``secondary_source``, int16 pass on the device per
-        written stem.  None: take the generic path."""
-        got = self._device_stems()
-        if got is None:
-            return None
-        stems_d, kind, entries = got
-        t0 = self._now()
-        _, views = self._host_planar_stems(stems_d)
-        self._sync()
-        self._tick("stems_d2h", t0)
+    def _emit_plan(self, kind, entries, fetch, custom_output_names):
+        """``_stem_plan`` -> files; ``fetch(key)`` is the [N, 2] array of one stem, called once per stem.  ``separate`` has reset
+        the file state, so ``primary_source`` / ``secondary_source`` are always this file's."""
         files = []
-        if kind == "single":
-            if self._wanted(self.primary_stem_name):
-                if not isinstance(self.primary_source, np.ndarray):
-                    self.primary_source = views[0]
-                self.primary_stem_output_path = self._emit_stem(self.primary_stem_name, self.primary_source, custom_output_names, files)
-            return files
         if kind == "all":
-            for k, i in entries:
-                self._emit_stem(k, views[i], custom_output_names, files)
-            return files
-        if not isinstance(self.primary_source, np.ndarray):
-            self.primary_source = views[entries[1][1]]
-        if not isinstance(self.secondary_source, np.ndarray):
-            self.secondary_source = views[entries[0][1]]
-        return self._emit_pair(custom_output_names)
+            for name, key in entries:
+                self._emit_stem(name, fetch(key), custom_output_names, files)
+        elif kind == "pair":
+            self.primary_source, self.secondary_source = fetch(entries[1][1]), fetch(entries[0][1])
+            files = self._emit_pair(custom_output_names)
+        elif self._wanted(self.primary_stem_name):        # "single" (mdxc_separator.py:213-225)
+            self.primary_source = fetch(entries[0][1])
+            self.primary_stem_output_path = self._emit_stem(self.primary_stem_name, self.primary_source, custom_output_names, files)
+        return files
 
     def separate(self, audio_file_path, custom_output_names=None):
         """mdxc_separator.py:118-227."""
         self._reset_file_state()
         self._begin_file(audio_file_path)
-        files = self._separate_on_device(custom_output_names)
-        if files is not None:
-            return files
+        got = self._device_stems()
+        if got is not None:
+            # host mirrors (pinned) of the device stems as the sources; the int16 pass of each written stem runs on the device
+            stems_d, kind, entries = got
+            t0 = self._now()
+            _, views = self._host_planar_stems(stems_d)
+            self._sync()
+            self._tick("stems_d2h", t0)
+            return self._emit_plan(kind, entries, views.__getitem__, custom_output_names)
         mix = self.prepare_mix(self.audio_file_path)
-
-        seconds = mix.shape[1] / self.sample_rate
-        if seconds < 10.0 and not self.override_model_segment_size:
-            self.override_model_segment_size = True
-            self.logger.warning(f"{seconds:.2f} s of audio (< 10 s): switching to the configured segment size "
-                                "(override_model_segment_size), as the reference does for short files")
-
+        self._short_file_rule(mix.shape[1] / self.sample_rate)
         dm = self._demixer()
-        eng = dm.engine
-        norm = lambda w: eng.normalize(w, self.normalization_threshold, self.amplification_threshold)   # noqa: E731
-        mix = norm(np.ascontiguousarray(mix, np.float32))
-        source = dm.demix(mix)
-
-        training = self.model_data.get("training", {}) or {}
-        if not isinstance(source, dict):
-            # single-target model without residual: one array (mdxc_separator.py:213-225)
-            files = []
-            if self._wanted(self.primary_stem_name):
-                if not isinstance(self.primary_source, np.ndarray):
-                    self.primary_source = source.T
-                self.primary_stem_output_path = self._emit_stem(self.primary_stem_name, self.primary_source, custom_output_names, files)
-            return files
-        stems = [training["target_instrument"]] if training.get("target_instrument") else list(training.get("instruments") or [])
-        if self.process_all_stems and len(stems) > 2:
-            files = []
-            for name in stems:
-                self._emit_stem(name, norm(source[name]).T, custom_output_names, files)
-            return files
-        if not isinstance(self.primary_source, np.ndarray):
-            self.primary_source = norm(source[self.primary_stem_name]).T
-        if not isinstance(self.secondary_source, np.ndarray):
-            self.secondary_source = norm(source[self.secondary_stem_name]).T
-        return self._emit_pair(custom_output_names)
+        norm = lambda w: dm.engine.normalize(w, self.normalization_threshold, self.amplification_threshold)   # noqa: E731
+        source = dm.demix(norm(np.ascontiguousarray(mix, np.float32)))
+        kind, entries = self._stem_plan(list(source) if isinstance(source, dict) else [None])
+        # (the one array of a "single" plan goes to the writer as it is; every other stem is normalised when it is fetched)
+        return self._emit_plan(kind, entries, lambda key: source.T if key is None else norm(source[key]).T, custom_output_names)

@@ -47,7 +47,7 @@ class VRSeparator(CommonSeparator):
                                "aggr_correction": self.model_params.get("aggr_correction")}
         self.model_samplerate = self.model_params["sr"]
         self.res_type = resolve_res_type(arch_config.get("asx_res_type"))
-        self._common, self._arch = dict(common_config), dict(arch_config)
+        self._keep_configs(common_config, arch_config)
         self._dm = None
         self.model_run = None
         self.logger.debug(f"VR arch params: enable_tta={self.enable_tta}, enable_post_process={self.enable_post_process}, "
@@ -80,7 +80,7 @@ class VRSeparator(CommonSeparator):
         common = dict(self._common)
         common.update(model_params=self.model_params, primary_stem_name=self.primary_stem_name, logger=self.logger)
         self._dm = VRDemixer(common, self._arch, state_dict, nn_arch_size, capacity=self._common.get("asx_capacity"),
-                             max_batch=int(self._arch.get("asx_max_batch", 0)))
+                             max_batch=self._max_batch)
         self.engine = self._dm.engine
         self.model_run = self._dm.engine.vr_forward
         self._warn_resampler()
@@ -88,7 +88,8 @@ class VRSeparator(CommonSeparator):
 
     def _begin_vr_file(self, audio_file_path):
         """What ``separate`` does before any sample is touched (vr_separator.py:115-156): per-file state, the input's sample
-        format for the writer, the model, the ``output_single_stem`` check.  Returns (demixer, want primary, want secondary)."""
+        format for the writer, the model, the ``output_single_stem`` check.  Returns (demixer, the top band's parameters, want
+        primary, want secondary)."""
         self._reset_file_state()
         self._begin_file(audio_file_path)
         try:
@@ -113,17 +114,17 @@ class VRSeparator(CommonSeparator):
             self.logger.warning(f"output_single_stem = '{self.output_single_stem}' names neither '{self.primary_stem_name}' nor "
                                 f"'{self.secondary_stem_name}' (model {self.model_name}): ignored, both stems are written")
             self.output_single_stem = None
-        return dm, self._wanted(self.primary_stem_name), self._wanted(self.secondary_stem_name)
+        bands = self.model_params["band"]
+        return dm, bands[len(bands)], self._wanted(self.primary_stem_name), self._wanted(self.secondary_stem_name)
 
-    def _device_stems(self, dm, audio_file_path):
+    def _device_stems(self, dm, top, audio_file_path):
         """Device-resident path (RIFF/WAVE at the top band's rate, which is also the rate the stems are written at): the data
         chunk is decoded on the device and both stems stay in HBM -- one CUDA tensor [2 (primary, secondary), 2, N'].  None when
         the file needs the host decoder."""
-        bands = self.model_params["band"]
-        top = bands[len(bands)]
+        # _device_mix records prepare_mix's fields; VR keeps its own (input_subtype None), so they are restored around it
         keep = (self.input_subtype, self.input_bit_depth)
         wave_d = self._device_mix(audio_file_path, check_silent=False) if (top["sr"] == self.sample_rate and self.model_samplerate == 44100) else None
-        self.input_subtype, self.input_bit_depth = keep          # _device_mix records prepare_mix's fields; VR keeps its own
+        self.input_subtype, self.input_bit_depth = keep
         if wave_d is None:
             return None
         t0 = self._now()
@@ -135,8 +136,8 @@ class VRSeparator(CommonSeparator):
         """The stems ``separate(audio_file_path)`` would hand to write_audio, primary first, left on the device:
         [(stem name, CUDA tensor [2, N'], "planar")]; honours ``output_single_stem``.  None when the file needs the host
         decoder.  Writes nothing."""
-        dm, want_p, want_s = self._begin_vr_file(audio_file_path)
-        stems_d = self._device_stems(dm, audio_file_path)
+        dm, top, want_p, want_s = self._begin_vr_file(audio_file_path)
+        stems_d = self._device_stems(dm, top, audio_file_path)
         if stems_d is None:
             return None
         return [(name, stems_d[i], "planar") for i, (name, want) in enumerate(((self.primary_stem_name, want_p),
@@ -144,36 +145,29 @@ class VRSeparator(CommonSeparator):
 
     def separate(self, audio_file_path, custom_output_names=None):
         """vr_separator.py:115-253."""
-        dm, want_p, want_s = self._begin_vr_file(audio_file_path)
-        bands = self.model_params["band"]
-        top = bands[len(bands)]
-
-        primary = secondary = None
-        stems_d = self._device_stems(dm, audio_file_path)
-        if stems_d is not None:
+        dm, top, want_p, want_s = self._begin_vr_file(audio_file_path)
+        stems = self._device_stems(dm, top, audio_file_path)
+        if stems is not None:
             t0 = self._now()
-            _, views = self._host_planar_stems(stems_d)
+            _, stems = self._host_planar_stems(stems)
             self._sync()
             self._tick("stems_d2h", t0)
-            primary, secondary = (views[0] if want_p else None), (views[1] if want_s else None)
         else:
             # loading_mix (:255-291): the top band is the file decoded at the band's rate; everything below happens on the device
             wave, _ = audio_io.load(audio_file_path, sr=top["sr"], mono=False)
             if wave.ndim == 1:
                 wave = np.asarray([wave, wave])
             wave = np.ascontiguousarray(wave, np.float32)
-            primary, secondary = dm.separate_stems(wave, want_primary=want_p, want_secondary=want_s)
+            stems = dm.separate_stems(wave, want_primary=want_p, want_secondary=want_s)
 
-        # primary first here (vr_separator.py:211-246), unlike the MDX family
+        # primary first here (vr_separator.py:211-246), unlike the MDX family; _begin_vr_file has reset the sources
         files = []
-        if want_p:
-            if not isinstance(self.primary_source, np.ndarray):
-                self.primary_source = self._to_44100(primary)
-            self.primary_stem_output_path = self._emit_stem(self.primary_stem_name, self.primary_source, custom_output_names, files)
-        if want_s:
-            if not isinstance(self.secondary_source, np.ndarray):
-                self.secondary_source = self._to_44100(secondary)
-            self.secondary_stem_output_path = self._emit_stem(self.secondary_stem_name, self.secondary_source, custom_output_names, files)
+        for which, name, stem, want in (("primary", self.primary_stem_name, stems[0], want_p),
+                                        ("secondary", self.secondary_stem_name, stems[1], want_s)):
+            if want:
+                source = self._to_44100(stem)
+                setattr(self, f"{which}_source", source)
+                setattr(self, f"{which}_stem_output_path", self._emit_stem(name, source, custom_output_names, files))
         return files
 
     def _to_44100(self, stem):

@@ -10,6 +10,7 @@ a subclass without an engine cannot write audio.
 """
 from __future__ import annotations
 
+import contextlib
 import functools
 import gc
 import logging
@@ -61,16 +62,8 @@ class CommonSeparator:
         if inner is not None:
             @functools.wraps(inner)
             def separate(self, *args, **kwargs):
-                self._in_separate = True
-                try:
-                    result = inner(self, *args, **kwargs)
-                except BaseException:
-                    self._in_separate = False
-                    self._drain_writes(raise_errors=False)      # the caller's exception wins over a writer's
-                    raise
-                self._in_separate = False
-                self._drain_writes()
-                return result
+                with self._writing():
+                    return inner(self, *args, **kwargs)
             cls.separate = separate
 
     def __init__(self, config: dict):
@@ -137,6 +130,12 @@ class CommonSeparator:
         for key, default in table:
             setattr(self, key, arch_config.get(key, default))
 
+    def _keep_configs(self, common_config: dict, arch_config: dict):
+        """What ``load_model`` builds the demixer from.  ``asx_max_batch`` is an engine knob, not a reference option: chunks per
+        device batch (results do not depend on it)."""
+        self._common, self._arch = dict(common_config), dict(arch_config)
+        self._max_batch = int(arch_config.get("asx_max_batch", 0))
+
     def _begin_file(self, audio_file_path: str):
         self.audio_file_path = audio_file_path
         self.audio_file_base = os.path.splitext(os.path.basename(audio_file_path))[0]
@@ -178,6 +177,19 @@ class CommonSeparator:
             if raise_errors:
                 raise err
             self.logger.error(f"a container write failed: {err}")
+
+    @contextlib.contextmanager
+    def _writing(self):
+        """The span in which write_audio may leave container writes to worker threads: they have finished when it ends."""
+        self._in_separate = True
+        try:
+            yield
+        except BaseException:
+            self._in_separate = False
+            self._drain_writes(raise_errors=False)      # the caller's exception wins over a writer's
+            raise
+        self._in_separate = False
+        self._drain_writes()
 
     def _tick(self, phase: str, t0: float) -> float:
         """Accumulate wall time of ``phase`` since ``t0`` (device drained first) when per-file profiling is on."""
@@ -257,6 +269,34 @@ class CommonSeparator:
             raise ValueError(msg)
         return mix
 
+    def _device_decode(self, path):
+        """``_device_mix`` where the plugin lets the device decoder have the file (hook)."""
+        return self._device_mix(path)
+
+    def _require_stereo(self, mix):
+        """The plugin's own refusal of a host mix that is not [2, N] (hook: the texts differ between the architectures)."""
+
+    def _host_mix(self, path):
+        mix = self.prepare_mix(path)
+        self._require_stereo(mix)
+        return np.ascontiguousarray(mix, np.float32)
+
+    def _load_mix(self, path):
+        """One input file as a mix [2, N]: (CUDA tensor, None) when the device decoder takes it, else (None, float32 array) from
+        ``prepare_mix``, with the refusals of both."""
+        mix = self._device_decode(path)
+        return (mix, None) if mix is not None else (None, self._host_mix(path))
+
+    def _device_mixes(self, mixes):
+        """What ``_load_mix`` returned for a list of files -> all of them on the device."""
+        import torch
+        dev = self._torch_device()
+        return [d if d is not None else torch.from_numpy(h).to(dev) for d, h in mixes]
+
+    @staticmethod
+    def _to_host(stems):
+        return stems if isinstance(stems, np.ndarray) else stems.cpu().numpy()
+
     def _host_stem(self, dev_stem):
         """A device stem [N, 2] as the numpy array the reference leaves in ``primary_source`` / ``secondary_source`` (pinned
         staging, one asynchronous copy) and remember which device tensor it mirrors, so write_audio can quantise on the device
@@ -305,14 +345,70 @@ class CommonSeparator:
         files.append(path)
         return path
 
+    def _wanted_pair(self) -> list:
+        """[(stem name, "secondary" | "primary")] of the stems that get written: the secondary one first, then the primary one --
+        the order the reference returns them in (mdx_separator.py:184-203)."""
+        return [(name, which) for name, which in ((self.secondary_stem_name, "secondary"), (self.primary_stem_name, "primary"))
+                if self._wanted(name)]
+
     def _emit_pair(self, custom_output_names) -> list:
-        """Secondary stem first, then the primary one -- the order the reference returns them in (mdx_separator.py:184-203)."""
+        """``secondary_source`` / ``primary_source`` -> files, as ``_wanted_pair`` orders and filters them."""
         files = []
-        if self._wanted(self.secondary_stem_name):
-            self.secondary_stem_output_path = self._emit_stem(self.secondary_stem_name, self.secondary_source, custom_output_names, files)
-        if self._wanted(self.primary_stem_name):
-            self.primary_stem_output_path = self._emit_stem(self.primary_stem_name, self.primary_source, custom_output_names, files)
+        for name, which in self._wanted_pair():
+            path = self._emit_stem(name, getattr(self, f"{which}_source"), custom_output_names, files)
+            setattr(self, f"{which}_stem_output_path", path)
         return files
+
+    # ---- a batch of files in one pooled engine call -----------------------------------------------------------------
+    # A plugin that implements the hooks ``_pooled_stems`` and ``_emit_file`` (and ``_prepare_model`` where it needs one) publishes the
+    # shell as ``separate_many``; the others have no such attribute.
+    _PER_FILE = ("audio_file_path", "audio_file_base", "input_bit_depth", "input_subtype", "_file_seconds")
+
+    def _prepare_model(self):
+        """Hook: what has to be ready before the first file is loaded."""
+
+    def _separate_many(self, paths, custom_output_names=None):
+        """``separate`` for a list of files with ONE pooled engine call: every file is loaded as ``separate`` loads it
+        (``_load_mix``), ``_pooled_stems([(device mix or None, host mix or None)])`` returns the stems of all of them, then
+        ``_emit_file(stems, decoded on the device?, custom_output_names)`` -- the step ``separate`` ends with -- writes each file's.
+        Returns one list of output names per input, in order; the files are byte-identical to those of ``separate(path)`` called
+        per path.
+
+        A file that cannot be used (unreadable, empty or silent, not stereo) fails alone, like the orchestrator's per-file
+        ``try``: its entry in the result is an empty list, the exception is logged and kept in ``self.batch_errors[index]``;
+        the other files are processed.  ``custom_output_names`` applies to every file, as it does in ``separate``."""
+        paths = list(paths)
+        self.batch_errors = {}
+        results = [[] for _ in paths]
+
+        def failed(i, path, e):                           # this file only
+            self.logger.error(f"{path}: {e}")
+            self.batch_errors[i] = e
+        with self._writing():
+            self._prepare_model()
+            loaded = []                                   # (index, per-file state, device mix, host mix)
+            for i, path in enumerate(paths):
+                try:
+                    self._reset_file_state()
+                    self._begin_file(path)
+                    dev_mix, host_mix = self._load_mix(path)
+                except Exception as e:
+                    failed(i, path, e)
+                    continue
+                loaded.append((i, {k: getattr(self, k) for k in self._PER_FILE}, dev_mix, host_mix))
+            if not loaded:
+                self._reset_file_state()
+                return results
+            stems = self._pooled_stems([(d, h) for _, _, d, h in loaded])
+            for (i, state, dev_mix, _), file_stems in zip(loaded, stems):
+                self._reset_file_state()
+                for k, v in state.items():
+                    setattr(self, k, v)
+                try:
+                    results[i] = self._emit_file(file_stems, dev_mix is not None, custom_output_names)
+                except Exception as e:
+                    failed(i, state["audio_file_path"], e)
+        return results
 
     # ---- stem naming -------------------------------------------------------
     def secondary_stem(self, primary_stem: str):

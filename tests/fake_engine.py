@@ -91,6 +91,12 @@ class OracleEngine:
     def separate(self, mix, max_peak, min_peak, compensate):
         return O.separate_stems(mix, self._params(compensate), self._net, max_peak, min_peak)
 
+    def demix_batch(self, mixes, is_match_mix=False):
+        return [self.demix(m, is_match_mix) for m in mixes]
+
+    def separate_batch(self, mixes, max_peak, min_peak, compensate):
+        return [self.separate(m, max_peak, min_peak, compensate) for m in mixes]
+
     # ---- edges ------------------------------------------------------------------------------------------
     def normalize(self, wave, max_peak=1.0, min_peak=None):
         return O.normalize(wave, max_peak, min_peak)

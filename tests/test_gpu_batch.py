@@ -249,6 +249,52 @@ def test_separate_many_files(tmp_path):
     assert audio_io.info(os.path.join(many_dir, want[1][0]))["subtype"] == "PCM_24"
 
 
+@pytest.mark.parametrize("family", ["mdx", "demucs"])
+def test_separate_many_mixed_decode(family, tmp_path, monkeypatch):
+    """One batch in which the first and the last file are decoded on the device and the middle one (PCM_24) on the host, so both
+    branches of the plugin's emit step run between the same pooled call and the same per-file state: the same names and the same
+    bytes as separate() per file under the same decoders (and, for Demucs, the same seed)."""
+    import random
+    from audio_separator_amd import audio_io
+    tag, cls, common, arch, wav, _ = SC.cases(family, str(tmp_path))[0]
+    x, sr = audio_io.read_wav(wav)
+    assert sr == common["sample_rate"] and x.shape[0] == 2
+    srcs = []
+    for i, (n, subtype) in enumerate([(x.shape[1], "PCM_16"), (x.shape[1] * 2 // 3 + 1, "PCM_24"), (x.shape[1] // 3, "PCM_16")]):
+        path = str(tmp_path / f"song{i}.wav")
+        audio_io.write_wav(path, np.ascontiguousarray(x[:, :n].T), sr, subtype)
+        srcs.append(path)
+    klass = SC.plugin_class(cls)
+    real, decoded = klass._device_mix, []
+
+    def device_mix(self, path, check_silent=True):
+        mix = None if path == srcs[1] else real(self, path, check_silent)
+        decoded.append((path, mix is not None))
+        return mix
+    monkeypatch.setattr(klass, "_device_mix", device_mix)
+    mixed = [(srcs[0], True), (srcs[1], False), (srcs[2], True)]
+    one_dir, many_dir = str(tmp_path / "one"), str(tmp_path / "many")
+    inst = klass(common_config=dict(common, output_dir=one_dir), arch_config=arch)
+    random.seed(5)
+    want = []
+    for path in srcs:
+        want.append(inst.separate(path, None))
+        inst.clear_gpu_cache()
+        inst.clear_file_specific_paths()
+    assert decoded == mixed                                          # one decode attempt per file, the middle one refused
+    del decoded[:]
+    inst = klass(common_config=dict(common, output_dir=many_dir), arch_config=arch)
+    random.seed(5)
+    got = inst.separate_many(srcs)
+    assert decoded == mixed and inst.batch_errors == {}
+    assert got == want and all(len(names) == (4 if family == "demucs" else 2) for names in got)
+    for names in want:
+        for name in names:
+            assert filecmp.cmp(os.path.join(one_dir, name), os.path.join(many_dir, name), shallow=False), name
+    assert audio_io.info(os.path.join(many_dir, want[1][0]))["subtype"] == "PCM_24"
+    assert audio_io.info(os.path.join(many_dir, want[2][0]))["subtype"] == "PCM_16"
+
+
 def test_config5_rank_share_on_one_gpu(A):
     """BASELINE config 5's per-rank workload on the HIP engine: 8 distinct seeded songs at the HQ_3 geometry and weights
     through FilesPipeline(world=1, demix_many=...); every stem bit-identical to the single-song demix_dev result."""

@@ -1,6 +1,7 @@
 """CPU side of the batch entry points: FilesPipeline's ``demix_many`` hook over the CPU test double of the engine (world 1 and
 gloo world 2), the Python-level shape / dtype refusals of the batch methods, and the C boundary -- include/asx.h declares
-asx_demix_batch_dev / asx_separate_batch_dev and engine.py binds them with matching argument counts and struct layouts."""
+asx_demix_batch_dev / asx_separate_batch_dev and engine.py binds them with matching argument counts and struct layouts -- and
+``MDXSeparator.separate_many`` over the same double (the batch shell of CommonSeparator on host arrays)."""
 import ctypes as C
 import os
 import re
@@ -166,3 +167,58 @@ def test_header_declares_and_binding_matches():
     assert lib.asx_abi_version() == 7
     # the entry points validate before they touch the engine
     assert lib.asx_demix_batch_dev(None, None, 0, 0, None) != 0 and lib.asx_separate_batch_dev(None, None, 0, 0.9, 0.0, 0, 1.0, None) != 0
+
+
+def test_separate_many_through_the_mdx_plugin(tmp_path, monkeypatch):
+    """The batch shell of CommonSeparator through MDXSeparator over the engine double (tests/test_host_demucs_batch.py drives it
+    through DemucsSeparator): ``invert_using_spec`` keeps every array on the host.  A bad file fails alone, the files equal
+    those of ``separate`` per path byte for byte, and an exception out of the pooled call leaves no write pending."""
+    import filecmp
+    import threading
+    from tests import fake_engine
+    from tests import separate_cases as SC
+    from audio_separator_amd import audio_io
+    fake_engine.install(monkeypatch)
+    monkeypatch.setenv("ASX_ASYNC_WRITES", "0")
+    _, cls, common, arch, _, _ = SC.cases("mdx", str(tmp_path))[0]
+    wavs = []
+    for i, n in enumerate((4000, 6100, 2500)):
+        p = str(tmp_path / f"in{i}.wav")
+        x = (0.3 * np.random.default_rng(40 + i).standard_normal((n, 2))).astype(np.float32)
+        audio_io.write_wav(p, np.clip(x, -0.99, 0.99), common["sample_rate"], "PCM_16")
+        wavs.append(p)
+    bad = str(tmp_path / "broken.wav")
+    with open(bad, "w") as f:
+        f.write("not audio")
+    paths = [wavs[0], bad, wavs[1], str(tmp_path / "missing.wav"), wavs[2]]
+
+    def make(out_dir):
+        return SC.plugin_class(cls)(common_config=dict(common, output_dir=out_dir, invert_using_spec=True), arch_config=arch)
+    one_dir, many_dir = str(tmp_path / "one"), str(tmp_path / "many")
+    sep = make(one_dir)
+    want = []
+    for p in wavs:
+        want.append(sep.separate(p))
+        sep.clear_file_specific_paths()
+    sep = make(many_dir)
+    got = sep.separate_many(paths)
+    assert got[1] == [] and got[3] == [] and sorted(sep.batch_errors) == [1, 3]
+    assert all(isinstance(e, Exception) for e in sep.batch_errors.values())
+    assert [got[0], got[2], got[4]] == want and all(len(names) == 2 for names in want)
+    for names in want:
+        for name in names:
+            assert filecmp.cmp(os.path.join(one_dir, name), os.path.join(many_dir, name), shallow=False), name
+    assert sep.separate_many([bad]) == [[]] and list(sep.batch_errors) == [0]
+    assert sep.audio_file_path is None and sep.primary_source is None          # nothing loaded: the file state is reset
+
+    # an exception out of the pooled call is the caller's; a write that was in flight is joined and its own error only logged
+    def boom(mixes):
+        raise RuntimeError("pooled call failed")
+    monkeypatch.setattr(sep, "_pooled_stems", boom)
+    writer = threading.Thread(target=lambda: None)
+    writer.start()
+    sep._pending_writes.append((writer, [OSError("disk full")]))
+    with pytest.raises(RuntimeError, match="pooled call failed"):
+        sep.separate_many(wavs[:2])
+    assert sep._pending_writes == [] and not writer.is_alive() and sep._in_separate is False
+    assert sep.batch_errors == {}
