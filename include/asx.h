@@ -478,6 +478,29 @@ int asx_vr_separate(asx_engine *e, const float *wave_host, int64_t n_samples, co
 int asx_vr_separate_dev(asx_engine *e, const float *wave_dev, int64_t n_samples, const asx_vr_params *params, float *primary_dev,
                         float *secondary_dev, void *stream);
 
+/* A pool of songs in one call: the patches of all songs share the net passes -- the flat patch list of the pool (song after song,
+ * first every song's plain pass, then, with enable_tta, every song's TTA pass with one more patch each) runs in passes of
+ * even_batches(total, max_batch) patches, so a pass may hold patches of several songs and a song's patches may span several
+ * passes.  The reference separates file by file; a folder of short clips (about 8 patches per 20 s on the 4band_44100 layout,
+ * where the cascade wants 48 per pass) is what this is for.  wave_dev [2, n_samples] at the top band's rate; primary_dev /
+ * secondary_dev [2, n_out] with n_out from asx_vr_plan, either may be NULL (that stem is not synthesised); every output equals
+ * what asx_vr_separate_dev writes for that song alone.  `songs` is HOST memory, read during the call; one asx_vr_params holds for
+ * all songs.  Analysis, peak, mask post-processing and synthesis run per song; enable_post_process synchronises `stream` once
+ * for the pool (asx_vr_separate_dev: twice per song).  Every song is checked before anything is enqueued -- a NULL wave_dev,
+ * fewer than 2 frames, or a refusal of high_end_process reject the call with ASX_ERR_INVALID, the message names the song's
+ * index and no output byte is written; n_songs == 0 is ASX_OK.  Memory: the engine keeps the spectrogram and the mask of EVERY
+ * song of the pool at once (24 * (bins + 1) bytes per frame), the net workspace stays max_batch patches: a caller with more
+ * songs than that allows splits them over several calls.  A pass that touches more than ASX_VR_POOL_SEGMENTS songs takes one
+ * gather and one scatter launch per that many.  (Added within ABI 7: a new function, a new struct and a new counter only.) */
+#define ASX_VR_POOL_SEGMENTS 16
+typedef struct asx_vr_song {
+  const float *wave_dev;    /* [2, n_samples] */
+  int64_t n_samples;
+  float *primary_dev;       /* [2, n_out] or NULL */
+  float *secondary_dev;     /* [2, n_out] or NULL */
+} asx_vr_song;
+int asx_vr_separate_batch_dev(asx_engine *e, const asx_vr_song *songs, int32_t n_songs, const asx_vr_params *params, void *stream);
+
 /* librosa.resample(y, orig_sr, target_sr, res_type="sinc_fastest") for ANY ratio = float(target_sr) / orig_sr, i.e. libsamplerate's
  * SRC_SINC_FASTEST through python-samplerate as above (restated algorithm, regenerated table: parity unpinned).  Replaces
  * spec_utils.change_pitch_semitones (uvr_lib_v5/spec_utils.py:783-790; MDXC pitch_shift, mdxc_separator.py:230-243,268-270) and
@@ -575,6 +598,8 @@ int asx_ensemble_slot_dev(asx_engine *e, const float *stem_dev, int64_t n_sample
  * "conv3h_fin_launches" (those of them in the fused-input form, option "conv_fuse_input": one per net pass where it applies),
  * "down6_launches" / "up6_launches" (ABI 7: conv_down6_kernel / conv_up6_kernel, the level-change convs on the 16-bit matrix pipe),
  * "hd_rounds" (ABI 7: rounds of chunk groups the Demucs v3 forward has run -- the groups of a round share the BLSTM launches),
+ * "vr_net_passes" (ABI 7, additive: passes of the VR net, CascadedASPPNet or CascadedNet, on a batch of patches -- asx_vr_separate_batch_dev runs
+ * fewer of them than a loop of asx_vr_separate_dev over the same songs),
  * "tdf3_pair_image_launches" (ABI 7: the tdf3_kernel launches that read their x operand as a pair image -- option "gemm_pair_images", experimental builds).
  * ASX_ERR_INVALID for an unknown name. */
 int asx_counter(const asx_engine *e, const char *name, int64_t *out);

@@ -86,12 +86,30 @@ class VRSeparator(CommonSeparator):
         self._warn_resampler()
         return self._dm
 
+    def _prepare_model(self):
+        """What ``separate`` does before a sample is touched, apart from the per-file state (vr_separator.py:158-178 and the
+        ``output_single_stem`` check): the resident model -- which binds ``self.engine``, needed by the device decode -- and a
+        single-stem name the model knows."""
+        dm = self.load_model()
+        if self.output_single_stem and self.output_single_stem.lower() not in (self.primary_stem_name.lower(),
+                                                                               self.secondary_stem_name.lower()):
+            self.logger.warning(f"output_single_stem = '{self.output_single_stem}' names neither '{self.primary_stem_name}' nor "
+                                f"'{self.secondary_stem_name}' (model {self.model_name}): ignored, both stems are written")
+            self.output_single_stem = None
+        return dm
+
     def _begin_vr_file(self, audio_file_path):
-        """What ``separate`` does before any sample is touched (vr_separator.py:115-156): per-file state, the input's sample
-        format for the writer, the model, the ``output_single_stem`` check.  Returns (demixer, the top band's parameters, want
-        primary, want secondary)."""
+        """Per-file state and the model.  Returns (demixer, want primary, want secondary)."""
         self._reset_file_state()
         self._begin_file(audio_file_path)
+        dm = self._prepare_model()
+        return dm, self._wanted(self.primary_stem_name), self._wanted(self.secondary_stem_name)
+
+    # what a file leaves for the writer here, on top of the base class's list: VR records the input's sample format itself
+    _PER_FILE = CommonSeparator._PER_FILE + ("wav_subtype", "input_audio_subtype")
+
+    def _probe_vr_format(self, audio_file_path):
+        """vr_separator.py:115-156: the input's sample format for the writer."""
         try:
             self.input_audio_subtype = audio_io.info(audio_file_path)["subtype"]
             if "24" in self.input_audio_subtype:
@@ -107,68 +125,95 @@ class VRSeparator(CommonSeparator):
         # PCM_16 / 24 / 32 from input_bit_depth (common_separator.py:390-402); keep that
         self.input_subtype = None
 
-        dm = self.load_model()
-
-        if self.output_single_stem and self.output_single_stem.lower() not in (self.primary_stem_name.lower(),
-                                                                               self.secondary_stem_name.lower()):
-            self.logger.warning(f"output_single_stem = '{self.output_single_stem}' names neither '{self.primary_stem_name}' nor "
-                                f"'{self.secondary_stem_name}' (model {self.model_name}): ignored, both stems are written")
-            self.output_single_stem = None
+    def _device_decode(self, path):
+        """Device-resident decode (RIFF/WAVE at the top band's rate, which is also the rate the stems are written at).  None
+        when the file needs the host decoder.  A silent file is not refused: the reference's VR path has no such check."""
         bands = self.model_params["band"]
-        return dm, bands[len(bands)], self._wanted(self.primary_stem_name), self._wanted(self.secondary_stem_name)
-
-    def _device_stems(self, dm, top, audio_file_path):
-        """Device-resident path (RIFF/WAVE at the top band's rate, which is also the rate the stems are written at): the data
-        chunk is decoded on the device and both stems stay in HBM -- one CUDA tensor [2 (primary, secondary), 2, N'].  None when
-        the file needs the host decoder."""
+        if not (bands[len(bands)]["sr"] == self.sample_rate and self.model_samplerate == 44100):
+            return None
         # _device_mix records prepare_mix's fields; VR keeps its own (input_subtype None), so they are restored around it
         keep = (self.input_subtype, self.input_bit_depth)
-        wave_d = self._device_mix(audio_file_path, check_silent=False) if (top["sr"] == self.sample_rate and self.model_samplerate == 44100) else None
+        wave_d = self._device_mix(path, check_silent=False)
         self.input_subtype, self.input_bit_depth = keep
-        if wave_d is None:
-            return None
-        t0 = self._now()
-        stems_d = dm.separate_stems_dev(wave_d)
-        self._tick("demix", t0)
-        return stems_d
+        return wave_d
+
+    def _host_mix(self, path):
+        """loading_mix (:255-291): the top band is the file decoded at the band's rate, mono duplicated; never ``prepare_mix``."""
+        bands = self.model_params["band"]
+        wave, _ = audio_io.load(path, sr=bands[len(bands)]["sr"], mono=False)
+        if wave.ndim == 1:
+            wave = np.asarray([wave, wave])
+        return np.ascontiguousarray(wave, np.float32)
+
+    def _load_mix(self, path):
+        """One input file as the top band's wave [2, N]: (CUDA tensor, None) or (None, float32 array), after recording the
+        input's sample format the way this plugin does."""
+        self._probe_vr_format(path)
+        return super()._load_mix(path)
+
+    def _check_loaded(self, dev_mix, host_mix):
+        """A wave too short for the model must not reach the pooled call, which would reject the whole pool."""
+        n = (dev_mix if dev_mix is not None else host_mix).shape[1]
+        frames, _ = self.engine.vr_plan(n)
+        if frames < 2:
+            raise ValueError(f"input too short: {n} samples make {frames} frame(s), the model needs 2")
 
     def stems_dev(self, audio_file_path):
         """The stems ``separate(audio_file_path)`` would hand to write_audio, primary first, left on the device:
         [(stem name, CUDA tensor [2, N'], "planar")]; honours ``output_single_stem``.  None when the file needs the host
         decoder.  Writes nothing."""
-        dm, top, want_p, want_s = self._begin_vr_file(audio_file_path)
-        stems_d = self._device_stems(dm, top, audio_file_path)
-        if stems_d is None:
+        dm, want_p, want_s = self._begin_vr_file(audio_file_path)
+        self._probe_vr_format(audio_file_path)
+        wave_d = self._device_decode(audio_file_path)
+        if wave_d is None:
             return None
+        t0 = self._now()
+        stems_d = dm.separate_stems_dev(wave_d)
+        self._tick("demix", t0)
         return [(name, stems_d[i], "planar") for i, (name, want) in enumerate(((self.primary_stem_name, want_p),
                                                                               (self.secondary_stem_name, want_s))) if want]
 
-    def separate(self, audio_file_path, custom_output_names=None):
-        """vr_separator.py:115-253."""
-        dm, top, want_p, want_s = self._begin_vr_file(audio_file_path)
-        stems = self._device_stems(dm, top, audio_file_path)
-        if stems is not None:
-            t0 = self._now()
-            _, stems = self._host_planar_stems(stems)
-            self._sync()
-            self._tick("stems_d2h", t0)
-        else:
-            # loading_mix (:255-291): the top band is the file decoded at the band's rate; everything below happens on the device
-            wave, _ = audio_io.load(audio_file_path, sr=top["sr"], mono=False)
-            if wave.ndim == 1:
-                wave = np.asarray([wave, wave])
-            wave = np.ascontiguousarray(wave, np.float32)
-            stems = dm.separate_stems(wave, want_primary=want_p, want_secondary=want_s)
-
-        # primary first here (vr_separator.py:211-246), unlike the MDX family; _begin_vr_file has reset the sources
+    def _emit_file(self, stems, on_device, custom_output_names):
+        """The stems of the current file -> its output files, primary first (vr_separator.py:211-246), unlike the MDX family.
+        ``stems``: one CUDA tensor [2 (primary, secondary), 2, N'] -- mirrored into pinned host memory with every ``stems[i].T``
+        view registered against its device tensor when the file was decoded on the device, so the int16 pass runs there; brought
+        to the host otherwise -- or the pair of host arrays [N', 2] (None = not wanted) of ``VRDemixer.separate_stems``."""
+        if not isinstance(stems, (tuple, list)):
+            if on_device:
+                t0 = self._now()
+                _, stems = self._host_planar_stems(stems)
+                self._sync()
+                self._tick("stems_d2h", t0)
+            else:
+                stems = [stem.T for stem in self._to_host(stems)]
         files = []
-        for which, name, stem, want in (("primary", self.primary_stem_name, stems[0], want_p),
-                                        ("secondary", self.secondary_stem_name, stems[1], want_s)):
-            if want:
+        for which, name, stem in (("primary", self.primary_stem_name, stems[0]), ("secondary", self.secondary_stem_name, stems[1])):
+            if self._wanted(name):
                 source = self._to_44100(stem)
                 setattr(self, f"{which}_source", source)
                 setattr(self, f"{which}_stem_output_path", self._emit_stem(name, source, custom_output_names, files))
         return files
+
+    def separate(self, audio_file_path, custom_output_names=None):
+        """vr_separator.py:115-253."""
+        dm, want_p, want_s = self._begin_vr_file(audio_file_path)
+        dev_mix, host_mix = self._load_mix(audio_file_path)
+        if dev_mix is not None:
+            t0 = self._now()
+            stems = dm.separate_stems_dev(dev_mix)
+            self._tick("demix", t0)
+        else:
+            stems = dm.separate_stems(host_mix, want_primary=want_p, want_secondary=want_s)
+        return self._emit_file(stems, dev_mix is not None, custom_output_names)
+
+    # ---- a batch of files: the hooks of CommonSeparator._separate_many ------------------------------------------------------
+    separate_many = CommonSeparator._separate_many
+
+    def _pooled_stems(self, mixes):
+        """``VRDemixer.separate_stems_many_dev``: the patches of all files share the net passes; a stem ``output_single_stem``
+        leaves out is not synthesised."""
+        return self._dm.separate_stems_many_dev(self._device_mixes(mixes), want_primary=self._wanted(self.primary_stem_name),
+                                                want_secondary=self._wanted(self.secondary_stem_name))
 
     def _to_44100(self, stem):
         """vr_separator.py:218-220, :238-240: models trained at another rate are brought back with librosa.resample's

@@ -360,12 +360,16 @@ class CommonSeparator:
         return files
 
     # ---- a batch of files in one pooled engine call -----------------------------------------------------------------
-    # A plugin that implements the hooks ``_pooled_stems`` and ``_emit_file`` (and ``_prepare_model`` where it needs one) publishes the
-    # shell as ``separate_many``; the others have no such attribute.
+    # A plugin that implements the hooks ``_pooled_stems`` and ``_emit_file`` (and ``_prepare_model`` / ``_check_loaded`` where it needs
+    # one) publishes the shell as ``separate_many``; the others have no such attribute.  ``_PER_FILE`` lists what loading a file leaves
+    # for its writer; a plugin that records more extends it.
     _PER_FILE = ("audio_file_path", "audio_file_base", "input_bit_depth", "input_subtype", "_file_seconds")
 
     def _prepare_model(self):
         """Hook: what has to be ready before the first file is loaded."""
+
+    def _check_loaded(self, dev_mix, host_mix):
+        """Hook: refuse (raise for) a loaded file that the pooled call could not take, so that it fails alone."""
 
     def _separate_many(self, paths, custom_output_names=None):
         """``separate`` for a list of files with ONE pooled engine call: every file is loaded as ``separate`` loads it
@@ -392,6 +396,7 @@ class CommonSeparator:
                     self._reset_file_state()
                     self._begin_file(path)
                     dev_mix, host_mix = self._load_mix(path)
+                    self._check_loaded(dev_mix, host_mix)
                 except Exception as e:
                     failed(i, path, e)
                     continue

@@ -2170,8 +2170,8 @@ int asx_vr_analysis(asx_engine *e, const float *wave_host, int64_t n_samples, fl
   DevBuf dw;
   BufGuard g{{&dw}};
   CHK(to_dev(dw, wave_host, (size_t)2 * n_samples));
-  n.he_n = 0;
-  CHK(vr_analysis_dev(e, dw.f(), n_samples, T, nullptr));
+  CHK(n.X.ensure((size_t)2 * T * n.nb1 * 8));
+  CHK(vr_analysis_dev(e, dw.f(), n_samples, VrSongView{reinterpret_cast<float2 *>(n.X.p), nullptr, nullptr, nullptr, T, 0}, nullptr));
   CHK(to_host(spec_host, n.X, (size_t)2 * T * n.nb1 * 2));
   return ASX_OK;
 }
@@ -2182,6 +2182,13 @@ int asx_vr_separate_dev(asx_engine *e, const float *wave_dev, int64_t n_samples,
   READY(e->vr, "asx_vr_separate_dev");
   HIPCHK(hipSetDevice(e->device));
   return vr_separate_dev(e, wave_dev, n_samples, params, primary_dev, secondary_dev, reinterpret_cast<hipStream_t>(stream));
+}
+
+int asx_vr_separate_batch_dev(asx_engine *e, const asx_vr_song *songs, int32_t n_songs, const asx_vr_params *params, void *stream) {
+  REQUIRE(e && params && n_songs >= 0 && (songs || n_songs == 0), "asx_vr_separate_batch_dev: bad argument");
+  READY(e->vr, "asx_vr_separate_batch_dev");
+  HIPCHK(hipSetDevice(e->device));
+  return vr_separate_pool_dev(e, songs, n_songs, params, reinterpret_cast<hipStream_t>(stream));
 }
 
 int asx_vr_separate(asx_engine *e, const float *wave_host, int64_t n_samples, const asx_vr_params *params, float *primary_host,
@@ -2220,6 +2227,7 @@ int asx_counter(const asx_engine *e, const char *name, int64_t *out) {
   else if (nm == "down6_launches") *out = (int64_t)g_down6_launches.load();
   else if (nm == "up6_launches") *out = (int64_t)g_up6_launches.load();
   else if (nm == "hd_rounds") *out = (int64_t)g_hd_rounds.load();
+  else if (nm == "vr_net_passes") *out = (int64_t)g_vr_net_passes.load();
   else {
     set_err("asx_counter: unknown counter '%s'", name);
     return ASX_ERR_INVALID;

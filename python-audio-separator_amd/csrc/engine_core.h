@@ -278,12 +278,7 @@ struct asx_engine {
 // launch enough workgroups to fill 256 CUs (measured 328 vs 337 ms per song against batches of 8)
 static int pick_batch(const asx_engine *e) { return e->cfg.max_batch > 0 ? e->cfg.max_batch : 64; }
 
-// Items per launch when nk >= 1 items run in the fewest batches of at most maxB: evened out, so that no short tail batch runs
-// alone (85 items at maxB 32: 29 + 29 + 27, not 32 + 32 + 21).  The callers walk `for (j = 0; j < nk; j += per)`.
-static int even_batches(int nk, int maxB) {
-  const int nbatch = (nk + maxB - 1) / maxB;
-  return (nk + nbatch - 1) / nbatch;
-}
+#include "batching.h"   // even_batches
 
 // ----------------------------------------------------------------------------
 // profiling wrapper

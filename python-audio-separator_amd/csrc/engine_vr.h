@@ -1,7 +1,13 @@
 // VR architecture on the engine: VRSeparator.loading_mix / inference_vr / spec_to_wav
 // (architectures/vr_separator.py:255-375), the spec_utils band logic they call and CascadedASPPNet
 // (uvr_lib_v5/vr_network/nets.py:95-175, layers.py).  Included by asx.hip (one TU).
+//
+// One call keeps the state of the songs it separates in the buffers X, M, HE (slabs) and peak, fmin, wgt (slots) of VrNet: the
+// single-song call uses them for its one song; asx_vr_separate_batch_dev lays the songs of a pool end to end in them
+// (vr_pool_plan.h), so the slabs hold the WHOLE pool at once -- 2 * (bins + 1) * 12 bytes per frame of every song -- and stay
+// that large afterwards.  Walking a very large pool in waves is left to the caller.
 #pragma once
+#include "vr_pool_plan.h"
 
 struct VrConv {
   HtGemm g;
@@ -67,7 +73,12 @@ struct VrNet {
     std::vector<float *> D, E, O;
   } b;
   DevBuf X, M, M2, peak, fmin, wgt, frames, wss, HE, sinc_tab;
-  int he_n = 0;   // rows kept for high_end_process (0 = off for the current call)
+  // The pool's merge weights on their way to `wgt`.  The upload is asynchronous and this vector is pageable, so it must not change
+  // while a copy may be in flight: it is written only in vr_separate_pool_dev, right after that call has synchronised its stream
+  // (the fmin read-back), which also drains the previous pool's upload -- on the SAME stream.  An engine serves one stream at a
+  // time (its workspaces are shared anyway); calls on two streams at once are not supported.
+  std::vector<float> wgt_host;
+  VrPlanCfg plan_cfg;            // what vr_pool_plan.h needs of the committed net (vr_commit)
   std::vector<DevBuf> wav_ana, wav_syn, wav_up;
 };
 
@@ -302,6 +313,7 @@ static int vr_sinc_table(DevBuf &buf) {
 }
 
 static int vr51_commit_net(asx_engine *e);
+static VrPlanCfg vr_plan_cfg(const VrNet &n);
 
 static int vr_commit(asx_engine *e) {
   VrNet &n = *e->vr;
@@ -451,6 +463,7 @@ static int vr_commit(asx_engine *e) {
   }
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&vr_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_f);
   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&vr_istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds_i);
+  n.plan_cfg = vr_plan_cfg(n);
   n.ready = true;
   return ASX_OK;
 }
@@ -578,8 +591,11 @@ static int vr_ensure_workspace(asx_engine *e, int B) {
   return ASX_OK;
 }
 
+static std::atomic<long long> g_vr_net_passes{0};   // calls of vr_net_dev / vr51_net_dev since the process started (asx_counter "vr_net_passes")
+
 // CascadedASPPNet.forward (nets.py:132-161) on B patches already in hc[..., 0:4]; result (sigmoid mask) in b.mk [B, max_bin, W, 4]
 static int vr_net_dev(asx_engine *e, int B, hipStream_t s) {
+  g_vr_net_passes.fetch_add(1);
   VrNet &n = *e->vr;
   const asx_vr_config &c = n.cfg;
   auto &b = n.b;
@@ -827,6 +843,7 @@ static int vr51_ensure_workspace(asx_engine *e, int B) {
 
 // CascadedNet.forward (nets_new.py:115-150) on B windows already in hc[..., 0:4]
 static int vr51_net_dev(asx_engine *e, int B, hipStream_t s) {
+  g_vr_net_passes.fetch_add(1);
   VrNet &n = *e->vr;
   const asx_vr_config &c = n.cfg;
   auto &b = n.b;
@@ -927,32 +944,53 @@ static int resample_sinc_dev(asx_engine *e, DevBuf &tabbuf, const float *x, int 
 }
 
 static int64_t vr_resampled_len(const VrFilt &f, int64_t n_in) {   // ceil(n * ratio) == resample_poly's n_out == librosa's fix_length
-  const int64_t t = n_in * f.up;
-  return t / f.down + (t % f.down ? 1 : 0);
+  return vr_plan_resampled_len(f.up, f.down, n_in);
+}
+
+// what the host-only plan (vr_pool_plan.h) needs of the committed net; built once, by vr_commit
+static VrPlanCfg vr_plan_cfg(const VrNet &n) {
+  const asx_vr_config &c = n.cfg;
+  VrPlanCfg pc;
+  pc.band.resize(c.n_bands);
+  for (int d = 0; d < c.n_bands; ++d) {
+    pc.band[d].hl = n.band[d].b.hl;
+    if (d < c.n_bands - 1) {
+      pc.band[d].up = n.band[d].ana.up;
+      pc.band[d].down = n.band[d].ana.down;
+    }
+  }
+  pc.window_size = c.window_size;
+  pc.offset = c.offset;
+  pc.max_batch = c.max_batch;
+  pc.top_n_fft = c.band[c.n_bands - 1].n_fft;
+  pc.top_crop_stop = c.band[c.n_bands - 1].crop_stop;
+  pc.pre_filter_start = c.pre_filter_start;
+  pc.pre_filter_stop = c.pre_filter_stop;
+  return pc;
 }
 
 // frames of the combined spectrogram and output length for an input of n samples at the top band's rate
 static int vr_plan(const VrNet &n, int64_t n_samples, int *T, int64_t *n_out) {
-  const int NB = n.cfg.n_bands;
-  int64_t len = n_samples;
-  int Tmin = 0;
-  for (int d = NB - 1; d >= 0; --d) {
-    if (d < NB - 1) len = vr_resampled_len(n.band[d].ana, len);
-    const int t = (int)(1 + len / n.band[d].b.hl);
-    Tmin = d == NB - 1 ? t : std::min(Tmin, t);
-  }
-  *T = Tmin;
-  *n_out = (int64_t)n.band[NB - 1].b.hl * (Tmin - 1);
+  vr_plan_frames(n.plan_cfg, n_samples, T, n_out);
   return ASX_OK;
 }
 
+// one song's share of the call's state: spectrogram [2, T, bins+1] complex, mask [2, T, bins+1], the rows high_end_process
+// keeps [2, T, he_n] complex (he_n = 0: off for the current call), the peak slot
+struct VrSongView {
+  float2 *X;
+  float *M;
+  float2 *HE;
+  unsigned int *peak;
+  int T, he_n;
+};
+
 // loading_mix (vr_separator.py:255-291): wave [2, n] float32 at band[N].sr -> X [2, T, bins+1] complex64
-static int vr_analysis_dev(asx_engine *e, const float *wave, int64_t n_samples, int T, hipStream_t s) {
+static int vr_analysis_dev(asx_engine *e, const float *wave, int64_t n_samples, const VrSongView &v, hipStream_t s) {
   VrNet &n = *e->vr;
-  const int NB = n.cfg.n_bands;
+  const int NB = n.cfg.n_bands, T = v.T;
   n.wav_ana.resize(NB);
-  CHK(n.X.ensure((size_t)2 * T * n.nb1 * 8));
-  HIPCHK(hipMemsetAsync(n.X.p, 0, (size_t)2 * T * n.nb1 * 8, s));
+  HIPCHK(hipMemsetAsync(v.X, 0, (size_t)2 * T * n.nb1 * 8, s));
   const float *cur = wave;
   int64_t len = n_samples;
   std::vector<int> row_off(NB, 0);
@@ -968,9 +1006,9 @@ static int vr_analysis_dev(asx_engine *e, const float *wave, int64_t n_samples, 
     }
     CHK(timed(e, ASX_PROF_STFT, 0.0, 8.0 * len + 16.0 * T * (B.b.crop_stop - B.b.crop_start), s, [&]() {
       hipLaunchKernelGGL(vr_stft_kernel, dim3(T, 2), dim3(256), stft_lds(B.plan), s, cur, len, B.b.hl, n.cfg.v51 ? B.b.convert : n.cfg.channel_mode,
-                         B.b.crop_start, B.b.crop_stop, row_off[d], n.nb1, n.gain_ana.f(), reinterpret_cast<float2 *>(n.X.p),
+                         B.b.crop_start, B.b.crop_stop, row_off[d], n.nb1, n.gain_ana.f(), v.X,
                          B.window.f(), reinterpret_cast<const float2 *>(B.tw.p), B.plan,
-                         (d == NB - 1 && n.he_n > 0) ? reinterpret_cast<float2 *>(n.HE.p) : nullptr, n.he_n);
+                         (d == NB - 1 && v.he_n > 0) ? v.HE : nullptr, v.he_n);
     }));
   }
   return ASX_OK;
@@ -1058,9 +1096,9 @@ static bool vr_artifact_weight(const std::vector<float> &fmin, float thres, std:
 }
 
 // cmb_spectrogram_to_wave (spec_utils.py:341-396) of y_spec (which = 0) or v_spec (which = 1) -> out [2, n_out]
-static int vr_synthesis_dev(asx_engine *e, int which, const float *M, int T, float *out, int64_t n_out, hipStream_t s) {
+static int vr_synthesis_dev(asx_engine *e, int which, const VrSongView &v, float *out, int64_t n_out, hipStream_t s) {
   VrNet &n = *e->vr;
-  const int NB = n.cfg.n_bands;
+  const int NB = n.cfg.n_bands, T = v.T;
   n.wav_syn.resize(NB);
   n.wav_up.resize(NB);
   int row_off = 0;
@@ -1085,11 +1123,11 @@ static int vr_synthesis_dev(asx_engine *e, int which, const float *M, int T, flo
       HIPCHK(hipGetLastError());
     }
     CHK(timed(e, ASX_PROF_ISTFT, 0.0, 4.0 * 2 * T * (3.0 * (B.b.crop_stop - B.b.crop_start) + nf), s, [&]() {
-      hipLaunchKernelGGL(vr_istft_kernel, dim3(T, 2), dim3(256), istft_lds(B.plan), s, reinterpret_cast<const float2 *>(n.X.p), M, which,
+      hipLaunchKernelGGL(vr_istft_kernel, dim3(T, 2), dim3(256), istft_lds(B.plan), s, (const float2 *)v.X, (const float *)v.M, which,
                          n.nb1, B.b.crop_start, B.b.crop_stop, row_off, B.gain_syn.f(), n.frames.f(), B.window.f(),
                          reinterpret_cast<const float2 *>(B.tw.p), B.plan,
-                         (d == NB - 1 && n.he_n > 0) ? reinterpret_cast<const float2 *>(n.HE.p) : nullptr, n.he_n,
-                         n.cfg.pre_filter_start - 10 - n.he_n);
+                         (d == NB - 1 && v.he_n > 0) ? (const float2 *)v.HE : nullptr, v.he_n,
+                         n.cfg.pre_filter_start - 10 - v.he_n);
     }));
     row_off += B.b.crop_stop - B.b.crop_start;
     float *dst = d == NB - 1 ? out : nullptr;
@@ -1117,6 +1155,22 @@ static int vr_synthesis_dev(asx_engine *e, int which, const float *M, int T, flo
   return ASX_OK;
 }
 
+// adjust_aggr (spec_utils.py:472-492) of one song's mask
+static int vr_aggr_dev(asx_engine *e, const asx_vr_params *pr, float *M, int T, hipStream_t s) {
+  VrNet &n = *e->vr;
+  double aggr = (double)pr->aggr_value * 2.0;
+  if (aggr == 0.0) return ASX_OK;
+  if (pr->is_non_accom) aggr = 1.0 - aggr;
+  double a0 = aggr, a1 = aggr;
+  if (pr->has_corr) {
+    a0 += pr->corr_left;
+    a1 += pr->corr_right;
+  }
+  const int64_t nx = (int64_t)2 * T * n.nb1;
+  return vr_ew(e, s, nx, 8.0 * nx, vr_aggr_kernel, M, T, n.nb1, (int)pr->split_bin, (float)(1.0 + a0 / 3.0), (float)(1.0 + a0),
+               (float)(1.0 + a1 / 3.0), (float)(1.0 + a1));
+}
+
 // VRSeparator.separate on arrays (vr_separator.py:168-236): wave [2, n] -> primary [2, n_out], secondary [2, n_out]
 static int vr_separate_dev(asx_engine *e, const float *wave, int64_t n_samples, const asx_vr_params *pr, float *primary, float *secondary,
                            hipStream_t s) {
@@ -1126,7 +1180,7 @@ static int vr_separate_dev(asx_engine *e, const float *wave, int64_t n_samples, 
   int64_t n_out;
   CHK(vr_plan(n, n_samples, &T, &n_out));
   REQUIRE(T >= 2, "input too short: %d frames", T);
-  n.he_n = 0;
+  int he_n = 0;
   if (pr->high_end_process) {
     // input_high_end_h (vr_separator.py:287): bins above the top band's crop + the pre-filter ramp
     const asx_vr_band &tb = c.band[c.n_bands - 1];
@@ -1135,13 +1189,17 @@ static int vr_separate_dev(asx_engine *e, const float *wave, int64_t n_samples, 
             h);
     const int t_top = (int)(1 + n_samples / tb.hl);
     REQUIRE(t_top == T, "high_end_process needs the top band's frame count (%d) to equal the combined spectrogram's (%d)", t_top, T);
-    n.he_n = h;
+    he_n = h;
     CHK(n.HE.ensure((size_t)2 * T * h * 8));
   }
-  CHK(vr_analysis_dev(e, wave, n_samples, T, s));
-  CHK(n.peak.ensure(4));
-  HIPCHK(hipMemsetAsync(n.peak.p, 0, 4, s));
   const int64_t nx = (int64_t)2 * T * n.nb1;
+  CHK(n.X.ensure((size_t)nx * 8));
+  CHK(n.M.ensure((size_t)nx * 4));
+  CHK(n.peak.ensure(4));
+  // this call's one song owns the state buffers from their start
+  const VrSongView v{reinterpret_cast<float2 *>(n.X.p), n.M.f(), reinterpret_cast<float2 *>(n.HE.p), reinterpret_cast<unsigned int *>(n.peak.p), T, he_n};
+  CHK(vr_analysis_dev(e, wave, n_samples, v, s));
+  HIPCHK(hipMemsetAsync(n.peak.p, 0, 4, s));
   hipLaunchKernelGGL(vr_absmax_kernel, dim3(512), dim3(256), 0, s, reinterpret_cast<const float2 *>(n.X.p), nx,
                      reinterpret_cast<unsigned int *>(n.peak.p));
   HIPCHK(hipGetLastError());
@@ -1150,21 +1208,9 @@ static int vr_separate_dev(asx_engine *e, const float *wave, int64_t n_samples, 
   int roi = W - 2 * c.offset;
   if (roi == 0) roi = W;
   const int patches = T / roi + 1;
-  CHK(n.M.ensure((size_t)nx * 4));
   CHK(vr_mask_pass(e, T, c.offset, 0, patches, 0, n.M.f(), s));
   if (pr->enable_tta) CHK(vr_mask_pass(e, T, c.offset + roi / 2, roi / 2, patches + 1, 1, n.M.f(), s));
-  // adjust_aggr (spec_utils.py:472-492)
-  double aggr = (double)pr->aggr_value * 2.0;
-  if (aggr != 0.0) {
-    if (pr->is_non_accom) aggr = 1.0 - aggr;
-    double a0 = aggr, a1 = aggr;
-    if (pr->has_corr) {
-      a0 += pr->corr_left;
-      a1 += pr->corr_right;
-    }
-    CHK(vr_ew(e, s, nx, 8.0 * nx, vr_aggr_kernel, n.M.f(), T, n.nb1, (int)pr->split_bin, (float)(1.0 + a0 / 3.0), (float)(1.0 + a0),
-              (float)(1.0 + a1 / 3.0), (float)(1.0 + a1)));
-  }
+  CHK(vr_aggr_dev(e, pr, n.M.f(), T, s));
   if (pr->enable_post_process) {
     CHK(n.fmin.ensure((size_t)T * 4));
     CHK(n.wgt.ensure((size_t)T * 4));
@@ -1179,7 +1225,126 @@ static int vr_separate_dev(asx_engine *e, const float *wave, int64_t n_samples, 
       CHK(vr_ew(e, s, nx, 8.0 * nx, vr_merge_kernel, n.M.f(), T, n.nb1, (const float *)n.wgt.f()));
     }
   }
-  if (primary) CHK(vr_synthesis_dev(e, 0, n.M.f(), T, primary, n_out, s));
-  if (secondary) CHK(vr_synthesis_dev(e, 1, n.M.f(), T, secondary, n_out, s));
+  if (primary) CHK(vr_synthesis_dev(e, 0, v, primary, n_out, s));
+  if (secondary) CHK(vr_synthesis_dev(e, 1, v, secondary, n_out, s));
+  return ASX_OK;
+}
+
+// ---- the same for a pool of songs: the patches of all of them share the net passes --------------------------------------
+// One pass kind (plain, or TTA with one more patch per song) over the flat patch list of the pool, in passes of
+// even_batches(total, max_batch) patches whichever song a patch belongs to.  The gather and the scatter take one launch per
+// VR_POOL_SEGMENTS songs a pass touches; the net runs once per pass on the same workspace of max_batch patches.
+static int vr_mask_pass_pool(asx_engine *e, const VrPlanCfg &pc, const VrPoolPlan &pp, const std::vector<VrSongView> &views, int tta,
+                             hipStream_t s) {
+  VrNet &n = *e->vr;
+  const asx_vr_config &c = n.cfg;
+  const std::vector<VrPoolPatch> &list = tta ? pp.tta : pp.plain;
+  const int total = (int)list.size();
+  if (total == 0) return ASX_OK;
+  const int W = c.window_size, roi = pp.roi;
+  const int pad_l = tta ? c.offset + roi / 2 : c.offset, shift = tta ? roi / 2 : 0;
+  const int per = vr_pool_per_pass(pc, total);
+  CHK(c.v51 ? vr51_ensure_workspace(e, per) : vr_ensure_workspace(e, per));
+  std::vector<VrPoolRun> runs;
+  // the segments of runs [r0, r1) with slots counted from the first of them; returns the slots they take
+  auto segments = [&](int r0, int r1, int B, VrPoolSegs &sg) {
+    sg.n = r1 - r0;
+    for (int r = r0; r < r1; ++r) {
+      const VrSongView &v = views[runs[r].song];
+      sg.v[r - r0] = VrPoolSeg{v.X, v.M, v.peak, v.T, runs[r].k0, runs[r].slot0 - runs[r0].slot0};
+    }
+    return (r1 < (int)runs.size() ? runs[r1].slot0 : B) - runs[r0].slot0;
+  };
+  for (int j0 = 0; j0 < total; j0 += per) {
+    const int B = std::min(per, total - j0);
+    vr_pool_runs(list, j0, B, runs);
+    const int nr = (int)runs.size();
+    for (int r0 = 0; r0 < nr; r0 += VR_POOL_SEGMENTS) {
+      VrPoolSegs sg{};
+      const int64_t nb = segments(r0, std::min(nr, r0 + VR_POOL_SEGMENTS), B, sg);
+      CHK(vr_ew(e, s, nb * n.max_bin * W, 16.0 * nb * n.max_bin * W, vr_patch_pool_kernel, sg, n.nb1, n.max_bin, W, roi, pad_l,
+                n.b.hc + (int64_t)runs[r0].slot0 * n.max_bin * W * n.ctot, n.ctot));
+    }
+    CHK(c.v51 ? vr51_net_dev(e, B, s) : vr_net_dev(e, B, s));
+    for (int r0 = 0; r0 < nr; r0 += VR_POOL_SEGMENTS) {
+      VrPoolSegs sg{};
+      const int64_t nb = segments(r0, std::min(nr, r0 + VR_POOL_SEGMENTS), B, sg);
+      CHK(vr_ew(e, s, nb * roi * n.nb1, 16.0 * nb * roi * n.nb1, vr_mask_pool_kernel,
+                (const float *)(n.b.mk + (int64_t)runs[r0].slot0 * n.max_bin * W * 4), sg, n.max_bin, W, c.offset, roi, shift, n.nb1, tta));
+    }
+  }
+  return ASX_OK;
+}
+
+// songs[i].wave_dev [2, n_i] -> songs[i].primary_dev / secondary_dev [2, n_out_i], each what vr_separate_dev writes for that
+// song alone.  Every song is checked and planned before anything is enqueued (vr_pool_plan.h).  Analysis, the peak, the mask
+// post-processing and the synthesis run per song on the single-song kernels, each on its song's view of the pooled state; the
+// mask passes are shared.  enable_post_process costs one device-to-host copy and one synchronisation for the whole pool.
+static int vr_separate_pool_dev(asx_engine *e, const asx_vr_song *songs, int n_songs, const asx_vr_params *pr, hipStream_t s) {
+  VrNet &n = *e->vr;
+  const VrPlanCfg &pc = n.plan_cfg;
+  std::vector<VrPoolSongIn> in((size_t)n_songs);
+  for (int i = 0; i < n_songs; ++i) in[i] = VrPoolSongIn{songs[i].wave_dev != nullptr, songs[i].n_samples};
+  VrPoolPlan pp;
+  std::string err;
+  REQUIRE(vr_pool_build(pc, in.data(), n_songs, pr->high_end_process != 0, pp, err), "%s", err.c_str());
+  if (n_songs == 0) return ASX_OK;
+  const int64_t nb1 = n.nb1, F = pp.frames;
+  CHK(n.X.ensure((size_t)2 * F * nb1 * 8));
+  CHK(n.M.ensure((size_t)2 * F * nb1 * 4));
+  CHK(n.peak.ensure((size_t)n_songs * 4));
+  if (pp.he_rows > 0) CHK(n.HE.ensure((size_t)2 * F * pp.he_rows * 8));
+  std::vector<VrSongView> views((size_t)n_songs);
+  for (int i = 0; i < n_songs; ++i) {
+    const VrPoolSong &ps = pp.song[i];
+    views[i] = VrSongView{reinterpret_cast<float2 *>(n.X.p) + 2 * ps.frame0 * nb1, n.M.f() + 2 * ps.frame0 * nb1,
+                          reinterpret_cast<float2 *>(n.HE.p) + 2 * ps.frame0 * pp.he_rows, reinterpret_cast<unsigned int *>(n.peak.p) + i, ps.T,
+                          pp.he_rows};
+  }
+  HIPCHK(hipMemsetAsync(n.peak.p, 0, (size_t)n_songs * 4, s));
+  for (int i = 0; i < n_songs; ++i) {
+    CHK(vr_analysis_dev(e, songs[i].wave_dev, songs[i].n_samples, views[i], s));
+    hipLaunchKernelGGL(vr_absmax_kernel, dim3(512), dim3(256), 0, s, (const float2 *)views[i].X, (int64_t)2 * views[i].T * nb1, views[i].peak);
+    HIPCHK(hipGetLastError());
+  }
+  CHK(vr_mask_pass_pool(e, pc, pp, views, 0, s));
+  if (pr->enable_tta) CHK(vr_mask_pass_pool(e, pc, pp, views, 1, s));
+  for (int i = 0; i < n_songs; ++i) CHK(vr_aggr_dev(e, pr, views[i].M, views[i].T, s));
+  if (pr->enable_post_process) {
+    CHK(n.fmin.ensure((size_t)F * 4));
+    CHK(n.wgt.ensure((size_t)F * 4));
+    for (int i = 0; i < n_songs; ++i) {
+      hipLaunchKernelGGL(vr_frame_min_kernel, dim3((views[i].T + 3) / 4), dim3(256), 0, s, (const float *)views[i].M, views[i].T, n.nb1,
+                         n.fmin.f() + pp.song[i].frame0);
+      HIPCHK(hipGetLastError());
+    }
+    std::vector<float> fmin_all((size_t)F), fmin, weight;
+    HIPCHK(hipMemcpyAsync(fmin_all.data(), n.fmin.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    n.wgt_host.assign((size_t)F, 0.f);
+    std::vector<char> merge((size_t)n_songs, 0);
+    bool any = false;
+    for (int i = 0; i < n_songs; ++i) {
+      const VrPoolSong &ps = pp.song[i];
+      fmin.assign(fmin_all.begin() + ps.frame0, fmin_all.begin() + ps.frame0 + ps.T);
+      if (vr_artifact_weight(fmin, pr->post_thres, weight)) {
+        std::copy(weight.begin(), weight.end(), n.wgt_host.begin() + ps.frame0);
+        merge[i] = 1;
+        any = true;
+      }
+    }
+    if (any) {
+      HIPCHK(hipMemcpyAsync(n.wgt.p, n.wgt_host.data(), (size_t)F * 4, hipMemcpyHostToDevice, s));
+      for (int i = 0; i < n_songs; ++i)
+        if (merge[i]) {
+          const int64_t nx = (int64_t)2 * views[i].T * nb1;
+          CHK(vr_ew(e, s, nx, 8.0 * nx, vr_merge_kernel, views[i].M, views[i].T, n.nb1, (const float *)(n.wgt.f() + pp.song[i].frame0)));
+        }
+    }
+  }
+  for (int i = 0; i < n_songs; ++i) {
+    if (songs[i].primary_dev) CHK(vr_synthesis_dev(e, 0, views[i], songs[i].primary_dev, pp.song[i].n_out, s));
+    if (songs[i].secondary_dev) CHK(vr_synthesis_dev(e, 1, views[i], songs[i].secondary_dev, pp.song[i].n_out, s));
+  }
   return ASX_OK;
 }

@@ -347,6 +347,76 @@ __global__ __launch_bounds__(256) void vr_mask_kernel(const float *__restrict__ 
   }
 }
 
+// ---- the same two for a pass that holds patches of several songs (asx_vr_separate_batch_dev) -----------------------------
+// A pass is a run of consecutive patches of consecutive songs, so a few segments describe it; they travel by value.  Segment i
+// fills slots [slot0, v[i + 1].slot0) of the launch (the last one up to the launch's slot count) with patches k0, k0 + 1, ... of
+// its song; a slot finds its segment with a scan of the launch arguments.  `hc` / `m` point at the launch's first slot.
+#define VR_POOL_SEGMENTS 16   // ASX_VR_POOL_SEGMENTS (asx.h)
+struct VrPoolSeg {
+  const float2 *X;                  // the song's spectrogram [2, T, nbins1]
+  float *M;                         // the song's mask [2, T, nbins1]
+  const unsigned int *peak_bits;    // the song's peak slot
+  int T, k0, slot0;
+};
+struct VrPoolSegs {
+  VrPoolSeg v[VR_POOL_SEGMENTS];
+  int n;
+};
+
+// vr_patch_kernel with the song (X, T, peak) and the patch index k resolved per slot b
+__global__ __launch_bounds__(256) void vr_patch_pool_kernel(VrPoolSegs segs, int nbins1, int max_bin, int W, int roi, int pad_l,
+                                                            float *__restrict__ out, int ld, int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // over slots * max_bin * W
+  if (idx >= total) return;
+  const int tl = (int)(idx % W);
+  int64_t p = idx / W;
+  const int f = (int)(p % max_bin);
+  const int b = (int)(p / max_bin);
+  int si = 0;
+  while (si + 1 < segs.n && b >= segs.v[si + 1].slot0) ++si;
+  const float2 *__restrict__ X = segs.v[si].X;
+  const int T = segs.v[si].T;
+  const int k = segs.v[si].k0 + (b - segs.v[si].slot0);
+  const int t = k * roi + tl - pad_l;
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (t >= 0 && t < T) {
+    const float peak = __uint_as_float(*segs.v[si].peak_bits);
+    const float2 l = X[(int64_t)t * nbins1 + f], r = X[((int64_t)T + t) * nbins1 + f];
+    o.x = hypotf(l.x, l.y) / peak;
+    o.y = hypotf(r.x, r.y) / peak;
+  }
+  *reinterpret_cast<float4 *>(out + idx * ld) = o;
+}
+
+// vr_mask_kernel with the song (M, T) and the patch index k resolved per slot b
+__global__ __launch_bounds__(256) void vr_mask_pool_kernel(const float *__restrict__ m, VrPoolSegs segs, int max_bin, int W, int offset,
+                                                           int roi, int shift, int nbins1, int tta, int64_t total) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // over slots * roi_w * nbins1 ; f fastest
+  if (idx >= total) return;
+  const int roi_w = W - 2 * offset;
+  const int f = (int)(idx % nbins1);
+  int64_t p = idx / nbins1;
+  const int tl = (int)(p % roi_w);
+  const int b = (int)(p / roi_w);
+  int si = 0;
+  while (si + 1 < segs.n && b >= segs.v[si + 1].slot0) ++si;
+  float *__restrict__ M = segs.v[si].M;
+  const int T = segs.v[si].T;
+  const int k = segs.v[si].k0 + (b - segs.v[si].slot0);
+  const int t = k * roi + tl - shift;
+  if (t < 0 || t >= T) return;
+  const int fs = f < max_bin ? f : max_bin - 1;
+  const float2 v = *reinterpret_cast<const float2 *>(m + (((int64_t)b * max_bin + fs) * W + tl + offset) * 4);
+  float *d0 = M + (int64_t)t * nbins1 + f, *d1 = M + ((int64_t)T + t) * nbins1 + f;
+  if (tta) {
+    *d0 = (*d0 + v.x) * 0.5f;
+    *d1 = (*d1 + v.y) * 0.5f;
+  } else {
+    *d0 = v.x;
+    *d1 = v.y;
+  }
+}
+
 // adjust_aggr (spec_utils.py:472-492): mask[ch, f < split] **= e_lo[ch], mask[ch, f >= split] **= e_hi[ch]
 __global__ __launch_bounds__(256) void vr_aggr_kernel(float *__restrict__ M, int T, int nbins1, int split, float lo0, float hi0,
                                                       float lo1, float hi1, int64_t total) {

@@ -275,7 +275,7 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_ensemble_dev", "asx_invert_stem", "asx_normalize", "asx_normalize_dev", "asx_residual_dev",
            "asx_profile_launches", "asx_debug_trace", "asx_resample_sinc", "asx_resample_sinc_dev", "asx_counter",
            "asx_set_stft_window", "asx_op_tdf_block", "asx_op_attention", "asx_op_mha", "asx_get_option",
-           "asx_demix_batch_dev", "asx_separate_batch_dev", "asx_ensemble_slot_dev"]
+           "asx_demix_batch_dev", "asx_separate_batch_dev", "asx_ensemble_slot_dev", "asx_vr_separate_batch_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -292,6 +292,13 @@ class _Song(C.Structure):          # struct asx_song
 
 class _ApplySong(C.Structure):     # struct asx_apply_song
     _fields_ = [("mix_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_samples", C.c_int64), ("offsets", C.POINTER(C.c_int64))]
+
+
+class _VrSong(C.Structure):        # struct asx_vr_song
+    _fields_ = [("wave_dev", C.c_void_p), ("n_samples", C.c_int64), ("primary_dev", C.c_void_p), ("secondary_dev", C.c_void_p)]
+
+
+VR_POOL_SEGMENTS = 16              # ASX_VR_POOL_SEGMENTS: songs one gather / scatter launch of a pooled VR pass serves
 
 
 class _SongStems(C.Structure):     # struct asx_song_stems
@@ -384,6 +391,7 @@ def load_library():
     lib.asx_vr_analysis.argtypes = [vp, _FP, i64, _FP]
     lib.asx_vr_separate.argtypes = [vp, _FP, i64, C.POINTER(_VrParams), _FP, _FP]
     lib.asx_vr_separate_dev.argtypes = [vp, vp, i64, C.POINTER(_VrParams), vp, vp, vp]
+    lib.asx_vr_separate_batch_dev.argtypes = [vp, C.POINTER(_VrSong), i32, C.POINTER(_VrParams), vp]
     lib.asx_debug_fetch.argtypes = [vp, C.c_char_p, _FP, i64]
     lib.asx_resample_sinc.argtypes = [vp, _FP, i32, i64, C.c_double, i32, _FP, i64]
     lib.asx_resample_sinc_dev.argtypes = [vp, vp, i32, i64, C.c_double, i32, vp, i64, vp]
@@ -789,6 +797,13 @@ class Engine:
         self._check(self._lib.asx_vr_analysis(self._h, _ptr(wave), wave.shape[1], _ptr(buf)))
         return np.ascontiguousarray(buf.view(np.complex64)[..., 0].transpose(0, 2, 1))
 
+    @staticmethod
+    def _vr_params(aggr_value, split_bin, is_non_accom, aggr_correction, enable_tta, enable_post_process, post_thres, high_end_process):
+        corr = aggr_correction or {}
+        return _VrParams(float(aggr_value), int(split_bin), int(bool(is_non_accom)), int(aggr_correction is not None),
+                         float(corr.get("left", 0.0)), float(corr.get("right", 0.0)), int(bool(enable_tta)),
+                         int(bool(enable_post_process)), float(post_thres), int(bool(high_end_process)))
+
     def vr_separate(self, wave: np.ndarray, aggr_value: float, split_bin: int, is_non_accom: bool = False, aggr_correction=None,
                     enable_tta: bool = False, enable_post_process: bool = False, post_thres: float = 0.2,
                     high_end_process: bool = False):
@@ -796,10 +811,7 @@ class Engine:
         if wave.ndim != 2 or wave.shape[0] != 2:
             raise ValueError(f"Expected a 2-channel audio signal, but got shape {wave.shape}")
         _, n_out = self.vr_plan(wave.shape[1])
-        corr = aggr_correction or {}
-        pr = _VrParams(float(aggr_value), int(split_bin), int(bool(is_non_accom)), int(aggr_correction is not None),
-                       float(corr.get("left", 0.0)), float(corr.get("right", 0.0)), int(bool(enable_tta)),
-                       int(bool(enable_post_process)), float(post_thres), int(bool(high_end_process)))
+        pr = self._vr_params(aggr_value, split_bin, is_non_accom, aggr_correction, enable_tta, enable_post_process, post_thres, high_end_process)
         p = np.empty((2, n_out), np.float32)
         q = np.empty((2, n_out), np.float32)
         self._check(self._lib.asx_vr_separate(self._h, _ptr(wave), wave.shape[1], C.byref(pr), _ptr(p), _ptr(q)))
@@ -808,12 +820,22 @@ class Engine:
     def vr_separate_dev(self, wave_ptr: int, n_samples: int, primary_ptr: int, secondary_ptr: int, aggr_value: float,
                         split_bin: int, is_non_accom: bool = False, enable_tta: bool = False, enable_post_process: bool = False,
                         post_thres: float = 0.2, stream: int = 0, aggr_correction=None, high_end_process: bool = False):
-        corr = aggr_correction or {}
-        pr = _VrParams(float(aggr_value), int(split_bin), int(bool(is_non_accom)), int(aggr_correction is not None),
-                       float(corr.get("left", 0.0)), float(corr.get("right", 0.0)), int(bool(enable_tta)),
-                       int(bool(enable_post_process)), float(post_thres), int(bool(high_end_process)))
+        pr = self._vr_params(aggr_value, split_bin, is_non_accom, aggr_correction, enable_tta, enable_post_process, post_thres, high_end_process)
         self._check(self._lib.asx_vr_separate_dev(self._h, wave_ptr, n_samples, C.byref(pr), primary_ptr or None,
                                                   secondary_ptr or None, stream or None))
+
+    def vr_separate_batch_dev(self, songs, aggr_value: float, split_bin: int, is_non_accom: bool = False, enable_tta: bool = False,
+                              enable_post_process: bool = False, post_thres: float = 0.2, stream: int = 0, aggr_correction=None,
+                              high_end_process: bool = False):
+        """``songs``: a list of ``(wave_ptr, n_samples, primary_ptr or 0, secondary_ptr or 0)`` -- wave [2, n] and the stems
+        [2, n_out] (``vr_plan``) in HBM; a 0 output pointer leaves that stem out.  The patches of all songs share the net passes;
+        every stem equals what ``vr_separate_dev`` writes for that song alone (asx_vr_separate_batch_dev)."""
+        songs = list(songs)
+        arr = (_VrSong * max(1, len(songs)))()
+        for i, (wave_ptr, n, primary_ptr, secondary_ptr) in enumerate(songs):
+            arr[i] = _VrSong(wave_ptr or None, int(n), primary_ptr or None, secondary_ptr or None)
+        pr = self._vr_params(aggr_value, split_bin, is_non_accom, aggr_correction, enable_tta, enable_post_process, post_thres, high_end_process)
+        self._check(self._lib.asx_vr_separate_batch_dev(self._h, arr, len(songs), C.byref(pr), stream or None))
 
     # -- chunk-range halves of the sibling loops (multi-GPU sharding, sharding.py) ----------------------------
     def mdxc_chunks_dev(self, mix_ptr, n, overlap, k0, k1, out_ptr, stream=0):

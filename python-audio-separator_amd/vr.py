@@ -158,6 +158,12 @@ class VRDemixer:
             pass
         return want
 
+    def _options(self) -> dict:
+        """The keywords of ``Engine.vr_separate*`` this demixer's configuration amounts to."""
+        return dict(is_non_accom=self.primary_stem_name in NON_ACCOM_STEMS, aggr_correction=self.aggressiveness["aggr_correction"],
+                    enable_tta=self.enable_tta, enable_post_process=self.enable_post_process, post_thres=self.post_process_threshold,
+                    high_end_process=self.high_end_process)
+
     def separate_stems_dev(self, wave_d):
         """The same with the wave [2, n] and both stems in HBM: returns one CUDA tensor [2 (primary, secondary), 2, n_out]
         (planar stems; ``stems[i].T`` is what the reference hands to write_audio)."""
@@ -166,21 +172,51 @@ class VRDemixer:
         _, n_out = self.engine.vr_plan(n)
         out = torch.empty((2, 2, n_out), dtype=torch.float32, device=wave_d.device)
         self.engine.vr_separate_dev(wave_d.data_ptr(), n, out[0].data_ptr(), out[1].data_ptr(), self.aggressiveness["value"],
-                                    self.aggressiveness["split_bin"], is_non_accom=self.primary_stem_name in NON_ACCOM_STEMS,
-                                    enable_tta=self.enable_tta, enable_post_process=self.enable_post_process,
-                                    post_thres=self.post_process_threshold,
-                                    stream=torch.cuda.current_stream(wave_d.device).cuda_stream,
-                                    aggr_correction=self.aggressiveness["aggr_correction"], high_end_process=self.high_end_process)
+                                    self.aggressiveness["split_bin"], stream=torch.cuda.current_stream(wave_d.device).cuda_stream,
+                                    **self._options())
         return out
+
+    def separate_stems_many_dev(self, waves_d, want_primary: bool = True, want_secondary: bool = True):
+        """``separate_stems_dev`` for a list of waves [2, n_i] in HBM with ONE pooled engine call (asx_vr_separate_batch_dev): the
+        patches of all songs share the net passes.  Returns a list of CUDA tensors [2, 2, n_out_i], each equal to what
+        ``separate_stems_dev`` returns for that wave; a stem that is not wanted is not synthesised (its half is left unwritten)."""
+        import torch
+        waves_d = list(waves_d)
+        if not waves_d:
+            return []
+        outs, songs = [], []
+        for w in waves_d:
+            n = w.shape[1]
+            _, n_out = self.engine.vr_plan(n)
+            out = torch.empty((2, 2, n_out), dtype=torch.float32, device=w.device)
+            outs.append(out)
+            songs.append((w.data_ptr(), n, out[0].data_ptr() if want_primary else 0, out[1].data_ptr() if want_secondary else 0))
+        self.engine.vr_separate_batch_dev(songs, self.aggressiveness["value"], self.aggressiveness["split_bin"],
+                                          stream=torch.cuda.current_stream(waves_d[0].device).cuda_stream, **self._options())
+        return outs
+
+    def separate_stems_many(self, waves, want_primary: bool = True, want_secondary: bool = True):
+        """``separate_stems`` for a list of host waves [2, n_i] through ``separate_stems_many_dev``: per song what
+        ``separate_stems`` returns."""
+        import torch
+        host = []
+        for w in waves:
+            w = np.ascontiguousarray(w, np.float32)
+            if w.ndim != 2 or w.shape[0] != 2:
+                raise ValueError(f"Expected a 2-channel audio signal, but got shape {w.shape}")
+            host.append(w)
+        dev = torch.device("cuda", self.engine.device)
+        outs = self.separate_stems_many_dev([torch.from_numpy(w).to(dev) for w in host], want_primary, want_secondary)
+        res = []
+        for o in outs:
+            o = o.cpu().numpy()
+            res.append((o[0].T if want_primary else None, o[1].T if want_secondary else None))
+        return res
 
     def separate_stems(self, wave: np.ndarray, want_primary: bool = True, want_secondary: bool = True):
         """(primary_source, secondary_source) as [n', 2] arrays (vr_separator.py:211-236, before final_process), at the
         MODEL's sample rate ``self.model_samplerate``: for parameter sets with sr != 44100 the reference then calls
         librosa.resample(..., target_sr=44100) (:218-220, :238-240), which the file-level VRSeparator does on the host.
         A stem that is not wanted (output_single_stem) comes back as None."""
-        p, s = self.engine.vr_separate(wave, self.aggressiveness["value"], self.aggressiveness["split_bin"],
-                                       is_non_accom=self.primary_stem_name in NON_ACCOM_STEMS,
-                                       aggr_correction=self.aggressiveness["aggr_correction"], enable_tta=self.enable_tta,
-                                       enable_post_process=self.enable_post_process, post_thres=self.post_process_threshold,
-                                       high_end_process=self.high_end_process)
+        p, s = self.engine.vr_separate(wave, self.aggressiveness["value"], self.aggressiveness["split_bin"], **self._options())
         return (p.T if want_primary else None), (s.T if want_secondary else None)
