@@ -10,8 +10,10 @@
 //   y[b, co, t, f] = act(bias[co] + prev[b, co, t, f] + sum_{ci, ky, kx} w[co, ci, ky, kx] x[b, ci, t + ky - 1, f + kx - 1])        [B, C, T, F] fp32, F fastest
 //
 // GEMM view.  M = output pixels (16 consecutive f per MFMA tile), N = output channels (3 tiles of 16), K = (ky, kx, ci): a kernel row is
-// 3 x 48 = 144 = 18 groups of eight channels = 4.5 stages of `v_mfma_f32_16x16x32_f16`, padded to 5 (a stage never straddles input rows: rows of
-// different blocks carry different exponents) -- 15 stages per tile.  A lane's eight K values are eight consecutive input channels of ONE
+// 3 x 48 = 144 = 18 groups of eight channels = 4.5 stages of `v_mfma_f32_16x16x32_f16`.  A stage never mixes rows of different four-row blocks
+// (they carry different exponents), but the half stages of two kernel rows of ONE block share a stage, half the lanes each: 14 stages per
+// tile (Conv3hCfg::PLAN: 12 full, one merged, one half stage padded with a zero weight fragment), 252 MFMAs and 140 fragment reads per wave.
+// A lane's eight K values are eight consecutive input channels of ONE
 // tap at ONE pixel, so the x operand is kept channels-LAST in LDS ([ring row][34 pixels][48 halves], 96 bytes per pixel and part).
 //
 // One persistent 512-thread workgroup per CU (grid 256), two kinds of waves, ONE `s_barrier` per 4 x 32 output tile:
@@ -22,8 +24,9 @@
 //     12-row ring (`ds_write_b128`, 2-way at worst);
 //   * waves 0-3 CONSUME block s: wave r owns output row r of the tile (two 16-pixel MFMA tiles x three 16-channel tiles = six accumulators);
 //     per stage it reads six weight fragments and four x fragments (`ds_read_b128`, a stage ahead) and issues 18 MFMAs (w_l x_h, w_h x_l,
-//     w_h x_h); where the exponent moved between the tile's two blocks, the accumulators are rescaled at the kernel-row boundary.  The finished
-//     tile's epilogue and its six whole-line nontemporal stores run among the MFMAs of the next tile.
+//     w_h x_h); where the exponent moved between the tile's two blocks, the accumulators are rescaled between the last stage of the previous
+//     block's rows and the first of this block's.  The finished tile's epilogue and its six whole-line nontemporal stores run among the MFMAs
+//     of the next tile.
 //   The two-part weight image (432 x 48 x 2 x 2 B = 81 KB, fragment order, one exponent per OUTPUT channel) is copied into LDS once per
 //   workgroup and stays for the whole launch.  LDS: 82944 (W) + 78336 (ring) + tables = 161.3 KB of the 160 KiB.
 // Bank conflicts: a 16-pixel fragment read at the 96-byte pixel stride puts the sixteen lanes of every `ds_read_b128` service group on
@@ -63,14 +66,47 @@ struct Conv3hCfg {
   static constexpr int RING = 12;                                 // ring rows: three blocks of four
   static constexpr int PART = RING * ROWB;                        // 39168 bytes per part
   static constexpr int KGY = 3 * CG8;                             // 18 k groups per kernel row
-  static constexpr int SPK = (KGY + 3) / 4;                       // 5 stages per kernel row, the last one half empty
-  static constexpr int NST = 3 * SPK;                             // 15 stages
+  static constexpr int SPK = (KGY + 3) / 4;                       // 5 stage groups per kernel row in the weight image, the last one (k groups 16, 17) half a fragment
+  static constexpr int NST = (3 * KGY + 3) / 4;                   // 14 stages per tile: 54 k groups = 13.5 stages (stage plan below)
   static constexpr int WKY = (KGY / 4) * 3 * 2 * 1024 + 3 * 2 * 512;   // 27648 bytes of weight fragments per kernel row
   static constexpr int WBYTES = 3 * WKY;                          // 82944
   static constexpr int W_OFF = 0, X_OFF = WBYTES, TAB_OFF = X_OFF + 2 * PART;
   static constexpr int LDS_BYTES = TAB_OFF + 64;                  // maxima [2][4] floats, exponents [3] ints, 16 bytes of zeros at + 48
   static constexpr size_t IMG_U32 = WBYTES / 4 + 48;              // image size in 32-bit words
   static constexpr int EUP = 8;                                   // the running exponent of a walk follows a quieter block only when it is more than this many bits quieter
+
+  // Stage plan of a consumer wave's tile.  A kernel row is four FULL stages (stage group sg: k groups 4 sg .. 4 sg + 3) and half a stage (k groups
+  // 16, 17: stage group 4, a half fragment in the weight image).  Two half stages whose input rows lie in the SAME four-row block (one exponent)
+  // share one MERGED stage: lanes g < 2 carry row ky's k groups 16, 17 (x fragment and weight half fragment), lanes g >= 2 row kyb's -- the half
+  // fragment's lane order puts k group 16 + (g & 1) at (lane & 31) * 16, so lanes 32..63 read kyb's half fragment where lanes 0..31 read ky's.
+  // The third row keeps a PADDED half stage (lanes g >= 2: a zero weight fragment).  Wave r reads ring row u = r + ky for kernel row ky; u < 2 is
+  // the previous block, u >= 2 the current one: wave 0 (old, old, cur) merges rows 0 and 1, wave 1 (old, cur, cur) rows 1 and 2, waves 2 and 3 (all
+  // cur) run wave 0's program.  `rto` >= 0: behind this stage the accumulators go from row rfrom's exponent to row rto's (the only block change
+  // of the wave that runs the program) -- the scale moves old -> cur as it did with five stages per kernel row.
+  enum { FULL = 0, MERGED = 1, PADDED = 2 };
+  struct Stage {
+    int kind, ky, kyb, sg;   // kyb: the second row of a merged stage (= ky otherwise)
+    int rfrom, rto;
+  };
+  static constexpr int NPROG = 2;
+  static constexpr int PROG_OF_WAVE[4] = {0, 1, 0, 0};
+  static constexpr Stage PLAN[NPROG][NST] = {
+      {{FULL, 0, 0, 0, -1, -1}, {FULL, 0, 0, 1, -1, -1}, {FULL, 0, 0, 2, -1, -1}, {FULL, 0, 0, 3, -1, -1},
+       {FULL, 1, 1, 0, -1, -1}, {FULL, 1, 1, 1, -1, -1}, {FULL, 1, 1, 2, -1, -1}, {FULL, 1, 1, 3, -1, -1},
+       {MERGED, 0, 1, 4, 1, 2},
+       {FULL, 2, 2, 0, -1, -1}, {FULL, 2, 2, 1, -1, -1}, {FULL, 2, 2, 2, -1, -1}, {FULL, 2, 2, 3, -1, -1},
+       {PADDED, 2, 2, 4, -1, -1}},
+      {{FULL, 0, 0, 0, -1, -1}, {FULL, 0, 0, 1, -1, -1}, {FULL, 0, 0, 2, -1, -1}, {FULL, 0, 0, 3, -1, -1},
+       {PADDED, 0, 0, 4, 0, 1},
+       {FULL, 1, 1, 0, -1, -1}, {FULL, 1, 1, 1, -1, -1}, {FULL, 1, 1, 2, -1, -1}, {FULL, 1, 1, 3, -1, -1},
+       {FULL, 2, 2, 0, -1, -1}, {FULL, 2, 2, 1, -1, -1}, {FULL, 2, 2, 2, -1, -1}, {FULL, 2, 2, 3, -1, -1},
+       {MERGED, 1, 2, 4, -1, -1}}};
+  // the stage of kind `kind` of program p (each program has one merged and one padded stage)
+  static constexpr Stage plan_find(int p, int kind) {
+    for (int s = 0; s < NST; ++s)
+      if (PLAN[p][s].kind == kind) return PLAN[p][s];
+    return Stage{-1, -1, -1, -1, -1, -1};
+  }
 };
 
 // host: w [48, 48, 3, 3] fp32 -> the LDS image.  Stage (ky, sg) = k groups 4 sg .. 4 sg + 3 of kernel row ky, k group kk = (kx = kk / 6, eight
@@ -458,26 +494,32 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
   } else {
     // =================================================================== consumer ===================================================
+    // One body per stage program (Conv3hCfg::PLAN): wave 1 runs program 1, waves 0, 2, 3 program 0 -- one wave-uniform branch per launch
+    auto consume = [&](auto progc) {
+    constexpr int PROG = decltype(progc)::value;
+    constexpr CFG::Stage MST = CFG::plan_find(PROG, CFG::MERGED), PST = CFG::plan_find(PROG, CFG::PADDED);
     const int li = lane & 15, g = lane >> 4;
     int vl[CFG::SPK];                                  // lane part of the x fragment address per stage of a kernel row: (kx + pixel) * 96 + channel group * 16
 #pragma unroll
     for (int sg = 0; sg < CFG::SPK; ++sg) {
       int kk = 4 * sg + g;
-      kk = kk < CFG::KGY ? kk : CFG::KGY - 2 + (g & 1);   // half stage: lanes past the last k group re-read groups 16 / 17 (an odd slot distance: no bank conflict; their weight fragment is zero)
+      kk = kk < CFG::KGY ? kk : CFG::KGY - 2 + (g & 1);   // half stages: lanes g >= 2 re-read groups 16 / 17 (an odd slot distance: no bank conflict) -- of the second row (merged) or against a zero weight fragment (padded)
       vl[sg] = (kk / CFG::CG8 + li) * CFG::PSTR + (kk % CFG::CG8) * 16 + CFG::X_OFF;
     }
     const char *wl = lds + CFG::W_OFF + lane * 16;
-    // half stage: lanes without a k group behind them (k groups 18, 19) read a 16-byte slot of zeros as their WEIGHT fragment (their x
+    // padded half stage: lanes without a k group behind them (k groups 18, 19) read a 16-byte slot of zeros as their WEIGHT fragment (their x
     // fragment is the real data of k group 17 -- finite whenever the tile's legitimate operands are)
+    // merged stage: lanes g < 2 read the half fragment of row MST.ky, lanes g >= 2 that of row MST.kyb (k group 16 + (g & 1) either way)
     const bool pad_lane = g >= (CFG::KGY % 4);
-    int wh[3][3][2];
+    int whp[3][2], whm[3][2];
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
+    for (int c = 0; c < 3; ++c)
 #pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-          wh[ky][c][p] = pad_lane ? CFG::TAB_OFF + 48 : CFG::W_OFF + ky * CFG::WKY + (CFG::SPK - 1) * 6144 + (c * 2 + p) * 512 + (lane & 31) * 16;
+      for (int p = 0; p < 2; ++p) {
+        const int hf = CFG::W_OFF + (CFG::SPK - 1) * 6144 + (c * 2 + p) * 512 + (lane & 31) * 16;
+        whp[c][p] = pad_lane ? CFG::TAB_OFF + 48 : hf + PST.ky * CFG::WKY;
+        whm[c][p] = hf + (pad_lane ? MST.kyb : MST.ky) * CFG::WKY;
+      }
     if (tid < 4) reinterpret_cast<unsigned *>(lds + CFG::TAB_OFF + 48)[tid] = 0u;   // (published by barrier P0)
     const int *wexp = reinterpret_cast<const int *>(a.wimg) + CFG::WBYTES / 4;
     int ew[3];
@@ -511,10 +553,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
     };
     // The finished tile's accumulators wait in `pacc`; its epilogue (scale, bias, activation, lane swap: ~50 VALU instructions per channel
-    // tile) runs among the MFMAs of the NEXT tile's stages 1 / 3 / 5 and its six stores behind stages 7..12 -- off the wave's critical path.
+    // tile) runs among the MFMAs of the NEXT tile's stages 1..6 and its six stores behind stages 8..13 (the last one) -- off the wave's critical path.
     f32x4 pacc[2][3];
     int pend_e = 0;
-    // accumulate mode (a.prev): the six lines of the other input slice's partial sums, fetched in the stores' own lane arrangement behind stage 6
+    // accumulate mode (a.prev): the six lines of the other input slice's partial sums, fetched in the stores' own lane arrangement behind stage 7
     // of the tile they belong to (the previous tile's epilogue has used the registers by then) and added in front of the activation
     f32x4 pprev[6];
 #pragma unroll
@@ -585,6 +627,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           rowoff[ky] = (u < 2 ? sp * 4 + 2 + u : s3 * 4 + u - 2) * CFG::ROWB;
           eky[ky] = u < 2 ? e_old : e_cur;
         }
+        const int xm = (pad_lane ? rowoff[MST.kyb] : rowoff[MST.ky]) + vl[CFG::SPK - 1];   // merged stage: the lane's row (both rows in one block slot)
         f32x4 acc[2][3];
 #pragma unroll
         for (int p = 0; p < 2; ++p)
@@ -594,16 +637,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         f16x8 wf[PF + 1][3][2], xf[PF + 1][2][2];
         auto load_stage = [&](auto bufc, auto sc) {
           constexpr int BUF = decltype(bufc)::value, S = decltype(sc)::value;
-          constexpr int KY = S / CFG::SPK, SG = S % CFG::SPK;
-          constexpr bool half = SG == CFG::SPK - 1;
+          constexpr CFG::Stage ST = CFG::PLAN[PROG][S];
+          constexpr int KY = ST.ky, SG = ST.sg;
 #pragma unroll
           for (int c = 0; c < 3; ++c)
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-              if constexpr (half) wf[BUF][c][p] = *reinterpret_cast<const f16x8 *>(lds + wh[KY][c][p]);
+              if constexpr (ST.kind == CFG::MERGED) wf[BUF][c][p] = *reinterpret_cast<const f16x8 *>(lds + whm[c][p]);
+              else if constexpr (ST.kind == CFG::PADDED) wf[BUF][c][p] = *reinterpret_cast<const f16x8 *>(lds + whp[c][p]);
               else wf[BUF][c][p] = *reinterpret_cast<const f16x8 *>(wl + KY * CFG::WKY + SG * 6144 + (c * 2 + p) * 1024);
             }
-          const char *xs = lds + (rowoff[KY] + vl[SG]);
+          const char *xs = lds + (ST.kind == CFG::MERGED ? xm : rowoff[KY] + vl[SG]);
 #pragma unroll
           for (int qq = 0; qq < 2; ++qq)
 #pragma unroll
@@ -660,11 +704,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if constexpr (S == 13) pend_rs = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, 0, 0x00020000);
             __builtin_amdgcn_sched_barrier(0);
           }
-          if constexpr ((ABL & 256) == 0 && S + 1 < CFG::NST && (S + 1) % CFG::SPK == 0) {
-            // next kernel row: its input row may belong to the other block -- bring the accumulators to that block's scale (exact;
+          if constexpr ((ABL & 256) == 0 && CFG::PLAN[PROG][S].rto >= 0) {
+            // the stages that follow read rows of the other block -- bring the accumulators to that block's scale (exact;
             // rises are bounded by EUP, a fall flushes what is negligible against what follows)
-            constexpr int KY = S / CFG::SPK;
-            const int d = eky[KY + 1] - eky[KY];
+            const int d = eky[CFG::PLAN[PROG][S].rto] - eky[CFG::PLAN[PROG][S].rfrom];
             if (d != 0) {
 #pragma unroll
               for (int qq = 0; qq < 2; ++qq)
@@ -709,6 +752,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       s3 = s3 == 2 ? 0 : s3 + 1;
     }
     flush();
+    };
+    static_assert(CFG::NPROG == 2 && CFG::PROG_OF_WAVE[0] == 0 && CFG::PROG_OF_WAVE[1] == 1 && CFG::PROG_OF_WAVE[2] == 0 && CFG::PROG_OF_WAVE[3] == 0, "the branch below is the table");
+    if (wave == 1) consume(IntC<1>{});
+    else consume(IntC<0>{});
   }
 }
 
