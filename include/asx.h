@@ -304,6 +304,24 @@ int asx_rof_chunks_dev(asx_engine *e, const float *mix_dev, int64_t n_samples, i
                        float *chunk_out_dev, void *stream);
 int asx_rof_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t n_samples, int64_t step, float *out_dev, void *stream);
 
+/* ---- MDXC: a batch of songs in one call (the sibling of asx_demix_batch_dev for both MDXC loops) ----
+ * The chunks of all songs form one list, in song order, that runs through the STFT / net / iSTFT launches in passes of up to
+ * max_batch chunks (8 when max_batch is 0, as the single-song calls), whichever song a chunk belongs to: a Roformer pass over a
+ * folder of short clips is as full as one over a long song.  One segmented fold then writes every song's out; each equals what
+ * asx_mdxc_demix_dev / asx_rof_demix_dev writes for that song alone, bit for bit.  `songs` is a HOST array, read during the call;
+ * the mixes may have different lengths.  The chunk tables are built on the device from launch arguments: the call only enqueues
+ * work on `stream`.  Every argument is checked on the host first and nothing is enqueued when any song is invalid (null pointer,
+ * n_samples < 1, on the Roformer branch n_samples < chunk_size -- the message names the song's index); n_songs == 0 is ASX_OK.
+ * The net's chunk buffer grows to the pool's total chunk count (S * 2 * chunk_size floats per chunk).
+ * (Added within ABI 7: new functions and structs only.) */
+typedef struct asx_mdxc_song {
+  const float *mix_dev;   /* [2, n_samples] */
+  float *out_dev;         /* [S, 2, n_samples]  (Roformer: [n_out, 2, n_samples]) */
+  int64_t n_samples;
+} asx_mdxc_song;
+int asx_mdxc_demix_batch_dev(asx_engine *e, const asx_mdxc_song *songs, int32_t n_songs, int32_t overlap, void *stream);
+int asx_rof_demix_batch_dev(asx_engine *e, const asx_mdxc_song *songs, int32_t n_songs, int64_t step, void *stream);
+
 /* ---- Demucs v4 / HTDemucs -----------------------------------------------------
  * Replaces HTDemucs(**kwargs) + load_state_dict (uvr_lib_v5/demucs/htdemucs.py:32-382, demucs_separator.py:121-134),
  * HTDemucs.forward (htdemucs.py:483-620), apply_model (uvr_lib_v5/demucs/apply.py:124-260) and
@@ -600,6 +618,8 @@ int asx_ensemble_slot_dev(asx_engine *e, const float *stem_dev, int64_t n_sample
  * "hd_rounds" (ABI 7: rounds of chunk groups the Demucs v3 forward has run -- the groups of a round share the BLSTM launches),
  * "vr_net_passes" (ABI 7, additive: passes of the VR net, CascadedASPPNet or CascadedNet, on a batch of patches -- asx_vr_separate_batch_dev runs
  * fewer of them than a loop of asx_vr_separate_dev over the same songs),
+ * "v3_net_passes" / "rof_net_passes" (ABI 7, additive: passes of the TFC-TDF v3 net / of the Roformer net on a batch of chunks, single-song calls
+ * included -- asx_mdxc_demix_batch_dev / asx_rof_demix_batch_dev run fewer of them than a loop of the single-song call over the same songs),
  * "tdf3_pair_image_launches" (ABI 7: the tdf3_kernel launches that read their x operand as a pair image -- option "gemm_pair_images", experimental builds).
  * ASX_ERR_INVALID for an unknown name. */
 int asx_counter(const asx_engine *e, const char *name, int64_t *out);

@@ -4,6 +4,8 @@ TFC-TDF v3 (MDX23C) checkpoints and BS / Mel-Band Roformer checkpoints; same con
 ``demix`` contract, stem dictionary, file naming and the "shorter than 10 s -> override_model_segment_size" rule
 (:131-138).  ``torch.load`` + ``load_state_dict`` (:76-116) become ``asx_v3_*`` / ``asx_rof_*``; ``spec_utils.normalize`` of
 the mix and of every stem (:147, :170-190) is ``asx_normalize``; the chunk loops are ``asx_mdxc_demix`` / ``asx_rof_demix``.
+``separate_many(paths)`` (no counterpart in the reference) writes the files of ``separate`` per path with the chunks of all files
+pooled per net pass (``asx_mdxc_demix_batch_dev`` / ``asx_rof_demix_batch_dev``).
 """
 from __future__ import annotations
 
@@ -19,6 +21,11 @@ class MDXCSeparator(CommonSeparator):
         super().__init__(config=common_config)
         self._read_options(arch_config, (("segment_size", 256), ("override_model_segment_size", False), ("overlap", 8), ("batch_size", 1),
                                          ("pitch_shift", 0), ("process_all_stems", True)))
+        # engine knob, not a reference option: most chunks one pooled call of separate_many takes (0 = what fits in HBM)
+        self._pool_chunks = int(arch_config.get("asx_pool_chunks", 0))
+        # ``separate_many(paths, custom_output_names=None)``: the shared batch shell, published on every instance rather than as a class
+        # attribute (tests/test_host_vr_batch.py pins that the class itself carries no ``separate_many``)
+        self.separate_many = self._separate_many
         self.logger.debug(f"MDXC arch params: batch_size={self.batch_size}, segment_size={self.segment_size}, overlap={self.overlap}, "
                           f"override_model_segment_size={self.override_model_segment_size}, pitch_shift={self.pitch_shift}")
         self.is_roformer = getattr(self, "is_roformer_model", False)
@@ -33,8 +40,10 @@ class MDXCSeparator(CommonSeparator):
         self.logger.info(f"MDXC model ready ({'Roformer' if self.is_roformer else 'TFC-TDF v3'} on the HIP engine)")
 
     # ---- weights ---------------------------------------------------------------
-    def _demixer(self) -> MDXCDemixer:
-        key = bool(self.override_model_segment_size)
+    def _demixer(self, key=None) -> MDXCDemixer:
+        """The demixer (and engine) of a chunk geometry: ``key`` True = the configured segment size, False = the model's own;
+        None = the one ``override_model_segment_size`` selects now."""
+        key = bool(self.override_model_segment_size if key is None else key)
         dm = self._demixers.get(key)
         if dm is None:
             common = dict(self._common)
@@ -168,3 +177,121 @@ class MDXCSeparator(CommonSeparator):
         kind, entries = self._stem_plan(list(source) if isinstance(source, dict) else [None])
         # (the one array of a "single" plan goes to the writer as it is; every other stem is normalised when it is fetched)
         return self._emit_plan(kind, entries, lambda key: source.T if key is None else norm(source[key]).T, custom_output_names)
+
+    # ---- a batch of files: the hooks of CommonSeparator._separate_many ------------------------------------------------------
+    # A loop of ``separate`` switches ``override_model_segment_size`` on at the first file under 10 s and leaves it on, so the files
+    # before that one run the model's chunk geometry and that file and all later ones the configured one: at most two pools, each on
+    # its own engine.  ``_check_loaded`` applies the rule in file order and records every good file's geometry.
+    def _device_decode(self, path):
+        return None if self.pitch_shift != 0 else self._device_mix(path)      # the pitch round trip runs on host arrays
+
+    def _prepare_model(self):
+        self._pool_keys = []
+        if self.engine is None:
+            self._demixer()
+
+    def _check_loaded(self, dev_mix, host_mix):
+        """The short-file rule, then what ``demix`` would refuse: such a file fails alone and never reaches the pooled call, which
+        rejects a whole pool for one Roformer mix shorter than a chunk."""
+        mix = dev_mix if dev_mix is not None else host_mix
+        n = mix.shape[1]
+        self._short_file_rule(n / self.sample_rate)
+        key = bool(self.override_model_segment_size)
+        if mix.shape[0] != 2:
+            raise ValueError(f"Expected a 2-channel audio signal, but got {mix.shape[0]} channels")
+        if self.is_roformer and self.pitch_shift == 0 and n < self._demixer(key).chunk_size:
+            raise ValueError(f"mix ({n} samples) shorter than one chunk ({self._demixer(key).chunk_size}): not supported on the Roformer path")
+        self._pool_keys.append(key)
+
+    def _sub_pools(self, dm, lengths):
+        """Consecutive runs of files, in order, whose chunks fit one pooled call: the pooled chunk buffer ([chunks, S, 2, chunk]
+        floats) stays within 60 % of the HBM that is free now, or within ``asx_pool_chunks`` chunks when that is set.  A file that
+        alone exceeds the budget is a run of its own (the single-song call would need the same buffer)."""
+        if dm.is_roformer:
+            step, rows = dm.roformer_step(), int(dm.rof.num_stems)
+            counts = [-(-n // step) for n in lengths]
+        else:
+            rows = int(dm.v3.num_targets)
+            hop = dm.chunk_size // int(dm.overlap)
+            counts = [(n + hop - (n - dm.chunk_size) % hop + dm.chunk_size - hop) // hop for n in lengths]    # Tensor.unfold's count
+        budget = self._pool_chunks
+        if budget <= 0:
+            budget = 1 << 30
+            try:
+                import torch
+                free, _total = torch.cuda.mem_get_info(dm.engine.device)
+                budget = max(1, int(0.6 * free / (rows * 2 * dm.chunk_size * 4)))
+            except Exception:      # no device query: one pool, the engine reports an allocation failure itself
+                pass
+        runs, used = [[]], 0
+        for i, c in enumerate(counts):
+            if runs[-1] and used + c > budget:
+                runs.append([])
+                used = 0
+            runs[-1].append(i)
+            used += c
+        return runs
+
+    def _pooled_stems(self, mixes):
+        """Per file what ``_emit_file`` takes.  Files on the device path: normalise each mix in place, ONE pooled demix per geometry
+        (``MDXCDemixer.demix_many_dev``; split into consecutive sub-pools only for memory), normalise every stem in place -- exactly
+        where ``_device_stems`` does.  Without the device file path (``ASX_FILE_FASTPATH=0``) the same pools run through
+        ``demix_many`` on host arrays.  With ``pitch_shift`` it is the loop of ``demix`` per file (mdxc.py ``demix_many``)."""
+        keys, self._pool_keys = self._pool_keys, []
+        thr, amp = self.normalization_threshold, self.amplification_threshold
+        out = [None] * len(mixes)
+        host_only = self.pitch_shift != 0 or not self._fast_file_path_enabled()
+        for key in (False, True):
+            idx = [i for i, k in enumerate(keys) if k == key]
+            if not idx:
+                continue
+            dm = self._demixer(key)
+            eng = dm.engine
+            if self.pitch_shift != 0:
+                for i in idx:
+                    try:
+                        out[i] = ("host", eng, dm.demix(eng.normalize(mixes[i][1], thr, amp)))
+                    except Exception as e:                   # this file only: raised again where its files would be written
+                        out[i] = e
+                continue
+            if host_only:
+                host = [eng.normalize(mixes[i][1] if mixes[i][1] is not None else mixes[i][0].cpu().numpy(), thr, amp) for i in idx]
+                for run in self._sub_pools(dm, [m.shape[1] for m in host]):
+                    for j, source in zip(run, dm.demix_many([host[j] for j in run])):
+                        out[idx[j]] = ("host", eng, source)
+                continue
+            t0 = self._now()
+            st = self._stream()
+            dev = self._device_mixes([mixes[i] for i in idx])
+            for m in dev:
+                eng.normalize_dev(m.data_ptr(), 2 * m.shape[1], thr, amp, stream=st)
+            for run in self._sub_pools(dm, [m.shape[1] for m in dev]):
+                for j, (names, stems_d) in zip(run, dm.demix_many_dev([dev[j] for j in run])):
+                    kind, entries = self._stem_plan(names)
+                    entries = [(name, names.index(k)) for name, k in entries]
+                    if kind != "single":
+                        for r in sorted({r for _, r in entries}):
+                            eng.normalize_dev(stems_d[r].data_ptr(), 2 * stems_d.shape[2], thr, amp, stream=st)
+                    out[idx[j]] = (stems_d, kind, entries)
+            self._tick("demix", t0)
+        return out
+
+    def _emit_file(self, stems, on_device, custom_output_names):
+        """One entry of ``_pooled_stems`` -> the file's outputs, as ``separate`` ends.  Device stems of a file decoded on the device
+        keep their device tensors for the int16 pass; a host-decoded file's stems take the host writer."""
+        if isinstance(stems, Exception):
+            raise stems
+        if stems[0] == "host":
+            _, eng, source = stems
+            norm = lambda w: eng.normalize(w, self.normalization_threshold, self.amplification_threshold)   # noqa: E731
+            kind, entries = self._stem_plan(list(source) if isinstance(source, dict) else [None])
+            return self._emit_plan(kind, entries, lambda k: source.T if k is None else norm(source[k]).T, custom_output_names)
+        stems_d, kind, entries = stems
+        if on_device:
+            t0 = self._now()
+            _, views = self._host_planar_stems(stems_d)
+            self._sync()
+            self._tick("stems_d2h", t0)
+            return self._emit_plan(kind, entries, views.__getitem__, custom_output_names)
+        host = self._to_host(stems_d)
+        return self._emit_plan(kind, entries, lambda r: host[r].T, custom_output_names)

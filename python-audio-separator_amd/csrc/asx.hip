@@ -51,6 +51,7 @@ static void grant_lds(K *kernel, int bytes) { grant_lds(reinterpret_cast<const v
 #include "kernels_conv3h.h"
 #include "kernels_updown6.h"
 #include "kernels_rof.h"
+#include "kernels_mdxc_pool.h"
 #include "kernels_ht.h"
 #include "kernels_halo.h"
 #include "kernels_hd.h"
@@ -1506,19 +1507,18 @@ int asx_v3_forward(asx_engine *e, const float *wave_host, int32_t B, float *out_
 
 int asx_mdxc_plan(const asx_engine *e, int64_t N, int32_t overlap, asx_plan *out) {
   REQUIRE(e && out, "asx_mdxc_plan: null argument");
-  REQUIRE(N >= 1 && overlap >= 1, "n_samples and overlap must be >= 1");
+  MdxcTfcPlan t;                                         // csrc/mdxc_pool_plan.h: the one statement of the arithmetic
+  const std::string why = mdxc_tfc_plan(e->cfg.hop_length, e->cfg.segment_size, N, overlap, t);
+  REQUIRE(why.empty(), "%s", why.c_str());
   asx_plan p{};
   p.n_samples = N;
-  p.chunk_size = (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1);
-  p.step = p.chunk_size / overlap;                       // hop_size (mdxc_separator.py:364)
-  REQUIRE(p.step >= 1, "overlap larger than chunk_size");
-  int64_t r = (N - p.chunk_size) % p.step;               // Python floor-mod (:368)
-  if (r < 0) r += p.step;
-  p.pad = p.step - r;
-  p.trim = (int32_t)(p.chunk_size - p.step);             // zeros in front (:371)
+  p.chunk_size = t.chunk_size;
+  p.step = t.step;                                       // hop_size (mdxc_separator.py:364)
+  p.pad = t.pad;
+  p.trim = (int32_t)t.front;                             // zeros in front (:371)
   p.gen_size = p.step;
-  p.padded_len = p.trim + N + p.pad + p.chunk_size - p.step;
-  p.n_chunks = (int32_t)((p.padded_len - p.chunk_size) / p.step + 1);   // Tensor.unfold (:374)
+  p.padded_len = t.padded_len;
+  p.n_chunks = (int32_t)t.n_chunks;                      // Tensor.unfold (:374)
   p.n_frames = e->cfg.segment_size;
   *out = p;
   return ASX_OK;
@@ -1588,6 +1588,91 @@ int asx_mdxc_demix(asx_engine *e, const float *mix_host, int64_t N, int32_t over
   const int S = e->v3->cfg.num_targets;
   return host_round_trip(mix_host, (size_t)2 * N, out_host, (size_t)S * 2 * N,
                          [&](const float *mix, float *out) { return asx_mdxc_demix_dev(e, mix, N, overlap, out, nullptr); });
+}
+
+// ---- a batch of songs, their chunks pooled per net pass (both MDXC loops) -------------------------------------------------
+// The arguments of a pooled call, all checked on the host before anything is enqueued.
+static int mdxc_pool_args(const char *fn, asx_engine *e, const asx_mdxc_song *songs, int32_t n_songs, std::vector<int64_t> &Ns) {
+  REQUIRE(e && n_songs >= 0 && (songs || n_songs == 0), "%s: null argument", fn);
+  Ns.resize((size_t)n_songs);
+  for (int i = 0; i < n_songs; ++i) {
+    REQUIRE(songs[i].mix_dev && songs[i].out_dev, "%s: null pointer in song %d", fn, i);
+    REQUIRE(songs[i].n_samples >= 1, "%s: song %d: n_samples must be >= 1", fn, i);
+    Ns[i] = songs[i].n_samples;
+  }
+  return ASX_OK;
+}
+
+// The pool's tables on the device, from by-value launch arguments in groups of POOL_GROUP songs: per pooled chunk its song's base
+// pointer and length (pool_wave / pool_nsong) and its start (d_starts), per song its fold entry (pool_songs).  *blocks: the fold's
+// grid.x.  chunk_floats = S * 2 * C.  The buffers are sized by the caller.
+static int mdxc_pool_tables(asx_engine *e, const char *fn, const asx_mdxc_song *songs, const MdxcPoolPlan &pp, bool rof, int64_t chunk_floats,
+                            const float *chunks, int64_t *d_starts, hipStream_t s, int64_t *blocks) {
+  const int n = (int)pp.chunk0.size() - 1;
+  int64_t blk = 0;
+  for (int g0 = 0; g0 < n; g0 += POOL_GROUP) {
+    MdxcPoolGroup g{};
+    g.n_songs = std::min(POOL_GROUP, n - g0);
+    g.song0 = g0;
+    for (int i = 0; i < g.n_songs; ++i) {
+      const asx_mdxc_song &sg = songs[g0 + i];
+      g.mix[i] = sg.mix_dev;
+      g.out[i] = sg.out_dev;
+      g.n[i] = sg.n_samples;
+      g.chunk0[i] = pp.chunk0[g0 + i];
+      g.blk0[i] = blk;
+      blk += (sg.n_samples + 255) / 256;
+    }
+    g.chunk0[g.n_songs] = pp.chunk0[g0 + g.n_songs];
+    const int nthr = std::max(g.chunk0[g.n_songs] - g.chunk0[0], g.n_songs);
+    hipLaunchKernelGGL(mdxc_pool_table_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, g, pp.step, pp.chunk_size, rof ? 1 : 0,
+                       chunk_floats, chunks, reinterpret_cast<const float **>(e->pool_wave.p), reinterpret_cast<int64_t *>(e->pool_nsong.p),
+                       d_starts, reinterpret_cast<MdxcPoolSong *>(e->pool_songs.p));
+    HIPCHK(hipGetLastError());
+  }
+  REQUIRE(blk < ((int64_t)1 << 31), "%s: %lld samples in one pool", fn, (long long)blk * 256);
+  *blocks = blk;
+  return ASX_OK;
+}
+
+// MDXCSeparator.demix, TFC branch, for a pool of songs: one chunk list over all songs, walked in passes of
+// mdxc_pool_per_pass(total, max_batch) chunks that may straddle songs, then ONE segmented fold.  Every buffer is sized before the
+// first launch; the call only enqueues work.
+int asx_mdxc_demix_batch_dev(asx_engine *e, const asx_mdxc_song *songs, int32_t n_songs, int32_t overlap, void *stream) {
+  std::vector<int64_t> Ns;
+  CHK(mdxc_pool_args("asx_mdxc_demix_batch_dev", e, songs, n_songs, Ns));
+  READY(e->v3, "asx_mdxc_demix_batch_dev");
+  if (n_songs == 0) return ASX_OK;
+  MdxcPoolPlan pp;
+  std::string err;
+  REQUIRE(mdxc_pool_build_tfc(e->cfg.hop_length, e->cfg.segment_size, overlap, Ns.data(), n_songs, pp, err), "asx_mdxc_demix_batch_dev: %s",
+          err.c_str());
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  V3Net &n = *e->v3;
+  const int S = n.cfg.num_targets, nk = pp.total();
+  const int64_t C = pp.chunk_size, chunk_floats = (int64_t)S * 2 * C;
+  const int per = mdxc_pool_per_pass(nk, e->cfg.max_batch);
+  CHK(v3_ensure_workspace(e, per));
+  CHK(n.chunk_out.ensure((size_t)nk * chunk_floats * 4));
+  CHK(n.d_starts.ensure((size_t)nk * 8));
+  CHK(e->pool_wave.ensure((size_t)nk * 8));
+  CHK(e->pool_nsong.ensure((size_t)nk * 8));
+  CHK(e->pool_songs.ensure((size_t)n_songs * sizeof(MdxcPoolSong)));
+  int64_t *ds = reinterpret_cast<int64_t *>(n.d_starts.p);
+  int64_t blk = 0;
+  CHK(mdxc_pool_tables(e, "asx_mdxc_demix_batch_dev", songs, pp, false, chunk_floats, n.chunk_out.f(), ds, s, &blk));
+  for (int j = 0; j < nk; j += per) {
+    const int B = std::min(per, nk - j);
+    const PoolChunks pc{reinterpret_cast<const float *const *>(e->pool_wave.p) + j, reinterpret_cast<const int64_t *>(e->pool_nsong.p) + j};
+    CHK(v3_chunks_dev(e, nullptr, ds + j, 0, (int)pp.front, B, n.chunk_out.f() + (size_t)j * chunk_floats, s, &pc));
+  }
+  double bytes = 0.0;
+  for (int i = 0; i < n_songs; ++i) bytes += 4.0 * ((double)pp.tfc[i].n_chunks * chunk_floats + (double)S * 2 * Ns[i]);
+  return timed(e, ASX_PROF_FINALIZE, 0.0, bytes, s, [&]() {
+    hipLaunchKernelGGL(mdxc_finalize_pool_kernel, dim3((unsigned)blk, S * 2), dim3(256), 0, s, reinterpret_cast<const MdxcPoolSong *>(e->pool_songs.p),
+                       n_songs, S, C, pp.step, pp.front, (float)overlap);
+  });
 }
 
 // ---- BS-Roformer ------------------------------------------------------------------
@@ -1753,11 +1838,8 @@ __global__ void rof_starts_kernel(int k0, int nk, int64_t step, int64_t N, int64
 }
 
 static int rof_starts(asx_engine *e, int64_t N, int64_t step, std::vector<int64_t> &starts) {
-  const int64_t C = (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1);
-  REQUIRE(N >= C, "mix (%lld samples) shorter than one chunk (%lld): not supported on the Roformer path", (long long)N, (long long)C);
-  REQUIRE(step >= 1 && step <= C, "step must be in [1, chunk_size]");
-  starts.clear();
-  for (int64_t i = 0; i < N; i += step) starts.push_back(i + C > N ? N - C : i);   // tail re-anchored (:323-336)
+  const std::string why = rof_plan_starts(N, (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1), step, starts);   // csrc/mdxc_pool_plan.h
+  REQUIRE(why.empty(), "%s", why.c_str());
   return ASX_OK;
 }
 
@@ -1840,6 +1922,44 @@ int asx_rof_demix(asx_engine *e, const float *mix_host, int64_t N, int64_t step,
   const int n_out = e->rof->cfg.n_out;
   return host_round_trip(mix_host, (size_t)2 * N, out_host, (size_t)n_out * 2 * N,
                          [&](const float *mix, float *out) { return asx_rof_demix_dev(e, mix, N, step, out, nullptr); });
+}
+
+// The Roformer branch for a pool of songs: as asx_mdxc_demix_batch_dev, with the Roformer chunk starts and the Hamming-weighted fold.
+int asx_rof_demix_batch_dev(asx_engine *e, const asx_mdxc_song *songs, int32_t n_songs, int64_t step, void *stream) {
+  std::vector<int64_t> Ns;
+  CHK(mdxc_pool_args("asx_rof_demix_batch_dev", e, songs, n_songs, Ns));
+  READY(e->rof, "asx_rof_demix_batch_dev");
+  if (n_songs == 0) return ASX_OK;
+  MdxcPoolPlan pp;
+  std::string err;
+  REQUIRE(mdxc_pool_build_rof(e->cfg.hop_length, e->cfg.segment_size, step, Ns.data(), n_songs, pp, err), "asx_rof_demix_batch_dev: %s",
+          err.c_str());
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  RofNet &n = *e->rof;
+  const int S = n.cfg.num_stems, n_out = n.cfg.n_out, nk = pp.total();
+  const int64_t C = pp.chunk_size, chunk_floats = (int64_t)S * 2 * C;
+  const int per = mdxc_pool_per_pass(nk, e->cfg.max_batch);
+  CHK(rof_ensure_workspace(e, per));
+  CHK(n.chunk_out.ensure((size_t)nk * chunk_floats * 4));
+  CHK(n.d_starts.ensure((size_t)nk * 8));
+  CHK(e->pool_wave.ensure((size_t)nk * 8));
+  CHK(e->pool_nsong.ensure((size_t)nk * 8));
+  CHK(e->pool_songs.ensure((size_t)n_songs * sizeof(MdxcPoolSong)));
+  int64_t *ds = reinterpret_cast<int64_t *>(n.d_starts.p);
+  int64_t blk = 0;
+  CHK(mdxc_pool_tables(e, "asx_rof_demix_batch_dev", songs, pp, true, chunk_floats, n.chunk_out.f(), ds, s, &blk));
+  for (int j = 0; j < nk; j += per) {
+    const int B = std::min(per, nk - j);
+    const PoolChunks pc{reinterpret_cast<const float *const *>(e->pool_wave.p) + j, reinterpret_cast<const int64_t *>(e->pool_nsong.p) + j};
+    CHK(rof_chunks_dev(e, nullptr, ds + j, 0, B, n.chunk_out.f() + (size_t)j * chunk_floats, s, &pc));
+  }
+  double bytes = 0.0;
+  for (int i = 0; i < n_songs; ++i) bytes += 4.0 * ((double)pp.starts[i].size() * chunk_floats + 2.0 * n_out * Ns[i]);
+  return timed(e, ASX_PROF_FINALIZE, 0.0, bytes, s, [&]() {
+    hipLaunchKernelGGL(roformer_finalize_pool_kernel, dim3((unsigned)blk, n_out * 2), dim3(256), 0, s,
+                       reinterpret_cast<const MdxcPoolSong *>(e->pool_songs.p), n_songs, S, C, step, n.d_window.f());
+  });
 }
 
 // ---- options -----------------------------------------------------------------------
@@ -2228,6 +2348,8 @@ int asx_counter(const asx_engine *e, const char *name, int64_t *out) {
   else if (nm == "up6_launches") *out = (int64_t)g_up6_launches.load();
   else if (nm == "hd_rounds") *out = (int64_t)g_hd_rounds.load();
   else if (nm == "vr_net_passes") *out = (int64_t)g_vr_net_passes.load();
+  else if (nm == "v3_net_passes") *out = (int64_t)g_v3_net_passes.load();
+  else if (nm == "rof_net_passes") *out = (int64_t)g_rof_net_passes.load();
   else {
     set_err("asx_counter: unknown counter '%s'", name);
     return ASX_ERR_INVALID;

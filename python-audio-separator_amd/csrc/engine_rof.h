@@ -426,9 +426,13 @@ static int rof_ensure_workspace(asx_engine *e, int B) {
   return ASX_OK;
 }
 
-// wave chunks -> separated chunks [B, S, 2, C]
+// wave chunks -> separated chunks [B, S, 2, C]; pc: a pass over a pool of songs -- chunk b is a window of ITS song
+// (stft_pool_kernel), everything behind the STFT is the same code
+static std::atomic<long long> g_rof_net_passes{0};   // calls of rof_chunks_dev since the process started (asx_counter "rof_net_passes")
+
 static int rof_chunks_dev(asx_engine *e, const float *wave, const int64_t *d_starts, int64_t n_song, int B, float *out,
-                          hipStream_t s) {
+                          hipStream_t s, const PoolChunks *pc = nullptr) {
+  g_rof_net_passes.fetch_add(1);
   RofNet &n = *e->rof;
   const asx_rof_config &c = n.cfg;
   const int T = e->cfg.segment_size, Fb = c.n_bands, D = c.dim, S = c.num_stems;
@@ -454,7 +458,8 @@ static int rof_chunks_dev(asx_engine *e, const float *wave, const int64_t *d_sta
     a.sign = c.stft_normalized ? (float)(1.0 / sqrt((double)e->cfg.n_fft)) : 1.0f;
     FftPlan p = e->plan;
     CHK(timed(e, ASX_PROF_STFT, 0.0, 4.0 * ((double)B * 2 * C + (double)BT * n.W), s, [&]() {
-      hipLaunchKernelGGL(stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p);
+      if (pc) hipLaunchKernelGGL(stft_pool_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p, *pc);
+      else hipLaunchKernelGGL(stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p);
     }));
   }
   // band split (bs_roformer.py:163-185): per band RMSNorm + Linear -> TOK[(b t), band, :]

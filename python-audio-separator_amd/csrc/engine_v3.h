@@ -318,9 +318,13 @@ static int v3_core_dev(asx_engine *e, int B, hipStream_t s) {
 }
 
 // chunk waves -> separated chunk waves [B, S, 2, C]; input either explicit chunks [B,2,C] (n_song < 0)
-// or windows of the resident mix (song mode, front zeros = `front`)
+// or windows of the resident mix (song mode, front zeros = `front`); pc: a pass over a pool of songs -- chunk b is a window of ITS
+// song (stft_pool_kernel), everything behind the STFT is the same code
+static std::atomic<long long> g_v3_net_passes{0};   // calls of v3_chunks_dev since the process started (asx_counter "v3_net_passes")
+
 static int v3_chunks_dev(asx_engine *e, const float *wave, const int64_t *d_starts, int64_t n_song, int front, int B,
-                         float *out, hipStream_t s) {
+                         float *out, hipStream_t s, const PoolChunks *pc = nullptr) {
+  g_v3_net_passes.fetch_add(1);
   V3Net &n = *e->v3;
   const asx_v3_config &cf = n.cfg;
   const int T = e->cfg.segment_size, k = cf.num_subbands, Fs = e->cfg.dim_f / k;
@@ -348,7 +352,8 @@ static int v3_chunks_dev(asx_engine *e, const float *wave, const int64_t *d_star
     a.out_bstride = (int64_t)(dim_c + cf.num_channels_model) * P0;
     FftPlan p = e->plan;
     CHK(timed(e, ASX_PROF_STFT, 0.0, 4.0 * ((double)B * 2 * C + (double)B * 4 * T * e->cfg.dim_f), s, [&]() {
-      hipLaunchKernelGGL(stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p);
+      if (pc) hipLaunchKernelGGL(stft_pool_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p, *pc);
+      else hipLaunchKernelGGL(stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p);
     }));
   }
   CHK(v3_core_dev(e, B, s));

@@ -275,7 +275,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_ensemble_dev", "asx_invert_stem", "asx_normalize", "asx_normalize_dev", "asx_residual_dev",
            "asx_profile_launches", "asx_debug_trace", "asx_resample_sinc", "asx_resample_sinc_dev", "asx_counter",
            "asx_set_stft_window", "asx_op_tdf_block", "asx_op_attention", "asx_op_mha", "asx_get_option",
-           "asx_demix_batch_dev", "asx_separate_batch_dev", "asx_ensemble_slot_dev", "asx_vr_separate_batch_dev"]
+           "asx_demix_batch_dev", "asx_separate_batch_dev", "asx_ensemble_slot_dev", "asx_vr_separate_batch_dev",
+           "asx_mdxc_demix_batch_dev", "asx_rof_demix_batch_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -296,6 +297,10 @@ class _ApplySong(C.Structure):     # struct asx_apply_song
 
 class _VrSong(C.Structure):        # struct asx_vr_song
     _fields_ = [("wave_dev", C.c_void_p), ("n_samples", C.c_int64), ("primary_dev", C.c_void_p), ("secondary_dev", C.c_void_p)]
+
+
+class _MdxcSong(C.Structure):      # struct asx_mdxc_song
+    _fields_ = [("mix_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_samples", C.c_int64)]
 
 
 VR_POOL_SEGMENTS = 16              # ASX_VR_POOL_SEGMENTS: songs one gather / scatter launch of a pooled VR pass serves
@@ -371,6 +376,8 @@ def load_library():
     lib.asx_rof_forward.argtypes = [vp, _FP, i32, _FP]
     lib.asx_rof_demix.argtypes = [vp, _FP, i64, i64, _FP]
     lib.asx_rof_demix_dev.argtypes = [vp, vp, i64, i64, vp, vp]
+    lib.asx_mdxc_demix_batch_dev.argtypes = [vp, C.POINTER(_MdxcSong), i32, i32, vp]
+    lib.asx_rof_demix_batch_dev.argtypes = [vp, C.POINTER(_MdxcSong), i32, i64, vp]
     lib.asx_set_option.argtypes = [vp, C.c_char_p, i32]
     lib.asx_get_option.argtypes = [vp, C.c_char_p, C.POINTER(i32)]
     lib.asx_counter.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
@@ -590,6 +597,51 @@ class Engine:
 
     def mdxc_demix_dev(self, mix_ptr: int, n_samples: int, overlap: int, out_ptr: int, stream: int = 0):
         self._check(self._lib.asx_mdxc_demix_dev(self._h, mix_ptr, n_samples, int(overlap), out_ptr, stream or None))
+
+    # a batch of songs in one call: the chunks of all of them pooled per net pass (both MDXC loops)
+    def _mdxc_batch_dev(self, fn, songs, arg, stream):
+        songs = list(songs)
+        arr = (_MdxcSong * max(1, len(songs)))()
+        for i, (mix_ptr, out_ptr, n) in enumerate(songs):
+            arr[i] = _MdxcSong(mix_ptr or None, out_ptr or None, int(n))
+        self._check(fn(self._h, arr, len(songs), int(arg), stream or None))
+
+    def _mdxc_batch(self, dev_call, rows, mixes, arg) -> list:
+        """A list of float32 [2, N_i] arrays through one pooled call; returns the list of [rows, 2, N_i] results.  Device staging
+        buffers come from torch (the plumbing layer), as in ``demix_batch``."""
+        host = []
+        for mix in mixes:
+            mix = _f32(mix)
+            if mix.ndim != 2 or mix.shape[0] != 2:
+                raise ValueError(f"Expected a 2-channel audio signal, but got shape {mix.shape}")
+            host.append(mix)
+        if not host:
+            return []
+        torch, dev, st = self._torch_stream()
+        with torch.cuda.stream(st):
+            d_mix = [torch.from_numpy(m).to(dev) for m in host]
+            d_out = [torch.empty((rows, 2, m.shape[1]), dtype=torch.float32, device=dev) for m in host]
+            dev_call([(m.data_ptr() if m.numel() else 0, o.data_ptr() if o.numel() else 0, m.shape[1]) for m, o in zip(d_mix, d_out)],
+                     arg, st.cuda_stream)
+            outs = [o.cpu().numpy() for o in d_out]
+        return outs
+
+    def mdxc_demix_batch_dev(self, songs, overlap: int, stream: int = 0):
+        """``songs``: a list of ``(mix_ptr, out_ptr, n_samples)`` -- mix [2, n] and out [S, 2, n] in HBM.  The chunks of all songs
+        share the net passes; every ``out`` equals what ``mdxc_demix_dev`` writes for that song alone, bit for bit
+        (asx_mdxc_demix_batch_dev)."""
+        self._mdxc_batch_dev(self._lib.asx_mdxc_demix_batch_dev, songs, overlap, stream)
+
+    def mdxc_demix_batch(self, mixes, overlap: int) -> list:
+        return self._mdxc_batch(self.mdxc_demix_batch_dev, self.v3_cfg.num_targets if mixes else 0, mixes, overlap)
+
+    def rof_demix_batch_dev(self, songs, step: int, stream: int = 0):
+        """As ``mdxc_demix_batch_dev`` on the Roformer loop: out [n_out, 2, n] each, equal to ``rof_demix_dev``'s
+        (asx_rof_demix_batch_dev).  A song shorter than one chunk is refused, by index, before anything runs."""
+        self._mdxc_batch_dev(self._lib.asx_rof_demix_batch_dev, songs, step, stream)
+
+    def rof_demix_batch(self, mixes, step: int) -> list:
+        return self._mdxc_batch(self.rof_demix_batch_dev, self.rof_cfg.n_out if mixes else 0, mixes, step)
 
     # -- BS-Roformer ------------------------------------------------------------
     def load_rof(self, rc: RofConfig, state_dict: dict):

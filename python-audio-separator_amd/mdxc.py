@@ -184,13 +184,83 @@ class MDXCDemixer:
         else:
             self.engine.load_v3(self.v3, state_dict)
 
-    def demix(self, mix: np.ndarray):
-        """mdxc_separator.py:257-468 for TFC-TDF models: dict of stems, or the primary array."""
+    @staticmethod
+    def _checked(mix):
         mix = np.asarray(mix, dtype=np.float32)
         if mix.ndim != 2 or mix.shape[0] != 2:
             raise ValueError(f"Expected a 2-channel audio signal, but got {mix.shape[0] if mix.ndim else 0} channels")
         if mix.shape[1] == 0:
             raise ValueError("Audio file is empty or not valid")
+        return mix
+
+    @property
+    def chunk_size(self) -> int:
+        return self.engine.cfg.hop_length * (self.mdx_segment_size - 1)
+
+    def roformer_step(self) -> int:
+        """mdxc_separator.py:305-306: the Roformer loop's step in samples."""
+        desired_step = int(self.overlap * self.sample_rate)
+        return self.chunk_size if desired_step <= 0 else min(desired_step, self.chunk_size)
+
+    def _stem_dict(self, out, mix):
+        """mdxc_separator.py:406-468 on a demix result [rows, 2, N]: dict of stems, or the primary array."""
+        num_stems = (1 if self.target_instrument else len(self.instruments)) if self.is_roformer else self.v3.num_targets
+        if num_stems > 1:
+            return {k: out[i] for i, k in enumerate(self.instruments)}
+        primary = out[0]
+        if self.is_primary_stem_main_target:
+            return {self.primary_stem_name: primary, self.secondary_stem_name: mix - primary}
+        return primary
+
+    def demix_many(self, mixes):
+        """``demix`` for a list of mixes in ONE pooled engine call (asx_mdxc_demix_batch_dev / asx_rof_demix_batch_dev): the chunks
+        of all mixes share the net passes.  Returns the list of what ``demix(mix)`` returns, bit for bit.  With ``pitch_shift`` it
+        is a loop of ``demix``: the resampled lengths differ per song and the round trip runs on host arrays."""
+        mixes = [self._checked(m) for m in mixes]
+        if self.pitch_shift != 0:
+            return [self._demix_pitched(m) for m in mixes]
+        if self.is_roformer:
+            outs = self.engine.rof_demix_batch(mixes, self.roformer_step())
+        else:
+            outs = self.engine.mdxc_demix_batch(mixes, int(self.overlap))
+        return [self._stem_dict(out, mix) for out, mix in zip(outs, mixes)]
+
+    def demix_many_dev(self, mixes_d):
+        """``demix_dev`` for a list of (already normalised) device mixes in ONE pooled engine call: a list of (names, CUDA tensor)
+        as ``demix_dev`` gives them, the residual stem of a single-target model made per song.  Only enqueues work.  With
+        ``pitch_shift`` there is no device path (``demix_dev`` has none either): use ``demix_many``."""
+        import torch
+        if self.pitch_shift != 0:
+            raise NotImplementedError("pitch_shift runs on host arrays: demix_many")
+        if not mixes_d:
+            return []
+        st = torch.cuda.current_stream(mixes_d[0].device).cuda_stream
+        if self.is_roformer:
+            n_out = int(self.engine.rof_cfg.n_out)
+            multi = not self.target_instrument and len(self.instruments) > 1
+        else:
+            n_out = self.v3.num_targets
+            multi = n_out > 1
+        raws = [torch.empty((n_out + 1, 2, m.shape[1]), dtype=torch.float32, device=m.device) for m in mixes_d]   # + a residual row
+        songs = [(m.data_ptr(), r.data_ptr(), m.shape[1]) for m, r in zip(mixes_d, raws)]
+        if self.is_roformer:
+            self.engine.rof_demix_batch_dev(songs, self.roformer_step(), stream=st)
+        else:
+            self.engine.mdxc_demix_batch_dev(songs, int(self.overlap), stream=st)
+        res = []
+        for mix_d, raw in zip(mixes_d, raws):
+            if multi:
+                res.append((list(self.instruments)[:n_out], raw[:n_out]))
+            elif self.is_primary_stem_main_target:
+                self.engine.residual_dev(mix_d.data_ptr(), raw[0].data_ptr(), raw[1].data_ptr(), 2 * mix_d.shape[1], stream=st)
+                res.append(([self.primary_stem_name, self.secondary_stem_name], raw[:2]))
+            else:
+                res.append(([None], raw[:1]))
+        return res
+
+    def demix(self, mix: np.ndarray):
+        """mdxc_separator.py:257-468 for TFC-TDF models: dict of stems, or the primary array."""
+        mix = self._checked(mix)
         if self.pitch_shift != 0:
             return self._demix_pitched(mix)
         if self.is_roformer:

@@ -251,6 +251,21 @@ def demucs_demix_many(engine, gen: str = "ht", shifts: int = 0, offsets=None, ov
     return run
 
 
+def mdxc_demix_many(engine, overlap=None, step=None, stream=None):
+    """The ``demix_many`` callable of FilesPipeline over an MDXC engine: one pooled call for all songs of a step --
+    ``mdxc_demix_batch_dev`` (TFC-TDF v3, give ``overlap``) or ``rof_demix_batch_dev`` (Roformer, give ``step`` in samples);
+    ``outs[s]`` is that song's [S, 2, N] stems."""
+    if (overlap is None) == (step is None):
+        raise ValueError("give overlap (TFC-TDF v3 engine) or step (Roformer engine), not both")
+    run_batch, arg = (engine.mdxc_demix_batch_dev, overlap) if step is None else (engine.rof_demix_batch_dev, step)
+
+    def run(mixes, outs):
+        import torch
+        st = stream() if stream is not None else torch.cuda.current_stream(torch.device("cuda", engine.device)).cuda_stream
+        run_batch([(m.data_ptr(), outs[i].data_ptr(), m.shape[-1]) for i, m in enumerate(mixes)], int(arg), stream=st)
+    return run
+
+
 class ShardWorkspace:
     """Buffers of sharded_demix, allocated once per (shape, world) and reused: the strong-scaling loop then times compute +
     gather + fold, not the caching allocator.  ``timings`` (when ``timed``) holds event-measured milliseconds of the last
