@@ -583,7 +583,13 @@ int asx_residual_dev(asx_engine *e, const float *mix_dev, const float *stem_dev,
  *                  6 min_fft, 7 max_fft, 8 uvr_max_spec, 9 uvr_min_spec, 10 ensemble_wav (spec_utils.py:1245-1266: each
  *                  channel from the input with the smallest mean |x|); weights [K] (avg_* only) or NULL; out [2, *n_out]
  *                  (*n_out = N, or 1024 * (N / 1024) for the uvr_* algorithms, which do not pass a length to istft).
- * asx_invert_stem = spec_utils.invert_stem(mixture, stem) (uvr_lib_v5/spec_utils.py:573-580), planar [2, *n_out]. */
+ * asx_invert_stem = spec_utils.invert_stem(mixture, stem) (uvr_lib_v5/spec_utils.py:573-580), planar [2, *n_out],
+ *                  *n_out = 1024 * (N / 1024).
+ * 2 <= K <= 8 and N >= 1, else ASX_ERR_INVALID.  *n_out = 0 (N < 1024 for uvr_* and asx_invert_stem) is a result, not an
+ * error: nothing is launched or written and the call returns ASX_OK, as the reference returns an empty array there.
+ * Outside the parity domain: ensemble_wav compares sums of |x| held in float64, numpy's means are float32 sums; two
+ * inputs whose channel means agree to float32 rounding but not exactly may be ranked differently (the engine by the
+ * float64 sums).  Exactly equal sums keep the first input, as np.argmin does. */
 int asx_ensemble(asx_engine *e, const float *waves_host, int32_t k, int64_t n_samples, int32_t algorithm, const double *weights,
                  float *out_host, int64_t *n_out);
 int asx_ensemble_dev(asx_engine *e, const float *waves_dev, int32_t k, int64_t n_samples, int32_t algorithm, const double *weights,

@@ -29,14 +29,17 @@ static int ens_ctx(asx_engine *e) {
   }
   CHK(ht_up(c.tw, tw));
   const int lds = (int)(((size_t)c.plan.nh * 2 + (size_t)(c.plan.nh + 1) * (2 + ENS_MAX_K)) * sizeof(float2));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ens_fft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ens_invert_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  // median_fft needs 65,584 B of dynamic LDS at K = 4 and 98,384 B at K = 8: a refused raise is an error here, not a failed launch later.
+  // Per engine (= per device), so not through the process-wide grant_lds record.
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ens_fft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ens_invert_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   c.ready = true;
   return ASX_OK;
 }
 
-// librosa.istft fold of frames [2, T, 2048] -> out [2, len] (len = N for length=N, hop*(T-1) otherwise)
+// librosa.istft fold of frames [2, T, 2048] -> out [2, len] (len = N for length=N, hop*(T-1) otherwise); len = 0 writes nothing
 static int ens_fold(asx_engine *e, int T, int64_t len, float *out, hipStream_t s) {
+  if (len <= 0) return ASX_OK;
   EnsCtx &c = *e->ens;
   const int nf = c.plan.n_fft, hop = 1024;
   std::vector<float> w;
@@ -90,6 +93,10 @@ static int ens_ensemble_dev(asx_engine *e, const float *waves, int K, int64_t N,
   }
   const int hop = 1024, nh = c.plan.nh;
   const int T = (int)(1 + N / hop);
+  if (alg >= ENS_UVR_MAX_SPEC && T < 2) {   // one frame, no length argument: the reference's istft returns [2, 0]
+    *n_out = 0;
+    return ASX_OK;
+  }
   CHK(c.frames.ensure((size_t)2 * T * c.plan.n_fft * 4));
   const size_t lds = ((size_t)nh * 2 + (size_t)(nh + 1) * (2 + (alg == ENS_MEDIAN_FFT ? K : 0))) * sizeof(float2);
   CHK(timed(e, ASX_PROF_STFT, 0.0, 4.0 * ((double)K * 2 * N + 2.0 * T * c.plan.n_fft), s, [&]() {
@@ -105,7 +112,10 @@ static int ens_invert_dev(asx_engine *e, const float *mix, const float *stem, in
   EnsCtx &c = *e->ens;
   const int hop = 1024, nh = c.plan.nh;
   const int T = (int)(1 + N / hop);
-  REQUIRE(T >= 2, "input too short");
+  if (T < 2) {   // fewer than 1024 samples: hop * (T - 1) = 0, the reference returns an empty [0, 2]
+    *n_out = 0;
+    return ASX_OK;
+  }
   CHK(c.frames.ensure((size_t)2 * T * c.plan.n_fft * 4));
   const size_t lds = ((size_t)nh * 2 + (size_t)(nh + 1) * 2) * sizeof(float2);
   CHK(timed(e, ASX_PROF_STFT, 0.0, 4.0 * (4.0 * N + 2.0 * T * c.plan.n_fft), s, [&]() {

@@ -1093,9 +1093,8 @@ class Engine:
         stack = np.zeros((len(ws), 2, n), np.float32)
         for k, w in enumerate(ws):
             stack[k, :, : w.shape[1]] = w
-        wt = None
-        if weights is not None and len(weights) == len(ws) and np.all(np.isfinite(weights)) and np.sum(weights) != 0:
-            wt = (C.c_double * len(ws))(*[float(v) for v in weights])
+        wl = self.ensemble_weights(weights, len(ws))
+        wt = (C.c_double * len(ws))(*wl) if wl is not None else None
         out = np.empty((2, n), np.float32)
         n_out = C.c_int64()
         self._check(self._lib.asx_ensemble(self._h, _ptr(stack), len(ws), n, self.ENSEMBLE_ALGORITHMS.index(algorithm), wt, _ptr(out),
