@@ -612,6 +612,35 @@ int asx_invert_stem(asx_engine *e, const float *mix_host, const float *stem_host
 int asx_ensemble_slot_dev(asx_engine *e, const float *stem_dev, int64_t n_samples, int32_t layout, float max_peak, float min_peak,
                           int32_t has_min, int32_t mode, float *stack_dev, int32_t k, int64_t n_max, float *peak_after, void *stream);
 
+/* The ensembles of many (file, stem group) jobs in one call: per job exactly what asx_ensemble_slot_dev for each contributor
+ * followed by asx_ensemble_dev over the stack gives (bit for bit), with one launch per stage over all jobs, no stack in memory
+ * and one wait of the host (for the peaks).
+ *   peaks      peak_after[c] is what asx_ensemble_slot_dev reports for contributor c under `mode` and the thresholds
+ *   live set   a contributor with (double)peak_after < silent_below takes no part (its 16-bit file would not have been written); the
+ *              others are zero padded to the longest of THEM (n_max); live = how many took part
+ *   result     live == 0: none (n_out = 0, out_dev untouched); live == 1: that contributor's slot image (n_out = its n);
+ *              else asx_ensemble_dev's: n_out = n_max, or 1024 * (n_max / 1024) for the uvr_* algorithms (0, and nothing
+ *              written, below two frames).  out_dev receives planar [2, n_out] and nothing beyond 2 * n_out floats.
+ *   weights    [n_weights] or NULL, for avg_* only: a job with live == n_weights gives weights[i] to its i-th live contributor,
+ *              any other job uses equal weights -- what Ensembler.ensemble does with a weights list (ensembler.py:32-44)
+ * Every argument of every job is checked before anything is enqueued; the message names the job.  n_jobs == 0 does nothing.
+ * At most ASX_ENS_MAX_JOBS jobs per call.  Additive to ABI 7. */
+#define ASX_ENS_MAX_K 8
+#define ASX_ENS_MAX_JOBS 8191
+typedef struct asx_ens_job {
+  int32_t k;                              /* contributors, 1 .. ASX_ENS_MAX_K */
+  int32_t live;                           /* written: contributors that took part */
+  const float *stem_dev[ASX_ENS_MAX_K];   /* planar [2, n] or rows [n, 2]; may be NULL where n == 0 */
+  int64_t n_samples[ASX_ENS_MAX_K];
+  int32_t layout[ASX_ENS_MAX_K];          /* ASX_STEM_PLANAR / ASX_STEM_ROWS */
+  float *out_dev;                         /* planar, room for [2, out_capacity] */
+  int64_t out_capacity;                   /* >= the longest n_samples of the job */
+  int64_t n_out;                          /* written: samples per channel of the result; 0 = no result */
+  float peak_after[ASX_ENS_MAX_K];        /* written */
+} asx_ens_job;
+int asx_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int32_t n_jobs, int32_t algorithm, const double *weights, int32_t n_weights,
+                           int32_t mode, float max_peak, float min_peak, int32_t has_min, double silent_below, void *stream);
+
 /* Launch counters of this process (tests use them to prove which kernel family ran; ABI 6 -- until ABI 5 they travelled through a
  * float of asx_debug_fetch, which stops resolving single launches past 2^24): "tdf3_launches" (split-operand row GEMM, either arithmetic),
  * "tdf3h_launches" (those of them, plain or GATHER mode, that ran the fp16 x 3 arithmetic),

@@ -97,7 +97,11 @@ class DemucsSeparator(CommonSeparator):
         dm = self._prepare_model()
         mix_d = self._device_decode(self.audio_file_path)
         out_d = self._device_stems(dm, mix_d) if mix_d is not None else None
-        if out_d is None:
+        return self._stems_of(out_d)
+
+    def _stems_of(self, out_d):
+        """Stems [S, 2, N] in HBM -> the list ``stems_dev`` returns (None: the configuration combined on the host)."""
+        if out_d is None or isinstance(out_d, np.ndarray):
             return None
         return [(name, out_d[index], "planar") for name, index in self._written_stems(len(out_d))]
 
@@ -135,6 +139,7 @@ class DemucsSeparator(CommonSeparator):
     # ---- a batch of files: the hooks of CommonSeparator._separate_many ------------------------------------------------------
     # The shift offsets are drawn in file order, so under one ``random.seed`` the files equal those of ``separate(path)`` called per path.
     separate_many = CommonSeparator._separate_many
+    stems_dev_many = CommonSeparator._stems_dev_many
 
     def _pooled_stems(self, mixes):
         """``DemucsDemixer.demix_many_dev``: the segments of all files share the forwards."""

@@ -113,7 +113,13 @@ class MDXSeparator(CommonSeparator):
         mix = self._device_decode(self.audio_file_path)
         if mix is None:
             return None
-        stems = dict(zip(("primary", "secondary"), self._device_stems(mix)))
+        return self._stems_of(self._device_stems(mix))
+
+    def _stems_of(self, stems):
+        """(primary, secondary) CUDA tensors [N, 2] -> the list ``stems_dev`` returns."""
+        if isinstance(stems[0], np.ndarray):              # invert_using_spec: host stems (no file reaches here on the device path)
+            return None
+        stems = dict(zip(("primary", "secondary"), stems))
         return [(name, stems[which], "rows") for name, which in self._wanted_pair()]
 
     def _emit_file(self, stems, on_device, custom_output_names):
@@ -146,6 +152,7 @@ class MDXSeparator(CommonSeparator):
 
     # ---- a batch of files: the hooks of CommonSeparator._separate_many ------------------------------------------------------
     separate_many = CommonSeparator._separate_many
+    stems_dev_many = CommonSeparator._stems_dev_many
 
     def _pooled_stems(self, mixes):
         """asx_separate_batch_dev: the chunks of all files share the net passes."""

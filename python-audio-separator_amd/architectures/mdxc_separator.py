@@ -136,10 +136,18 @@ class MDXCSeparator(CommonSeparator):
         self._reset_file_state()
         self._begin_file(audio_file_path)
         got = self._device_stems()
-        if got is None:
+        return None if got is None else self._stems_of(got)
+
+    def _stems_of(self, got):
+        """(stems [S, 2, N], kind, entries) as ``_device_stems`` and ``_pooled_stems`` have them -> the list ``stems_dev`` returns."""
+        if isinstance(got, Exception):
+            raise got
+        if got[0] == "host":                              # pitch_shift, or no device file path: host stems
             return None
         stems_d, kind, entries = got
         return [(name, stems_d[i], "planar") for name, i in entries if kind == "all" or self._wanted(name)]
+
+    stems_dev_many = CommonSeparator._stems_dev_many
 
     def _emit_plan(self, kind, entries, fetch, custom_output_names):
         """``_stem_plan`` -> files; ``fetch(key)`` is the [N, 2] array of one stem, called once per stem.  ``separate`` has reset

@@ -170,8 +170,11 @@ class VRSeparator(CommonSeparator):
         t0 = self._now()
         stems_d = dm.separate_stems_dev(wave_d)
         self._tick("demix", t0)
-        return [(name, stems_d[i], "planar") for i, (name, want) in enumerate(((self.primary_stem_name, want_p),
-                                                                              (self.secondary_stem_name, want_s))) if want]
+        return self._stems_of(stems_d)
+
+    def _stems_of(self, stems_d):
+        """One CUDA tensor [2 (primary, secondary), 2, N'] -> the list ``stems_dev`` returns."""
+        return [(name, stems_d[i], "planar") for i, name in enumerate((self.primary_stem_name, self.secondary_stem_name)) if self._wanted(name)]
 
     def _emit_file(self, stems, on_device, custom_output_names):
         """The stems of the current file -> its output files, primary first (vr_separator.py:211-246), unlike the MDX family.
@@ -208,6 +211,7 @@ class VRSeparator(CommonSeparator):
 
     # ---- a batch of files: the hooks of CommonSeparator._separate_many ------------------------------------------------------
     separate_many = CommonSeparator._separate_many
+    stems_dev_many = CommonSeparator._stems_dev_many
 
     def _pooled_stems(self, mixes):
         """``VRDemixer.separate_stems_many_dev``: the patches of all files share the net passes; a stem ``output_single_stem``

@@ -361,7 +361,8 @@ class CommonSeparator:
 
     # ---- a batch of files in one pooled engine call -----------------------------------------------------------------
     # A plugin that implements the hooks ``_pooled_stems`` and ``_emit_file`` (and ``_prepare_model`` / ``_check_loaded`` where it needs
-    # one) publishes the shell as ``separate_many``; the others have no such attribute.  ``_PER_FILE`` lists what loading a file leaves
+    # one) publishes the shell as ``separate_many``; the others have no such attribute.  With the hook ``_stems_of`` it also publishes
+    # ``_stems_dev_many`` as ``stems_dev_many``: the same pool, the stems left on the device instead of written (ensemble.py).  ``_PER_FILE`` lists what loading a file leaves
     # for its writer; a plugin that records more extends it.
     _PER_FILE = ("audio_file_path", "audio_file_base", "input_bit_depth", "input_subtype", "_file_seconds")
 
@@ -370,6 +371,48 @@ class CommonSeparator:
 
     def _check_loaded(self, dev_mix, host_mix):
         """Hook: refuse (raise for) a loaded file that the pooled call could not take, so that it fails alone."""
+
+    def _stems_of(self, file_stems):
+        """Hook: one entry of ``_pooled_stems`` for a file decoded on the device -> what ``stems_dev`` returns for that file,
+        [(stem name, CUDA tensor, "rows" | "planar")] (None: the stems did not stay on the device)."""
+        raise NotImplementedError
+
+    def _pool_files(self, paths, device_only=False):
+        """The part ``_separate_many`` and ``_stems_dev_many`` share: every file is loaded as ``separate`` loads it (``_load_mix``)
+        and checked (``_check_loaded``), then ONE ``_pooled_stems([(device mix or None, host mix or None)])`` call returns the stems
+        of all of them.  A file that cannot be used fails alone: the exception is logged and kept in ``self.batch_errors[index]``.
+        ``device_only``: a file the device decoder does not take is left out of the pool (and not checked).  Returns
+        ([(index, per-file state, device mix, stems)] of the pooled files, [indices left out])."""
+        self.batch_errors = {}
+        self._prepare_model()
+        loaded, left_out = [], []                     # (index, per-file state, device mix, host mix)
+        for i, path in enumerate(paths):
+            try:
+                self._reset_file_state()
+                self._begin_file(path)
+                dev_mix, host_mix = self._load_mix(path)
+                if device_only and dev_mix is None:
+                    left_out.append(i)
+                    continue
+                self._check_loaded(dev_mix, host_mix)
+            except Exception as e:
+                self._file_failed(i, path, e)
+                continue
+            loaded.append((i, {k: getattr(self, k) for k in self._PER_FILE}, dev_mix, host_mix))
+        if not loaded:
+            self._reset_file_state()
+            return [], left_out
+        stems = self._pooled_stems([(d, h) for _, _, d, h in loaded])
+        return [(i, state, dev_mix, file_stems) for (i, state, dev_mix, _), file_stems in zip(loaded, stems)], left_out
+
+    def _file_failed(self, i, path, e):                # this file only
+        self.logger.error(f"{path}: {e}")
+        self.batch_errors[i] = e
+
+    def _restore_file(self, state):
+        self._reset_file_state()
+        for k, v in state.items():
+            setattr(self, k, v)
 
     def _separate_many(self, paths, custom_output_names=None):
         """``separate`` for a list of files with ONE pooled engine call: every file is loaded as ``separate`` loads it
@@ -382,38 +425,46 @@ class CommonSeparator:
         ``try``: its entry in the result is an empty list, the exception is logged and kept in ``self.batch_errors[index]``;
         the other files are processed.  ``custom_output_names`` applies to every file, as it does in ``separate``."""
         paths = list(paths)
-        self.batch_errors = {}
         results = [[] for _ in paths]
-
-        def failed(i, path, e):                           # this file only
-            self.logger.error(f"{path}: {e}")
-            self.batch_errors[i] = e
         with self._writing():
-            self._prepare_model()
-            loaded = []                                   # (index, per-file state, device mix, host mix)
-            for i, path in enumerate(paths):
-                try:
-                    self._reset_file_state()
-                    self._begin_file(path)
-                    dev_mix, host_mix = self._load_mix(path)
-                    self._check_loaded(dev_mix, host_mix)
-                except Exception as e:
-                    failed(i, path, e)
-                    continue
-                loaded.append((i, {k: getattr(self, k) for k in self._PER_FILE}, dev_mix, host_mix))
-            if not loaded:
-                self._reset_file_state()
-                return results
-            stems = self._pooled_stems([(d, h) for _, _, d, h in loaded])
-            for (i, state, dev_mix, _), file_stems in zip(loaded, stems):
-                self._reset_file_state()
-                for k, v in state.items():
-                    setattr(self, k, v)
+            pooled, _ = self._pool_files(paths)
+            for i, state, dev_mix, file_stems in pooled:
+                self._restore_file(state)
                 try:
                     results[i] = self._emit_file(file_stems, dev_mix is not None, custom_output_names)
                 except Exception as e:
-                    failed(i, state["audio_file_path"], e)
+                    self._file_failed(i, state["audio_file_path"], e)
         return results
+
+    def _stems_dev_many(self, paths):
+        """``stems_dev`` for a list of files with ONE pooled engine call (the loading loop and the fail-alone rule of
+        ``_separate_many``; nothing is written).  Returns ``(stems, states)``, one entry per input, in order.  ``stems[i]`` is
+
+        * what ``stems_dev(paths[i])`` returns -- [(stem name, CUDA tensor, "rows" | "planar")], honouring ``output_single_stem``;
+          the pooled engine calls give every song the bits of the single-song call, so the tensors equal those of ``stems_dev``;
+        * None when the file needs the host decoder (it never enters the pool);
+        * the exception the file raised (also kept in ``self.batch_errors[i]``).
+
+        ``states[i]`` is the ``_PER_FILE`` state the file left (None unless ``stems[i]`` is a list): restored on the plugin
+        (``_restore_file``) it makes ``get_stem_output_path`` name that file's stems.  The plugin's own per-file state is reset
+        when the call returns.
+
+        The files are seen in list order, so state that evolves from file to file evolves as in a loop of ``stems_dev``: the
+        MDXC short-file rule (at most two pools), the Demucs shift offsets (drawn from ``random`` in file order)."""
+        paths = list(paths)
+        stems, states = [None] * len(paths), [None] * len(paths)
+        pooled, _ = self._pool_files(paths, device_only=True)
+        for i, state, _, file_stems in pooled:
+            self._restore_file(state)
+            try:
+                stems[i] = self._stems_of(file_stems)
+                states[i] = state if stems[i] is not None else None
+            except Exception as e:
+                self._file_failed(i, state["audio_file_path"], e)
+        for i, e in self.batch_errors.items():
+            stems[i] = e
+        self._reset_file_state()
+        return stems, states
 
     # ---- stem naming -------------------------------------------------------
     def secondary_stem(self, primary_stem: str):

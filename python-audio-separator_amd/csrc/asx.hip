@@ -2475,6 +2475,15 @@ int asx_ensemble_slot_dev(asx_engine *e, const float *stem_dev, int64_t n, int32
   return ASX_OK;
 }
 
+int asx_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int32_t n_jobs, int32_t algorithm, const double *weights, int32_t n_weights,
+                           int32_t mode, float max_peak, float min_peak, int32_t has_min, double silent_below, void *stream) {
+  REQUIRE(e, "asx_ensemble_batch_dev: null engine");
+  static_assert(ASX_ENS_MAX_K == ENS_MAX_K && ASX_ENS_MAX_K == ENS_PLAN_MAX_K && ASX_ENS_MAX_JOBS == ENS_PLAN_MAX_JOBS, "asx.h and the plan disagree");
+  HIPCHK(hipSetDevice(e->device));
+  return ens_ensemble_batch_dev(e, jobs, n_jobs, algorithm, weights, n_weights, mode, max_peak, min_peak, has_min, silent_below,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
 int asx_invert_stem(asx_engine *e, const float *mix_host, const float *stem_host, int64_t N, float *out_host, int64_t *n_out) {
   REQUIRE(e && mix_host && stem_host && out_host && n_out && N >= 1, "asx_invert_stem: bad argument");
   HIPCHK(hipSetDevice(e->device));

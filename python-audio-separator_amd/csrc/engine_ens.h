@@ -1,14 +1,47 @@
 // Spectral edges: Ensembler.ensemble and spec_utils.invert_stem on the engine (kernels_ens.h).  Included by asx.hip.
 #pragma once
+#include "ens_pool_plan.h"
+
+// pinned host staging of the pooled call's tables: what an asynchronous copy reads must stay put until the copy has run
+struct PinBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  int ensure(size_t n) {
+    if (n <= bytes) return ASX_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+    HIPCHK(hipHostMalloc(&p, n, hipHostMallocDefault));
+    bytes = n;
+    return ASX_OK;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+};
 
 struct EnsCtx {
   FftPlan plan{};
   DevBuf window, tw, frames, wss, dweights, din, din2, dout, partial, sel;
+  // asx_ensemble_batch_dev: contributor table, peaks, job table, ensemble_wav's sums and choices; their host staging and the event
+  // behind the last copy out of it
+  DevBuf psrcs, ppeaks, pjobs, ppartial, psel;
+  PinBuf stage;
+  hipEvent_t staged = nullptr;
   bool ready = false;
 };
 
 static void ens_destroy(EnsCtx *c) {
-  for (DevBuf *b : {&c->window, &c->tw, &c->frames, &c->wss, &c->dweights, &c->din, &c->din2, &c->dout, &c->partial, &c->sel}) b->release();
+  for (DevBuf *b : {&c->window, &c->tw, &c->frames, &c->wss, &c->dweights, &c->din, &c->din2, &c->dout, &c->partial, &c->sel, &c->psrcs,
+                    &c->ppeaks, &c->pjobs, &c->ppartial, &c->psel})
+    b->release();
+  if (c->staged) {
+    (void)hipEventSynchronize(c->staged);
+    (void)hipEventDestroy(c->staged);
+  }
+  c->stage.release();
   delete c;
 }
 
@@ -33,6 +66,7 @@ static int ens_ctx(asx_engine *e) {
   // Per engine (= per device), so not through the process-wide grant_lds record.
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ens_fft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ens_invert_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ens_pool_fft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   c.ready = true;
   return ASX_OK;
 }
@@ -124,4 +158,154 @@ static int ens_invert_dev(asx_engine *e, const float *mix, const float *stem, in
   }));
   *n_out = (int64_t)hop * (T - 1);
   return ens_fold(e, T, *n_out, out, s);
+}
+
+// ---- a pool of (file, stem group) jobs ------------------------------------------------------------------------------------
+// What EnsembleSeparator's per-file loop does per job with asx_ensemble_slot_dev and asx_ensemble_dev, for all jobs at once: one
+// launch for the peaks of all contributors, one copy and one wait for them, the live sets and the plan on the host
+// (ens_pool_plan.h), one table upload, then one launch per stage (kernels_ens.h).  Nothing is launched before every argument has
+// been checked.
+static float ens_peak_after(float maxv, int mode, float max_peak, float min_peak, int has_min) {   // asx_ensemble_slot_dev's report
+  float scale = 1.0f;
+  if (mode == ASX_SLOT_PCM16) {
+    if (maxv > max_peak) scale = max_peak / maxv;
+    else if (has_min && maxv < min_peak) scale = min_peak / maxv;
+  }
+  return maxv * scale;
+}
+
+static int ens_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int n_jobs, int alg, const double *weights, int n_weights, int mode,
+                                  float max_peak, float min_peak, int has_min, double silent_below, hipStream_t s) {
+  const char *fn = "asx_ensemble_batch_dev";
+  REQUIRE(n_jobs >= 0 && (jobs || n_jobs == 0), "%s: bad argument (jobs %p, n_jobs %d)", fn, (void *)jobs, n_jobs);
+  REQUIRE(mode == ASX_SLOT_PCM16 || mode == ASX_SLOT_FLOAT32, "%s: mode %d (0 pcm16 round trip, 1 float32 copy)", fn, mode);
+  REQUIRE(n_weights >= 0 && n_weights <= ENS_MAX_K && (weights || n_weights == 0), "%s: %d weights (0 .. %d)", fn, n_weights, ENS_MAX_K);
+  std::vector<EnsPlanJobIn> in((size_t)n_jobs);
+  int total_src = 0;
+  int64_t longest = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    in[j].k = jobs[j].k;
+    for (int c = 0; c < ENS_MAX_K && c < jobs[j].k; ++c) in[j].n[c] = jobs[j].n_samples[c];
+  }
+  const std::string why = ens_pool_check(in.data(), n_jobs, alg);
+  REQUIRE(why.empty(), "%s: %s", fn, why.c_str());
+  for (int j = 0; j < n_jobs; ++j) {
+    const asx_ens_job &jb = jobs[j];
+    int64_t n_job = 0;
+    for (int c = 0; c < jb.k; ++c) {
+      REQUIRE(jb.stem_dev[c] || jb.n_samples[c] == 0, "%s: job %d: contributor %d has a null stem with n = %lld", fn, j, c, (long long)jb.n_samples[c]);
+      REQUIRE(jb.layout[c] == ASX_STEM_PLANAR || jb.layout[c] == ASX_STEM_ROWS, "%s: job %d: contributor %d has layout %d (0 planar [2, n], 1 rows [n, 2])",
+              fn, j, c, (int)jb.layout[c]);
+      n_job = std::max<int64_t>(n_job, jb.n_samples[c]);
+    }
+    REQUIRE(jb.out_dev, "%s: job %d: null output", fn, j);
+    REQUIRE(jb.out_capacity >= n_job, "%s: job %d: output capacity %lld below its longest contributor (%lld)", fn, j, (long long)jb.out_capacity,
+            (long long)n_job);
+    total_src += jb.k;
+    longest = std::max(longest, n_job);
+  }
+  if (n_jobs == 0) return ASX_OK;
+  CHK(ens_ctx(e));
+  EnsCtx &c = *e->ens;
+
+  // ---- peaks ------------------------------------------------------------------------------------------------------------
+  const size_t src_bytes = (size_t)total_src * sizeof(EnsPoolSrc), peak_bytes = (size_t)total_src * 4, job_bytes = (size_t)n_jobs * sizeof(EnsPoolJob);
+  if (c.staged) HIPCHK(hipEventSynchronize(c.staged));   // the last call's copies out of the staging area have run
+  else HIPCHK(hipEventCreateWithFlags(&c.staged, hipEventDisableTiming));
+  CHK(c.stage.ensure(src_bytes + peak_bytes + job_bytes));
+  CHK(c.psrcs.ensure(src_bytes));
+  CHK(c.ppeaks.ensure(peak_bytes));
+  CHK(c.pjobs.ensure(job_bytes));
+  EnsPoolSrc *h_src = reinterpret_cast<EnsPoolSrc *>(c.stage.p);
+  EnsPoolJob *h_job = reinterpret_cast<EnsPoolJob *>(reinterpret_cast<char *>(c.stage.p) + src_bytes);   // (multiples of 8 bytes before it)
+  unsigned int *h_peak = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(c.stage.p) + src_bytes + job_bytes);
+  std::vector<int> first_src((size_t)n_jobs);
+  for (int j = 0, q = 0; j < n_jobs; ++j) {
+    first_src[j] = q;
+    for (int k = 0; k < jobs[j].k; ++k, ++q) h_src[q] = EnsPoolSrc{jobs[j].stem_dev[k], jobs[j].n_samples[k], (int32_t)(jobs[j].layout[k] == ASX_STEM_ROWS), q};
+  }
+  unsigned int *d_peak = reinterpret_cast<unsigned int *>(c.ppeaks.p);
+  HIPCHK(hipMemcpyAsync(c.psrcs.p, h_src, src_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(d_peak, 0, peak_bytes, s));
+  if (longest > 0) {
+    const unsigned nb = (unsigned)std::min<int64_t>((2 * longest + 255) / 256, 2048);
+    CHK(timed(e, ASX_PROF_MISC, 0.0, 0.0, s, [&]() {
+      hipLaunchKernelGGL(ens_pool_peak_kernel, dim3(nb, (unsigned)total_src), dim3(256), 0, s, reinterpret_cast<const EnsPoolSrc *>(c.psrcs.p), d_peak);
+    }));
+  }
+  HIPCHK(hipMemcpyAsync(h_peak, d_peak, peak_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+
+  // ---- live sets, plan, job table ---------------------------------------------------------------------------------------------
+  for (int j = 0; j < n_jobs; ++j)
+    for (int k = 0; k < jobs[j].k; ++k) {
+      float maxv;
+      memcpy(&maxv, &h_peak[first_src[j] + k], 4);
+      in[j].peak_after[k] = jobs[j].peak_after[k] = ens_peak_after(maxv, mode, max_peak, min_peak, has_min);
+    }
+  EnsPoolPlan pp;
+  ens_pool_build(in.data(), n_jobs, alg, silent_below, pp);
+  REQUIRE(pp.wave_blocks < ((int64_t)1 << 31) && pp.frames < ((int64_t)1 << 31) && pp.fold_blocks < ((int64_t)1 << 31),
+          "%s: the jobs of one call make %lld / %lld / %lld workgroups of a stage (2^31 - 1 at most)", fn, (long long)pp.wave_blocks,
+          (long long)pp.frames, (long long)pp.fold_blocks);
+  int k_spectral = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const EnsPlanJob &p = pp.job[j];
+    EnsPoolJob &d = h_job[j];
+    memset(&d, 0, sizeof(d));
+    const bool weighted = weights && n_weights == p.live;   // Ensembler.ensemble: a weights list of another length means equal weights
+    for (int k = 0; k < p.live; ++k) {
+      d.src[k] = h_src[first_src[j] + p.who[k]];
+      d.w[k] = weighted ? weights[k] : 1.0;
+      d.wsum += d.w[k];
+    }
+    d.out = jobs[j].out_dev;
+    d.n_max = p.n_max;
+    d.n_out = p.n_out;
+    d.wave_blk0 = p.wave_blk0;
+    d.fold_blk0 = p.fold_blk0;
+    d.frame0 = p.frame0;
+    d.K = p.live;
+    d.T = p.T;
+    d.pick = p.pick ? 1 : 0;
+    if (p.frames) k_spectral = std::max(k_spectral, p.live);
+    jobs[j].live = p.live;
+    jobs[j].n_out = p.n_out;
+  }
+  const int nf = c.plan.n_fft, nh = c.plan.nh, hop = ENS_PLAN_HOP;
+  if (pp.frames) CHK(c.frames.ensure((size_t)pp.frames * 2 * nf * 4));
+  if (pp.picks) {
+    CHK(c.ppartial.ensure((size_t)n_jobs * 2 * ENS_MAX_K * ENS_ABS_BLOCKS * 8));
+    CHK(c.psel.ensure((size_t)n_jobs * 2 * 4));
+  }
+  HIPCHK(hipMemcpyAsync(c.pjobs.p, h_job, job_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(c.staged, s));
+
+  // ---- one launch per stage ---------------------------------------------------------------------------------------------------
+  const EnsPoolJob *dj = reinterpret_cast<const EnsPoolJob *>(c.pjobs.p);
+  const EnsSlotEdge ed{d_peak, max_peak, min_peak, has_min, (int32_t)(mode == ASX_SLOT_PCM16)};
+  if (pp.picks)
+    CHK(timed(e, ASX_PROF_MISC, 0.0, 0.0, s, [&]() {
+      hipLaunchKernelGGL(ens_pool_abssum_kernel, dim3((unsigned)(ENS_ABS_BLOCKS * n_jobs), 2 * ENS_MAX_K), dim3(256), 0, s, dj, ed,
+                         reinterpret_cast<double *>(c.ppartial.p));
+      hipLaunchKernelGGL(ens_pool_pick_kernel, dim3((unsigned)n_jobs), dim3(64), 0, s, dj, reinterpret_cast<const double *>(c.ppartial.p),
+                         reinterpret_cast<int *>(c.psel.p));
+    }));
+  if (pp.wave_blocks)
+    CHK(timed(e, ASX_PROF_MISC, 0.0, 4.0 * 256 * pp.wave_blocks, s, [&]() {
+      hipLaunchKernelGGL(ens_pool_wave_kernel, dim3((unsigned)pp.wave_blocks), dim3(256), 0, s, dj, n_jobs, alg, ed, reinterpret_cast<const int *>(c.psel.p));
+    }));
+  if (pp.frames) {
+    const size_t lds = ((size_t)nh * 2 + (size_t)(nh + 1) * (2 + (alg == ENS_MEDIAN_FFT ? k_spectral : 0))) * sizeof(float2);
+    CHK(timed(e, ASX_PROF_STFT, 0.0, 4.0 * 2.0 * pp.frames * nf, s, [&]() {
+      hipLaunchKernelGGL(ens_pool_fft_kernel, dim3((unsigned)pp.frames, 2), dim3(256), lds, s, dj, n_jobs, alg, hop, ed, c.frames.f(), c.window.f(),
+                         reinterpret_cast<const float2 *>(c.tw.p), c.plan);
+    }));
+    if (pp.fold_blocks)
+      CHK(timed(e, ASX_PROF_OLA, 0.0, 4.0 * 2.0 * pp.frames * nf, s, [&]() {
+        hipLaunchKernelGGL(ens_pool_fold_kernel, dim3((unsigned)pp.fold_blocks), dim3(256), 0, s, dj, n_jobs, (const float *)c.frames.f(), (const float *)c.window.f(),
+                           nf, hop);
+      }));
+  }
+  return ASX_OK;
 }

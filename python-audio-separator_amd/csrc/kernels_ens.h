@@ -26,41 +26,47 @@ __device__ __forceinline__ float median_small(float *v, int K) {
   return (K & 1) ? v[K / 2] : (v[K / 2 - 1] + v[K / 2]) / 2.0f;   // np.median: mean of the two middle values
 }
 
-// avg / median / min / max over K waveforms [K, 2, N] (ensembler.py:48-64); weights only for avg
+// avg / median / min / max of one sample over K waveforms (ensembler.py:48-64); weights only for avg.  ld(k): the sample of input k.
+template <class Load>
+__device__ __forceinline__ float ens_wave_combine(Load ld, int K, int alg, const double *__restrict__ weights, double wsum) {
+  if (alg == ENS_AVG_WAVE) {
+    float acc = 0.f;   // `ensembled += w * weight` rounds to float32 after every term (float64 product)
+    for (int k = 0; k < K; ++k) acc = (float)((double)acc + (double)ld(k) * weights[k]);
+    return (float)((double)acc / wsum);
+  }
+  if (alg == ENS_MEDIAN_WAVE) {
+    float v[ENS_MAX_K];
+    for (int k = 0; k < K; ++k) v[k] = ld(k);
+    return median_small(v, K);
+  }
+  float best = ld(0), bm = fabsf(best);
+  for (int k = 1; k < K; ++k) {   // np.argmin / np.argmax: the first extremum wins
+    const float x = ld(k), m = fabsf(x);
+    if (alg == ENS_MIN_WAVE ? m < bm : m > bm) {
+      best = x;
+      bm = m;
+    }
+  }
+  return best;
+}
+
+// the same over a stack [K, 2, N]
 __global__ __launch_bounds__(256) void ens_wave_kernel(const float *__restrict__ waves, int K, int64_t n2, int alg,
                                                        const double *__restrict__ weights, double wsum, float *__restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n2) return;
-  if (alg == ENS_AVG_WAVE) {
-    float acc = 0.f;   // `ensembled += w * weight` rounds to float32 after every term (float64 product)
-    for (int k = 0; k < K; ++k) acc = (float)((double)acc + (double)waves[(int64_t)k * n2 + i] * weights[k]);
-    out[i] = (float)((double)acc / wsum);
-  } else if (alg == ENS_MEDIAN_WAVE) {
-    float v[ENS_MAX_K];
-    for (int k = 0; k < K; ++k) v[k] = waves[(int64_t)k * n2 + i];
-    out[i] = median_small(v, K);
-  } else {
-    float best = waves[i], bm = fabsf(best);
-    for (int k = 1; k < K; ++k) {   // np.argmin / np.argmax: the first extremum wins
-      const float x = waves[(int64_t)k * n2 + i], m = fabsf(x);
-      if (alg == ENS_MIN_WAVE ? m < bm : m > bm) {
-        best = x;
-        bm = m;
-      }
-    }
-    out[i] = best;
-  }
+  out[i] = ens_wave_combine([&](int k) { return waves[(int64_t)k * n2 + i]; }, K, alg, weights, wsum);
 }
 
 // spec_utils.ensemble_wav as Ensembler.ensemble calls it (uvr_lib_v5/spec_utils.py:1245-1266, ensembler.py:71-72): every channel
 // is taken whole from the input whose mean |x| over that channel is smallest (np.array_split along axis 0 of a [2, N] array:
 // section c < 2 is channel c, the other 238 sections are empty).  Three deterministic steps: partial sums of |x| in float64
 // (fixed strided order per block), the argmin per channel (first minimum; a NaN sum wins like in np.argmin), the row copy.
-__global__ __launch_bounds__(256) void ens_abssum_kernel(const float *__restrict__ waves, int64_t N, double *__restrict__ partial) {
-  const int kc = blockIdx.y;                        // input * 2 + channel
-  const float *x = waves + (int64_t)kc * N;
+// block `bx` of `gx` over one channel of one input: its strided share of sum |x| in float64, reduced in a fixed tree.  ld(i): sample i.
+template <class Load>
+__device__ __forceinline__ void ens_abssum_block(Load ld, int64_t N, int bx, int gx, double *__restrict__ dst) {
   double acc = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) acc += (double)fabsf(x[i]);
+  for (int64_t i = (int64_t)bx * 256 + threadIdx.x; i < N; i += (int64_t)gx * 256) acc += (double)fabsf(ld(i));
   __shared__ double sh[256];
   sh[threadIdx.x] = acc;
   __syncthreads();
@@ -68,11 +74,15 @@ __global__ __launch_bounds__(256) void ens_abssum_kernel(const float *__restrict
     if ((int)threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
     __syncthreads();
   }
-  if (threadIdx.x == 0) partial[(int64_t)kc * gridDim.x + blockIdx.x] = sh[0];
+  if (threadIdx.x == 0) *dst = sh[0];
 }
-__global__ void ens_pick_kernel(const double *__restrict__ partial, int K, int P, int *__restrict__ sel) {
-  const int ch = threadIdx.x;
-  if (ch >= 2) return;
+__global__ __launch_bounds__(256) void ens_abssum_kernel(const float *__restrict__ waves, int64_t N, double *__restrict__ partial) {
+  const int kc = blockIdx.y;                        // input * 2 + channel
+  const float *x = waves + (int64_t)kc * N;
+  ens_abssum_block([&](int64_t i) { return x[i]; }, N, (int)blockIdx.x, (int)gridDim.x, partial + (int64_t)kc * gridDim.x + blockIdx.x);
+}
+// partial [K, 2, P] -> the input channel `ch` is taken from
+__device__ __forceinline__ int ens_pick_channel(const double *__restrict__ partial, int K, int P, int ch) {
   int best = 0;
   double bt = 0.0;
   for (int k = 0; k < K; ++k) {
@@ -85,7 +95,12 @@ __global__ void ens_pick_kernel(const double *__restrict__ partial, int K, int P
       bt = t;
     }
   }
-  sel[ch] = best;
+  return best;
+}
+__global__ void ens_pick_kernel(const double *__restrict__ partial, int K, int P, int *__restrict__ sel) {
+  const int ch = threadIdx.x;
+  if (ch >= 2) return;
+  sel[ch] = ens_pick_channel(partial, K, P, ch);
 }
 __global__ __launch_bounds__(256) void ens_take_kernel(const float *__restrict__ waves, int64_t N, const int *__restrict__ sel,
                                                        float *__restrict__ out) {
@@ -101,48 +116,47 @@ __global__ __launch_bounds__(256) void ens_take_kernel(const float *__restrict__
 // pcm16_kernel's, operation for operation (float32, one rounding each, C truncation), so slot * 32768 IS the int16 that
 // kernel writes; int16 -> float and the division by 2^15 are exact.  quantise == 0: plain copy (+ transpose) and pad.
 // Every element of the slot is written: the stack needs no clearing.
+__device__ __forceinline__ float ens_slot_quantise(float x, float maxv, float max_peak, float min_peak, int has_min) {
+#pragma clang fp contract(off)
+  float scale = 1.0f;
+  bool scaled = false;
+  if (maxv > max_peak) {
+    scale = __fdiv_rn(max_peak, maxv);
+    scaled = true;
+  } else if (has_min && maxv < min_peak) {
+    scale = __fdiv_rn(min_peak, maxv);
+    scaled = true;
+  }
+  if (scaled) x = x * scale;
+  const float q = x * 32767.0f;
+  return (float)(short)(int)q * (1.0f / 32768.0f);
+}
+// sample i of channel ch of a stem of n samples as its slot holds it (zero from n on)
+__device__ __forceinline__ float ens_slot_value(const float *__restrict__ stem, int64_t n, int rows, int ch, int64_t i, float maxv,
+                                                float max_peak, float min_peak, int has_min, int quantise) {
+  if (i >= n) return 0.f;
+  const float x = rows ? stem[2 * i + ch] : stem[(int64_t)ch * n + i];
+  return quantise ? ens_slot_quantise(x, maxv, max_peak, min_peak, has_min) : x;
+}
 __global__ __launch_bounds__(256) void ens_slot_kernel(const float *__restrict__ stem, int64_t n, int rows,
                                                        const unsigned int *peak_bits, float max_peak, float min_peak, int has_min,
                                                        int quantise, float *__restrict__ slot, int64_t n_max) {
-#pragma clang fp contract(off)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_max) return;
-  float l = 0.f, r = 0.f;
-  if (i < n) {
-    l = rows ? stem[2 * i] : stem[i];
-    r = rows ? stem[2 * i + 1] : stem[n + i];
-    if (quantise) {
-      const float maxv = __uint_as_float(*peak_bits);
-      float scale = 1.0f;
-      bool scaled = false;
-      if (maxv > max_peak) {
-        scale = __fdiv_rn(max_peak, maxv);
-        scaled = true;
-      } else if (has_min && maxv < min_peak) {
-        scale = __fdiv_rn(min_peak, maxv);
-        scaled = true;
-      }
-      if (scaled) {
-        l = l * scale;
-        r = r * scale;
-      }
-      const float lq = l * 32767.0f, rq = r * 32767.0f;
-      l = (float)(short)(int)lq * (1.0f / 32768.0f);
-      r = (float)(short)(int)rq * (1.0f / 32768.0f);
-    }
-  }
-  slot[i] = l;
-  slot[n_max + i] = r;
+  const float maxv = (quantise && i < n) ? __uint_as_float(*peak_bits) : 0.f;
+  slot[i] = ens_slot_value(stem, n, rows, 0, i, maxv, max_peak, min_peak, has_min, quantise);
+  slot[n_max + i] = ens_slot_value(stem, n, rows, 1, i, maxv, max_peak, min_peak, has_min, quantise);
 }
 
-// librosa.stft frame t of channel ch of wave [2, n] (centre, zero padding) -> X[0 .. nh] in LDS
-__device__ __forceinline__ void ens_frame_spectrum(const float *__restrict__ wave, int64_t n, int ch, int t, int hop,
-                                                   const float *__restrict__ window, const float2 *__restrict__ tw,
-                                                   const FftPlan &p, float2 *bufA, float2 *bufB, float2 *X) {
+// librosa.stft frame t of one channel of n samples (centre, zero padding) -> X[0 .. nh] in LDS.  ld(q): sample q, 0 <= q < n.
+template <class Load>
+__device__ __forceinline__ void ens_frame_spectrum_of(Load ld, int64_t n, int t, int hop, const float *__restrict__ window,
+                                                      const float2 *__restrict__ tw, const FftPlan &p, float2 *bufA, float2 *bufB,
+                                                      float2 *X) {
   float *fa = reinterpret_cast<float *>(bufA);
   for (int e = threadIdx.x; e < p.n_fft; e += blockDim.x) {
     const int64_t q = (int64_t)t * hop + e - p.nh;
-    fa[e] = (q >= 0 && q < n) ? wave[(int64_t)ch * n + q] * window[e] : 0.f;
+    fa[e] = (q >= 0 && q < n) ? ld(q) * window[e] : 0.f;
   }
   float2 *Z = fft_lds<-1>(bufA, bufB, p, tw);
   const int nh = p.nh;
@@ -157,6 +171,13 @@ __device__ __forceinline__ void ens_frame_spectrum(const float *__restrict__ wav
     X[k] = cadd(E, cmul(w, O));
   }
   __syncthreads();
+}
+// the same for channel ch of a wave [2, n] in memory
+__device__ __forceinline__ void ens_frame_spectrum(const float *__restrict__ wave, int64_t n, int ch, int t, int hop,
+                                                   const float *__restrict__ window, const float2 *__restrict__ tw,
+                                                   const FftPlan &p, float2 *bufA, float2 *bufB, float2 *X) {
+  const float *x = wave + (int64_t)ch * n;
+  ens_frame_spectrum_of([&](int64_t q) { return x[q]; }, n, t, hop, window, tw, p, bufA, bufB, X);
 }
 
 // X[0 .. nh] in LDS -> windowed inverse frame (librosa.istft's ytmp), scaled by `sign`
@@ -191,19 +212,18 @@ __device__ __forceinline__ void ens_inverse_frame(float2 *X, float *__restrict__
   }
 }
 
-// *_fft and uvr_*_spec ensembles (ensembler.py:120-156, spec_utils.ensembling :583-607): grid = (T, 2).
-// LDS: bufA, bufB (nh each), cur (nh+1), sel (nh+1), and for the median K * (nh+1) spectra.
-__global__ __launch_bounds__(256) void ens_fft_kernel(const float *__restrict__ waves, int K, int64_t n, int alg,
-                                                      const double *__restrict__ weights, double wsum, int hop,
-                                                      float *__restrict__ frames, const float *__restrict__ window,
-                                                      const float2 *__restrict__ tw, FftPlan p) {
-  extern __shared__ float2 lds[];
+// *_fft and uvr_*_spec ensembles (ensembler.py:120-156, spec_utils.ensembling :583-607) for frame t of channel ch: the K input
+// frames are transformed, combined per bin in LDS and inverse-transformed into frames[ch, t, :] of a [2, T, n_fft] buffer.
+// ld(k, q): sample q of that channel of input k.  LDS: bufA, bufB (nh each), cur (nh+1), sel (nh+1), and for the median K * (nh+1) spectra.
+template <class Load>
+__device__ __forceinline__ void ens_fft_frame(Load ld, int K, int64_t n, int alg, const double *__restrict__ weights, double wsum, int hop,
+                                              int t, int ch, int T, float *__restrict__ frames, const float *__restrict__ window,
+                                              const float2 *__restrict__ tw, const FftPlan &p, float2 *lds) {
   const int nh = p.nh;
   float2 *bufA = lds, *bufB = lds + nh, *cur = lds + 2 * nh, *sel = cur + (nh + 1), *all = sel + (nh + 1);
-  const int t = blockIdx.x, ch = blockIdx.y, T = gridDim.x;
   for (int k = 0; k < K; ++k) {
     float2 *dst = (alg == ENS_MEDIAN_FFT) ? all + (size_t)k * (nh + 1) : cur;
-    ens_frame_spectrum(waves + (int64_t)k * 2 * n, n, ch, t, hop, window, tw, p, bufA, bufB, dst);
+    ens_frame_spectrum_of([&](int64_t q) { return ld(k, q); }, n, t, hop, window, tw, p, bufA, bufB, dst);
     if (alg == ENS_MEDIAN_FFT) continue;
     for (int b = threadIdx.x; b <= nh; b += blockDim.x) {
       const float2 x = cur[b];
@@ -248,6 +268,17 @@ __global__ __launch_bounds__(256) void ens_fft_kernel(const float *__restrict__ 
   ens_inverse_frame(sel, frames + ((int64_t)ch * T + t) * p.n_fft, window, tw, p, bufA, bufB, 1.0f);
 }
 
+// over a stack [K, 2, n]: grid = (T, 2)
+__global__ __launch_bounds__(256) void ens_fft_kernel(const float *__restrict__ waves, int K, int64_t n, int alg,
+                                                      const double *__restrict__ weights, double wsum, int hop,
+                                                      float *__restrict__ frames, const float *__restrict__ window,
+                                                      const float2 *__restrict__ tw, FftPlan p) {
+  extern __shared__ float2 lds[];
+  const int ch = blockIdx.y;
+  ens_fft_frame([&](int k, int64_t q) { return waves[((int64_t)k * 2 + ch) * n + q]; }, K, n, alg, weights, wsum, hop, (int)blockIdx.x, ch,
+                (int)gridDim.x, frames, window, tw, p, lds);
+}
+
 // invert_audio (spec_utils.py:557-571): v = Y - max(|X|, |Y|) * exp(j angle(X)); invert_stem returns -istft(v)
 __global__ __launch_bounds__(256) void ens_invert_kernel(const float *__restrict__ mix, const float *__restrict__ stem, int64_t n,
                                                          int hop, float *__restrict__ frames, const float *__restrict__ window,
@@ -267,6 +298,126 @@ __global__ __launch_bounds__(256) void ens_invert_kernel(const float *__restrict
   }
   __syncthreads();
   ens_inverse_frame(Y, frames + ((int64_t)ch * T + t) * p.n_fft, window, tw, p, bufA, bufB, -1.0f);
+}
+
+// ---- a pool of (file, stem group) jobs: asx_ensemble_batch_dev ---------------------------------------------------------------
+// Every stage of the combine is ONE launch over all jobs: a workgroup finds its job in the job table (its first workgroup / first
+// frame in that launch's grid, ascending; a job that takes no part in a stage owns no workgroups there) and then runs the device
+// functions above -- the ones the single-job kernels run.  No [K, 2, n_max] stack exists: a contributor's sample is read from
+// the member's stem and goes through ens_slot_value, the function ens_slot_kernel stores the stack with, so what a combine
+// reads is the float that kernel would have stored and a load would have returned (a float32 store and load change no bit, and
+// no arithmetic of the combine can be contracted with the quantiser's: its last operation is a multiplication whose result is
+// only ever multiplied, converted or compared next).
+struct EnsPoolSrc {
+  const float *stem;   // planar [2, n] or rows [n, 2]
+  int64_t n;
+  int32_t rows;
+  int32_t peak;        // its word of the peak array
+};
+struct EnsPoolJob {
+  EnsPoolSrc src[ENS_MAX_K];   // the contributors that take part, in order
+  double w[ENS_MAX_K];         // their weights (avg_*)
+  double wsum;
+  float *out;                  // planar [2, n_out]
+  int64_t n_max, n_out;
+  int64_t wave_blk0, fold_blk0, frame0;
+  int32_t K, T, pick, pad_;
+};
+struct EnsSlotEdge {           // the member -> Ensembler edge of the call
+  const unsigned int *peaks;   // max |stem| of every contributor, float bits
+  float max_peak, min_peak;
+  int32_t has_min, quantise;
+};
+
+__device__ __forceinline__ float ens_pool_load(const EnsPoolSrc &s, const EnsSlotEdge &ed, int ch, int64_t i) {
+  const float maxv = (ed.quantise && i < s.n) ? __uint_as_float(ed.peaks[s.peak]) : 0.f;
+  return ens_slot_value(s.stem, s.n, s.rows, ch, i, maxv, ed.max_peak, ed.min_peak, ed.has_min, ed.quantise);
+}
+
+// the last job whose first workgroup (or frame) of this stage is <= x
+template <int64_t EnsPoolJob::*FIRST>
+__device__ __forceinline__ int ens_pool_find(const EnsPoolJob *__restrict__ jobs, int n_jobs, int64_t x) {
+  int lo = 0, hi = n_jobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].*FIRST <= x) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// max |x| of every contributor of every job: grid = (workgroups per contributor, contributors); peaks cleared before
+__global__ __launch_bounds__(256) void ens_pool_peak_kernel(const EnsPoolSrc *__restrict__ srcs, unsigned int *__restrict__ peaks) {
+  const EnsPoolSrc s = srcs[blockIdx.y];
+  if ((int64_t)blockIdx.x * 256 >= 2 * s.n) return;   // (the whole workgroup: nothing of this stem is in its share)
+  absmax_block(s.stem, 2 * s.n, blockIdx.x, gridDim.x, peaks + s.peak);
+}
+
+// results formed per sample: the wave algorithms, ensemble_wav's row copy (sel [n_jobs, 2]) and a lone contributor's slot image
+__global__ __launch_bounds__(256) void ens_pool_wave_kernel(const EnsPoolJob *__restrict__ jobs, int n_jobs, int alg, EnsSlotEdge ed,
+                                                            const int *__restrict__ sel) {
+  const int j = ens_pool_find<&EnsPoolJob::wave_blk0>(jobs, n_jobs, blockIdx.x);
+  const EnsPoolJob &jb = jobs[j];
+  const int64_t N = jb.n_out;
+  const int64_t i = ((int64_t)blockIdx.x - jb.wave_blk0) * 256 + threadIdx.x;
+  if (i >= 2 * N) return;
+  const int ch = i >= N ? 1 : 0;
+  const int64_t q = i - (int64_t)ch * N;
+  float v;
+  if (jb.K == 1) v = ens_pool_load(jb.src[0], ed, ch, q);
+  else if (alg == ENS_ENSEMBLE_WAV) v = ens_pool_load(jb.src[sel[2 * j + ch]], ed, ch, q);
+  else v = ens_wave_combine([&](int k) { return ens_pool_load(jb.src[k], ed, ch, q); }, jb.K, alg, jb.w, jb.wsum);
+  jb.out[i] = v;
+}
+
+// ensemble_wav, steps 1 and 2.  grid = (ENS_ABS_BLOCKS * n_jobs, 2 * ENS_MAX_K): the single call's ENS_ABS_BLOCKS strided partial sums
+// per (input, channel) of every job, partial [n_jobs, 2 * ENS_MAX_K, ENS_ABS_BLOCKS]; then one workgroup per job.
+__global__ __launch_bounds__(256) void ens_pool_abssum_kernel(const EnsPoolJob *__restrict__ jobs, EnsSlotEdge ed, double *__restrict__ partial) {
+  const int j = blockIdx.x / ENS_ABS_BLOCKS, bx = blockIdx.x % ENS_ABS_BLOCKS, kc = blockIdx.y;
+  const EnsPoolJob &jb = jobs[j];
+  if (!jb.pick || kc >= 2 * jb.K) return;
+  const int k = kc >> 1, ch = kc & 1;
+  ens_abssum_block([&](int64_t i) { return ens_pool_load(jb.src[k], ed, ch, i); }, jb.n_max, bx, ENS_ABS_BLOCKS,
+                   partial + ((int64_t)j * 2 * ENS_MAX_K + kc) * ENS_ABS_BLOCKS + bx);
+}
+__global__ void ens_pool_pick_kernel(const EnsPoolJob *__restrict__ jobs, const double *__restrict__ partial, int *__restrict__ sel) {
+  const int j = blockIdx.x, ch = threadIdx.x;
+  if (ch >= 2 || !jobs[j].pick) return;
+  sel[2 * j + ch] = ens_pick_channel(partial + (int64_t)j * 2 * ENS_MAX_K * ENS_ABS_BLOCKS, jobs[j].K, ENS_ABS_BLOCKS, ch);
+}
+
+// *_fft and uvr_*_spec: grid = (frames of all jobs, 2); job j's inverse frames are [2, T_j, n_fft] from frame0_j * 2 * n_fft of `frames`
+__global__ __launch_bounds__(256) void ens_pool_fft_kernel(const EnsPoolJob *__restrict__ jobs, int n_jobs, int alg, int hop, EnsSlotEdge ed,
+                                                           float *__restrict__ frames, const float *__restrict__ window,
+                                                           const float2 *__restrict__ tw, FftPlan p) {
+  extern __shared__ float2 lds[];
+  const EnsPoolJob &jb = jobs[ens_pool_find<&EnsPoolJob::frame0>(jobs, n_jobs, blockIdx.x)];
+  const int t = (int)((int64_t)blockIdx.x - jb.frame0), ch = blockIdx.y;
+  ens_fft_frame([&](int k, int64_t q) { return ens_pool_load(jb.src[k], ed, ch, q); }, jb.K, jb.n_max, alg, jb.w, jb.wsum, hop, t, ch, jb.T,
+                frames + jb.frame0 * 2 * p.n_fft, window, tw, p, lds);
+}
+
+// librosa.istft's fold of every job's frames (vr_ola_kernel's sums) with the window-sum-square formed here: position m is covered by
+// at most n_fft / hop frames; their squared window values are added in float64 in ascending frame order and rounded to float32
+// once -- the value the single call's host table holds there (0 where no frame reaches).
+__global__ __launch_bounds__(256) void ens_pool_fold_kernel(const EnsPoolJob *__restrict__ jobs, int n_jobs, const float *__restrict__ frames,
+                                                            const float *__restrict__ window, int n_fft, int hop) {
+  const EnsPoolJob &jb = jobs[ens_pool_find<&EnsPoolJob::fold_blk0>(jobs, n_jobs, blockIdx.x)];
+  const int64_t len = jb.n_out;
+  const int64_t i = ((int64_t)blockIdx.x - jb.fold_blk0) * 256 + threadIdx.x;
+  if (i >= len) return;
+  const int64_t m = i + n_fft / 2;
+  int64_t t_lo, t_hi;
+  ola_frame_range(m, n_fft, hop, jb.T, &t_lo, &t_hi);
+  double ss = 0.0;
+  for (int64_t t = t_lo; t <= t_hi; ++t) {
+    const double w = (double)window[m - t * hop];
+    ss += w * w;
+  }
+  const float s = (float)ss;
+  const float *fr = frames + jb.frame0 * 2 * n_fft;
+  jb.out[i] = ola_sample(fr, n_fft, hop, m, t_lo, t_hi, s);
+  jb.out[len + i] = ola_sample(fr + (int64_t)jb.T * n_fft, n_fft, hop, m, t_lo, t_hi, s);
 }
 
 }  // namespace asx

@@ -582,9 +582,10 @@ __global__ __launch_bounds__(256) void finalize_pool_kernel(const PoolSong *__re
 //   secondary[i, ch] = (-primary[i, ch] * compensate) + mix[ch, i]             mdx_separator.py:182
 // All arithmetic is float32 with one rounding per operation (numpy semantics; no fma contraction).
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ x, int64_t n, unsigned int *peak_bits) {
+// workgroup `bx` of `gx` over x[0 .. n): its strided share of max |x| into *peak_bits
+__device__ __forceinline__ void absmax_block(const float *__restrict__ x, int64_t n, unsigned bx, unsigned gx, unsigned int *peak_bits) {
   float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+  for (int64_t i = (int64_t)bx * blockDim.x + threadIdx.x; i < n; i += (int64_t)gx * blockDim.x)
     m = fmaxf(m, fabsf(x[i]));
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
@@ -595,6 +596,9 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ x
     m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
     atomicMax(peak_bits, __float_as_uint(m));   // non-negative floats order like their bit patterns
   }
+}
+__global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ x, int64_t n, unsigned int *peak_bits) {
+  absmax_block(x, n, blockIdx.x, gridDim.x, peak_bits);
 }
 
 __global__ __launch_bounds__(256) void normalize_kernel(float *__restrict__ x, int64_t n, const unsigned int *peak_bits,

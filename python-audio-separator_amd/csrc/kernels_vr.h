@@ -536,24 +536,29 @@ __global__ __launch_bounds__(256) void vr_istft_kernel(const float2 *__restrict_
 // librosa.istft fold: y[j] = sum_t frames[t][j + n/2 - t*hop] / wss[j + n/2], length hop*(T-1); wss = squared-window sum
 // over the T frames (computed on the host).  Then the channel conversion of spectrogram_to_wave (spec_utils.py:331-336)
 // and `wave = np.add(wave, ...)` with the lower bands' resampled sum (`lower`, may be null).  grid.x over samples.
+// the frames [t_lo, t_hi] of T that cover position m of the padded signal
+__device__ __forceinline__ void ola_frame_range(int64_t m, int n_fft, int hop, int T, int64_t *t_lo, int64_t *t_hi) {
+  *t_lo = (m - n_fft + hop) / hop;
+  if (m - n_fft + 1 <= 0) *t_lo = 0;
+  *t_hi = m / hop;
+  if (*t_hi > T - 1) *t_hi = T - 1;
+}
+// position m of one channel's frames [T, n_fft]: the covering frames added in ascending order, over the window-sum-square s there
+__device__ __forceinline__ float ola_sample(const float *__restrict__ fr, int n_fft, int hop, int64_t m, int64_t t_lo, int64_t t_hi, float s) {
+  float acc = 0.f;
+  for (int64_t t = t_lo; t <= t_hi; ++t) acc += fr[t * n_fft + (m - t * hop)];
+  return s > 1.17549435e-38f ? acc / s : acc;
+}
 __global__ __launch_bounds__(256) void vr_ola_kernel(const float *__restrict__ frames, const float *__restrict__ wss, int n_fft,
                                                      int hop, int T, int64_t len, int mode, const float *__restrict__ lower,
                                                      float *__restrict__ out) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= len) return;
   const int64_t m = j + n_fft / 2;
-  int64_t t_lo = (m - n_fft + hop) / hop;
-  if (m - n_fft + 1 <= 0) t_lo = 0;
-  int64_t t_hi = m / hop;
-  if (t_hi > T - 1) t_hi = T - 1;
+  int64_t t_lo, t_hi;
+  ola_frame_range(m, n_fft, hop, T, &t_lo, &t_hi);
   float a[2];
-  for (int ch = 0; ch < 2; ++ch) {
-    const float *fr = frames + (int64_t)ch * T * n_fft;
-    float acc = 0.f;
-    for (int64_t t = t_lo; t <= t_hi; ++t) acc += fr[t * n_fft + (m - t * hop)];
-    const float s = wss[m];
-    a[ch] = s > 1.17549435e-38f ? acc / s : acc;
-  }
+  for (int ch = 0; ch < 2; ++ch) a[ch] = ola_sample(frames + (int64_t)ch * T * n_fft, n_fft, hop, m, t_lo, t_hi, wss[m]);
   float l = a[0], r = a[1];
   int64_t jo = j;
   if (mode == 1) {

@@ -276,7 +276,7 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_profile_launches", "asx_debug_trace", "asx_resample_sinc", "asx_resample_sinc_dev", "asx_counter",
            "asx_set_stft_window", "asx_op_tdf_block", "asx_op_attention", "asx_op_mha", "asx_get_option",
            "asx_demix_batch_dev", "asx_separate_batch_dev", "asx_ensemble_slot_dev", "asx_vr_separate_batch_dev",
-           "asx_mdxc_demix_batch_dev", "asx_rof_demix_batch_dev"]
+           "asx_mdxc_demix_batch_dev", "asx_rof_demix_batch_dev", "asx_ensemble_batch_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -301,6 +301,15 @@ class _VrSong(C.Structure):        # struct asx_vr_song
 
 class _MdxcSong(C.Structure):      # struct asx_mdxc_song
     _fields_ = [("mix_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_samples", C.c_int64)]
+
+
+ENS_MAX_K = 8                      # ASX_ENS_MAX_K: contributors of one ensemble job
+
+
+class _EnsJob(C.Structure):        # struct asx_ens_job
+    _fields_ = [("k", C.c_int32), ("live", C.c_int32), ("stem_dev", C.c_void_p * ENS_MAX_K), ("n_samples", C.c_int64 * ENS_MAX_K),
+                ("layout", C.c_int32 * ENS_MAX_K), ("out_dev", C.c_void_p), ("out_capacity", C.c_int64), ("n_out", C.c_int64),
+                ("peak_after", C.c_float * ENS_MAX_K)]
 
 
 VR_POOL_SEGMENTS = 16              # ASX_VR_POOL_SEGMENTS: songs one gather / scatter launch of a pooled VR pass serves
@@ -405,6 +414,8 @@ def load_library():
     lib.asx_ensemble.argtypes = [vp, _FP, i32, i64, i32, C.POINTER(C.c_double), _FP, C.POINTER(i64)]
     lib.asx_ensemble_dev.argtypes = [vp, vp, i32, i64, i32, C.POINTER(C.c_double), vp, C.POINTER(i64), vp]
     lib.asx_invert_stem.argtypes = [vp, _FP, _FP, i64, _FP, C.POINTER(i64)]
+    lib.asx_ensemble_batch_dev.argtypes = [vp, C.POINTER(_EnsJob), i32, i32, C.POINTER(C.c_double), i32, i32, C.c_float, C.c_float, i32,
+                                           C.c_double, vp]
     lib.asx_ensemble_slot_dev.argtypes = [vp, vp, i64, i32, C.c_float, C.c_float, i32, i32, vp, i32, i64, _FP, vp]
     lib.asx_pcm16.argtypes = [vp, _FP, i64, C.c_float, C.c_float, i32, C.POINTER(C.c_int16), _FP]
     lib.asx_normalize.argtypes = [vp, _FP, i64, C.c_float, C.c_float, i32, _FP]
@@ -1139,6 +1150,36 @@ class Engine:
         self._check(self._lib.asx_ensemble_dev(self._h, stack_ptr or None, k, n_samples, self.ENSEMBLE_ALGORITHMS.index(algorithm), wt,
                                                out_ptr or None, C.byref(n_out), stream or None))
         return int(n_out.value)
+
+    def ensemble_batch_dev(self, jobs, algorithm, weights, max_peak: float, min_peak, silent_below: float = 1e-6, mode: str = "pcm16",
+                           stream: int = 0):
+        """asx_ensemble_batch_dev: the ensembles of many (file, stem group) jobs in one call.  ``jobs``: a list of
+        ``(contributors, out_ptr, out_capacity)`` with ``contributors`` = [(stem_ptr, n_samples, "planar" | "rows")], 1 .. 8 of them,
+        and ``out`` a device buffer of 2 * out_capacity floats, out_capacity >= the longest contributor.  Per job, bit for bit what
+        ``ensemble_slot_dev`` per contributor (dropping those whose peak is below ``silent_below`` and padding the rest to the
+        longest left) followed by ``ensemble_dev`` gives; a lone contributor left comes out as its slot image.  ``weights`` as
+        Ensembler.ensemble treats them: used by a job with exactly that many contributors left, equal weights otherwise.
+        Returns per job ``(n_out, live, [peak_after per contributor])``: ``out`` holds planar [2, n_out]; n_out == 0: no result,
+        nothing written.  Synchronises the stream once (for the peaks); the combine itself is only enqueued."""
+        if isinstance(algorithm, str):
+            if algorithm not in self.ENSEMBLE_ALGORITHMS:
+                raise ValueError(f"Unknown ensemble algorithm: {algorithm}")
+            algorithm = self.ENSEMBLE_ALGORITHMS.index(algorithm)
+        jobs = list(jobs)
+        w = self.ensemble_weights(weights, len(weights)) if weights is not None and 0 < len(weights) <= ENS_MAX_K else None
+        wt = (C.c_double * len(w))(*w) if w is not None else None
+        arr = (_EnsJob * max(1, len(jobs)))()
+        for j, (contributors, out_ptr, capacity) in enumerate(jobs):
+            contributors = list(contributors)
+            arr[j].k = len(contributors)
+            for c, (ptr, n, layout) in enumerate(contributors[:ENS_MAX_K]):
+                arr[j].stem_dev[c], arr[j].n_samples[c], arr[j].layout[c] = ptr or None, int(n), self.SLOT_LAYOUTS[layout]
+            arr[j].out_dev, arr[j].out_capacity = out_ptr or None, int(capacity)
+        self._check(self._lib.asx_ensemble_batch_dev(self._h, arr, len(jobs), int(algorithm), wt, len(w) if w is not None else 0,
+                                                     self.SLOT_MODES[mode], float(max_peak), float(min_peak or 0.0), int(min_peak is not None),
+                                                     float(silent_below), stream or None))
+        return [(int(arr[j].n_out), int(arr[j].live), [float(arr[j].peak_after[c]) for c in range(min(arr[j].k, ENS_MAX_K))])
+                for j in range(len(jobs))]
 
     def invert_stem(self, mixture: np.ndarray, stem: np.ndarray) -> np.ndarray:
         """spec_utils.invert_stem(mixture [2, N], stem [2, N]) -> [N', 2]."""

@@ -110,12 +110,13 @@ class EnsembleSeparator:
                   "uvr_max_spec", "uvr_min_spec", "ensemble_wav")
 
     def __init__(self, members, algorithm="avg_wave", weights=None, preset=None, model_filenames=None, intermediate="pcm16",
-                 via_files=False, logger=None):
+                 via_files=False, logger=None, pool_files=None):
         """``members``: loaded plugin instances (MDXSeparator / MDXCSeparator / DemucsSeparator / VRSeparator, any mix); they
         and their engines stay resident across files.  ``algorithm`` / ``weights``: Ensembler's.  ``preset`` only names the
         outputs (``..._preset_<preset>``); ``model_filenames`` (default: each member's model file basename) name them
         otherwise.  ``intermediate``: "pcm16" (what the reference's 16-bit intermediate files carry, the default) or
-        "float32" (unquantised stems between members and combine; device path only).  ``via_files``: the literal flow."""
+        "float32" (unquantised stems between members and combine; device path only).  ``via_files``: the literal flow.
+        ``pool_files``: files per pooled run of ``separate_many`` (None: as many as the memory rule allows)."""
         self.members = list(members)
         if not self.members:
             raise ValueError("an ensemble needs at least one member")
@@ -142,7 +143,12 @@ class EnsembleSeparator:
         self.sample_rate = first.sample_rate
         writer = self.members[-1]                   # separator.py:1372-1379: the model loaded last writes the result
         self.output_dir, self.output_format = writer.output_dir, writer.output_format
+        if pool_files is not None and int(pool_files) < 1:
+            raise ValueError(f"pool_files must be at least 1, not {pool_files!r}")
+        self.pool_files = None if pool_files is None else int(pool_files)
         self.last_path_taken = None                 # "device" | "files": the path the last input took
+        self.last_paths_taken = []                  # separate_many: "device" | "files" | "failed" per input
+        self.batch_errors = {}                      # separate_many: input index -> the exception that file raised
 
     # ---- shared pieces ---------------------------------------------------------------------------------------------
     def _group_names(self, member, stem_names):
@@ -297,6 +303,166 @@ class EnsembleSeparator:
             writer._sync()
             outputs.append(self._write(path, stem_name, views[0], custom_output_names))
         return outputs
+
+    # ---- a batch of files: every member pools its files, one pooled combine ----------------------------------------------------
+    HBM_SHARE = 0.4          # of the HBM free at the start of separate_many: what the stems of one run may take (estimated)
+
+    def _stems_per_file(self, member):
+        """Stems ``member`` keeps per file, for the memory estimate (an upper bound where the model decides)."""
+        if hasattr(member, "demucs_source_map") or hasattr(member, "demucs_model_instance"):
+            return 6
+        instruments = ((getattr(member, "model_data", None) or {}).get("training") or {}).get("instruments") or []
+        return len(instruments) if getattr(member, "process_all_stems", False) and len(instruments) > 2 else 2
+
+    def _free_hbm(self):
+        try:
+            import torch
+            return torch.cuda.mem_get_info(self.members[-1].engine.device)[0]
+        except Exception:        # no device query: one run, an allocation failure is reported where it happens
+            return None
+
+    def _runs(self, paths):
+        """``paths`` as consecutive runs of indices, in order.  ``pool_files`` set: that many per run.  Else a run's estimated stem
+        bytes -- frames (audio_io.wav_info) x 8 bytes x stems of all members -- stay within ``HBM_SHARE`` of the free HBM; a run of
+        one file is always allowed."""
+        if not paths:
+            return []
+        if self.pool_files is not None:
+            return [list(range(i, min(i + self.pool_files, len(paths)))) for i in range(0, len(paths), self.pool_files)]
+        free = self._free_hbm()
+        if free is None:
+            return [list(range(len(paths)))]
+        per_frame = 8 * sum(self._stems_per_file(m) for m in self.members)
+        runs, used = [[]], 0
+        for i, path in enumerate(paths):
+            try:
+                cost = audio_io.wav_info(path)["frames"] * per_frame
+            except Exception:    # not a RIFF/WAVE file: it takes the file path or fails, no stems are kept for it
+                cost = 0
+            if runs[-1] and used + cost > self.HBM_SHARE * free:
+                runs.append([])
+                used = 0
+            runs[-1].append(i)
+            used += cost
+        return runs
+
+    def separate_many(self, paths, custom_output_names=None):
+        """``separate`` for a list of files with every member making ONE pooled call for all of them (``stems_dev_many``: the
+        chunks, segments or patches of all files share the net passes) and ONE pooled device call combining the stems of all
+        (file, stem group) pairs (``Engine.ensemble_batch_dev``).  Returns one list of output files per input, in order; the files
+        are byte-identical to those of ``separate(path)`` called per path on the same members.
+
+        * A file some member needs the host decoder for goes through the intermediate-file path alone, after the pooled files.
+        * A file some member raised for fails alone: its result is an empty list, the exception is kept in
+          ``self.batch_errors[index]`` and logged.
+        * ``last_paths_taken[index]`` is "device", "files" or "failed".
+        * What keeps the whole call off the device path (``via_files``, a soundfile writer, a lossy output format, a member without
+          ``stems_dev_many``) makes it the loop of ``separate`` per path.
+        * Memory: the stems of all members for all files of a run are alive at once; ``paths`` is cut into consecutive runs (``_runs``).
+        * Members see the files in list order, so the MDXC short-file rule evolves as in the loop.  Demucs members with
+          ``shifts > 0`` draw their offsets from ``random`` member by member (each for all files), the loop file by file: with at
+          most one such member the draws -- and the files -- are the same, with two or more they are assigned differently and the
+          outputs need not match the loop's."""
+        paths = list(paths)
+        self.batch_errors = {}
+        self.last_paths_taken = [None] * len(paths)
+        results = [[] for _ in paths]
+        why = self._device_path_refusal()
+        if why is None and any(not hasattr(m, "stems_dev_many") for m in self.members):
+            why = "a member has no pooled device-stem hook"
+        if why is not None:
+            if not self.via_files:
+                self.logger.info(f"ensemble of {len(paths)} files one by one ({why})")
+            for i, path in enumerate(paths):
+                results[i] = self.separate(path, custom_output_names)
+                self.last_paths_taken[i] = self.last_path_taken
+            return results
+        for run in self._runs(paths):
+            self._separate_run(paths, run, custom_output_names, results)
+        return results
+
+    def _fail(self, i, path, e):
+        self.logger.error(f"{path}: {e}")
+        self.batch_errors[i] = e
+        self.last_paths_taken[i] = "failed"
+
+    def _separate_run(self, paths, run, custom_output_names, results):
+        writer = self.members[-1]
+        sub = [paths[i] for i in run]
+        for path in sub:
+            self.logger.info(f"Ensemble processing for file: {path}")
+        pooled = [member.stems_dev_many(sub) for member in self.members]        # per member (stems per file, state per file)
+        engine = writer.engine
+        on_device, via_files = [], []              # (position in the run, groups) / positions
+        for pos, i in enumerate(run):
+            entries = [stems[pos] for stems, _ in pooled]
+            error = next((e for e in entries if isinstance(e, BaseException)), None)
+            if error is not None:
+                self._fail(i, paths[i], error)
+                continue
+            needs_host = [index for index, e in enumerate(entries) if e is None]
+            if needs_host:
+                index = needs_host[0]
+                self.logger.info(f"{paths[i]}: ensemble through intermediate files (member {index}, {self.members[index].model_name}, needs the host decoder)")
+                via_files.append(pos)
+                continue
+            groups = {}                            # group name -> [(member index, device stem, layout)], first-seen order
+            for index, (member, stems) in enumerate(zip(self.members, entries)):
+                member._restore_file(pooled[index][1][pos])
+                names = self._group_names(member, [name for name, _, _ in stems])
+                for (_, tensor, layout), group in zip(stems, names):
+                    groups.setdefault(group, []).append((index, tensor if tensor.is_contiguous() else tensor.contiguous(), layout))
+            if any(t.device.index != engine.device for contributors in groups.values() for _, t, _ in contributors):
+                self.logger.info(f"{paths[i]}: ensemble through intermediate files (members sit on different devices)")
+                via_files.append(pos)
+                continue
+            on_device.append((pos, groups))
+        for member in self.members:
+            member._reset_file_state()
+        # one pooled combine for every (file, group)
+        jobs, outs = [], []
+        for pos, groups in on_device:
+            for stem_name, contributors in groups.items():
+                lengths = [t.shape[1] if layout == "planar" else t.shape[0] for _, t, layout in contributors]
+                out = self._result_buffer(contributors[0][1], 2 * max(lengths))
+                outs.append(out)
+                jobs.append(([(t.data_ptr(), n, layout) for (_, t, layout), n in zip(contributors, lengths)], out.data_ptr(), max(lengths)))
+        stream = writer._stream() if jobs else 0
+        done = engine.ensemble_batch_dev(jobs, self.algorithm, self.weights, writer.normalization_threshold, writer.amplification_threshold,
+                                         silent_below=_SILENT, mode=self.intermediate, stream=stream) if jobs else []
+        with writer._writing():
+            j = 0
+            for pos, groups in on_device:
+                i = run[pos]
+                writer._restore_file(pooled[-1][1][pos])      # what its own pass over this file left for the writer (bit depth, subtype)
+                outputs = []
+                for stem_name, contributors in groups.items():
+                    (n_out, live, peaks), out = done[j], outs[j]
+                    j += 1
+                    for (index, _, _), peak in zip(contributors, peaks):
+                        if peak < _SILENT:
+                            self.logger.warning(f"{stem_name}: the stem of member {index} ({self.members[index].model_name}) is silent, left out of the ensemble")
+                    if live == 0:
+                        continue
+                    self.logger.info(f"Ensembling {live} stems for type: {stem_name}")
+                    _, views = writer._host_planar_stems(out[: 2 * n_out].view(1, 2, n_out))
+                    outputs.append(self._write(paths[i], stem_name, views[0], custom_output_names))
+                results[i] = outputs
+                self.last_paths_taken[i] = self.last_path_taken = "device"
+        writer._reset_file_state()
+        del outs, pooled, on_device
+        for pos in via_files:
+            i = run[pos]
+            try:
+                results[i] = self._separate_via_files(paths[i], custom_output_names)
+                self.last_paths_taken[i] = self.last_path_taken = "files"
+            except Exception as e:
+                self._fail(i, paths[i], e)
+
+    @staticmethod
+    def _result_buffer(like, numel):
+        import torch
+        return torch.empty((numel,), dtype=torch.float32, device=like.device)
 
 
 class Ensembler:
