@@ -531,6 +531,24 @@ int asx_resample_sinc(asx_engine *e, const float *x_host, int32_t channels, int6
 int asx_resample_sinc_dev(asx_engine *e, const float *x_dev, int32_t channels, int64_t n_in, double ratio, int32_t mono_calls,
                           float *y_dev, int64_t n_out, void *stream);
 
+/* High-quality rational polyphase converter for input files whose sample rate is not the model's (the step librosa.load delegates to
+ * soxr_hq, common_separator.py:252; the plugins' opt-in "asx_input_resample" = "device").  This project's own design in that converter's
+ * published class -- Kaiser-windowed sinc, 125 dB, pass band to 0.913 of the lower Nyquist frequency; parity with soxr unpinned.  With
+ * g = gcd(sr_in, sr_out), L = sr_out / g, M = sr_in / g:  y[m] = sum_i x[i] h[m M - i L] over 0 <= i < n_in, zero history at both ends, zero
+ * delay, n_out = ceil(n_in L / M) (librosa's length).  Taps float32, float32 FMA accumulation in a fixed order (bit-identical runs).
+ *   asx_resample_rational_plan  pure host: n_out for n_in (n_out may be NULL; n_in is then ignored), L, M and the taps per output.
+ *                               ASX_ERR_INVALID + asx_last_error() for equal rates and for pairs whose coefficient table L x taps
+ *                               would exceed 2^20 floats (44056 -> 44100 Hz and the like).
+ *   asx_resample_rational_dev   x [channels, n_in] planar -> y [channels, n_out] on the device, one launch on `stream`; n_out must be
+ *                               the plan's.  The table of a pair is built at its first call and kept on the engine.
+ *   asx_resample_rational       the same for host arrays.
+ * Additive within ABI 7. */
+int asx_resample_rational_plan(int32_t sr_in, int32_t sr_out, int64_t n_in, int64_t *n_out, int32_t *L, int32_t *M, int32_t *taps_per_phase);
+int asx_resample_rational_dev(asx_engine *e, const float *x_dev, int32_t channels, int64_t n_in, int32_t sr_in, int32_t sr_out, float *y_dev,
+                              int64_t n_out, void *stream);
+int asx_resample_rational(asx_engine *e, const float *x_host, int32_t channels, int64_t n_in, int32_t sr_in, int32_t sr_out, float *y_host,
+                          int64_t n_out);
+
 /* BagOfModels on the device (uvr_lib_v5/demucs/apply.py:169-196 + demucs_separator.py:171-189; ABI 4).  Every member of a
  * bag keeps its own engine (weights resident across files); the caller demixes the STANDARDISED mix with each member
  * (flags 0) and combines without a host round trip:

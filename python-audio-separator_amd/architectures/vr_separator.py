@@ -27,6 +27,10 @@ from ..vr import NN_ARCH_SIZES, VR_5_1, VRDemixer, load_model_params, reference_
 
 
 class VRSeparator(CommonSeparator):
+    # ``asx_input_resample`` = "device" does not reach this plugin: the reference decodes a VR input with the top band's own res_type
+    # (vr_separator.py:255-291), not with librosa.load's soxr_hq, so a file at another rate keeps going to ``_host_mix``
+    _resamples_input_files = False
+
     def __init__(self, common_config, arch_config: dict):
         super().__init__(config=common_config)
         self.model_capacity = 32, 128

@@ -75,6 +75,7 @@ class CommonSeparator:
             self.model_data = {}
         self.engine = None                       # the libasx.so handle; set by the architecture subclass
         self.asx_profile_file = bool(config.get("asx_profile_file"))   # per-phase wall times of separate() in file_timings
+        self.asx_input_resample = self._input_resample_mode(config)    # who converts a file at another rate than the model's
         self.file_timings = {}
         self._pending_writes = []                # (thread, error box) of container writes in flight
 
@@ -113,6 +114,37 @@ class CommonSeparator:
 
         self._reset_file_state()
         self.cached_sources_map = {}
+
+    # ``common_config["asx_input_resample"]``: "host" (the default) leaves a file whose rate is not ``sample_rate`` to librosa.load, as the
+    # reference does (soxr_hq on one host thread; AudioIOError where librosa is not installed); "device" converts a RIFF/WAVE file with
+    # the engine's rational polyphase converter (asx_resample_rational: this project's own filter in soxr_hq's class, so the samples
+    # differ from the reference's in the transition band -- hence opt-in).  The environment variable ASX_INPUT_RESAMPLE, when set and
+    # not empty, overrides the configuration of every plugin of the process.
+    INPUT_RESAMPLE_MODES = ("host", "device")
+    _resamples_input_files = True      # (a plugin whose reference loads files through another converter says False)
+
+    @classmethod
+    def _input_resample_mode(cls, config) -> str:
+        mode = os.environ.get("ASX_INPUT_RESAMPLE") or config.get("asx_input_resample") or "host"
+        if mode not in cls.INPUT_RESAMPLE_MODES:
+            raise ValueError(f"asx_input_resample must be one of {cls.INPUT_RESAMPLE_MODES}, not {mode!r}")
+        return mode
+
+    def _resample_plan(self, file_rate):
+        """(n_out for n_in) -> callable when ``asx_input_resample`` is "device" and the engine's converter takes ``file_rate`` ->
+        ``sample_rate``; None otherwise (the setting is "host", the rates are equal, the pair is refused: behave as before)."""
+        if getattr(self, "asx_input_resample", "host") != "device" or self.engine is None or not self.sample_rate:
+            return None
+        if not self._resamples_input_files:
+            return None
+        if file_rate == self.sample_rate or not hasattr(self.engine, "resample_rational_plan"):
+            return None
+        try:
+            self.engine.resample_rational_plan(file_rate, self.sample_rate, 1)
+        except Exception as e:
+            self.logger.debug(f"no device converter for {file_rate} -> {self.sample_rate} Hz ({e}): the host decoder takes the file")
+            return None
+        return lambda n_in: self.engine.resample_rational_plan(file_rate, self.sample_rate, n_in)[0]
 
     # what one input file leaves behind (common_separator.py:136-147, 509-520): reset by clear_file_specific_paths
     _FILE_STATE = ("audio_file_path", "audio_file_base", "primary_source", "secondary_source", "primary_stem_output_path",
@@ -230,7 +262,9 @@ class CommonSeparator:
     def _device_mix(self, path, check_silent=True):
         """prepare_mix for a RIFF/WAVE file at the model's rate WITHOUT a host float array: the data chunk is read into pinned
         memory, copied to HBM once and converted to the planar float32 mix [2, N] on the device (asx_pcm_decode_dev: the same
-        x / 2^(bits-1) conversion libsndfile applies under librosa.load, common_separator.py:252).  Returns a CUDA tensor, or
+        x / 2^(bits-1) conversion libsndfile applies under librosa.load, common_separator.py:252).  With ``asx_input_resample`` =
+        "device" a file at another rate is decoded at its own frame count and brought to ``sample_rate`` by
+        asx_resample_rational_dev ([2, ceil(N * sample_rate / file rate)]).  Returns a CUDA tensor, or
         None when the file needs the host decoder (other container, other rate, exotic subtype) -- the caller then takes
         prepare_mix.  Raises the reference's ValueError for a silent file (:268-271) unless ``check_silent`` is False: the VR
         plugin never calls prepare_mix (vr_separator.py:255-291 loads with librosa directly), so a silent file must come out the
@@ -242,8 +276,13 @@ class CommonSeparator:
             info = audio_io.wav_info(path)
         except (audio_io.AudioIOError, OSError):
             return None
-        if info["samplerate"] != self.sample_rate or info["subtype"] not in self.engine.PCM_FORMATS or info["frames"] < 1 or info["channels"] > 2:
+        if info["subtype"] not in self.engine.PCM_FORMATS or info["frames"] < 1 or info["channels"] > 2:
             return None                # (more than two channels: prepare_mix + the reference's "Expected a 2-channel" error)
+        n_resampled = None             # a file at another rate: only with asx_input_resample = "device" and a pair the converter takes
+        if info["samplerate"] != self.sample_rate:
+            n_resampled = self._resample_plan(info["samplerate"])
+            if n_resampled is None:
+                return None
         t0 = self._now()
         # what _probe_bit_depth records for the writer (common_separator.py:231-250)
         self.input_subtype = st = info["subtype"]
@@ -262,11 +301,18 @@ class CommonSeparator:
         raw = staged.to(dev, non_blocking=True)
         mix = torch.empty((2, frames), dtype=torch.float32, device=dev)
         peak = self.engine.pcm_decode_dev(raw.data_ptr(), frames, ch, st, mix.data_ptr(), stream=self._stream())
-        self._tick("h2d_decode", t0)
+        t0 = self._tick("h2d_decode", t0)
         if check_silent and not peak > 0.0:
             msg = f"Audio file {path} is empty or not valid"
             self.logger.error(msg)
             raise ValueError(msg)
+        if n_resampled is not None:
+            n_out = n_resampled(frames)
+            at_rate = torch.empty((2, n_out), dtype=torch.float32, device=dev)
+            self.engine.resample_rational_dev(mix.data_ptr(), 2, frames, info["samplerate"], self.sample_rate, at_rate.data_ptr(), n_out,
+                                              stream=self._stream())
+            mix = at_rate
+            self._tick("resample", t0)
         return mix
 
     def _device_decode(self, path):
@@ -520,13 +566,32 @@ class CommonSeparator:
             self.logger.warning(f"no container info for {path} ({e}): stems will be written as 16-bit PCM")
             self.input_bit_depth, self.input_subtype = 16, "PCM_16"
 
+    def _load_resampled(self, path):
+        """The host-array form of ``_device_mix``'s conversion, for a file the device decoder does not get (ASX_FILE_FASTPATH=0, a plugin
+        option that keeps the arrays on the host): audio_io.read_wav, then Engine.resample_rational -- the bits ``_device_mix`` produces.
+        None unless ``asx_input_resample`` is "device" and the file is RIFF/WAVE at a rate the converter takes."""
+        if getattr(self, "asx_input_resample", "host") != "device" or self.engine is None or not isinstance(path, str):
+            return None
+        try:
+            info = audio_io.wav_info(path)
+        except (audio_io.AudioIOError, OSError):
+            return None
+        if info["frames"] < 1 or self._resample_plan(info["samplerate"]) is None:
+            return None
+        t0 = self._now()
+        x, file_rate = audio_io.read_wav(path)
+        t0 = self._tick("read", t0)
+        y = self.engine.resample_rational(x, file_rate, self.sample_rate)
+        self._tick("resample", t0)
+        return (y[0] if y.shape[0] == 1 else y), self.sample_rate
+
     def prepare_mix(self, mix):
         """common_separator.py:217-282: path -> float32 [2, N] at ``sample_rate``; an ndarray [N, ch] is transposed;
         mono is duplicated; an all-zero file raises ValueError."""
         audio_path = mix
         if not isinstance(mix, np.ndarray):
             self._probe_bit_depth(mix)
-            mix, sr = audio_io.load(mix, mono=False, sr=self.sample_rate)
+            mix, sr = self._load_resampled(mix) or audio_io.load(mix, mono=False, sr=self.sample_rate)
             self.logger.debug(f"decoded {audio_path}: {mix.shape[-1]} samples x {mix.shape[0] if mix.ndim > 1 else 1} channel(s) at {sr} Hz")
         else:
             if self.input_bit_depth is None:

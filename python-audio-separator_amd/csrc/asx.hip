@@ -22,6 +22,7 @@
 
 #include "../../include/asx.h"
 #include "knobs.h"
+#include "resample_plan.h"
 
 // Raise a kernel's dynamic-LDS limit to `bytes` unless an earlier call granted as much.  Engines are driven from several host threads
 // (one per bag member / rank): one lock covers the record and the attribute call, so no launch can overtake the grant it needs.
@@ -57,6 +58,7 @@ static void grant_lds(K *kernel, int bytes) { grant_lds(reinterpret_cast<const v
 #include "kernels_hd.h"
 #include "kernels_vr.h"
 #include "kernels_ens.h"
+#include "kernels_resample.h"
 
 using namespace asx;
 
@@ -280,6 +282,11 @@ void asx_engine_destroy(asx_engine *e) {
   }
   if (e->div_ev) (void)hipEventDestroy(e->div_ev);
   e->sinc_tab.release();
+  for (RsTable *t : e->rs_tabs) {
+    t->tab.release();
+    delete t;
+  }
+  e->rs_tabs.clear();
   e->d_window.release();
   e->d_tw.release();
   e->d_env.release();
@@ -508,6 +515,7 @@ double asx_net_flops(const asx_engine *e, int32_t batch) {
 #include "engine_hd.h"
 #include "engine_vr.h"
 #include "engine_ens.h"
+#include "engine_resample.h"
 extern "C" {
 
 // ---- plan ------------------------------------------------------------------
@@ -1003,6 +1011,58 @@ int asx_resample_sinc_dev(asx_engine *e, const float *x_dev, int32_t channels, i
   REQUIRE(ratio > 1.0 / 256 && ratio < 256.0, "asx_resample_sinc_dev: ratio %g outside libsamplerate's (1/256, 256)", ratio);
   HIPCHK(hipSetDevice(e->device));
   return resample_sinc_dev(e, e->sinc_tab, x_dev, channels, n_in, ratio, mono_calls, y_dev, n_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The rational polyphase converter (resample_plan.h, kernels_resample.h): the plan of a pair of rates, pure host
+int asx_resample_rational_plan(int32_t sr_in, int32_t sr_out, int64_t n_in, int64_t *n_out, int32_t *L, int32_t *M, int32_t *taps_per_phase) {
+  ResamplePlan p;
+  const std::string why = resample_plan_make(sr_in, sr_out, p);
+  REQUIRE(why.empty(), "asx_resample_rational_plan: %s", why.c_str());
+  if (n_out) {
+    const std::string bad = resample_plan_check_n(p, n_in);
+    REQUIRE(bad.empty(), "asx_resample_rational_plan: %s", bad.c_str());
+    *n_out = resample_plan_n_out(p, n_in);
+  }
+  if (L) *L = (int32_t)p.L;
+  if (M) *M = (int32_t)p.M;
+  if (taps_per_phase) *taps_per_phase = (int32_t)p.T;
+  return ASX_OK;
+}
+
+int asx_resample_rational_dev(asx_engine *e, const float *x_dev, int32_t channels, int64_t n_in, int32_t sr_in, int32_t sr_out, float *y_dev,
+                              int64_t n_out, void *stream) {
+  REQUIRE(e && x_dev && y_dev, "asx_resample_rational_dev: null argument");
+  REQUIRE(channels >= 1 && channels <= 65535, "asx_resample_rational_dev: %d channels (1 .. 65535)", channels);
+  ResamplePlan p;
+  const std::string why = resample_plan_make(sr_in, sr_out, p);
+  REQUIRE(why.empty(), "asx_resample_rational_dev: %s", why.c_str());
+  const std::string bad = resample_plan_check_n(p, n_in);
+  REQUIRE(bad.empty(), "asx_resample_rational_dev: %s", bad.c_str());
+  REQUIRE(n_out == resample_plan_n_out(p, n_in), "asx_resample_rational_dev: n_out = %lld, but %lld samples at %d Hz are %lld at %d Hz",
+          (long long)n_out, (long long)n_in, sr_in, (long long)resample_plan_n_out(p, n_in), sr_out);
+  REQUIRE(p.K == 8 || !p.taps_in_lds, "asx_resample_rational_dev: no kernel for the tile of %d -> %d Hz", sr_in, sr_out);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  const RsTable *t = nullptr;
+  CHK(rs_table(e, p, &t));
+  const float *tab = t->tab.f();
+  return timed(e, ASX_PROF_MISC, 2.0 * channels * (double)n_out * (double)p.T, 4.0 * channels * ((double)n_in + (double)n_out), s, [&]() {
+    if (p.taps_in_lds) rs_launch<8, true>(p, x_dev, channels, n_in, tab, y_dev, n_out, s);
+    else if (p.K == 8) rs_launch<8, false>(p, x_dev, channels, n_in, tab, y_dev, n_out, s);
+    else if (p.K == 4) rs_launch<4, false>(p, x_dev, channels, n_in, tab, y_dev, n_out, s);
+    else if (p.K == 2) rs_launch<2, false>(p, x_dev, channels, n_in, tab, y_dev, n_out, s);
+    else rs_launch<1, false>(p, x_dev, channels, n_in, tab, y_dev, n_out, s);
+  });
+}
+
+int asx_resample_rational(asx_engine *e, const float *x_host, int32_t channels, int64_t n_in, int32_t sr_in, int32_t sr_out, float *y_host,
+                          int64_t n_out) {
+  REQUIRE(e && x_host && y_host, "asx_resample_rational: null argument");
+  REQUIRE(channels >= 1 && channels <= 65535 && n_in >= 1 && n_out >= 1, "asx_resample_rational: bad argument");
+  HIPCHK(hipSetDevice(e->device));
+  return host_round_trip(x_host, (size_t)channels * n_in, y_host, (size_t)channels * n_out, [&](const float *x, float *y) {
+    return asx_resample_rational_dev(e, x, channels, n_in, sr_in, sr_out, y, n_out, nullptr);
+  });
 }
 
 // ---- stage hooks -------------------------------------------------------------

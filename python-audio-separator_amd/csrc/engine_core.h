@@ -146,6 +146,12 @@ struct ProfRec {
   double flops, bytes;
 };
 
+// plan and device table of the rational converter for one pair of rates (resample_plan.h)
+struct RsTable {
+  ResamplePlan plan;
+  DevBuf tab;
+};
+
 struct V3Net;
 struct RofNet;
 struct HtNet;
@@ -213,6 +219,10 @@ struct asx_engine {
   DevBuf d_div;      // divider of the chunk fold for div_key's plan (input-independent: built once, asx_finalize_dev)
   DivKey div_key;
   DevBuf sinc_tab;   // coefficient table of asx_resample_sinc (built on first use)
+  // coefficient tables of asx_resample_rational, one per (sr_in, sr_out), built on first use and kept until the engine goes (the entries never
+  // move: a launch in flight reads its table)
+  std::vector<RsTable *> rs_tabs;
+  std::mutex rs_mu;
   hipEvent_t div_ev = nullptr;       // recorded behind the kernel that built d_div; a call on ANOTHER stream waits for it
   hipStream_t div_stream = nullptr;
   std::vector<DevBuf> skip;

@@ -276,7 +276,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_profile_launches", "asx_debug_trace", "asx_resample_sinc", "asx_resample_sinc_dev", "asx_counter",
            "asx_set_stft_window", "asx_op_tdf_block", "asx_op_attention", "asx_op_mha", "asx_get_option",
            "asx_demix_batch_dev", "asx_separate_batch_dev", "asx_ensemble_slot_dev", "asx_vr_separate_batch_dev",
-           "asx_mdxc_demix_batch_dev", "asx_rof_demix_batch_dev", "asx_ensemble_batch_dev"]
+           "asx_mdxc_demix_batch_dev", "asx_rof_demix_batch_dev", "asx_ensemble_batch_dev", "asx_resample_rational_plan",
+           "asx_resample_rational", "asx_resample_rational_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -411,6 +412,9 @@ def load_library():
     lib.asx_debug_fetch.argtypes = [vp, C.c_char_p, _FP, i64]
     lib.asx_resample_sinc.argtypes = [vp, _FP, i32, i64, C.c_double, i32, _FP, i64]
     lib.asx_resample_sinc_dev.argtypes = [vp, vp, i32, i64, C.c_double, i32, vp, i64, vp]
+    lib.asx_resample_rational_plan.argtypes = [i32, i32, i64, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    lib.asx_resample_rational.argtypes = [vp, _FP, i32, i64, i32, i32, _FP, i64]
+    lib.asx_resample_rational_dev.argtypes = [vp, vp, i32, i64, i32, i32, vp, i64, vp]
     lib.asx_ensemble.argtypes = [vp, _FP, i32, i64, i32, C.POINTER(C.c_double), _FP, C.POINTER(i64)]
     lib.asx_ensemble_dev.argtypes = [vp, vp, i32, i64, i32, C.POINTER(C.c_double), vp, C.POINTER(i64), vp]
     lib.asx_invert_stem.argtypes = [vp, _FP, _FP, i64, _FP, C.POINTER(i64)]
@@ -835,6 +839,36 @@ class Engine:
     def resample_sinc_dev(self, x_ptr: int, channels: int, n_in: int, ratio: float, mono_calls: bool, y_ptr: int, n_out: int, stream: int = 0):
         self._check(self._lib.asx_resample_sinc_dev(self._h, x_ptr, int(channels), int(n_in), float(ratio), int(bool(mono_calls)), y_ptr,
                                                     int(n_out), stream or None))
+
+    @staticmethod
+    def resample_rational_plan(sr_in: int, sr_out: int, n_in: int = 1):
+        """asx_resample_rational_plan (pure host: no engine, no GPU): (n_out, L, M, taps per output) of the rational polyphase
+        converter for ``n_in`` samples at ``sr_in`` Hz -> ``sr_out`` Hz.  Raises AsxError for a pair the converter refuses (equal
+        rates, a coefficient table beyond 2^20 floats)."""
+        lib = load_library()
+        n_out, up, down, taps = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
+        rc = lib.asx_resample_rational_plan(int(sr_in), int(sr_out), int(n_in), C.byref(n_out), C.byref(up), C.byref(down), C.byref(taps))
+        if rc != 0:
+            msg = lib.asx_last_error()
+            raise AsxError(f"asx error {rc}: {msg.decode() if msg else '?'}")
+        return n_out.value, up.value, down.value, taps.value
+
+    def resample_rational(self, x: np.ndarray, sr_in: int, sr_out: int) -> np.ndarray:
+        """x [C, n] (or [n]) at ``sr_in`` Hz -> [C, ceil(n * sr_out / sr_in)] at ``sr_out`` Hz through the high-quality polyphase
+        converter (asx_resample_rational: the step of loading a file at another rate than the model's)."""
+        x = _f32(x)
+        one = x.ndim == 1
+        x2 = np.ascontiguousarray(x[None] if one else x)
+        if x2.ndim != 2 or x2.shape[1] < 1:
+            raise ValueError(f"resample_rational expects [channels, n], got {x.shape}")
+        n_out = self.resample_rational_plan(sr_in, sr_out, x2.shape[1])[0]
+        y = np.empty((x2.shape[0], n_out), np.float32)
+        self._check(self._lib.asx_resample_rational(self._h, _ptr(x2), x2.shape[0], x2.shape[1], int(sr_in), int(sr_out), _ptr(y), n_out))
+        return y[0] if one else y
+
+    def resample_rational_dev(self, x_ptr: int, channels: int, n_in: int, sr_in: int, sr_out: int, y_ptr: int, n_out: int, stream: int = 0):
+        self._check(self._lib.asx_resample_rational_dev(self._h, x_ptr, int(channels), int(n_in), int(sr_in), int(sr_out), y_ptr, int(n_out),
+                                                        stream or None))
 
     def vr_flops(self) -> float:
         return float(self._lib.asx_vr_flops(self._h))

@@ -133,6 +133,10 @@ class EnsembleSeparator:
             if any(v != values[0] for v in values):
                 # the orchestrator hands every model the same values; intermediates are not resampled between rates
                 raise ValueError(f"ensemble members differ in {key}: {values}")
+        modes = [getattr(m, "asx_input_resample", "host") for m in self.members]
+        if any(v != modes[0] for v in modes):
+            # a file at another rate would reach the members through different converters (or fail in some of them only)
+            raise ValueError(f"ensemble members differ in asx_input_resample: {modes}")
         if model_filenames is not None and len(model_filenames) != len(self.members):
             raise ValueError(f"{len(model_filenames)} model file names for {len(self.members)} members")
         self.algorithm, self.weights, self.preset = algorithm, weights, preset
