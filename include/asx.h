@@ -258,7 +258,9 @@ int asx_mdxc_plan(const asx_engine *e, int64_t n_samples, int32_t overlap, asx_p
 /* MDXCSeparator.demix, TFC branch (mdxc_separator.py:345-404): mix [2,N] -> out [S,2,N]
  * (= accumulated[..., chunk-hop : -(pad+chunk-hop)] / overlap). */
 int asx_mdxc_demix(asx_engine *e, const float *mix_host, int64_t n_samples, int32_t overlap, float *out_host);
-/* halves of asx_mdxc_demix_dev for multi-GPU sharding: chunk_out [n_chunks (asx_mdxc_plan), S, 2, chunk_size] */
+/* halves of asx_mdxc_demix_dev for multi-GPU sharding: chunk_out [n_chunks (asx_mdxc_plan), S, 2, chunk_size].  The three single-song
+ * calls run a pool of ONE song through the loop and the fold of asx_mdxc_demix_batch_dev (below): chunks_dev runs chunks [k0, k1) into
+ * the caller's buffer in passes of up to max_batch chunks, finalize_dev folds the caller's buffer, demix_dev does both on the engine's. */
 int asx_mdxc_chunks_dev(asx_engine *e, const float *mix_dev, int64_t n_samples, int32_t overlap, int32_t k0, int32_t k1,
                         float *chunk_out_dev, void *stream);
 int asx_mdxc_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t n_samples, int32_t overlap, float *out_dev, void *stream);
@@ -298,7 +300,8 @@ int asx_rof_forward(asx_engine *e, const float *wave_host, int32_t batch, float 
 int asx_rof_demix(asx_engine *e, const float *mix_host, int64_t n_samples, int64_t step, float *out_host);
 int asx_rof_demix_dev(asx_engine *e, const float *mix_dev, int64_t n_samples, int64_t step, float *out_dev,
                       void *stream);
-/* halves of asx_rof_demix_dev for multi-GPU sharding: chunk_out [n_chunks, S, 2, chunk_size] */
+/* halves of asx_rof_demix_dev for multi-GPU sharding: chunk_out [n_chunks, S, 2, chunk_size]; as on the TFC branch, the single-song
+ * calls are a pool of one song on asx_rof_demix_batch_dev's loop and fold */
 int asx_rof_plan(const asx_engine *e, int64_t n_samples, int64_t step, int32_t *n_chunks, int64_t *chunk_size);
 int asx_rof_chunks_dev(asx_engine *e, const float *mix_dev, int64_t n_samples, int64_t step, int32_t k0, int32_t k1,
                        float *chunk_out_dev, void *stream);
@@ -308,7 +311,7 @@ int asx_rof_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t n_sa
  * The chunks of all songs form one list, in song order, that runs through the STFT / net / iSTFT launches in passes of up to
  * max_batch chunks (8 when max_batch is 0, as the single-song calls), whichever song a chunk belongs to: a Roformer pass over a
  * folder of short clips is as full as one over a long song.  One segmented fold then writes every song's out; each equals what
- * asx_mdxc_demix_dev / asx_rof_demix_dev writes for that song alone, bit for bit.  `songs` is a HOST array, read during the call;
+ * asx_mdxc_demix_dev / asx_rof_demix_dev writes for that song alone, bit for bit (those calls ARE this one with n_songs = 1).  `songs` is a HOST array, read during the call;
  * the mixes may have different lengths.  The chunk tables are built on the device from launch arguments: the call only enqueues
  * work on `stream`.  Every argument is checked on the host first and nothing is enqueued when any song is invalid (null pointer,
  * n_samples < 1, on the Roformer branch n_samples < chunk_size -- the message names the song's index); n_songs == 0 is ASX_OK.

@@ -1584,157 +1584,6 @@ int asx_mdxc_plan(const asx_engine *e, int64_t N, int32_t overlap, asx_plan *out
   return ASX_OK;
 }
 
-// chunks [k0, k1) of the unfold loop (mdxc_separator.py:374-392) -> chunk_out [k1-k0, S, 2, chunk]
-int asx_mdxc_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t overlap, int32_t k0, int32_t k1, float *chunk_out_dev,
-                        void *stream) {
-  REQUIRE(e && mix_dev && chunk_out_dev, "asx_mdxc_chunks_dev: null argument");
-  READY(e->v3, "asx_mdxc_chunks_dev");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  HIPCHK(hipSetDevice(e->device));
-  asx_plan p;
-  CHK(asx_mdxc_plan(e, N, overlap, &p));
-  REQUIRE(k0 >= 0 && k0 <= k1 && k1 <= p.n_chunks, "chunk range [%d, %d) outside [0, %d)", k0, k1, p.n_chunks);
-  if (k1 == k0) return ASX_OK;
-  V3Net &n = *e->v3;
-  const int S = n.cfg.num_targets;
-  const int64_t C = p.chunk_size;
-  const int nk = k1 - k0;
-  CHK(n.d_starts.ensure((size_t)nk * 16));   // starts | (unused) active lengths, built on the device: no host sync
-  hipLaunchKernelGGL(chunk_table_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, k0, nk, p.step, p.chunk_size,
-                     p.padded_len, 0, reinterpret_cast<int64_t *>(n.d_starts.p), reinterpret_cast<int64_t *>(n.d_starts.p) + nk);
-  HIPCHK(hipGetLastError());
-  const int per = even_batches(nk, e->cfg.max_batch > 0 ? e->cfg.max_batch : 8);
-  for (int j = 0; j < nk; j += per) {
-    const int B = std::min(per, nk - j);
-    CHK(v3_chunks_dev(e, mix_dev, reinterpret_cast<const int64_t *>(n.d_starts.p) + j, N, p.trim, B,
-                      chunk_out_dev + (size_t)j * S * 2 * C, s));
-  }
-  return ASX_OK;
-}
-
-// uniform fold of ALL chunks, / overlap (mdxc_separator.py:246-255, 394-404): chunk_out [n_chunks, S, 2, chunk] -> out [S, 2, N]
-int asx_mdxc_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t N, int32_t overlap, float *out_dev, void *stream) {
-  REQUIRE(e && chunk_out_dev && out_dev, "asx_mdxc_finalize_dev: null argument");
-  READY(e->v3, "asx_mdxc_finalize_dev");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  HIPCHK(hipSetDevice(e->device));
-  asx_plan p;
-  CHK(asx_mdxc_plan(e, N, overlap, &p));
-  const int S = e->v3->cfg.num_targets;
-  const int64_t C = p.chunk_size;
-  const double bytes = 4.0 * ((double)p.n_chunks * S * 2 * C + (double)S * 2 * N);
-  return timed(e, ASX_PROF_FINALIZE, 0.0, bytes, s, [&]() {
-    hipLaunchKernelGGL(mdxc_finalize_kernel, dim3((unsigned)((N + 255) / 256), S * 2), dim3(256), 0, s, chunk_out_dev, p.n_chunks, S, C,
-                       p.step, (int64_t)p.trim, N, (float)overlap, out_dev);
-  });
-}
-
-int asx_mdxc_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t overlap, float *out_dev, void *stream) {
-  REQUIRE(e && mix_dev && out_dev, "asx_mdxc_demix_dev: null argument");
-  READY(e->v3, "asx_mdxc_demix_dev");
-  asx_plan p;
-  CHK(asx_mdxc_plan(e, N, overlap, &p));
-  V3Net &n = *e->v3;
-  CHK(n.chunk_out.ensure((size_t)p.n_chunks * n.cfg.num_targets * 2 * p.chunk_size * 4));
-  CHK(asx_mdxc_chunks_dev(e, mix_dev, N, overlap, 0, p.n_chunks, n.chunk_out.f(), stream));
-  return asx_mdxc_finalize_dev(e, n.chunk_out.f(), N, overlap, out_dev, stream);
-}
-
-int asx_mdxc_demix(asx_engine *e, const float *mix_host, int64_t N, int32_t overlap, float *out_host) {
-  REQUIRE(e && mix_host && out_host, "asx_mdxc_demix: null argument");
-  REQUIRE(N >= 1, "n_samples must be >= 1");
-  READY(e->v3, "asx_mdxc_demix");
-  HIPCHK(hipSetDevice(e->device));
-  const int S = e->v3->cfg.num_targets;
-  return host_round_trip(mix_host, (size_t)2 * N, out_host, (size_t)S * 2 * N,
-                         [&](const float *mix, float *out) { return asx_mdxc_demix_dev(e, mix, N, overlap, out, nullptr); });
-}
-
-// ---- a batch of songs, their chunks pooled per net pass (both MDXC loops) -------------------------------------------------
-// The arguments of a pooled call, all checked on the host before anything is enqueued.
-static int mdxc_pool_args(const char *fn, asx_engine *e, const asx_mdxc_song *songs, int32_t n_songs, std::vector<int64_t> &Ns) {
-  REQUIRE(e && n_songs >= 0 && (songs || n_songs == 0), "%s: null argument", fn);
-  Ns.resize((size_t)n_songs);
-  for (int i = 0; i < n_songs; ++i) {
-    REQUIRE(songs[i].mix_dev && songs[i].out_dev, "%s: null pointer in song %d", fn, i);
-    REQUIRE(songs[i].n_samples >= 1, "%s: song %d: n_samples must be >= 1", fn, i);
-    Ns[i] = songs[i].n_samples;
-  }
-  return ASX_OK;
-}
-
-// The pool's tables on the device, from by-value launch arguments in groups of POOL_GROUP songs: per pooled chunk its song's base
-// pointer and length (pool_wave / pool_nsong) and its start (d_starts), per song its fold entry (pool_songs).  *blocks: the fold's
-// grid.x.  chunk_floats = S * 2 * C.  The buffers are sized by the caller.
-static int mdxc_pool_tables(asx_engine *e, const char *fn, const asx_mdxc_song *songs, const MdxcPoolPlan &pp, bool rof, int64_t chunk_floats,
-                            const float *chunks, int64_t *d_starts, hipStream_t s, int64_t *blocks) {
-  const int n = (int)pp.chunk0.size() - 1;
-  int64_t blk = 0;
-  for (int g0 = 0; g0 < n; g0 += POOL_GROUP) {
-    MdxcPoolGroup g{};
-    g.n_songs = std::min(POOL_GROUP, n - g0);
-    g.song0 = g0;
-    for (int i = 0; i < g.n_songs; ++i) {
-      const asx_mdxc_song &sg = songs[g0 + i];
-      g.mix[i] = sg.mix_dev;
-      g.out[i] = sg.out_dev;
-      g.n[i] = sg.n_samples;
-      g.chunk0[i] = pp.chunk0[g0 + i];
-      g.blk0[i] = blk;
-      blk += (sg.n_samples + 255) / 256;
-    }
-    g.chunk0[g.n_songs] = pp.chunk0[g0 + g.n_songs];
-    const int nthr = std::max(g.chunk0[g.n_songs] - g.chunk0[0], g.n_songs);
-    hipLaunchKernelGGL(mdxc_pool_table_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, g, pp.step, pp.chunk_size, rof ? 1 : 0,
-                       chunk_floats, chunks, reinterpret_cast<const float **>(e->pool_wave.p), reinterpret_cast<int64_t *>(e->pool_nsong.p),
-                       d_starts, reinterpret_cast<MdxcPoolSong *>(e->pool_songs.p));
-    HIPCHK(hipGetLastError());
-  }
-  REQUIRE(blk < ((int64_t)1 << 31), "%s: %lld samples in one pool", fn, (long long)blk * 256);
-  *blocks = blk;
-  return ASX_OK;
-}
-
-// MDXCSeparator.demix, TFC branch, for a pool of songs: one chunk list over all songs, walked in passes of
-// mdxc_pool_per_pass(total, max_batch) chunks that may straddle songs, then ONE segmented fold.  Every buffer is sized before the
-// first launch; the call only enqueues work.
-int asx_mdxc_demix_batch_dev(asx_engine *e, const asx_mdxc_song *songs, int32_t n_songs, int32_t overlap, void *stream) {
-  std::vector<int64_t> Ns;
-  CHK(mdxc_pool_args("asx_mdxc_demix_batch_dev", e, songs, n_songs, Ns));
-  READY(e->v3, "asx_mdxc_demix_batch_dev");
-  if (n_songs == 0) return ASX_OK;
-  MdxcPoolPlan pp;
-  std::string err;
-  REQUIRE(mdxc_pool_build_tfc(e->cfg.hop_length, e->cfg.segment_size, overlap, Ns.data(), n_songs, pp, err), "asx_mdxc_demix_batch_dev: %s",
-          err.c_str());
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  HIPCHK(hipSetDevice(e->device));
-  V3Net &n = *e->v3;
-  const int S = n.cfg.num_targets, nk = pp.total();
-  const int64_t C = pp.chunk_size, chunk_floats = (int64_t)S * 2 * C;
-  const int per = mdxc_pool_per_pass(nk, e->cfg.max_batch);
-  CHK(v3_ensure_workspace(e, per));
-  CHK(n.chunk_out.ensure((size_t)nk * chunk_floats * 4));
-  CHK(n.d_starts.ensure((size_t)nk * 8));
-  CHK(e->pool_wave.ensure((size_t)nk * 8));
-  CHK(e->pool_nsong.ensure((size_t)nk * 8));
-  CHK(e->pool_songs.ensure((size_t)n_songs * sizeof(MdxcPoolSong)));
-  int64_t *ds = reinterpret_cast<int64_t *>(n.d_starts.p);
-  int64_t blk = 0;
-  CHK(mdxc_pool_tables(e, "asx_mdxc_demix_batch_dev", songs, pp, false, chunk_floats, n.chunk_out.f(), ds, s, &blk));
-  for (int j = 0; j < nk; j += per) {
-    const int B = std::min(per, nk - j);
-    const PoolChunks pc{reinterpret_cast<const float *const *>(e->pool_wave.p) + j, reinterpret_cast<const int64_t *>(e->pool_nsong.p) + j};
-    CHK(v3_chunks_dev(e, nullptr, ds + j, 0, (int)pp.front, B, n.chunk_out.f() + (size_t)j * chunk_floats, s, &pc));
-  }
-  double bytes = 0.0;
-  for (int i = 0; i < n_songs; ++i) bytes += 4.0 * ((double)pp.tfc[i].n_chunks * chunk_floats + (double)S * 2 * Ns[i]);
-  return timed(e, ASX_PROF_FINALIZE, 0.0, bytes, s, [&]() {
-    hipLaunchKernelGGL(mdxc_finalize_pool_kernel, dim3((unsigned)blk, S * 2), dim3(256), 0, s, reinterpret_cast<const MdxcPoolSong *>(e->pool_songs.p),
-                       n_songs, S, C, pp.step, pp.front, (float)overlap);
-  });
-}
-
 // ---- BS-Roformer ------------------------------------------------------------------
 int asx_rof_begin(asx_engine *e, const asx_rof_config *cfg) {
   w3_flush(e);
@@ -1889,90 +1738,222 @@ int asx_rof_forward(asx_engine *e, const float *wave_host, int32_t B, float *out
                          [&](const float *w, float *out) { return rof_chunks_dev(e, w, nullptr, -1, B, out, nullptr); });
 }
 
-// start of Roformer chunk k0 + t: t * step, the last one re-anchored to N - C (mdxc_separator.py:323-336)
-__global__ void rof_starts_kernel(int k0, int nk, int64_t step, int64_t N, int64_t C, int64_t *__restrict__ starts) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nk) return;
-  const int64_t i = (int64_t)(k0 + t) * step;
-  starts[t] = i + C > N ? N - C : i;
-}
-
-static int rof_starts(asx_engine *e, int64_t N, int64_t step, std::vector<int64_t> &starts) {
-  const std::string why = rof_plan_starts(N, (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1), step, starts);   // csrc/mdxc_pool_plan.h
-  REQUIRE(why.empty(), "%s", why.c_str());
-  return ASX_OK;
-}
-
 int asx_rof_plan(const asx_engine *e, int64_t N, int64_t step, int32_t *n_chunks, int64_t *chunk_size) {
   REQUIRE(e && n_chunks && chunk_size, "asx_rof_plan: null argument");
-  std::vector<int64_t> starts;
-  CHK(rof_starts(const_cast<asx_engine *>(e), N, step, starts));
-  *n_chunks = (int32_t)starts.size();
-  *chunk_size = (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1);
+  const int64_t C = (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1);
+  const std::string why = rof_plan_check(N, C, step);   // csrc/mdxc_pool_plan.h
+  REQUIRE(why.empty(), "%s", why.c_str());
+  *n_chunks = (int32_t)rof_plan_count(N, step);
+  *chunk_size = C;
   return ASX_OK;
 }
 
-// chunks [k0, k1) of the Roformer loop (mdxc_separator.py:318-336) -> chunk_out [k1-k0, S, 2, chunk]
-int asx_rof_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int64_t step, int32_t k0, int32_t k1, float *chunk_out_dev,
-                       void *stream) {
-  REQUIRE(e && mix_dev && chunk_out_dev, "asx_rof_chunks_dev: null argument");
-  READY(e->rof, "asx_rof_chunks_dev");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  HIPCHK(hipSetDevice(e->device));
-  RofNet &n = *e->rof;
-  const int S = n.cfg.num_stems;
-  const int64_t C = (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1);
-  std::vector<int64_t> starts;
-  CHK(rof_starts(e, N, step, starts));
-  REQUIRE(k0 >= 0 && k0 <= k1 && k1 <= (int)starts.size(), "chunk range [%d, %d) outside [0, %d)", k0, k1, (int)starts.size());
-  if (k1 == k0) return ASX_OK;
-  const int nk = k1 - k0;
-  CHK(n.d_starts.ensure((size_t)starts.size() * 8));
-  // chunk starts built on the device (like chunk_table_kernel for MDX): the call only enqueues work
-  hipLaunchKernelGGL(rof_starts_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, k0, nk, step, N, C,
-                     reinterpret_cast<int64_t *>(n.d_starts.p));
-  HIPCHK(hipGetLastError());
-  const int per = even_batches(nk, e->cfg.max_batch > 0 ? e->cfg.max_batch : 8);
-  for (int j = 0; j < nk; j += per) {
-    const int B = std::min(per, nk - j);
-    CHK(rof_chunks_dev(e, mix_dev, reinterpret_cast<const int64_t *>(n.d_starts.p) + j, N, B, chunk_out_dev + (size_t)j * S * 2 * C, s));
+// ---- MDXCSeparator.demix: the TFC branch (mdxc_separator.py:345-404) and the Roformer branch (:272-343) ------------------------
+// Both loops exist once, for a pool of songs: one chunk list over all songs, in song order (MdxcPoolPlan), walked in net passes
+// that may straddle songs, then ONE segmented fold.  The single-song calls run a pool of one song.
+struct MdxcBranch {             // what the two branches do not share
+  bool rof;
+  int S, rows;                  // stems per chunk; rows of a song's out (Roformer: n_out, row o reads stem o % S)
+  DevBuf &chunk_out, &d_starts;
+  int64_t chunk_floats(const MdxcPoolPlan &pp) const { return (int64_t)S * 2 * pp.chunk_size; }
+};
+static MdxcBranch mdxc_branch(asx_engine *e, bool rof) {
+  if (rof) return {true, e->rof->cfg.num_stems, e->rof->cfg.n_out, e->rof->chunk_out, e->rof->d_starts};
+  return {false, e->v3->cfg.num_targets, e->v3->cfg.num_targets, e->v3->chunk_out, e->v3->d_starts};
+}
+
+static int mdxc_ready(const asx_engine *e, bool rof, const char *fn) {
+  if (rof) READY(e->rof, fn);
+  else READY(e->v3, fn);
+  return ASX_OK;
+}
+
+// The pool's tables on the device, from by-value launch arguments in groups of POOL_GROUP songs: per pooled chunk its song's base
+// pointer and length (pool_wave / pool_nsong) and its start (d_starts), per song its fold entry (pool_songs) into `chunks`, the
+// buffer that holds pooled chunk 0 first.  *blocks: the fold's grid.x.
+static int mdxc_pool_tables(asx_engine *e, const char *fn, const MdxcBranch &br, const asx_mdxc_song *songs, const MdxcPoolPlan &pp,
+                            const float *chunks, hipStream_t s, int64_t *blocks) {
+  const int n = (int)pp.chunk0.size() - 1, nk = pp.total();
+  CHK(br.d_starts.ensure((size_t)nk * 8));
+  CHK(e->pool_wave.ensure((size_t)nk * 8));
+  CHK(e->pool_nsong.ensure((size_t)nk * 8));
+  CHK(e->pool_songs.ensure((size_t)n * sizeof(MdxcPoolSong)));
+  int64_t blk = 0;
+  for (int g0 = 0; g0 < n; g0 += POOL_GROUP) {
+    MdxcPoolGroup g{};
+    g.n_songs = std::min(POOL_GROUP, n - g0);
+    g.song0 = g0;
+    for (int i = 0; i < g.n_songs; ++i) {
+      const asx_mdxc_song &sg = songs[g0 + i];
+      g.mix[i] = sg.mix_dev;
+      g.out[i] = sg.out_dev;
+      g.n[i] = sg.n_samples;
+      g.chunk0[i] = pp.chunk0[g0 + i];
+      g.blk0[i] = blk;
+      blk += (sg.n_samples + 255) / 256;
+    }
+    g.chunk0[g.n_songs] = pp.chunk0[g0 + g.n_songs];
+    const int nthr = std::max(g.chunk0[g.n_songs] - g.chunk0[0], g.n_songs);
+    hipLaunchKernelGGL(mdxc_pool_table_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, g, pp.step, pp.chunk_size, br.rof ? 1 : 0,
+                       br.chunk_floats(pp), chunks, reinterpret_cast<const float **>(e->pool_wave.p), reinterpret_cast<int64_t *>(e->pool_nsong.p),
+                       reinterpret_cast<int64_t *>(br.d_starts.p), reinterpret_cast<MdxcPoolSong *>(e->pool_songs.p));
+    HIPCHK(hipGetLastError());
+  }
+  REQUIRE(blk < ((int64_t)1 << 31), "%s: %lld samples in one pool", fn, (long long)blk * 256);
+  *blocks = blk;
+  return ASX_OK;
+}
+
+// Pooled chunks [j0, j1), j0 < j1, through the net in passes of mdxc_pool_per_pass(j1 - j0, max_batch): chunk j -> dst + (j - j0) * S * 2 * C
+static int mdxc_pool_chunks(asx_engine *e, const MdxcBranch &br, const MdxcPoolPlan &pp, int j0, int j1, float *dst, hipStream_t s) {
+  const int per = mdxc_pool_per_pass(j1 - j0, e->cfg.max_batch);
+  for (int j = j0; j < j1; j += per) {
+    const int B = std::min(per, j1 - j);
+    const PoolChunks pc{reinterpret_cast<const float *const *>(e->pool_wave.p) + j, reinterpret_cast<const int64_t *>(e->pool_nsong.p) + j};
+    const int64_t *starts = reinterpret_cast<const int64_t *>(br.d_starts.p) + j;
+    float *out = dst + (size_t)(j - j0) * br.chunk_floats(pp);
+    CHK(br.rof ? rof_chunks_dev(e, nullptr, starts, 0, B, out, s, &pc) : v3_chunks_dev(e, nullptr, starts, 0, (int)pp.front, B, out, s, &pc));
   }
   return ASX_OK;
 }
 
-// Hamming-weighted fold of ALL chunks / counter.clamp(1e-10) (mdxc_separator.py:310-343)
-int asx_rof_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t N, int64_t step, float *out_dev, void *stream) {
-  REQUIRE(e && chunk_out_dev && out_dev, "asx_rof_finalize_dev: null argument");
-  READY(e->rof, "asx_rof_finalize_dev");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  HIPCHK(hipSetDevice(e->device));
-  RofNet &n = *e->rof;
-  const int S = n.cfg.num_stems;
-  const int64_t C = (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1);
-  std::vector<int64_t> starts;
-  CHK(rof_starts(e, N, step, starts));
-  const int nk = (int)starts.size();
-  CHK(n.d_starts.ensure((size_t)nk * 8));
-  hipLaunchKernelGGL(rof_starts_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, 0, nk, step, N, C,
-                     reinterpret_cast<int64_t *>(n.d_starts.p));
-  HIPCHK(hipGetLastError());
-  const int n_out = n.cfg.n_out;
-  return timed(e, ASX_PROF_FINALIZE, 0.0, 4.0 * ((double)nk * S * 2 * C + 2.0 * n_out * N), s, [&]() {
-    hipLaunchKernelGGL(roformer_finalize_kernel, dim3((unsigned)((N + 255) / 256), n_out * 2), dim3(256), 0, s, chunk_out_dev,
-                       reinterpret_cast<const int64_t *>(n.d_starts.p), nk, S, C, n.d_window.f(), N, out_dev);
+// The segmented fold of the chunk buffer the songs' fold entries point into (mdxc_pool_tables) -> every song's out
+static int mdxc_pool_fold(asx_engine *e, const MdxcBranch &br, const asx_mdxc_song *songs, const MdxcPoolPlan &pp, int64_t blocks, hipStream_t s) {
+  const int n = (int)pp.chunk0.size() - 1;
+  const int64_t C = pp.chunk_size;
+  double bytes = 4.0 * (double)pp.total() * br.chunk_floats(pp);
+  for (int i = 0; i < n; ++i) bytes += 4.0 * br.rows * 2 * (double)songs[i].n_samples;
+  const MdxcPoolSong *table = reinterpret_cast<const MdxcPoolSong *>(e->pool_songs.p);
+  return timed(e, ASX_PROF_FINALIZE, 0.0, bytes, s, [&]() {
+    if (br.rof)
+      hipLaunchKernelGGL(roformer_finalize_pool_kernel, dim3((unsigned)blocks, br.rows * 2), dim3(256), 0, s, table, n, br.S, C, pp.step,
+                         e->rof->d_window.f());
+    else
+      hipLaunchKernelGGL(mdxc_finalize_pool_kernel, dim3((unsigned)blocks, br.rows * 2), dim3(256), 0, s, table, n, br.S, C, pp.step, pp.front,
+                         (float)pp.overlap);
   });
 }
 
+// A planned pool through its whole loop, the chunks in the engine's chunk buffer.  Every buffer is sized before the first launch;
+// the call only enqueues work.
+static int mdxc_pool_demix(asx_engine *e, const char *fn, bool rof, const asx_mdxc_song *songs, const MdxcPoolPlan &pp, void *stream) {
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  const MdxcBranch br = mdxc_branch(e, rof);
+  const int nk = pp.total(), per = mdxc_pool_per_pass(nk, e->cfg.max_batch);
+  CHK(rof ? rof_ensure_workspace(e, per) : v3_ensure_workspace(e, per));
+  CHK(br.chunk_out.ensure((size_t)nk * br.chunk_floats(pp) * 4));
+  int64_t blk = 0;
+  CHK(mdxc_pool_tables(e, fn, br, songs, pp, br.chunk_out.f(), s, &blk));
+  CHK(mdxc_pool_chunks(e, br, pp, 0, nk, br.chunk_out.f(), s));
+  return mdxc_pool_fold(e, br, songs, pp, blk, s);
+}
+
+// The arguments of a pooled call, all checked on the host before anything is enqueued; `geom`: overlap (TFC) or step (Roformer).
+static int mdxc_pool_plan(const char *fn, asx_engine *e, bool rof, const asx_mdxc_song *songs, int32_t n_songs, int64_t geom, MdxcPoolPlan &pp) {
+  REQUIRE(e && n_songs >= 0 && (songs || n_songs == 0), "%s: null argument", fn);
+  std::vector<int64_t> Ns((size_t)n_songs);
+  for (int i = 0; i < n_songs; ++i) {
+    REQUIRE(songs[i].mix_dev && songs[i].out_dev, "%s: null pointer in song %d", fn, i);
+    REQUIRE(songs[i].n_samples >= 1, "%s: song %d: n_samples must be >= 1", fn, i);
+    Ns[i] = songs[i].n_samples;
+  }
+  CHK(mdxc_ready(e, rof, fn));
+  std::string err;
+  const bool ok = rof ? mdxc_pool_build_rof(e->cfg.hop_length, e->cfg.segment_size, geom, Ns.data(), n_songs, pp, err)
+                      : mdxc_pool_build_tfc(e->cfg.hop_length, e->cfg.segment_size, (int)geom, Ns.data(), n_songs, pp, err);
+  REQUIRE(ok, "%s: %s", fn, err.c_str());
+  return ASX_OK;
+}
+
+int asx_mdxc_demix_batch_dev(asx_engine *e, const asx_mdxc_song *songs, int32_t n_songs, int32_t overlap, void *stream) {
+  MdxcPoolPlan pp;
+  CHK(mdxc_pool_plan("asx_mdxc_demix_batch_dev", e, false, songs, n_songs, overlap, pp));
+  return n_songs ? mdxc_pool_demix(e, "asx_mdxc_demix_batch_dev", false, songs, pp, stream) : ASX_OK;
+}
+
+int asx_rof_demix_batch_dev(asx_engine *e, const asx_mdxc_song *songs, int32_t n_songs, int64_t step, void *stream) {
+  MdxcPoolPlan pp;
+  CHK(mdxc_pool_plan("asx_rof_demix_batch_dev", e, true, songs, n_songs, step, pp));
+  return n_songs ? mdxc_pool_demix(e, "asx_rof_demix_batch_dev", true, songs, pp, stream) : ASX_OK;
+}
+
+// ---- one song: a pool of one.  `mix` (chunks), `out` (fold) or both (demix) are given; errors name no song ---------------------
+static int mdxc_one_plan(const char *fn, asx_engine *e, bool rof, const void *a, const void *b, int64_t N, int64_t geom, MdxcPoolPlan &pp) {
+  REQUIRE(e && a && b, "%s: null argument", fn);
+  CHK(mdxc_ready(e, rof, fn));
+  const std::string why = rof ? mdxc_pool_push_rof(pp, e->cfg.hop_length, e->cfg.segment_size, geom, N)
+                              : mdxc_pool_push_tfc(pp, e->cfg.hop_length, e->cfg.segment_size, (int)geom, N);
+  REQUIRE(why.empty(), "%s", why.c_str());
+  return ASX_OK;
+}
+
+// chunks [k0, k1) of the song's loop (mdxc_separator.py:374-392 / :318-336) -> chunk_out [k1-k0, S, 2, chunk]
+static int mdxc_one_chunks(const char *fn, asx_engine *e, bool rof, const float *mix, int64_t N, int64_t geom, int32_t k0, int32_t k1,
+                           float *chunk_out, void *stream) {
+  MdxcPoolPlan pp;
+  CHK(mdxc_one_plan(fn, e, rof, mix, chunk_out, N, geom, pp));
+  REQUIRE(k0 >= 0 && k0 <= k1 && k1 <= pp.total(), "chunk range [%d, %d) outside [0, %d)", k0, k1, pp.total());
+  if (k1 == k0) return ASX_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  const MdxcBranch br = mdxc_branch(e, rof);
+  const asx_mdxc_song song{mix, nullptr, N};
+  int64_t blk = 0;
+  CHK(mdxc_pool_tables(e, fn, br, &song, pp, nullptr, s, &blk));
+  return mdxc_pool_chunks(e, br, pp, k0, k1, chunk_out, s);
+}
+
+// the fold of ALL chunks of the song (mdxc_separator.py:246-255, 394-404 / :310-343): chunk_out [n_chunks, S, 2, chunk] -> out
+static int mdxc_one_finalize(const char *fn, asx_engine *e, bool rof, const float *chunk_out, int64_t N, int64_t geom, float *out,
+                             void *stream) {
+  MdxcPoolPlan pp;
+  CHK(mdxc_one_plan(fn, e, rof, chunk_out, out, N, geom, pp));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  const MdxcBranch br = mdxc_branch(e, rof);
+  const asx_mdxc_song song{nullptr, out, N};
+  int64_t blk = 0;
+  CHK(mdxc_pool_tables(e, fn, br, &song, pp, chunk_out, s, &blk));
+  return mdxc_pool_fold(e, br, &song, pp, blk, s);
+}
+
+static int mdxc_one_demix(const char *fn, asx_engine *e, bool rof, const float *mix, int64_t N, int64_t geom, float *out, void *stream) {
+  MdxcPoolPlan pp;
+  CHK(mdxc_one_plan(fn, e, rof, mix, out, N, geom, pp));
+  const asx_mdxc_song song{mix, out, N};
+  return mdxc_pool_demix(e, fn, rof, &song, pp, stream);
+}
+
+int asx_mdxc_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t overlap, int32_t k0, int32_t k1, float *chunk_out_dev,
+                        void *stream) {
+  return mdxc_one_chunks("asx_mdxc_chunks_dev", e, false, mix_dev, N, overlap, k0, k1, chunk_out_dev, stream);
+}
+int asx_mdxc_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t N, int32_t overlap, float *out_dev, void *stream) {
+  return mdxc_one_finalize("asx_mdxc_finalize_dev", e, false, chunk_out_dev, N, overlap, out_dev, stream);
+}
+int asx_mdxc_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t overlap, float *out_dev, void *stream) {
+  return mdxc_one_demix("asx_mdxc_demix_dev", e, false, mix_dev, N, overlap, out_dev, stream);
+}
+int asx_rof_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int64_t step, int32_t k0, int32_t k1, float *chunk_out_dev,
+                       void *stream) {
+  return mdxc_one_chunks("asx_rof_chunks_dev", e, true, mix_dev, N, step, k0, k1, chunk_out_dev, stream);
+}
+int asx_rof_finalize_dev(asx_engine *e, const float *chunk_out_dev, int64_t N, int64_t step, float *out_dev, void *stream) {
+  return mdxc_one_finalize("asx_rof_finalize_dev", e, true, chunk_out_dev, N, step, out_dev, stream);
+}
 int asx_rof_demix_dev(asx_engine *e, const float *mix_dev, int64_t N, int64_t step, float *out_dev, void *stream) {
-  REQUIRE(e && mix_dev && out_dev, "asx_rof_demix_dev: null argument");
-  READY(e->rof, "asx_rof_demix_dev");
-  RofNet &n = *e->rof;
-  std::vector<int64_t> starts;
-  CHK(rof_starts(e, N, step, starts));
-  const int64_t C = (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1);
-  CHK(n.chunk_out.ensure(starts.size() * n.cfg.num_stems * 2 * C * 4));
-  CHK(asx_rof_chunks_dev(e, mix_dev, N, step, 0, (int32_t)starts.size(), n.chunk_out.f(), stream));
-  return asx_rof_finalize_dev(e, n.chunk_out.f(), N, step, out_dev, stream);
+  return mdxc_one_demix("asx_rof_demix_dev", e, true, mix_dev, N, step, out_dev, stream);
+}
+
+int asx_mdxc_demix(asx_engine *e, const float *mix_host, int64_t N, int32_t overlap, float *out_host) {
+  REQUIRE(e && mix_host && out_host, "asx_mdxc_demix: null argument");
+  REQUIRE(N >= 1, "n_samples must be >= 1");
+  READY(e->v3, "asx_mdxc_demix");
+  HIPCHK(hipSetDevice(e->device));
+  const int S = e->v3->cfg.num_targets;
+  return host_round_trip(mix_host, (size_t)2 * N, out_host, (size_t)S * 2 * N,
+                         [&](const float *mix, float *out) { return asx_mdxc_demix_dev(e, mix, N, overlap, out, nullptr); });
 }
 
 int asx_rof_demix(asx_engine *e, const float *mix_host, int64_t N, int64_t step, float *out_host) {
@@ -1982,44 +1963,6 @@ int asx_rof_demix(asx_engine *e, const float *mix_host, int64_t N, int64_t step,
   const int n_out = e->rof->cfg.n_out;
   return host_round_trip(mix_host, (size_t)2 * N, out_host, (size_t)n_out * 2 * N,
                          [&](const float *mix, float *out) { return asx_rof_demix_dev(e, mix, N, step, out, nullptr); });
-}
-
-// The Roformer branch for a pool of songs: as asx_mdxc_demix_batch_dev, with the Roformer chunk starts and the Hamming-weighted fold.
-int asx_rof_demix_batch_dev(asx_engine *e, const asx_mdxc_song *songs, int32_t n_songs, int64_t step, void *stream) {
-  std::vector<int64_t> Ns;
-  CHK(mdxc_pool_args("asx_rof_demix_batch_dev", e, songs, n_songs, Ns));
-  READY(e->rof, "asx_rof_demix_batch_dev");
-  if (n_songs == 0) return ASX_OK;
-  MdxcPoolPlan pp;
-  std::string err;
-  REQUIRE(mdxc_pool_build_rof(e->cfg.hop_length, e->cfg.segment_size, step, Ns.data(), n_songs, pp, err), "asx_rof_demix_batch_dev: %s",
-          err.c_str());
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  HIPCHK(hipSetDevice(e->device));
-  RofNet &n = *e->rof;
-  const int S = n.cfg.num_stems, n_out = n.cfg.n_out, nk = pp.total();
-  const int64_t C = pp.chunk_size, chunk_floats = (int64_t)S * 2 * C;
-  const int per = mdxc_pool_per_pass(nk, e->cfg.max_batch);
-  CHK(rof_ensure_workspace(e, per));
-  CHK(n.chunk_out.ensure((size_t)nk * chunk_floats * 4));
-  CHK(n.d_starts.ensure((size_t)nk * 8));
-  CHK(e->pool_wave.ensure((size_t)nk * 8));
-  CHK(e->pool_nsong.ensure((size_t)nk * 8));
-  CHK(e->pool_songs.ensure((size_t)n_songs * sizeof(MdxcPoolSong)));
-  int64_t *ds = reinterpret_cast<int64_t *>(n.d_starts.p);
-  int64_t blk = 0;
-  CHK(mdxc_pool_tables(e, "asx_rof_demix_batch_dev", songs, pp, true, chunk_floats, n.chunk_out.f(), ds, s, &blk));
-  for (int j = 0; j < nk; j += per) {
-    const int B = std::min(per, nk - j);
-    const PoolChunks pc{reinterpret_cast<const float *const *>(e->pool_wave.p) + j, reinterpret_cast<const int64_t *>(e->pool_nsong.p) + j};
-    CHK(rof_chunks_dev(e, nullptr, ds + j, 0, B, n.chunk_out.f() + (size_t)j * chunk_floats, s, &pc));
-  }
-  double bytes = 0.0;
-  for (int i = 0; i < n_songs; ++i) bytes += 4.0 * ((double)pp.starts[i].size() * chunk_floats + 2.0 * n_out * Ns[i]);
-  return timed(e, ASX_PROF_FINALIZE, 0.0, bytes, s, [&]() {
-    hipLaunchKernelGGL(roformer_finalize_pool_kernel, dim3((unsigned)blk, n_out * 2), dim3(256), 0, s,
-                       reinterpret_cast<const MdxcPoolSong *>(e->pool_songs.p), n_songs, S, C, step, n.d_window.f());
-  });
 }
 
 // ---- options -----------------------------------------------------------------------

@@ -756,27 +756,6 @@ __global__ __launch_bounds__(256) void stems_kernel(const float *__restrict__ de
 }
 
 // ---------------------------------------------------------------------------
-// MDXC (TFC branch) fold: accumulated[..., k*hop : k*hop+chunk] += out_k ; result = accumulated / overlap
-// (mdxc_separator.py:398-402).  Gather form over the covering chunks in increasing k.
-// chunk_out [n_chunks, S, 2, C];  out [S, 2, N];  sample i sits at padded position i + front.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mdxc_finalize_kernel(const float *__restrict__ chunk_out, int n_chunks, int S,
-                                                            int64_t C, int64_t hop, int64_t front, int64_t N,
-                                                            float overlap, float *__restrict__ out) {
-  const int sc = blockIdx.y;  // s*2 + ch
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  const int64_t m = i + front;
-  int64_t k_hi = m / hop;
-  if (k_hi > n_chunks - 1) k_hi = n_chunks - 1;
-  int64_t k_lo = 0;
-  if (m - C >= 0) k_lo = (m - C) / hop + 1;
-  float acc = 0.f;
-  for (int64_t k = k_lo; k <= k_hi; ++k) acc += chunk_out[((k * S * 2) + sc) * C + (m - k * hop)];
-  out[(int64_t)sc * N + i] = acc / overlap;
-}
-
-// ---------------------------------------------------------------------------
 // TFC-TDF v3 pre-activation blocks: InstanceNorm2d(affine) / GroupNorm statistics and norm -> act.
 // x is a channel-slice view [B, C, P] (P = T*F) with batch stride x_bstride.
 // stats[b*C + c] = (mean, 1/sqrt(var + eps)), biased variance, accumulated in float64.

@@ -1,5 +1,5 @@
-// A pool of songs on the MDXC plugin's two demix loops (asx_mdxc_demix_batch_dev / asx_rof_demix_batch_dev): the chunks of all
-// songs stand one after the other in one chunk buffer [total, S, 2, C] and go through the STFT / net / iSTFT launches in passes that
+// A pool of songs on the MDXC plugin's two demix loops (asx_mdxc_demix_batch_dev / asx_rof_demix_batch_dev; the single-song
+// calls run a pool of one -- these are the plugin's only table and fold kernels): the chunks of all songs stand one after the other in one chunk buffer [total, S, 2, C] and go through the STFT / net / iSTFT launches in passes that
 // may straddle songs (stft_pool_kernel reads chunk b from ITS song, kernels_fft.h PoolChunks).  Per-song are only the tables
 // below, built on the device from launch arguments (no host copy: the call stays stream-ordered), and the two folds.
 #pragma once
@@ -66,9 +66,9 @@ __device__ __forceinline__ int mdxc_pool_find(const MdxcPoolSong *__restrict__ s
   return lo;
 }
 
-// mdxc_finalize_kernel for every song of a pool in one launch: grid.x = the songs' workgroups one after the other, grid.y = S * 2.
-// Per sample the sum over the covering chunks of the sample's own song in increasing k, divided by overlap -- the single-song
-// kernel's additions in its order, so the same float.
+// TFC branch fold (mdxc_separator.py:398-402): accumulated[..., k*hop : k*hop+chunk] += out_k ; result = accumulated / overlap, for
+// every song of a pool in one launch: grid.x = the songs' workgroups one after the other, grid.y = S * 2.  Gather form: per sample the
+// sum over the covering chunks of the sample's own song in increasing k; sample i sits at padded position i + front.
 __global__ __launch_bounds__(256) void mdxc_finalize_pool_kernel(const MdxcPoolSong *__restrict__ songs, int n_songs, int S, int64_t C,
                                                                  int64_t hop, int64_t front, float overlap) {
   const MdxcPoolSong sg = songs[mdxc_pool_find(songs, n_songs)];
@@ -87,10 +87,10 @@ __global__ __launch_bounds__(256) void mdxc_finalize_pool_kernel(const MdxcPoolS
   sg.out[(int64_t)sc * N + i] = acc / overlap;
 }
 
-// roformer_finalize_kernel for every song of a pool in one launch: grid.y = n_out * 2.  That kernel walks ALL chunks of its song in
-// increasing k and skips the ones that do not cover the sample; this one visits only the chunks that can cover it
-// (rof_fold_range: the regular ones, then the re-anchored tail chunks), in the same order -- the same additions into acc and cnt,
-// and work per sample bounded by the geometry (about 2 C / step chunks), not by the song's or the pool's chunk count.
+// Roformer fold (mdxc_separator.py:320-343): result += x * w, counter += w, out = result / clamp(counter, 1e-10), for every song of
+// a pool in one launch: grid.y = n_out * 2, out row o reads chunk stem o % S (the reference broadcasts a single-stem output over
+// len(instruments) rows).  Per sample the chunks k with 0 <= i - start_k < C in increasing k -- rof_fold_range: the regular ones, then
+// the re-anchored tail chunks -- so work per sample is bounded by the geometry (about 2 C / step chunks), not by the chunk count.
 __global__ __launch_bounds__(256) void roformer_finalize_pool_kernel(const MdxcPoolSong *__restrict__ songs, int n_songs, int S, int64_t C,
                                                                      int64_t step, const float *__restrict__ window) {
   const MdxcPoolSong sg = songs[mdxc_pool_find(songs, n_songs)];

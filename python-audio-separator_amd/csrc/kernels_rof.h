@@ -827,30 +827,4 @@ __global__ __launch_bounds__(256) void mel_mask_merge_kernel(const float *__rest
   mask[idx] = acc / fmaxf((float)(j1 - j0 + 1), 1e-8f);
 }
 
-// ---------------------------------------------------------------------------
-// Roformer chunk fold (mdxc_separator.py:320-343): result += x * w, counter += w,
-// out = result / clamp(counter, 1e-10); chunk k covers [starts[k], starts[k] + C).
-// chunk_out [n_chunks, S, 2, C];  out [n_out, 2, N] where stem row o reads chunk stem (o % S)
-// (the reference broadcasts a single-stem output over len(instruments) rows).
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void roformer_finalize_kernel(const float *__restrict__ chunk_out,
-                                                                const int64_t *__restrict__ starts, int n_chunks, int S,
-                                                                int64_t C, const float *__restrict__ window, int64_t N,
-                                                                float *__restrict__ out) {
-  const int oc = blockIdx.y;  // o*2 + ch
-  const int o = oc >> 1, ch = oc & 1;
-  const int s = o % S;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  float acc = 0.f, cnt = 0.f;
-  for (int k = 0; k < n_chunks; ++k) {
-    const int64_t j = i - starts[k];
-    if (j < 0 || j >= C) continue;
-    const float w = window[j];
-    acc += chunk_out[(((int64_t)k * S + s) * 2 + ch) * C + j] * w;
-    cnt += w;
-  }
-  out[(int64_t)oc * N + i] = acc / fmaxf(cnt, 1e-10f);
-}
-
 }  // namespace asx

@@ -1,7 +1,7 @@
 // The chunk plans of the MDXC plugin's two demix loops on the host (no HIP): the TFC branch (mdxc_separator.py:361-402 -- front
 // zeros, pad, Tensor.unfold) and the Roformer branch (:298-341 -- starts 0, step, ... < N with the tail re-anchored to N - C), for
 // one song and for a pool of songs (asx_mdxc_demix_batch_dev / asx_rof_demix_batch_dev): every song's first pooled chunk and the
-// passes that cut the pooled list.  Included by asx.hip -- asx_mdxc_plan and rof_starts are these functions -- by the fold kernels
+// passes that cut the pooled list.  Included by asx.hip -- asx_mdxc_plan, asx_rof_plan and every demix call are these functions -- by the fold kernels
 // (the chunk range of a sample) and, for the host test, by tests/host/mdxc_pool_host.cpp.
 #pragma once
 #include <cstdint>
@@ -89,57 +89,64 @@ MDXC_PLAN_HD static inline RofFoldRange rof_fold_range(int64_t i, int64_t N, int
 // The chunks of all songs stand one after the other in song order; song i owns pooled chunks [chunk0[i], chunk0[i + 1]).
 struct MdxcPoolPlan {
   int64_t chunk_size = 0, step = 0, front = 0;
-  std::vector<int> chunk0;                 // n_songs + 1 entries
+  int overlap = 0;                         // TFC branch: the fold's divisor
+  std::vector<int> chunk0 = {0};           // n_songs + 1 entries
   std::vector<MdxcTfcPlan> tfc;            // TFC branch: per song
   std::vector<std::vector<int64_t>> starts;   // Roformer branch: per song
-  int total() const { return chunk0.empty() ? 0 : chunk0.back(); }
+  int total() const { return chunk0.back(); }
 };
 
-static inline std::string mdxc_pool_add(MdxcPoolPlan &pp, int song, int64_t n_chunks) {
+static inline std::string mdxc_pool_add(MdxcPoolPlan &pp, int64_t n_chunks) {
   const int64_t total = (int64_t)pp.chunk0.back() + n_chunks;
-  if (total >= ((int64_t)1 << 30)) return "song " + std::to_string(song) + ": " + std::to_string(total) + " chunks in one pool";
+  if (total >= ((int64_t)1 << 30)) return std::to_string(total) + " chunks in one pool";
   pp.chunk0.push_back((int)total);
+  return "";
+}
+
+// One more song behind the ones `pp` holds: "" or why not, `pp` then unchanged.  A single-song call is these on an empty plan.
+static inline std::string mdxc_pool_push_tfc(MdxcPoolPlan &pp, int hop, int dim_t, int overlap, int64_t N) {
+  MdxcTfcPlan p;
+  std::string why = mdxc_tfc_plan(hop, dim_t, N, overlap, p);
+  if (why.empty()) why = mdxc_pool_add(pp, p.n_chunks);
+  if (!why.empty()) return why;
+  pp.tfc.push_back(p);
+  pp.chunk_size = p.chunk_size;
+  pp.step = p.step;
+  pp.front = p.front;
+  pp.overlap = overlap;
+  return "";
+}
+
+static inline std::string mdxc_pool_push_rof(MdxcPoolPlan &pp, int hop, int dim_t, int64_t step, int64_t N) {
+  std::vector<int64_t> st;
+  std::string why = rof_plan_starts(N, (int64_t)hop * (dim_t - 1), step, st);
+  if (why.empty()) why = mdxc_pool_add(pp, (int64_t)st.size());
+  if (!why.empty()) return why;
+  pp.starts.push_back(st);
+  pp.chunk_size = (int64_t)hop * (dim_t - 1);
+  pp.step = step;
   return "";
 }
 
 // false (and `err`, naming the song) when any one song is rejected: the caller then enqueues nothing.
 static inline bool mdxc_pool_build_tfc(int hop, int dim_t, int overlap, const int64_t *Ns, int n_songs, MdxcPoolPlan &pp, std::string &err) {
   pp = MdxcPoolPlan();
-  pp.chunk0.push_back(0);
-  for (int i = 0; i < n_songs; ++i) {
-    MdxcTfcPlan p;
-    std::string why = mdxc_tfc_plan(hop, dim_t, Ns[i], overlap, p);
-    if (why.empty()) why = mdxc_pool_add(pp, i, p.n_chunks);
-    else why = "song " + std::to_string(i) + ": " + why;
-    if (!why.empty()) {
-      err = why;
-      return false;
-    }
-    pp.tfc.push_back(p);
-    pp.chunk_size = p.chunk_size;
-    pp.step = p.step;
-    pp.front = p.front;
+  err.clear();
+  for (int i = 0; i < n_songs && err.empty(); ++i) {
+    const std::string why = mdxc_pool_push_tfc(pp, hop, dim_t, overlap, Ns[i]);
+    if (!why.empty()) err = "song " + std::to_string(i) + ": " + why;
   }
-  return true;
+  return err.empty();
 }
 
 static inline bool mdxc_pool_build_rof(int hop, int dim_t, int64_t step, const int64_t *Ns, int n_songs, MdxcPoolPlan &pp, std::string &err) {
   pp = MdxcPoolPlan();
-  pp.chunk0.push_back(0);
-  pp.chunk_size = (int64_t)hop * (dim_t - 1);
-  pp.step = step;
-  for (int i = 0; i < n_songs; ++i) {
-    std::vector<int64_t> st;
-    std::string why = Ns[i] < 1 ? std::string("n_samples must be >= 1") : rof_plan_starts(Ns[i], pp.chunk_size, step, st);
-    if (why.empty()) why = mdxc_pool_add(pp, i, (int64_t)st.size());
-    else why = "song " + std::to_string(i) + ": " + why;
-    if (!why.empty()) {
-      err = why;
-      return false;
-    }
-    pp.starts.push_back(st);
+  err.clear();
+  for (int i = 0; i < n_songs && err.empty(); ++i) {
+    const std::string why = Ns[i] < 1 ? std::string("n_samples must be >= 1") : mdxc_pool_push_rof(pp, hop, dim_t, step, Ns[i]);
+    if (!why.empty()) err = "song " + std::to_string(i) + ": " + why;
   }
-  return true;
+  return err.empty();
 }
 
 // chunks per net pass for a pool of `total` chunks (8 when max_batch is 0, as the single-song calls)

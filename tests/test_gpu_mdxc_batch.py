@@ -1,10 +1,10 @@
 """asx_mdxc_demix_batch_dev / asx_rof_demix_batch_dev: a pool of songs whose chunks share the net passes, on the toy nets of
 test_gpu_mdxc.py and test_gpu_roformer.py.
 
-Both nets give the same floats whatever the number of chunks in a pass (``test_batching_is_invisible`` in those two files), and the
-pooled folds add the covering chunks of a sample in the single-song kernels' order, so every pooled output is held to
-np.array_equal on the uint32 view against the single-song call on the same engine; the library's pass counters prove that the
-chunks really were pooled."""
+Both nets give the same floats whatever the number of chunks in a pass (``test_batching_is_invisible`` in those two files), and a
+single-song call is a pool of one song through the same loop and fold, so every pooled output is held to np.array_equal on the
+uint32 view against the single-song call on the same engine; the library's pass counters prove that the chunks really were
+pooled.  The two folds alone are held to their definition on chunk buffers the tests make up."""
 import filecmp
 import os
 
@@ -188,6 +188,77 @@ def test_sharding_adaptor_runs_the_pooled_call(A):
     assert eng.counter("v3_net_passes") - n0 == passes(3 * eng.mdxc_plan(n, 4)["n_chunks"], 5)
     for s in range(3):
         assert same_bits(pipe.outs[0][s].cpu().numpy(), want[s]), s
+    eng.close()
+
+
+# ---- the folds alone, against their definition ------------------------------------------------------------------------------
+def run_fold(eng, kind, chunks, n, arg, rows):
+    """*_finalize_dev on a chunk buffer of the test's own -> out [rows, 2, n] (NaN where the fold wrote nothing)"""
+    import torch
+    d_chunks = torch.from_numpy(chunks).cuda()
+    d_out = torch.full((rows, 2, n), float("nan"), dtype=torch.float32, device="cuda")
+    call = eng.mdxc_finalize_dev if kind == "tfc" else eng.rof_finalize_dev
+    call(d_chunks.data_ptr(), n, arg, d_out.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return d_out.cpu().numpy()
+
+
+def test_tfc_fold_equals_the_reference_loop(A):
+    """mdxc_separator.py:394-404 on chunks the test makes up: ``accumulated[k*step : k*step+C] += chunk_k``, the front zeros cropped,
+    ``/ overlap``.  Integer-valued chunks in [-8, 8] and overlap a power of two: every partial sum and the division are exact in
+    float32, so the fold must EQUAL the loop whatever order it adds in."""
+    eng = TM.demixer(A, TM.CFG2, 5, 4).engine
+    S, C = eng.v3_cfg.num_targets, 240
+    rng = np.random.default_rng(900)
+    for overlap in (1, 2, 4, 8):
+        for n in (1, 100, 240, 241, 3000):
+            step = C // overlap                                             # mdxc_separator.py:364-374
+            pad = step - (n - C) % step
+            front = C - step
+            length = front + n + pad + C - step
+            nk = (length - C) // step + 1
+            plan = eng.mdxc_plan(n, overlap)
+            assert (plan["n_chunks"], plan["step"], plan["trim"], plan["padded_len"]) == (nk, step, front, length)
+            chunks = rng.integers(-8, 9, (nk, S, 2, C)).astype(np.float32)
+            acc = np.zeros((S, 2, length), np.float32)
+            for k in range(nk):
+                acc[..., k * step:k * step + C] += chunks[k]
+            want = acc[..., front:front + n] / np.float32(overlap)
+            got = run_fold(eng, "tfc", chunks, n, overlap, S)
+            assert same_bits(got, want), (overlap, n)
+    eng.close()
+
+
+def test_roformer_fold_against_float64(A):
+    """mdxc_separator.py:310-343 on standard-normal chunks: every chunk k with 0 <= i - start_k < C, in increasing k, adds
+    ``x_k * w`` to the result and ``w`` to the counter; out = result / clamp(counter, 1e-10), w = float32(float64 Hamming) as the
+    engine builds it.  Reference in float64.  For a sample covered by n chunks the bound is (2n + 6) * 2^-24 * sum|x_k w| / sum w:
+    float32 rounding of n products and n additions in the numerator, n additions in the denominator and one division (each a
+    relative 2^-24 of a term bounded by sum|x_k w| / sum w); the rest covers the window table's own rounding."""
+    eng = TR.demixer(A, TR.CFG, 7, 2).engine
+    S, rows, C = eng.rof_cfg.num_stems, eng.rof_cfg.n_out, 320
+    assert rows > S == 1                                                    # out row o reads chunk stem o % S
+    w = (0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(C) / (C - 1))).astype(np.float32).astype(np.float64)
+    rng = np.random.default_rng(901)
+    for step in (200, 320):
+        for n in (320, 321, 640, 777, 1500):
+            starts = [n - C if i + C > n else i for i in range(0, n, step)]  # mdxc_separator.py:320-341
+            assert eng.rof_plan(n, step) == {"n_chunks": len(starts), "chunk_size": C}
+            chunks = rng.standard_normal((len(starts), S, 2, C)).astype(np.float32)
+            num, mag, den, cover = (np.zeros((S, 2, n)) for _ in range(4))
+            for k, st in enumerate(starts):
+                num[..., st:st + C] += chunks[k].astype(np.float64) * w
+                mag[..., st:st + C] += np.abs(chunks[k].astype(np.float64)) * w
+                den[..., st:st + C] += w
+                cover[..., st:st + C] += 1
+            assert cover.min() >= 1
+            want = num / np.maximum(den, 1e-10)
+            tol = (2 * cover + 6) * 2.0 ** -24 * mag / den
+            got = run_fold(eng, "rof", chunks, n, step, rows)
+            for o in range(rows):
+                err = np.abs(got[o].astype(np.float64) - want[o % S])
+                print("rof fold step", step, "n", n, "row", o, "max err / tol", float((err / tol[o % S]).max()))
+                assert np.isfinite(got[o]).all() and (err <= tol[o % S]).all(), (step, n, o)
     eng.close()
 
 

@@ -50,6 +50,9 @@ def test_roformer_halves(A):
     ad = RoformerAdapter(dm.engine, 200)
     assert np.array_equal(sharded_demix(ad, mix).cpu().numpy(), want)
     assert np.array_equal(_split_run(ad, mix, torch, 3), want)
+    nk = ad.plan(1700)["n_chunks"]                       # step 200, chunk 320: 9 chunks, the last two re-anchored to 1380
+    assert nk == 9
+    assert np.array_equal(_split_run(ad, mix, torch, nk), want)      # one call per chunk: ranges that start on a re-anchored chunk
 
 
 def test_mdxc_halves(A):
@@ -65,6 +68,7 @@ def test_mdxc_halves(A):
     ad = MdxcAdapter(dm.engine, 4)
     assert np.array_equal(sharded_demix(ad, mix).cpu().numpy(), want)
     assert np.array_equal(_split_run(ad, mix, torch, 4), want)
+    assert np.array_equal(_split_run(ad, mix, torch, ad.plan(1500)["n_chunks"]), want)      # one call per chunk
 
 
 def test_demucs_halves(A):

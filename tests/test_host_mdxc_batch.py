@@ -131,8 +131,8 @@ def test_invalid_songs_are_reported_by_index(host_exe):
 @pytest.mark.parametrize("step", [200, 320, 100])
 def test_bounded_fold_visits_exactly_the_covering_chunks(host_exe, step):
     """roformer_finalize_pool_kernel walks rof_fold_range's chunks: the regular ones [k_lo, k_hi], then the re-anchored ones
-    [r_lo, r_hi].  For every sample that list must be {k : 0 <= i - start_k < C} in increasing k -- what roformer_finalize_kernel's
-    walk over all chunks keeps -- and its length is bounded by the geometry."""
+    [r_lo, r_hi].  For every sample that list must be what the reference loop adds to it -- every chunk k with
+    0 <= i - start_k < C, in increasing k -- and its length is bounded by the geometry."""
     chunk = 320
     for n in ROF_LENGTHS:
         starts = np.array(ref_rof_starts(n, chunk, step))
