@@ -774,6 +774,12 @@ int asx_op_mha(asx_engine *e, const float *q_host, int64_t ldq, const float *k_h
  * conv3h_kernel at 48 channels, its producer waves compute the net's 1x1 input convolution (4 -> 48 channels, folded BatchNorm, ReLU) themselves
  * from the four spectrogram planes: no launch of its own, no 48-channel activation written to memory and read back.  0 = two launches.  A
  * GroupNorm net, another width or another 3x3 kernel: two launches either way.
+ * "conv3h_partial_scratch" (an option only, no environment variable): how the n launches that make one 48-channel output slice of a 96- or
+ * 144-channel conv3h_kernel layer hand their partial sum on.  1 (default) = through a private scratch buffer of the engine in the consumer
+ * waves' fragment order (every lane stores and re-loads its own accumulator quads, 1 KB contiguous per instruction; only the last launch of a
+ * slice writes the planar output); 0 = through the output tensor itself, in the planar layout.  The values and the order of the additions are
+ * the same: results are equal bit for bit, and "conv3h_launches" counts n x n per layer either way.  The scratch (24576 bytes per 4 x 32 tile of
+ * the largest sliced layer, times the batch) is allocated with the engine's workspaces, never at a launch.
  * "conv_down_bf16x6" / "conv_up_bf16x6" (ABI 7; also ASX_DOWN6 / ASX_UP6): 1 (default) = the 2 x 2 / stride-2 convolutions between the levels
  * (mdxnet.py:66-72) and the transposed ones of the decoder with their `x *= skip` (mdxnet.py:80-86, 113) run conv_down6_kernel / conv_up6_kernel
  * (csrc/kernels_updown6.h) while "gemm_bf16x6" is on: the arithmetic of that option -- both fp32 operands split EXACTLY into three bf16 parts, six

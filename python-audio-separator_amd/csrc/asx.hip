@@ -92,6 +92,7 @@ static const struct EngineOption {
     {"gemm_f16x3", &asx_engine::gemm_f16x3, &EngineKnobs::gemm_f16x3, opt_onoff},
     {"conv_direct_f16x3", &asx_engine::conv3h, &EngineKnobs::conv3h, opt_nonneg},
     {"conv_fuse_input", &asx_engine::conv_fuse_input, &EngineKnobs::conv_fuse_input, opt_onoff},
+    {"conv3h_partial_scratch", &asx_engine::conv3h_ps, &EngineKnobs::conv3h_ps, opt_onoff},
     {"conv_down_bf16x6", &asx_engine::down6, &EngineKnobs::down6, opt_onoff},
     {"conv_up_bf16x6", &asx_engine::up6, &EngineKnobs::up6, opt_onoff},
     {"gemm_pair_images", &asx_engine::pair_images, &EngineKnobs::pair_images, opt_onoff,
@@ -304,6 +305,7 @@ void asx_engine_destroy(asx_engine *e) {
   e->spec_in.release();
   e->spec_out.release();
   for (auto &r : e->R) r.release();
+  e->c3h_ps.release();
   e->H.release();
   e->frames.release();
   e->chunk_out.release();
@@ -1299,6 +1301,7 @@ int asx_op_conv(asx_engine *e, const char *op, const float *x_host, int32_t B, i
   CHK(dy.ensure(ny * 4));
   HIPCHK(hipMemset(dy.p, 0xff, ny * 4));  // NaN canary: every output element must be written
   if (kind == CK_UP) CHK(to_dev(dskip, aux_host, ny));
+  CHK(e->c3h_ps.ensure(conv3h_ps_need(L, B, t, f)));   // (the nets size it with their workspaces; to_host below waits before anything else can regrow it)
   CHK(conv_launch(e, L, dx.f(), dskip.f(), dy.f(), B, t, f, nullptr));
   CHK(to_host(y_host, dy, ny));
   return ASX_OK;

@@ -215,6 +215,8 @@ struct asx_engine {
   // a pool of songs (asx_demix_batch_dev / asx_separate_batch_dev): per-chunk song table (base pointer, length) beside d_starts / d_nact,
   // the per-song fold table (PoolSong), the dividers of the distinct song lengths, one peak word per song
   DevBuf pool_wave, pool_nsong, pool_songs, pool_div, pool_peak;
+  DevBuf c3h_ps;     // conv3h_kernel's partial sums between the slice launches of a 96- / 144-channel layer (Conv3hCfg::ps_bytes of the largest such
+                     // layer and batch); sized with the workspaces, never at a launch: a captured graph holds the pointer
   DevBuf gn_part;    // per-plane float64 (sum, sum of squares) of the GroupNorm variant of the net (asx_net_config.norm == 1)
   DevBuf d_div;      // divider of the chunk fold for div_key's plan (input-independent: built once, asx_finalize_dev)
   DivKey div_key;
@@ -226,7 +228,7 @@ struct asx_engine {
   hipEvent_t div_ev = nullptr;       // recorded behind the kernel that built d_div; a call on ANOTHER stream waits for it
   hipStream_t div_stream = nullptr;
   std::vector<DevBuf> skip;
-  // The ten engine options (asx_set_option / asx_get_option; asx_engine_create sets them from EngineKnobs, knobs.h).
+  // The eleven engine options (asx_set_option / asx_get_option; asx_engine_create sets them from EngineKnobs, knobs.h).
   // 3x3 / pad-1 convs of the ConvTDFNet and TFC-TDF-v3 nets: 3 = Winograd F(2x2,3x3) (conv_wino3_kernel, the default), 0 = the
   // direct kernel (conv_dma_kernel), 1 / 2 = the earlier Winograd generations (kept for A/B runs; experimental builds only).
   // ASX_WINOGRAD or asx_set_option("winograd", n).
@@ -249,12 +251,19 @@ struct asx_engine {
   // HQ_3 net down, equal on level 1, slower on level 0 (profiles/r05_wino6_forms.txt).  ASX_WINO6 or asx_set_option("winograd_bf16x6", n).
   int wino6 = 144;
   // 3x3 TFC convs of 48 n -> 48 n channels with at most this many channels run the DIRECT implicit GEMM on the fp16 x 3 arithmetic (conv3h_kernel,
-  // kernels_conv3h.h: 48 x 48 weight slices resident in LDS, no Winograd transforms; n x n launches per layer, the input slices summed through
-  // the output) while "winograd" is 3 and "gemm_bf16x6" / "gemm_f16x3" are on; 0: never.  Default 144: levels 0, 1 and 2 of the HQ_3 geometry --
+  // kernels_conv3h.h: 48 x 48 weight slices resident in LDS, no Winograd transforms; n x n launches per layer, the partial sum of an output slice
+  // handed from one input slice's launch to the next through the scratch c3h_ps -- option "conv3h_partial_scratch" below -- or through the
+  // output) while "winograd" is 3 and "gemm_bf16x6" / "gemm_f16x3" are on; 0: never.  Default 144: levels 0, 1 and 2 of the HQ_3 geometry --
   // 5.2-5.5 ms per launch of 55 chunks against 8.5-8.9 on conv_wino3_kernel at 48 channels, 6.0 against 8.0-8.2 at 96, 3.76 against 4.0-4.1
   // (conv_wino6_kernel) at 144; the image is packed up to 144 channels.
   // ASX_CONV3H or asx_set_option("conv_direct_f16x3", n).
   int conv3h = 144;
+  // 1 (default): the n launches of one 48-channel output slice of a 96- / 144-channel conv3h layer hand their partial sum on through the private
+  // scratch c3h_ps in the consumer waves' FRAGMENT order (every lane stores and re-loads its own accumulator quads: 1 KB contiguous per
+  // instruction, no lane swap) -- only the last launch of a slice writes the planar output, with the activation.  0: through the output tensor
+  // itself in the planar layout (a.prev = a.y: six stores / loads of eight separate 128-byte lines per wave and tile).  Same values, same order
+  // of additions: the results are equal bit for bit.  asx_set_option("conv3h_partial_scratch", n); no environment variable.
+  int conv3h_ps = 1;
   // 1 (default): the net's 1x1 input conv (4 -> 48 channels, folded BatchNorm, ReLU) is computed by the producer waves of the first TFC conv's
   // conv3h_kernel launch (its fused-input form) instead of in a launch of its own: the 48-channel level-0 activation is never written to
   // memory and read back.  0: two launches.  Only where the first 3x3 layer runs conv3h_kernel at 48 channels and the net uses BatchNorm.

@@ -270,6 +270,13 @@ static bool conv3h_takes(const asx_engine *e, const ConvLayer &L, bool dma, cons
          y_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
 }
 
+// bytes of partial-sum scratch (asx_engine::c3h_ps) a conv_launch of this layer on B items of T x F may use: whoever sizes the workspaces of a
+// net asks for every 3x3 layer and keeps the maximum (whatever the options say at that moment: they may change between two forwards)
+static size_t conv3h_ps_need(const ConvLayer &L, int B, int T, int F) {
+  if (L.kind != CK_3X3 || L.w3h.p == nullptr || L.cin <= Conv3hCfg::C || F % 32 != 0 || B <= 0 || T <= 0) return 0;
+  return (size_t)Conv3hCfg::ps_bytes(B, (T + 3) / 4, F / 32);
+}
+
 // x [B,cin,T,F] -> y
 static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const float *skip, float *y, int B, int T,
                        int F, hipStream_t s, const ConvView &v = ConvView()) {
@@ -373,7 +380,10 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
   if (conv3h_takes(e, L, dma, v.res, a.act, T, F, a.y_bstride, y)) {
     // direct implicit GEMM on the fp16 pipe, weights resident in LDS: one persistent 512-thread workgroup per CU (the walk assumes 8 XCDs x 32).
     // A layer of 48 n channels runs as n x n launches: for every 48-channel slice of the OUTPUT, the input slices one after the other, each
-    // added to the sum of those before it (a.prev = the output itself), bias with the first, activation with the last.
+    // added to the sum of those before it, bias with the first, activation with the last.  The partial sum goes from launch to launch through
+    // the scratch e->c3h_ps in fragment order (option "conv3h_partial_scratch"; only the last launch writes y) or through y itself (a.prev = y).
+    // One scratch serves every output slice: on the one stream, launch (ob, nb - 1) has consumed it before (ob + 1, 0) writes.  The walk
+    // arguments of all n x n launches are built HERE, once: the scratch forms rely on identical walks (kernels_conv3h.h, PS).
     const int nb = L.cin / Conv3hCfg::C;
     const int tilesT = (T + 3) / 4, tilesF = F / 32;
     // walk geometry: bands of 32 / 16 / 8 strips -- whole bands on the plane's width, charged for the extra block per segment of T and for how evenly
@@ -394,34 +404,47 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     grant_lds(&conv3h_kernel<0, false>, Conv3hCfg::LDS_BYTES);
     grant_lds(&conv3h_kernel<0, true>, Conv3hCfg::LDS_BYTES);
     grant_lds(&conv3h_kernel<0, false, true>, Conv3hCfg::LDS_BYTES);
+    grant_lds(&conv3h_kernel<0, false, false, 1>, Conv3hCfg::LDS_BYTES);
+    grant_lds(&conv3h_kernel<0, false, false, 2>, Conv3hCfg::LDS_BYTES);
+    grant_lds(&conv3h_kernel<0, false, false, 3>, Conv3hCfg::LDS_BYTES);
     const int64_t plane = (int64_t)T * F;
+    const bool ps = e->conv3h_ps > 0 && nb > 1;
+    const int64_t ps_item = Conv3hCfg::ps_item_bytes(tilesT, tilesF);
+    REQUIRE(!ps || (ps_item < ((int64_t)1 << 32) && e->c3h_ps.p != nullptr && e->c3h_ps.bytes >= conv3h_ps_need(L, B, T, F)),
+            "conv3h_kernel: the partial-sum scratch is not sized for %d x %d x %d (the workspace set-up sizes it)", B, T, F);
+    Conv3hArgs walk{};                                 // what every launch of the layer shares: the shape and the walk
+    walk.B = B;
+    walk.T = T;
+    walk.F = F;
+    walk.x_bstride = a.x_bstride;
+    walk.y_bstride = a.y_bstride;
+    walk.tilesT = tilesT;
+    walk.tilesF = tilesF;
+    walk.bw = bw;
+    walk.tps = (tilesT * bw) % 32 == 0 ? tilesT * bw / 32 : tilesT;
+    walk.ps = ps ? e->c3h_ps.p : nullptr;
+    walk.ps_bstride = ps_item;
     return timed(e, cls, flops, bytes, s, [&]() {
       e->prof_nprod = 3;
       for (int ob = 0; ob < nb; ++ob)
         for (int ib = 0; ib < nb; ++ib) {
-          Conv3hArgs ca{};
+          Conv3hArgs ca = walk;
           ca.x = x + (int64_t)ib * Conv3hCfg::C * plane;
           ca.y = y + (int64_t)ob * Conv3hCfg::C * plane;
-          ca.prev = ib > 0 ? ca.y : nullptr;
+          ca.prev = ib > 0 && !ps ? ca.y : nullptr;
           ca.wimg = reinterpret_cast<const u32x4 *>(reinterpret_cast<const uint32_t *>(L.w3h.p) + (size_t)(ob * nb + ib) * Conv3hCfg::IMG_U32);
           ca.bias = ib == 0 ? L.b.f() + ob * Conv3hCfg::C : nullptr;
-          ca.B = B;
-          ca.T = T;
-          ca.F = F;
-          ca.x_bstride = a.x_bstride;
-          ca.y_bstride = a.y_bstride;
           ca.act = ib == nb - 1 ? a.act : ACT_NONE;
-          ca.tilesT = tilesT;
-          ca.tilesF = tilesF;
-          ca.bw = bw;
-          ca.tps = (tilesT * bw) % 32 == 0 ? tilesT * bw / 32 : tilesT;
           if (v.fin) {                                 // (nb == 1) the algorithmic flops / bytes of the record stay the 3x3 layer's own
             ca.xin = v.fin_x;
             ca.xin_bstride = 4 * plane;
             ca.w1 = v.fin->w1f.f();
             hipLaunchKernelGGL((conv3h_kernel<0, false, true>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
             g_conv3h_fin_launches.fetch_add(1);
-          } else if (ib > 0) hipLaunchKernelGGL((conv3h_kernel<0, true>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
+          } else if (ps && ib == 0) hipLaunchKernelGGL((conv3h_kernel<0, false, false, 2>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);   // partial out
+          else if (ps && ib < nb - 1) hipLaunchKernelGGL((conv3h_kernel<0, false, false, 3>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);   // in and out, in place
+          else if (ps) hipLaunchKernelGGL((conv3h_kernel<0, false, false, 1>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);   // partial in, planar out
+          else if (ib > 0) hipLaunchKernelGGL((conv3h_kernel<0, true>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
           else hipLaunchKernelGGL((conv3h_kernel<0, false>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
           g_conv3h_launches.fetch_add(1);
         }
@@ -1329,6 +1352,15 @@ static int ensure_workspace(asx_engine *e, int Bchunks, bool need_net) {
       const size_t c = (size_t)e->net.g * (i + 1), t = T >> i, f = Fq >> i;
       CHK(e->skip[i].ensure(Bn * c * t * f * 4));
     }
+    // partial sums of the sliced conv3h layers (levels 1 and 2 of a 48-channel net): the largest need over the net's 3x3 layers
+    size_t ps = 0;
+    auto ps_block = [&](const Block &blk) {
+      for (const ConvLayer &L : blk.tfc) ps = std::max(ps, conv3h_ps_need(L, (int)Bn, blk.t, blk.f));
+    };
+    for (const Block &blk : e->enc) ps_block(blk);
+    ps_block(e->mid);
+    for (const Block &blk : e->dec) ps_block(blk);
+    CHK(e->c3h_ps.ensure(ps));
   }
   e->ws_batch = std::max(e->ws_batch, Bchunks);
   return ASX_OK;

@@ -249,6 +249,20 @@ static int v3_ensure_workspace(asx_engine *e, int B) {
     c += cf.growth;
     P /= 4;
   }
+  // conv3h_kernel's partial sums, where a tfc1 of 96 -> 96 / 144 -> 144 channels runs it (v3_core_dev's walk over the levels)
+  {
+    size_t ps = 0;
+    auto ps_blocks = [&](const std::vector<V3Block> &bs, int t, int f) {
+      for (const V3Block &b : bs) ps = std::max(ps, std::max(conv3h_ps_need(b.tfc1, B, t, f), conv3h_ps_need(b.tfc2, B, t, f)));
+    };
+    int t = T, f = Fs;
+    for (int i = 0; i < cf.num_scales; ++i, t /= 2, f /= 2) {
+      ps_blocks(n.enc[i], t, f);
+      ps_blocks(n.dec[cf.num_scales - 1 - i], t, f);
+    }
+    ps_blocks(n.mid, t, f);
+    CHK(e->c3h_ps.ensure(ps));
+  }
   CHK(n.out_spec.ensure((size_t)B * cf.num_targets * dim_c * P0 * 4));
   CHK(n.frames.ensure((size_t)B * cf.num_targets * 2 * T * e->cfg.n_fft * 4));
   n.ws_batch = B;

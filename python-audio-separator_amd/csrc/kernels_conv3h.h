@@ -1,7 +1,11 @@
 // 3x3 / pad 1 convolution of the TFC blocks (uvr_lib_v5/modules.py:11-17, mdxnet.py:97-113) as a DIRECT implicit GEMM on the fp16
 // matrix pipe with the fp16 x 3 arithmetic of kernels_gemm3.h (two-part operands, three products, fp32 accumulation) -- no Winograd
 // transforms, no cross-wave exchange.  One kernel for 48 -> 48 channels; layers of 96 / 144 channels run as 4 / 9 launches over 48-channel
-// slices (accumulate mode).  DESIGN.md 6k has the design record and the measurements behind every choice below.
+// slices: for every output slice the input slices one after the other, each launch adding its sum to the partial sum of those before it.  The
+// partial sum travels between two consecutive launches through a private scratch buffer in FRAGMENT order (template parameter PS: every lane
+// stores and re-loads its own six accumulator quads, 1 KB contiguous per instruction), or -- engine option "conv3h_partial_scratch" = 0 --
+// through the output tensor itself in the planar layout (accumulate mode, ACC).  DESIGN.md 6k has the design record and the measurements
+// behind every choice below.
 // Fused-input form (template flag FIN, engine option "conv_fuse_input"): for the net's FIRST 3x3 layer, x is relu(b1 + w1 xin), the 4 -> 48 1x1
 // input conv of the net -- the producers fetch the four planes of xin (four loads per item instead of eight) and form their eight channels in
 // registers in a fixed fma order; pixels outside the plane enter the ring as 0 (the padding is of the 48-channel activation).  The 1x1 conv's
@@ -56,6 +60,9 @@ struct Conv3hArgs {
   const float *xin;          // [B, 4, T, F] view (xin_bstride floats between batch items)
   const float *w1;           // w1 [48][4], then b1 [48] (BatchNorm folded)
   int64_t xin_bstride;
+  // partial-sum scratch (PS): [B][tilesF][tilesT][wave 4][store 6][lane 64] x 16 bytes (Conv3hCfg::ps_off), ps_bstride BYTES between batch items
+  void *ps;
+  int64_t ps_bstride;
 };
 
 struct Conv3hCfg {
@@ -74,6 +81,18 @@ struct Conv3hCfg {
   static constexpr int LDS_BYTES = TAB_OFF + 64;                  // maxima [2][4] floats, exponents [3] ints, 16 bytes of zeros at + 48
   static constexpr size_t IMG_U32 = WBYTES / 4 + 48;              // image size in 32-bit words
   static constexpr int EUP = 8;                                   // the running exponent of a walk follows a quieter block only when it is more than this many bits quieter
+
+  // Partial-sum scratch (template parameter PS of the kernel): the sum a launch hands to the next launch of the same output slice, in the order
+  // the consumer waves hold it.  Wave r of tile (b, strip, jt) owns six stores of 1 KB -- store k = accumulator (channel tile k / 2, pixel tile
+  // k % 2), lane l its own 16 bytes -- so a tile is 4 x 6 x 1024 = 24576 bytes = 48 channels x 4 rows x 32 pixels of fp32, and a batch item
+  // tilesF x tilesT tiles (strip major).  The offset inside an item stays a 32-bit number (the launcher checks); the item goes into the base.
+  static constexpr int PS_STORE = 1024, PS_WAVE = 6 * PS_STORE, PS_TILE = 4 * PS_WAVE;
+  static constexpr int64_t ps_item_bytes(int tilesT, int tilesF) { return (int64_t)tilesF * tilesT * PS_TILE; }
+  static constexpr int64_t ps_bytes(int B, int tilesT, int tilesF) { return (int64_t)B * ps_item_bytes(tilesT, tilesF); }   // the whole buffer
+  static constexpr unsigned ps_wave_off(int tilesT, int strip, int jt, int r) { return (unsigned)((strip * tilesT + jt) * 4 + r) * (unsigned)PS_WAVE; }   // inside the item
+  static constexpr int64_t ps_off(int tilesT, int tilesF, int b, int strip, int jt, int r, int k, int lane) {
+    return (int64_t)b * ps_item_bytes(tilesT, tilesF) + ps_wave_off(tilesT, strip, jt, r) + k * PS_STORE + lane * 16;
+  }
 
   // Stage plan of a consumer wave's tile.  A kernel row is four FULL stages (stage group sg: k groups 4 sg .. 4 sg + 3) and half a stage (k groups
   // 16, 17: stage group 4, a half fragment in the weight image).  Two half stages whose input rows lie in the SAME four-row block (one exponent)
@@ -281,9 +300,18 @@ struct Conv3hFinRegs<true> {
 // v = max(0, fma(w3, in3, fma(w2, in2, fma(w1, in1, fma(w0, in0, b))))) in this fixed order (a halo pixel is computed by two tiles: same bits),
 // at the step that first consumes the block (the maximum); a pixel outside the plane enters the ring as 0 -- the 3x3 conv pads the 48-channel
 // activation, not the four planes, so relu(b) must not leak in -- through the item's in-image predicate, kept beside the raw set.
-template <int ABL = 0, bool ACC = false, bool FIN = false>
+// PS: partial sums through the scratch a.ps (never with ACC or FIN; compile-time for the reason given at ACC).  Bit 1 (partial OUT: the launch
+// is not the last input slice of its output slice): the epilogue's values -- the ones the planar form would store, computed in the same order
+// -- go to the scratch, every lane its own six accumulator quads, no lane swap; bit 0 (partial IN): `prev` is the scratch, six loads at the
+// same addresses behind stage 7, each value added where the planar `prev` is added (behind the fma, in front of the activation).
+// INVARIANT: a launch with both bits reads and writes the SAME scratch in place, and a launch reads what the one before it wrote.  That is
+// safe because a lane only ever touches its own 16 bytes per (tile, store) -- loaded behind stage 7 of the tile, overwritten a step later --
+// and because the launches of one output slice walk identically: same B, T, F, tilesT, tilesF, bw, tps (the launcher builds them from one place).
+template <int ABL = 0, bool ACC = false, bool FIN = false, int PS = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3h_kernel(Conv3hArgs a) {
   using CFG = Conv3hCfg;
+  constexpr bool PIN = (PS & 1) != 0, POUT = (PS & 2) != 0;
+  static_assert(!(PS != 0 && (ACC || FIN)), "partial sums through the scratch: neither the planar accumulate mode nor the fused input");
   extern __shared__ float lds_f[];
   char *lds = reinterpret_cast<char *>(lds_f);
   const int tid = threadIdx.x;
@@ -523,10 +551,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (tid < 4) reinterpret_cast<unsigned *>(lds + CFG::TAB_OFF + 48)[tid] = 0u;   // (published by barrier P0)
     const int *wexp = reinterpret_cast<const int *>(a.wimg) + CFG::WBYTES / 4;
     int ew[3];
-    float bz[3];
+    float bz[3], wsc[3];                               // wsc = 2^-ew (the PS forms: one register per channel tile instead of the exponent and its sum with the tile's)
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       ew[c] = wexp[c * 16 + li];
+      wsc[c] = __builtin_ldexpf(1.0f, -ew[c]);
       bz[c] = a.bias ? a.bias[c * 16 + li] : 0.f;
     }
     // finished tile waiting for its stores (issued in the middle of the next step's MFMAs, when the producers' fetch burst has drained:
@@ -536,18 +565,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // li ^ 8 swap one of them (DPP row_ror:8).  Whole lines, nontemporal: the fetch + store skeleton of this kernel (no arithmetic at all,
     // tools/experimental/micro_fetch.hip) runs 3.97 ms per level-0 launch that way against 4.52 with half-line stores.
     f32x4 pend[6];                                     // store k = (channel tile k / 2, channel half k % 2)
-    int pend_vo = 0;                                   // byte offset of (channel li & 7, row, column f0 + chunk * 4) in the batch item
+    int pend_vo = 0;                                   // byte offset of (channel li & 7, row, column f0 + chunk * 4) in the batch item (partial out: of the wave's 6 KB, wave-uniform)
     __amdgpu_buffer_rsrc_t pend_rs = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, 0, 0x00020000);   // num_records 0: every store dropped
     int soff[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) soff[k] = (int)(((k / 2) * 16 + (k % 2) * 8) * TF * 4);
-    const bool hi8 = (li & 8) != 0;
-    const float act_lo = a.act == ACT_RELU ? 0.f : -__builtin_inff();
+    const unsigned ps_item = (unsigned)CFG::ps_item_bytes(a.tilesT, a.tilesF);
+    // (partial out: never an activation -- a constant, no register)
+    const float act_lo = !POUT && a.act == ACT_RELU ? 0.f : -__builtin_inff();
 
     auto flush_one = [&](auto kc) {
       constexpr int K = decltype(kc)::value;
       if constexpr ((ABL & 4) == 0) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pend[K]), pend_rs, pend_vo, soff[K], (ABL & 512) ? 0 : 2);
+        if constexpr (POUT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pend[K]), pend_rs, lane * 16, pend_vo + K * CFG::PS_STORE, (ABL & 512) ? 0 : 2);
+        else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pend[K]), pend_rs, pend_vo, soff[K], (ABL & 512) ? 0 : 2);
       } else {
         if (pend[K].x == 1.2345e-30f) a.y[0] = pend[K].y;   // keeps the arithmetic alive in the no-store build
       }
@@ -558,12 +589,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     int pend_e = 0;
     // accumulate mode (a.prev): the six lines of the other input slice's partial sums, fetched in the stores' own lane arrangement behind stage 7
     // of the tile they belong to (the previous tile's epilogue has used the registers by then) and added in front of the activation
+    // partial in (PIN): the same six registers hold the lane's own quads of the scratch, pprev[k] = accumulator (channel tile k / 2, pixel tile k % 2)
     f32x4 pprev[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) pprev[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
     auto epi_chunk = [&](auto kc) {                    // store k of the pending tile: channels (k / 2) * 16 + (k % 2) * 8 .. + 7, one whole 128-byte row each
       constexpr int K = decltype(kc)::value, c = K / 2;
-      const float sc = __builtin_ldexpf(1.0f, -(pend_e + ew[c]));   // exact power of two (|exponent| well inside the float range: weights and activations are)
+      // exact power of two (|exponent| well inside the float range: weights and activations are) -- the same number either way
+      const float sc = PS != 0 ? __builtin_ldexpf(wsc[c], -pend_e) : __builtin_ldexpf(1.0f, -(pend_e + ew[c]));
+      if constexpr (POUT) {
+        // partial out: store k is the lane's own accumulator (channel tile c, pixel tile k % 2) -- the planar form's values (the `fmaxf` against
+        // -inf included: it is what the planar form's intermediate launch does to a NaN), four fmas instead of eight and no lane swap
+        constexpr int qq = K % 2;
+        f32x4 o = (f32x4){__builtin_fmaf(pacc[qq][c].x, sc, bz[c]), __builtin_fmaf(pacc[qq][c].y, sc, bz[c]), __builtin_fmaf(pacc[qq][c].z, sc, bz[c]),
+                          __builtin_fmaf(pacc[qq][c].w, sc, bz[c])};
+        if constexpr (PIN) o += pprev[K];
+        pend[K] = (f32x4){fmaxf(o.x, act_lo), fmaxf(o.y, act_lo), fmaxf(o.z, act_lo), fmaxf(o.w, act_lo)};
+        return;
+      }
       f32x4 v[2];
 #pragma unroll
       for (int qq = 0; qq < 2; ++qq) {
@@ -571,6 +614,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         v[qq].y = __builtin_fmaf(pacc[qq][c].y, sc, bz[c]);
         v[qq].z = __builtin_fmaf(pacc[qq][c].z, sc, bz[c]);
         v[qq].w = __builtin_fmaf(pacc[qq][c].w, sc, bz[c]);
+        if constexpr (PIN) v[qq] += pprev[c * 2 + qq];   // in front of the lane swap: the element's own partial sum, where the planar form adds it
       }
       // even k: lanes li < 8 keep their own pixel tile 0, lanes li >= 8 take pixel tile 1 of lane li - 8; odd k: lanes li >= 8 keep their own
       // pixel tile 1, lanes li < 8 take pixel tile 0 of lane li + 8 (`v_mov_b32_dpp row_ror:8` written under a bank mask: one instruction per
@@ -604,7 +648,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     conv3h_walk_init(a, wg, wk);
     int s3 = 0;                                        // s % 3
     for (int s = 0; s < NB; ++s) {
-      const int tb = wk.b, j = wk.j, f0 = wk.strip * 32;
+      const int tb = wk.b, j = wk.j, wk_strip = wk.strip, f0 = wk_strip * 32;
       conv3h_walk_next(a, wg, wk);
       if constexpr ((ABL & 32) != 0) {
         if (wg == 0 && wave == 0 && s < 64) {
@@ -617,6 +661,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int tt = row0 + j * 4 + wave;
         const bool cur_ok = tt < a.T && f0 < a.F;
         const int cur_vo = (((li & 7) * a.T + tt) * a.F + f0 + ((li >> 3) * 4 + g) * 4) * 4;
+        // the wave's 6 KB of the scratch: wave-uniform (a scalar offset of the loads and stores), the lane adds lane * 16 (cur_ok: strip < tilesF, tile row < tilesT)
+        const int cur_ps = (int)CFG::ps_wave_off(a.tilesT, wk_strip, (row0 >> 2) + j, wave);
         // rows of the tile: u = 0, 1 = the last two rows of the previous block, u = 2..5 = this block; wave r, kernel row ky reads u = r + ky
         const int sp = s3 == 0 ? 2 : s3 - 1;
         const int e_cur = __builtin_amdgcn_readfirstlane(exps[s3]), e_old = __builtin_amdgcn_readfirstlane(exps[sp]);
@@ -693,6 +739,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
+          if constexpr (PIN && S == 7) {
+            __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(static_cast<char *>(a.ps) + (int64_t)tb * a.ps_bstride, 0, cur_ok ? ps_item : 0u, 0x00020000);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) pprev[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(prs, lane * 16, cur_ps + k * CFG::PS_STORE, 0));
+            __builtin_amdgcn_sched_barrier(0);
+          }
           if constexpr (ACC && S == 7) {
             __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.prev + (int64_t)tb * a.y_bstride), 0, cur_ok ? plane_bytes : 0u, 0x00020000);
 #pragma unroll
@@ -736,8 +788,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int c = 0; c < 3; ++c) pacc[qq][c] = acc[qq][c];
         pend_e = e_cur;
-        pend_rs = __builtin_amdgcn_make_buffer_rsrc(a.y + (int64_t)tb * a.y_bstride, 0, cur_ok ? plane_bytes : 0u, 0x00020000);
-        pend_vo = cur_vo;
+        if constexpr (POUT) {
+          pend_rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<char *>(a.ps) + (int64_t)tb * a.ps_bstride, 0, cur_ok ? ps_item : 0u, 0x00020000);
+          pend_vo = cur_ps;
+        } else {
+          pend_rs = __builtin_amdgcn_make_buffer_rsrc(a.y + (int64_t)tb * a.y_bstride, 0, cur_ok ? plane_bytes : 0u, 0x00020000);
+          pend_vo = cur_vo;
+        }
         if constexpr ((ABL & 128) != 0) flush();
       } else {
         flush();                                       // first block of an item: nothing to compute yet

@@ -1,7 +1,7 @@
 // Stand-alone harness of the direct fp16 x 3 convolution kernel (python-audio-separator_amd/csrc/kernels_conv3h.h): a float64 direct
 // convolution on small shapes (borders, ragged sizes) and on sampled outputs of the HQ_3 level-0 shape, then time per launch.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/proto_conv3h tools/proto_conv3h.hip
-//   tools/proto_conv3h [abl] [order] [B of the timing shape] [reps]
+//   tools/proto_conv3h [abl] [order] [B of the timing shape] [reps] [quick] [alias] [bw] [partial sums through the scratch: 1 / 0]
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -39,6 +39,19 @@ static void launch(const Conv3hArgs &a, hipStream_t s) {
   }
   if (a.prev) hipLaunchKernelGGL((conv3h_kernel<ABL, true>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, a);
   else hipLaunchKernelGGL((conv3h_kernel<ABL, false>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, a);
+}
+// the partial-sum forms (template parameter PS: bit 0 = partial in, bit 1 = partial out), plain build only
+static void launch_ps(int ps, const Conv3hArgs &a, hipStream_t s) {
+  static bool done = false;
+  if (!done) {
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3h_kernel<0, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, Conv3hCfg::LDS_BYTES));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3h_kernel<0, false, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, Conv3hCfg::LDS_BYTES));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3h_kernel<0, false, false, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, Conv3hCfg::LDS_BYTES));
+    done = true;
+  }
+  if (ps == 1) hipLaunchKernelGGL((conv3h_kernel<0, false, false, 1>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, a);
+  else if (ps == 2) hipLaunchKernelGGL((conv3h_kernel<0, false, false, 2>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, a);
+  else hipLaunchKernelGGL((conv3h_kernel<0, false, false, 3>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, a);
 }
 static void launch_abl(int abl, const Conv3hArgs &a, hipStream_t s) {
   switch (abl) {
@@ -86,6 +99,7 @@ static double ref_at(const std::vector<float> &x, const std::vector<float> &w, c
 }
 
 static int g_bw = 32;      // strips per band (argv[7]: 32, 16, 8)
+static int g_ps = 1;       // 96 -> 96 layer: partial sums through the fragment-order scratch (argv[8]; 0: through the output, planar)
 static int g_alias = 0;   // 1: every batch item reads item 0's planes, 2: and writes item 0's output (cache-resident traffic: is the launch DRAM- or CU-bound?)
 static int run_shape(const Shape &sh, int abl, int order, int reps) {
   const int C = 48;
@@ -235,7 +249,8 @@ static int run_shape(const Shape &sh, int abl, int order, int reps) {
 }
 
 // A 96 -> 96 layer as four launches of the 48-channel kernel: for each half of the output channels, the first half of the input channels
-// (bias, no activation), then the second half ADDED to it (a.prev = the output itself) with the activation.
+// (bias, no activation), then the second half ADDED to it with the activation -- the partial sum goes through the fragment-order scratch
+// (g_ps) or through the output itself (a.prev = the output).
 static int run_shape96(const Shape &sh, int reps) {
   const int C = 96;
   const size_t nb = (size_t)C * sh.T * sh.F, n = nb * sh.B;
@@ -272,13 +287,18 @@ static int run_shape96(const Shape &sh, int reps) {
     }
   long long *ddbg = nullptr;
   CK(hipMalloc(&ddbg, (512 + 4 * 2048) * 8));
+  void *dps = nullptr;
+  const int64_t ps_item = Conv3hCfg::ps_item_bytes((sh.T + 3) / 4, sh.F / 32);
+  CK(hipMalloc(&dps, (size_t)Conv3hCfg::ps_bytes(sh.B, (sh.T + 3) / 4, sh.F / 32)));
   auto go = [&]() {
     for (int ob = 0; ob < 2; ++ob)
       for (int ib = 0; ib < 2; ++ib) {
         Conv3hArgs a{};
         a.x = dx + (size_t)ib * 48 * sh.T * sh.F;
         a.y = dy + (size_t)ob * 48 * sh.T * sh.F;
-        a.prev = ib ? a.y : nullptr;
+        a.prev = ib && !g_ps ? a.y : nullptr;
+        a.ps = dps;
+        a.ps_bstride = ps_item;
         a.wimg = reinterpret_cast<const u32x4 *>(dimg[ob][ib]);
         a.bias = ib ? nullptr : dbias + ob * 48;
         a.B = sh.B;
@@ -295,7 +315,8 @@ static int run_shape96(const Shape &sh, int reps) {
           a.tps = a.tilesT;
         }
         a.dbg = ddbg;
-        launch<0>(a, 0);
+        if (g_ps) launch_ps(ib ? 1 : 2, a, 0);
+        else launch<0>(a, 0);
       }
   };
   go();
@@ -353,10 +374,11 @@ static int run_shape96(const Shape &sh, int reps) {
     CK(hipEventSynchronize(e1));
     float ms = 0;
     CK(hipEventElapsedTime(&ms, e0, e1));
-    printf("  %s: %.3f ms per 96 -> 96 layer (four launches), bw %d\n", sh.name, ms / reps, g_bw);
+    printf("  %s: %.3f ms per 96 -> 96 layer (four launches), bw %d, partial sums %s\n", sh.name, ms / reps, g_bw, g_ps ? "scratch" : "planar");
   }
   CK(hipFree(dx));
   CK(hipFree(dy));
+  CK(hipFree(dps));
   return bad;
 }
 
@@ -368,6 +390,7 @@ int main(int argc, char **argv) {
   const int quick = argc > 5 ? atoi(argv[5]) : 0;      // 1: the timing shape only (profiling runs)
   g_alias = argc > 6 ? atoi(argv[6]) : 0;
   g_bw = argc > 7 ? atoi(argv[7]) : 32;
+  g_ps = argc > 8 ? atoi(argv[8]) : 1;
   int bad = 0;
   if (abl == 0 && !quick) {
     const Shape small[] = {
