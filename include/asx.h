@@ -747,6 +747,34 @@ int asx_op_attention(asx_engine *e, const float *qkv_host, const float *gate_hos
 int asx_op_mha(asx_engine *e, const float *q_host, int64_t ldq, const float *k_host, int64_t ldk, const float *v_host, int64_t ldv,
                const float *decay_host, int64_t ldd, int32_t batch, int32_t nq, int32_t nk, int32_t heads, int32_t dh, int32_t exact,
                const char *variant, float *out_host, int64_t ldo, int32_t *resolved);
+/* (ABI 7) Single launches of the recurrent kernels, through the engines' own launch code -- single-op test hooks like asx_op_mha: host
+ * buffers, no net needed; every output is read as well as written (its contents are uploaded first, so elements the kernel does not own
+ * keep them); a shape the kernels are not built for is ASX_ERR_INVALID, never a launch.
+ *
+ * asx_op_hd_lstm_layer: the recurrence of one bidirectional nn.LSTM layer of the BLSTM of HDemucs / Demucs v3 (demucs.py:19-66) for n
+ * independent sequences of `steps` steps from zero state: h and c are zeroed, then hd_lstm_step_kernel runs `steps` times.
+ * xp [steps * n, 2, 4h] (row step * n + sequence; the input projection plus both biases of direction 0 | 1, gate order i, f, g, o),
+ * whh [2, 4h, h], out [steps * n, 2h] (forward half | reverse half; the reverse direction walks steps-1 .. 0), c_host (optional)
+ * [2, n, h]: the final cell state.  h must be a multiple of 16. */
+int asx_op_hd_lstm_layer(asx_engine *e, const float *xp_host, const float *whh_host, int32_t n, int32_t h, int32_t steps, float *out_host,
+                         float *c_host);
+/* asx_op_hd_lstm_frames: the framing of that BLSTM.  A sequence of t <= 200 frames is one sequence of t steps; a longer one is cut into
+ * nfr = ceil(t / 100) frames of 200 steps with stride 100, zero padded.  Rows are sequence-major: row step * ntot + n_off + b * nfr + k
+ * for frame k of batch item b, where ntot >= n_off + b * nfr counts the sequences of every group that shares the recurrence launches.
+ * dir 0 (hd_lstm_frame_kernel): h [b, t, hdim] -> rows [steps * ntot, hdim]; rows of other groups keep the caller's contents.
+ * dir 1 (hd_lstm_unframe_kernel): h [b, t, hdim] += the rows BLSTM.forward stitches (frame 0 gives steps [0, 150), the last [50, 200),
+ * the others [50, 150)); h_host is updated.  steps_out / nfr_out (optional): the step and frame counts the engine derives from t. */
+int asx_op_hd_lstm_frames(asx_engine *e, int32_t dir, float *h_host, int32_t b, int32_t t, int32_t hdim, int32_t ntot, int32_t n_off,
+                          float *rows_host, int32_t *steps_out, int32_t *nfr_out);
+/* asx_op_vr_lstm: the recurrence of the LSTMModule of VR 5.1 (layers_new.py:129-149), one vr_lstm_seq_kernel<hs> launch over w frames
+ * of b sequences from zero state: xp [w, b, 2, 4 * hs] (as above), whh [2, 4 * hs, hs], out [w, b, 2 * hs].  hs is 4, 8, 16, 32, 64
+ * or 128. */
+int asx_op_vr_lstm(asx_engine *e, const float *xp_host, const float *whh_host, int32_t w, int32_t b, int32_t hs, float *out_host);
+/* asx_op_vr_lstm_layout: the two layout kernels around it.  dir 0 (vr_lstm_in_kernel): channel ch0 of src [b, h, w, ld] -> dst [w, b, h].
+ * dir 1 (vr_lstm_out_kernel): src [w, b, h] -> channel ch0 of dst [b, h, w, ld] with channels ch0+1 .. ch0+3 zeroed and every other
+ * channel left alone; ld and ch0 must be multiples of 4 with ch0 + 4 <= ld (one 16-byte store per pixel). */
+int asx_op_vr_lstm_layout(asx_engine *e, int32_t dir, const float *src_host, int32_t b, int32_t h, int32_t w, int32_t ld, int32_t ch0,
+                          float *dst_host);
 
 /* ---- options ------------------------------------------------------------ */
 /* Engine options.  Each engine takes its defaults from the environment variable named beside the option when it is created (values go

@@ -1479,6 +1479,88 @@ int asx_op_mha(asx_engine *e, const float *q_host, int64_t ldq, const float *k_h
   return ASX_OK;
 }
 
+// single launches of the recurrent kernels through the engines' launch code (engine_hd.h, engine_vr.h); outputs are uploaded first
+int asx_op_hd_lstm_layer(asx_engine *e, const float *xp_host, const float *whh_host, int32_t N, int32_t H, int32_t steps, float *out_host,
+                         float *c_host) {
+  REQUIRE(e && xp_host && whh_host && out_host && N > 0 && H > 0 && steps > 0, "asx_op_hd_lstm_layer: bad argument");
+  REQUIRE(H % 16 == 0, "asx_op_hd_lstm_layer: the hidden size must be a multiple of 16, got %d", H);
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dxp, dwhh, dout, dhb, dcst;
+  BufGuard g{{&dxp, &dwhh, &dout, &dhb, &dcst}};
+  const size_t rows = (size_t)steps * N;
+  CHK(to_dev(dxp, xp_host, rows * 8 * H));
+  CHK(to_dev(dwhh, whh_host, (size_t)8 * H * H));
+  CHK(to_dev(dout, out_host, rows * 2 * H));
+  CHK(dhb.ensure((size_t)4 * N * H * 4));
+  CHK(dcst.ensure((size_t)2 * N * H * 4));
+  CHK(hd_lstm_recurrence(e, dxp.f(), dwhh.f(), dhb.f(), dcst.f(), dout.f(), N, H, steps, nullptr));
+  CHK(to_host(out_host, dout, rows * 2 * H));
+  if (c_host) CHK(to_host(c_host, dcst, (size_t)2 * N * H));
+  return ASX_OK;
+}
+
+int asx_op_hd_lstm_frames(asx_engine *e, int32_t dir, float *h_host, int32_t B, int32_t T, int32_t H, int32_t ntot, int32_t n_off,
+                          float *rows_host, int32_t *steps_out, int32_t *nfr_out) {
+  REQUIRE(e && h_host && rows_host && (dir == 0 || dir == 1) && B > 0 && T > 0 && H > 0 && n_off >= 0, "asx_op_hd_lstm_frames: bad argument");
+  int steps, nfr;
+  hd_lstm_framing(T, steps, nfr);
+  REQUIRE((int64_t)n_off + (int64_t)B * nfr <= ntot, "asx_op_hd_lstm_frames: %d x %d sequences from %d do not fit in %d", B, nfr, n_off, ntot);
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dh, drows;
+  BufGuard g{{&dh, &drows}};
+  const size_t nh = (size_t)B * T * H, nr = (size_t)steps * ntot * H;
+  CHK(to_dev(dh, h_host, nh));
+  CHK(to_dev(drows, rows_host, nr));
+  if (dir == 0) {
+    const int64_t tot = (int64_t)steps * B * nfr * H;
+    CHK(timed(e, ASX_PROF_MISC, 0.0, 8.0 * (double)tot, nullptr, [&]() {
+      hipLaunchKernelGGL(hd_lstm_frame_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, dh.f(), B, T, H, nfr, steps, 100, ntot,
+                         n_off, drows.f(), tot);
+    }));
+    CHK(to_host(rows_host, drows, nr));
+  } else {
+    const int64_t tot = (int64_t)nh;
+    CHK(timed(e, ASX_PROF_MISC, 0.0, 12.0 * (double)tot, nullptr, [&]() {
+      hipLaunchKernelGGL(hd_lstm_unframe_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, nullptr, drows.f(), B, T, H, nfr, 100, ntot,
+                         n_off, dh.f(), tot);
+    }));
+    CHK(to_host(h_host, dh, nh));
+  }
+  if (steps_out) *steps_out = steps;
+  if (nfr_out) *nfr_out = nfr;
+  return ASX_OK;
+}
+
+int asx_op_vr_lstm(asx_engine *e, const float *xp_host, const float *whh_host, int32_t W, int32_t B, int32_t hs, float *out_host) {
+  REQUIRE(e && xp_host && whh_host && out_host && W > 0 && B > 0, "asx_op_vr_lstm: bad argument");
+  REQUIRE(hs == 4 || hs == 8 || hs == 16 || hs == 32 || hs == 64 || hs == 128, "asx_op_vr_lstm: hidden size %d per direction is not built", hs);
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dxp, dwhh, dout;
+  BufGuard g{{&dxp, &dwhh, &dout}};
+  CHK(to_dev(dxp, xp_host, (size_t)W * B * 8 * hs));
+  CHK(to_dev(dwhh, whh_host, (size_t)8 * hs * hs));
+  CHK(to_dev(dout, out_host, (size_t)W * B * 2 * hs));
+  CHK(vr51_lstm(e, hs, dxp.f(), dwhh.f(), W, B, dout.f(), nullptr));
+  return to_host(out_host, dout, (size_t)W * B * 2 * hs);
+}
+
+int asx_op_vr_lstm_layout(asx_engine *e, int32_t dir, const float *src_host, int32_t B, int32_t H, int32_t W, int32_t ld, int32_t ch0,
+                          float *dst_host) {
+  REQUIRE(e && src_host && dst_host && (dir == 0 || dir == 1) && B > 0 && H > 0 && W > 0 && ld > 0 && ch0 >= 0, "asx_op_vr_lstm_layout: bad argument");
+  // vr_lstm_out_kernel stores channels ch0 .. ch0+3 of a pixel as one 16-byte vector
+  if (dir == 0) REQUIRE(ch0 < ld, "asx_op_vr_lstm_layout: channel %d of %d", ch0, ld);
+  else REQUIRE(ld % 4 == 0 && ch0 % 4 == 0 && ch0 + 4 <= ld, "asx_op_vr_lstm_layout: channels %d .. %d of %d are no aligned group of four", ch0, ch0 + 3, ld);
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dsrc, ddst;
+  BufGuard g{{&dsrc, &ddst}};
+  const size_t np = (size_t)B * H * W;
+  CHK(to_dev(dsrc, src_host, dir == 0 ? np * ld : np));
+  CHK(to_dev(ddst, dst_host, dir == 0 ? np : np * ld));
+  if (dir == 0) CHK(vr_ew(e, nullptr, (int64_t)np, 8.0 * np, vr_lstm_in_kernel, (const float *)(dsrc.f() + ch0), B, H, W, ld, ddst.f()));
+  else CHK(vr_ew(e, nullptr, (int64_t)np, 8.0 * np, vr_lstm_out_kernel, (const float *)dsrc.f(), B, H, W, ddst.f(), ld, ch0));
+  return to_host(dst_host, ddst, dir == 0 ? np : np * ld);
+}
+
 // ---- MDXC / TFC-TDF v3 --------------------------------------------------------------
 int asx_v3_begin(asx_engine *e, const asx_v3_config *cfg) {
   w3_flush(e);

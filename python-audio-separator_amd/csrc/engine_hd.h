@@ -246,15 +246,18 @@ static int hd_commit(asx_engine *e) {
 struct HdDims {
   int T, T2, nfrA, nfrZ, stepsA, stepsZ;
 };
+// BLSTM framing (demucs.py:41-48): a sequence of up to max_steps = 200 frames runs whole, a longer one as frames of 200 with stride 100
+static void hd_lstm_framing(int T, int &steps, int &nfr) {
+  steps = T > 200 ? 200 : T;
+  nfr = T > 200 ? (T + 99) / 100 : 1;
+}
 static HdDims hd_dims(const HdNet &h, int64_t L) {
   HdDims d;
   const int hop = h.cfg.nfft / 4, ts = h.cfg.time_stride;
   d.T = (int)((L + hop - 1) / hop);
   d.T2 = (d.T + ts - 1) / ts;
-  d.stepsA = d.T > 200 ? 200 : d.T;
-  d.nfrA = d.T > 200 ? (d.T + 99) / 100 : 1;
-  d.stepsZ = d.T2 > 200 ? 200 : d.T2;
-  d.nfrZ = d.T2 > 200 ? (d.T2 + 99) / 100 : 1;
+  hd_lstm_framing(d.T, d.stepsA, d.nfrA);
+  hd_lstm_framing(d.T2, d.stepsZ, d.nfrZ);
   return d;
 }
 
@@ -382,6 +385,26 @@ static int hd_clone(asx_engine *e, size_t idx) {
   return ASX_OK;
 }
 
+// The recurrence of one bidirectional nn.LSTM layer from zero state: steps launches of hd_lstm_step_kernel over xp [steps * N, 2, 4H]
+// and whh [2, 4H, H] into out [steps * N, 2H]; hb [2][2, N, H] is the ping-pong of h, cst [2, N, H] ends as the final cell state
+// (hd_blstm_joint below and the single-op hook asx_op_hd_lstm_layer)
+static int hd_lstm_recurrence(asx_engine *e, const float *xp, const float *whh, float *hb, float *cst, float *out, int N, int H, int steps,
+                              hipStream_t s) {
+  REQUIRE(N > 0 && steps > 0 && H > 0 && H % 16 == 0, "hd_lstm_step_kernel takes hidden sizes that are multiples of 16, got %d (%d sequences, %d steps)", H,
+          N, steps);
+  HIPCHK(hipMemsetAsync(hb, 0, (size_t)4 * N * H * 4, s));
+  HIPCHK(hipMemsetAsync(cst, 0, (size_t)2 * N * H * 4, s));
+  // sequence tiles of 16 are spread evenly over the z blocks (<= 8 tiles each): 18 tiles run as 6 + 6 + 6, not 8 + 8 + 2
+  const int tiles = (N + 15) / 16, nz = (tiles + 7) / 8, tpz = (tiles + nz - 1) / nz;
+  const dim3 grid((unsigned)(H / 4), 2, (unsigned)nz);
+  return timed(e, ASX_PROF_CONV1X1, 2.0 * steps * 2.0 * N * 4.0 * H * H, 4.0 * steps * 2.0 * (4.0 * H * H + 10.0 * N * H), s, [&]() {
+    for (int st = 0; st < steps; ++st) {
+      float *hp = hb + (size_t)(st & 1) * 2 * N * H, *hn = hb + (size_t)((st + 1) & 1) * 2 * N * H;
+      hipLaunchKernelGGL(hd_lstm_step_kernel, grid, dim3(256), 0, s, xp, whh, hp, hn, cst, out, N, H, st, steps, tpz);
+    }
+  });
+}
+
 // BLSTM(dim, layers=2, max_steps=200, skip=True) (demucs.py:33-66) in place on the DConv hidden buffers b.h [B, T, H] of
 // every group, level A (T frames) or Z (T2)
 static int hd_blstm_joint(asx_engine *e, std::vector<HdGroup> &G, bool levelZ, size_t d, hipStream_t s) {
@@ -429,17 +452,7 @@ static int hd_blstm_joint(asx_engine *e, std::vector<HdGroup> &G, bool levelZ, s
       const HtGemm &ih = layer ? L.ih1 : L.ih0;
       const float *whh = layer ? L.whh1.f() : L.whh0.f();
       CHK(ht_linear(e, ih, in, din, rows, xp, 8 * H, 0, nullptr, 0, s));
-      HIPCHK(hipMemsetAsync(hb, 0, (size_t)4 * N * H * 4, s));
-      HIPCHK(hipMemsetAsync(cst, 0, (size_t)2 * N * H * 4, s));
-      // sequence tiles of 16 are spread evenly over the z blocks (<= 8 tiles each): 18 tiles run as 6 + 6 + 6, not 8 + 8 + 2
-      const int tiles = (N + 15) / 16, nz = (tiles + 7) / 8, tpz = (tiles + nz - 1) / nz;
-      const dim3 grid((unsigned)(H / 4), 2, (unsigned)nz);
-      CHK(timed(e, ASX_PROF_CONV1X1, 2.0 * steps * 2.0 * N * 4.0 * H * H, 4.0 * steps * 2.0 * (4.0 * H * H + 10.0 * N * H), s, [&]() {
-        for (int st = 0; st < steps; ++st) {
-          float *hp = hb + (size_t)(st & 1) * 2 * N * H, *hn = hb + (size_t)((st + 1) & 1) * 2 * N * H;
-          hipLaunchKernelGGL(hd_lstm_step_kernel, grid, dim3(256), 0, s, xp, whh, hp, hn, cst, out, N, H, st, steps, tpz);
-        }
-      }));
+      CHK(hd_lstm_recurrence(e, xp, whh, hb, cst, out, N, H, steps, s));
       in = out;
       din = 2 * H;
     }

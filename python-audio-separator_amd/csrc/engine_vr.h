@@ -718,6 +718,23 @@ static void vr51_launch_lstm(const float *xp, const float *whh, int W, int B, fl
   hipLaunchKernelGGL((vr_lstm_seq_kernel<HS>), dim3((unsigned)B, 2), dim3(4 * HS), 0, s, xp, whh, W, B, out);
 }
 
+// the recurrence of the LSTMModule: vr_lstm_seq_kernel<hs> over xp [W, B, 2, 4 * hs], whh [2, 4 * hs, hs] into out [W, B, 2 * hs]
+// (vr51_base below and the single-op hook asx_op_vr_lstm)
+static int vr51_lstm(asx_engine *e, int hs, const float *xp, const float *whh, int W, int B, float *out, hipStream_t s) {
+  REQUIRE(hs == 4 || hs == 8 || hs == 16 || hs == 32 || hs == 64 || hs == 128, "LSTM hidden size %d per direction is not built", hs);
+  REQUIRE(W > 0 && B > 0, "LSTM over %d frames of %d sequences", W, B);
+  return timed(e, ASX_PROF_MISC, 0.0, 4.0 * W * B * 10.0 * hs, s, [&]() {
+    switch (hs) {
+      case 4: vr51_launch_lstm<4>(xp, whh, W, B, out, s); break;
+      case 8: vr51_launch_lstm<8>(xp, whh, W, B, out, s); break;
+      case 16: vr51_launch_lstm<16>(xp, whh, W, B, out, s); break;
+      case 32: vr51_launch_lstm<32>(xp, whh, W, B, out, s); break;
+      case 64: vr51_launch_lstm<64>(xp, whh, W, B, out, s); break;
+      default: vr51_launch_lstm<128>(xp, whh, W, B, out, s); break;
+    }
+  });
+}
+
 // BaseNet.__call__ (nets_new.py:40-56): x view [B, H, W, nin_p] -> y view [B, H, W, n]
 static int vr51_base(asx_engine *e, const Vr51Base &bs, const float *x, int x_ld, int64_t x_bs, int B, int H, int W, float *y, int y_ld,
                      int64_t y_bs, hipStream_t s) {
@@ -773,16 +790,7 @@ static int vr51_base(asx_engine *e, const Vr51Base &bs, const float *x, int x_ld
     CHK(vr_conv(e, L.conv, w.ol, old_, 0, B, H1, W1, 1, w.hcv, 4, 0, s));
     CHK(vr_ew(e, s, (int64_t)W1 * B * H1, 8.0 * W1 * B * H1, vr_lstm_in_kernel, (const float *)w.hcv, B, H1, W1, 4, w.xs));
     CHK(ht_linear(e, L.ih, w.xs, H1, (int64_t)W1 * B, w.xp, 8 * L.hs, 0, nullptr, 0, s));
-    CHK(timed(e, ASX_PROF_MISC, 0.0, 4.0 * W1 * B * 10.0 * L.hs, s, [&]() {
-      switch (L.hs) {
-        case 4: vr51_launch_lstm<4>(w.xp, L.whh.f(), W1, B, w.hsq, s); break;
-        case 8: vr51_launch_lstm<8>(w.xp, L.whh.f(), W1, B, w.hsq, s); break;
-        case 16: vr51_launch_lstm<16>(w.xp, L.whh.f(), W1, B, w.hsq, s); break;
-        case 32: vr51_launch_lstm<32>(w.xp, L.whh.f(), W1, B, w.hsq, s); break;
-        case 64: vr51_launch_lstm<64>(w.xp, L.whh.f(), W1, B, w.hsq, s); break;
-        default: vr51_launch_lstm<128>(w.xp, L.whh.f(), W1, B, w.hsq, s); break;
-      }
-    }));
+    CHK(vr51_lstm(e, L.hs, w.xp, L.whh.f(), W1, B, w.hsq, s));
     CHK(ht_linear(e, L.dense, w.hsq, 2 * L.hs, (int64_t)W1 * B, w.ys, H1, 1, nullptr, 0, s));
     CHK(vr_ew(e, s, (int64_t)B * H1 * W1, 8.0 * B * H1 * W1, vr_lstm_out_kernel, (const float *)w.ys, B, H1, W1, w.ol, old_, 2 * n));
   }

@@ -277,7 +277,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_set_stft_window", "asx_op_tdf_block", "asx_op_attention", "asx_op_mha", "asx_get_option",
            "asx_demix_batch_dev", "asx_separate_batch_dev", "asx_ensemble_slot_dev", "asx_vr_separate_batch_dev",
            "asx_mdxc_demix_batch_dev", "asx_rof_demix_batch_dev", "asx_ensemble_batch_dev", "asx_resample_rational_plan",
-           "asx_resample_rational", "asx_resample_rational_dev"]
+           "asx_resample_rational", "asx_resample_rational_dev", "asx_op_hd_lstm_layer", "asx_op_hd_lstm_frames", "asx_op_vr_lstm",
+           "asx_op_vr_lstm_layout"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -371,6 +372,10 @@ def load_library():
     lib.asx_op_attention.argtypes = [vp, _FP, _FP, i64, i32, i32, i32, i32, i32, i32, i32, C.c_char_p, _FP, C.POINTER(i32)]
     lib.asx_op_mha.argtypes = [vp, _FP, i64, _FP, i64, _FP, i64, _FP, i64, i32, i32, i32, i32, i32, i32, C.c_char_p, _FP, i64,
                                C.POINTER(i32)]
+    lib.asx_op_hd_lstm_layer.argtypes = [vp, _FP, _FP, i32, i32, i32, _FP, _FP]
+    lib.asx_op_hd_lstm_frames.argtypes = [vp, i32, _FP, i32, i32, i32, i32, i32, _FP, C.POINTER(i32), C.POINTER(i32)]
+    lib.asx_op_vr_lstm.argtypes = [vp, _FP, _FP, i32, i32, i32, _FP]
+    lib.asx_op_vr_lstm_layout.argtypes = [vp, i32, _FP, i32, i32, i32, i32, i32, _FP]
     lib.asx_v3_begin.argtypes = [vp, C.POINTER(_V3Cfg)]
     lib.asx_v3_commit.argtypes = [vp]
     lib.asx_v3_flops.argtypes = [vp, i32]
@@ -1463,6 +1468,64 @@ class Engine:
                                          decay.shape[1] if decay is not None else 0, B, nq, nk, heads, dh, int(exact),
                                          variant.encode(), _ptr(out), out.shape[1], C.byref(res)))
         return out, ATTN_VARIANTS[res.value]
+
+    def op_hd_lstm_layer(self, xp, whh, N, H, steps, out=None):
+        """The recurrence of one bidirectional LSTM layer of the HDemucs BLSTM (asx_op_hd_lstm_layer): `steps` launches of
+        hd_lstm_step_kernel from zero state.  xp [steps * N, 2, 4H], whh [2, 4H, H]; `out` [steps * N, 2H] is uploaded before the
+        launches, default NaN.  Returns (out, final cell state [2, N, H])."""
+        xp, whh = _f32(xp), _f32(whh)
+        if xp.size != steps * N * 8 * H or whh.size != 8 * H * H:
+            raise AsxError(f"op_hd_lstm_layer: xp {xp.shape} / whh {whh.shape} are not [{steps * N}, 2, {4 * H}] / [2, {4 * H}, {H}]")
+        out = np.full((steps * N, 2 * H), np.nan, np.float32) if out is None else np.array(out, np.float32, order="C")
+        if out.shape != (steps * N, 2 * H):
+            raise AsxError(f"op_hd_lstm_layer: out {out.shape} is not [{steps * N}, {2 * H}]")
+        c = np.full((2, N, H), np.nan, np.float32)
+        self._check(self._lib.asx_op_hd_lstm_layer(self._h, _ptr(xp), _ptr(whh), N, H, steps, _ptr(out), _ptr(c)))
+        return out, c
+
+    def op_hd_lstm_frames(self, h, ntot, n_off, rows=None, unframe=False):
+        """The framing kernels of the HDemucs BLSTM (asx_op_hd_lstm_frames) on h [B, T, H].  unframe False: hd_lstm_frame_kernel writes
+        this group's rows of `rows` [steps * ntot, H] (uploaded first, default NaN); returns (rows, steps, nfr).  unframe True:
+        hd_lstm_unframe_kernel adds the stitched rows of `rows` to h; returns (h, steps, nfr)."""
+        h = np.array(h, np.float32, order="C")
+        B, T, H = h.shape
+        steps, nfr = C.c_int32(-1), C.c_int32(-1)
+        if rows is None:
+            if unframe:
+                raise AsxError("op_hd_lstm_frames: unframe needs rows")
+            rows = np.full((min(T, 200) * ntot, H), np.nan, np.float32)
+        rows = np.array(rows, np.float32, order="C")
+        if rows.ndim != 2 or rows.shape != (min(T, 200) * ntot, H):
+            raise AsxError(f"op_hd_lstm_frames: rows {rows.shape} is not [{min(T, 200) * ntot}, {H}]")
+        self._check(self._lib.asx_op_hd_lstm_frames(self._h, int(unframe), _ptr(h), B, T, H, ntot, n_off, _ptr(rows), C.byref(steps),
+                                                    C.byref(nfr)))
+        return (h if unframe else rows), steps.value, nfr.value
+
+    def op_vr_lstm(self, xp, whh, W, B, hs, out=None):
+        """The recurrence of the VR 5.1 LSTMModule (asx_op_vr_lstm): one vr_lstm_seq_kernel<hs> launch.  xp [W, B, 2, 4 * hs],
+        whh [2, 4 * hs, hs]; `out` [W, B, 2 * hs] is uploaded first, default NaN."""
+        xp, whh = _f32(xp), _f32(whh)
+        if xp.size != W * B * 8 * hs or whh.size != 8 * hs * hs:
+            raise AsxError(f"op_vr_lstm: xp {xp.shape} / whh {whh.shape} are not [{W}, {B}, 2, {4 * hs}] / [2, {4 * hs}, {hs}]")
+        out = np.full((W, B, 2 * hs), np.nan, np.float32) if out is None else np.array(out, np.float32, order="C")
+        if out.shape != (W, B, 2 * hs):
+            raise AsxError(f"op_vr_lstm: out {out.shape} is not [{W}, {B}, {2 * hs}]")
+        self._check(self._lib.asx_op_vr_lstm(self._h, _ptr(xp), _ptr(whh), W, B, hs, _ptr(out)))
+        return out
+
+    def op_vr_lstm_layout(self, src, B, H, W, ld, ch0, dst=None, out=False):
+        """The layout kernels of the VR 5.1 LSTMModule (asx_op_vr_lstm_layout).  out False: vr_lstm_in_kernel, channel ch0 of src
+        [B, H, W, ld] -> [W, B, H].  out True: vr_lstm_out_kernel, src [W, B, H] -> channels ch0 .. ch0+3 of `dst` [B, H, W, ld]
+        (uploaded first, default NaN)."""
+        src = _f32(src)
+        s_shape, d_shape = ((W, B, H), (B, H, W, ld)) if out else ((B, H, W, ld), (W, B, H))
+        if src.shape != s_shape:
+            raise AsxError(f"op_vr_lstm_layout: src {src.shape} is not {s_shape}")
+        dst = np.full(d_shape, np.nan, np.float32) if dst is None else np.array(dst, np.float32, order="C")
+        if dst.shape != d_shape:
+            raise AsxError(f"op_vr_lstm_layout: dst {dst.shape} is not {d_shape}")
+        self._check(self._lib.asx_op_vr_lstm_layout(self._h, int(out), _ptr(src), B, H, W, ld, ch0, _ptr(dst)))
+        return dst
 
     # -- profiling --------------------------------------------------------------
     def profile_enable(self, on: bool = True):
