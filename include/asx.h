@@ -580,6 +580,29 @@ int asx_pcm16_dev(asx_engine *e, const float *stem_dev, int64_t n_samples, float
 int asx_pcm16_rows_dev(asx_engine *e, const float *stem_rows_dev, int64_t n_samples, float max_peak, float min_peak, int32_t has_min,
                        int16_t *pcm_dev, float *peak_after, void *stream);
 
+/* FLAC encoder for the writer edge (RFC 9639; CommonSeparator.write_audio_pydub with a .flac path): interleaved int16 [n, 2] -> the audio
+ * frames of a fixed-blocksize, 2-channel stream, lossless.  bits_per_sample 16, or 24 = every value shifted left by 8 with the wasted
+ * bits flagged per subframe (what ffmpeg's -sample_fmt s32 makes of 16-bit input).  Per block: constant, verbatim, fixed orders 0..4 and
+ * LPC orders 1..8 at 15-bit coefficients per candidate channel, exact Rice bits for partition orders 0..6 (method 0, no escapes), the
+ * cheapest of L/R, L/S, S/R and M/S.  Runs of one input are byte-identical.  The caller writes "fLaC" and STREAMINFO.
+ *   asx_flac_plan        pure host: frames, the stride of the per-frame scratch slots (the worst case of a frame: header + 2 x (16 + 17 x
+ *                        block_size) bits + padding + CRC-16, rounded up to 16), the worst case of the output and the engine scratch the call
+ *                        will hold (any out pointer may be NULL).  ASX_ERR_INVALID + asx_last_error() for channels != 2, bits_per_sample
+ *                        other than 16 / 24, block_size outside 16 .. 4608 and n_samples < 1.
+ *   asx_flac_encode_dev  pcm16_dev [n, 2] -> out_dev: the frames back to back; frame_bytes_dev [n_blocks] int32: their sizes;
+ *                        *total_bytes: their sum.  out_capacity >= the plan's max_bytes.  Every argument is checked before anything is
+ *                        enqueued; the call synchronises `stream` once, for the total.
+ *   asx_flac_encode      the same for host arrays.
+ * With the profile on (asx_profile_enable) lane 0 of every block stamps the shader clock; asx_counter "flac_block_cycles" and
+ * "flac_crc16_cycles" are the sums over all blocks this engine has encoded that way: the whole block, and its CRC-16 phases.
+ * Additive within ABI 7. */
+int asx_flac_plan(int64_t n_samples, int32_t channels, int32_t bits_per_sample, int32_t block_size, int64_t *n_blocks, int32_t *frame_stride,
+                  int64_t *max_bytes, int64_t *scratch_bytes);
+int asx_flac_encode_dev(asx_engine *e, const int16_t *pcm16_dev, int64_t n_samples, int32_t sample_rate, int32_t bits_per_sample, int32_t block_size,
+                        uint8_t *out_dev, int64_t out_capacity, int32_t *frame_bytes_dev, int64_t *total_bytes, void *stream);
+int asx_flac_encode(asx_engine *e, const int16_t *pcm16_host, int64_t n_samples, int32_t sample_rate, int32_t bits_per_sample, int32_t block_size,
+                    uint8_t *out_host, int64_t out_capacity, int32_t *frame_bytes_host, int64_t *total_bytes);
+
 /* Decode edge (common_separator.py:217-282 prepare_mix -> librosa.load -> libsndfile): the `data` chunk of a RIFF/WAVE file,
  * [frames, channels] interleaved little-endian samples already copied to the device, -> float32 planar mix [2, frames]
  * (a mono file feeds both rows, :278-280; channels beyond the second are ignored).  sample_format: 16 / 24 / 32 = integer

@@ -6,7 +6,8 @@ When they are not (this image ships none of them), RIFF/WAVE files -- integer PC
 32/64, plain or WAVE_FORMAT_EXTENSIBLE -- are read and written by the small codec below so that
 ``separate(path) -> [file names]`` works end to end; every other container then raises with the name of the
 missing package.  Nothing here touches the GPU: the sample arithmetic of the writer (normalise, * 32767,
-int16 cast, interleave) is ``asx_pcm16`` (include/asx.h), called by CommonSeparator.
+int16 cast, interleave) is ``asx_pcm16`` (include/asx.h), called by CommonSeparator.  FLAC output needs no package either:
+the audio frames come from the device encoder (``asx_flac_encode_dev``) and ``write_flac`` puts the container around them.
 """
 from __future__ import annotations
 
@@ -135,12 +136,52 @@ def write_wav(path: str, data: np.ndarray, samplerate: int, subtype: str = "PCM_
         f.write(body)
 
 
+def write_flac(path: str, frames, frame_sizes, samplerate: int, bits_per_sample: int, total_samples: int, md5=None,
+               block_size: int = 4096, channels: int = 2):
+    """A .flac file around audio frames that are already coded (Engine.flac_encode*): the marker, one STREAMINFO block (the last
+    metadata block) and ``frames`` (bytes-like, the frames back to back).  STREAMINFO: minimum = maximum block size ``block_size``
+    (a fixed-blocksize stream; only the last frame may be shorter), the smallest and largest entry of ``frame_sizes``, sample rate,
+    channels, bits per sample, ``total_samples`` inter-channel samples, and ``md5``: the 16-byte digest of the little-endian
+    interleaved PCM at the stream's sample width, or None = not computed (sixteen zero bytes, as the format provides)."""
+    sizes = np.asarray(frame_sizes, np.int64).reshape(-1)
+    if sizes.size == 0 or total_samples < 1:
+        raise AudioIOError("write_flac: no frames")
+    if not (1 <= samplerate < 1 << 20 and 1 <= channels <= 8 and 4 <= bits_per_sample <= 32 and total_samples < 1 << 36):
+        raise AudioIOError("write_flac: stream parameters outside what STREAMINFO holds")
+    body = memoryview(frames).cast("B") if not isinstance(frames, (bytes, bytearray)) else frames
+    if int(sizes.sum()) != len(body):
+        raise AudioIOError(f"write_flac: the size table sums to {int(sizes.sum())} bytes, the frames are {len(body)}")
+    digest = bytes(16) if md5 is None else bytes(md5)
+    if len(digest) != 16:
+        raise AudioIOError("write_flac: md5 must be 16 bytes")
+    packed = (samplerate << 44) | ((channels - 1) << 41) | ((bits_per_sample - 1) << 36) | int(total_samples)
+    info = struct.pack(">HH", block_size, block_size) + min(int(sizes.min()), 0xFFFFFF).to_bytes(3, "big") + \
+        min(int(sizes.max()), 0xFFFFFF).to_bytes(3, "big") + packed.to_bytes(8, "big") + digest
+    with open(path, "wb") as f:
+        f.write(b"fLaC" + bytes([0x80]) + len(info).to_bytes(3, "big") + info)
+        f.write(body)
+
+
+def flac_info(path: str) -> dict:
+    """{samplerate, channels, frames, subtype} from the STREAMINFO block of a .flac file"""
+    with open(path, "rb") as f:
+        head = f.read(8 + 34)
+    if len(head) < 42 or head[:4] != b"fLaC" or head[4] & 127 != 0:
+        raise AudioIOError("not a FLAC file (no marker, or STREAMINFO is not its first block)")
+    v = int.from_bytes(head[18:26], "big")
+    bits = ((v >> 36) & 31) + 1
+    return {"samplerate": v >> 44, "channels": ((v >> 41) & 7) + 1, "frames": v & ((1 << 36) - 1),
+            "subtype": {8: "PCM_S8", 16: "PCM_16", 24: "PCM_24"}.get(bits, f"PCM_{bits}"), "bits": bits}
+
+
 def info(path: str) -> dict:
     """soundfile.info's fields the plugin reads (subtype; common_separator.py:233-250, vr_separator.py:137-156)."""
     sf = _optional("soundfile")
     if sf is not None:
         i = sf.info(path)
         return {"samplerate": i.samplerate, "channels": i.channels, "frames": i.frames, "subtype": i.subtype}
+    if isinstance(path, str) and path.lower().endswith(".flac"):
+        return flac_info(path)
     return wav_info(path)
 
 

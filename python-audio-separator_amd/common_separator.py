@@ -76,8 +76,10 @@ class CommonSeparator:
         self.engine = None                       # the libasx.so handle; set by the architecture subclass
         self.asx_profile_file = bool(config.get("asx_profile_file"))   # per-phase wall times of separate() in file_timings
         self.asx_input_resample = self._input_resample_mode(config)    # who converts a file at another rate than the model's
+        self.asx_output_encoder = self._output_encoder_mode(config)    # who compresses a .flac stem when pydub is installed
         self.file_timings = {}
         self._pending_writes = []                # (thread, error box) of container writes in flight
+        self.last_write_path = None              # "flac_device_resident" | "flac_device_upload": how the last .flac stem reached the encoder
 
         self.roformer_loader = None
         self.is_roformer_model = self._detect_roformer_model()
@@ -130,6 +132,19 @@ class CommonSeparator:
             raise ValueError(f"asx_input_resample must be one of {cls.INPUT_RESAMPLE_MODES}, not {mode!r}")
         return mode
 
+    # ``common_config["asx_output_encoder"]``: who writes a ``.flac`` stem where pydub is installed.  "host" (the default): pydub / ffmpeg, as
+    # the reference does; "device": the engine's encoder (asx_flac_encode_dev) and audio_io.write_flac.  Without pydub the built-in encoder
+    # writes FLAC under either setting, as the built-in writer does for WAV.  The environment variable ASX_OUTPUT_ENCODER, when set and not
+    # empty, overrides the configuration of every plugin of the process.  Other compressed formats always need pydub.
+    OUTPUT_ENCODER_MODES = ("host", "device")
+
+    @classmethod
+    def _output_encoder_mode(cls, config) -> str:
+        mode = os.environ.get("ASX_OUTPUT_ENCODER") or config.get("asx_output_encoder") or "host"
+        if mode not in cls.OUTPUT_ENCODER_MODES:
+            raise ValueError(f"asx_output_encoder must be one of {cls.OUTPUT_ENCODER_MODES}, not {mode!r}")
+        return mode
+
     def _resample_plan(self, file_rate):
         """(n_out for n_in) -> callable when ``asx_input_resample`` is "device" and the engine's converter takes ``file_rate`` ->
         ``sample_rate``; None otherwise (the setting is "host", the rates are equal, the pair is refused: behave as before)."""
@@ -179,16 +194,20 @@ class CommonSeparator:
     # ---- concurrent container writes -----------------------------------------------------------------------------
     def _write_wav_async(self, stem_path, pcm, subtype):
         """audio_io.write_wav on a worker thread (the file write releases the GIL); drained before ``separate`` returns."""
+        self._write_async(lambda: audio_io.write_wav(stem_path, pcm, self.sample_rate, subtype))
+
+    def _write_async(self, write):
+        """``write()`` -- one container write -- on a worker thread; drained before ``separate`` returns."""
         # a write_audio call from outside separate() (the orchestrator's ensemble output, separator.py:1379) is synchronous:
         # nobody would drain it
         if os.environ.get("ASX_ASYNC_WRITES", "1") == "0" or not getattr(self, "_in_separate", False):
-            audio_io.write_wav(stem_path, pcm, self.sample_rate, subtype)
+            write()
             return
         box = []
 
         def work():
             try:
-                audio_io.write_wav(stem_path, pcm, self.sample_rate, subtype)
+                write()
             except BaseException as e:          # re-raised by _drain_writes on the caller's thread
                 box.append(e)
         t = threading.Thread(target=work, name="asx-wav-writer", daemon=True)
@@ -630,13 +649,66 @@ class CommonSeparator:
             raise ValueError(f"write_audio expects a [N, 2] stem, got {a.shape}")
         return a
 
+    def _flac_on_device(self, stem_path: str) -> bool:
+        """whether this stem is compressed by the engine's FLAC encoder: a ``.flac`` path, and pydub absent or ``asx_output_encoder`` = "device" """
+        if stem_path.lower().split(".")[-1] != "flac":
+            return False
+        pydub = audio_io._optional("pydub")
+        has_pydub = pydub is not None and hasattr(pydub, "AudioSegment") and hasattr(pydub.AudioSegment, "export")
+        return not has_pydub or getattr(self, "asx_output_encoder", "host") == "device"
+
+    def _write_flac_device(self, stem_path: str, pcm_dev, pcm_host, n: int, depth):
+        """One ``.flac`` stem through asx_flac_encode_dev: ``pcm_dev`` (a device int16 tensor [n, 2]; the samples stay in HBM, only the
+        compressed frames and their size table come back) or ``pcm_host`` (int16 [n, 2], uploaded by the engine).  An input of 24 or 32
+        bits gives a 24-bit stream of v << 8 (ffmpeg's -sample_fmt s32 for the reference), anything else a 16-bit one.  The container
+        is written on the WAV writer's worker threads; the MD5 of STREAMINFO is taken there when the samples are on the host, and left
+        unset (zero, "not computed") for samples that never left the device."""
+        eng = self.engine
+        bits = 24 if depth in (24, 32) else 16
+        block = getattr(eng, "FLAC_BLOCK_SIZE", 4096)
+        t0 = self._now()
+        if pcm_dev is not None:
+            import torch
+            plan = eng.flac_plan(n, 2, bits, block)
+            out = torch.empty(plan["max_bytes"], dtype=torch.uint8, device=pcm_dev.device)
+            sizes = torch.empty(plan["n_blocks"], dtype=torch.int32, device=pcm_dev.device)
+            total = eng.flac_encode_dev(pcm_dev.data_ptr(), n, self.sample_rate, bits, block, out.data_ptr(), plan["max_bytes"], sizes.data_ptr(),
+                                        stream=self._stream())
+            frames_host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            sizes_host = torch.empty(plan["n_blocks"], dtype=torch.int32, pin_memory=True)
+            frames_host.copy_(out[:total], non_blocking=True)
+            sizes_host.copy_(sizes, non_blocking=True)
+            self._sync()
+            frames, frame_sizes = frames_host.numpy(), sizes_host.numpy()
+            self.last_write_path = "flac_device_resident"
+        else:
+            frames, frame_sizes = eng.flac_encode(pcm_host, self.sample_rate, bits, block)
+            self.last_write_path = "flac_device_upload"
+        self.file_timings["flac_encode"] = self.file_timings.get("flac_encode", 0.0) + (self._now() - t0)
+        rate = self.sample_rate
+
+        def write():
+            md5 = None
+            if pcm_host is not None:
+                import hashlib
+                raw = pcm_host if bits == 16 else (pcm_host.astype(np.int32) << 8)
+                body = np.ascontiguousarray(raw.astype("<i2" if bits == 16 else "<i4", copy=False))
+                if bits == 24:
+                    body = np.ascontiguousarray(body.view(np.uint8).reshape(-1, 4)[:, :3])
+                md5 = hashlib.md5(memoryview(body).cast("B")).digest()
+            audio_io.write_flac(stem_path, frames, frame_sizes, rate, bits, n, md5, block_size=block)
+        self._write_async(write)
+
     def write_audio_pydub(self, stem_path: str, stem_source):
         """common_separator.py:305-397.  normalize -> silence check -> (x * 32767).astype(int16) -> interleave is one
         device pass (asx_pcm16, bit-exact); the container is written by pydub when it is installed, else by the
-        built-in WAV writer (int16 widened exactly like ffmpeg's s16 -> s32 / pcm_s24le conversion)."""
+        built-in WAV writer (int16 widened exactly like ffmpeg's s16 -> s32 / pcm_s24le conversion) or, for a ``.flac``
+        path, by the engine's FLAC encoder and audio_io.write_flac (also with pydub when ``asx_output_encoder`` is "device")."""
         eng = self._require_engine()
         a = self._stereo_rows(stem_source)
         t0 = self._now()
+        flac_dev = self._flac_on_device(stem_path)
+        pcm_dev = None
         entry = self._device_stem_entry(stem_source)
         dev_stem = entry[1] if entry is not None else None
         if dev_stem is not None:
@@ -648,10 +720,13 @@ class CommonSeparator:
             quantise = eng.pcm16_planar_dev if planar else eng.pcm16_rows_dev
             peak = quantise(dev_stem.data_ptr(), n, self.normalization_threshold, self.amplification_threshold,
                             pcm_dev.data_ptr(), stream=self._stream())
-            pcm_host = torch.empty((n, 2), dtype=torch.int16, pin_memory=True)
-            pcm_host.copy_(pcm_dev, non_blocking=True)
-            self._sync()
-            pcm = pcm_host.numpy()
+            pcm = None
+            if not flac_dev:                                  # (the FLAC encoder reads the int16 where it is)
+                pcm_host = torch.empty((n, 2), dtype=torch.int16, pin_memory=True)
+                pcm_host.copy_(pcm_dev, non_blocking=True)
+                self._sync()
+                pcm = pcm_host.numpy()
+                pcm_dev = None
             # written: the device stem and its pinned mirror are released with this entry (planar stems share one mirror, which
             # lives until the last of them is written)
             self._dev_stems.pop(id(stem_source), None)
@@ -672,6 +747,10 @@ class CommonSeparator:
         depth = self.input_bit_depth if self.input_bit_depth is not None else 16
         self.logger.info(f"{stem_path}: {depth}-bit output (the input's bit depth)")
         file_format = stem_path.lower().split(".")[-1]
+        if flac_dev:
+            self._write_flac_device(stem_path, pcm_dev, pcm, a.shape[0], depth)
+            self._tick("container_write", t0)
+            return
         pydub = audio_io._optional("pydub")
         if pydub is not None and hasattr(pydub, "AudioSegment") and hasattr(pydub.AudioSegment, "export"):
             seg = pydub.AudioSegment(pcm.reshape(-1).tobytes(), frame_rate=self.sample_rate, sample_width=2, channels=2)
@@ -693,7 +772,7 @@ class CommonSeparator:
                 self.logger.error(f"{stem_path}: the container write failed: {e}")
             return
         if file_format != "wav":
-            raise audio_io.AudioIOError(f"writing .{file_format} needs pydub + ffmpeg (not installed); WAV is built in")
+            raise audio_io.AudioIOError(f"writing .{file_format} needs pydub + ffmpeg (not installed); WAV and FLAC are built in")
         self._write_wav_async(stem_path, pcm, {16: "PCM_16", 24: "PCM_24", 32: "PCM_32"}.get(depth, "PCM_16"))
         self._tick("container_write", t0)
 

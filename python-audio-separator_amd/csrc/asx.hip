@@ -59,6 +59,7 @@ static void grant_lds(K *kernel, int bytes) { grant_lds(reinterpret_cast<const v
 #include "kernels_vr.h"
 #include "kernels_ens.h"
 #include "kernels_resample.h"
+#include "kernels_flac.h"
 
 using namespace asx;
 
@@ -283,6 +284,9 @@ void asx_engine_destroy(asx_engine *e) {
   }
   if (e->div_ev) (void)hipEventDestroy(e->div_ev);
   e->sinc_tab.release();
+  e->flac_frames.release();
+  e->flac_cycles.release();
+  e->flac_off.release();
   for (RsTable *t : e->rs_tabs) {
     t->tab.release();
     delete t;
@@ -518,6 +522,7 @@ double asx_net_flops(const asx_engine *e, int32_t batch) {
 #include "engine_vr.h"
 #include "engine_ens.h"
 #include "engine_resample.h"
+#include "engine_flac.h"
 extern "C" {
 
 // ---- plan ------------------------------------------------------------------
@@ -1065,6 +1070,56 @@ int asx_resample_rational(asx_engine *e, const float *x_host, int32_t channels, 
   return host_round_trip(x_host, (size_t)channels * n_in, y_host, (size_t)channels * n_out, [&](const float *x, float *y) {
     return asx_resample_rational_dev(e, x, channels, n_in, sr_in, sr_out, y, n_out, nullptr);
   });
+}
+
+// The FLAC encoder (kernels_flac.h, engine_flac.h): the plan of a stream, pure host
+int asx_flac_plan(int64_t n_samples, int32_t channels, int32_t bits_per_sample, int32_t block_size, int64_t *n_blocks, int32_t *frame_stride,
+                  int64_t *max_bytes, int64_t *scratch_bytes) {
+  FlacPlan p;
+  const std::string why = flac_plan_make(n_samples, channels, bits_per_sample, block_size, p);
+  REQUIRE(why.empty(), "asx_flac_plan: %s", why.c_str());
+  if (n_blocks) *n_blocks = p.n_blocks;
+  if (frame_stride) *frame_stride = p.stride;
+  if (max_bytes) *max_bytes = p.max_bytes;
+  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+  return ASX_OK;
+}
+
+int asx_flac_encode_dev(asx_engine *e, const int16_t *pcm16_dev, int64_t n_samples, int32_t sample_rate, int32_t bits_per_sample, int32_t block_size,
+                        uint8_t *out_dev, int64_t out_capacity, int32_t *frame_bytes_dev, int64_t *total_bytes, void *stream) {
+  REQUIRE(e && pcm16_dev && out_dev && frame_bytes_dev && total_bytes, "asx_flac_encode_dev: null argument");
+  FlacPlan p;
+  const std::string why = flac_plan_make(n_samples, 2, bits_per_sample, block_size, p);
+  REQUIRE(why.empty(), "asx_flac_encode_dev: %s", why.c_str());
+  REQUIRE(sample_rate >= 1 && sample_rate <= 1048575, "asx_flac_encode_dev: sample rate %d Hz (1 .. 1048575)", sample_rate);
+  REQUIRE(out_capacity >= p.max_bytes, "asx_flac_encode_dev: out_capacity %lld below the plan's worst case of %lld bytes", (long long)out_capacity,
+          (long long)p.max_bytes);
+  REQUIRE((((uintptr_t)pcm16_dev) & 3) == 0 && (((uintptr_t)frame_bytes_dev) & 3) == 0, "asx_flac_encode_dev: pcm16 and frame_bytes must be 4-byte aligned");
+  HIPCHK(hipSetDevice(e->device));
+  return flac_encode_launch(e, pcm16_dev, n_samples, sample_rate, bits_per_sample, block_size, p, out_dev, frame_bytes_dev, total_bytes,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+int asx_flac_encode(asx_engine *e, const int16_t *pcm16_host, int64_t n_samples, int32_t sample_rate, int32_t bits_per_sample, int32_t block_size,
+                    uint8_t *out_host, int64_t out_capacity, int32_t *frame_bytes_host, int64_t *total_bytes) {
+  REQUIRE(e && pcm16_host && out_host && frame_bytes_host && total_bytes, "asx_flac_encode: null argument");
+  FlacPlan p;
+  const std::string why = flac_plan_make(n_samples, 2, bits_per_sample, block_size, p);
+  REQUIRE(why.empty(), "asx_flac_encode: %s", why.c_str());
+  REQUIRE(out_capacity >= p.max_bytes, "asx_flac_encode: out_capacity %lld below the plan's worst case of %lld bytes", (long long)out_capacity,
+          (long long)p.max_bytes);
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf din, dout, dsz;
+  BufGuard g{{&din, &dout, &dsz}};
+  CHK(din.ensure((size_t)n_samples * 4));
+  CHK(dout.ensure((size_t)p.max_bytes));
+  CHK(dsz.ensure((size_t)p.n_blocks * 4));
+  HIPCHK(hipMemcpy(din.p, pcm16_host, (size_t)n_samples * 4, hipMemcpyHostToDevice));
+  CHK(asx_flac_encode_dev(e, reinterpret_cast<const int16_t *>(din.p), n_samples, sample_rate, bits_per_sample, block_size,
+                          reinterpret_cast<uint8_t *>(dout.p), p.max_bytes, reinterpret_cast<int32_t *>(dsz.p), total_bytes, nullptr));
+  HIPCHK(hipMemcpy(out_host, dout.p, (size_t)*total_bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(frame_bytes_host, dsz.p, (size_t)p.n_blocks * 4, hipMemcpyDeviceToHost));
+  return ASX_OK;
 }
 
 // ---- stage hooks -------------------------------------------------------------
@@ -2438,6 +2493,8 @@ int asx_counter(const asx_engine *e, const char *name, int64_t *out) {
   else if (nm == "vr_net_passes") *out = (int64_t)g_vr_net_passes.load();
   else if (nm == "v3_net_passes") *out = (int64_t)g_v3_net_passes.load();
   else if (nm == "rof_net_passes") *out = (int64_t)g_rof_net_passes.load();
+  else if (nm == "flac_block_cycles") *out = (int64_t)e->flac_block_cycles;
+  else if (nm == "flac_crc16_cycles") *out = (int64_t)e->flac_crc16_cycles;
   else {
     set_err("asx_counter: unknown counter '%s'", name);
     return ASX_ERR_INVALID;

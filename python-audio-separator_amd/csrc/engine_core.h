@@ -221,6 +221,9 @@ struct asx_engine {
   DevBuf d_div;      // divider of the chunk fold for div_key's plan (input-independent: built once, asx_finalize_dev)
   DivKey div_key;
   DevBuf sinc_tab;   // coefficient table of asx_resample_sinc (built on first use)
+  DevBuf flac_cycles;             // the two clock sums of a profiled encode, and their totals since the engine was created
+  long long flac_block_cycles = 0, flac_crc16_cycles = 0;
+  DevBuf flac_frames, flac_off;   // asx_flac_encode_dev: frame slots at the plan's stride, and the offsets of the compacted frames
   // coefficient tables of asx_resample_rational, one per (sr_in, sr_out), built on first use and kept until the engine goes (the entries never
   // move: a launch in flight reads its table)
   std::vector<RsTable *> rs_tabs;

@@ -278,7 +278,7 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_demix_batch_dev", "asx_separate_batch_dev", "asx_ensemble_slot_dev", "asx_vr_separate_batch_dev",
            "asx_mdxc_demix_batch_dev", "asx_rof_demix_batch_dev", "asx_ensemble_batch_dev", "asx_resample_rational_plan",
            "asx_resample_rational", "asx_resample_rational_dev", "asx_op_hd_lstm_layer", "asx_op_hd_lstm_frames", "asx_op_vr_lstm",
-           "asx_op_vr_lstm_layout"]
+           "asx_op_vr_lstm_layout", "asx_flac_plan", "asx_flac_encode", "asx_flac_encode_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -420,6 +420,9 @@ def load_library():
     lib.asx_resample_rational_plan.argtypes = [i32, i32, i64, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.asx_resample_rational.argtypes = [vp, _FP, i32, i64, i32, i32, _FP, i64]
     lib.asx_resample_rational_dev.argtypes = [vp, vp, i32, i64, i32, i32, vp, i64, vp]
+    lib.asx_flac_plan.argtypes = [i64, i32, i32, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
+    lib.asx_flac_encode.argtypes = [vp, C.POINTER(C.c_int16), i64, i32, i32, i32, C.POINTER(C.c_uint8), i64, C.POINTER(i32), C.POINTER(i64)]
+    lib.asx_flac_encode_dev.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, vp, C.POINTER(i64), vp]
     lib.asx_ensemble.argtypes = [vp, _FP, i32, i64, i32, C.POINTER(C.c_double), _FP, C.POINTER(i64)]
     lib.asx_ensemble_dev.argtypes = [vp, vp, i32, i64, i32, C.POINTER(C.c_double), vp, C.POINTER(i64), vp]
     lib.asx_invert_stem.argtypes = [vp, _FP, _FP, i64, _FP, C.POINTER(i64)]
@@ -1075,6 +1078,47 @@ class Engine:
         self._check(self._lib.asx_pcm16(self._h, _ptr(planar), n, float(max_peak), float(min_peak or 0.0), int(min_peak is not None),
                                         out.ctypes.data_as(C.POINTER(C.c_int16)), C.byref(pk)))
         return out, pk.value
+
+    FLAC_BLOCK_SIZE = 4096
+
+    @staticmethod
+    def flac_plan(n_samples: int, channels: int = 2, bits_per_sample: int = 16, block_size: int = FLAC_BLOCK_SIZE) -> dict:
+        """asx_flac_plan (pure host: no engine, no GPU): {n_blocks, frame_stride, max_bytes, scratch_bytes} of the FLAC encoder for
+        ``n_samples`` inter-channel samples.  Raises AsxError for what the encoder refuses (channels other than 2, bits per sample other
+        than 16 / 24, a block size outside 16 .. 4608, no samples)."""
+        lib = load_library()
+        nb, stride, mx, scratch = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64()
+        rc = lib.asx_flac_plan(int(n_samples), int(channels), int(bits_per_sample), int(block_size), C.byref(nb), C.byref(stride), C.byref(mx),
+                               C.byref(scratch))
+        if rc != 0:
+            msg = lib.asx_last_error()
+            raise AsxError(f"asx error {rc}: {msg.decode() if msg else '?'}")
+        return {"n_blocks": nb.value, "frame_stride": stride.value, "max_bytes": mx.value, "scratch_bytes": scratch.value}
+
+    def flac_encode(self, pcm: np.ndarray, samplerate: int, bits_per_sample: int = 16, block_size: int = FLAC_BLOCK_SIZE):
+        """int16 [n, 2] -> (the stream's audio frames back to back as uint8, their sizes as int32 [n_blocks]); asx_flac_encode.
+        ``bits_per_sample`` 24 writes every value shifted left by 8."""
+        a = np.asarray(pcm)
+        if a.dtype != np.int16 or a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError(f"flac_encode expects int16 [n, 2], got {a.dtype} {a.shape}")
+        a = np.ascontiguousarray(a)
+        plan = self.flac_plan(a.shape[0], 2, bits_per_sample, block_size)
+        out = np.empty(plan["max_bytes"], np.uint8)
+        sizes = np.empty(plan["n_blocks"], np.int32)
+        total = C.c_int64()
+        self._check(self._lib.asx_flac_encode(self._h, a.ctypes.data_as(C.POINTER(C.c_int16)), a.shape[0], int(samplerate), int(bits_per_sample),
+                                              int(block_size), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size,
+                                              sizes.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(total)))
+        return out[:total.value], sizes
+
+    def flac_encode_dev(self, pcm_ptr: int, n_samples: int, samplerate: int, bits_per_sample: int, block_size: int, out_ptr: int,
+                        out_capacity: int, frame_bytes_ptr: int, stream: int = 0) -> int:
+        """asx_flac_encode_dev: device int16 [n, 2] -> frames in ``out_ptr`` (room for the plan's max_bytes), sizes in
+        ``frame_bytes_ptr`` (int32 [n_blocks]); returns the frames' total bytes (synchronises the stream once)."""
+        total = C.c_int64()
+        self._check(self._lib.asx_flac_encode_dev(self._h, pcm_ptr, int(n_samples), int(samplerate), int(bits_per_sample), int(block_size), out_ptr,
+                                                  int(out_capacity), frame_bytes_ptr, C.byref(total), stream or None))
+        return total.value
 
     def pcm16_rows_dev(self, stem_ptr: int, n_samples: int, max_peak: float, min_peak, pcm_ptr: int, stream: int = 0,
                        want_peak: bool = True):
