@@ -603,6 +603,36 @@ int asx_flac_encode_dev(asx_engine *e, const int16_t *pcm16_dev, int64_t n_sampl
 int asx_flac_encode(asx_engine *e, const int16_t *pcm16_host, int64_t n_samples, int32_t sample_rate, int32_t bits_per_sample, int32_t block_size,
                     uint8_t *out_host, int64_t out_capacity, int32_t *frame_bytes_host, int64_t *total_bytes);
 
+/* FLAC decoder for the input edge (RFC 9639): the audio part of a native FLAC stream -- everything behind the last metadata block, already in
+ * HBM -- -> the planar float32 mix [2, n] = x / 2^(bits_per_sample - 1), which is what librosa.load / libsndfile give for the file at its own
+ * rate (a mono stream feeds both rows).  The arguments are STREAMINFO's fields.  Taken: 1 or 2 channels, 8 .. 24 bits per sample, fixed or
+ * variable block sizes up to 16384, any sample rate.  A stream has no frame index and the sync code also occurs inside frames, so: every
+ * byte position whose header passes all checks (its CRC-8 included) becomes a candidate; every candidate is decoded, one wave each, with its
+ * CRC-16; the host keeps the chain of valid candidates that follow each other from byte 0 and drops the rest; the chain's frames are
+ * converted.  The chain ends at the end of the data or at the first frame that is damaged or cut: *bytes_consumed < audio_bytes tells.  The
+ * frame CRCs are the integrity check (STREAMINFO's MD5 and total_samples are not used).
+ *   asx_flac_decode_plan        pure host: the capacity of the candidate list (audio_bytes / 5 + 1: two headers are at least 5 bytes apart),
+ *                               the bytes of one candidate's slot and the fixed scratch; the slots of the candidates found come on top (any
+ *                               out pointer may be NULL).  ASX_ERR_INVALID + asx_last_error() for 32-bit (or any width outside 8 .. 24)
+ *                               streams, more than two channels, a maximum block size outside 16 .. 16384 and empty input.
+ *   asx_flac_decode_scan_dev    sync, frame decode and chain walk; *n_samples (may be 0), *n_frames, *bytes_consumed.  The decoded frames stay
+ *                               in engine scratch.  audio_dev is 4-byte aligned.  Synchronises `stream` twice (the candidate count sizes the
+ *                               slots; the records feed the walk).
+ *   asx_flac_decode_finish_dev  the frames of the last scan -> mix_dev [2, n_samples]; *peak (optional, synchronises) = max |mix|.
+ *                               ASX_ERR_INVALID unless a scan on this engine came before it and found n_samples >= 1 samples.
+ *   asx_flac_decode             the same for host arrays; mix_host holds [2, *n_samples], at most `capacity` samples per row (ASX_ERR_INVALID
+ *                               with *n_samples set when the stream holds more).
+ * Every argument is checked before anything is enqueued.  Additive within ABI 7. */
+int asx_flac_decode_plan(int64_t audio_bytes, int32_t channels, int32_t bits_per_sample, int32_t max_blocksize, int32_t max_framesize,
+                         int64_t *max_candidates, int64_t *slot_bytes, int64_t *scratch_bytes);
+int asx_flac_decode_scan_dev(asx_engine *e, const uint8_t *audio_dev, int64_t audio_bytes, int32_t sample_rate, int32_t channels,
+                             int32_t bits_per_sample, int32_t max_blocksize, int32_t max_framesize, int64_t *n_samples, int64_t *n_frames,
+                             int64_t *bytes_consumed, void *stream);
+int asx_flac_decode_finish_dev(asx_engine *e, float *mix_dev, int64_t n_samples, float *peak, void *stream);
+int asx_flac_decode(asx_engine *e, const uint8_t *audio_host, int64_t audio_bytes, int32_t sample_rate, int32_t channels, int32_t bits_per_sample,
+                    int32_t max_blocksize, int32_t max_framesize, float *mix_host, int64_t capacity, int64_t *n_samples, int64_t *n_frames,
+                    int64_t *bytes_consumed, float *peak);
+
 /* Decode edge (common_separator.py:217-282 prepare_mix -> librosa.load -> libsndfile): the `data` chunk of a RIFF/WAVE file,
  * [frames, channels] interleaved little-endian samples already copied to the device, -> float32 planar mix [2, frames]
  * (a mono file feeds both rows, :278-280; channels beyond the second are ignored).  sample_format: 16 / 24 / 32 = integer

@@ -174,6 +174,68 @@ def flac_info(path: str) -> dict:
             "subtype": {8: "PCM_S8", 16: "PCM_16", 24: "PCM_24"}.get(bits, f"PCM_{bits}"), "bits": bits}
 
 
+def _id3v2_size(head: bytes) -> int:
+    """bytes of an ID3v2 tag at the start of ``head`` (10 bytes of header with a sync-safe size, plus a footer when flagged), or 0"""
+    if len(head) < 10 or head[:3] != b"ID3" or any(b & 0x80 for b in head[6:10]):
+        return 0
+    size = (head[6] << 21) | (head[7] << 14) | (head[8] << 7) | head[9]
+    return 10 + size + (10 if head[5] & 0x10 else 0)
+
+
+def is_flac(path: str) -> bool:
+    """True when the file carries the fLaC marker, at its start or behind an ID3v2 tag (the extension is not looked at)"""
+    try:
+        with open(path, "rb") as f:
+            head = f.read(10)
+            if head[:4] == b"fLaC":
+                return True
+            skip = _id3v2_size(head)
+            if not skip:
+                return False
+            f.seek(skip)
+            return f.read(4) == b"fLaC"
+    except OSError:
+        return False
+
+
+def flac_stream(path: str) -> dict:
+    """A native FLAC file as the device decoder needs it: STREAMINFO's fields {min_blocksize, max_blocksize, min_framesize, max_framesize,
+    samplerate, channels, bits_per_sample, total_samples (a hint: 0 = unknown), md5} plus audio_offset and audio_bytes -- the audio
+    frames are everything behind the last metadata block, to the end of the file.  An ID3v2 tag in front of the marker is skipped; any
+    number and kind of metadata blocks may follow STREAMINFO."""
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        pos = _id3v2_size(f.read(10))
+        f.seek(pos)
+        if f.read(4) != b"fLaC":
+            raise AudioIOError("not a FLAC file (no fLaC marker)")
+        pos += 4
+        fields, first = None, True
+        while True:
+            head = f.read(4)
+            if len(head) < 4:
+                raise AudioIOError("FLAC metadata runs past the end of the file")
+            kind, length = head[0] & 127, int.from_bytes(head[1:4], "big")
+            if first:
+                body = f.read(34)
+                if kind != 0 or length != 34 or len(body) != 34:
+                    raise AudioIOError("not a FLAC file (STREAMINFO is not its first block)")
+                v = int.from_bytes(body[10:18], "big")
+                fields = {"min_blocksize": int.from_bytes(body[0:2], "big"), "max_blocksize": int.from_bytes(body[2:4], "big"),
+                          "min_framesize": int.from_bytes(body[4:7], "big"), "max_framesize": int.from_bytes(body[7:10], "big"),
+                          "samplerate": v >> 44, "channels": ((v >> 41) & 7) + 1, "bits_per_sample": ((v >> 36) & 31) + 1,
+                          "total_samples": v & ((1 << 36) - 1), "md5": bytes(body[18:34])}
+                first = False
+            pos += 4 + length
+            if pos > size:
+                raise AudioIOError("FLAC metadata runs past the end of the file")
+            f.seek(pos)
+            if head[0] & 0x80:
+                break
+    fields.update(audio_offset=pos, audio_bytes=size - pos)
+    return fields
+
+
 def info(path: str) -> dict:
     """soundfile.info's fields the plugin reads (subtype; common_separator.py:233-250, vr_separator.py:137-156)."""
     sf = _optional("soundfile")
@@ -202,6 +264,15 @@ def load(path: str, sr: int | None = 44100, mono: bool = False, res_type: str | 
     try:
         x, file_sr = read_wav(path)
     except AudioIOError as e:
+        if isinstance(path, str) and is_flac(path):
+            try:
+                file_sr = flac_stream(path)["samplerate"]
+            except AudioIOError:
+                file_sr = None
+            if sr is not None and file_sr is not None and file_sr != sr:
+                raise AudioIOError(f"{path} is sampled at {file_sr} Hz and librosa (which resamples to {sr} Hz on load) is not installed") from e
+            raise AudioIOError(f"{path}: FLAC is decoded on the device (the file fast path of the separators, 16- or 24-bit mono / stereo "
+                               f"streams); this host loader reads RIFF/WAVE only -- install librosa (+ soundfile) for a host decode") from e
         raise AudioIOError(f"{path}: {e}; install librosa (+ soundfile / audioread) to decode other containers") from e
     if sr is not None and file_sr != sr:
         raise AudioIOError(f"{path} is sampled at {file_sr} Hz and librosa (which resamples to {sr} Hz on load) is not installed")

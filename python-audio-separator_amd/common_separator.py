@@ -283,7 +283,7 @@ class CommonSeparator:
         memory, copied to HBM once and converted to the planar float32 mix [2, N] on the device (asx_pcm_decode_dev: the same
         x / 2^(bits-1) conversion libsndfile applies under librosa.load, common_separator.py:252).  With ``asx_input_resample`` =
         "device" a file at another rate is decoded at its own frame count and brought to ``sample_rate`` by
-        asx_resample_rational_dev ([2, ceil(N * sample_rate / file rate)]).  Returns a CUDA tensor, or
+        asx_resample_rational_dev ([2, ceil(N * sample_rate / file rate)]).  A native FLAC file takes ``_device_mix_flac``.  Returns a CUDA tensor, or
         None when the file needs the host decoder (other container, other rate, exotic subtype) -- the caller then takes
         prepare_mix.  Raises the reference's ValueError for a silent file (:268-271) unless ``check_silent`` is False: the VR
         plugin never calls prepare_mix (vr_separator.py:255-291 loads with librosa directly), so a silent file must come out the
@@ -294,7 +294,7 @@ class CommonSeparator:
         try:
             info = audio_io.wav_info(path)
         except (audio_io.AudioIOError, OSError):
-            return None
+            return self._device_mix_flac(path, check_silent) if audio_io.is_flac(path) else None
         if info["subtype"] not in self.engine.PCM_FORMATS or info["frames"] < 1 or info["channels"] > 2:
             return None                # (more than two channels: prepare_mix + the reference's "Expected a 2-channel" error)
         n_resampled = None             # a file at another rate: only with asx_input_resample = "device" and a pair the converter takes
@@ -321,6 +321,67 @@ class CommonSeparator:
         mix = torch.empty((2, frames), dtype=torch.float32, device=dev)
         peak = self.engine.pcm_decode_dev(raw.data_ptr(), frames, ch, st, mix.data_ptr(), stream=self._stream())
         t0 = self._tick("h2d_decode", t0)
+        if check_silent and not peak > 0.0:
+            msg = f"Audio file {path} is empty or not valid"
+            self.logger.error(msg)
+            raise ValueError(msg)
+        if n_resampled is not None:
+            n_out = n_resampled(frames)
+            at_rate = torch.empty((2, n_out), dtype=torch.float32, device=dev)
+            self.engine.resample_rational_dev(mix.data_ptr(), 2, frames, info["samplerate"], self.sample_rate, at_rate.data_ptr(), n_out,
+                                              stream=self._stream())
+            mix = at_rate
+            self._tick("resample", t0)
+        return mix
+
+    def _device_mix_flac(self, path, check_silent=True):
+        """``_device_mix`` for a native FLAC file (found by its marker) of 16 or 24 bits and at most two channels: the audio frames are
+        read into pinned memory, copied to HBM once and decoded there (Engine.flac_decode_scan_dev / flac_decode_finish_dev) into the
+        mix libsndfile gives, x / 2^(bits-1).  None for every other stream, a file at another rate without a device converter, or an
+        engine without the decoder."""
+        if not hasattr(self.engine, "flac_decode_scan_dev"):
+            return None
+        import torch
+        try:
+            info = audio_io.flac_stream(path)
+            self.engine.flac_decode_plan(info["audio_bytes"], info["channels"], info["bits_per_sample"], info["max_blocksize"], info["max_framesize"])
+        except Exception as e:
+            self.logger.debug(f"{path}: no device FLAC decode ({e})")
+            return None
+        if info["bits_per_sample"] not in (16, 24) or info["channels"] > 2:
+            return None
+        n_resampled = None
+        if info["samplerate"] != self.sample_rate:
+            n_resampled = self._resample_plan(info["samplerate"])
+            if n_resampled is None:
+                return None
+        t0 = self._now()
+        nbytes = info["audio_bytes"]
+        staged = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        with open(path, "rb") as f:
+            f.seek(info["audio_offset"])
+            got = f.readinto(memoryview(staged.numpy()))
+        if got != nbytes:
+            return None
+        t0 = self._tick("read", t0)
+        dev = self._torch_device()
+        raw = staged.to(dev, non_blocking=True)
+        found = self.engine.flac_decode_scan_dev(raw.data_ptr(), nbytes, info, stream=self._stream())
+        frames = found["n_samples"]
+        if found["bytes_consumed"] < nbytes:
+            self.logger.warning(f"{path}: FLAC frames end at byte {found['bytes_consumed']} of {nbytes} of the audio part (a trailing tag, a cut "
+                                f"file or a damaged frame); the {found['n_frames']} frames before it are used")
+        if frames < 1:
+            msg = f"Audio file {path} is empty or not valid"
+            self.logger.error(msg)
+            raise ValueError(msg)
+        # what _probe_bit_depth records for the writer (common_separator.py:231-250)
+        self.input_subtype = "PCM_16" if info["bits_per_sample"] == 16 else "PCM_24"
+        self.input_bit_depth = info["bits_per_sample"]
+        self._file_seconds = frames / float(info["samplerate"])
+        mix = torch.empty((2, frames), dtype=torch.float32, device=dev)
+        peak = self.engine.flac_decode_finish_dev(mix.data_ptr(), frames, stream=self._stream())
+        t0 = self._tick("flac_decode", t0)
         if check_silent and not peak > 0.0:
             msg = f"Audio file {path} is empty or not valid"
             self.logger.error(msg)

@@ -23,6 +23,7 @@
 #include "../../include/asx.h"
 #include "knobs.h"
 #include "resample_plan.h"
+#include "flac_dec_plan.h"
 
 // Raise a kernel's dynamic-LDS limit to `bytes` unless an earlier call granted as much.  Engines are driven from several host threads
 // (one per bag member / rank): one lock covers the record and the attribute call, so no launch can overtake the grant it needs.
@@ -60,6 +61,7 @@ static void grant_lds(K *kernel, int bytes) { grant_lds(reinterpret_cast<const v
 #include "kernels_ens.h"
 #include "kernels_resample.h"
 #include "kernels_flac.h"
+#include "kernels_flac_dec.h"
 
 using namespace asx;
 
@@ -287,6 +289,9 @@ void asx_engine_destroy(asx_engine *e) {
   e->flac_frames.release();
   e->flac_cycles.release();
   e->flac_off.release();
+  e->flacdec_list.release();
+  e->flacdec_slots.release();
+  e->flacdec_accept.release();
   for (RsTable *t : e->rs_tabs) {
     t->tab.release();
     delete t;
@@ -523,6 +528,7 @@ double asx_net_flops(const asx_engine *e, int32_t batch) {
 #include "engine_ens.h"
 #include "engine_resample.h"
 #include "engine_flac.h"
+#include "engine_flac_dec.h"
 extern "C" {
 
 // ---- plan ------------------------------------------------------------------
@@ -1119,6 +1125,66 @@ int asx_flac_encode(asx_engine *e, const int16_t *pcm16_host, int64_t n_samples,
                           reinterpret_cast<uint8_t *>(dout.p), p.max_bytes, reinterpret_cast<int32_t *>(dsz.p), total_bytes, nullptr));
   HIPCHK(hipMemcpy(out_host, dout.p, (size_t)*total_bytes, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(frame_bytes_host, dsz.p, (size_t)p.n_blocks * 4, hipMemcpyDeviceToHost));
+  return ASX_OK;
+}
+
+// The FLAC decoder (kernels_flac_dec.h, flac_dec_plan.h, engine_flac_dec.h): which streams it takes, pure host
+int asx_flac_decode_plan(int64_t audio_bytes, int32_t channels, int32_t bits_per_sample, int32_t max_blocksize, int32_t max_framesize,
+                         int64_t *max_candidates, int64_t *slot_bytes, int64_t *scratch_bytes) {
+  FlacDecPlan p;
+  const std::string why = flac_dec_plan_make(audio_bytes, channels, bits_per_sample, max_blocksize, max_framesize, p);
+  REQUIRE(why.empty(), "asx_flac_decode_plan: %s", why.c_str());
+  if (max_candidates) *max_candidates = p.max_candidates;
+  if (slot_bytes) *slot_bytes = p.slot_bytes;
+  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+  return ASX_OK;
+}
+
+int asx_flac_decode_scan_dev(asx_engine *e, const uint8_t *audio_dev, int64_t audio_bytes, int32_t sample_rate, int32_t channels,
+                             int32_t bits_per_sample, int32_t max_blocksize, int32_t max_framesize, int64_t *n_samples, int64_t *n_frames,
+                             int64_t *bytes_consumed, void *stream) {
+  REQUIRE(e && audio_dev && n_samples, "asx_flac_decode_scan_dev: null argument");
+  FlacDecPlan p;
+  const std::string why = flac_dec_plan_make(audio_bytes, channels, bits_per_sample, max_blocksize, max_framesize, p);
+  REQUIRE(why.empty(), "asx_flac_decode_scan_dev: %s", why.c_str());
+  REQUIRE(sample_rate >= 1 && sample_rate <= 1048575, "asx_flac_decode_scan_dev: sample rate %d Hz (1 .. 1048575)", sample_rate);
+  REQUIRE((((uintptr_t)audio_dev) & 3) == 0, "asx_flac_decode_scan_dev: the audio bytes must be 4-byte aligned");
+  HIPCHK(hipSetDevice(e->device));
+  const flacdec::Info I{sample_rate, channels, bits_per_sample, max_blocksize, max_framesize};
+  return flac_decode_scan_launch(e, audio_dev, audio_bytes, I, p, n_samples, n_frames, bytes_consumed, reinterpret_cast<hipStream_t>(stream));
+}
+
+int asx_flac_decode_finish_dev(asx_engine *e, float *mix_dev, int64_t n_samples, float *peak, void *stream) {
+  REQUIRE(e && mix_dev, "asx_flac_decode_finish_dev: null argument");
+  REQUIRE(e->flacdec_n_samples >= 0, "asx_flac_decode_finish_dev: no asx_flac_decode_scan_dev on this engine before it");
+  REQUIRE(n_samples >= 1 && n_samples == e->flacdec_n_samples, "asx_flac_decode_finish_dev: n_samples = %lld, the scan found %lld", (long long)n_samples,
+          (long long)e->flacdec_n_samples);
+  REQUIRE((((uintptr_t)mix_dev) & 3) == 0, "asx_flac_decode_finish_dev: mix must be 4-byte aligned");
+  HIPCHK(hipSetDevice(e->device));
+  return flac_decode_finish_launch(e, mix_dev, n_samples, peak, reinterpret_cast<hipStream_t>(stream));
+}
+
+int asx_flac_decode(asx_engine *e, const uint8_t *audio_host, int64_t audio_bytes, int32_t sample_rate, int32_t channels, int32_t bits_per_sample,
+                    int32_t max_blocksize, int32_t max_framesize, float *mix_host, int64_t capacity, int64_t *n_samples, int64_t *n_frames,
+                    int64_t *bytes_consumed, float *peak) {
+  REQUIRE(e && audio_host && n_samples && (mix_host || capacity == 0) && capacity >= 0, "asx_flac_decode: null argument");
+  FlacDecPlan p;
+  const std::string why = flac_dec_plan_make(audio_bytes, channels, bits_per_sample, max_blocksize, max_framesize, p);
+  REQUIRE(why.empty(), "asx_flac_decode: %s", why.c_str());
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf din, dmix;
+  BufGuard g{{&din, &dmix}};
+  CHK(din.ensure(((size_t)audio_bytes + 3) / 4 * 4));
+  HIPCHK(hipMemcpy(din.p, audio_host, (size_t)audio_bytes, hipMemcpyHostToDevice));
+  CHK(asx_flac_decode_scan_dev(e, reinterpret_cast<const uint8_t *>(din.p), audio_bytes, sample_rate, channels, bits_per_sample, max_blocksize,
+                               max_framesize, n_samples, n_frames, bytes_consumed, nullptr));
+  if (peak) *peak = 0.f;
+  if (*n_samples == 0) return ASX_OK;
+  REQUIRE(capacity >= *n_samples, "asx_flac_decode: capacity of %lld samples per row, the stream holds %lld", (long long)capacity, (long long)*n_samples);
+  CHK(dmix.ensure((size_t)2 * (size_t)*n_samples * 4));
+  CHK(asx_flac_decode_finish_dev(e, dmix.f(), *n_samples, peak, nullptr));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(mix_host, dmix.p, (size_t)2 * (size_t)*n_samples * 4, hipMemcpyDeviceToHost));
   return ASX_OK;
 }
 

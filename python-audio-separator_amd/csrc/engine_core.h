@@ -224,6 +224,13 @@ struct asx_engine {
   DevBuf flac_cycles;             // the two clock sums of a profiled encode, and their totals since the engine was created
   long long flac_block_cycles = 0, flac_crc16_cycles = 0;
   DevBuf flac_frames, flac_off;   // asx_flac_encode_dev: frame slots at the plan's stride, and the offsets of the compacted frames
+  // asx_flac_decode_scan_dev: the counter, candidate list and records; the candidates' slots [candidate][2][max_blocksize]; the chain's frames.
+  // What the last scan left for asx_flac_decode_finish_dev: the sample count (-1: no scan), the frames, the stream's shape.
+  DevBuf flacdec_list, flacdec_slots, flacdec_accept;
+  std::vector<flacdec::Accept> flacdec_accept_host;   // the source of the copy into flacdec_accept, alive until the next scan
+  int64_t flacdec_n_samples = -1, flacdec_n_frames = 0;
+  int32_t flacdec_channels = 0, flacdec_bps = 0, flacdec_max_bs = 0;
+  size_t flacdec_slot_off = 0;       // the slots begin behind the records in flacdec_slots
   // coefficient tables of asx_resample_rational, one per (sr_in, sr_out), built on first use and kept until the engine goes (the entries never
   // move: a launch in flight reads its table)
   std::vector<RsTable *> rs_tabs;

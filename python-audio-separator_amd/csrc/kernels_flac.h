@@ -27,7 +27,7 @@
 #include <cmath>
 #include <cstring>
 #define FLAC_FN static inline
-#define FLAC_LANES for (int tid = 0; tid < asx::flac::NT; ++tid)
+#define FLAC_LANES_OF(N) for (int tid = 0; tid < (N); ++tid)
 #define FLAC_SYNC() ((void)0)
 #define FLAC_ADD64(p, v) (*(p) += (v))
 #define FLAC_OR32(p, v) (*(p) |= (v))
@@ -36,13 +36,14 @@
 #else
 #include <hip/hip_runtime.h>
 #define FLAC_FN static __host__ __device__ inline
-#define FLAC_LANES for (int tid = (int)threadIdx.x, once_ = 0; once_ < 1; ++once_)
+#define FLAC_LANES_OF(N) for (int tid = (int)threadIdx.x, once_ = 0; once_ < 1; ++once_)
 #define FLAC_SYNC() __syncthreads()
 #define FLAC_ADD64(p, v) atomicAdd((p), (v))
 #define FLAC_OR32(p, v) atomicOr((p), (v))
 #define FLAC_MIN64(p, v) atomicMin((p), (v))
 #define FLAC_CLOCK(P) (((P).cycles != nullptr && threadIdx.x == 0) ? (long long)clock64() : 0ll)   // lane 0's stamps, for the profile only
 #endif
+#define FLAC_LANES FLAC_LANES_OF(asx::flac::NT)   // the encoder's workgroup; the decoder (kernels_flac_dec.h) names its own lane count
 
 namespace asx {
 namespace flac {
@@ -63,15 +64,20 @@ FLAC_FN int64_t worst_frame_bytes(int64_t bs) { return HEADER_MAX + (2 * (16 + 1
 FLAC_FN int frame_stride(int block_size) { return (int)((worst_frame_bytes(block_size) + 15) / 16 * 16); }
 
 // the header's block-size code: a table entry, else 6 / 7 = (size - 1) in 8 / 16 bits behind the frame number
+// the block size of a table code 1 .. 5 and 8 .. 15 (0 for the reserved code and for 6 / 7, whose size follows the frame number)
+FLAC_FN int table_block_size(int code) {
+  return code == 1 ? 192 : (code >= 2 && code <= 5) ? (576 << (code - 2)) : (code >= 8 && code <= 15) ? (256 << (code - 8)) : 0;
+}
 FLAC_FN int block_size_code(int bs, bool table) {
-  if (table) {
-    if (bs == 192) return 1;
-    for (int c = 2; c <= 5; ++c)
-      if (bs == (576 << (c - 2))) return c;
-    for (int c = 8; c <= 15; ++c)
-      if (bs == (256 << (c - 8))) return c;
-  }
+  if (table)
+    for (int c = 1; c <= 15; ++c)
+      if (bs == table_block_size(c)) return c;
   return bs <= 256 ? 6 : 7;
+}
+// the sample rate of a table code 1 .. 11 (0 for every other code)
+FLAC_FN int table_sample_rate(int code) {
+  const int tab[12] = {0, 88200, 176400, 192000, 8000, 16000, 22050, 24000, 32000, 44100, 48000, 96000};
+  return code >= 1 && code <= 11 ? tab[code] : 0;
 }
 
 struct Stream {
@@ -90,11 +96,10 @@ struct Stream {
 
 // the header's sample-rate fields for a rate the format can carry (1 .. 1048575 Hz)
 FLAC_FN void sample_rate_code(int sr, int32_t *code, int32_t *extra_bits, uint32_t *extra) {
-  const int tab[12] = {0, 88200, 176400, 192000, 8000, 16000, 22050, 24000, 32000, 44100, 48000, 96000};
   *extra_bits = 0;
   *extra = 0;
   for (int c = 1; c < 12; ++c)
-    if (sr == tab[c]) {
+    if (sr == table_sample_rate(c)) {
       *code = c;
       return;
     }
@@ -165,6 +170,21 @@ FLAC_FN uint32_t crc16_mul(uint32_t a, uint32_t b) {
     if ((b >> i) & 1u) r ^= a;
   }
   return r;
+}
+// `crc` (the CRC-16 of everything before) continued over `nbytes` more bytes whose CRCs per CRC_CHUNK bytes (the last chunk may be shorter)
+// are crcs[0 .. nchunks): one multiplication by x^(8 * chunk bytes) mod P per chunk
+FLAC_FN uint32_t crc16_combine(uint32_t crc, const uint32_t *crcs, int nchunks, int nbytes) {
+  uint32_t x512 = 1;                            // x^(8 * CRC_CHUNK) mod P: a CRC state moved past one chunk of zero bytes
+  for (int b = 0; b < CRC_CHUNK; ++b) x512 = crc16_byte(x512, 0);
+  for (int j = 0; j < nchunks; ++j) {
+    uint32_t mul = x512;
+    if (j == nchunks - 1) {
+      mul = 1;
+      for (int b = j * CRC_CHUNK; b < nbytes; ++b) mul = crc16_byte(mul, 0);
+    }
+    crc = crc16_mul(crc, mul) ^ crcs[j];
+  }
+  return crc;
 }
 FLAC_FN uint32_t crc8_byte(uint32_t crc, uint32_t b) {
   crc ^= b;
@@ -595,17 +615,7 @@ static __device__ __forceinline__ void encode_block(const Stream &P, int64_t blk
   FLAC_SYNC();
   FLAC_LANES {
     if (tid == 0) {
-      uint32_t x512 = 1;                        // x^(8 * CRC_CHUNK) mod P: a CRC state moved past one chunk of zero bytes
-      for (int b = 0; b < CRC_CHUNK; ++b) x512 = crc16_byte(x512, 0);
-      uint32_t crc = 0;
-      for (int j = 0; j < nchunks; ++j) {
-        uint32_t mul = x512;
-        if (j == nchunks - 1) {
-          mul = 1;
-          for (int b = j * CRC_CHUNK; b < nbytes; ++b) mul = crc16_byte(mul, 0);
-        }
-        crc = crc16_mul(crc, mul) ^ S.crcs[j];
-      }
+      const uint32_t crc = crc16_combine(0u, S.crcs, nchunks, nbytes);
       put_bits(img, (uint32_t)nbytes * 8u, 16, crc);
       P.frame_bytes[blk] = S.frame_len;
     }

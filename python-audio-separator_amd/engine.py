@@ -278,7 +278,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_demix_batch_dev", "asx_separate_batch_dev", "asx_ensemble_slot_dev", "asx_vr_separate_batch_dev",
            "asx_mdxc_demix_batch_dev", "asx_rof_demix_batch_dev", "asx_ensemble_batch_dev", "asx_resample_rational_plan",
            "asx_resample_rational", "asx_resample_rational_dev", "asx_op_hd_lstm_layer", "asx_op_hd_lstm_frames", "asx_op_vr_lstm",
-           "asx_op_vr_lstm_layout", "asx_flac_plan", "asx_flac_encode", "asx_flac_encode_dev"]
+           "asx_op_vr_lstm_layout", "asx_flac_plan", "asx_flac_encode", "asx_flac_encode_dev",
+           "asx_flac_decode_plan", "asx_flac_decode_scan_dev", "asx_flac_decode_finish_dev", "asx_flac_decode"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -423,6 +424,11 @@ def load_library():
     lib.asx_flac_plan.argtypes = [i64, i32, i32, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
     lib.asx_flac_encode.argtypes = [vp, C.POINTER(C.c_int16), i64, i32, i32, i32, C.POINTER(C.c_uint8), i64, C.POINTER(i32), C.POINTER(i64)]
     lib.asx_flac_encode_dev.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, vp, C.POINTER(i64), vp]
+    lib.asx_flac_decode_plan.argtypes = [i64, i32, i32, i32, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    lib.asx_flac_decode_scan_dev.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp]
+    lib.asx_flac_decode_finish_dev.argtypes = [vp, vp, i64, _FP, vp]
+    lib.asx_flac_decode.argtypes = [vp, C.POINTER(C.c_uint8), i64, i32, i32, i32, i32, i32, _FP, i64, C.POINTER(i64), C.POINTER(i64),
+                                    C.POINTER(i64), _FP]
     lib.asx_ensemble.argtypes = [vp, _FP, i32, i64, i32, C.POINTER(C.c_double), _FP, C.POINTER(i64)]
     lib.asx_ensemble_dev.argtypes = [vp, vp, i32, i64, i32, C.POINTER(C.c_double), vp, C.POINTER(i64), vp]
     lib.asx_invert_stem.argtypes = [vp, _FP, _FP, i64, _FP, C.POINTER(i64)]
@@ -1119,6 +1125,58 @@ class Engine:
         self._check(self._lib.asx_flac_encode_dev(self._h, pcm_ptr, int(n_samples), int(samplerate), int(bits_per_sample), int(block_size), out_ptr,
                                                   int(out_capacity), frame_bytes_ptr, C.byref(total), stream or None))
         return total.value
+
+    @staticmethod
+    def flac_decode_plan(audio_bytes: int, channels: int = 2, bits_per_sample: int = 16, max_blocksize: int = FLAC_BLOCK_SIZE,
+                         max_framesize: int = 0) -> dict:
+        """asx_flac_decode_plan (pure host: no engine, no GPU): {max_candidates, slot_bytes, scratch_bytes} of the FLAC decoder for an audio
+        part of ``audio_bytes``.  Raises AsxError for what the decoder refuses: widths outside 8 .. 24 bits, more than two channels, a
+        maximum block size outside 16 .. 16384, empty input."""
+        lib = load_library()
+        cap, slot, scratch = C.c_int64(), C.c_int64(), C.c_int64()
+        rc = lib.asx_flac_decode_plan(int(audio_bytes), int(channels), int(bits_per_sample), int(max_blocksize), int(max_framesize),
+                                      C.byref(cap), C.byref(slot), C.byref(scratch))
+        if rc != 0:
+            msg = lib.asx_last_error()
+            raise AsxError(f"asx error {rc}: {msg.decode() if msg else '?'}")
+        return {"max_candidates": cap.value, "slot_bytes": slot.value, "scratch_bytes": scratch.value}
+
+    def flac_decode_scan_dev(self, audio_ptr: int, audio_bytes: int, info: dict, stream: int = 0) -> dict:
+        """asx_flac_decode_scan_dev: the audio part of a FLAC stream on the device (``info``: audio_io.flac_stream's STREAMINFO fields) ->
+        {n_samples, n_frames, bytes_consumed}; the decoded frames stay in engine scratch for ``flac_decode_finish_dev``."""
+        n, nf, used = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._lib.asx_flac_decode_scan_dev(self._h, audio_ptr, int(audio_bytes), int(info["samplerate"]), int(info["channels"]),
+                                                       int(info["bits_per_sample"]), int(info["max_blocksize"]), int(info["max_framesize"]),
+                                                       C.byref(n), C.byref(nf), C.byref(used), stream or None))
+        return {"n_samples": n.value, "n_frames": nf.value, "bytes_consumed": used.value}
+
+    def flac_decode_finish_dev(self, mix_ptr: int, n_samples: int, stream: int = 0, want_peak: bool = True):
+        """asx_flac_decode_finish_dev: the frames of the last scan -> float32 planar [2, n_samples] at ``mix_ptr``; returns max |mix|
+        (synchronises the stream) or None."""
+        pk = C.c_float()
+        self._check(self._lib.asx_flac_decode_finish_dev(self._h, mix_ptr, int(n_samples), C.byref(pk) if want_peak else None, stream or None))
+        return pk.value if want_peak else None
+
+    def flac_decode(self, data, info: dict, details: bool = False):
+        """The audio part of a FLAC stream (bytes or uint8 array) -> float32 [2, n]; asx_flac_decode.  ``details``: also
+        {n_samples, n_frames, bytes_consumed, peak}."""
+        a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8).reshape(-1)
+        args = (int(info["samplerate"]), int(info["channels"]), int(info["bits_per_sample"]), int(info["max_blocksize"]), int(info["max_framesize"]))
+        self.flac_decode_plan(a.size, *args[1:])
+        n, nf, used, pk = C.c_int64(), C.c_int64(), C.c_int64(), C.c_float()
+        capacity = int(info.get("total_samples") or 0) or 16 * a.size
+        for _ in range(2):                       # total_samples is a hint: a stream that holds more is decoded again at its own count
+            out = np.empty((2, capacity), np.float32)
+            rc = self._lib.asx_flac_decode(self._h, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.size, *args, _ptr(out), capacity, C.byref(n),
+                                           C.byref(nf), C.byref(used), C.byref(pk))
+            if rc == 0 or n.value <= capacity:
+                break
+            capacity = n.value
+        self._check(rc)
+        mix = np.ascontiguousarray(out.reshape(-1)[:2 * n.value].reshape(2, n.value))
+        if details:
+            return mix, {"n_samples": n.value, "n_frames": nf.value, "bytes_consumed": used.value, "peak": pk.value}
+        return mix
 
     def pcm16_rows_dev(self, stem_ptr: int, n_samples: int, max_peak: float, min_peak, pcm_ptr: int, stream: int = 0,
                        want_peak: bool = True):

@@ -327,7 +327,7 @@ class EnsembleSeparator:
 
     def _runs(self, paths):
         """``paths`` as consecutive runs of indices, in order.  ``pool_files`` set: that many per run.  Else a run's estimated stem
-        bytes -- frames (audio_io.wav_info) x 8 bytes x stems of all members -- stay within ``HBM_SHARE`` of the free HBM; a run of
+        bytes -- frames (audio_io.wav_info, or a FLAC stream's total_samples) x 8 bytes x stems of all members -- stay within ``HBM_SHARE`` of the free HBM; a run of
         one file is always allowed."""
         if not paths:
             return []
@@ -341,8 +341,11 @@ class EnsembleSeparator:
         for i, path in enumerate(paths):
             try:
                 cost = audio_io.wav_info(path)["frames"] * per_frame
-            except Exception:    # not a RIFF/WAVE file: it takes the file path or fails, no stems are kept for it
-                cost = 0
+            except Exception:    # not a RIFF/WAVE file: a FLAC stream by STREAMINFO's sample count where it gives one; anything else takes the
+                try:             # file path or fails, no stems are kept for it
+                    cost = audio_io.flac_stream(path)["total_samples"] * per_frame
+                except Exception:
+                    cost = 0
             if runs[-1] and used + cost > self.HBM_SHARE * free:
                 runs.append([])
                 used = 0
