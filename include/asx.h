@@ -848,8 +848,8 @@ int asx_op_vr_lstm_layout(asx_engine *e, int32_t dir, const float *src_host, int
  * with 48n <= N (at most 144: the weight image is packed up to 144 channels) on planes whose width is a multiple of 32 (levels 0, 1 and 2 of
  * the HQ_3 geometry) runs conv3h_kernel (csrc/kernels_conv3h.h): a DIRECT implicit GEMM on the fp16
  * matrix pipe with the arithmetic of "gemm_f16x3" (which must be on, as "gemm_bf16x6" and "winograd" = 3) -- the two-part weight image stays in
- * LDS for the whole launch, producer waves fetch four input rows per step into a ring walked down T and split them under one running
- * power-of-two exponent per walk, consumer waves multiply; n x n launches over 48-channel slices; 5.3-5.8 ms per launch of 55 chunks against
+ * LDS for the whole launch, producer waves fetch four input rows per step into a ring walked down T and split them under one
+ * power-of-two exponent per four-row block, consumer waves multiply; n x n launches over 48-channel slices; 5.3-5.8 ms per launch of 55 chunks against
  * 8.5-8.9 on conv_wino3_kernel at 48 channels.  0 = never (conv_wino3_kernel / conv_wino6_kernel).
  * "conv_fuse_input" (an option only, no environment variable): 1 (default) = where the first 3x3 TFC convolution of a BatchNorm ConvTDFNet runs
  * conv3h_kernel at 48 channels, its producer waves compute the net's 1x1 input convolution (4 -> 48 channels, folded BatchNorm, ReLU) themselves
@@ -861,6 +861,11 @@ int asx_op_vr_lstm_layout(asx_engine *e, int32_t dir, const float *src_host, int
  * slice writes the planar output); 0 = through the output tensor itself, in the planar layout.  The values and the order of the additions are
  * the same: results are equal bit for bit, and "conv3h_launches" counts n x n per layer either way.  The scratch (24576 bytes per 4 x 32 tile of
  * the largest sliced layer, times the batch) is allocated with the engine's workspaces, never at a launch.
+ * "conv3h_walk" (an option only, no environment variable): how conv3h_kernel's 256 persistent workgroups share the (batch item, band of strips,
+ * tile rows) of a launch -- a table planned on the host (csrc/conv3h_walk_plan.h) and uploaded with the engine's workspaces, never at a launch.
+ * 1 (default) = balanced: whole planes to every group of workgroups while whole rounds remain, the leftover items cut into equal shares of tile
+ * rows over all groups; 0 = the arithmetic walk (XCD x takes items x, x + 8, ..., a fixed segment of T per group).  A block's exponent is a
+ * function of the block alone, so the results are equal bit for bit under either schedule and for a chunk alone or in any batch.
  * "conv_down_bf16x6" / "conv_up_bf16x6" (ABI 7; also ASX_DOWN6 / ASX_UP6): 1 (default) = the 2 x 2 / stride-2 convolutions between the levels
  * (mdxnet.py:66-72) and the transposed ones of the decoder with their `x *= skip` (mdxnet.py:80-86, 113) run conv_down6_kernel / conv_up6_kernel
  * (csrc/kernels_updown6.h) while "gemm_bf16x6" is on: the arithmetic of that option -- both fp32 operands split EXACTLY into three bf16 parts, six

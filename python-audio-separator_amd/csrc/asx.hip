@@ -96,6 +96,7 @@ static const struct EngineOption {
     {"conv_direct_f16x3", &asx_engine::conv3h, &EngineKnobs::conv3h, opt_nonneg},
     {"conv_fuse_input", &asx_engine::conv_fuse_input, &EngineKnobs::conv_fuse_input, opt_onoff},
     {"conv3h_partial_scratch", &asx_engine::conv3h_ps, &EngineKnobs::conv3h_ps, opt_onoff},
+    {"conv3h_walk", &asx_engine::conv3h_walk, &EngineKnobs::conv3h_walk, opt_onoff},
     {"conv_down_bf16x6", &asx_engine::down6, &EngineKnobs::down6, opt_onoff},
     {"conv_up_bf16x6", &asx_engine::up6, &EngineKnobs::up6, opt_onoff},
     {"gemm_pair_images", &asx_engine::pair_images, &EngineKnobs::pair_images, opt_onoff,
@@ -315,6 +316,11 @@ void asx_engine_destroy(asx_engine *e) {
   e->spec_out.release();
   for (auto &r : e->R) r.release();
   e->c3h_ps.release();
+  for (Conv3hWalkTab *t : e->c3h_walks) {
+    t->tab.release();
+    delete t;
+  }
+  e->c3h_walks.clear();
   e->H.release();
   e->frames.release();
   e->chunk_out.release();
@@ -603,6 +609,7 @@ int asx_demix_chunks_dev(asx_engine *e, const float *mix_dev, int64_t N, int32_t
   if (nk == 0) return ASX_OK;
   const int per = even_batches(nk, pick_batch(e));
   CHK(ensure_workspace(e, per, need_net));
+  if (need_net && nk % per) CHK(net_walks_ensure(e, (nk % per) * (e->cfg.enable_denoise ? 2 : 1)));   // the last, shorter pass walks its own tables
   // chunk tables, built on the device: start of chunk k = k * step, active length = min(chunk, L - start), or negative
   // for "no chunk window" (overlap == 0, mdx_separator.py:389-390).  No host copy, no host synchronisation: the call
   // only enqueues work on `stream` (hipGraph-capturable, and a gather of step k can overlap the compute of step k + 1).
@@ -732,6 +739,7 @@ static int demix_pool_dev(asx_engine *e, const float *const *mix, float *const *
   for (int i = 0; i < n; ++i)
     if (div_off.emplace(Ns[i], div_floats).second) div_floats += (Ns[i] + 3) / 4 * 4;
   CHK(ensure_workspace(e, per, need_net));
+  if (need_net && nk % per) CHK(net_walks_ensure(e, (nk % per) * (e->cfg.enable_denoise ? 2 : 1)));
   CHK(e->d_starts.ensure((size_t)nk * 8));
   CHK(e->d_nact.ensure((size_t)nk * 8));
   CHK(e->pool_wave.ensure((size_t)nk * 8));
@@ -1423,6 +1431,7 @@ int asx_op_conv(asx_engine *e, const char *op, const float *x_host, int32_t B, i
   HIPCHK(hipMemset(dy.p, 0xff, ny * 4));  // NaN canary: every output element must be written
   if (kind == CK_UP) CHK(to_dev(dskip, aux_host, ny));
   CHK(e->c3h_ps.ensure(conv3h_ps_need(L, B, t, f)));   // (the nets size it with their workspaces; to_host below waits before anything else can regrow it)
+  CHK(conv3h_walk_ensure(e, L, B, t, f));
   CHK(conv_launch(e, L, dx.f(), dskip.f(), dy.f(), B, t, f, nullptr));
   CHK(to_host(y_host, dy, ny));
   return ASX_OK;
@@ -2048,6 +2057,7 @@ static int mdxc_pool_demix(asx_engine *e, const char *fn, bool rof, const asx_md
   const MdxcBranch br = mdxc_branch(e, rof);
   const int nk = pp.total(), per = mdxc_pool_per_pass(nk, e->cfg.max_batch);
   CHK(rof ? rof_ensure_workspace(e, per) : v3_ensure_workspace(e, per));
+  if (!rof && nk % per) CHK(v3_walks_ensure(e, nk % per));   // the last, shorter pass walks its own tables
   CHK(br.chunk_out.ensure((size_t)nk * br.chunk_floats(pp) * 4));
   int64_t blk = 0;
   CHK(mdxc_pool_tables(e, fn, br, songs, pp, br.chunk_out.f(), s, &blk));

@@ -152,6 +152,13 @@ struct RsTable {
   DevBuf tab;
 };
 
+// one uploaded walk table of conv3h_kernel and what it was planned for
+struct Conv3hWalkTab {
+  int B, tilesT, tilesF, mode;   // mode: option "conv3h_walk"
+  int bw, stride;
+  DevBuf tab;
+};
+
 struct V3Net;
 struct RofNet;
 struct HtNet;
@@ -217,6 +224,9 @@ struct asx_engine {
   DevBuf pool_wave, pool_nsong, pool_songs, pool_div, pool_peak;
   DevBuf c3h_ps;     // conv3h_kernel's partial sums between the slice launches of a 96- / 144-channel layer (Conv3hCfg::ps_bytes of the largest such
                      // layer and batch); sized with the workspaces, never at a launch: a captured graph holds the pointer
+  // conv3h_kernel's walk tables (conv3h_walk_plan.h), one per (batch, tile rows, strips, schedule): built and uploaded with the workspaces
+  // (conv3h_walk_ensure, engine_mdx.h), never at a launch, and kept until the engine goes (the entries never move: a captured graph holds the pointer)
+  std::vector<Conv3hWalkTab *> c3h_walks;
   DevBuf gn_part;    // per-plane float64 (sum, sum of squares) of the GroupNorm variant of the net (asx_net_config.norm == 1)
   DevBuf d_div;      // divider of the chunk fold for div_key's plan (input-independent: built once, asx_finalize_dev)
   DivKey div_key;
@@ -238,7 +248,7 @@ struct asx_engine {
   hipEvent_t div_ev = nullptr;       // recorded behind the kernel that built d_div; a call on ANOTHER stream waits for it
   hipStream_t div_stream = nullptr;
   std::vector<DevBuf> skip;
-  // The eleven engine options (asx_set_option / asx_get_option; asx_engine_create sets them from EngineKnobs, knobs.h).
+  // The twelve engine options (asx_set_option / asx_get_option; asx_engine_create sets them from EngineKnobs, knobs.h).
   // 3x3 / pad-1 convs of the ConvTDFNet and TFC-TDF-v3 nets: 3 = Winograd F(2x2,3x3) (conv_wino3_kernel, the default), 0 = the
   // direct kernel (conv_dma_kernel), 1 / 2 = the earlier Winograd generations (kept for A/B runs; experimental builds only).
   // ASX_WINOGRAD or asx_set_option("winograd", n).
@@ -274,6 +284,11 @@ struct asx_engine {
   // itself in the planar layout (a.prev = a.y: six stores / loads of eight separate 128-byte lines per wave and tile).  Same values, same order
   // of additions: the results are equal bit for bit.  asx_set_option("conv3h_partial_scratch", n); no environment variable.
   int conv3h_ps = 1;
+  // How conv3h_kernel's 256 workgroups share a launch's (batch item, band of strips, tile rows) -- the walk table, conv3h_walk_plan.h.  1 (default):
+  // balanced -- whole planes to every group of workgroups while whole rounds remain, the leftover items cut into equal shares of tile rows over
+  // all groups; 0: the arithmetic walk (XCD x takes items x, x + 8, ..., a fixed segment of T per group), through the same table path.  The
+  // results are equal bit for bit: a block's exponent does not depend on the walk.  asx_set_option("conv3h_walk", n); no environment variable.
+  int conv3h_walk = 1;
   // 1 (default): the net's 1x1 input conv (4 -> 48 channels, folded BatchNorm, ReLU) is computed by the producer waves of the first TFC conv's
   // conv3h_kernel launch (its fused-input form) instead of in a launch of its own: the 48-channel level-0 activation is never written to
   // memory and read back.  0: two launches.  Only where the first 3x3 layer runs conv3h_kernel at 48 channels and the net uses BatchNorm.

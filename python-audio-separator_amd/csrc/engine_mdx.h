@@ -277,6 +277,36 @@ static size_t conv3h_ps_need(const ConvLayer &L, int B, int T, int F) {
   return (size_t)Conv3hCfg::ps_bytes(B, (T + 3) / 4, F / 32);
 }
 
+// The walk tables (conv3h_walk_plan.h) a conv_launch of this layer on B items of T x F may read -- both schedules, since option "conv3h_walk" may
+// change between two forwards: planned, uploaded and kept.  Called wherever c3h_ps is sized, for every batch size a pass will launch with.
+static const Conv3hWalkTab *conv3h_walk_find(const asx_engine *e, int B, int tilesT, int tilesF, int mode) {
+  for (const Conv3hWalkTab *t : e->c3h_walks)
+    if (t->B == B && t->tilesT == tilesT && t->tilesF == tilesF && t->mode == mode) return t;
+  return nullptr;
+}
+static int conv3h_walk_ensure(asx_engine *e, const ConvLayer &L, int B, int T, int F) {
+  if (L.kind != CK_3X3 || L.w3h.p == nullptr || F % 32 != 0 || B <= 0 || T <= 0) return ASX_OK;
+  const int tilesT = (T + 3) / 4, tilesF = F / 32;
+  for (int mode = 0; mode < 2; ++mode) {
+    if (conv3h_walk_find(e, B, tilesT, tilesF, mode)) continue;
+    const Conv3hWalkPlan plan = conv3h_walk_plan(B, tilesT, tilesF, 1, mode);   // granularity 1: a block's exponent does not depend on the walk
+    std::vector<int32_t> tab;
+    Conv3hWalkTab *t = new Conv3hWalkTab{B, tilesT, tilesF, mode, plan.bw, conv3h_walk_table(plan, tab), DevBuf()};
+    int rc = t->tab.ensure(tab.size() * 4);
+    if (rc == ASX_OK && hipMemcpy(t->tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+      set_err("conv3h_walk_ensure: the upload of a walk table failed");
+      rc = ASX_ERR_HIP;
+    }
+    if (rc != ASX_OK) {
+      t->tab.release();
+      delete t;
+      return rc;
+    }
+    e->c3h_walks.push_back(t);
+  }
+  return ASX_OK;
+}
+
 // x [B,cin,T,F] -> y
 static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const float *skip, float *y, int B, int T,
                        int F, hipStream_t s, const ConvView &v = ConvView()) {
@@ -386,21 +416,10 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     // arguments of all n x n launches are built HERE, once: the scratch forms rely on identical walks (kernels_conv3h.h, PS).
     const int nb = L.cin / Conv3hCfg::C;
     const int tilesT = (T + 3) / 4, tilesF = F / 32;
-    // walk geometry: bands of 32 / 16 / 8 strips -- whole bands on the plane's width, charged for the extra block per segment of T and for how evenly
-    // the (b, band) items deal out over the 8 XCDs (a 7-chunk strong-scaling pass has 21 items of 32 strips at level 0: 3 / 2 per XCD; 84 of 8 strips: 11 / 10)
-    int bw = 32;
-    double best = 1e30;
-    for (int cand : {32, 16, 8}) {
-      if ((tilesT * cand) % 32 != 0) continue;
-      const int tps = tilesT * cand / 32;
-      const int bands = (tilesF + cand - 1) / cand, items = B * bands;
-      const double cost = (double)(bands * cand) / tilesF * (tps + 1.0) / tps * (double)((items + 7) / 8) / (items / 8.0);
-      if (cost < best - 1e-9) {
-        best = cost;
-        bw = cand;
-      }
-    }
-    if (best > 1e29) bw = 32;                          // (tilesT not divisible: one segment)
+    // the walk of the 256 workgroups over (item, band of strips, tile rows): a table planned with the workspaces (option "conv3h_walk": 1 = balanced,
+    // 0 = the arithmetic walk), never built here -- a launch allocates and copies nothing
+    const Conv3hWalkTab *wt = conv3h_walk_find(e, B, tilesT, tilesF, e->conv3h_walk > 0 ? 1 : 0);
+    REQUIRE(wt != nullptr, "conv3h_kernel: no walk table for %d x %d x %d (the workspace set-up plans them)", B, T, F);
     grant_lds(&conv3h_kernel<0, false>, Conv3hCfg::LDS_BYTES);
     grant_lds(&conv3h_kernel<0, true>, Conv3hCfg::LDS_BYTES);
     grant_lds(&conv3h_kernel<0, false, true>, Conv3hCfg::LDS_BYTES);
@@ -420,8 +439,9 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     walk.y_bstride = a.y_bstride;
     walk.tilesT = tilesT;
     walk.tilesF = tilesF;
-    walk.bw = bw;
-    walk.tps = (tilesT * bw) % 32 == 0 ? tilesT * bw / 32 : tilesT;
+    walk.bw = wt->bw;
+    walk.walk = reinterpret_cast<const u32x4 *>(wt->tab.p);
+    walk.walk_stride = wt->stride;
     walk.ps = ps ? e->c3h_ps.p : nullptr;
     walk.ps_bstride = ps_item;
     return timed(e, cls, flops, bytes, s, [&]() {
@@ -1332,6 +1352,18 @@ static int net_forward_dev(asx_engine *e, const float *spec_in, float *spec_out,
 // ----------------------------------------------------------------------------
 // workspace
 // ----------------------------------------------------------------------------
+// conv3h_kernel's walk tables for a forward of Bn items (ensure_workspace plans the pass size; a call whose last pass is shorter asks for that size too)
+static int net_walks_ensure(asx_engine *e, int Bn) {
+  auto walks = [&](const Block &blk) -> int {
+    for (const ConvLayer &L : blk.tfc) CHK(conv3h_walk_ensure(e, L, Bn, blk.t, blk.f));
+    return ASX_OK;
+  };
+  for (const Block &blk : e->enc) CHK(walks(blk));
+  CHK(walks(e->mid));
+  for (const Block &blk : e->dec) CHK(walks(blk));
+  return ASX_OK;
+}
+
 static int ensure_workspace(asx_engine *e, int Bchunks, bool need_net) {
   const int T = e->cfg.segment_size, Fq = e->cfg.dim_f;
   const int mult = (need_net && e->cfg.enable_denoise) ? 2 : 1;
@@ -1361,6 +1393,7 @@ static int ensure_workspace(asx_engine *e, int Bchunks, bool need_net) {
     ps_block(e->mid);
     for (const Block &blk : e->dec) ps_block(blk);
     CHK(e->c3h_ps.ensure(ps));
+    CHK(net_walks_ensure(e, (int)Bn));
   }
   e->ws_batch = std::max(e->ws_batch, Bchunks);
   return ASX_OK;

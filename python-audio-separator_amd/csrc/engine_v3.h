@@ -219,8 +219,28 @@ static int v3_tfc_tdf(asx_engine *e, const std::vector<V3Block> &blocks, V3View 
   return ASX_OK;
 }
 
+// conv3h_kernel's walk tables (conv3h_walk_ensure) for a forward of B chunks: v3_core_dev's walk over the levels
+static int v3_walks_ensure(asx_engine *e, int B) {
+  V3Net &n = *e->v3;
+  const asx_v3_config &cf = n.cfg;
+  auto walks = [&](const std::vector<V3Block> &bs, int t, int f) -> int {
+    for (const V3Block &b : bs) {
+      CHK(conv3h_walk_ensure(e, b.tfc1, B, t, f));
+      CHK(conv3h_walk_ensure(e, b.tfc2, B, t, f));
+    }
+    return ASX_OK;
+  };
+  int t = e->cfg.segment_size, f = e->cfg.dim_f / cf.num_subbands;
+  for (int i = 0; i < cf.num_scales; ++i, t /= 2, f /= 2) {
+    CHK(walks(n.enc[i], t, f));
+    CHK(walks(n.dec[cf.num_scales - 1 - i], t, f));
+  }
+  return walks(n.mid, t, f);
+}
+
 static int v3_ensure_workspace(asx_engine *e, int B) {
   V3Net &n = *e->v3;
+  CHK(v3_walks_ensure(e, B));                          // (per batch size, not per largest batch: a table is planned for its B)
   if (B <= n.ws_batch) return ASX_OK;
   const asx_v3_config &cf = n.cfg;
   const int T = e->cfg.segment_size, k = cf.num_subbands, Fs = e->cfg.dim_f / k;

@@ -24,7 +24,7 @@
 //   * waves 4-7 PRODUCE a block of four input rows x 40 columns x 48 channels per step: 240 (row, 8-channel group, column quad) items, one per
 //     lane, eight `buffer_load_dwordx4` each (out-of-image rows / columns through the buffer bounds check = 0).  Four register sets: block
 //     s + 4 is fetched, block s + 2's largest |x| reduced (v_max3 + DPP in a wave, a four-entry LDS table across waves, published by the step
-//     barrier), block s + 1 scaled by the walk's running power of two, split h + l (`v_fma_mixlo / hi_f16`) and written to its slot of a
+//     barrier), block s + 1 scaled by the block's own power of two, split h + l (`v_fma_mixlo / hi_f16`) and written to its slot of a
 //     12-row ring (`ds_write_b128`, 2-way at worst);
 //   * waves 0-3 CONSUME block s: wave r owns output row r of the tile (two 16-pixel MFMA tiles x three 16-channel tiles = six accumulators);
 //     per stage it reads six weight fragments and four x fragments (`ds_read_b128`, a stage ahead) and issues 18 MFMAs (w_l x_h, w_h x_l,
@@ -40,6 +40,7 @@
 #include <cstring>
 #include <vector>
 
+#include "conv3h_walk_plan.h"
 #include "kernels_gemm3.h"
 
 namespace asx {
@@ -53,7 +54,9 @@ struct Conv3hArgs {
   int64_t x_bstride, y_bstride;
   int act;                   // ACT_NONE / ACT_RELU
   int tilesT, tilesF;        // ceil(T / 4), F / 32
-  int bw, tps;               // walk geometry: strips per band (32, 16 or 8: an XCD's 32 workgroups take bw strips x 32 / bw segments of T), tiles per segment (tilesT * bw / 32)
+  int bw;                    // walk geometry: strips per band (32, 16 or 8: an XCD's 32 workgroups are 32 / bw groups of bw adjacent strips)
+  const u32x4 *walk;         // the walk table (conv3h_walk_plan.h, conv3h_walk_table): row g = {steps, units, 0, 0}, the units {b, band, t0, tiles} of group g, a closing unit
+  int walk_stride;           // entries per row
   const float *prev;         // nullptr, or a [B, 48, T, F] view (y's strides) ADDED in front of the activation: the partial sum of another 48-channel slice of the input
   long long *dbg;            // ABL & 32 (timeline build): [64 steps][8] s_memtime stamps of workgroup 0, then [4 workgroups][2048] step starts
   // fused-input form (FIN): x is unused; the 48 input channels are relu(b1 + w1 xin), the net's 1x1 input conv, formed by the producers
@@ -80,7 +83,8 @@ struct Conv3hCfg {
   static constexpr int W_OFF = 0, X_OFF = WBYTES, TAB_OFF = X_OFF + 2 * PART;
   static constexpr int LDS_BYTES = TAB_OFF + 64;                  // maxima [2][4] floats, exponents [3] ints, 16 bytes of zeros at + 48
   static constexpr size_t IMG_U32 = WBYTES / 4 + 48;              // image size in 32-bit words
-  static constexpr int EUP = 8;                                   // the running exponent of a walk follows a quieter block only when it is more than this many bits quieter
+  static constexpr int EUP = 8;                                   // a block's largest element is never this many bits under the fp16 range ...
+  static constexpr int EQ = 8;                                    // ... its exponent is the block's need rounded down to a multiple of this (a power of two, <= EUP)
 
   // Partial-sum scratch (template parameter PS of the kernel): the sum a launch hands to the next launch of the same output slice, in the order
   // the consumer waves hold it.  Wave r of tile (b, strip, jt) owns six stores of 1 KB -- store k = accumulator (channel tile k / 2, pixel tile
@@ -230,36 +234,42 @@ inline void conv3h_pack(const float *w, std::vector<uint32_t> &img) {
     }
 }
 
-// Block walk.  XCD x (block id & 7: where the dispatcher puts the workgroup, for speed only) takes the (b, band of bw strips) items x, x + 8, ...;
-// its 32 workgroups (block id >> 3) are bw adjacent strips x 32 / bw segments of T and walk their segment down T together, so the halo
-// columns a strip shares with its neighbours are re-read from that XCD's L2 (bw = 32: one segment, planes at least 1024 wide; 16 / 8 for the
-// narrower planes of the deeper levels, where 32 strips would leave workgroups without work).  A segment is tps + 1 blocks of four input rows:
-// block j = rows r0 + 4 j + 1 .. r0 + 4 j + 4, j = -1 .. tps - 1 (r0 = the segment's first row); output tile j (rows r0 + 4 j .. + 3) needs rows
-// r0 + 4 j - 1 .. r0 + 4 j + 4 = the last two rows of block j - 1 and block j.  Strips past tilesF are all-padding (never stored): they keep the
-// walk in step.  The grid is 256 workgroups.
+// Block walk.  XCD x (block id & 7: where the dispatcher puts the workgroup, for speed only) holds 32 workgroups (block id >> 3): 32 / bw GROUPS
+// of bw adjacent strips.  A group walks the UNITS of its row of the walk table (conv3h_walk_plan.h plans them on the host; the reads are
+// wave-uniform) one after the other: unit {b, band, t0, tiles} = tile rows t0 .. t0 + tiles - 1 of strips band * bw .. of batch item b, the bw
+// workgroups down T together, so the halo columns a strip shares with its neighbours are re-read from that XCD's L2.  A unit is tiles + 1
+// blocks of four input rows: block j = rows 4 (t0 + j) + 1 .. + 4, j = -1 .. tiles - 1; output tile j (rows 4 (t0 + j) .. + 3) needs rows
+// 4 (t0 + j) - 1 .. 4 (t0 + j) + 4 = the last two rows of block j - 1 and block j.  Where a unit begins changes no result: a block's exponent
+// is a function of the block alone (split_store).  Strips past tilesF are all-padding (never stored): they keep the walk in step.  The grid
+// is 256 workgroups; the row's closing unit (2^30 tiles) is never left, whatever the producers' look-ahead.
 struct Conv3hWalk {
-  int item, j, b, strip;
+  int u, j, b, strip, t0, tiles;   // u: entry of the current unit in the table
 };
-__device__ __forceinline__ void conv3h_walk_item(const Conv3hArgs &a, int wg, Conv3hWalk &w) {
-  const int nbands = (a.tilesF + a.bw - 1) / a.bw;
-  w.b = w.item / nbands;
-  w.strip = (w.item - w.b * nbands) * a.bw + (wg >> 3) % a.bw;
+__device__ __forceinline__ void conv3h_walk_unit(const Conv3hArgs &a, int wg, Conv3hWalk &w) {
+  // (behind the kernel's first store the compiler reads the table through the vector cache: the unit goes back to scalar registers, where the
+  // resources and offsets built from it want it)
+  const u32x4 un = a.walk[w.u];
+  w.b = __builtin_amdgcn_readfirstlane((int)un.x);
+  w.strip = __builtin_amdgcn_readfirstlane((int)un.y) * a.bw + ((wg >> 3) & (a.bw - 1));
+  w.t0 = __builtin_amdgcn_readfirstlane((int)un.z);
+  w.tiles = __builtin_amdgcn_readfirstlane((int)un.w);
 }
-__device__ __forceinline__ int conv3h_row0(const Conv3hArgs &a, int wg) { return ((wg >> 3) / a.bw) * a.tps * 4; }   // first row of the workgroup's segment
-__device__ __forceinline__ int conv3h_nblocks(const Conv3hArgs &a, int wg) {
-  const int items = a.B * ((a.tilesF + a.bw - 1) / a.bw), x = wg & 7;
-  return x < items ? ((items - x + 7) >> 3) * (a.tps + 1) : 0;
+__device__ __forceinline__ int conv3h_walk_row(const Conv3hArgs &a, int wg) {   // first entry of the group's row (bw is a power of two)
+  const int sh = __builtin_ctz((unsigned)a.bw);
+  return ((wg & 7) * (32 >> sh) + ((wg >> 3) >> sh)) * a.walk_stride;
 }
+__device__ __forceinline__ int conv3h_row0(const Conv3hWalk &w) { return w.t0 * 4; }   // first row of the unit
+__device__ __forceinline__ int conv3h_nblocks(const Conv3hArgs &a, int wg) { return (int)a.walk[conv3h_walk_row(a, wg)].x; }
 __device__ __forceinline__ void conv3h_walk_init(const Conv3hArgs &a, int wg, Conv3hWalk &w) {
-  w.item = wg & 7;
+  w.u = conv3h_walk_row(a, wg) + 1;
   w.j = -1;
-  conv3h_walk_item(a, wg, w);
+  conv3h_walk_unit(a, wg, w);
 }
 __device__ __forceinline__ void conv3h_walk_next(const Conv3hArgs &a, int wg, Conv3hWalk &w) {
-  if (++w.j == a.tps) {
+  if (++w.j == w.tiles) {
     w.j = -1;
-    w.item += 8;
-    conv3h_walk_item(a, wg, w);
+    ++w.u;
+    conv3h_walk_unit(a, wg, w);
   }
 }
 
@@ -306,7 +316,7 @@ struct Conv3hFinRegs<true> {
 // same addresses behind stage 7, each value added where the planar `prev` is added (behind the fma, in front of the activation).
 // INVARIANT: a launch with both bits reads and writes the SAME scratch in place, and a launch reads what the one before it wrote.  That is
 // safe because a lane only ever touches its own 16 bytes per (tile, store) -- loaded behind stage 7 of the tile, overwritten a step later --
-// and because the launches of one output slice walk identically: same B, T, F, tilesT, tilesF, bw, tps (the launcher builds them from one place).
+// and because the launches of one output slice walk identically: same B, T, F, tilesT, tilesF, bw and walk table (the launcher builds them from one place).
 template <int ABL = 0, bool ACC = false, bool FIN = false, int PS = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3h_kernel(Conv3hArgs a) {
   using CFG = Conv3hCfg;
@@ -328,8 +338,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i = tid; i < CFG::WBYTES / 16; i += 512) dst[i] = src[i];
   }
   const int64_t TF = (int64_t)a.T * a.F;
-  const int NB = conv3h_nblocks(a, wg);
-  const int row0 = conv3h_row0(a, wg);
+  const int NB = __builtin_amdgcn_readfirstlane(conv3h_nblocks(a, wg));
   const unsigned plane_bytes = (unsigned)(CFG::C * TF * 4);
 
   if (wave >= 4) {
@@ -381,7 +390,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     auto fetch = [&](auto setc) {                      // the next block of the walk (nothing past the last one: every offset out of range)
       constexpr int S = decltype(setc)::value;
       const int tb = nf < NB ? wk.b : 0, f0 = wk.strip * 32;
-      const int t1 = nf < NB ? row0 + wk.j * 4 + 1 : -(1 << 20);
+      const int t1 = nf < NB ? conv3h_row0(wk) + wk.j * 4 + 1 : -(1 << 20);
       ++nf;
       conv3h_walk_next(a, wg, wk);
       __amdgpu_buffer_rsrc_t rs = FIN ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.xin + (int64_t)tb * a.xin_bstride), 0, in_bytes, 0x00020000)
@@ -432,22 +441,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       if (lane == 0) maxtab[slot * 4 + pw] = m;
     };
-    int e_prev = 0, js = -1;                           // exponent of the block split last, position of the next block to split inside its item
+    int e_prev = 0;                                    // exponent of the block split last
     auto split_store = [&](auto setc, int par, int slot3) {   // set S -> ring rows of block slot `slot3` under the block's exponent
       constexpr int S = decltype(setc)::value % NSET;
       const f32x4 mv = *reinterpret_cast<const f32x4 *>(maxtab + par * 4);
       const float m = fmaxf(fmaxf(mv.x, mv.y), fmaxf(mv.z, mv.w));
-      // Running exponent of the walk down T: it follows a block's need (largest |x| 2^need in [2^14, 2^15)) only when the block would
-      // overflow (need < e: one more bit of headroom is taken, so the next few louder blocks pass) or is more than EUP bits quieter --
-      // an element keeps its 22 significand bits down to 2^-12 of a block maximum that sits EUP = 8 bits under the range, and an
-      // absolute error of 2^-34 of that maximum below: the consumers rescale accumulators only where the exponent moves (rarely).
+      // Block exponent: the block's need (largest |x| 2^need in [2^13, 2^14)) rounded DOWN to a multiple of EQ = 8 -- a function of the block
+      // alone, so the bits of a tile do not depend on where the walk that reaches it began (which unit, which batch size).  The block's
+      // largest element sits at most EQ - 1 = 7 bits under the range: an element keeps its 22 significand bits down to 2^-12 of such a block
+      // maximum, and an absolute error of 2^-34 of that maximum below.  Neighbouring blocks share an exponent unless their maxima lie on
+      // either side of a multiple of 2^8: the consumers rescale accumulators only there (rarely).  A block without a finite nonzero element
+      // keeps the exponent of the block split before it: whatever that is, every product with the block is 0 (or not finite) and the rescale
+      // around it exact, so it changes no bit -- and a block of zeros behind a loud one asks no rise of 2^(100 - e) from the accumulators.
+      // Between two blocks with nonzero elements the rise is their needs' difference (at most 2^(100 - need), the clamp below): the
+      // accumulators (under 2^39) stay finite unless the two maxima are more than 2^80 apart.
       int need = f16_scale_exp(m) - 1;
       need = need < 100 ? need : 100;                  // 2^e and the epilogue's 2^-(e + weight exponent) stay normal floats
-      int e = e_prev;
-      if (js < 0 || need < e_prev) e = need;
-      else if (need > e_prev + CFG::EUP) e = need < e_prev + 40 ? need : e_prev + 40;   // (a rise multiplies accumulators by 2^rise: bounded)
+      const int e = m > 0.f ? need & ~(CFG::EQ - 1) : e_prev;
       e_prev = e;
-      if (++js == a.tps) js = -1;
       if (ptid == 0) exps[slot3] = e;
       const float sc = __builtin_ldexpf(1.0f, e);
       char *dst = lds + CFG::X_OFF + slot3 * 4 * CFG::ROWB + loff;
@@ -648,7 +659,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     conv3h_walk_init(a, wg, wk);
     int s3 = 0;                                        // s % 3
     for (int s = 0; s < NB; ++s) {
-      const int tb = wk.b, j = wk.j, wk_strip = wk.strip, f0 = wk_strip * 32;
+      const int tb = wk.b, j = wk.j, wk_strip = wk.strip, wk_t0 = wk.t0, f0 = wk_strip * 32;
       conv3h_walk_next(a, wg, wk);
       if constexpr ((ABL & 32) != 0) {
         if (wg == 0 && wave == 0 && s < 64) {
@@ -658,11 +669,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       if (j >= 0) {
         // F % 32 == 0 (launcher): a strip is inside the image or outside as a whole; rows past T and padding strips get num_records 0
-        const int tt = row0 + j * 4 + wave;
+        const int tt = (wk_t0 + j) * 4 + wave;
         const bool cur_ok = tt < a.T && f0 < a.F;
         const int cur_vo = (((li & 7) * a.T + tt) * a.F + f0 + ((li >> 3) * 4 + g) * 4) * 4;
         // the wave's 6 KB of the scratch: wave-uniform (a scalar offset of the loads and stores), the lane adds lane * 16 (cur_ok: strip < tilesF, tile row < tilesT)
-        const int cur_ps = (int)CFG::ps_wave_off(a.tilesT, wk_strip, (row0 >> 2) + j, wave);
+        const int cur_ps = (int)CFG::ps_wave_off(a.tilesT, wk_strip, wk_t0 + j, wave);
         // rows of the tile: u = 0, 1 = the last two rows of the previous block, u = 2..5 = this block; wave r, kernel row ky reads u = r + ky
         const int sp = s3 == 0 ? 2 : s3 - 1;
         const int e_cur = __builtin_amdgcn_readfirstlane(exps[s3]), e_old = __builtin_amdgcn_readfirstlane(exps[sp]);
@@ -758,7 +769,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           }
           if constexpr ((ABL & 256) == 0 && CFG::PLAN[PROG][S].rto >= 0) {
             // the stages that follow read rows of the other block -- bring the accumulators to that block's scale (exact;
-            // rises are bounded by EUP, a fall flushes what is negligible against what follows)
+            // a rise is the difference of two blocks' needs (split_store), a fall flushes what is negligible against what follows)
             const int d = eky[CFG::PLAN[PROG][S].rto] - eky[CFG::PLAN[PROG][S].rfrom];
             if (d != 0) {
 #pragma unroll

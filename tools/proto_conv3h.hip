@@ -98,7 +98,19 @@ static double ref_at(const std::vector<float> &x, const std::vector<float> &w, c
   return s;
 }
 
-static int g_bw = 32;      // strips per band (argv[7]: 32, 16, 8)
+static int g_bw = 32;      // strips per band of the arithmetic walk (argv[7]: 32, 16, 8), or 0: the balanced walk (conv3h_walk_plan.h)
+
+// plans the walk of a launch (g_bw), uploads its table (kept until the process ends) and fills the walk arguments
+static void set_walk(Conv3hArgs &a) {
+  const Conv3hWalkPlan plan = g_bw > 0 ? conv3h_walk_arith(a.B, a.tilesT, a.tilesF, g_bw) : conv3h_walk_plan(a.B, a.tilesT, a.tilesF, 1, 1);
+  std::vector<int32_t> tab;
+  a.walk_stride = conv3h_walk_table(plan, tab);
+  a.bw = plan.bw;
+  void *d = nullptr;
+  CK(hipMalloc(&d, tab.size() * 4));
+  CK(hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  a.walk = reinterpret_cast<const u32x4 *>(d);
+}
 static int g_ps = 1;       // 96 -> 96 layer: partial sums through the fragment-order scratch (argv[8]; 0: through the output, planar)
 static int g_alias = 0;   // 1: every batch item reads item 0's planes, 2: and writes item 0's output (cache-resident traffic: is the launch DRAM- or CU-bound?)
 static int run_shape(const Shape &sh, int abl, int order, int reps) {
@@ -150,12 +162,7 @@ static int run_shape(const Shape &sh, int abl, int order, int reps) {
   a.act = sh.act;
   a.tilesT = (sh.T + 3) / 4;
   a.tilesF = (sh.F + 31) / 32;
-  a.bw = g_bw;
-  a.tps = a.tilesT * g_bw / 32;
-  if ((a.tilesT * g_bw) % 32 != 0) {
-    a.bw = 32;
-    a.tps = a.tilesT;
-  }
+  set_walk(a);
   long long *ddbg = nullptr;
   CK(hipMalloc(&ddbg, (512 + 4 * 2048) * 8));
   CK(hipMemset(ddbg, 0, (512 + 4 * 2048) * 8));
@@ -290,6 +297,11 @@ static int run_shape96(const Shape &sh, int reps) {
   void *dps = nullptr;
   const int64_t ps_item = Conv3hCfg::ps_item_bytes((sh.T + 3) / 4, sh.F / 32);
   CK(hipMalloc(&dps, (size_t)Conv3hCfg::ps_bytes(sh.B, (sh.T + 3) / 4, sh.F / 32)));
+  Conv3hArgs wk{};                                     // the walk all four launches share
+  wk.B = sh.B;
+  wk.tilesT = (sh.T + 3) / 4;
+  wk.tilesF = sh.F / 32;
+  set_walk(wk);
   auto go = [&]() {
     for (int ob = 0; ob < 2; ++ob)
       for (int ib = 0; ib < 2; ++ib) {
@@ -308,12 +320,9 @@ static int run_shape96(const Shape &sh, int reps) {
         a.act = ib ? sh.act : ACT_NONE;
         a.tilesT = (sh.T + 3) / 4;
         a.tilesF = sh.F / 32;
-        a.bw = g_bw;
-        a.tps = a.tilesT * g_bw / 32;
-        if ((a.tilesT * g_bw) % 32 != 0) {
-          a.bw = 32;
-          a.tps = a.tilesT;
-        }
+        a.bw = wk.bw;
+        a.walk = wk.walk;
+        a.walk_stride = wk.walk_stride;
         a.dbg = ddbg;
         if (g_ps) launch_ps(ib ? 1 : 2, a, 0);
         else launch<0>(a, 0);
