@@ -603,6 +603,39 @@ int asx_flac_encode_dev(asx_engine *e, const int16_t *pcm16_dev, int64_t n_sampl
 int asx_flac_encode(asx_engine *e, const int16_t *pcm16_host, int64_t n_samples, int32_t sample_rate, int32_t bits_per_sample, int32_t block_size,
                     uint8_t *out_host, int64_t out_capacity, int32_t *frame_bytes_host, int64_t *total_bytes);
 
+/* The same encoder for samples of 16 or 24 REAL bits (CommonSeparator.write_audio_soundfile with a .flac path, where the reference's
+ * sf.write keeps a PCM_24 input's width): interleaved int32 [n, 2], every value inside bits_per_sample bits (the host form checks, the device
+ * form trusts its caller).  No wasted bits; the side channel is L - R at bits_per_sample + 1, the mid channel (L + R) >> 1.  Against the int16
+ * form: exact Rice bits for the parameters 0 .. 23 at partition orders 0 .. 5; a subframe takes Rice method 1 (5-bit parameters) only where
+ * that is smaller than method 0 restricted to 0 .. 14; a predictor with a residual outside 32 bits is no candidate.  The worst case of a
+ * frame, hence stride and max_bytes, is header + 2 x (16 + (bits_per_sample + 1) x block_size) bits + padding + CRC-16.  Arguments, refusals
+ * and outputs as for asx_flac_plan / asx_flac_encode_dev / asx_flac_encode.  Additive within ABI 7. */
+int asx_flac_plan_pcm(int64_t n_samples, int32_t channels, int32_t bits_per_sample, int32_t block_size, int64_t *n_blocks, int32_t *frame_stride,
+                      int64_t *max_bytes, int64_t *scratch_bytes);
+int asx_flac_encode_pcm_dev(asx_engine *e, const int32_t *pcm_dev, int64_t n_samples, int32_t sample_rate, int32_t bits_per_sample,
+                            int32_t block_size, uint8_t *out_dev, int64_t out_capacity, int32_t *frame_bytes_dev, int64_t *total_bytes,
+                            void *stream);
+int asx_flac_encode_pcm(asx_engine *e, const int32_t *pcm_host, int64_t n_samples, int32_t sample_rate, int32_t bits_per_sample, int32_t block_size,
+                        uint8_t *out_host, int64_t out_capacity, int32_t *frame_bytes_host, int64_t *total_bytes);
+
+/* Writer edge of CommonSeparator.write_audio_soundfile (common_separator.py:399-461) for a stem in HBM: spec_utils.normalize exactly as
+ * asx_normalize_dev computes it, then the samples in the file's own format, interleaved [n, 2] -- the body of a WAVE data chunk.
+ *   stem_dev       float32, planar [2, n] (ASX_STEM_PLANAR) or rows [n, 2] (ASX_STEM_ROWS); only read
+ *   sample_format  16, 24 (3-byte packed), 32: little-endian integer PCM = clip(rint((double)x * (2^(b-1) - 1)), -2^(b-1), 2^(b-1) - 1), ties
+ *                  to even (audio_io.write_wav's rule and libsndfile's scale factor; not asx_pcm16's truncating x * 32767);
+ *                  0x120: float32, the normalised value; ASX_PCM_S16_IN_32 / ASX_PCM_S24_IN_32: the 16- / 24-bit integers in int32
+ *                  containers, the input of asx_flac_encode_pcm_dev
+ *   out_dev        n x 4, 6 or 8 bytes, 16-byte aligned
+ *   *peak_after    (optional; synchronises) max |stem| after normalisation, float32: the writer skips the file below 1e-6
+ * Non-finite samples are outside the contract.  Every argument is checked before anything is enqueued (ASX_ERR_INVALID + asx_last_error():
+ * null pointers, n_samples < 1, unknown layout, unknown format).  asx_pcm_encode: the same for host arrays.  Additive within ABI 7. */
+#define ASX_PCM_S16_IN_32 0x410
+#define ASX_PCM_S24_IN_32 0x418
+int asx_pcm_encode_dev(asx_engine *e, const float *stem_dev, int64_t n_samples, int32_t layout, float max_peak, float min_peak, int32_t has_min,
+                       int32_t sample_format, void *out_dev, float *peak_after, void *stream);
+int asx_pcm_encode(asx_engine *e, const float *stem_host, int64_t n_samples, int32_t layout, float max_peak, float min_peak, int32_t has_min,
+                   int32_t sample_format, void *out_host, float *peak_after);
+
 /* FLAC decoder for the input edge (RFC 9639): the audio part of a native FLAC stream -- everything behind the last metadata block, already in
  * HBM -- -> the planar float32 mix [2, n] = x / 2^(bits_per_sample - 1), which is what librosa.load / libsndfile give for the file at its own
  * rate (a mono stream feeds both rows).  The arguments are STREAMINFO's fields.  Taken: 1 or 2 channels, 8 .. 24 bits per sample, fixed or

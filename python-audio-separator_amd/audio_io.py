@@ -128,12 +128,34 @@ def write_wav(path: str, data: np.ndarray, samplerate: int, subtype: str = "PCM_
             u = (v & 0xFFFFFF).astype(np.uint32).reshape(-1)
             body = np.stack([u & 0xFF, (u >> 8) & 0xFF, (u >> 16) & 0xFF], axis=1).astype(np.uint8).tobytes()
         tag = _FMT_PCM
+    _write_riff(path, tag, ch, samplerate, bits, body)
+
+
+def _write_riff(path, tag, ch, samplerate, bits, body):
     align = ch * bits // 8
     with open(path, "wb") as f:
         f.write(b"RIFF" + struct.pack("<I", 36 + len(body)) + b"WAVE")
         f.write(b"fmt " + struct.pack("<IHHIIHH", 16, tag, ch, samplerate, samplerate * align, align, bits))
         f.write(b"data" + struct.pack("<I", len(body)))
         f.write(body)
+
+
+_WAV_BODY_FORMATS = {"PCM_16": (_FMT_PCM, 16), "PCM_24": (_FMT_PCM, 24), "PCM_32": (_FMT_PCM, 32), "FLOAT": (_FMT_FLOAT, 32)}
+
+
+def write_wav_body(path: str, body, samplerate: int, subtype: str, frames: int, channels: int = 2):
+    """The file ``write_wav`` writes, around samples that are already in the file's format (Engine.pcm_encode*): ``body`` (bytes-like) is
+    the data chunk of ``frames`` interleaved frames, little-endian, at ``subtype`` PCM_16 / PCM_24 (3-byte packed) / PCM_32 / FLOAT."""
+    if subtype not in _WAV_BODY_FORMATS:
+        raise AudioIOError(f"unsupported WAV subtype {subtype}")
+    tag, bits = _WAV_BODY_FORMATS[subtype]
+    body = body if isinstance(body, (bytes, bytearray)) else memoryview(body).cast("B")
+    align = channels * bits // 8
+    if len(body) != frames * align:
+        raise AudioIOError(f"write_wav_body: {frames} frames of {align} bytes are {frames * align} bytes, the body holds {len(body)}")
+    if 36 + len(body) >= 1 << 32:
+        raise AudioIOError("write_wav_body: the body does not fit a RIFF file's 32-bit sizes")
+    _write_riff(path, tag, channels, samplerate, bits, body)
 
 
 def write_flac(path: str, frames, frame_sizes, samplerate: int, bits_per_sample: int, total_samples: int, md5=None,

@@ -79,7 +79,9 @@ class CommonSeparator:
         self.asx_output_encoder = self._output_encoder_mode(config)    # who compresses a .flac stem when pydub is installed
         self.file_timings = {}
         self._pending_writes = []                # (thread, error box) of container writes in flight
-        self.last_write_path = None              # "flac_device_resident" | "flac_device_upload": how the last .flac stem reached the encoder
+        # how the last stem reached its encoder: "flac_device_resident" | "flac_device_upload" (.flac), "wav_device_resident" (a .wav of
+        # write_audio_soundfile whose samples were converted to the file's format in HBM)
+        self.last_write_path = None
 
         self.roformer_loader = None
         self.is_roformer_model = self._detect_roformer_model()
@@ -136,6 +138,10 @@ class CommonSeparator:
     # the reference does; "device": the engine's encoder (asx_flac_encode_dev) and audio_io.write_flac.  Without pydub the built-in encoder
     # writes FLAC under either setting, as the built-in writer does for WAV.  The environment variable ASX_OUTPUT_ENCODER, when set and not
     # empty, overrides the configuration of every plugin of the process.  Other compressed formats always need pydub.
+    # With ``use_soundfile`` the same knob decides for soundfile: "host" leaves every stem to sf.write where soundfile is installed; "device"
+    # converts a stem that is still in HBM there (asx_pcm_encode_dev / asx_flac_encode_pcm_dev) -- opt-in because libsndfile multiplies in
+    # float32 where this project (audio_io.write_wav's rule) multiplies in float64, so single samples can differ by one unit.  Without
+    # soundfile the device path is taken under either setting.
     OUTPUT_ENCODER_MODES = ("host", "device")
 
     @classmethod
@@ -837,12 +843,93 @@ class CommonSeparator:
         self._write_wav_async(stem_path, pcm, {16: "PCM_16", 24: "PCM_24", 32: "PCM_32"}.get(depth, "PCM_16"))
         self._tick("container_write", t0)
 
+    def _output_subtype(self) -> str:
+        """the sample format write_audio_soundfile keeps: the input's (common_separator.py:425-437)"""
+        if self.input_subtype:
+            return self.input_subtype
+        if self.input_bit_depth:
+            return {16: "PCM_16", 24: "PCM_24", 32: "PCM_32"}.get(self.input_bit_depth, "PCM_16")
+        return "PCM_16"
+
+    _DEVICE_WAV_SUBTYPES = {"PCM_16": 4, "PCM_24": 6, "PCM_32": 8, "FLOAT": 8}     # bytes per stereo frame
+    _DEVICE_FLAC_SUBTYPES = {"PCM_16": (16, "S16_IN_32"), "PCM_24": (24, "S24_IN_32")}
+
+    def _write_soundfile_device(self, stem_path: str, stem_source, entry) -> bool:
+        """write_audio_soundfile for a stem that is still in HBM (``entry`` of ``_dev_stems``): normalise and convert to the file's own
+        sample format there (asx_pcm_encode_dev), bring back the file's bytes -- or, for a ``.flac`` name, its compressed frames
+        (asx_flac_encode_pcm_dev: a PCM_24 input keeps 24 real bits) -- and write the container on the writer threads.  False: not a case
+        of this path (another container, a subtype without a device encoder, soundfile installed and not overruled); the caller goes on."""
+        sf = audio_io._optional("soundfile")
+        if sf is not None and hasattr(sf, "write") and getattr(self, "asx_output_encoder", "host") != "device":
+            return False
+        eng = self.engine
+        file_format = stem_path.lower().split(".")[-1]
+        subtype = self._output_subtype()
+        if file_format not in ("wav", "flac") or subtype not in self._DEVICE_WAV_SUBTYPES:
+            return False
+        if file_format == "flac" and subtype not in self._DEVICE_FLAC_SUBTYPES:
+            # what sf.write does under the reference: libsndfile's FLAC takes neither 32-bit nor float samples
+            self.logger.error(f"{stem_path}: the container write failed: FLAC holds no {subtype} samples")
+            self._dev_stems.pop(id(stem_source), None)
+            return True
+        import torch
+        dev_stem = entry[1]
+        layout = "planar" if entry[3] == "planar" else "rows"
+        n = dev_stem.shape[1] if layout == "planar" else dev_stem.shape[0]
+        t0 = self._now()
+        if file_format == "wav":
+            fmt, dev_body = subtype, torch.empty(n * self._DEVICE_WAV_SUBTYPES[subtype], dtype=torch.uint8, device=dev_stem.device)
+        else:
+            bits, fmt = self._DEVICE_FLAC_SUBTYPES[subtype]
+            dev_body = torch.empty((n, 2), dtype=torch.int32, device=dev_stem.device)
+        peak = eng.pcm_encode_dev(dev_stem.data_ptr(), n, layout, self.normalization_threshold, self.amplification_threshold, fmt,
+                                  dev_body.data_ptr(), stream=self._stream())
+        # written (or silent): the device stem and its pinned mirror are released with this entry, as in write_audio_pydub
+        self._dev_stems.pop(id(stem_source), None)
+        if peak < 1e-6:
+            self.logger.warning(f"{stem_path}: nothing to write (the stem is empty or silent)")
+            return True
+        if self.output_dir:
+            os.makedirs(self.output_dir, exist_ok=True)
+            stem_path = os.path.join(self.output_dir, stem_path)
+        rate = self.sample_rate
+        if file_format == "wav":
+            body = torch.empty(dev_body.shape, dtype=torch.uint8, pin_memory=True)
+            body.copy_(dev_body, non_blocking=True)
+            self._sync()
+            self.file_timings["pcm_encode_d2h"] = self.file_timings.get("pcm_encode_d2h", 0.0) + (self._now() - t0)
+            self.last_write_path = "wav_device_resident"
+            self._write_async(lambda: audio_io.write_wav_body(stem_path, body.numpy(), rate, subtype, n))
+            return True
+        self.file_timings["pcm_encode_d2h"] = self.file_timings.get("pcm_encode_d2h", 0.0) + (self._now() - t0)
+        t0 = self._now()
+        block = getattr(eng, "FLAC_BLOCK_SIZE", 4096)
+        plan = eng.flac_plan_pcm(n, 2, bits, block)
+        out = torch.empty(plan["max_bytes"], dtype=torch.uint8, device=dev_stem.device)
+        sizes = torch.empty(plan["n_blocks"], dtype=torch.int32, device=dev_stem.device)
+        total = eng.flac_encode_pcm_dev(dev_body.data_ptr(), n, rate, bits, block, out.data_ptr(), plan["max_bytes"], sizes.data_ptr(),
+                                        stream=self._stream())
+        frames = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        frame_sizes = torch.empty(plan["n_blocks"], dtype=torch.int32, pin_memory=True)
+        frames.copy_(out[:total], non_blocking=True)
+        frame_sizes.copy_(sizes, non_blocking=True)
+        self._sync()
+        self.file_timings["flac_encode"] = self.file_timings.get("flac_encode", 0.0) + (self._now() - t0)
+        self.last_write_path = "flac_device_resident"
+        # the MD5 of STREAMINFO stays unset ("not computed"): the samples never reached the host
+        self._write_async(lambda: audio_io.write_flac(stem_path, frames.numpy(), frame_sizes.numpy(), rate, bits, n, None, block_size=block))
+        return True
+
     def write_audio_soundfile(self, stem_path: str, stem_source):
-        """common_separator.py:399-461: normalise (device), keep the input's subtype, hand floats to the container."""
+        """common_separator.py:399-461: normalise (device), keep the input's subtype, hand floats to the container.  A stem that is still
+        in HBM is converted to the file's format there (``_write_soundfile_device``)."""
         eng = self._require_engine()
         a = self._stereo_rows(stem_source)
         if a.shape[0] == 0:
             self.logger.warning(f"{stem_path}: nothing to write (the stem is empty or silent)")
+            return
+        entry = self._device_stem_entry(stem_source)
+        if entry is not None and self._write_soundfile_device(stem_path, stem_source, entry):
             return
         buf = eng.normalize(np.ascontiguousarray(a, np.float32), self.normalization_threshold, self.amplification_threshold)
         if np.max(np.abs(buf)) < 1e-6:

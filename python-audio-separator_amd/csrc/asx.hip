@@ -61,6 +61,7 @@ static void grant_lds(K *kernel, int bytes) { grant_lds(reinterpret_cast<const v
 #include "kernels_ens.h"
 #include "kernels_resample.h"
 #include "kernels_flac.h"
+#include "kernels_pcm_encode.h"
 #include "kernels_flac_dec.h"
 
 using namespace asx;
@@ -1110,8 +1111,8 @@ int asx_flac_encode_dev(asx_engine *e, const int16_t *pcm16_dev, int64_t n_sampl
           (long long)p.max_bytes);
   REQUIRE((((uintptr_t)pcm16_dev) & 3) == 0 && (((uintptr_t)frame_bytes_dev) & 3) == 0, "asx_flac_encode_dev: pcm16 and frame_bytes must be 4-byte aligned");
   HIPCHK(hipSetDevice(e->device));
-  return flac_encode_launch(e, pcm16_dev, n_samples, sample_rate, bits_per_sample, block_size, p, out_dev, frame_bytes_dev, total_bytes,
-                            reinterpret_cast<hipStream_t>(stream));
+  return flac_encode_launch<false>(e, pcm16_dev, n_samples, sample_rate, bits_per_sample, block_size, p, out_dev, frame_bytes_dev, total_bytes,
+                                   reinterpret_cast<hipStream_t>(stream));
 }
 
 int asx_flac_encode(asx_engine *e, const int16_t *pcm16_host, int64_t n_samples, int32_t sample_rate, int32_t bits_per_sample, int32_t block_size,
@@ -1131,6 +1132,62 @@ int asx_flac_encode(asx_engine *e, const int16_t *pcm16_host, int64_t n_samples,
   HIPCHK(hipMemcpy(din.p, pcm16_host, (size_t)n_samples * 4, hipMemcpyHostToDevice));
   CHK(asx_flac_encode_dev(e, reinterpret_cast<const int16_t *>(din.p), n_samples, sample_rate, bits_per_sample, block_size,
                           reinterpret_cast<uint8_t *>(dout.p), p.max_bytes, reinterpret_cast<int32_t *>(dsz.p), total_bytes, nullptr));
+  HIPCHK(hipMemcpy(out_host, dout.p, (size_t)*total_bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(frame_bytes_host, dsz.p, (size_t)p.n_blocks * 4, hipMemcpyDeviceToHost));
+  return ASX_OK;
+}
+
+// The same encoder for int32 [n, 2] samples of 16 or 24 real bits (flac_encode_kernel<true>): no wasted bits, the side channel at bps + 1
+int asx_flac_plan_pcm(int64_t n_samples, int32_t channels, int32_t bits_per_sample, int32_t block_size, int64_t *n_blocks, int32_t *frame_stride,
+                      int64_t *max_bytes, int64_t *scratch_bytes) {
+  FlacPlan p;
+  const std::string why = flac_plan_make(n_samples, channels, bits_per_sample, block_size, p, true);
+  REQUIRE(why.empty(), "asx_flac_plan_pcm: %s", why.c_str());
+  if (n_blocks) *n_blocks = p.n_blocks;
+  if (frame_stride) *frame_stride = p.stride;
+  if (max_bytes) *max_bytes = p.max_bytes;
+  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+  return ASX_OK;
+}
+
+int asx_flac_encode_pcm_dev(asx_engine *e, const int32_t *pcm_dev, int64_t n_samples, int32_t sample_rate, int32_t bits_per_sample,
+                            int32_t block_size, uint8_t *out_dev, int64_t out_capacity, int32_t *frame_bytes_dev, int64_t *total_bytes,
+                            void *stream) {
+  FlacPlan p;
+  const std::string why = flac_plan_make(n_samples, 2, bits_per_sample, block_size, p, true);
+  REQUIRE(why.empty(), "asx_flac_encode_pcm_dev: %s", why.c_str());
+  REQUIRE(sample_rate >= 1 && sample_rate <= 1048575, "asx_flac_encode_pcm_dev: sample rate %d Hz (1 .. 1048575)", sample_rate);
+  REQUIRE(e && pcm_dev && out_dev && frame_bytes_dev && total_bytes, "asx_flac_encode_pcm_dev: null argument");
+  REQUIRE(out_capacity >= p.max_bytes, "asx_flac_encode_pcm_dev: out_capacity %lld below the plan's worst case of %lld bytes",
+          (long long)out_capacity, (long long)p.max_bytes);
+  REQUIRE((((uintptr_t)pcm_dev) & 3) == 0 && (((uintptr_t)frame_bytes_dev) & 3) == 0, "asx_flac_encode_pcm_dev: pcm and frame_bytes must be 4-byte aligned");
+  HIPCHK(hipSetDevice(e->device));
+  return flac_encode_launch<true>(e, pcm_dev, n_samples, sample_rate, bits_per_sample, block_size, p, out_dev, frame_bytes_dev, total_bytes,
+                                  reinterpret_cast<hipStream_t>(stream));
+}
+
+int asx_flac_encode_pcm(asx_engine *e, const int32_t *pcm_host, int64_t n_samples, int32_t sample_rate, int32_t bits_per_sample, int32_t block_size,
+                        uint8_t *out_host, int64_t out_capacity, int32_t *frame_bytes_host, int64_t *total_bytes) {
+  FlacPlan p;
+  const std::string why = flac_plan_make(n_samples, 2, bits_per_sample, block_size, p, true);
+  REQUIRE(why.empty(), "asx_flac_encode_pcm: %s", why.c_str());
+  REQUIRE(sample_rate >= 1 && sample_rate <= 1048575, "asx_flac_encode_pcm: sample rate %d Hz (1 .. 1048575)", sample_rate);
+  REQUIRE(e && pcm_host && out_host && frame_bytes_host && total_bytes, "asx_flac_encode_pcm: null argument");
+  REQUIRE(out_capacity >= p.max_bytes, "asx_flac_encode_pcm: out_capacity %lld below the plan's worst case of %lld bytes", (long long)out_capacity,
+          (long long)p.max_bytes);
+  const int32_t lo = -(1 << (bits_per_sample - 1)), hi = (1 << (bits_per_sample - 1)) - 1;
+  for (int64_t i = 0; i < 2 * n_samples; ++i)
+    REQUIRE(pcm_host[i] >= lo && pcm_host[i] <= hi, "asx_flac_encode_pcm: sample %lld = %d is outside %d bits", (long long)i, pcm_host[i],
+            bits_per_sample);
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf din, dout, dsz;
+  BufGuard g{{&din, &dout, &dsz}};
+  CHK(din.ensure((size_t)n_samples * 8));
+  CHK(dout.ensure((size_t)p.max_bytes));
+  CHK(dsz.ensure((size_t)p.n_blocks * 4));
+  HIPCHK(hipMemcpy(din.p, pcm_host, (size_t)n_samples * 8, hipMemcpyHostToDevice));
+  CHK(asx_flac_encode_pcm_dev(e, reinterpret_cast<const int32_t *>(din.p), n_samples, sample_rate, bits_per_sample, block_size,
+                              reinterpret_cast<uint8_t *>(dout.p), p.max_bytes, reinterpret_cast<int32_t *>(dsz.p), total_bytes, nullptr));
   HIPCHK(hipMemcpy(out_host, dout.p, (size_t)*total_bytes, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(frame_bytes_host, dsz.p, (size_t)p.n_blocks * 4, hipMemcpyDeviceToHost));
   return ASX_OK;
@@ -1258,6 +1315,72 @@ int asx_pcm16_rows_dev(asx_engine *e, const float *stem_rows_dev, int64_t N, flo
     else if (has_min && maxv < min_peak) scale = min_peak / maxv;
     *peak_after = maxv * scale;
   }
+  return ASX_OK;
+}
+
+// write_audio_soundfile's array work for a stem in HBM (kernels_pcm_encode.h): normalise, then the samples in the file's own format,
+// interleaved [n, 2]; *peak_after = max |stem| after normalisation.  stem_dev is only read.
+int asx_pcm_encode_dev(asx_engine *e, const float *stem_dev, int64_t n_samples, int32_t layout, float max_peak, float min_peak, int32_t has_min,
+                       int32_t sample_format, void *out_dev, float *peak_after, void *stream) {
+  // every argument is judged before anything is enqueued, the engine last (so that the refusals can be told apart without a device)
+  REQUIRE(stem_dev && out_dev, "asx_pcm_encode_dev: null stem or output");
+  REQUIRE(n_samples >= 1 && n_samples <= ((int64_t)1 << 40), "asx_pcm_encode_dev: n_samples = %lld (1 .. 2^40)", (long long)n_samples);
+  REQUIRE(layout == ASX_STEM_PLANAR || layout == ASX_STEM_ROWS, "asx_pcm_encode_dev: layout %d (0 planar [2, n], 1 rows [n, 2])", (int)layout);
+  REQUIRE(pcmenc_known(sample_format),
+          "asx_pcm_encode_dev: sample format %d (16, 24, 32 = integer PCM bits, 0x120 = IEEE float32, 0x410 / 0x418 = 16 / 24 bits in int32)",
+          (int)sample_format);
+  REQUIRE((((uintptr_t)stem_dev) & 3) == 0 && (((uintptr_t)out_dev) & 15) == 0, "asx_pcm_encode_dev: stem must be 4-byte and the output 16-byte aligned");
+  REQUIRE(e, "asx_pcm_encode_dev: null engine");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  CHK(e->d_peak.ensure(256));
+  unsigned int *pk = reinterpret_cast<unsigned int *>(e->d_peak.p) + 4;   // its own word (0: separate / pcm16, 1: decode, 2: normalize_dev, 3: ensemble slot)
+  HIPCHK(hipMemsetAsync(pk, 0, 4, s));
+  const int64_t n2 = 2 * n_samples;
+  const unsigned nb = (unsigned)std::min<int64_t>((n2 + 255) / 256, 2048);
+  unsigned char *out = reinterpret_cast<unsigned char *>(out_dev);
+  const int rows = layout == ASX_STEM_ROWS;
+  CHK(timed(e, ASX_PROF_MISC, 0.0, 4.0 * n2, s, [&]() { hipLaunchKernelGGL(absmax_kernel, dim3(nb), dim3(256), 0, s, stem_dev, n2, pk); }));
+  CHK(timed(e, ASX_PROF_MISC, 0.0, (8.0 + pcmenc_frame_bytes(sample_format)) * n_samples, s, [&]() {
+    switch (sample_format) {
+      case PCMENC_S16: pcm_encode_launch<PCMENC_S16>(stem_dev, n_samples, rows, pk, max_peak, min_peak, has_min, out, s); break;
+      case PCMENC_S24: pcm_encode_launch<PCMENC_S24>(stem_dev, n_samples, rows, pk, max_peak, min_peak, has_min, out, s); break;
+      case PCMENC_S32: pcm_encode_launch<PCMENC_S32>(stem_dev, n_samples, rows, pk, max_peak, min_peak, has_min, out, s); break;
+      case PCMENC_F32: pcm_encode_launch<PCMENC_F32>(stem_dev, n_samples, rows, pk, max_peak, min_peak, has_min, out, s); break;
+      case PCMENC_S16_IN_32: pcm_encode_launch<PCMENC_S16_IN_32>(stem_dev, n_samples, rows, pk, max_peak, min_peak, has_min, out, s); break;
+      default: pcm_encode_launch<PCMENC_S24_IN_32>(stem_dev, n_samples, rows, pk, max_peak, min_peak, has_min, out, s); break;
+    }
+  }));
+  if (peak_after) {
+    float maxv = 0.f;
+    HIPCHK(hipMemcpyAsync(&maxv, pk, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    float scale = 1.0f;
+    if (maxv > max_peak) scale = max_peak / maxv;
+    else if (has_min && maxv < min_peak) scale = min_peak / maxv;
+    *peak_after = maxv * scale;
+  }
+  return ASX_OK;
+}
+
+int asx_pcm_encode(asx_engine *e, const float *stem_host, int64_t n_samples, int32_t layout, float max_peak, float min_peak, int32_t has_min,
+                   int32_t sample_format, void *out_host, float *peak_after) {
+  REQUIRE(stem_host && out_host, "asx_pcm_encode: null stem or output");
+  REQUIRE(n_samples >= 1 && n_samples <= ((int64_t)1 << 40), "asx_pcm_encode: n_samples = %lld (1 .. 2^40)", (long long)n_samples);
+  REQUIRE(layout == ASX_STEM_PLANAR || layout == ASX_STEM_ROWS, "asx_pcm_encode: layout %d (0 planar [2, n], 1 rows [n, 2])", (int)layout);
+  REQUIRE(pcmenc_known(sample_format),
+          "asx_pcm_encode: sample format %d (16, 24, 32 = integer PCM bits, 0x120 = IEEE float32, 0x410 / 0x418 = 16 / 24 bits in int32)",
+          (int)sample_format);
+  REQUIRE(e, "asx_pcm_encode: null engine");
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf ds, dp;
+  BufGuard g{{&ds, &dp}};
+  const size_t bytes = (size_t)n_samples * (size_t)pcmenc_frame_bytes(sample_format);
+  CHK(to_dev(ds, stem_host, (size_t)2 * n_samples));
+  CHK(dp.ensure(bytes));
+  CHK(asx_pcm_encode_dev(e, ds.f(), n_samples, layout, max_peak, min_peak, has_min, sample_format, dp.p, peak_after, nullptr));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out_host, dp.p, bytes, hipMemcpyDeviceToHost));
   return ASX_OK;
 }
 

@@ -1,6 +1,12 @@
 // FLAC encoder of asx_flac_encode_dev for gfx950: interleaved int16 [n, 2] -> the audio frames of a fixed-blocksize, 2-channel stream
 // (RFC 9639), 16 bits per sample or 24 (the same values shifted left by 8, every subframe flagging its wasted bits).
 //
+// The same text with PCM = true is the encoder of asx_flac_encode_pcm_dev: int32 [n, 2] samples of 16 or 24 real bits, no wasted bits,
+// S = L - R at bps + 1 bits and M = (L + R) >> 1.  What differs there: exact Rice bits for the parameters 0..23 and partition orders 0..5 (the
+// table of a pass must fit the union region), a second minimum per partition over the parameters 0..14 only, so that a subframe takes
+// Rice method 0 (4-bit parameters) wherever that is not larger than method 1 (5-bit), and a predictor is dropped when a residual leaves
+// the 32 bits the format gives it.  The PCM = false instantiation writes the bytes it always wrote.
+//
 // flac_encode_kernel: one workgroup per block of `block_size` inter-channel samples (the last block is shorter).  The block's four candidate
 // channels L, R, M = (L + R) >> 1 and S = L - R sit in LDS as int32 (24-bit streams: M = L + R with 7 wasted bits, so that M/S still
 // restores v << 8 exactly).  Per candidate channel 13 predictors are tried in 13 passes over all four channels: the fixed predictors of
@@ -56,12 +62,16 @@ constexpr int NPRED = 13;            // passes: fixed orders 0..4, then LPC orde
 constexpr int QLP_BITS = 15;         // coefficient precision in the stream
 constexpr int MAX_PO = 6;            // Rice partition orders 0..6
 constexpr int NK = 15;               // Rice parameters 0..14 (15 is method 0's escape code)
+constexpr int MAX_PO_PCM = 5;        // the int32-sample form: orders 0..5, so that the table of its 24 parameters fits the union region
+constexpr int NK_PCM = 24;           // ... parameters 0..23; method 1 above 14 (31 is its escape code)
+constexpr int SIDE_BITS = 17;        // the widest subframe sample of the int16 form (also of its shifted 24-bit stream: 8 or 7 bits are wasted)
+constexpr int SIDE_BITS_MAX = 25;    // ... and of the int32 form at 24 bits per sample
 constexpr int HEADER_MAX = 15;       // sync 2, sizes/rate 1, channels/width 1, frame number <= 6, block size <= 2, rate <= 2, CRC-8 1
 constexpr int CRC_CHUNK = 64;
 
-// worst case of one frame: header + 2 x (16 + 17 * block) bits + padding to a byte + CRC-16
-FLAC_FN int64_t worst_frame_bytes(int64_t bs) { return HEADER_MAX + (2 * (16 + 17 * bs) + 7) / 8 + 2; }
-FLAC_FN int frame_stride(int block_size) { return (int)((worst_frame_bytes(block_size) + 15) / 16 * 16); }
+// worst case of one frame: header + 2 x (16 + side_bits * block) bits + padding to a byte + CRC-16 (side_bits: the side channel's sample size)
+FLAC_FN int64_t worst_frame_bytes(int64_t bs, int side_bits = SIDE_BITS) { return HEADER_MAX + (2 * (16 + side_bits * bs) + 7) / 8 + 2; }
+FLAC_FN int frame_stride(int block_size, int side_bits = SIDE_BITS) { return (int)((worst_frame_bytes(block_size, side_bits) + 15) / 16 * 16); }
 
 // the header's block-size code: a table entry, else 6 / 7 = (size - 1) in 8 / 16 bits behind the frame number
 // the block size of a table code 1 .. 5 and 8 .. 15 (0 for the reserved code and for 6 / 7, whose size follows the frame number)
@@ -81,10 +91,10 @@ FLAC_FN int table_sample_rate(int code) {
 }
 
 struct Stream {
-  const int32_t *pcm;        // [n] samples, L in the low and R in the high half
+  const int32_t *pcm;        // [n] samples, L in the low and R in the high half; the int32 form: [n, 2]
   int64_t n;
   int32_t block_size;
-  int32_t bps;               // 16 or 24
+  int32_t bps;               // 16 or 24 (the int16 form at 24: the values shifted left by 8)
   int32_t sr_code;           // the header's sample-rate code ...
   int32_t sr_extra_bits;     // ... and the 0, 8 or 16 bits it puts behind the block size
   uint32_t sr_extra;
@@ -118,29 +128,38 @@ struct Small {
   double ac[4][MAX_ORDER + 1];
   unsigned long long cost[4][MAX_PO + 1];
   unsigned long long best_bits[4];
-  unsigned long long pk[4][128];                        // per partition [(1 << po) - 1 + j]: min over k of (Rice bits << 4 | k)
+  unsigned long long cost1[4][MAX_PO + 1];             // the int32 form: the same with method 1's parameters
+  unsigned long long pk[4][128];                        // per partition [(1 << po) - 1 + j]: min over k <= 14 of (Rice bits << 4 | k) (int32 form: << 5)
+  unsigned long long pk1[4][128];                       // the int32 form: min over every k
   int32_t coef[4][NPRED][MAX_ORDER];
   int32_t shift[4][NPRED];
   int32_t valid[4][NPRED];
   int32_t noteq[4], bad[4], sub_bps[4], hdr_bits[4];
   int32_t best_type[4], best_pred[4], best_po[4];      // type: 0 constant, 1 verbatim, 2 predicted (fixed or LPC by best_pred)
+  int32_t best_method[4];                               // Rice method of the best predictor: 0 = 4-bit, 1 = 5-bit parameters
   uint32_t csum[2][NT];
   int32_t sel[2];
   uint32_t sub_start[2], res_start[2];
   int32_t frame_len;
-  uint32_t crcs[(HEADER_MAX + (2 * (16 + 17 * MAX_BLOCK) + 7) / 8 + 2) / CRC_CHUNK + 2];
+  uint32_t crcs[(HEADER_MAX + (2 * (16 + SIDE_BITS_MAX * MAX_BLOCK) + 7) / 8 + 2) / CRC_CHUNK + 2];
   uint8_t kb[4][128];                                   // best parameter of partition j at order po: [(1 << po) - 1 + j]
+  uint8_t kb1[4][128];                                  // the int32 form: the same of pk1
   uint8_t best_k[4][64];
 };
 
-constexpr int IMG_WORDS = (int)(((HEADER_MAX + (2 * (16 + 17 * (int64_t)MAX_BLOCK) + 7) / 8 + 2 + 15) / 16 * 16) / 4);
-constexpr int UNION_BYTES = 2 * MAX_BLOCK * 4;          // acp [NT][9] doubles = sums [4][64][15] u64 (smaller) = res [2][MAX_BLOCK] u32
-static_assert(NT % 16 == 0 && (NT / 16) * (MAX_ORDER + 1) <= NT && NT * (MAX_ORDER + 1) * 8 <= UNION_BYTES && 4 * 64 * NK * 8 <= UNION_BYTES, "union region");
+constexpr int img_words(int side_bits) { return (int)(((HEADER_MAX + (2 * (16 + side_bits * (int64_t)MAX_BLOCK) + 7) / 8 + 2 + 15) / 16 * 16) / 4); }
+constexpr int IMG_WORDS = img_words(SIDE_BITS_MAX);     // the int32 form's image; the int16 form's is img_words(SIDE_BITS), and its layout ends sooner
+constexpr int UNION_BYTES = 2 * MAX_BLOCK * 4;          // acp [NT][9] doubles = sums [4][64][15] or [4][32][24] u64 (smaller) = res [2][MAX_BLOCK] u32
+static_assert(NT % 16 == 0 && (NT / 16) * (MAX_ORDER + 1) <= NT && NT * (MAX_ORDER + 1) * 8 <= UNION_BYTES && 4 * 64 * NK * 8 <= UNION_BYTES &&
+                  4 * (1 << MAX_PO_PCM) * NK_PCM * 8 <= UNION_BYTES && MAX_PO_PCM <= MAX_PO && NK_PCM <= 31,
+              "union region");
 constexpr int OFF_UNION = 4 * MAX_BLOCK * 4;
 constexpr int OFF_IMG = OFF_UNION + UNION_BYTES;
-constexpr int OFF_SMALL = OFF_IMG + IMG_WORDS * 4;
-constexpr int LDS_BYTES = OFF_SMALL + (int)((sizeof(Small) + 15) / 16 * 16);
-static_assert(OFF_SMALL % 16 == 0 && LDS_BYTES <= 160 * 1024, "one block's working set must fit a CU's 160 KiB of LDS");
+constexpr int off_small(bool pcm) { return OFF_IMG + (pcm ? IMG_WORDS : img_words(SIDE_BITS)) * 4; }
+constexpr int lds_bytes(bool pcm) { return off_small(pcm) + (int)((sizeof(Small) + 15) / 16 * 16); }
+constexpr int LDS_BYTES = lds_bytes(true);              // the larger of the two forms
+static_assert(off_small(false) % 16 == 0 && off_small(true) % 16 == 0 && lds_bytes(false) <= LDS_BYTES && LDS_BYTES <= 160 * 1024,
+              "one block's working set must fit a CU's 160 KiB of LDS");
 
 // n <= 32 bits of v at bit `pos` of the big-endian image (the image is zero where nothing was written yet)
 FLAC_FN void put_bits(uint32_t *img, uint32_t pos, int n, uint32_t v) {
@@ -204,47 +223,59 @@ FLAC_FN int64_t residual(const int32_t *x, int i, const int32_t *cf, int order, 
 }
 FLAC_FN int pred_order(int p) { return p < 5 ? p : p - 4; }
 // the largest admissible partition order: it divides the block and leaves more than `order` samples to the first partition
-FLAC_FN int max_partition_order(int bs, int order) {
+FLAC_FN int max_partition_order(int bs, int order, int cap = MAX_PO) {
   int mp = 0;
-  while (mp < MAX_PO && ((bs >> mp) & 1) == 0) ++mp;
+  while (mp < cap && ((bs >> mp) & 1) == 0) ++mp;
   while (mp > 0 && (bs >> mp) <= order) --mp;
   return mp;
 }
 
-// One block.  `lds` is LDS_BYTES of 16-byte aligned workgroup memory.
+// One block.  `lds` is lds_bytes(PCM) of 16-byte aligned workgroup memory.  PCM: the int32 form (above).
+template <bool PCM>
 #ifdef ASX_FLAC_HOST
 static void encode_block(const Stream &P, int64_t blk, unsigned char *lds)
 #else
 static __device__ __forceinline__ void encode_block(const Stream &P, int64_t blk, unsigned char *lds)
 #endif
 {
+  constexpr int NK = PCM ? NK_PCM : flac::NK;                 // parameters with exact bit counts
+  constexpr int KSH = PCM ? 5 : 4;                            // the parameter's field under the bits in pk / pk1
+  constexpr int PO_CAP = PCM ? MAX_PO_PCM : MAX_PO;
+  constexpr int MY_IMG_WORDS = PCM ? IMG_WORDS : img_words(SIDE_BITS);
+  constexpr long long RES_LIMIT = PCM ? 0x7fffffffll : (1ll << 30);   // |residual| below it, or the predictor is no candidate
   int32_t(*ch)[MAX_BLOCK] = reinterpret_cast<int32_t(*)[MAX_BLOCK]>(lds);
   double(*acp)[MAX_ORDER + 1] = reinterpret_cast<double(*)[MAX_ORDER + 1]>(lds + OFF_UNION);
   unsigned long long *sums = reinterpret_cast<unsigned long long *>(lds + OFF_UNION);   // [4][F][NK]
   uint32_t(*res)[MAX_BLOCK] = reinterpret_cast<uint32_t(*)[MAX_BLOCK]>(lds + OFF_UNION);
   uint32_t *img = reinterpret_cast<uint32_t *>(lds + OFF_IMG);
-  Small &S = *reinterpret_cast<Small *>(lds + OFF_SMALL);
+  Small &S = *reinterpret_cast<Small *>(lds + off_small(PCM));
 
   const int64_t first = blk * (int64_t)P.block_size;
   const int bs = (int)((P.n - first) < (int64_t)P.block_size ? (P.n - first) : (int64_t)P.block_size);
   const int chunk = (bs + NT - 1) / NT;
-  const bool wide = P.bps == 24;
+  const bool wide = !PCM && P.bps == 24;                      // the shifted stream of the int16 form
   const long long clk_begin = FLAC_CLOCK(P);
 
   // ---- load the four candidate channels, clear the image
   FLAC_LANES {
     for (int i = tid; i < bs; i += NT) {
-      const int32_t v = P.pcm[first + i];
-      const int32_t l = (int32_t)(int16_t)(v & 0xffff), r = v >> 16;
+      int32_t l, r;
+      if (PCM) {
+        l = P.pcm[2 * (first + i)];
+        r = P.pcm[2 * (first + i) + 1];
+      } else {
+        const int32_t v = P.pcm[first + i];
+        l = (int32_t)(int16_t)(v & 0xffff), r = v >> 16;
+      }
       ch[0][i] = l;
       ch[1][i] = r;
       ch[2][i] = wide ? l + r : (l + r) >> 1;
       ch[3][i] = l - r;
     }
-    for (int w = tid; w < IMG_WORDS; w += NT) img[w] = 0u;
+    for (int w = tid; w < MY_IMG_WORDS; w += NT) img[w] = 0u;
     if (tid < 4) {
       S.noteq[tid] = 0;
-      S.sub_bps[tid] = (tid == 3 || (tid == 2 && wide)) ? 17 : 16;
+      S.sub_bps[tid] = PCM ? P.bps + (tid == 3 ? 1 : 0) : (tid == 3 || (tid == 2 && wide)) ? 17 : 16;
       S.hdr_bits[tid] = 8 + (wide ? (tid == 2 ? 7 : 8) : 0);
       for (int p = 0; p < NPRED; ++p) {
         S.valid[tid][p] = p < 5 ? 1 : 0;
@@ -352,6 +383,7 @@ static __device__ __forceinline__ void encode_block(const Stream &P, int64_t blk
       }
       S.best_pred[c] = 0;
       S.best_po[c] = 0;
+      S.best_method[c] = 0;
     }
   }
   FLAC_SYNC();
@@ -360,14 +392,20 @@ static __device__ __forceinline__ void encode_block(const Stream &P, int64_t blk
   for (int p = 0; p < NPRED; ++p) {
     const int order = pred_order(p);
     if (order >= bs) continue;
-    const int mp = max_partition_order(bs, order);
+    const int mp = max_partition_order(bs, order, PO_CAP);
     const int F = 1 << mp, plen = bs >> mp;
     FLAC_LANES {
       for (int q = tid; q < 4 * F * NK; q += NT) sums[q] = 0ull;
-      for (int q = tid; q < 4 * 128; q += NT) S.pk[q >> 7][q & 127] = ~0ull;
+      for (int q = tid; q < 4 * 128; q += NT) {
+        S.pk[q >> 7][q & 127] = ~0ull;
+        if (PCM) S.pk1[q >> 7][q & 127] = ~0ull;
+      }
       if (tid < 4) {
         S.bad[tid] = 0;
-        for (int o = 0; o <= MAX_PO; ++o) S.cost[tid][o] = 0ull;
+        for (int o = 0; o <= MAX_PO; ++o) {
+          S.cost[tid][o] = 0ull;
+          if (PCM) S.cost1[tid][o] = 0ull;
+        }
       }
     }
     FLAC_SYNC();
@@ -395,7 +433,7 @@ static __device__ __forceinline__ void encode_block(const Stream &P, int64_t blk
             next += plen;
           }
           int64_t r = residual(ch[c], i, cf, order, sh);
-          if (r >= (1ll << 30) || r < -(1ll << 30)) {
+          if (PCM ? (r >= RES_LIMIT || r <= -RES_LIMIT) : (r >= RES_LIMIT || r < -RES_LIMIT)) {
             bad = true;
             r = 0;
           }
@@ -420,7 +458,8 @@ static __device__ __forceinline__ void encode_block(const Stream &P, int64_t blk
         const int span = F >> po;
         unsigned long long bits = (unsigned long long)(k + 1) * (unsigned long long)((bs >> po) - (j == 0 ? order : 0));
         for (int f = 0; f < span; ++f) bits += sums[(c * F + j * span + f) * NK + k];
-        FLAC_MIN64(&S.pk[c][qq], (bits << 4) | (unsigned long long)k);
+        if (!PCM || k < flac::NK) FLAC_MIN64(&S.pk[c][qq], (bits << KSH) | (unsigned long long)k);
+        if (PCM) FLAC_MIN64(&S.pk1[c][qq], (bits << KSH) | (unsigned long long)k);
       }
     }
     FLAC_SYNC();
@@ -431,25 +470,34 @@ static __device__ __forceinline__ void encode_block(const Stream &P, int64_t blk
         int po = 0;
         while ((2 << po) - 1 <= qq) ++po;
         const unsigned long long v = S.pk[c][qq];
-        S.kb[c][qq] = (uint8_t)(v & 15ull);
-        FLAC_ADD64(&S.cost[c][po], (v >> 4) + 4ull);
+        S.kb[c][qq] = (uint8_t)(v & ((1ull << KSH) - 1ull));
+        FLAC_ADD64(&S.cost[c][po], (v >> KSH) + 4ull);
+        if (PCM) {
+          const unsigned long long v1 = S.pk1[c][qq];
+          S.kb1[c][qq] = (uint8_t)(v1 & ((1ull << KSH) - 1ull));
+          FLAC_ADD64(&S.cost1[c][po], (v1 >> KSH) + 5ull);
+        }
       }
     }
     FLAC_SYNC();
     FLAC_LANES {
       if (tid < 4 && S.valid[tid][p] && !S.bad[tid]) {
         const int c = tid;
-        int po = 0;
-        for (int o = 1; o <= mp; ++o)
-          if (S.cost[c][o] < S.cost[c][po]) po = o;
+        int po = 0, method = 0;                  // equal costs: the lower order, and method 0 before method 1
+        unsigned long long least = S.cost[c][0];
+        for (int o = 0; o <= mp; ++o) {
+          if (S.cost[c][o] < least) least = S.cost[c][o], po = o, method = 0;
+          if (PCM && S.cost1[c][o] < least) least = S.cost1[c][o], po = o, method = 1;
+        }
         const unsigned long long bits = (unsigned long long)(S.hdr_bits[c] + order * S.sub_bps[c] + (p >= 5 ? 4 + 5 + order * QLP_BITS : 0) + 2 + 4) +
-                                        S.cost[c][po];
+                                        least;
         if (bits < S.best_bits[c]) {
           S.best_bits[c] = bits;
           S.best_type[c] = 2;
           S.best_pred[c] = p;
           S.best_po[c] = po;
-          for (int j = 0; j < (1 << po); ++j) S.best_k[c][j] = S.kb[c][(1 << po) - 1 + j];
+          S.best_method[c] = method;
+          for (int j = 0; j < (1 << po); ++j) S.best_k[c][j] = method ? S.kb1[c][(1 << po) - 1 + j] : S.kb[c][(1 << po) - 1 + j];
         }
       }
     }
@@ -473,7 +521,7 @@ static __device__ __forceinline__ void encode_block(const Stream &P, int64_t blk
       hb[nh++] = 0xffu;
       hb[nh++] = 0xf8u;
       hb[nh++] = (uint32_t)((bcode << 4) | P.sr_code);
-      hb[nh++] = (uint32_t)((assign[mode] << 4) | ((wide ? 6 : 4) << 1));
+      hb[nh++] = (uint32_t)((assign[mode] << 4) | ((P.bps == 24 ? 6 : 4) << 1));
       const uint32_t fn = (uint32_t)blk;
       if (fn < 0x80u) {
         hb[nh++] = fn;
@@ -520,7 +568,7 @@ static __device__ __forceinline__ void encode_block(const Stream &P, int64_t blk
           pos += 9;
           for (int j = 0; j < order; ++j, pos += QLP_BITS) put_bits(img, pos, QLP_BITS, (uint32_t)S.coef[c][p][j]);
         }
-        put_bits(img, pos, 6, (uint32_t)S.best_po[c]);   // method 0 (two zero bits), then the partition order
+        put_bits(img, pos, 6, (uint32_t)((S.best_method[c] << 4) | S.best_po[c]));   // the method in two bits, then the partition order
         pos += 6;
       }
       S.res_start[tid] = pos;
@@ -581,14 +629,15 @@ static __device__ __forceinline__ void encode_block(const Stream &P, int64_t blk
         if (i0 < order) i0 = order;
         if (i0 < i1) {
           int part = i0 / plen;
-          uint32_t pos = S.res_start[s] + S.csum[s][tid] + 4u * (uint32_t)(part + 1);
+          const uint32_t pb = S.best_method[c] ? 5u : 4u;   // bits of a partition's parameter
+          uint32_t pos = S.res_start[s] + S.csum[s][tid] + pb * (uint32_t)(part + 1);
           for (int i = i0; i < i1; ++i) {
             if (i == (part + 1) * plen) {
               ++part;
-              pos += 4u;
+              pos += pb;
             }
             const int k = S.best_k[c][part];
-            if (i == (part == 0 ? order : part * plen)) put_bits(img, pos - 4u, 4, (uint32_t)k);
+            if (i == (part == 0 ? order : part * plen)) put_bits(img, pos - pb, (int)pb, (uint32_t)k);
             const uint32_t u = res[s][i];
             const uint32_t q = u >> k;
             put_bits(img, pos + q, k + 1, (1u << k) | (u & ((1u << k) - 1u)));
@@ -651,9 +700,10 @@ static __device__ __forceinline__ void encode_block(const Stream &P, int64_t blk
 }
 
 #ifndef ASX_FLAC_HOST
+template <bool PCM>
 __global__ __launch_bounds__(NT) void flac_encode_kernel(Stream P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char flac_lds[];
-  encode_block(P, (int64_t)blockIdx.x, flac_lds);
+  encode_block<PCM>(P, (int64_t)blockIdx.x, flac_lds);
 }
 
 // offsets[b] = sum of frame_bytes[0 .. b), offsets[nb] = the stream's audio bytes: one workgroup, a run of blocks per lane

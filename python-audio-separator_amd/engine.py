@@ -279,7 +279,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_mdxc_demix_batch_dev", "asx_rof_demix_batch_dev", "asx_ensemble_batch_dev", "asx_resample_rational_plan",
            "asx_resample_rational", "asx_resample_rational_dev", "asx_op_hd_lstm_layer", "asx_op_hd_lstm_frames", "asx_op_vr_lstm",
            "asx_op_vr_lstm_layout", "asx_flac_plan", "asx_flac_encode", "asx_flac_encode_dev",
-           "asx_flac_decode_plan", "asx_flac_decode_scan_dev", "asx_flac_decode_finish_dev", "asx_flac_decode"]
+           "asx_flac_decode_plan", "asx_flac_decode_scan_dev", "asx_flac_decode_finish_dev", "asx_flac_decode",
+           "asx_flac_plan_pcm", "asx_flac_encode_pcm", "asx_flac_encode_pcm_dev", "asx_pcm_encode", "asx_pcm_encode_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -424,6 +425,11 @@ def load_library():
     lib.asx_flac_plan.argtypes = [i64, i32, i32, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
     lib.asx_flac_encode.argtypes = [vp, C.POINTER(C.c_int16), i64, i32, i32, i32, C.POINTER(C.c_uint8), i64, C.POINTER(i32), C.POINTER(i64)]
     lib.asx_flac_encode_dev.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, vp, C.POINTER(i64), vp]
+    lib.asx_flac_plan_pcm.argtypes = lib.asx_flac_plan.argtypes
+    lib.asx_flac_encode_pcm.argtypes = [vp, C.POINTER(i32), i64, i32, i32, i32, C.POINTER(C.c_uint8), i64, C.POINTER(i32), C.POINTER(i64)]
+    lib.asx_flac_encode_pcm_dev.argtypes = lib.asx_flac_encode_dev.argtypes
+    lib.asx_pcm_encode.argtypes = [vp, _FP, i64, i32, C.c_float, C.c_float, i32, i32, vp, _FP]
+    lib.asx_pcm_encode_dev.argtypes = [vp, vp, i64, i32, C.c_float, C.c_float, i32, i32, vp, _FP, vp]
     lib.asx_flac_decode_plan.argtypes = [i64, i32, i32, i32, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     lib.asx_flac_decode_scan_dev.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp]
     lib.asx_flac_decode_finish_dev.argtypes = [vp, vp, i64, _FP, vp]
@@ -1092,10 +1098,14 @@ class Engine:
         """asx_flac_plan (pure host: no engine, no GPU): {n_blocks, frame_stride, max_bytes, scratch_bytes} of the FLAC encoder for
         ``n_samples`` inter-channel samples.  Raises AsxError for what the encoder refuses (channels other than 2, bits per sample other
         than 16 / 24, a block size outside 16 .. 4608, no samples)."""
+        return Engine._flac_plan("asx_flac_plan", n_samples, channels, bits_per_sample, block_size)
+
+    @staticmethod
+    def _flac_plan(symbol, n_samples, channels, bits_per_sample, block_size) -> dict:
         lib = load_library()
         nb, stride, mx, scratch = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64()
-        rc = lib.asx_flac_plan(int(n_samples), int(channels), int(bits_per_sample), int(block_size), C.byref(nb), C.byref(stride), C.byref(mx),
-                               C.byref(scratch))
+        rc = getattr(lib, symbol)(int(n_samples), int(channels), int(bits_per_sample), int(block_size), C.byref(nb), C.byref(stride), C.byref(mx),
+                                  C.byref(scratch))
         if rc != 0:
             msg = lib.asx_last_error()
             raise AsxError(f"asx error {rc}: {msg.decode() if msg else '?'}")
@@ -1124,6 +1134,37 @@ class Engine:
         total = C.c_int64()
         self._check(self._lib.asx_flac_encode_dev(self._h, pcm_ptr, int(n_samples), int(samplerate), int(bits_per_sample), int(block_size), out_ptr,
                                                   int(out_capacity), frame_bytes_ptr, C.byref(total), stream or None))
+        return total.value
+
+    @staticmethod
+    def flac_plan_pcm(n_samples: int, channels: int = 2, bits_per_sample: int = 24, block_size: int = FLAC_BLOCK_SIZE) -> dict:
+        """asx_flac_plan_pcm (pure host): ``flac_plan`` for the encoder of int32 samples of 16 or 24 real bits, whose worst frame is
+        header + 2 x (16 + (bits_per_sample + 1) x block_size) bits + padding + CRC-16."""
+        return Engine._flac_plan("asx_flac_plan_pcm", n_samples, channels, bits_per_sample, block_size)
+
+    def flac_encode_pcm(self, pcm: np.ndarray, samplerate: int, bits_per_sample: int = 24, block_size: int = FLAC_BLOCK_SIZE):
+        """int32 [n, 2] samples of ``bits_per_sample`` (16 or 24) real bits -> (the stream's audio frames back to back as uint8, their
+        sizes as int32 [n_blocks]); asx_flac_encode_pcm.  A sample outside the width is refused."""
+        a = np.asarray(pcm)
+        if a.dtype != np.int32 or a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError(f"flac_encode_pcm expects int32 [n, 2], got {a.dtype} {a.shape}")
+        a = np.ascontiguousarray(a)
+        plan = self.flac_plan_pcm(a.shape[0], 2, bits_per_sample, block_size)
+        out = np.empty(plan["max_bytes"], np.uint8)
+        sizes = np.empty(plan["n_blocks"], np.int32)
+        total = C.c_int64()
+        self._check(self._lib.asx_flac_encode_pcm(self._h, a.ctypes.data_as(C.POINTER(C.c_int32)), a.shape[0], int(samplerate), int(bits_per_sample),
+                                                  int(block_size), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size,
+                                                  sizes.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(total)))
+        return out[:total.value], sizes
+
+    def flac_encode_pcm_dev(self, pcm_ptr: int, n_samples: int, samplerate: int, bits_per_sample: int, block_size: int, out_ptr: int,
+                            out_capacity: int, frame_bytes_ptr: int, stream: int = 0) -> int:
+        """asx_flac_encode_pcm_dev: device int32 [n, 2] (``pcm_encode_dev`` with "S16_IN_32" / "S24_IN_32") -> frames in ``out_ptr`` (room
+        for ``flac_plan_pcm``'s max_bytes), sizes in ``frame_bytes_ptr``; returns the frames' total bytes (synchronises the stream once)."""
+        total = C.c_int64()
+        self._check(self._lib.asx_flac_encode_pcm_dev(self._h, pcm_ptr, int(n_samples), int(samplerate), int(bits_per_sample), int(block_size),
+                                                      out_ptr, int(out_capacity), frame_bytes_ptr, C.byref(total), stream or None))
         return total.value
 
     @staticmethod
@@ -1197,6 +1238,40 @@ class Engine:
         return pk.value if want_peak else None
 
     PCM_FORMATS = {"PCM_16": 16, "PCM_24": 24, "PCM_32": 32, "FLOAT": 0x120}
+
+    # sample formats of pcm_encode*: the WAV subtypes, and the 16- / 24-bit integers in int32 containers that flac_encode_pcm_dev reads
+    PCM_ENCODE_FORMATS = dict(PCM_FORMATS, S16_IN_32=0x410, S24_IN_32=0x418)
+    PCM_ENCODE_DTYPES = {"PCM_16": ("<i2", 2), "PCM_24": ("u1", 6), "PCM_32": ("<i4", 2), "FLOAT": ("<f4", 2), "S16_IN_32": ("<i4", 2),
+                         "S24_IN_32": ("<i4", 2)}          # numpy dtype and columns per frame of the encoded body
+    STEM_LAYOUTS = {"planar": 0, "rows": 1}
+
+    def pcm_encode(self, stem: np.ndarray, subtype: str, max_peak: float = 1.0, min_peak=None, layout: str = "rows"):
+        """write_audio_soundfile's array work: ``stem`` float32 [n, 2] (``layout`` "rows") or [2, n] ("planar") -> (the samples in the
+        file's format, interleaved: [n, 2] of the subtype's dtype, PCM_24 as uint8 [n, 6]; the peak after normalisation).  asx_pcm_encode."""
+        if subtype not in self.PCM_ENCODE_FORMATS:
+            raise ValueError(f"no device encoder for subtype {subtype}")
+        a = np.ascontiguousarray(stem, np.float32)
+        if a.ndim != 2 or a.shape[1 if layout == "rows" else 0] != 2:
+            raise ValueError(f"pcm_encode expects a {'[n, 2]' if layout == 'rows' else '[2, n]'} stem, got {a.shape}")
+        n = a.shape[0 if layout == "rows" else 1]
+        dtype, cols = self.PCM_ENCODE_DTYPES[subtype]
+        out = np.empty((n, cols), dtype)
+        pk = C.c_float()
+        self._check(self._lib.asx_pcm_encode(self._h, _ptr(a), n, self.STEM_LAYOUTS[layout], float(max_peak), float(min_peak or 0.0),
+                                             int(min_peak is not None), self.PCM_ENCODE_FORMATS[subtype], out.ctypes.data, C.byref(pk)))
+        return out, pk.value
+
+    def pcm_encode_dev(self, stem_ptr: int, n_samples: int, layout: str, max_peak: float, min_peak, subtype: str, out_ptr: int,
+                       stream: int = 0, want_peak: bool = True):
+        """asx_pcm_encode_dev: a device-resident stem (only read) -> the body of a WAVE data chunk at ``out_ptr`` (16-byte aligned,
+        n_samples x 4, 6 or 8 bytes); returns the peak after normalisation (synchronises the stream) or None."""
+        if subtype not in self.PCM_ENCODE_FORMATS:
+            raise ValueError(f"no device encoder for subtype {subtype}")
+        pk = C.c_float()
+        self._check(self._lib.asx_pcm_encode_dev(self._h, stem_ptr, int(n_samples), self.STEM_LAYOUTS[layout], float(max_peak),
+                                                 float(min_peak or 0.0), int(min_peak is not None), self.PCM_ENCODE_FORMATS[subtype], out_ptr,
+                                                 C.byref(pk) if want_peak else None, stream or None))
+        return pk.value if want_peak else None
 
     def pcm_decode_dev(self, raw_ptr: int, frames: int, channels: int, subtype: str, mix_ptr: int, stream: int = 0,
                        want_peak: bool = True):
