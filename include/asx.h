@@ -748,6 +748,37 @@ typedef struct asx_ens_job {
 int asx_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int32_t n_jobs, int32_t algorithm, const double *weights, int32_t n_weights,
                            int32_t mode, float max_peak, float min_peak, int32_t has_min, double silent_below, void *stream);
 
+/* asx_invert_stem with every array in HBM: spec_utils.invert_stem(mix, stem * stem_scale).
+ *   mix_dev      planar [2, n_samples], float32, only read
+ *   stem_dev     planar [2, n_samples] (ASX_STEM_PLANAR) or rows [n_samples, 2] (ASX_STEM_ROWS, as asx_separate_dev leaves the primary
+ *                stem), only read; stem_scale is applied as one float32 multiplication of every sample read (numpy's
+ *                primary * compensate), 1.0f changes nothing
+ *   out_dev      rows [*n_out, 2], *n_out = 1024 * (n_samples / 1024) <= out_capacity; nothing beyond 2 * *n_out floats is written
+ * The call only enqueues work on `stream`: no copy from or to the host, no synchronisation.  *n_out = 0 (n_samples < 1024) is a
+ * result: nothing is launched and out_dev may be NULL.  For a planar stem the result is, bit for bit, asx_invert_stem's for the stem
+ * multiplied on the host, transposed.  ASX_ERR_INVALID + asx_last_error() for null pointers, n_samples outside 1 .. 2^38, an unknown
+ * layout or out_capacity < *n_out, before anything is enqueued.
+ *
+ * asx_invert_stem_batch_dev: the same for a list of songs of any lengths with ONE launch per stage (frames, fold) over all of
+ * them; a song of fewer than 1024 samples takes part in neither and gets n_out = 0.  Every song's result is bit for bit that of
+ * asx_invert_stem_dev for that song alone.  Every argument of every song is checked before anything is enqueued or any n_out
+ * written; the message names the song.  One table upload from pinned memory per call.  The host does
+ * not wait for the work it enqueues; it may wait for the table copy of the previous pooled call on this engine (this one's or
+ * asx_ensemble_batch_dev's: they share the staging area and its event).  The first spectral call on an engine, of either form,
+ * uploads the window and twiddle tables once.  Additive within ABI 7. */
+typedef struct asx_invert_song {
+  const float *mix_dev;     /* planar [2, n_samples] */
+  const float *stem_dev;    /* planar [2, n_samples] or rows [n_samples, 2] */
+  float *out_dev;           /* rows, room for [out_capacity, 2]; may be NULL where n_out == 0 */
+  int64_t n_samples;
+  int64_t out_capacity;     /* >= 1024 * (n_samples / 1024) */
+  int64_t n_out;            /* written */
+  int32_t stem_layout;      /* ASX_STEM_PLANAR / ASX_STEM_ROWS */
+} asx_invert_song;
+int asx_invert_stem_dev(asx_engine *e, const float *mix_dev, const float *stem_dev, int64_t n_samples, int32_t stem_layout, float stem_scale,
+                        float *out_dev, int64_t out_capacity, int64_t *n_out, void *stream);
+int asx_invert_stem_batch_dev(asx_engine *e, asx_invert_song *songs, int32_t n_songs, float stem_scale, void *stream);
+
 /* Launch counters of this process (tests use them to prove which kernel family ran; ABI 6 -- until ABI 5 they travelled through a
  * float of asx_debug_fetch, which stops resolving single launches past 2^24): "tdf3_launches" (split-operand row GEMM, either arithmetic),
  * "tdf3h_launches" (those of them, plain or GATHER mode, that ran the fp16 x 3 arithmetic),

@@ -82,9 +82,6 @@ class MDXSeparator(CommonSeparator):
         return self._dm.run_model(mix, is_match_mix=is_match_mix)
 
     # ---- one file: load (base ``_load_mix``), stems, ``_emit_file`` ---------------------------------------------------------
-    def _device_decode(self, path):
-        return None if self.invert_using_spec else self._device_mix(path)     # invert_stem runs on host arrays
-
     def _require_stereo(self, mix):
         if mix.shape[0] != 2:
             msg = f"Expected a 2-channel audio signal, but got {mix.shape[0]} channels"
@@ -93,7 +90,9 @@ class MDXSeparator(CommonSeparator):
 
     def _device_stems(self, mix):
         """The stems of a mix decoded on the device (CUDA tensor [2, N]) with every array in HBM: asx_separate_dev.  Returns
-        (primary, secondary), CUDA tensors [N, 2]."""
+        (primary, secondary), CUDA tensors [N, 2].  ``invert_using_spec``: the steps of MDXDemixer.separate_stems on the same stream --
+        the match-mix demix of the normalised mix, then asx_invert_stem_dev over the rows primary scaled by ``compensate``; the
+        secondary stem is [1024 * (N // 1024), 2], shorter than the primary as on the host path."""
         import torch
         t0 = self._now()
         self.initialize_model_settings()
@@ -102,13 +101,24 @@ class MDXSeparator(CommonSeparator):
         secondary = torch.empty((n, 2), dtype=torch.float32, device=mix.device)
         self.engine.separate_dev(mix.data_ptr(), n, self.normalization_threshold, self.amplification_threshold, self.compensate,
                                  primary.data_ptr(), secondary.data_ptr(), stream=self._stream())
+        if self.invert_using_spec:
+            raw = secondary.view(2, n)                    # mix.T - compensate * primary is not used: its buffer takes the match-mix demix
+            self.engine.demix_dev(mix.data_ptr(), n, raw.data_ptr(), is_match_mix=True, stream=self._stream())
+            t0 = self._tick("demix", t0)
+            n_out = 1024 * (n // 1024)
+            secondary = torch.empty((n_out, 2), dtype=torch.float32, device=mix.device)
+            self.engine.invert_stem_dev(raw.data_ptr(), primary.data_ptr(), n, "rows", self.compensate, secondary.data_ptr(), n_out,
+                                        stream=self._stream())
+            self._tick("invert", t0)
+            return primary, secondary
         self._tick("demix", t0)
         return primary, secondary
 
     def stems_dev(self, audio_file_path):
         """The stems ``separate(audio_file_path)`` would hand to write_audio, in its order (secondary first), left on the device:
         [(stem name, CUDA tensor [N, 2], "rows")]; honours ``output_single_stem``.  None when the file needs the host decoder
-        (the condition under which ``_device_decode`` returns None).  Writes nothing."""
+        (the condition under which ``_device_decode`` returns None).  Writes nothing.  With ``invert_using_spec`` the secondary stem
+        has 1024 * (N // 1024) rows, and is not in the list below 1024 samples."""
         self._begin_file(audio_file_path)
         mix = self._device_decode(self.audio_file_path)
         if mix is None:
@@ -116,18 +126,19 @@ class MDXSeparator(CommonSeparator):
         return self._stems_of(self._device_stems(mix))
 
     def _stems_of(self, stems):
-        """(primary, secondary) CUDA tensors [N, 2] -> the list ``stems_dev`` returns."""
-        if isinstance(stems[0], np.ndarray):              # invert_using_spec: host stems (no file reaches here on the device path)
-            return None
+        """(primary, secondary) CUDA tensors [N, 2] -> the list ``stems_dev`` returns.  An empty stem (``invert_using_spec`` on fewer
+        than 1024 samples) is left out: ``separate`` writes no file for it, so an ensemble has nothing of it to combine."""
         stems = dict(zip(("primary", "secondary"), stems))
-        return [(name, stems[which], "rows") for name, which in self._wanted_pair()]
+        return [(name, stems[which], "rows") for name, which in self._wanted_pair() if stems[which].shape[0]]
 
     def _emit_file(self, stems, on_device, custom_output_names):
         """(primary, secondary) of the current file -> its output files.  Decoded on the device: the float stems stay there, the
         sources are their pinned host mirrors and asx_pcm16_rows_dev quantises each written stem without a second upload.
         Decoded on the host: host stems and the host writer."""
         t0 = self._now()
-        mirror = self._host_stem if on_device else self._to_host
+        # (an empty stem -- invert_using_spec on fewer than 1024 samples -- has nothing to quantise on the device: the writer's "nothing
+        # to write" branch gets a plain empty array, as on the host path)
+        mirror = (lambda stem: self._host_stem(stem) if stem.shape[0] else self._to_host(stem)) if on_device else self._to_host
         # a primary_source / secondary_source set before separate() is honoured: unlike MDXC and VR, separate() here does not
         # reset the file state first (separate_many does, per file)
         for which, stem in zip(("primary", "secondary"), stems):
@@ -157,7 +168,7 @@ class MDXSeparator(CommonSeparator):
     def _pooled_stems(self, mixes):
         """asx_separate_batch_dev: the chunks of all files share the net passes."""
         self.initialize_model_settings()                  # after the files are loaded, where separate() runs it
-        if self.invert_using_spec:                        # every file was decoded on the host
+        if self.invert_using_spec and not self._fast_file_path_enabled():      # every file was decoded on the host: the host arrays' path
             return self._dm.separate_stems_many([h for _, h in mixes])
         import torch
         mixes = self._device_mixes(mixes)
@@ -166,4 +177,13 @@ class MDXSeparator(CommonSeparator):
         self.engine.separate_batch_dev([(m.data_ptr(), p.data_ptr(), s.data_ptr(), m.shape[1]) for m, p, s in zip(mixes, prim, sec)],
                                        self.normalization_threshold, self.amplification_threshold, self.compensate,
                                        stream=self._stream())
+        if self.invert_using_spec:
+            # MDXDemixer.separate_stems_many on the device: one pooled match-mix demix of the normalised mixes (into the buffers of the
+            # unused mix.T - compensate * primary), one pooled invert_stem over the rows primaries scaled by ``compensate``
+            raws = [s.view(2, m.shape[1]) for m, s in zip(mixes, sec)]
+            self.engine.demix_batch_dev([(m.data_ptr(), r.data_ptr(), m.shape[1]) for m, r in zip(mixes, raws)], is_match_mix=True,
+                                        stream=self._stream())
+            sec = [torch.empty((1024 * (m.shape[1] // 1024), 2), dtype=torch.float32, device=m.device) for m in mixes]
+            self.engine.invert_stem_batch_dev([(r.data_ptr(), p.data_ptr(), m.shape[1], "rows", s.data_ptr(), s.shape[0])
+                                               for m, r, p, s in zip(mixes, raws, prim, sec)], self.compensate, stream=self._stream())
         return list(zip(prim, sec))

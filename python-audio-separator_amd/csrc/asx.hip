@@ -2844,6 +2844,19 @@ int asx_invert_stem(asx_engine *e, const float *mix_host, const float *stem_host
   return ASX_OK;
 }
 
+int asx_invert_stem_dev(asx_engine *e, const float *mix_dev, const float *stem_dev, int64_t N, int32_t stem_layout, float stem_scale,
+                        float *out_dev, int64_t out_capacity, int64_t *n_out, void *stream) {
+  REQUIRE(e && n_out, "asx_invert_stem_dev: null engine or n_out");
+  HIPCHK(hipSetDevice(e->device));
+  return ens_invert_stem_dev(e, mix_dev, stem_dev, N, (int)stem_layout, stem_scale, out_dev, out_capacity, n_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+int asx_invert_stem_batch_dev(asx_engine *e, asx_invert_song *songs, int32_t n_songs, float stem_scale, void *stream) {
+  REQUIRE(e, "asx_invert_stem_batch_dev: null engine");
+  HIPCHK(hipSetDevice(e->device));
+  return ens_invert_stem_batch_dev(e, songs, n_songs, stem_scale, reinterpret_cast<hipStream_t>(stream));
+}
+
 // ---- BagOfModels combine on the device (every member keeps its own engine / weights; no float stem visits the host) -------
 int asx_ht_standardize_dev(asx_engine *e, const float *mix_dev, int64_t N, float *out_dev, void *stream) {
   REQUIRE(e && mix_dev && out_dev && N >= 2, "asx_ht_standardize_dev: bad argument");

@@ -28,6 +28,7 @@ struct EnsCtx {
   // asx_ensemble_batch_dev: contributor table, peaks, job table, ensemble_wav's sums and choices; their host staging and the event
   // behind the last copy out of it
   DevBuf psrcs, ppeaks, pjobs, ppartial, psel;
+  DevBuf isongs;   // asx_invert_stem_batch_dev: song table (staged like the job table)
   PinBuf stage;
   hipEvent_t staged = nullptr;
   bool ready = false;
@@ -35,7 +36,7 @@ struct EnsCtx {
 
 static void ens_destroy(EnsCtx *c) {
   for (DevBuf *b : {&c->window, &c->tw, &c->frames, &c->wss, &c->dweights, &c->din, &c->din2, &c->dout, &c->partial, &c->sel, &c->psrcs,
-                    &c->ppeaks, &c->pjobs, &c->ppartial, &c->psel})
+                    &c->ppeaks, &c->pjobs, &c->ppartial, &c->psel, &c->isongs})
     b->release();
   if (c->staged) {
     (void)hipEventSynchronize(c->staged);
@@ -67,6 +68,12 @@ static int ens_ctx(asx_engine *e) {
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ens_fft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ens_invert_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ens_pool_fft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  // The invert kernels on device arrays hold two spectra: 32,784 B, inside the limit every device starts with.  They need no raise on
+  // any device, so the process-wide record of grant_lds, which the raises above must avoid, does them no harm: the grant goes through
+  // the one guarded path and changes nothing.  Should their LDS ever pass the default limit, they need a per-engine raise as above.
+  const int inv_lds = (int)(((size_t)c.plan.nh * 2 + (size_t)(c.plan.nh + 1) * 2) * sizeof(float2));
+  grant_lds(&ens_invert_dev_kernel, inv_lds);
+  grant_lds(&ens_invert_pool_kernel, inv_lds);
   c.ready = true;
   return ASX_OK;
 }
@@ -158,6 +165,92 @@ static int ens_invert_dev(asx_engine *e, const float *mix, const float *stem, in
   }));
   *n_out = (int64_t)hop * (T - 1);
   return ens_fold(e, T, *n_out, out, s);
+}
+
+// ---- invert_stem with every array in HBM ----------------------------------------------------------------------------------
+// One song of asx_invert_stem_dev / asx_invert_stem_batch_dev, checked: its frame count in *T (1: no result).  `who` names the song
+// in the message ("" for the single call).
+static int ens_invert_check(const char *fn, const char *who, const float *mix, const float *stem, int64_t N, int layout, const float *out,
+                            int64_t capacity, int *T) {
+  REQUIRE(mix && stem, "%s: %snull mix or stem", fn, who);
+  REQUIRE(N >= 1 && N <= ((int64_t)1 << 38), "%s: %sn_samples %lld (1 .. 2^38)", fn, who, (long long)N);
+  REQUIRE(layout == ASX_STEM_PLANAR || layout == ASX_STEM_ROWS, "%s: %sstem layout %d (0 planar [2, n], 1 rows [n, 2])", fn, who, layout);
+  *T = (int)(1 + N / ENS_PLAN_HOP);
+  const int64_t n_out = (int64_t)ENS_PLAN_HOP * (*T - 1);
+  REQUIRE(capacity >= n_out, "%s: %soutput capacity %lld below n_out = %lld", fn, who, (long long)capacity, (long long)n_out);
+  REQUIRE(out || n_out == 0, "%s: %snull output", fn, who);
+  return ASX_OK;
+}
+
+static int ens_invert_stem_dev(asx_engine *e, const float *mix, const float *stem, int64_t N, int layout, float scale, float *out,
+                               int64_t capacity, int64_t *n_out, hipStream_t s) {
+  int T = 0;
+  CHK(ens_invert_check("asx_invert_stem_dev", "", mix, stem, N, layout, out, capacity, &T));
+  if (T < 2) {   // fewer than 1024 samples: nothing is launched, as in asx_invert_stem
+    *n_out = 0;
+    return ASX_OK;
+  }
+  CHK(ens_ctx(e));
+  EnsCtx &c = *e->ens;
+  const int nf = c.plan.n_fft, nh = c.plan.nh, hop = ENS_PLAN_HOP;
+  const EnsInvSong sg{mix, stem, out, N, (int64_t)hop * (T - 1), 0, 0, T, (int32_t)(layout == ASX_STEM_ROWS)};
+  CHK(c.frames.ensure((size_t)2 * T * nf * 4));
+  const size_t lds = ((size_t)nh * 2 + (size_t)(nh + 1) * 2) * sizeof(float2);
+  CHK(timed(e, ASX_PROF_STFT, 0.0, 4.0 * (4.0 * N + 2.0 * T * nf), s, [&]() {
+    hipLaunchKernelGGL(ens_invert_dev_kernel, dim3(T, 2), dim3(256), lds, s, sg, scale, hop, c.frames.f(), c.window.f(),
+                       reinterpret_cast<const float2 *>(c.tw.p), c.plan);
+  }));
+  *n_out = sg.n_out;
+  return timed(e, ASX_PROF_OLA, 0.0, 4.0 * 2 * (T * (double)nf + sg.n_out), s, [&]() {
+    hipLaunchKernelGGL(ens_invert_dev_fold_kernel, dim3((unsigned)((sg.n_out + 255) / 256)), dim3(256), 0, s, sg, (const float *)c.frames.f(),
+                       (const float *)c.window.f(), nf, hop);
+  });
+}
+
+// The same for a list of songs: one table upload, then one launch per stage over the songs of at least two frames.
+static int ens_invert_stem_batch_dev(asx_engine *e, asx_invert_song *songs, int n_songs, float scale, hipStream_t s) {
+  const char *fn = "asx_invert_stem_batch_dev";
+  REQUIRE(n_songs >= 0 && (songs || n_songs == 0), "%s: bad argument (songs %p, n_songs %d)", fn, (void *)songs, n_songs);
+  std::vector<EnsInvSong> tab;
+  int64_t frames = 0, fold_blocks = 0;
+  for (int i = 0; i < n_songs; ++i) {   // nothing is enqueued, and no n_out written, unless every song is valid
+    const asx_invert_song &g = songs[i];
+    char who[32];
+    snprintf(who, sizeof(who), "song %d: ", i);
+    int T = 0;
+    CHK(ens_invert_check(fn, who, g.mix_dev, g.stem_dev, g.n_samples, (int)g.stem_layout, g.out_dev, g.out_capacity, &T));
+    if (T < 2) continue;
+    const int64_t n_out = (int64_t)ENS_PLAN_HOP * (T - 1);
+    tab.push_back(EnsInvSong{g.mix_dev, g.stem_dev, g.out_dev, g.n_samples, n_out, frames, fold_blocks, T, (int32_t)(g.stem_layout == ASX_STEM_ROWS)});
+    frames += T;
+    fold_blocks += (n_out + 255) / 256;
+    REQUIRE(frames < ((int64_t)1 << 31) && fold_blocks < ((int64_t)1 << 31), "%s: the songs of one call make %lld / %lld workgroups of a stage (2^31 - 1 at most)",
+            fn, (long long)frames, (long long)fold_blocks);
+  }
+  for (int i = 0; i < n_songs; ++i) songs[i].n_out = (int64_t)ENS_PLAN_HOP * (songs[i].n_samples / ENS_PLAN_HOP);
+  if (tab.empty()) return ASX_OK;
+  CHK(ens_ctx(e));
+  EnsCtx &c = *e->ens;
+  const int nf = c.plan.n_fft, nh = c.plan.nh, hop = ENS_PLAN_HOP, n_tab = (int)tab.size();
+  const size_t tab_bytes = tab.size() * sizeof(EnsInvSong);
+  if (c.staged) HIPCHK(hipEventSynchronize(c.staged));   // the last call's copies out of the staging area have run
+  else HIPCHK(hipEventCreateWithFlags(&c.staged, hipEventDisableTiming));
+  CHK(c.stage.ensure(tab_bytes));
+  CHK(c.isongs.ensure(tab_bytes));
+  CHK(c.frames.ensure((size_t)frames * 2 * nf * 4));
+  memcpy(c.stage.p, tab.data(), tab_bytes);
+  HIPCHK(hipMemcpyAsync(c.isongs.p, c.stage.p, tab_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(c.staged, s));
+  const EnsInvSong *ds = reinterpret_cast<const EnsInvSong *>(c.isongs.p);
+  const size_t lds = ((size_t)nh * 2 + (size_t)(nh + 1) * 2) * sizeof(float2);
+  CHK(timed(e, ASX_PROF_STFT, 0.0, 4.0 * 2.0 * frames * nf, s, [&]() {
+    hipLaunchKernelGGL(ens_invert_pool_kernel, dim3((unsigned)frames, 2), dim3(256), lds, s, ds, n_tab, scale, hop, c.frames.f(), c.window.f(),
+                       reinterpret_cast<const float2 *>(c.tw.p), c.plan);
+  }));
+  return timed(e, ASX_PROF_OLA, 0.0, 4.0 * 2.0 * frames * nf, s, [&]() {
+    hipLaunchKernelGGL(ens_invert_pool_fold_kernel, dim3((unsigned)fold_blocks), dim3(256), 0, s, ds, n_tab, (const float *)c.frames.f(),
+                       (const float *)c.window.f(), nf, hop);
+  });
 }
 
 // ---- a pool of (file, stem group) jobs ------------------------------------------------------------------------------------

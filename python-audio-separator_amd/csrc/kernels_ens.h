@@ -279,16 +279,16 @@ __global__ __launch_bounds__(256) void ens_fft_kernel(const float *__restrict__ 
                 (int)gridDim.x, frames, window, tw, p, lds);
 }
 
-// invert_audio (spec_utils.py:557-571): v = Y - max(|X|, |Y|) * exp(j angle(X)); invert_stem returns -istft(v)
-__global__ __launch_bounds__(256) void ens_invert_kernel(const float *__restrict__ mix, const float *__restrict__ stem, int64_t n,
-                                                         int hop, float *__restrict__ frames, const float *__restrict__ window,
-                                                         const float2 *__restrict__ tw, FftPlan p) {
-  extern __shared__ float2 lds[];
+// invert_audio (spec_utils.py:557-571): v = Y - max(|X|, |Y|) * exp(j angle(X)); invert_stem returns -istft(v).  Frame t of one channel
+// of n samples -> dst[0 .. n_fft).  ldm(q) / lds_(q): sample q of the mix / of the stem.  LDS: bufA, bufB (nh each), X, Y (nh + 1 each).
+template <class LoadMix, class LoadStem>
+__device__ __forceinline__ void ens_invert_frame(LoadMix ldm, LoadStem lds_, int64_t n, int t, int hop, float *__restrict__ dst,
+                                                 const float *__restrict__ window, const float2 *__restrict__ tw, const FftPlan &p,
+                                                 float2 *lds) {
   const int nh = p.nh;
   float2 *bufA = lds, *bufB = lds + nh, *X = lds + 2 * nh, *Y = X + (nh + 1);
-  const int t = blockIdx.x, ch = blockIdx.y, T = gridDim.x;
-  ens_frame_spectrum(mix, n, ch, t, hop, window, tw, p, bufA, bufB, X);
-  ens_frame_spectrum(stem, n, ch, t, hop, window, tw, p, bufA, bufB, Y);
+  ens_frame_spectrum_of(ldm, n, t, hop, window, tw, p, bufA, bufB, X);
+  ens_frame_spectrum_of(lds_, n, t, hop, window, tw, p, bufA, bufB, Y);
   for (int b = threadIdx.x; b <= nh; b += blockDim.x) {
     const float2 x = X[b], y = Y[b];
     const float xm = hypotf(x.x, x.y), ym = hypotf(y.x, y.y);
@@ -297,7 +297,17 @@ __global__ __launch_bounds__(256) void ens_invert_kernel(const float *__restrict
     Y[b] = make_float2(y.x - mm * cosf(ang), y.y - mm * sinf(ang));
   }
   __syncthreads();
-  ens_inverse_frame(Y, frames + ((int64_t)ch * T + t) * p.n_fft, window, tw, p, bufA, bufB, -1.0f);
+  ens_inverse_frame(Y, dst, window, tw, p, bufA, bufB, -1.0f);
+}
+// over planar mix and stem [2, n]: grid = (T, 2), frames [2, T, n_fft]
+__global__ __launch_bounds__(256) void ens_invert_kernel(const float *__restrict__ mix, const float *__restrict__ stem, int64_t n,
+                                                         int hop, float *__restrict__ frames, const float *__restrict__ window,
+                                                         const float2 *__restrict__ tw, FftPlan p) {
+  extern __shared__ float2 lds[];
+  const int t = blockIdx.x, ch = blockIdx.y, T = gridDim.x;
+  const float *x = mix + (int64_t)ch * n, *y = stem + (int64_t)ch * n;
+  ens_invert_frame([&](int64_t q) { return x[q]; }, [&](int64_t q) { return y[q]; }, n, t, hop, frames + ((int64_t)ch * T + t) * p.n_fft,
+                   window, tw, p, lds);
 }
 
 // ---- a pool of (file, stem group) jobs: asx_ensemble_batch_dev ---------------------------------------------------------------
@@ -335,8 +345,8 @@ __device__ __forceinline__ float ens_pool_load(const EnsPoolSrc &s, const EnsSlo
 }
 
 // the last job whose first workgroup (or frame) of this stage is <= x
-template <int64_t EnsPoolJob::*FIRST>
-__device__ __forceinline__ int ens_pool_find(const EnsPoolJob *__restrict__ jobs, int n_jobs, int64_t x) {
+template <class Job, int64_t Job::*FIRST>
+__device__ __forceinline__ int ens_pool_find(const Job *__restrict__ jobs, int n_jobs, int64_t x) {
   int lo = 0, hi = n_jobs - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -356,7 +366,7 @@ __global__ __launch_bounds__(256) void ens_pool_peak_kernel(const EnsPoolSrc *__
 // results formed per sample: the wave algorithms, ensemble_wav's row copy (sel [n_jobs, 2]) and a lone contributor's slot image
 __global__ __launch_bounds__(256) void ens_pool_wave_kernel(const EnsPoolJob *__restrict__ jobs, int n_jobs, int alg, EnsSlotEdge ed,
                                                             const int *__restrict__ sel) {
-  const int j = ens_pool_find<&EnsPoolJob::wave_blk0>(jobs, n_jobs, blockIdx.x);
+  const int j = ens_pool_find<EnsPoolJob, &EnsPoolJob::wave_blk0>(jobs, n_jobs, blockIdx.x);
   const EnsPoolJob &jb = jobs[j];
   const int64_t N = jb.n_out;
   const int64_t i = ((int64_t)blockIdx.x - jb.wave_blk0) * 256 + threadIdx.x;
@@ -391,7 +401,7 @@ __global__ __launch_bounds__(256) void ens_pool_fft_kernel(const EnsPoolJob *__r
                                                            float *__restrict__ frames, const float *__restrict__ window,
                                                            const float2 *__restrict__ tw, FftPlan p) {
   extern __shared__ float2 lds[];
-  const EnsPoolJob &jb = jobs[ens_pool_find<&EnsPoolJob::frame0>(jobs, n_jobs, blockIdx.x)];
+  const EnsPoolJob &jb = jobs[ens_pool_find<EnsPoolJob, &EnsPoolJob::frame0>(jobs, n_jobs, blockIdx.x)];
   const int t = (int)((int64_t)blockIdx.x - jb.frame0), ch = blockIdx.y;
   ens_fft_frame([&](int k, int64_t q) { return ens_pool_load(jb.src[k], ed, ch, q); }, jb.K, jb.n_max, alg, jb.w, jb.wsum, hop, t, ch, jb.T,
                 frames + jb.frame0 * 2 * p.n_fft, window, tw, p, lds);
@@ -402,7 +412,7 @@ __global__ __launch_bounds__(256) void ens_pool_fft_kernel(const EnsPoolJob *__r
 // once -- the value the single call's host table holds there (0 where no frame reaches).
 __global__ __launch_bounds__(256) void ens_pool_fold_kernel(const EnsPoolJob *__restrict__ jobs, int n_jobs, const float *__restrict__ frames,
                                                             const float *__restrict__ window, int n_fft, int hop) {
-  const EnsPoolJob &jb = jobs[ens_pool_find<&EnsPoolJob::fold_blk0>(jobs, n_jobs, blockIdx.x)];
+  const EnsPoolJob &jb = jobs[ens_pool_find<EnsPoolJob, &EnsPoolJob::fold_blk0>(jobs, n_jobs, blockIdx.x)];
   const int64_t len = jb.n_out;
   const int64_t i = ((int64_t)blockIdx.x - jb.fold_blk0) * 256 + threadIdx.x;
   if (i >= len) return;
@@ -418,6 +428,83 @@ __global__ __launch_bounds__(256) void ens_pool_fold_kernel(const EnsPoolJob *__
   const float *fr = frames + jb.frame0 * 2 * n_fft;
   jb.out[i] = ola_sample(fr, n_fft, hop, m, t_lo, t_hi, s);
   jb.out[len + i] = ola_sample(fr + (int64_t)jb.T * n_fft, n_fft, hop, m, t_lo, t_hi, s);
+}
+
+// ---- invert_stem on arrays in HBM: asx_invert_stem_dev and its pooled form asx_invert_stem_batch_dev ---------------------------
+// The mix is planar [2, n]; the stem is planar or rows [n, 2] and is scaled as it is read (MDXSeparator hands over
+// primary * compensate); the result is rows [n_out, 2], n_out = hop * (T - 1).  Two stages -- ens_invert_frame per (frame, channel),
+// then the fold -- each ONE launch: the single form passes its song by value, the pooled form finds a workgroup's song in a device
+// table (its first frame / first fold workgroup of the launch, ascending; only songs of at least two frames are in it).  Both run
+// ens_invert_song_frame / ens_invert_song_fold, so a song's bits do not depend on the form or on its neighbours.
+struct EnsInvSong {
+  const float *mix;            // planar [2, n]
+  const float *stem;           // planar [2, n] or rows [n, 2]
+  float *out;                  // rows [n_out, 2]
+  int64_t n, n_out;
+  int64_t frame0, fold_blk0;   // its first frame / fold workgroup in the launch; its inverse frames are [2, T, n_fft] from frame0 * 2 * n_fft
+  int32_t T, rows;
+};
+
+// sample q of channel ch of the stem, times `scale`: numpy's float32 (primary * compensate), one rounding.  What follows is the product
+// with the window -- a multiplication, so there is no addition this one could be contracted with; contraction is off all the same.
+__device__ __forceinline__ float ens_invert_stem_value(const EnsInvSong &sg, int ch, int64_t q, float scale) {
+#pragma clang fp contract(off)
+  const float x = sg.rows ? sg.stem[2 * q + ch] : sg.stem[(int64_t)ch * sg.n + q];
+  return x * scale;
+}
+
+__device__ __forceinline__ void ens_invert_song_frame(const EnsInvSong &sg, int t, int ch, float scale, int hop, float *__restrict__ frames,
+                                                      const float *__restrict__ window, const float2 *__restrict__ tw, const FftPlan &p,
+                                                      float2 *lds) {
+  const float *x = sg.mix + (int64_t)ch * sg.n;
+  ens_invert_frame([&](int64_t q) { return x[q]; }, [&](int64_t q) { return ens_invert_stem_value(sg, ch, q, scale); }, sg.n, t, hop,
+                   frames + ((sg.frame0 * 2 + (int64_t)ch * sg.T) + t) * p.n_fft, window, tw, p, lds);
+}
+
+// ens_pool_fold_kernel's fold (the single host call's vr_ola_kernel sums over the window-sum-square formed here), written as rows
+__device__ __forceinline__ void ens_invert_song_fold(const EnsInvSong &sg, int64_t blk, const float *__restrict__ frames,
+                                                     const float *__restrict__ window, int n_fft, int hop) {
+  const int64_t len = sg.n_out;
+  const int64_t i = (blk - sg.fold_blk0) * 256 + threadIdx.x;
+  if (i >= len) return;
+  const int64_t m = i + n_fft / 2;
+  int64_t t_lo, t_hi;
+  ola_frame_range(m, n_fft, hop, sg.T, &t_lo, &t_hi);
+  double ss = 0.0;
+  for (int64_t t = t_lo; t <= t_hi; ++t) {
+    const double w = (double)window[m - t * hop];
+    ss += w * w;
+  }
+  const float s = (float)ss;
+  const float *fr = frames + sg.frame0 * 2 * n_fft;
+  sg.out[2 * i] = ola_sample(fr, n_fft, hop, m, t_lo, t_hi, s);
+  sg.out[2 * i + 1] = ola_sample(fr + (int64_t)sg.T * n_fft, n_fft, hop, m, t_lo, t_hi, s);
+}
+
+// one song: grid = (T, 2), then ((n_out + 255) / 256)
+__global__ __launch_bounds__(256) void ens_invert_dev_kernel(EnsInvSong sg, float scale, int hop, float *__restrict__ frames,
+                                                             const float *__restrict__ window, const float2 *__restrict__ tw, FftPlan p) {
+  extern __shared__ float2 lds[];
+  ens_invert_song_frame(sg, (int)blockIdx.x, (int)blockIdx.y, scale, hop, frames, window, tw, p, lds);
+}
+__global__ __launch_bounds__(256) void ens_invert_dev_fold_kernel(EnsInvSong sg, const float *__restrict__ frames,
+                                                                  const float *__restrict__ window, int n_fft, int hop) {
+  ens_invert_song_fold(sg, blockIdx.x, frames, window, n_fft, hop);
+}
+
+// a pool of songs: grid = (frames of all songs, 2), then (fold workgroups of all songs)
+__global__ __launch_bounds__(256) void ens_invert_pool_kernel(const EnsInvSong *__restrict__ songs, int n_songs, float scale, int hop,
+                                                              float *__restrict__ frames, const float *__restrict__ window,
+                                                              const float2 *__restrict__ tw, FftPlan p) {
+  extern __shared__ float2 lds[];
+  const EnsInvSong &sg = songs[ens_pool_find<EnsInvSong, &EnsInvSong::frame0>(songs, n_songs, blockIdx.x)];
+  ens_invert_song_frame(sg, (int)((int64_t)blockIdx.x - sg.frame0), (int)blockIdx.y, scale, hop, frames, window, tw, p, lds);
+}
+__global__ __launch_bounds__(256) void ens_invert_pool_fold_kernel(const EnsInvSong *__restrict__ songs, int n_songs,
+                                                                   const float *__restrict__ frames, const float *__restrict__ window,
+                                                                   int n_fft, int hop) {
+  const EnsInvSong &sg = songs[ens_pool_find<EnsInvSong, &EnsInvSong::fold_blk0>(songs, n_songs, blockIdx.x)];
+  ens_invert_song_fold(sg, blockIdx.x, frames, window, n_fft, hop);
 }
 
 }  // namespace asx

@@ -280,7 +280,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_resample_rational", "asx_resample_rational_dev", "asx_op_hd_lstm_layer", "asx_op_hd_lstm_frames", "asx_op_vr_lstm",
            "asx_op_vr_lstm_layout", "asx_flac_plan", "asx_flac_encode", "asx_flac_encode_dev",
            "asx_flac_decode_plan", "asx_flac_decode_scan_dev", "asx_flac_decode_finish_dev", "asx_flac_decode",
-           "asx_flac_plan_pcm", "asx_flac_encode_pcm", "asx_flac_encode_pcm_dev", "asx_pcm_encode", "asx_pcm_encode_dev"]
+           "asx_flac_plan_pcm", "asx_flac_encode_pcm", "asx_flac_encode_pcm_dev", "asx_pcm_encode", "asx_pcm_encode_dev",
+           "asx_invert_stem_dev", "asx_invert_stem_batch_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -316,7 +317,12 @@ class _EnsJob(C.Structure):        # struct asx_ens_job
                 ("peak_after", C.c_float * ENS_MAX_K)]
 
 
-VR_POOL_SEGMENTS = 16              # ASX_VR_POOL_SEGMENTS: songs one gather / scatter launch of a pooled VR pass serves
+class _InvertSong(C.Structure):    # struct asx_invert_song
+    _fields_ = [("mix_dev", C.c_void_p), ("stem_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_samples", C.c_int64),
+                ("out_capacity", C.c_int64), ("n_out", C.c_int64), ("stem_layout", C.c_int32)]
+
+
+VR_POOL_SEGMENTS = 16             # ASX_VR_POOL_SEGMENTS: songs one gather / scatter launch of a pooled VR pass serves
 
 
 class _SongStems(C.Structure):     # struct asx_song_stems
@@ -438,6 +444,8 @@ def load_library():
     lib.asx_ensemble.argtypes = [vp, _FP, i32, i64, i32, C.POINTER(C.c_double), _FP, C.POINTER(i64)]
     lib.asx_ensemble_dev.argtypes = [vp, vp, i32, i64, i32, C.POINTER(C.c_double), vp, C.POINTER(i64), vp]
     lib.asx_invert_stem.argtypes = [vp, _FP, _FP, i64, _FP, C.POINTER(i64)]
+    lib.asx_invert_stem_dev.argtypes = [vp, vp, vp, i64, i32, C.c_float, vp, i64, C.POINTER(i64), vp]
+    lib.asx_invert_stem_batch_dev.argtypes = [vp, C.POINTER(_InvertSong), i32, C.c_float, vp]
     lib.asx_ensemble_batch_dev.argtypes = [vp, C.POINTER(_EnsJob), i32, i32, C.POINTER(C.c_double), i32, i32, C.c_float, C.c_float, i32,
                                            C.c_double, vp]
     lib.asx_ensemble_slot_dev.argtypes = [vp, vp, i64, i32, C.c_float, C.c_float, i32, i32, vp, i32, i64, _FP, vp]
@@ -1406,6 +1414,27 @@ class Engine:
         n_out = C.c_int64()
         self._check(self._lib.asx_invert_stem(self._h, _ptr(m), _ptr(st), n, _ptr(out), C.byref(n_out)))
         return np.ascontiguousarray(out.reshape(-1)[: 2 * n_out.value].reshape(2, n_out.value).T)
+
+    def invert_stem_dev(self, mix_ptr: int, stem_ptr: int, n_samples: int, stem_layout: str, stem_scale: float, out_ptr: int,
+                        out_capacity: int, stream: int = 0) -> int:
+        """asx_invert_stem_dev: spec_utils.invert_stem(mix, stem * stem_scale) with every array in HBM.  ``mix`` planar [2, n],
+        ``stem`` "planar" [2, n] or "rows" [n, 2], ``out`` rows with room for [out_capacity, 2].  Returns n_out =
+        1024 * (n // 1024); only enqueues work on ``stream``."""
+        n_out = C.c_int64()
+        self._check(self._lib.asx_invert_stem_dev(self._h, mix_ptr or None, stem_ptr or None, int(n_samples), self.SLOT_LAYOUTS[stem_layout],
+                                                  float(stem_scale), out_ptr or None, int(out_capacity), C.byref(n_out), stream or None))
+        return int(n_out.value)
+
+    def invert_stem_batch_dev(self, songs, stem_scale: float, stream: int = 0) -> list:
+        """asx_invert_stem_batch_dev: ``invert_stem_dev`` for a list of ``(mix_ptr, stem_ptr, n_samples, stem_layout, out_ptr,
+        out_capacity)`` with one launch per stage over all songs; every result equals the single call's bit for bit.  Returns the
+        list of n_out."""
+        songs = list(songs)
+        arr = (_InvertSong * max(1, len(songs)))()
+        for i, (mix_ptr, stem_ptr, n, layout, out_ptr, capacity) in enumerate(songs):
+            arr[i] = _InvertSong(mix_ptr or None, stem_ptr or None, out_ptr or None, int(n), int(capacity), 0, self.SLOT_LAYOUTS[layout])
+        self._check(self._lib.asx_invert_stem_batch_dev(self._h, arr, len(songs), float(stem_scale), stream or None))
+        return [int(arr[i].n_out) for i in range(len(songs))]
 
     def debug_fetch(self, name: str, shape) -> np.ndarray:
         out = np.empty(shape, np.float32)
