@@ -787,6 +787,7 @@ int asx_invert_stem_batch_dev(asx_engine *e, asx_invert_song *songs, int32_t n_s
  * "wino6_launches" (conv_wino6_kernel: Winograd F(2x2,3x3) on the 16-bit pipe), "wino6h_launches" (those on the fp16 x 3 arithmetic),
  * "conv3h_launches" (ABI 7: conv3h_kernel, the direct fp16 x 3 convolution of the 48-channel level),
  * "conv3h_fin_launches" (those of them in the fused-input form, option "conv_fuse_input": one per net pass where it applies),
+ * "conv3h_tiled_launches" (additive: those of them with a tile-order input or output, option "conv3h_tiled"),
  * "down6_launches" / "up6_launches" (ABI 7: conv_down6_kernel / conv_up6_kernel, the level-change convs on the 16-bit matrix pipe),
  * "hd_rounds" (ABI 7: rounds of chunk groups the Demucs v3 forward has run -- the groups of a round share the BLSTM launches),
  * "vr_net_passes" (ABI 7, additive: passes of the VR net, CascadedASPPNet or CascadedNet, on a batch of patches -- asx_vr_separate_batch_dev runs
@@ -817,6 +818,10 @@ int asx_run_model(asx_engine *e, const float *wave_host, int32_t batch, float *o
  *   op = "down"     w [cout,cin,2,2]  b [cout]   stride 2      -> relu(conv(x)+b)         [B,cout,T/2,F/2]
  *   op = "up"       w [cin,cout,2,2]  b [cout]   stride 2, aux = skip [B,cout,2T,2F]  -> relu(convT(x)+b)*skip
  *   op = "conv1x1"  w [cout,cin]      b [cout]
+ *   op = "conv3x3_to_tiled" / "conv3x3_tiled" / "conv3x3_from_tiled": "conv3x3" with its output / both sides / its input in conv3h_kernel's tile
+ *        order (option "conv3h_tiled": every 48-channel slice laid out by Conv3hCfg::tl_off, csrc/kernels_conv3h.h; the slice's size is the planar
+ *        one's) -- the raw buffer goes to or comes from the host.  An error where conv3h_kernel does not take the layer, T % 4 != 0, or a sliced
+ *        layer would run with "conv3h_partial_scratch" = 0.
  * `relu` = 0 drops the ReLU of any of them (ABI 6; until ABI 5 only conv1x1 honoured it): the GroupNorm variant of the net runs its
  * convolutions bare.
  *   op = "tdf"      w [n,k] bias [n] with x viewed as rows of length k=F;
@@ -930,6 +935,11 @@ int asx_op_vr_lstm_layout(asx_engine *e, int32_t dir, const float *src_host, int
  * 1 (default) = balanced: whole planes to every group of workgroups while whole rounds remain, the leftover items cut into equal shares of tile
  * rows over all groups; 0 = the arithmetic walk (XCD x takes items x, x + 8, ..., a fixed segment of T per group).  A block's exponent is a
  * function of the block alone, so the results are equal bit for bit under either schedule and for a chunk alone or in any batch.
+ * "conv3h_tiled" (an option only, no environment variable): 1 (default) = the outputs of the first and second 3x3 conv of a TFC block, which
+ * only the block's next conv reads, are written and read in conv3h_kernel's tile order -- 1-KB blocks of sixteen channels x sixteen pixels in the
+ * consumer waves' own lane order, so a store instruction is 1 KB contiguous and a producer item one 128-byte line -- wherever the kernel runs both
+ * layers, T % 4 == 0 and no GroupNorm pass stands between them; 0 = planar.  The block's input and output, every other level and kernel, and the
+ * TFC-TDF v3 nets stay planar.  Same accumulators and values, another address: the results are equal bit for bit.  No buffer grows.
  * "conv_down_bf16x6" / "conv_up_bf16x6" (ABI 7; also ASX_DOWN6 / ASX_UP6): 1 (default) = the 2 x 2 / stride-2 convolutions between the levels
  * (mdxnet.py:66-72) and the transposed ones of the decoder with their `x *= skip` (mdxnet.py:80-86, 113) run conv_down6_kernel / conv_up6_kernel
  * (csrc/kernels_updown6.h) while "gemm_bf16x6" is on: the arithmetic of that option -- both fp32 operands split EXACTLY into three bf16 parts, six

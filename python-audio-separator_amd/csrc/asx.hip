@@ -98,6 +98,7 @@ static const struct EngineOption {
     {"conv_fuse_input", &asx_engine::conv_fuse_input, &EngineKnobs::conv_fuse_input, opt_onoff},
     {"conv3h_partial_scratch", &asx_engine::conv3h_ps, &EngineKnobs::conv3h_ps, opt_onoff},
     {"conv3h_walk", &asx_engine::conv3h_walk, &EngineKnobs::conv3h_walk, opt_onoff},
+    {"conv3h_tiled", &asx_engine::conv3h_tiled, &EngineKnobs::conv3h_tiled, opt_onoff},
     {"conv_down_bf16x6", &asx_engine::down6, &EngineKnobs::down6, opt_onoff},
     {"conv_up_bf16x6", &asx_engine::up6, &EngineKnobs::up6, opt_onoff},
     {"gemm_pair_images", &asx_engine::pair_images, &EngineKnobs::pair_images, opt_onoff,
@@ -1528,8 +1529,15 @@ int asx_op_conv(asx_engine *e, const char *op, const float *x_host, int32_t B, i
   HIPCHK(hipSetDevice(e->device));
   int kind;
   int to = t, fo = f;
+  // "conv3x3_to_tiled" / "conv3x3_tiled" / "conv3x3_from_tiled": the 3x3 layer with its output / both / its input in conv3h_kernel's tile
+  // order (Conv3hCfg::tl_off per 48-channel slice), the raw buffer handed to or taken from the host -- an error where conv3h_kernel does not take the layer
+  ConvView view;
   if (!strcmp(op, "conv3x3")) kind = CK_3X3;
-  else if (!strcmp(op, "down")) {
+  else if (!strcmp(op, "conv3x3_to_tiled") || !strcmp(op, "conv3x3_tiled") || !strcmp(op, "conv3x3_from_tiled")) {
+    kind = CK_3X3;
+    view.x_tiled = strcmp(op, "conv3x3_to_tiled") != 0;
+    view.y_tiled = strcmp(op, "conv3x3_from_tiled") != 0;
+  } else if (!strcmp(op, "down")) {
     kind = CK_DOWN;
     to = t / 2;
     fo = f / 2;
@@ -1555,7 +1563,7 @@ int asx_op_conv(asx_engine *e, const char *op, const float *x_host, int32_t B, i
   if (kind == CK_UP) CHK(to_dev(dskip, aux_host, ny));
   CHK(e->c3h_ps.ensure(conv3h_ps_need(L, B, t, f)));   // (the nets size it with their workspaces; to_host below waits before anything else can regrow it)
   CHK(conv3h_walk_ensure(e, L, B, t, f));
-  CHK(conv_launch(e, L, dx.f(), dskip.f(), dy.f(), B, t, f, nullptr));
+  CHK(conv_launch(e, L, dx.f(), dskip.f(), dy.f(), B, t, f, nullptr, view));
   CHK(to_host(y_host, dy, ny));
   return ASX_OK;
 }
@@ -2685,6 +2693,7 @@ int asx_counter(const asx_engine *e, const char *name, int64_t *out) {
   else if (nm == "wino6h_launches") *out = (int64_t)g_wino6h_launches.load();
   else if (nm == "conv3h_launches") *out = (int64_t)g_conv3h_launches.load();
   else if (nm == "conv3h_fin_launches") *out = (int64_t)g_conv3h_fin_launches.load();
+  else if (nm == "conv3h_tiled_launches") *out = (int64_t)g_conv3h_tiled_launches.load();
   else if (nm == "tdf3_pair_image_launches") *out = (int64_t)g_tdf3ps_launches.load();
   else if (nm == "down6_launches") *out = (int64_t)g_down6_launches.load();
   else if (nm == "up6_launches") *out = (int64_t)g_up6_launches.load();

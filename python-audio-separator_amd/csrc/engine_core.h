@@ -289,6 +289,11 @@ struct asx_engine {
   // all groups; 0: the arithmetic walk (XCD x takes items x, x + 8, ..., a fixed segment of T per group), through the same table path.  The
   // results are equal bit for bit: a block's exponent does not depend on the walk.  asx_set_option("conv3h_walk", n); no environment variable.
   int conv3h_walk = 1;
+  // 1 (default): the outputs of the first and second 3x3 conv of a TFC block -- read by the next conv of the block and by nothing else -- travel
+  // in conv3h_kernel's TILE ORDER (Conv3hCfg::tl_off: 1-KB blocks of sixteen channels x sixteen pixels; template flags XT / YT) wherever the
+  // kernel runs both layers, T % 4 == 0 and no GroupNorm pass stands between them.  0: planar, as every other tensor.  Same accumulators, same
+  // values, another address: the results are equal bit for bit.  asx_set_option("conv3h_tiled", n); no environment variable.
+  int conv3h_tiled = 1;
   // 1 (default): the net's 1x1 input conv (4 -> 48 channels, folded BatchNorm, ReLU) is computed by the producer waves of the first TFC conv's
   // conv3h_kernel launch (its fused-input form) instead of in a launch of its own: the 48-channel level-0 activation is never written to
   // memory and read back.  0: two launches.  Only where the first 3x3 layer runs conv3h_kernel at 48 channels and the net uses BatchNorm.

@@ -242,6 +242,7 @@ static std::atomic<long long> g_wino6_launches{0};   // launches of conv_wino6_k
 static std::atomic<long long> g_wino6h_launches{0};  // ... of which on the fp16 x 3 arithmetic
 static std::atomic<long long> g_conv3h_launches{0};  // launches of conv3h_kernel (kernels_conv3h.h)
 static std::atomic<long long> g_conv3h_fin_launches{0};   // ... of which in the fused-input form (the net's 1x1 input conv computed by the producers)
+static std::atomic<long long> g_conv3h_tiled_launches{0}; // ... of which with a tile-order input or output (option "conv3h_tiled")
 static std::atomic<long long> g_down6_launches{0};   // launches of conv_down6_kernel (kernels_updown6.h)
 static std::atomic<long long> g_up6_launches{0};     // launches of conv_up6_kernel
 
@@ -257,6 +258,9 @@ struct ConvView {
   // fin_x [B, 4, T, F] (dense), formed in the kernel's producer waves.  The caller has asked conv3h_takes first: no other kernel has the form.
   const ConvLayer *fin = nullptr;
   const float *fin_x = nullptr;
+  // tile order (Conv3hCfg::tl_off; option "conv3h_tiled"): every 48-channel slice of x / of y is in conv3h_kernel's tile order instead of planar.
+  // The caller has asked conv3h_tiled_ok first: no other kernel reads or writes the layout.
+  bool x_tiled = false, y_tiled = false;
 };
 
 // does conv_launch run this 3x3 layer on conv3h_kernel?  (`dma`: F % 4 == 0, the input 16-byte aligned with a batch stride of whole float4, LDS-DMA not switched off)
@@ -269,6 +273,10 @@ static bool conv3h_takes(const asx_engine *e, const ConvLayer &L, bool dma, cons
          res == nullptr && (act == ACT_RELU || act == ACT_NONE) && F % 32 == 0 && (int64_t)Conv3hCfg::C * T * F < ((int64_t)1 << 29) &&
          y_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
 }
+
+// may a layer that conv3h_takes read or write tile order at this shape?  (whole tile rows; a sliced layer only through the scratch: the planar
+// accumulate mode adds to the output tensor itself)
+static bool conv3h_tiled_ok(const asx_engine *e, const ConvLayer &L, int T) { return T % 4 == 0 && (L.cin == Conv3hCfg::C || e->conv3h_ps > 0); }
 
 // bytes of partial-sum scratch (asx_engine::c3h_ps) a conv_launch of this layer on B items of T x F may use: whoever sizes the workspaces of a
 // net asks for every 3x3 layer and keeps the maximum (whatever the options say at that moment: they may change between two forwards)
@@ -368,6 +376,8 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
   const bool dma = (F % 4 == 0) && ((reinterpret_cast<uintptr_t>(v.fin ? v.fin_x : x) & 15) == 0) && (a.x_bstride % 4 == 0) && !knobs().no_dma;
   REQUIRE(!v.fin || (v.fin->w1f.p != nullptr && L.cin == Conv3hCfg::C && conv3h_takes(e, L, dma, v.res, a.act, T, F, a.y_bstride, y)),
           "fused-input 3x3 conv: the layer does not run conv3h_kernel");
+  REQUIRE(!(v.x_tiled || v.y_tiled) || (conv3h_takes(e, L, dma, v.res, a.act, T, F, a.y_bstride, y) && conv3h_tiled_ok(e, L, T) && !(v.x_tiled && v.fin)),
+          "tile-order 3x3 conv: the layer does not run conv3h_kernel in a form that has the layout");
   const ConvArgs &d = a;
 #ifdef ASX_EXPERIMENTAL_KERNELS   // measured-and-rejected generations (profiles/NOTES.md): python build.py --experimental, or ASX_EXPERIMENTAL=1 in the environment of the build
   if (L.kind == CK_3X3 && e->winograd == 3 && e->winos == 1 && dma && L.wus.p != nullptr && a.Fo % 32 == 0 && v.res == nullptr &&
@@ -426,6 +436,28 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     grant_lds(&conv3h_kernel<0, false, false, 1>, Conv3hCfg::LDS_BYTES);
     grant_lds(&conv3h_kernel<0, false, false, 2>, Conv3hCfg::LDS_BYTES);
     grant_lds(&conv3h_kernel<0, false, false, 3>, Conv3hCfg::LDS_BYTES);
+    // one launch in the layouts the view names (XT / YT of the kernel: compile-time)
+    auto go = [&](auto finc, auto psc, const Conv3hArgs &ca, bool yt) {
+      constexpr bool FIN = decltype(finc)::value;
+      constexpr int PS = decltype(psc)::value;
+      auto one = [&](auto kern) {
+        grant_lds(kern, Conv3hCfg::LDS_BYTES);
+        hipLaunchKernelGGL(kern, dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
+      };
+      if constexpr (FIN) {
+        if (yt) one(&conv3h_kernel<0, false, true, 0, false, true>);
+        else one(&conv3h_kernel<0, false, true>);
+      } else if constexpr ((PS & 2) != 0) {
+        if (v.x_tiled) one(&conv3h_kernel<0, false, false, PS, true, false>);
+        else one(&conv3h_kernel<0, false, false, PS>);
+      } else {
+        if (v.x_tiled && yt) one(&conv3h_kernel<0, false, false, PS, true, true>);
+        else if (v.x_tiled) one(&conv3h_kernel<0, false, false, PS, true, false>);
+        else if (yt) one(&conv3h_kernel<0, false, false, PS, false, true>);
+        else one(&conv3h_kernel<0, false, false, PS>);
+      }
+      if (v.x_tiled || yt) g_conv3h_tiled_launches.fetch_add(1);
+    };
     const int64_t plane = (int64_t)T * F;
     const bool ps = e->conv3h_ps > 0 && nb > 1;
     const int64_t ps_item = Conv3hCfg::ps_item_bytes(tilesT, tilesF);
@@ -459,13 +491,13 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
             ca.xin = v.fin_x;
             ca.xin_bstride = 4 * plane;
             ca.w1 = v.fin->w1f.f();
-            hipLaunchKernelGGL((conv3h_kernel<0, false, true>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
+            go(std::true_type{}, IntC<0>{}, ca, v.y_tiled);
             g_conv3h_fin_launches.fetch_add(1);
-          } else if (ps && ib == 0) hipLaunchKernelGGL((conv3h_kernel<0, false, false, 2>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);   // partial out
-          else if (ps && ib < nb - 1) hipLaunchKernelGGL((conv3h_kernel<0, false, false, 3>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);   // in and out, in place
-          else if (ps) hipLaunchKernelGGL((conv3h_kernel<0, false, false, 1>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);   // partial in, planar out
-          else if (ib > 0) hipLaunchKernelGGL((conv3h_kernel<0, true>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
-          else hipLaunchKernelGGL((conv3h_kernel<0, false>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);
+          } else if (ps && ib == 0) go(std::false_type{}, IntC<2>{}, ca, false);          // partial out
+          else if (ps && ib < nb - 1) go(std::false_type{}, IntC<3>{}, ca, false);        // in and out, in place
+          else if (ps) go(std::false_type{}, IntC<1>{}, ca, v.y_tiled);                   // partial in, final out (planar or tile order)
+          else if (ib > 0) hipLaunchKernelGGL((conv3h_kernel<0, true>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, ca);   // (never tile order: conv3h_tiled_ok)
+          else go(std::false_type{}, IntC<0>{}, ca, v.y_tiled);
           g_conv3h_launches.fetch_add(1);
         }
     });
@@ -1249,6 +1281,15 @@ static int block_forward(asx_engine *e, const Block &blk, float *&cur, float *de
   };
   const bool gn = e->net.norm == 1;
   const int64_t plane = (int64_t)blk.t * blk.f;
+  // Tile order between the block's 3x3 convs (option "conv3h_tiled"): the output of layer j is read by layer j + 1 and by nothing else, so where
+  // conv3h_kernel runs both it travels in the kernel's own layout (Conv3hCfg::tl_off).  The first conv's input and the last conv's output stay
+  // planar (TDF, skips, the level changes read them); with GroupNorm a planar norm pass stands between the convs.
+  auto c3h = [&](size_t j, const float *xin) {           // does layer j run conv3h_kernel here, in a form that has the layout?
+    const ConvLayer &L = blk.tfc[j];
+    const bool dma = blk.f % 4 == 0 && (reinterpret_cast<uintptr_t>(xin) & 15) == 0 && !knobs().no_dma;
+    return conv3h_takes(e, L, dma, nullptr, L.relu ? ACT_RELU : ACT_NONE, blk.t, blk.f, (int64_t)L.cout * plane, e->R[0].f()) && conv3h_tiled_ok(e, L, blk.t);
+  };
+  bool in_tiled = false;
   for (size_t j = 0; j < blk.tfc.size(); ++j) {
     float *out = next_free(cur, nullptr);
     ConvView v;
@@ -1256,6 +1297,9 @@ static int block_forward(asx_engine *e, const Block &blk, float *&cur, float *de
       v.fin = &e->first;
       v.fin_x = fin_x;
     }
+    v.x_tiled = in_tiled;
+    v.y_tiled = e->conv3h_tiled > 0 && !gn && j + 1 < blk.tfc.size() && (in_tiled || c3h(j, j == 0 && fin_x ? fin_x : cur)) && c3h(j + 1, out);
+    in_tiled = v.y_tiled;
     CHK(conv_launch(e, blk.tfc[j], cur, nullptr, out, B, blk.t, blk.f, s, v));
     if (gn) CHK(gn_launch(e, out, B, blk.c, plane, blk.tfc[j].gn_w, blk.tfc[j].gn_b, nullptr, nullptr, out, s));
     cur = out;

@@ -98,7 +98,34 @@ struct Conv3hCfg {
     return (int64_t)b * ps_item_bytes(tilesT, tilesF) + ps_wave_off(tilesT, strip, jt, r) + k * PS_STORE + lane * 16;
   }
 
-  // Stage plan of a consumer wave's tile.  A kernel row is four FULL stages (stage group sg: k groups 4 sg .. 4 sg + 3) and half a stage (k groups
+  // Tile order (template flags XT / YT of the kernel; engine option "conv3h_tiled"): the layout of a 48-channel slice that only this kernel
+  // writes AND reads -- the output of conv1 and conv2 of a TFC block.  One 1-KB block per (row t, 16-pixel tile f / 16, 16-channel tile c / 16),
+  // row major, the three channel tiles of a pixel tile side by side.  Inside a block the consumer's own lane order: lane g 16 + li (pixels
+  // 4 g .. 4 g + 3 of channel li of the tile) at lane 16 -- a consumer store instruction (one accumulator of one wave: sixteen channels x
+  // sixteen pixels) is one contiguous 1 KB with no lane swap, and the eight channels of a producer item (one pixel quad, channels 8 h .. 8 h + 7)
+  // are ONE aligned 128-byte line, TL_PIECE bytes apart.  A slice takes exactly the planar slice's bytes (T % 4 == 0, F % 32 == 0), so buffers,
+  // batch strides and slice offsets stay what they are.  (The other candidates -- the channel-in-group index outermost, eight lanes of a load
+  // on one line -- and their times, skeleton and kernel: DESIGN.md 6k, profiles/NOTES.md round 23.)
+  static constexpr int TL_BLOCK = 1024, TL_PIECE = 16;           // bytes per block; between the eight channels of a producer item
+  static constexpr int64_t tl_item_bytes(int T, int F) { return (int64_t)C * T * F * 4; }
+  static constexpr unsigned tl_block_off(int F, int t, int ftile, int n) { return ((unsigned)(t * (F / 16) + ftile) * 3u + (unsigned)n) * (unsigned)TL_BLOCK; }
+  static constexpr unsigned tl_in_block(int g, int ch) { return (unsigned)(g * 256 + ch * TL_PIECE); }   // pixel quad g, channel ch of the tile
+  static constexpr int64_t tl_off(int T, int F, int t, int f, int c) {   // byte offset of element (c, t, f) inside the slice
+    (void)T;
+    return (int64_t)tl_block_off(F, t, f / 16, c / 16) + tl_in_block((f % 16) / 4, c % 16) + (f % 4) * 4;
+  }
+  // consumer: lane (g = lane / 16, li = lane % 16) of store k = (channel tile k / 2, pixel tile k % 2) of the wave that owns row t of the tile at column f0
+  static constexpr unsigned tl_store_lane(int lane) { return tl_in_block(lane >> 4, lane & 15); }
+  static constexpr unsigned tl_store_off(int F, int t, int f0, int k) { return tl_block_off(F, t, f0 / 16 + k % 2, k / 2); }
+  // producer, XT: item (row, 8-channel group cig, aligned quad q = columns f0 - 4 + 4 q ..) of the block at (row t1, column f0): a lane part and
+  // a wave-uniform part (unsigned arithmetic: rows and columns outside the image are never dereferenced -- the in-image predicate -- but computed)
+  static constexpr unsigned tl_fetch_lane(int F, int row, int cig, int q) {
+    const int fq = 4 * q - 4;                                       // -4 .. 32: pixel tile (fq >> 4) = -1 (left neighbour), 0, 1, 2 (right neighbour)
+    return ((unsigned)(row * (F / 16) + (fq >> 4)) * 3u + (unsigned)(cig >> 1)) * (unsigned)TL_BLOCK + tl_in_block((fq & 15) >> 2, (cig & 1) * 8);
+  }
+  static constexpr unsigned tl_fetch_org(int F, int t1, int f0) { return (unsigned)(t1 * (F / 16) + f0 / 16) * 3u * (unsigned)TL_BLOCK; }
+
+  // Stage plan of a consumer wave's tile. A kernel row is four FULL stages (stage group sg: k groups 4 sg .. 4 sg + 3) and half a stage (k groups
   // 16, 17: stage group 4, a half fragment in the weight image).  Two half stages whose input rows lie in the SAME four-row block (one exponent)
   // share one MERGED stage: lanes g < 2 carry row ky's k groups 16, 17 (x fragment and weight half fragment), lanes g >= 2 row kyb's -- the half
   // fragment's lane order puts k group 16 + (g & 1) at (lane & 31) * 16, so lanes 32..63 read kyb's half fragment where lanes 0..31 read ky's.
@@ -317,11 +344,20 @@ struct Conv3hFinRegs<true> {
 // INVARIANT: a launch with both bits reads and writes the SAME scratch in place, and a launch reads what the one before it wrote.  That is
 // safe because a lane only ever touches its own 16 bytes per (tile, store) -- loaded behind stage 7 of the tile, overwritten a step later --
 // and because the launches of one output slice walk identically: same B, T, F, tilesT, tilesF, bw and walk table (the launcher builds them from one place).
-template <int ABL = 0, bool ACC = false, bool FIN = false, int PS = 0>
+// XT / YT: the input slice a.x / the final output slice a.y is in TILE ORDER (Conv3hCfg::tl_off) instead of planar -- for the tensors between the
+// 3x3 convs of one TFC block, which nothing but this kernel touches (compile-time for the reason given at ACC).  Same accumulators, same lanes,
+// same values, another address.  XT changes `fetch` alone: the lane's item is what it was, its eight channels lie TL_PIECE bytes apart (one
+// 128-byte line) behind an offset from the map, and the in-image predicate is what it was -- a row outside [0, T) or a quad outside [0, F) enters
+// the ring as 0 whatever a neighbouring block holds.  YT changes the final epilogue alone: the values of the planar store (bias, partial in,
+// activation, in that order), every lane its own six quads as the partial-out form stores them -- 1 KB contiguous per instruction, no lane
+// swap.  XT never with FIN or ACC, YT never with ACC; a partial-out launch (PS & 2) writes no final output: YT means nothing there.
+template <int ABL = 0, bool ACC = false, bool FIN = false, int PS = 0, bool XT = false, bool YT = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3h_kernel(Conv3hArgs a) {
   using CFG = Conv3hCfg;
   constexpr bool PIN = (PS & 1) != 0, POUT = (PS & 2) != 0;
+  constexpr bool OWNQ = POUT || YT;                    // the epilogue stores the lane's own accumulator quads (no lane swap)
   static_assert(!(PS != 0 && (ACC || FIN)), "partial sums through the scratch: neither the planar accumulate mode nor the fused input");
+  static_assert(!(XT && (FIN || ACC)) && !(YT && (ACC || POUT)), "tile order: never the accumulate mode; the fused input has no input slice, a partial-out launch no final output");
   extern __shared__ float lds_f[];
   char *lds = reinterpret_cast<char *>(lds_f);
   const int tid = threadIdx.x;
@@ -366,6 +402,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int loff = (row * CFG::IW + 4 * q - 3) * CFG::PSTR + cig * 16;   // pixel 0 of the quad inside a block slot (window column 4 q - 3: never written for quad 0)
     const int goff = FIN ? (int)((int64_t)row * a.F + 4 * q)              // FIN: the four planes are shared by the channel groups
                          : (int)(((int64_t)cig * 8 * a.T + row) * a.F + 4 * q);  // floats from (channel 0, row 4 j + 1, column f0 - 4); < 2^29 (launcher)
+    const unsigned tl_lane = CFG::tl_fetch_lane(a.F, row, cig, q);        // XT: bytes from the block of (row 4 j + 1, pixel tile f0 / 16, channel tile 0)
     // four register sets: block m lives in set m % 4 (fetched in step m - 4, its maximum taken in step m - 2, split in step m - 1).
     // FIN: the four fetched sets are fr.rin; the 48-channel values exist from the maximum to the split: two sets, m % 2
     constexpr int NSET = FIN ? 2 : 4;
@@ -398,7 +435,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int org = t1 * a.F + (f0 - 4);
       // F % 4 == 0 and the quad is aligned: inside the row or outside as a whole
       const bool ok = item_ok && (unsigned)(t1 + row) < (unsigned)a.T && (unsigned)(f0 - 4 + 4 * q) < (unsigned)a.F;
-      const unsigned vo = ok ? (unsigned)(goff + org) * 4u : 0xfffffff0u;   // past num_records: the load returns 0
+      const unsigned vo = !ok ? 0xfffffff0u                                 // past num_records: the load returns 0
+                              : (XT ? tl_lane + CFG::tl_fetch_org(a.F, t1, f0) : (unsigned)(goff + org) * 4u);
       if constexpr (FIN) {
         fr.ok[S] = ok;
 #pragma unroll
@@ -407,7 +445,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           if constexpr ((ABL & 2) != 0) raw[S][j] = (f32x4){0.25f, 0.5f, 0.75f, 1.f};
-          else raw[S][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, (int)(j * TF * 4), 0));
+          else raw[S][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, XT ? j * CFG::TL_PIECE : (int)(j * TF * 4), 0));
         }
       }
     };
@@ -584,11 +622,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const unsigned ps_item = (unsigned)CFG::ps_item_bytes(a.tilesT, a.tilesF);
     // (partial out: never an activation -- a constant, no register)
     const float act_lo = !POUT && a.act == ACT_RELU ? 0.f : -__builtin_inff();
+    const int tl_lane = (int)CFG::tl_store_lane(lane);  // YT: the lane's 16 bytes inside a store's 1-KB block
 
     auto flush_one = [&](auto kc) {
       constexpr int K = decltype(kc)::value;
       if constexpr ((ABL & 4) == 0) {
         if constexpr (POUT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pend[K]), pend_rs, lane * 16, pend_vo + K * CFG::PS_STORE, (ABL & 512) ? 0 : 2);
+        else if constexpr (YT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pend[K]), pend_rs, tl_lane, pend_vo + ((K % 2) * 3 + K / 2) * CFG::TL_BLOCK, (ABL & 512) ? 0 : 2);
         else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pend[K]), pend_rs, pend_vo, soff[K], (ABL & 512) ? 0 : 2);
       } else {
         if (pend[K].x == 1.2345e-30f) a.y[0] = pend[K].y;   // keeps the arithmetic alive in the no-store build
@@ -608,9 +648,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       constexpr int K = decltype(kc)::value, c = K / 2;
       // exact power of two (|exponent| well inside the float range: weights and activations are) -- the same number either way
       const float sc = PS != 0 ? __builtin_ldexpf(wsc[c], -pend_e) : __builtin_ldexpf(1.0f, -(pend_e + ew[c]));
-      if constexpr (POUT) {
+      if constexpr (OWNQ) {
         // partial out: store k is the lane's own accumulator (channel tile c, pixel tile k % 2) -- the planar form's values (the `fmaxf` against
         // -inf included: it is what the planar form's intermediate launch does to a NaN), four fmas instead of eight and no lane swap
+        // YT (final output in tile order): the same store of the lane's own quad, with the launch's activation -- element by element the planar
+        // final store's fma, partial-in addition and `fmaxf`
         constexpr int qq = K % 2;
         f32x4 o = (f32x4){__builtin_fmaf(pacc[qq][c].x, sc, bz[c]), __builtin_fmaf(pacc[qq][c].y, sc, bz[c]), __builtin_fmaf(pacc[qq][c].z, sc, bz[c]),
                           __builtin_fmaf(pacc[qq][c].w, sc, bz[c])};
@@ -674,6 +716,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int cur_vo = (((li & 7) * a.T + tt) * a.F + f0 + ((li >> 3) * 4 + g) * 4) * 4;
         // the wave's 6 KB of the scratch: wave-uniform (a scalar offset of the loads and stores), the lane adds lane * 16 (cur_ok: strip < tilesF, tile row < tilesT)
         const int cur_ps = (int)CFG::ps_wave_off(a.tilesT, wk_strip, wk_t0 + j, wave);
+        const int cur_tl = (int)CFG::tl_store_off(a.F, tt, f0, 0);   // YT: the wave's row of blocks (wave-uniform; cur_ok: inside the slice)
         // rows of the tile: u = 0, 1 = the last two rows of the previous block, u = 2..5 = this block; wave r, kernel row ky reads u = r + ky
         const int sp = s3 == 0 ? 2 : s3 - 1;
         const int e_cur = __builtin_amdgcn_readfirstlane(exps[s3]), e_old = __builtin_amdgcn_readfirstlane(exps[sp]);
@@ -804,7 +847,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           pend_vo = cur_ps;
         } else {
           pend_rs = __builtin_amdgcn_make_buffer_rsrc(a.y + (int64_t)tb * a.y_bstride, 0, cur_ok ? plane_bytes : 0u, 0x00020000);
-          pend_vo = cur_vo;
+          pend_vo = YT ? cur_tl : cur_vo;
         }
         if constexpr ((ABL & 128) != 0) flush();
       } else {

@@ -4,15 +4,23 @@
 //   pattern 1: vertical walk, 4 new rows x  8 aligned quads (the strip's own line only: no halo columns)          -- what the edge lines cost
 //   pattern 2: horizontal walk, 6 rows x 8 aligned quads (own line only; halo rows fetched, halo columns kept from the neighbour tiles)
 //   pattern 3: as 0 with the 8-lane groups on ONE channel plane (lane quads contiguous)
+// Tile-order candidates for the tensors only conv3h_kernel touches (one 1-KB block per (row t, 16-pixel tile, 16-channel tile n), blocks at
+// ((t (F / 16) + f / 16) 3 + c / 16) 1024; T % 4 == 0, F % 32 == 0), correct addresses, halo quads included -- `micro_fetch tiled` runs them:
+//   pattern 4: layout A (inside a block: lane g 16 + li of the consumer at lane 16 -- an item's eight pieces are ONE 128-byte line), the kernel's lane -> item map
+//   pattern 5: layout B (piece e = c % 8 of item (g, h = (c % 16) / 8) at e 128 + g 32 + h 16), the kernel's lane -> item map (four lanes on 64 contiguous bytes)
+//   pattern 6: layout B, eight consecutive lanes = the (g, h) of one block: a load instruction finds them on ONE 128-byte line (halo items: lane pairs on 32 bytes)
+//   pattern 7: layout A with pattern 6's lane -> item map (eight lanes on eight consecutive lines)
+//   stores 6 / 7: the consumer's six quads through layout A / B, 1 KB contiguous per instruction, nontemporal
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/experimental/micro_fetch tools/experimental/micro_fetch.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP %s line %d\n", hipGetErrorString(e_), __LINE__); exit(2); } } while (0)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-struct Args { const float *x; float *y; float *sink; int B, T, F, pattern, stores; };   // stores: 0 none, 1 the kernel's (16 channels x 64 B per instruction), 2 = 8 channels x 128 B per instruction, 3 = as 1 nontemporal, 4 = as 2 nontemporal, 5 = 1 KB contiguous per instruction (ceiling, wrong addresses)
+struct Args { const float *x; float *y; float *sink; int B, T, F, pattern, stores; };   // stores: 0 none, 1 the kernel's (16 channels x 64 B per instruction), 2 = 8 channels x 128 B per instruction, 3 = as 1 nontemporal, 4 = as 2 nontemporal, 5 = 1 KB contiguous per instruction (ceiling, wrong addresses), 6 / 7 = tile order A / B
 
 __global__ __launch_bounds__(256) void k(Args a) {
   const int tid = threadIdx.x, wg = blockIdx.x;
@@ -20,7 +28,12 @@ __global__ __launch_bounds__(256) void k(Args a) {
   const unsigned plane_bytes = (unsigned)(48 * TF * 4);
   // item decode per pattern
   int row, cig, q; bool ok;
-  if (a.pattern == 0) {
+  const bool tiled = a.pattern >= 4, layB = a.pattern == 5 || a.pattern == 6;
+  if (a.pattern == 6 || a.pattern == 7) {
+    if (tid < 192) { const int grp = tid >> 3; q = 1 + (grp & 1) * 4 + ((tid >> 1) & 3); cig = 2 * ((grp >> 1) % 3) + (tid & 1); row = grp / 6; }
+    else { const int u = tid - 192, rest = u >> 2; q = ((u >> 1) & 1) ? 9 : 0; cig = 2 * (rest % 3) + (u & 1); row = (rest / 3) & 3; }
+    ok = tid < 240;
+  } else if (a.pattern == 0 || a.pattern == 4 || a.pattern == 5) {
     if (tid < 160) { q = (tid & 1) + 2 * ((tid >> 3) % 5); cig = (tid >> 1) & 3; row = tid / 40; }
     else { const int u = tid - 160; q = (u & 1) + 2 * ((u >> 3) % 5); cig = 4 + ((u >> 1) & 1); row = ((u >> 2) & 1) + 2 * (u / 40); }
     ok = tid < 240;
@@ -32,6 +45,8 @@ __global__ __launch_bounds__(256) void k(Args a) {
     q = 1 + (tid & 7); cig = (tid >> 3) % 6; row = tid / 48; ok = tid < 288;   // 6 rows: 288 items > 256 lanes: rows 0..4 here, row 5 by a second round below
   }
   const int goff = (int)(((int64_t)cig * 8 * a.T + row) * a.F + 4 * q);
+  // tile order: the item's eight pieces are jstride bytes apart, its first one toff bytes into the 1-KB block (t, f / 16, cig / 2)
+  const int jstride = !tiled ? (int)(TF * 4) : (layB ? 128 : 16);
   const int x = wg & 7, jw = wg >> 3;
   const int tilesT = a.T / 4, tilesF = a.F / 32, nbands = tilesF / 32;
   float acc = 0.f;
@@ -59,10 +74,14 @@ __global__ __launch_bounds__(256) void k(Args a) {
     __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x + (int64_t)b * 48 * TF), 0, plane_bytes, 0x00020000);
     const int org = t1 * a.F + (f0 - 4);
     const bool in = s < nsteps && ok && (unsigned)(t1 + row) < (unsigned)a.T && (unsigned)(f0 - 4 + 4 * q) < (unsigned)a.F;
-    const unsigned vo = in ? (unsigned)(goff + org) * 4u : 0xfffffff0u;
+    unsigned vo = in ? (unsigned)(goff + org) * 4u : 0xfffffff0u;
+    if (tiled && in) {
+      const int fc = f0 - 4 + 4 * q, g = (fc & 15) >> 2, h = cig & 1;
+      vo = (unsigned)(((t1 + row) * (a.F / 16) + (fc >> 4)) * 3 + (cig >> 1)) * 1024u + (unsigned)(layB ? g * 32 + h * 16 : g * 256 + h * 128);
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      raw[set][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, (int)(j * TF * 4), 0));
+      raw[set][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)vo, j * jstride, 0));
     if (a.pattern == 2) {   // sixth row: 48 items (6 groups x 8 quads) on lanes 0..47, 8 loads each -> emulate with 2 loads on lanes 0..191
       const int r5q = 1 + (tid & 7), r5c = (tid >> 3) % 24;     // 24 (channel-pair) x 8 quads = 192 lanes, 2 planes each
       const bool in5 = s < nsteps && tid < 192 && (unsigned)(t1 + 5) < (unsigned)a.T;
@@ -101,6 +120,14 @@ __global__ __launch_bounds__(256) void k(Args a) {
         if (a.stores == 2) __builtin_amdgcn_raw_buffer_store_b128((u32x4){1u, 2u, 3u, (unsigned)s}, rs, vo, (int)((c * 8 * TF) * 4), 0);
         else __builtin_amdgcn_raw_buffer_store_b128((u32x4){1u, 2u, 3u, (unsigned)s}, rs, vo, (int)((c * 8 * TF) * 4), 2);
       }
+    } else if (a.stores == 6 || a.stores == 7) {
+      // store (c, qq) = block (tt, f0 / 16 + qq, c): lane (g, li) at lane 16 (A) or at (li & 7) 128 + g 32 + (li >> 3) 16 (B)
+      const int vo = a.stores == 6 ? (tid & 63) * 16 : (li & 7) * 128 + g * 32 + (li >> 3) * 16;
+      const int blk = (tt * (a.F / 16) + f0 / 16) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int qq = 0; qq < 2; ++qq) __builtin_amdgcn_raw_buffer_store_b128((u32x4){1u, 2u, 3u, (unsigned)s}, rs, vo, (blk + qq * 3 + c) * 1024, 2);
     } else {
       const int l = tid & 63;
       const int vo = ((wave * 6) * 256 + l * 4) * 4 + ((tt * a.F + f0) % (a.T * a.F - 8192)) * 4 * 0 + (int)((((int64_t)s * 4 + wave) * 6 * 1024) % (int64_t)(plane_bytes - 65536));
@@ -125,8 +152,7 @@ int main(int argc, char **argv) {
   CK(hipMalloc(&x, n * 4 + 4096)); CK(hipMalloc(&y, n * 4 + 4096)); CK(hipMalloc(&sink, 4));
   CK(hipMemset(x, 0, n * 4));
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  for (int stores = 0; stores < 6; ++stores)
-    for (int pattern = 0; pattern < 2; ++pattern) {
+  auto run = [&](int pattern, int stores) {
       Args a{x, y, sink, B, T, F, pattern, stores};
       hipLaunchKernelGGL(k, dim3(256), dim3(256), 0, 0, a);
       CK(hipEventRecord(e0, 0));
@@ -135,6 +161,14 @@ int main(int argc, char **argv) {
       float ms; CK(hipEventElapsedTime(&ms, e0, e1)); ms /= 3;
       const double steps = 21.0 * 64;
       printf("pattern %d stores %d: %.3f ms per launch, %.2f us per step\n", pattern, stores, ms, ms * 1e3 / steps);
-    }
+  };
+  if (argc > 1 && !strcmp(argv[1], "tiled")) {   // today's pair and the tile-order candidates, three rounds in one process
+    static const int pairs[][2] = {{0, 0}, {0, 4}, {4, 0}, {5, 0}, {6, 0}, {7, 0}, {0, 6}, {4, 6}, {7, 6}, {5, 7}, {6, 7}};
+    for (int round = 0; round < 3; ++round)
+      for (const auto &p : pairs) run(p[0], p[1]);
+    return 0;
+  }
+  for (int stores = 0; stores < 6; ++stores)
+    for (int pattern = 0; pattern < 2; ++pattern) run(pattern, stores);
   return 0;
 }

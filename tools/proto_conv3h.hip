@@ -1,7 +1,7 @@
 // Stand-alone harness of the direct fp16 x 3 convolution kernel (python-audio-separator_amd/csrc/kernels_conv3h.h): a float64 direct
 // convolution on small shapes (borders, ragged sizes) and on sampled outputs of the HQ_3 level-0 shape, then time per launch.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/proto_conv3h tools/proto_conv3h.hip
-//   tools/proto_conv3h [abl] [order] [B of the timing shape] [reps] [quick] [alias] [bw] [partial sums through the scratch: 1 / 0]
+//   tools/proto_conv3h [abl] [order] [B of the timing shape] [reps] [quick] [alias] [bw] [partial sums through the scratch: 1 / 0] [tile order: 1 = also the XT / YT forms]
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -52,6 +52,17 @@ static void launch_ps(int ps, const Conv3hArgs &a, hipStream_t s) {
   if (ps == 1) hipLaunchKernelGGL((conv3h_kernel<0, false, false, 1>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, a);
   else if (ps == 2) hipLaunchKernelGGL((conv3h_kernel<0, false, false, 2>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, a);
   else hipLaunchKernelGGL((conv3h_kernel<0, false, false, 3>), dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, a);
+}
+// the tile-order forms (template flags XT / YT: the input / the output slice in Conv3hCfg::tl_off order), plain build only
+static void launch_tl(bool xt, bool yt, const Conv3hArgs &a, hipStream_t s) {
+  auto one = [&](auto kern) {
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Conv3hCfg::LDS_BYTES));
+    hipLaunchKernelGGL(kern, dim3(256), dim3(512), Conv3hCfg::LDS_BYTES, s, a);
+  };
+  if (xt && yt) one(&conv3h_kernel<0, false, false, 0, true, true>);
+  else if (xt) one(&conv3h_kernel<0, false, false, 0, true, false>);
+  else if (yt) one(&conv3h_kernel<0, false, false, 0, false, true>);
+  else one(&conv3h_kernel<0, false>);
 }
 static void launch_abl(int abl, const Conv3hArgs &a, hipStream_t s) {
   switch (abl) {
@@ -112,6 +123,7 @@ static void set_walk(Conv3hArgs &a) {
   a.walk = reinterpret_cast<const u32x4 *>(d);
 }
 static int g_ps = 1;       // 96 -> 96 layer: partial sums through the fragment-order scratch (argv[8]; 0: through the output, planar)
+static int g_tiled = 0;    // argv[9]: 1 = the chain planar -> tile order -> tile order -> planar against three planar launches, bit for bit, and the forms' times
 static int g_alias = 0;   // 1: every batch item reads item 0's planes, 2: and writes item 0's output (cache-resident traffic: is the launch DRAM- or CU-bound?)
 static int run_shape(const Shape &sh, int abl, int order, int reps) {
   const int C = 48;
@@ -229,6 +241,63 @@ static int run_shape(const Shape &sh, int abl, int order, int reps) {
       for (int k = 0; k < 7; ++k) printf(" %8lld", d[st * 8 + k] - d[8 * 8]);
       printf("\n");
     }
+  }
+  if (g_tiled && abl == 0 && sh.T % 4 == 0) {
+    float *d1 = nullptr, *d2 = nullptr, *dr = nullptr;
+    CK(hipMalloc(&d1, n * 4));
+    CK(hipMalloc(&d2, n * 4));
+    CK(hipMalloc(&dr, n * 4));
+    auto run3 = [&](bool tiled, float *out) {          // the same layer three times over
+      Conv3hArgs b = a;
+      b.y = d1;
+      launch_tl(false, tiled, b, 0);
+      b.x = d1;
+      b.y = d2;
+      launch_tl(tiled, tiled, b, 0);
+      b.x = d2;
+      b.y = out;
+      launch_tl(tiled, false, b, 0);
+    };
+    CK(hipMemset(d1, 0xff, n * 4));
+    CK(hipMemset(d2, 0xff, n * 4));
+    run3(false, dr);
+    CK(hipMemset(d1, 0xff, n * 4));
+    CK(hipMemset(d2, 0xff, n * 4));
+    run3(true, dy);
+    CK(hipDeviceSynchronize());
+    std::vector<float> ya(nb), yb(nb);
+    for (int b : {0, sh.B - 1}) {
+      CK(hipMemcpy(ya.data(), dr + (size_t)b * nb, nb * 4, hipMemcpyDeviceToHost));
+      CK(hipMemcpy(yb.data(), dy + (size_t)b * nb, nb * 4, hipMemcpyDeviceToHost));
+      if (memcmp(ya.data(), yb.data(), nb * 4) != 0) {
+        printf("  %s: the tile-order chain differs from the planar chain in item %d\n", sh.name, b);
+        ++bad;
+      }
+    }
+    printf("  %s: tile-order chain of three layers against the planar chain: %s\n", sh.name, bad ? "FAIL" : "bit for bit");
+    if (reps > 0) {
+      hipEvent_t e0, e1;
+      CK(hipEventCreate(&e0));
+      CK(hipEventCreate(&e1));
+      Conv3hArgs b = a;
+      b.x = d1;
+      b.y = d2;
+      for (int round = 0; round < 2; ++round)
+        for (int form = 0; form < 4; ++form) {
+          const bool xt = form & 1, yt = form & 2;
+          launch_tl(xt, yt, b, 0);
+          CK(hipEventRecord(e0, 0));
+          for (int i = 0; i < reps; ++i) launch_tl(xt, yt, b, 0);
+          CK(hipEventRecord(e1, 0));
+          CK(hipEventSynchronize(e1));
+          float ms = 0;
+          CK(hipEventElapsedTime(&ms, e0, e1));
+          printf("  %s: input %s, output %s: %.3f ms per launch\n", sh.name, xt ? "tile order" : "planar", yt ? "tile order" : "planar", ms / reps);
+        }
+    }
+    CK(hipFree(d1));
+    CK(hipFree(d2));
+    CK(hipFree(dr));
   }
   if (g_alias >= 1) a.x_bstride = 0;
   if (g_alias >= 2) a.y_bstride = 0;
@@ -400,6 +469,7 @@ int main(int argc, char **argv) {
   g_alias = argc > 6 ? atoi(argv[6]) : 0;
   g_bw = argc > 7 ? atoi(argv[7]) : 32;
   g_ps = argc > 8 ? atoi(argv[8]) : 1;
+  g_tiled = argc > 9 ? atoi(argv[9]) : 0;
   int bad = 0;
   if (abl == 0 && !quick) {
     const Shape small[] = {
