@@ -897,6 +897,48 @@ int asx_op_vr_lstm(asx_engine *e, const float *xp_host, const float *whh_host, i
  * channel left alone; ld and ch0 must be multiples of 4 with ch0 + 4 <= ld (one 16-byte store per pixel). */
 int asx_op_vr_lstm_layout(asx_engine *e, int32_t dir, const float *src_host, int32_t b, int32_t h, int32_t w, int32_t ld, int32_t ch0,
                           float *dst_host);
+/* (ABI 7) One gathered-convolution launch of the channels-last nets (HTDemucs, HDemucs / Demucs v3, VR), through ht_gg of
+ * csrc/engine_ht.h unchanged -- single-op test hook like asx_op_mha: host buffers, no net needed; y (and nothing else) is read as well
+ * as written: its contents are uploaded first, so elements the launch does not own keep them; a descriptor or variant the launch code
+ * would not take is ASX_ERR_INVALID, never a launch.
+ * x is the view [B, O, I, Cin] at column x_col0 of a tensor [B][x_bs floats] whose pixels are ldc floats apart (x_bs 0: O * I * ldc);
+ * output row (b, oo, j), oo < OR (0: O), j < IR, gathers the KO x KI taps at input pixel (oo SO - PO + to DO, j SI - PI + ti DI), zero
+ * outside the image.  mode 0 (dense): y view [B, OR, IR, Cout] at column y_col0 of [B][y_bs floats] with rows of ldy floats (y_bs 0:
+ * OR * IR * ldy), y = act(conv + bias) (+ res); w [Cout, Cin, KI, KO] (the first kernel axis is the INNER one), bias [Cout].  mode 1
+ * (GLU): w [2 Cout, Cin, KI, KO], bias [2 Cout], y = value * sigmoid(gate) (+ res), act must be 0.  mode 2 (ConvTranspose along the
+ * inner axis, kernel 2 So, stride So, as two taps: KO 1, KI 2, SO = SI = 1): w [Cin, Cout, 2 So], bias [Cout]; row j scatters to
+ * positions So j - crop + r, r < So, of y [B * O, Iout, ldy] (y_bs must be 0), positions outside [0, Iout) dropped; y = act(.) (+ res).
+ * res (res = 1; ldr floats per row): the residual -- [B * OR * IR, ldr] for modes 0 / 1, [B * O, Iout, ldr] for mode 2, or with
+ * res_mod > 0 (modes 0 / 1) the table [res_mod, ldr] read at row % res_mod.  act: 0 none, 1 ReLU, 2 GELU (erf), 3 tanh, 4 leaky ReLU
+ * (0.01), 5 sigmoid, 6 GELU on the fast erf.  Channel counts, strides and column offsets are multiples of 4.  Weights are packed by
+ * the engine's own packers (ht_pack_conv / ht_pack_convtr / ht_glu_perm / ht_halo_pack).
+ * variant: "auto" = ht_gg's own rule -- with the halo-tile packing the Demucs decoder rewrites and the VR 3x3 layers carry wherever the
+ * layer is eligible for it, or without one (no_halo = 1), as the encoder and DConv convolutions are loaded; "gg" / "halo" / "gather" = only gg_kernel / the halo-tile kernel (csrc/kernels_halo.h) / the
+ * GATHER mode of the split-operand row GEMM (csrc/kernels_gemm3.h; bf16 x 6 or fp16 x 3 by the options "gemm_bf16x6" / "gemm_f16x3")
+ * may run.  resolved (optional, 3 ints): {1 gg / 2 halo / 3 gather, the N tile (gg, halo; 0 for gather), gg_kernel's lowai flag}. */
+typedef struct asx_gconv_desc {
+  int32_t B, O, I, Cin, ldc, Cout, ldy;
+  int32_t KO, KI, DO, DI, PO, PI, SO, SI, OR, IR;
+  int32_t x_col0, y_col0;
+  int32_t mode, act;
+  int32_t res, ldr, res_mod;
+  int32_t Iout, crop, So;
+  int32_t no_halo;
+  int64_t x_bs, y_bs;
+} asx_gconv_desc;
+int asx_op_gconv(asx_engine *e, const asx_gconv_desc *d, const float *x_host, const float *w_host, const float *b_host,
+                 const float *res_host, const char *variant, float *y_host, int32_t *resolved);
+/* (ABI 7) One DConv layer of the Demucs encoders (demucs.py:99-179) through ht_dconv_layer of csrc/engine_ht.h -- single-op test hook
+ * like asx_op_gconv -- on y [b, o, i, c] channels-last, in place: part 1 = conv k3 with dilation 2^d (along the outer axis when
+ * along_outer, else the inner) + GroupNorm(1, hid) + GELU -> h [b * o * i, hp = hid rounded up to 4]; part 2 = conv 1x1 +
+ * GroupNorm(1, 2 c) + GLU + LayerScale, added into y; 3 = both.  GroupNorm runs per (b, i) over (o, c) when along_outer (the
+ * spectrogram branch), else per b over (o, i, c).  Torch tensors: w1 [hid, c, 3], b1 [hid], g1w / g1b [hid], w2 [2 c, hid], b2 [2 c],
+ * g2w / g2b [2 c], ls [c].  h_host [b * o * i, hp]: uploaded first; the result of part 1, the input of part 2 alone; may be NULL for
+ * part 3.  The workspace ht_dconv_layer reads (h, the per-row partial sums, the float64 group sums, (mean, rstd), the arrival
+ * counters) is built for exactly this case.  ticket_left (optional): how many arrival counters are non-zero afterwards. */
+int asx_op_dconv(asx_engine *e, float *y_host, int32_t b, int32_t o, int32_t i, int32_t c, int32_t hid, int32_t along_outer, int32_t d,
+                 int32_t part, const float *w1, const float *b1, const float *g1w, const float *g1b, const float *w2, const float *b2,
+                 const float *g2w, const float *g2b, const float *ls, float *h_host, int32_t *ticket_left);
 
 /* ---- options ------------------------------------------------------------ */
 /* Engine options.  Each engine takes its defaults from the environment variable named beside the option when it is created (values go

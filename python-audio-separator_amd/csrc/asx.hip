@@ -1822,6 +1822,153 @@ int asx_op_vr_lstm_layout(asx_engine *e, int32_t dir, const float *src_host, int
   return to_host(dst_host, ddst, dir == 0 ? np : np * ld);
 }
 
+// one ht_gg launch from host buffers (engine_ht.h); every check below keeps the kernels' reads and writes inside the buffers uploaded here
+int asx_op_gconv(asx_engine *e, const asx_gconv_desc *d, const float *x_host, const float *w_host, const float *b_host,
+                 const float *res_host, const char *variant, float *y_host, int32_t *resolved) {
+  REQUIRE(e && d && x_host && w_host && b_host && y_host && variant, "asx_op_gconv: null argument");
+  int only = -1;
+  {
+    static const char *names[4] = {"auto", "gg", "halo", "gather"};
+    for (int i = 0; i < 4; ++i)
+      if (!strcmp(variant, names[i])) only = i;
+  }
+  REQUIRE(only >= 0, "asx_op_gconv: unknown variant '%s'", variant);
+  const int OR = d->OR ? d->OR : d->O;
+  REQUIRE(d->B > 0 && d->O > 0 && d->I > 0 && d->Cin > 0 && d->Cout > 0 && OR > 0 && d->IR > 0, "asx_op_gconv: sizes must be positive");
+  REQUIRE(d->KO >= 1 && d->KO <= 3 && d->KI >= 1 && d->KI <= 16 && d->DO >= 1 && d->DI >= 1 && d->PO >= 0 && d->PI >= 0 && d->SO >= 1 && d->SI >= 1,
+          "asx_op_gconv: taps %d x %d (at most 3 x 16), dilations, paddings and strides out of range", d->KO, d->KI);
+  REQUIRE((d->Cin & 3) == 0 && (d->ldc & 3) == 0 && (d->x_col0 & 3) == 0 && d->x_col0 >= 0 && d->x_col0 + d->Cin <= d->ldc,
+          "asx_op_gconv: Cin %d at column %d does not fit pixels of %d floats in whole groups of four", d->Cin, d->x_col0, d->ldc);
+  REQUIRE((d->Cout & 3) == 0 && (d->ldy & 3) == 0 && (d->y_col0 & 3) == 0 && d->y_col0 >= 0 && d->y_col0 + d->Cout <= d->ldy,
+          "asx_op_gconv: Cout %d at column %d does not fit rows of %d floats in whole groups of four", d->Cout, d->y_col0, d->ldy);
+  REQUIRE(d->mode >= GG_DENSE && d->mode <= GG_CONVT && d->act >= 0 && d->act <= 6 && (d->mode != GG_GLU || d->act == 0),
+          "asx_op_gconv: mode %d / act %d", d->mode, d->act);
+  const int64_t x_img = (int64_t)d->O * d->I * d->ldc, x_bs = d->x_bs ? d->x_bs : x_img;
+  const bool convt = d->mode == GG_CONVT;
+  const int64_t y_img = convt ? (int64_t)d->O * d->Iout * d->ldy : (int64_t)OR * d->IR * d->ldy, y_bs = (d->y_bs && !convt) ? d->y_bs : y_img;
+  REQUIRE(x_bs >= x_img && y_bs >= y_img && (!convt || d->y_bs == 0), "asx_op_gconv: batch strides smaller than an image");
+  if (convt)
+    REQUIRE(d->KO == 1 && d->KI == 2 && d->SO == 1 && d->SI == 1 && OR == d->O && d->So >= 1 && d->So <= 8 && d->Iout > 0 && d->crop >= 0 &&
+                d->res_mod == 0,
+            "asx_op_gconv: ConvTranspose takes KO 1, KI 2, unit strides, So 1 .. 8, Iout > 0, crop >= 0 and no residual table");
+  const int64_t M = (int64_t)d->B * OR * d->IR;
+  const int64_t nx = (int64_t)d->B * x_bs, ny = (int64_t)d->B * y_bs;
+  REQUIRE(nx < (1ll << 28) && ny < (1ll << 28) && M < (1ll << 26), "asx_op_gconv: the case is too large for a single-op test");
+  const int64_t res_rows = d->res_mod > 0 ? d->res_mod : (convt ? (int64_t)d->B * d->O * d->Iout : M);
+  if (d->res)
+    REQUIRE(res_host && (d->ldr & 3) == 0 && d->ldr >= d->Cout && d->res_mod >= 0, "asx_op_gconv: residual rows of %d floats for %d channels",
+            d->ldr, d->Cout);
+  HIPCHK(hipSetDevice(e->device));
+  HtGemm g;
+  DevBuf dx, dy, dres;
+  BufGuard guard{{&dx, &dy, &dres, &g.w, &g.b, &g.wh}};
+  const bool want_halo = (only == 0 && !d->no_halo) || only == 2;
+  if (convt) CHK(ht_pack_convtr_ptr(g, w_host, b_host, d->Cin, d->Cout, 2 * d->So, d->So));
+  else if (d->mode == GG_GLU) CHK(ht_pack_conv_ptr(g, w_host, b_host, 2 * d->Cout, d->Cin, d->KI, d->KO, true, 0, 0, want_halo));
+  else CHK(ht_pack_conv_ptr(g, w_host, b_host, d->Cout, d->Cin, d->KI, d->KO, false, 0, 0, want_halo));
+  CHK(to_dev(dx, x_host, (size_t)nx));
+  CHK(to_dev(dy, y_host, (size_t)ny));
+  if (d->res) CHK(to_dev(dres, res_host, (size_t)res_rows * d->ldr));
+  HtGeom q;
+  q.O = d->O;
+  q.I = d->I;
+  q.Cin = d->Cin;
+  q.ldc = d->ldc;
+  q.KO = d->KO;
+  q.KI = d->KI;
+  q.DO = d->DO;
+  q.DI = d->DI;
+  q.PO = d->PO;
+  q.PI = d->PI;
+  q.SI = d->SI;
+  q.IR = d->IR;
+  q.SO = d->SO;
+  q.OR = OR;
+  q.x_bs = x_bs;
+  q.y_bs = convt ? 0 : y_bs;
+  q.crop = d->crop;
+  q.So = d->So;
+  e->gg_only = only;
+  e->gg_ran[0] = 0;
+  int rc = ht_gg(e, g, dx.f() + d->x_col0, q, (int64_t)d->B * OR, dy.f() + d->y_col0, d->ldy, d->mode, d->act, d->res ? dres.f() : nullptr,
+                 d->ldr, d->res_mod, d->Iout, d->Cout, nullptr);
+  e->gg_only = 0;
+  if (rc == ASX_OK && hipGetLastError() != hipSuccess) {
+    set_err("asx_op_gconv: launch failed");
+    rc = ASX_ERR_HIP;
+  }
+  if (rc == ASX_OK) rc = to_host(y_host, dy, (size_t)ny);
+  else (void)hipDeviceSynchronize();
+  w3_drop(e, g.w.p);                                   // the temporary layer's split image goes with its weight buffer
+  if (resolved)
+    for (int i = 0; i < 3; ++i) resolved[i] = e->gg_ran[i];
+  return rc;
+}
+
+// one ht_dconv_layer call from host buffers, on a workspace of exactly the buffers it reads (engine_ht.h)
+int asx_op_dconv(asx_engine *e, float *y_host, int32_t B, int32_t O, int32_t I, int32_t C, int32_t hid, int32_t along_outer, int32_t d,
+                 int32_t part, const float *w1, const float *b1, const float *g1w, const float *g1b, const float *w2, const float *b2,
+                 const float *g2w, const float *g2b, const float *ls, float *h_host, int32_t *ticket_left) {
+  REQUIRE(e && y_host && w1 && b1 && g1w && g1b && w2 && b2 && g2w && g2b && ls, "asx_op_dconv: null argument");
+  REQUIRE(B > 0 && O > 0 && I > 0 && C > 0 && (C & 3) == 0 && hid > 0 && hid <= C && d >= 0 && d <= 8 && part >= 1 && part <= 3,
+          "asx_op_dconv: bad shape (c %d must be a multiple of 4, hid %d in 1 .. c, d %d in 0 .. 8, part %d in 1 .. 3)", C, hid, d, part);
+  REQUIRE(part == 3 || h_host, "asx_op_dconv: parts 1 and 2 alone need h_host");
+  REQUIRE(along_outer || O == 1, "asx_op_dconv: the inner-axis form is the waveform branch's, o must be 1 (got %d)", O);
+  const int64_t M = (int64_t)B * O * I;
+  REQUIRE(M * C < (1ll << 28), "asx_op_dconv: the case is too large for a single-op test");
+  HIPCHK(hipSetDevice(e->device));
+  HtEnc E;
+  E.cin = E.cout = C;
+  E.dc.assign((size_t)d + 1, HtDconv());
+  HtDconv &dc = E.dc[d];
+  HtNet net;
+  DevBuf dy, dh, drow, dacc, dmr, dtick;
+  BufGuard guard{{&dy, &dh, &drow, &dacc, &dmr, &dtick, &dc.c1.w, &dc.c1.b, &dc.c2.w, &dc.c2.b, &dc.g1w, &dc.g1b, &dc.g2w, &dc.g2b, &dc.ls}};
+  CHK(ht_pack_dconv(dc, C, hid, w1, b1, g1w, g1b, w2, b2, g2w, g2b, ls));
+  const int G2 = along_outer ? I : 1;
+  const int np = dc.c2.n;
+  const size_t t1 = (size_t)(dc.hp + gg_tile_n(dc.hp) - 1) / gg_tile_n(dc.hp), t2 = (size_t)(np + gg_tile_n(np, true) - 1) / gg_tile_n(np, true);
+  const size_t ng = (size_t)B * G2;
+  CHK(to_dev(dy, y_host, (size_t)M * C));
+  if (h_host) CHK(to_dev(dh, h_host, (size_t)M * dc.hp));
+  else CHK(dh.ensure((size_t)M * dc.hp * 4));
+  CHK(drow.ensure((size_t)M * std::max(t1, t2) * 8));
+  CHK(dacc.ensure(2 * ng * 16));
+  CHK(dmr.ensure(ng * 8));
+  CHK(dtick.ensure((size_t)B * 4));
+  HIPCHK(hipMemset(dtick.p, 0, (size_t)B * 4));
+  net.b.h = dh.f();
+  net.b.rowstat = drow.f();
+  net.b.acc_g = reinterpret_cast<double *>(dacc.p);
+  net.b.acc_g2 = net.b.acc_g + 2 * ng;
+  net.b.mr_g = dmr.f();
+  net.b.ticket = reinterpret_cast<unsigned *>(dtick.p);
+  HtNet *const saved = e->ht;
+  e->ht = &net;
+  int rc = ht_dconv_layer(e, E, (size_t)d, part, dy.f(), B, O, I, along_outer != 0, nullptr);
+  e->ht = saved;
+  if (rc == ASX_OK && hipGetLastError() != hipSuccess) {
+    set_err("asx_op_dconv: launch failed");
+    rc = ASX_ERR_HIP;
+  }
+  if (rc == ASX_OK) rc = to_host(y_host, dy, (size_t)M * C);
+  else (void)hipDeviceSynchronize();
+  if (rc == ASX_OK && h_host) rc = to_host(h_host, dh, (size_t)M * dc.hp);
+  if (rc == ASX_OK && ticket_left) {
+    std::vector<unsigned> t((size_t)B);
+    if (hipMemcpy(t.data(), dtick.p, (size_t)B * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+      set_err("asx_op_dconv: reading the arrival counters failed");
+      rc = ASX_ERR_HIP;
+    }
+    int nz = 0;
+    for (unsigned v : t) nz += v != 0;
+    *ticket_left = nz;
+  }
+  w3_drop(e, dc.c1.w.p);
+  w3_drop(e, dc.c2.w.p);
+  return rc;
+}
+
 // ---- MDXC / TFC-TDF v3 --------------------------------------------------------------
 int asx_v3_begin(asx_engine *e, const asx_v3_config *cfg) {
   w3_flush(e);

@@ -208,6 +208,11 @@ struct asx_engine {
   bool fft3 = false;             // n_fft == 6144 && hop == 1024 (and ASX_FFT3 != 0)
   bool fft3p = false;            // inverse with the LDS-DMA spectrum prefetch (ASX_FFT3P != 0)
   DevBuf d_zeros;                // zero page: source of out-of-range DMA slots
+  // test-only selector of ht_gg (engine_ht.h), set by asx_op_gconv alone: 0 = the engine's rule (every other caller), 1 / 2 / 3 = only
+  // gg_kernel / the halo-tile kernel / the GATHER row GEMM may run, and a launch the chosen one does not take is ASX_ERR_INVALID.
+  // gg_ran: what the last ht_gg launched -- {1 / 2 / 3 as above, N tile (0 for GATHER), gg_kernel's lowai}
+  int gg_only = 0;
+  int gg_ran[3] = {0, 0, 0};
   // net
   bool net_begun = false, net_ready = false;
   asx_net_config net{};

@@ -154,11 +154,8 @@ static void ht_glu_perm(std::vector<float> &w, std::vector<float> &b, int c, int
 
 // torch conv weight [Cout, Cin, KA, KB] (KB = 1 for 1-D) -> [Npad, (to*KI + ti)*CinP + ci];
 // inner_first: the first kernel axis (KA) is the inner (frequency) tap, the second the outer (time) tap
-static int ht_pack_conv(asx_engine *e, HtGemm &g, const std::string &name, int cout, int cin, int ka, int kb,
-                        bool glu, int npad = 0, int cinp = 0, bool halo = false) {
-  const float *w, *b;
-  CHK(get_tensor(e, name + ".weight", (int64_t)cout * cin * ka * kb, &w));
-  CHK(get_tensor(e, name + ".bias", cout, &b));
+static int ht_pack_conv_ptr(HtGemm &g, const float *w, const float *b, int cout, int cin, int ka, int kb, bool glu, int npad = 0,
+                            int cinp = 0, bool halo = false) {
   if (!npad) npad = cout;
   if (!cinp) cinp = cin;
   const int K = ka * kb * cinp;
@@ -184,12 +181,16 @@ static int ht_pack_conv(asx_engine *e, HtGemm &g, const std::string &name, int c
   if (halo) CHK(ht_halo_pack(g, pw, ka * kb, cinp));
   return ASX_OK;
 }
+static int ht_pack_conv(asx_engine *e, HtGemm &g, const std::string &name, int cout, int cin, int ka, int kb,
+                        bool glu, int npad = 0, int cinp = 0, bool halo = false) {
+  const float *w, *b;
+  CHK(get_tensor(e, name + ".weight", (int64_t)cout * cin * ka * kb, &w));
+  CHK(get_tensor(e, name + ".bias", cout, &b));
+  return ht_pack_conv_ptr(g, w, b, cout, cin, ka, kb, glu, npad, cinp, halo);
+}
 
 // ConvTranspose weight [Cin, Cout, 8(,1)], stride 4: W[(r, co)][tap*Cin + ci] = w[ci][co][r + 4*(1 - tap)]
-static int ht_pack_convtr(asx_engine *e, HtGemm &g, const std::string &name, int cin, int cout, int ksz, int stride) {
-  const float *w, *b;
-  CHK(get_tensor(e, name + ".weight", (int64_t)cin * cout * ksz, &w));
-  CHK(get_tensor(e, name + ".bias", cout, &b));
+static int ht_pack_convtr_ptr(HtGemm &g, const float *w, const float *b, int cin, int cout, int ksz, int stride) {
   const int N = stride * cout, K = 2 * cin;
   std::vector<float> pw((size_t)N * K), pb((size_t)N);
   for (int r = 0; r < stride; ++r)
@@ -204,6 +205,12 @@ static int ht_pack_convtr(asx_engine *e, HtGemm &g, const std::string &name, int
   CHK(ht_up(g.w, pw));
   CHK(ht_up(g.b, pb));
   return ASX_OK;
+}
+static int ht_pack_convtr(asx_engine *e, HtGemm &g, const std::string &name, int cin, int cout, int ksz, int stride) {
+  const float *w, *b;
+  CHK(get_tensor(e, name + ".weight", (int64_t)cin * cout * ksz, &w));
+  CHK(get_tensor(e, name + ".bias", cout, &b));
+  return ht_pack_convtr_ptr(g, w, b, cin, cout, ksz, stride);
 }
 
 // nn.Linear rows [r0, r1) of `name` (+ per-output-row scale: LayerScale folded in, transformer.py:258,263)
@@ -226,32 +233,43 @@ static int ht_pack_linear(asx_engine *e, HtGemm &g, const std::string &wname, co
   return ASX_OK;
 }
 
-// ins: modules inserted between the GELU and the 1x1 conv (Demucs v3's BLSTM / LocalState shift the Sequential's indices)
-static int ht_load_dconv(asx_engine *e, HtDconv &d, const std::string &p, int ch, int comp, int idx, int ins = 0) {
-  d.hid = ch / comp;
+// one DConv layer from its torch tensors: conv k3 [hid, ch, 3] + bias, GroupNorm(1, hid), conv 1x1 [2 ch, hid, 1] + bias, GroupNorm(1, 2 ch),
+// LayerScale [ch]
+static int ht_pack_dconv(HtDconv &d, int ch, int hid, const float *w1, const float *b1, const float *g, const float *b, const float *w2,
+                         const float *b2c, const float *g2, const float *b2, const float *ls) {
+  d.hid = hid;
   d.hp = (d.hid + 3) & ~3;
-  const std::string q = p + ".layers." + std::to_string(idx);
-  CHK(ht_pack_conv(e, d.c1, q + ".0", d.hid, ch, 3, 1, false, d.hp, 0));
-  CHK(ht_pack_conv(e, d.c2, q + "." + std::to_string(3 + ins), 2 * ch, d.hid, 1, 1, true, 0, d.hp));   // GLU row order for the fused epilogue
-  const float *g, *b;
-  CHK(get_tensor(e, q + ".1.weight", d.hid, &g));
-  CHK(get_tensor(e, q + ".1.bias", d.hid, &b));
+  CHK(ht_pack_conv_ptr(d.c1, w1, b1, d.hid, ch, 3, 1, false, d.hp, 0));
+  CHK(ht_pack_conv_ptr(d.c2, w2, b2c, 2 * ch, d.hid, 1, 1, true, 0, d.hp));   // GLU row order for the fused epilogue
   std::vector<float> gw(d.hp, 0.f), gb(d.hp, 0.f);
   std::copy(g, g + d.hid, gw.begin());
   std::copy(b, b + d.hid, gb.begin());
   CHK(ht_up(d.g1w, gw));
   CHK(ht_up(d.g1b, gb));
-  {
-    const float *g2, *b2;
-    CHK(get_tensor(e, q + "." + std::to_string(4 + ins) + ".weight", 2 * ch, &g2));
-    CHK(get_tensor(e, q + "." + std::to_string(4 + ins) + ".bias", 2 * ch, &b2));
-    std::vector<float> pg(g2, g2 + 2 * ch), pb2(b2, b2 + 2 * ch);
-    ht_glu_perm(pg, pb2, ch, 1);     // (weights, "bias") = (gamma, beta), one float per row
-    CHK(ht_up(d.g2w, pg));
-    CHK(ht_up(d.g2b, pb2));
-  }
-  CHK(ht_up_named(e, d.ls, q + "." + std::to_string(6 + ins) + ".scale", ch));
-  return ASX_OK;
+  std::vector<float> pg(g2, g2 + 2 * ch), pb2(b2, b2 + 2 * ch);
+  ht_glu_perm(pg, pb2, ch, 1);     // (weights, "bias") = (gamma, beta), one float per row
+  CHK(ht_up(d.g2w, pg));
+  CHK(ht_up(d.g2b, pb2));
+  std::vector<float> lsv(ls, ls + ch);
+  return ht_up(d.ls, lsv);
+}
+
+// ins: modules inserted between the GELU and the 1x1 conv (Demucs v3's BLSTM / LocalState shift the Sequential's indices)
+static int ht_load_dconv(asx_engine *e, HtDconv &d, const std::string &p, int ch, int comp, int idx, int ins = 0) {
+  const int hid = ch / comp;
+  const std::string q = p + ".layers." + std::to_string(idx);
+  const std::string c2 = q + "." + std::to_string(3 + ins), n2 = q + "." + std::to_string(4 + ins);
+  const float *w1, *b1, *g, *b, *w2, *b2c, *g2, *b2, *ls;
+  CHK(get_tensor(e, q + ".0.weight", (int64_t)hid * ch * 3, &w1));
+  CHK(get_tensor(e, q + ".0.bias", hid, &b1));
+  CHK(get_tensor(e, c2 + ".weight", (int64_t)2 * ch * hid, &w2));
+  CHK(get_tensor(e, c2 + ".bias", 2 * ch, &b2c));
+  CHK(get_tensor(e, q + ".1.weight", hid, &g));
+  CHK(get_tensor(e, q + ".1.bias", hid, &b));
+  CHK(get_tensor(e, n2 + ".weight", 2 * ch, &g2));
+  CHK(get_tensor(e, n2 + ".bias", 2 * ch, &b2));
+  CHK(get_tensor(e, q + "." + std::to_string(6 + ins) + ".scale", ch, &ls));
+  return ht_pack_dconv(d, ch, hid, w1, b1, g, b, w2, b2c, g2, b2, ls);
 }
 
 static int ht_load_tlayer(asx_engine *e, HtTLayer &L, const std::string &p, bool cross, int C, int hidden) {
@@ -570,7 +588,7 @@ static int ht_gg(asx_engine *e, const HtGemm &g, const float *x, const HtGeom &q
     // channel counts off the 32-grid (48, 80, ...): the last chunk of every tap is zero padded -- worth it from 70 % chunk use
     // (ASX_GATHER6_PARTIAL=0: only multiples of 32)
     const bool cin_ok = q.Cin % 32 == 0 || (k.gather6_partial && q.Cin % 8 == 0 && q.Cin > 32 && 10 * q.Cin >= 7 * 32 * ((q.Cin + 31) / 32));
-    if (k.gather6 && e->gemm_bf16x6 > 0 && (mode == GG_DENSE || glu) && res == nullptr && fz == nullptr && (unit || k.gather6_strided) &&
+    if ((e->gg_only == 0 || e->gg_only == 3) && k.gather6 && e->gemm_bf16x6 > 0 && (mode == GG_DENSE || glu) && res == nullptr && fz == nullptr && (unit || k.gather6_strided) &&
         q.SI >= 1 && q.SO >= 1 && q.KO <= 3 && q.KO * q.KI > 1 && cin_ok && g.n % 8 == 0 && g.n >= (glu ? 65 : k.gather6_minn) && (q.ldc & 3) == 0 && (ldy & 3) == 0 &&
         a.y_bs == (int64_t)a.OR * q.IR * ldy && a16(x) && a16(y) && a16(g.w.p) && a16(g.b.p) && a.M < (1ll << 31) &&
         (int64_t)(q.KO * q.DO + q.PO + 1) * q.I * q.ldc < (1ll << 31) && (uint64_t)16 * (uint64_t)ldy * 4 < (1ull << 31)) {
@@ -606,14 +624,19 @@ static int ht_gg(asx_engine *e, const HtGemm &g, const float *x, const HtGeom &q
       gq.x_bs = a.x_bs;
       bool done = false;
       CHK(timed(e, cls, flops, bytes, s, [&]() { done = launch_tdf3_gather_auto(e, d, gq, s); }));
-      if (done) return ASX_OK;
+      if (done) {
+        e->gg_ran[0] = 3;
+        e->gg_ran[1] = 0;
+        e->gg_ran[2] = 0;
+        return ASX_OK;
+      }
     }
   }
   // stride-1 k3 / 3x3 convs with a halo packing run on the halo-tile kernel (the input block enters LDS once for all taps)
   HgGeom hgm;
   // A/B knob: launches whose halo grid would be smaller than ASX_HALO_MINBLK workgroups stay on gg_kernel (128-row tiles)
   const int64_t halo_minblk = knobs().halo_minblk;
-  if (g.wh.p != nullptr && q.SI == 1 && q.SO == 1 && q.KI == 3 && (q.KO == 1 || q.KO == 3) && q.KO * q.KI == g.wh_taps &&
+  if ((e->gg_only == 0 || e->gg_only == 2) && g.wh.p != nullptr && q.SI == 1 && q.SO == 1 && q.KI == 3 && (q.KO == 1 || q.KO == 3) && q.KO * q.KI == g.wh_taps &&
       (mode == GG_DENSE || mode == GG_GLU) && res == nullptr && a.row_stat == nullptr && q.IR == q.I && a.OR == q.O &&
       (q.KO == 3 || q.O == 1) && (((uintptr_t)x | (uintptr_t)y) & 15) == 0 && hg_geometry(q.O, q.I, q.KO, q.DO, q.DI, &hgm) && (int64_t)q.O * q.I * q.ldc < (1ll << 31) &&   // 32-bit lane offsets inside an image
      
@@ -647,10 +670,20 @@ static int ht_gg(asx_engine *e, const HtGemm &g, const float *x, const HtGeom &q
     h.act = act;
     h.Cout = g.glu_c;
     const int Bn = (int)(rows_outer / q.O);
+    e->gg_ran[0] = 2;
+    e->gg_ran[1] = g.wh_nt;
+    e->gg_ran[2] = 0;
     return timed(e, cls, flops, bytes, s, [&]() {
       hg_dispatch(h, g.wh_nt, q.KO, Bn, s);
     });
   }
+  if (e->gg_only > 1) {
+    set_err("ht_gg: the %s does not take this launch", e->gg_only == 2 ? "halo-tile kernel" : "GATHER row GEMM");
+    return ASX_ERR_INVALID;
+  }
+  e->gg_ran[0] = 1;
+  e->gg_ran[1] = gg_tile_n(a.N, g.glu_c != 0);
+  e->gg_ran[2] = a.lowai;
   return timed(e, cls, flops, bytes, s, [&]() {
     ht_gg_dispatch(a, s);
   });

@@ -281,11 +281,21 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_op_vr_lstm_layout", "asx_flac_plan", "asx_flac_encode", "asx_flac_encode_dev",
            "asx_flac_decode_plan", "asx_flac_decode_scan_dev", "asx_flac_decode_finish_dev", "asx_flac_decode",
            "asx_flac_plan_pcm", "asx_flac_encode_pcm", "asx_flac_encode_pcm_dev", "asx_pcm_encode", "asx_pcm_encode_dev",
-           "asx_invert_stem_dev", "asx_invert_stem_batch_dev"]
+           "asx_invert_stem_dev", "asx_invert_stem_batch_dev", "asx_op_gconv", "asx_op_dconv"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
                  "mha6_wide", "mha6h", "mha6h_wide", "hd_local")
+
+
+GCONV_VARIANTS = ("auto", "gg", "halo", "gather")   # asx_op_gconv: `variant`, and resolved[0] as an index (0: nothing ran)
+GCONV_MODES = {"dense": 0, "glu": 1, "convt": 2}
+
+
+class _GconvDesc(C.Structure):     # struct asx_gconv_desc
+    _fields_ = [(n, C.c_int32) for n in ("B", "O", "I", "Cin", "ldc", "Cout", "ldy", "KO", "KI", "DO", "DI", "PO", "PI", "SO", "SI", "OR",
+                                         "IR", "x_col0", "y_col0", "mode", "act", "res", "ldr", "res_mod", "Iout", "crop", "So",
+                                         "no_halo")] + [("x_bs", C.c_int64), ("y_bs", C.c_int64)]
 
 
 class _LaunchRec(C.Structure):     # struct asx_launch_rec
@@ -384,6 +394,9 @@ def load_library():
     lib.asx_op_hd_lstm_frames.argtypes = [vp, i32, _FP, i32, i32, i32, i32, i32, _FP, C.POINTER(i32), C.POINTER(i32)]
     lib.asx_op_vr_lstm.argtypes = [vp, _FP, _FP, i32, i32, i32, _FP]
     lib.asx_op_vr_lstm_layout.argtypes = [vp, i32, _FP, i32, i32, i32, i32, i32, _FP]
+    lib.asx_op_gconv.argtypes = [vp, C.POINTER(_GconvDesc), _FP, _FP, _FP, _FP, C.c_char_p, _FP, C.POINTER(i32)]
+    lib.asx_op_dconv.argtypes = [vp, _FP, i32, i32, i32, i32, i32, i32, i32, i32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
+                                 C.POINTER(i32)]
     lib.asx_v3_begin.argtypes = [vp, C.POINTER(_V3Cfg)]
     lib.asx_v3_commit.argtypes = [vp]
     lib.asx_v3_flops.argtypes = [vp, i32]
@@ -1732,6 +1745,62 @@ class Engine:
             raise AsxError(f"op_vr_lstm_layout: dst {dst.shape} is not {d_shape}")
         self._check(self._lib.asx_op_vr_lstm_layout(self._h, int(out), _ptr(src), B, H, W, ld, ch0, _ptr(dst)))
         return dst
+
+    def op_gconv(self, x, w, b, y, res=None, variant="auto", **desc):
+        """One gathered-convolution launch (asx_op_gconv, include/asx.h): `desc` holds the fields of asx_gconv_desc (mode as "dense" /
+        "glu" / "convt" or its number; fields left out are 0, taps / dilations / strides default to 1), x / y / res the flat host
+        tensors the views live in.  `y` is uploaded before the launch and returned updated.  Returns (y, (kernel name, N tile, lowai))."""
+        x, w, b = _f32(x), _f32(w), _f32(b)
+        y = np.array(y, np.float32, order="C")
+        res = _f32(res) if res is not None else None
+        d = _GconvDesc()
+        for k in ("KO", "KI", "DO", "DI", "SO", "SI", "So"):
+            setattr(d, k, 1)
+        for k, v in desc.items():
+            if k == "mode" and isinstance(v, str):
+                v = GCONV_MODES[v]
+            if not hasattr(d, k):
+                raise AsxError(f"op_gconv: asx_gconv_desc has no field {k!r}")
+            setattr(d, k, int(v))
+        d.res = 0 if res is None else 1
+        OR = d.OR or d.O
+        convt = d.mode == 2
+        nx = d.B * (d.x_bs or d.O * d.I * d.ldc)
+        ny = d.B * d.O * d.Iout * d.ldy if convt else d.B * (d.y_bs or OR * d.IR * d.ldy)
+        nw = (2 * d.So if convt else d.KO * d.KI * (2 if d.mode == 1 else 1)) * d.Cin * d.Cout
+        nb = d.Cout * (2 if d.mode == 1 else 1)
+        nr = 0 if res is None else (d.res_mod or (d.B * d.O * d.Iout if convt else d.B * OR * d.IR)) * d.ldr
+        if x.size != nx or y.size != ny or w.size != nw or b.size != nb or (res is not None and res.size != nr):
+            raise AsxError(f"op_gconv: x {x.size} / y {y.size} / w {w.size} / b {b.size} / res {None if res is None else res.size} floats, "
+                           f"the descriptor wants {nx} / {ny} / {nw} / {nb} / {nr}")
+        ran = (C.c_int32 * 3)(0, 0, 0)
+        self._check(self._lib.asx_op_gconv(self._h, C.byref(d), _ptr(x), _ptr(w), _ptr(b), _optptr(res), variant.encode(), _ptr(y), ran))
+        return y, (GCONV_VARIANTS[ran[0]] if ran[0] else None, int(ran[1]), int(ran[2]))
+
+    def op_dconv(self, y, p, along_outer, d, part=3, h=None):
+        """One DConv layer (asx_op_dconv) on y [B, O, I, C] channels-last; p: dict of the layer's torch tensors w1 [hid, C, 3], b1, g1w,
+        g1b [hid], w2 [2C, hid(, 1)], b2, g2w, g2b [2C], ls [C].  part 1 / 2 / 3 = head / tail / both; `h` [B * O * I, hp] is the
+        head's output (uploaded first, default NaN) and the tail's input.  Returns (y, h, arrival counters left non-zero)."""
+        y = np.array(y, np.float32, order="C")
+        B, O, I, Cc = y.shape
+        t = {k: _f32(p[k]) for k in ("w1", "b1", "g1w", "g1b", "w2", "b2", "g2w", "g2b", "ls")}
+        hid = t["b1"].size
+        hp = (hid + 3) & ~3
+        if t["w1"].size != hid * Cc * 3 or t["w2"].size != 2 * Cc * hid or t["b2"].size != 2 * Cc or t["g1w"].size != hid or \
+                t["g1b"].size != hid or t["g2w"].size != 2 * Cc or t["g2b"].size != 2 * Cc or t["ls"].size != Cc:
+            raise AsxError(f"op_dconv: the layer's tensors do not fit C = {Cc}, hid = {hid}")
+        if h is None:
+            if part == 2:
+                raise AsxError("op_dconv: part 2 alone needs h")
+            h = np.full((B * O * I, hp), np.nan, np.float32)
+        h = np.array(h, np.float32, order="C")
+        if h.shape != (B * O * I, hp):
+            raise AsxError(f"op_dconv: h {h.shape} is not [{B * O * I}, {hp}]")
+        left = C.c_int32(-1)
+        self._check(self._lib.asx_op_dconv(self._h, _ptr(y), B, O, I, Cc, hid, int(bool(along_outer)), int(d), int(part), _ptr(t["w1"]),
+                                           _ptr(t["b1"]), _ptr(t["g1w"]), _ptr(t["g1b"]), _ptr(t["w2"]), _ptr(t["b2"]), _ptr(t["g2w"]),
+                                           _ptr(t["g2b"]), _ptr(t["ls"]), _ptr(h), C.byref(left)))
+        return y, h, left.value
 
     # -- profiling --------------------------------------------------------------
     def profile_enable(self, on: bool = True):

@@ -84,7 +84,8 @@ def test_header_is_plain_c_and_struct_layouts_match(tmp_path):
         pytest.skip("gcc not available")
     pairs = [("asx_mdx_config", E._MdxCfg), ("asx_net_config", E._NetCfg), ("asx_plan", E._Plan), ("asx_profile", E._Profile),
              ("asx_v3_config", E._V3Cfg), ("asx_rof_config", E._RofCfg), ("asx_ht_config", E._HtCfg), ("asx_hd_config", E._HdCfg), ("asx_vr_band", E._VrBand),
-             ("asx_vr_config", E._VrCfg), ("asx_vr_params", E._VrParams), ("asx_launch_rec", E._LaunchRec)]
+             ("asx_vr_config", E._VrCfg), ("asx_vr_params", E._VrParams), ("asx_launch_rec", E._LaunchRec),
+             ("asx_gconv_desc", E._GconvDesc)]
     src = '#include <stdio.h>\n#include "asx.h"\nint main(void) {\n' + \
           "".join(f'  printf("{n} %zu\\n", sizeof({n}));\n' for n, _ in pairs) + "  return 0;\n}\n"
     c = tmp_path / "sizes.c"
@@ -104,3 +105,12 @@ def test_null_engine_is_an_error_not_a_crash(lib):
         assert getattr(lib, f"asx_{fam}_begin")(None, None) != 0, fam
         assert getattr(lib, f"asx_{fam}_commit")(None) != 0, fam
     assert lib.asx_last_error()
+
+
+def test_gconv_hooks_are_additive_within_abi_7(lib):
+    """asx_op_gconv / asx_op_dconv: the descriptor is 28 int32 + 2 int64 with the strides last, and a null engine is an error"""
+    import ctypes as C
+    assert C.sizeof(E._GconvDesc) == 128 and E._GconvDesc.x_bs.offset == 112 and E._GconvDesc.no_halo.offset == 108
+    assert lib.asx_op_gconv(None, None, None, None, None, None, b"auto", None, None) != 0
+    assert lib.asx_op_dconv(None, None, 1, 1, 1, 4, 1, 0, 0, 3, None, None, None, None, None, None, None, None, None, None, None) != 0
+    assert E.GCONV_VARIANTS == ("auto", "gg", "halo", "gather") and E.GCONV_MODES == {"dense": 0, "glu": 1, "convt": 2}
