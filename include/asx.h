@@ -528,11 +528,35 @@ int asx_vr_separate_batch_dev(asx_engine *e, const asx_vr_song *songs, int32_t n
  * is the test hook of the converter.  x [channels, n_in] planar -> y [channels, n_out], n_out = ceil(n_in * ratio) (librosa's
  * fix_length; frames the library does not generate are zero).  mono_calls != 0: every channel is its own one-channel call -- the
  * library's end-of-input test then drops the last frame when n_in * ratio is an integer (change_pitch_semitones resamples channel
- * by channel); 0: the channels are the interleaved channels of one call (the VR chain).  ABI 5. */
+ * by channel); 0: the channels are the interleaved channels of one call (the VR chain).  ABI 5.
+ * n_out is the caller's: it need not be ceil(n_in * ratio).  The converter generates int(n_in * ratio) frames (one fewer in the
+ * end-of-input case above); frames of y at or beyond that count are zero, frames the caller leaves out are not computed.  Passing the
+ * length of another array is therefore spec_utils.match_array_shapes' trim or zero pad in the same pass (the way back of the pitch
+ * round trip passes the original mix's length). */
 int asx_resample_sinc(asx_engine *e, const float *x_host, int32_t channels, int64_t n_in, double ratio, int32_t mono_calls,
                       float *y_host, int64_t n_out);
 int asx_resample_sinc_dev(asx_engine *e, const float *x_dev, int32_t channels, int64_t n_in, double ratio, int32_t mono_calls,
                           float *y_dev, int64_t n_out, void *stream);
+
+/* asx_resample_sinc_dev for a list of jobs at ONE ratio (the pitched mixes of a batch of songs, or all stems of all songs on the way
+ * back) in one launch of the converter over all jobs; the job table travels to an engine-owned device buffer in launch arguments
+ * (a small table launch per 32 jobs), so the call only enqueues work on `stream` and never waits for the device -- but for an engine's
+ * FIRST sinc call of either kind, which builds the coefficient table with a blocking copy and allocates the job table, at once for the
+ * 65,535-job limit (3.7 MB), so that it never grows: growing would free it, and a free waits for the device.  Every job's y
+ * equals, bit for bit, what asx_resample_sinc_dev(x_dev, channels, n_in, ratio, mono_calls, y_dev, n_out) writes; n_out is free per
+ * job, as above.  Every argument is checked before anything is enqueued -- ASX_ERR_INVALID, asx_last_error() naming the job: a null
+ * pointer, n_in or n_out outside 1 .. 2^40, channels outside 1 .. 65535, a ratio outside (1/256, 256), more than 65,535 jobs, more than
+ * 2^31 - 1 blocks of 256 output frames in all.  n_jobs == 0 is ASX_OK.  The jobs' outputs must not overlap, nor any input an output;
+ * two calls on one engine share the table, so they belong on one stream.  `reserved` is ignored.  Additive within ABI 7. */
+typedef struct asx_sinc_job {
+  const float *x_dev;       /* [channels, n_in] planar */
+  float *y_dev;             /* [channels, n_out] planar */
+  int64_t n_in;
+  int64_t n_out;
+  int32_t channels;
+  int32_t reserved;
+} asx_sinc_job;
+int asx_resample_sinc_batch_dev(asx_engine *e, const asx_sinc_job *jobs, int32_t n_jobs, double ratio, int32_t mono_calls, void *stream);
 
 /* High-quality rational polyphase converter for input files whose sample rate is not the model's (the step librosa.load delegates to
  * soxr_hq, common_separator.py:252; the plugins' opt-in "asx_input_resample" = "device").  This project's own design in that converter's

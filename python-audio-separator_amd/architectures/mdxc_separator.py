@@ -103,9 +103,7 @@ class MDXCSeparator(CommonSeparator):
         """The stems of the current file with every array in HBM (RIFF/WAVE input at the model's rate): decode on the device,
         normalise the mix in place (asx_normalize_dev), demix, residual stem, normalise every stem in place.  Returns
         (stems [S, 2, N] CUDA tensor, kind, [(stem name, row of ``stems``)]) as ``_stem_plan`` has them.  None: take the
-        generic path."""
-        if self.pitch_shift != 0:
-            return None               # the pitch round trip runs through demix() on host arrays (mdxc.py _demix_pitched)
+        generic path.  With ``pitch_shift`` the round trip runs inside ``demix_dev`` (mdxc.py ``_pitched_many_dev``)."""
         if self.engine is None:
             self._demixer()
         mix_d = self._device_mix(self.audio_file_path)
@@ -142,7 +140,7 @@ class MDXCSeparator(CommonSeparator):
         """(stems [S, 2, N], kind, entries) as ``_device_stems`` and ``_pooled_stems`` have them -> the list ``stems_dev`` returns."""
         if isinstance(got, Exception):
             raise got
-        if got[0] == "host":                              # pitch_shift, or no device file path: host stems
+        if got[0] == "host":                              # no device file path: host stems
             return None
         stems_d, kind, entries = got
         return [(name, stems_d[i], "planar") for name, i in entries if kind == "all" or self._wanted(name)]
@@ -190,9 +188,6 @@ class MDXCSeparator(CommonSeparator):
     # A loop of ``separate`` switches ``override_model_segment_size`` on at the first file under 10 s and leaves it on, so the files
     # before that one run the model's chunk geometry and that file and all later ones the configured one: at most two pools, each on
     # its own engine.  ``_check_loaded`` applies the rule in file order and records every good file's geometry.
-    def _device_decode(self, path):
-        return None if self.pitch_shift != 0 else self._device_mix(path)      # the pitch round trip runs on host arrays
-
     def _prepare_model(self):
         self._pool_keys = []
         if self.engine is None:
@@ -207,14 +202,27 @@ class MDXCSeparator(CommonSeparator):
         key = bool(self.override_model_segment_size)
         if mix.shape[0] != 2:
             raise ValueError(f"Expected a 2-channel audio signal, but got {mix.shape[0]} channels")
-        if self.is_roformer and self.pitch_shift == 0 and n < self._demixer(key).chunk_size:
-            raise ValueError(f"mix ({n} samples) shorter than one chunk ({self._demixer(key).chunk_size}): not supported on the Roformer path")
+        if self.is_roformer and (self.pitch_shift == 0 or self._fast_file_path_enabled()):
+            # with pitch_shift the net sees the pitched mix.  Every file of the batch, host-decoded ones too, reaches the pooled device call
+            # when the device file path is on, and that call refuses a whole pool for one short mix; without the device file path the batch
+            # is the loop of demix, which refuses such a file itself, alone, as before
+            dm = self._demixer(key)
+            seen, what = (n, "mix") if self.pitch_shift == 0 else (dm.pitched_len(n), "pitched mix")
+            if seen < dm.chunk_size:
+                raise ValueError(f"{what} ({seen} samples) shorter than one chunk ({dm.chunk_size}): not supported on the Roformer path")
         self._pool_keys.append(key)
 
     def _sub_pools(self, dm, lengths):
         """Consecutive runs of files, in order, whose chunks fit one pooled call: the pooled chunk buffer ([chunks, S, 2, chunk]
         floats) stays within 60 % of the HBM that is free now, or within ``asx_pool_chunks`` chunks when that is set.  A file that
-        alone exceeds the budget is a run of its own (the single-song call would need the same buffer)."""
+        alone exceeds the budget is a run of its own (the single-song call would need the same buffer).  With ``pitch_shift`` the net
+        sees the pitched mixes: the chunks are counted from their lengths, and the temporaries of the round trip -- the pitched mix
+        [2, n'] and the stems at the pitched rate [rows, 2, n'] of every song of a run -- count against the HBM budget, in chunks
+        (``asx_pool_chunks`` counts chunks alone; the result rows [rows + 1, 2, N] are the caller's and are not charged, with or without
+        the option).  tests/test_gpu_mdxc_pitch_dev.py holds the charge against the allocator's peak beside the results."""
+        extra = [0] * len(lengths)
+        if self.pitch_shift != 0:
+            lengths = [dm.pitched_len(n) for n in lengths]
         if dm.is_roformer:
             step, rows = dm.roformer_step(), int(dm.rof.num_stems)
             counts = [-(-n // step) for n in lengths]
@@ -229,10 +237,13 @@ class MDXCSeparator(CommonSeparator):
                 import torch
                 free, _total = torch.cuda.mem_get_info(dm.engine.device)
                 budget = max(1, int(0.6 * free / (rows * 2 * dm.chunk_size * 4)))
+                if self.pitch_shift != 0:
+                    out_rows = max(rows, int(dm.rof.n_out)) if dm.is_roformer else rows
+                    extra = [-(-(out_rows + 1) * n // (rows * dm.chunk_size)) for n in lengths]
             except Exception:      # no device query: one pool, the engine reports an allocation failure itself
                 pass
         runs, used = [[]], 0
-        for i, c in enumerate(counts):
+        for i, c in enumerate(c + x for c, x in zip(counts, extra)):
             if runs[-1] and used + c > budget:
                 runs.append([])
                 used = 0
@@ -244,18 +255,19 @@ class MDXCSeparator(CommonSeparator):
         """Per file what ``_emit_file`` takes.  Files on the device path: normalise each mix in place, ONE pooled demix per geometry
         (``MDXCDemixer.demix_many_dev``; split into consecutive sub-pools only for memory), normalise every stem in place -- exactly
         where ``_device_stems`` does.  Without the device file path (``ASX_FILE_FASTPATH=0``) the same pools run through
-        ``demix_many`` on host arrays.  With ``pitch_shift`` it is the loop of ``demix`` per file (mdxc.py ``demix_many``)."""
+        ``demix_many`` on host arrays -- with ``pitch_shift`` the loop of ``demix`` per file (mdxc.py ``demix_many``); on the device path
+        the pitch round trip is part of ``demix_many_dev``."""
         keys, self._pool_keys = self._pool_keys, []
         thr, amp = self.normalization_threshold, self.amplification_threshold
         out = [None] * len(mixes)
-        host_only = self.pitch_shift != 0 or not self._fast_file_path_enabled()
+        host_only = not self._fast_file_path_enabled()
         for key in (False, True):
             idx = [i for i, k in enumerate(keys) if k == key]
             if not idx:
                 continue
             dm = self._demixer(key)
             eng = dm.engine
-            if self.pitch_shift != 0:
+            if host_only and self.pitch_shift != 0:
                 for i in idx:
                     try:
                         out[i] = ("host", eng, dm.demix(eng.normalize(mixes[i][1], thr, amp)))

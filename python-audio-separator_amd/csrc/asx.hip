@@ -289,6 +289,7 @@ void asx_engine_destroy(asx_engine *e) {
   }
   if (e->div_ev) (void)hipEventDestroy(e->div_ev);
   e->sinc_tab.release();
+  e->sinc_jobs.release();
   e->flac_frames.release();
   e->flac_cycles.release();
   e->flac_off.release();
@@ -1034,6 +1035,13 @@ int asx_resample_sinc_dev(asx_engine *e, const float *x_dev, int32_t channels, i
   REQUIRE(ratio > 1.0 / 256 && ratio < 256.0, "asx_resample_sinc_dev: ratio %g outside libsamplerate's (1/256, 256)", ratio);
   HIPCHK(hipSetDevice(e->device));
   return resample_sinc_dev(e, e->sinc_tab, x_dev, channels, n_in, ratio, mono_calls, y_dev, n_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the same for a list of jobs at one ratio in one launch (engine_vr.h resample_sinc_batch_dev; the checks: sinc_pool_plan.h)
+int asx_resample_sinc_batch_dev(asx_engine *e, const asx_sinc_job *jobs, int32_t n_jobs, double ratio, int32_t mono_calls, void *stream) {
+  REQUIRE(e, "asx_resample_sinc_batch_dev: null engine");
+  HIPCHK(hipSetDevice(e->device));
+  return resample_sinc_batch_dev(e, jobs, n_jobs, ratio, mono_calls, reinterpret_cast<hipStream_t>(stream));
 }
 
 // The rational polyphase converter (resample_plan.h, kernels_resample.h): the plan of a pair of rates, pure host

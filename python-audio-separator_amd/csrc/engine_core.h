@@ -236,6 +236,7 @@ struct asx_engine {
   DevBuf d_div;      // divider of the chunk fold for div_key's plan (input-independent: built once, asx_finalize_dev)
   DivKey div_key;
   DevBuf sinc_tab;   // coefficient table of asx_resample_sinc (built on first use)
+  DevBuf sinc_jobs;  // asx_resample_sinc_batch_dev: the job table (SincPoolJob, kernels_vr.h) of the last call
   DevBuf flac_cycles;             // the two clock sums of a profiled encode, and their totals since the engine was created
   long long flac_block_cycles = 0, flac_crc16_cycles = 0;
   DevBuf flac_frames, flac_off;   // asx_flac_encode_dev: frame slots at the plan's stride, and the offsets of the compacted frames

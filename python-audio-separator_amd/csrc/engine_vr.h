@@ -7,6 +7,7 @@
 // (vr_pool_plan.h), so the slabs hold the WHOLE pool at once -- 2 * (bins + 1) * 12 bytes per frame of every song -- and stay
 // that large afterwards.  Walking a very large pool in waves is left to the caller.
 #pragma once
+#include "sinc_pool_plan.h"
 #include "vr_pool_plan.h"
 
 struct VrConv {
@@ -940,14 +941,52 @@ static int resample_sinc_dev(asx_engine *e, DevBuf &tabbuf, const float *x, int 
   const float *tab = tabbuf.f();
   const double float_inc = VR_SINC_INC * (ratio < 1.0 ? ratio : 1.0);
   const long long inc_fp = llrint(float_inc * 4096.0);
-  const double t = (double)n_in * ratio;
-  int64_t n_gen = (int64_t)t;                                       // python-samplerate: int(num_frames * ratio)
-  if ((mono_calls || channels == 1) && (double)n_gen == t && n_gen > 0) --n_gen;   // frame + 1 / ratio would reach the end of the input
-  n_gen = std::min(n_gen, n_out);
+  // python-samplerate: int(num_frames * ratio); a one-channel call drops the frame that would reach the end of the input (sinc_pool_plan.h)
+  const int64_t n_gen = std::min(sinc_plan_generated(n_in, ratio, mono_calls || channels == 1), n_out);
   return timed(e, ASX_PROF_MISC, 0.0, 4.0 * channels * (n_in + n_out), s, [&]() {
     hipLaunchKernelGGL(vr_sinc_kernel, dim3((unsigned)((n_out + 255) / 256), channels), dim3(256), 2 * VR_SINC_TL * sizeof(float), s, x, n_in,
                        tab, tab + VR_SINC_TL, VR_SINC_TL, VR_SINC_TL - 2, 0, 1, 1.0 / ratio, float_inc, inc_fp, float_inc / VR_SINC_INC, n_gen,
                        y, n_out);
+  });
+}
+
+// resample_sinc_dev for a list of jobs at one ratio: the checks and the plan on the host (sinc_pool_plan.h), the job table written on
+// the device from launch arguments, then ONE launch of vr_sinc_batch_kernel over the workgroups of all jobs.  Nothing is enqueued
+// unless every job is valid; the call only enqueues work.
+static int resample_sinc_batch_dev(asx_engine *e, const asx_sinc_job *jobs, int n_jobs, double ratio, int mono_calls, hipStream_t s) {
+  const char *fn = "asx_resample_sinc_batch_dev";
+  std::vector<SincPlanJobIn> in((size_t)std::max(n_jobs, 0));
+  if (jobs)
+    for (int j = 0; j < n_jobs; ++j) in[j] = SincPlanJobIn{jobs[j].x_dev, jobs[j].y_dev, jobs[j].n_in, jobs[j].n_out, (int)jobs[j].channels};
+  const std::string why = sinc_pool_check(jobs ? in.data() : nullptr, n_jobs, ratio);
+  REQUIRE(why.empty(), "%s: %s", fn, why.c_str());
+  if (n_jobs == 0) return ASX_OK;
+  SincPoolPlan pp;
+  sinc_pool_build(in.data(), n_jobs, ratio, mono_calls != 0, pp);
+  if (e->sinc_tab.p == nullptr) CHK(vr_sinc_table(e->sinc_tab));
+  // sized once for the most jobs a call may carry (3.7 MB): a table that grew would be freed, and freeing waits for the device
+  CHK(e->sinc_jobs.ensure((size_t)SINC_PLAN_MAX_JOBS * sizeof(SincPoolJob)));
+  SincPoolJob *table = reinterpret_cast<SincPoolJob *>(e->sinc_jobs.p);
+  double bytes = 0.0;
+  for (int g0 = 0; g0 < n_jobs; g0 += SINC_POOL_GROUP) {
+    SincPoolGroup g{};
+    g.n_jobs = std::min(SINC_POOL_GROUP, n_jobs - g0);
+    g.job0 = g0;
+    for (int i = 0; i < g.n_jobs; ++i) {
+      const asx_sinc_job &jb = jobs[g0 + i];
+      g.job[i] = SincPoolJob{jb.x_dev, jb.y_dev, jb.n_in, jb.n_out, pp.job[g0 + i].n_gen, pp.job[g0 + i].blk0, jb.channels, 0};
+      bytes += 4.0 * jb.channels * (double)(jb.n_in + jb.n_out);
+    }
+    hipLaunchKernelGGL(sinc_pool_table_kernel, dim3(1), dim3(64), 0, s, g, table);
+    HIPCHK(hipGetLastError());
+  }
+  const float *tab = e->sinc_tab.f();
+  const double float_inc = VR_SINC_INC * (ratio < 1.0 ? ratio : 1.0);   // the arguments of resample_sinc_dev's launch
+  const long long inc_fp = llrint(float_inc * 4096.0);
+  return timed(e, ASX_PROF_MISC, 0.0, bytes, s, [&]() {
+    hipLaunchKernelGGL(vr_sinc_batch_kernel, dim3((unsigned)pp.blocks, (unsigned)pp.max_channels), dim3(256), 2 * VR_SINC_TL * sizeof(float), s,
+                       (const SincPoolJob *)table, n_jobs, tab, tab + VR_SINC_TL, VR_SINC_TL, VR_SINC_TL - 2, 1.0 / ratio, float_inc, inc_fp,
+                       float_inc / VR_SINC_INC);
   });
 }
 

@@ -161,26 +161,9 @@ __global__ __launch_bounds__(256) void vr_resample_kernel(const float *__restric
 // sum's rounding, ~1e-13 frames for rational ratios, ~1e-9 at ten million frames otherwise).
 // Table in LDS: the threads of a block walk it at a common stride from a handful of distinct start indices.  grid.y = channel.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void vr_sinc_kernel(const float *__restrict__ x, int64_t n_in, const float *__restrict__ tab,
-                                                      const float *__restrict__ dtab, int TL, int half_len, int up, int down,
-                                                      double pos_step, double float_inc, long long inc_fp, double scale, int64_t n_gen,
-                                                      float *__restrict__ y, int64_t n_out) {
-  extern __shared__ float sinc_lds[];
-  float *c = sinc_lds, *dc = sinc_lds + TL;
-  for (int i = threadIdx.x; i < TL; i += blockDim.x) {
-    c[i] = tab[i];
-    dc[i] = dtab[i];
-  }
-  __syncthreads();
-  const int ch = blockIdx.y;
-  const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= n_out) return;
-  float *yp = y + (int64_t)ch * n_out;
-  if (m >= n_gen) {
-    yp[m] = 0.f;
-    return;
-  }
-  const float *xp = x + (int64_t)ch * n_in;
+// output frame m < n_gen of one channel (xp: its n_in input frames; c, dc: the table and its differences in LDS)
+__device__ __forceinline__ float vr_sinc_frame(const float *__restrict__ xp, int64_t n_in, const float *c, const float *dc, int half_len,
+                                               int up, int down, double pos_step, double float_inc, long long inc_fp, double scale, int64_t m) {
   int64_t b;
   double frac;
   if (up > 0) {
@@ -220,7 +203,85 @@ __global__ __launch_bounds__(256) void vr_sinc_kernel(const float *__restrict__ 
       --i;
     } while (fi > 0);
   }
-  yp[m] = (float)(scale * (left + right));
+  return (float)(scale * (left + right));
+}
+
+__global__ __launch_bounds__(256) void vr_sinc_kernel(const float *__restrict__ x, int64_t n_in, const float *__restrict__ tab,
+                                                      const float *__restrict__ dtab, int TL, int half_len, int up, int down,
+                                                      double pos_step, double float_inc, long long inc_fp, double scale, int64_t n_gen,
+                                                      float *__restrict__ y, int64_t n_out) {
+  extern __shared__ float sinc_lds[];
+  float *c = sinc_lds, *dc = sinc_lds + TL;
+  for (int i = threadIdx.x; i < TL; i += blockDim.x) {
+    c[i] = tab[i];
+    dc[i] = dtab[i];
+  }
+  __syncthreads();
+  const int ch = blockIdx.y;
+  const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= n_out) return;
+  float *yp = y + (int64_t)ch * n_out;
+  if (m >= n_gen) {
+    yp[m] = 0.f;
+    return;
+  }
+  yp[m] = vr_sinc_frame(x + (int64_t)ch * n_in, n_in, c, dc, half_len, up, down, pos_step, float_inc, inc_fp, scale, m);
+}
+
+// ---------------------------------------------------------------------------
+// vr_sinc_kernel for a list of jobs at one irrational ratio in ONE launch (asx_resample_sinc_batch_dev; csrc/sinc_pool_plan.h): the
+// workgroups of the jobs stand one after the other in grid.x (SincPoolJob::blk0 ascending, 256 output frames each), grid.y = the
+// widest job's channel count -- a workgroup beyond its job's channels leaves before it loads the table.  Every frame goes through
+// vr_sinc_frame with the arguments the single launch gives it, so a job's output equals that launch's bit for bit.
+// The job table is written by sinc_pool_table_kernel from by-value launch arguments (no host copy: the call stays stream-ordered).
+// ---------------------------------------------------------------------------
+struct SincPoolJob {
+  const float *x;   // [channels, n_in]
+  float *y;         // [channels, n_out]
+  int64_t n_in, n_out;
+  int64_t n_gen;    // frames [n_gen, n_out) are zero
+  int64_t blk0;     // first workgroup (x) of the job
+  int32_t channels, reserved;
+};
+
+constexpr int SINC_POOL_GROUP = 32;
+struct SincPoolGroup {   // up to SINC_POOL_GROUP jobs, by value in the launch arguments
+  SincPoolJob job[SINC_POOL_GROUP];
+  int n_jobs, job0;      // jobs in this group, table index of its first
+};
+
+__global__ __launch_bounds__(64) void sinc_pool_table_kernel(SincPoolGroup g, SincPoolJob *__restrict__ jobs) {
+  const int i = threadIdx.x;
+  if (i < g.n_jobs) jobs[g.job0 + i] = g.job[i];
+}
+
+__global__ __launch_bounds__(256) void vr_sinc_batch_kernel(const SincPoolJob *__restrict__ jobs, int n_jobs, const float *__restrict__ tab,
+                                                            const float *__restrict__ dtab, int TL, int half_len, double pos_step,
+                                                            double float_inc, long long inc_fp, double scale) {
+  extern __shared__ float sinc_lds[];
+  int lo = 0, hi = n_jobs - 1;   // the job whose workgroups hold blockIdx.x
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].blk0 <= (int64_t)blockIdx.x) lo = mid;
+    else hi = mid - 1;
+  }
+  const SincPoolJob jb = jobs[lo];
+  const int ch = blockIdx.y;
+  if (ch >= jb.channels) return;   // (the whole workgroup)
+  float *c = sinc_lds, *dc = sinc_lds + TL;
+  for (int i = threadIdx.x; i < TL; i += blockDim.x) {
+    c[i] = tab[i];
+    dc[i] = dtab[i];
+  }
+  __syncthreads();
+  const int64_t m = ((int64_t)blockIdx.x - jb.blk0) * blockDim.x + threadIdx.x;
+  if (m >= jb.n_out) return;
+  float *yp = jb.y + (int64_t)ch * jb.n_out;
+  if (m >= jb.n_gen) {
+    yp[m] = 0.f;
+    return;
+  }
+  yp[m] = vr_sinc_frame(jb.x + (int64_t)ch * jb.n_in, jb.n_in, c, dc, half_len, 0, 1, pos_step, float_inc, inc_fp, scale, m);
 }
 
 // ---------------------------------------------------------------------------

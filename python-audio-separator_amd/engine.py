@@ -281,7 +281,7 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_op_vr_lstm_layout", "asx_flac_plan", "asx_flac_encode", "asx_flac_encode_dev",
            "asx_flac_decode_plan", "asx_flac_decode_scan_dev", "asx_flac_decode_finish_dev", "asx_flac_decode",
            "asx_flac_plan_pcm", "asx_flac_encode_pcm", "asx_flac_encode_pcm_dev", "asx_pcm_encode", "asx_pcm_encode_dev",
-           "asx_invert_stem_dev", "asx_invert_stem_batch_dev", "asx_op_gconv", "asx_op_dconv"]
+           "asx_invert_stem_dev", "asx_invert_stem_batch_dev", "asx_op_gconv", "asx_op_dconv", "asx_resample_sinc_batch_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -330,6 +330,11 @@ class _EnsJob(C.Structure):        # struct asx_ens_job
 class _InvertSong(C.Structure):    # struct asx_invert_song
     _fields_ = [("mix_dev", C.c_void_p), ("stem_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_samples", C.c_int64),
                 ("out_capacity", C.c_int64), ("n_out", C.c_int64), ("stem_layout", C.c_int32)]
+
+
+class _SincJob(C.Structure):       # struct asx_sinc_job
+    _fields_ = [("x_dev", C.c_void_p), ("y_dev", C.c_void_p), ("n_in", C.c_int64), ("n_out", C.c_int64), ("channels", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 VR_POOL_SEGMENTS = 16             # ASX_VR_POOL_SEGMENTS: songs one gather / scatter launch of a pooled VR pass serves
@@ -438,6 +443,7 @@ def load_library():
     lib.asx_debug_fetch.argtypes = [vp, C.c_char_p, _FP, i64]
     lib.asx_resample_sinc.argtypes = [vp, _FP, i32, i64, C.c_double, i32, _FP, i64]
     lib.asx_resample_sinc_dev.argtypes = [vp, vp, i32, i64, C.c_double, i32, vp, i64, vp]
+    lib.asx_resample_sinc_batch_dev.argtypes = [vp, C.POINTER(_SincJob), i32, C.c_double, i32, vp]
     lib.asx_resample_rational_plan.argtypes = [i32, i32, i64, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.asx_resample_rational.argtypes = [vp, _FP, i32, i64, i32, i32, _FP, i64]
     lib.asx_resample_rational_dev.argtypes = [vp, vp, i32, i64, i32, i32, vp, i64, vp]
@@ -880,6 +886,16 @@ class Engine:
     def resample_sinc_dev(self, x_ptr: int, channels: int, n_in: int, ratio: float, mono_calls: bool, y_ptr: int, n_out: int, stream: int = 0):
         self._check(self._lib.asx_resample_sinc_dev(self._h, x_ptr, int(channels), int(n_in), float(ratio), int(bool(mono_calls)), y_ptr,
                                                     int(n_out), stream or None))
+
+    def resample_sinc_batch_dev(self, jobs, ratio: float, mono_calls: bool, stream: int = 0):
+        """asx_resample_sinc_batch_dev: ``resample_sinc_dev`` for a list of ``(x_ptr, y_ptr, n_in, n_out, channels)`` at one ratio in
+        ONE launch of the converter; every output equals the single call's bit for bit, ``n_out`` is free per job (frames beyond the
+        generated count are zero).  Only enqueues work on ``stream`` (an engine's first sinc call also builds the coefficient table and allocates
+        the job table, once); a bad job raises AsxError naming it before anything runs."""
+        arr = (_SincJob * max(1, len(jobs)))()
+        for i, (x_ptr, y_ptr, n_in, n_out, channels) in enumerate(jobs):
+            arr[i] = _SincJob(x_ptr or None, y_ptr or None, int(n_in), int(n_out), int(channels), 0)
+        self._check(self._lib.asx_resample_sinc_batch_dev(self._h, arr, len(jobs), float(ratio), int(bool(mono_calls)), stream or None))
 
     @staticmethod
     def resample_rational_plan(sr_in: int, sr_out: int, n_in: int = 1):

@@ -215,7 +215,7 @@ class MDXCDemixer:
     def demix_many(self, mixes):
         """``demix`` for a list of mixes in ONE pooled engine call (asx_mdxc_demix_batch_dev / asx_rof_demix_batch_dev): the chunks
         of all mixes share the net passes.  Returns the list of what ``demix(mix)`` returns, bit for bit.  With ``pitch_shift`` it
-        is a loop of ``demix``: the resampled lengths differ per song and the round trip runs on host arrays."""
+        is a loop of ``demix`` on host arrays; the pooled round trip is ``demix_many_dev``."""
         mixes = [self._checked(m) for m in mixes]
         if self.pitch_shift != 0:
             return [self._demix_pitched(m) for m in mixes]
@@ -228,10 +228,9 @@ class MDXCDemixer:
     def demix_many_dev(self, mixes_d):
         """``demix_dev`` for a list of (already normalised) device mixes in ONE pooled engine call: a list of (names, CUDA tensor)
         as ``demix_dev`` gives them, the residual stem of a single-target model made per song.  Only enqueues work.  With
-        ``pitch_shift`` there is no device path (``demix_dev`` has none either): use ``demix_many``."""
+        ``pitch_shift`` the round trip stays in HBM (``_pitched_many_dev``): one pooled converter call down, the pooled demix on the
+        pitched mixes, one pooled converter call back for all stems of all songs."""
         import torch
-        if self.pitch_shift != 0:
-            raise NotImplementedError("pitch_shift runs on host arrays: demix_many")
         if not mixes_d:
             return []
         st = torch.cuda.current_stream(mixes_d[0].device).cuda_stream
@@ -242,11 +241,10 @@ class MDXCDemixer:
             n_out = self.v3.num_targets
             multi = n_out > 1
         raws = [torch.empty((n_out + 1, 2, m.shape[1]), dtype=torch.float32, device=m.device) for m in mixes_d]   # + a residual row
-        songs = [(m.data_ptr(), r.data_ptr(), m.shape[1]) for m, r in zip(mixes_d, raws)]
-        if self.is_roformer:
-            self.engine.rof_demix_batch_dev(songs, self.roformer_step(), stream=st)
+        if self.pitch_shift != 0:
+            self._pitched_many_dev(mixes_d, raws, n_out if multi else 1, st)
         else:
-            self.engine.mdxc_demix_batch_dev(songs, int(self.overlap), stream=st)
+            self._pool_dev([(m.data_ptr(), r.data_ptr(), m.shape[1]) for m, r in zip(mixes_d, raws)], st)
         res = []
         for mix_d, raw in zip(mixes_d, raws):
             if multi:
@@ -257,6 +255,51 @@ class MDXCDemixer:
             else:
                 res.append(([None], raw[:1]))
         return res
+
+    def _pool_dev(self, songs, st):
+        """The pooled demix of ``(mix_ptr, out_ptr, n_samples)`` songs, every array in HBM."""
+        if self.is_roformer:
+            self.engine.rof_demix_batch_dev(songs, self.roformer_step(), stream=st)
+        else:
+            self.engine.mdxc_demix_batch_dev(songs, int(self.overlap), stream=st)
+
+    def pitch_ratios(self):
+        """(down, back): the ratios the two ``change_pitch_semitones`` calls of the pitch round trip hand the converter -- the mix by
+        ``-pitch_shift`` from ``sample_rate``, every stem by ``+pitch_shift`` from the pitched rate -- formed by its very expressions."""
+        sr = self.sample_rate
+        target = sr * 2 ** (-self.pitch_shift / 12)
+        back = target * 2 ** (self.pitch_shift / 12)
+        return float(target) / sr, float(back) / target
+
+    def pitched_len(self, n: int) -> int:
+        """Samples of the pitched mix of an ``n``-sample mix: librosa's length, as ``Engine.resample_sinc`` forms it."""
+        return int(np.ceil(int(n) * self.pitch_ratios()[0]))
+
+    def _pitched_many_dev(self, mixes_d, raws, rows, st):
+        """``_demix_pitched`` for device mixes, into the first ``rows`` stems of every ``raws[i]`` [*, 2, N_i]: the mixes to the
+        pitched rate in one converter call (asx_resample_sinc_batch_dev, one-channel calls as ``change_pitch_semitones`` makes them),
+        the pooled demix at the pitched lengths, every stem back in one converter call whose ``n_out`` is the ORIGINAL length --
+        ``match_array_shapes``' trim or zero pad without a pass of its own.  Same kernels and same doubles as the host path."""
+        import torch
+        down, back = self.pitch_ratios()
+        lens = [self.pitched_len(m.shape[1]) for m in mixes_d]
+        if self.is_roformer:
+            for i, n in enumerate(lens):          # what the pooled call would refuse, before the converter has run
+                if n < self.chunk_size:
+                    raise ValueError(f"song {i}: pitched mix ({n} samples) shorter than one chunk ({self.chunk_size}): "
+                                     "not supported on the Roformer path")
+            n_net = int(self.engine.rof_cfg.n_out)
+        else:
+            n_net = self.v3.num_targets
+        dev = mixes_d[0].device
+        pitched = [torch.empty((2, n), dtype=torch.float32, device=dev) for n in lens]
+        self.engine.resample_sinc_batch_dev([(m.data_ptr(), p.data_ptr(), m.shape[1], n, 2) for m, p, n in zip(mixes_d, pitched, lens)],
+                                            down, True, stream=st)
+        outs = [torch.empty((n_net, 2, n), dtype=torch.float32, device=dev) for n in lens]
+        self._pool_dev([(p.data_ptr(), o.data_ptr(), n) for p, o, n in zip(pitched, outs, lens)], st)
+        # rows [rows, 2, n'] -> [rows, 2, N] are 2 * rows planar channels of one job
+        self.engine.resample_sinc_batch_dev([(o.data_ptr(), r.data_ptr(), n, r.shape[2], 2 * rows) for o, r, n in zip(outs, raws, lens)],
+                                            back, True, stream=st)
 
     def demix(self, mix: np.ndarray):
         """mdxc_separator.py:257-468 for TFC-TDF models: dict of stems, or the primary array."""
