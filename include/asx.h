@@ -811,6 +811,7 @@ int asx_invert_stem_batch_dev(asx_engine *e, asx_invert_song *songs, int32_t n_s
  * "wino6_launches" (conv_wino6_kernel: Winograd F(2x2,3x3) on the 16-bit pipe), "wino6h_launches" (those on the fp16 x 3 arithmetic),
  * "conv3h_launches" (ABI 7: conv3h_kernel, the direct fp16 x 3 convolution of the 48-channel level),
  * "conv3h_fin_launches" (those of them in the fused-input form, option "conv_fuse_input": one per net pass where it applies),
+ * "tdf_fused_output_launches" (additive: the tdf3_kernel launches in the fused-output form, option "tdf_fuse_output": one per net pass where it applies),
  * "conv3h_tiled_launches" (additive: those of them with a tile-order input or output, option "conv3h_tiled"),
  * "down6_launches" / "up6_launches" (ABI 7: conv_down6_kernel / conv_up6_kernel, the level-change convs on the 16-bit matrix pipe),
  * "hd_rounds" (ABI 7: rounds of chunk groups the Demucs v3 forward has run -- the groups of a round share the BLSTM launches),
@@ -990,6 +991,14 @@ int asx_op_dconv(asx_engine *e, float *y_host, int32_t b, int32_t o, int32_t i, 
  * conv3h_kernel at 48 channels, its producer waves compute the net's 1x1 input convolution (4 -> 48 channels, folded BatchNorm, ReLU) themselves
  * from the four spectrogram planes: no launch of its own, no 48-channel activation written to memory and read back.  0 = two launches.  A
  * GroupNorm net, another width or another 3x3 kernel: two launches either way.
+ * "tdf_fuse_output" (an option only, no environment variable): 1 (default) = the net's 1x1 output convolution (48 -> 4 channels, no activation) is
+ * computed in the epilogue of the last TDF block's second linear: that launch runs tdf3_kernel on channel-grouped row tiles (all 48 channels of
+ * four consecutive frames of one batch item per 192 x 128 tile), sums w_out[oc][c] * (relu(...) + x) over the channels in registers and two
+ * cross-lane steps, and writes the four output planes -- the block's 48-channel output is never written to memory and read back, and the conv has
+ * no launch of its own.  One fixed summation order: two runs give the same bits; the result differs from the two launches' in the last bits (the
+ * conv's sum runs in another order), a NaN stays inside its (batch item, frame).  0 = two launches.  Applies to a BatchNorm ConvTDFNet with a
+ * bottleneck whose last block has 48 channels, dim_t % 4 == 0 and dim_f % 128 == 0 and whose second linear runs the "gemm_f16x3" row GEMM; a
+ * GroupNorm net, another width, a ragged dim_t, "gemm_f16x3" = 0 or the TFC-TDF v3 nets: two launches either way, bit for bit as with 0.
  * "conv3h_partial_scratch" (an option only, no environment variable): how the n launches that make one 48-channel output slice of a 96- or
  * 144-channel conv3h_kernel layer hand their partial sum on.  1 (default) = through a private scratch buffer of the engine in the consumer
  * waves' fragment order (every lane stores and re-loads its own accumulator quads, 1 KB contiguous per instruction; only the last launch of a

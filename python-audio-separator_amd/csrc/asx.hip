@@ -96,6 +96,7 @@ static const struct EngineOption {
     {"gemm_f16x3", &asx_engine::gemm_f16x3, &EngineKnobs::gemm_f16x3, opt_onoff},
     {"conv_direct_f16x3", &asx_engine::conv3h, &EngineKnobs::conv3h, opt_nonneg},
     {"conv_fuse_input", &asx_engine::conv_fuse_input, &EngineKnobs::conv_fuse_input, opt_onoff},
+    {"tdf_fuse_output", &asx_engine::tdf_fuse_output, &EngineKnobs::tdf_fuse_output, opt_onoff},
     {"conv3h_partial_scratch", &asx_engine::conv3h_ps, &EngineKnobs::conv3h_ps, opt_onoff},
     {"conv3h_walk", &asx_engine::conv3h_walk, &EngineKnobs::conv3h_walk, opt_onoff},
     {"conv3h_tiled", &asx_engine::conv3h_tiled, &EngineKnobs::conv3h_tiled, opt_onoff},
@@ -260,6 +261,7 @@ static void free_conv(ConvLayer &L) {
   L.wu6h.release();
   L.w3h.release();
   L.w1f.release();
+  L.wof.release();
   L.wd6.release();
   L.wup6.release();
   L.gn_w.release();
@@ -2849,6 +2851,7 @@ int asx_counter(const asx_engine *e, const char *name, int64_t *out) {
   else if (nm == "conv3h_launches") *out = (int64_t)g_conv3h_launches.load();
   else if (nm == "conv3h_fin_launches") *out = (int64_t)g_conv3h_fin_launches.load();
   else if (nm == "conv3h_tiled_launches") *out = (int64_t)g_conv3h_tiled_launches.load();
+  else if (nm == "tdf_fused_output_launches") *out = (int64_t)g_tdf_fused_output_launches.load();
   else if (nm == "tdf3_pair_image_launches") *out = (int64_t)g_tdf3ps_launches.load();
   else if (nm == "down6_launches") *out = (int64_t)g_down6_launches.load();
   else if (nm == "up6_launches") *out = (int64_t)g_up6_launches.load();

@@ -120,6 +120,7 @@ struct ConvLayer {
   DevBuf wu6h;     // the same for the fp16 x 3 arithmetic (wino6_pack_h): two fp16 parts per U, scaled per (position, cout); exponents behind the fragments
   DevBuf w3h;      // conv3h_kernel (kernels_conv3h.h): the 48 -> 48 layers' two-part fp16 weights in fragment order, one exponent per output channel
   DevBuf w1f;      // CK_1X1 of 4 -> 48 channels: w [48][4] then b [48] as plain fp32, for the fused-input form of conv3h_kernel (the 3x3 conv behind it computes this layer in its producer)
+  DevBuf wof;      // CK_1X1 of 48 -> 4 channels: w as [48][4] (channel major) then b [4] as plain fp32, for the fused-output form of tdf3_kernel (the linear in front of it computes this layer in its epilogue)
   DevBuf wd6;      // CK_DOWN: conv_down6_kernel (kernels_updown6.h): the weights split three ways into bf16, fragment order [CG48][stage of 8 channels][part][n][lane][8]
   int wd6_cg = 0, wd6_nst = 0, wd6_nrep = 3;
   DevBuf wup6;     // CK_UP: conv_up6_kernel (kernels_updown6.h): [CG][stage of 32 channels][part][n][lane][8 bf16] over the 4 Cout virtual channels
@@ -305,6 +306,11 @@ struct asx_engine {
   // memory and read back.  0: two launches.  Only where the first 3x3 layer runs conv3h_kernel at 48 channels and the net uses BatchNorm.
   // asx_set_option("conv_fuse_input", n).
   int conv_fuse_input = 1;
+  // 1 (default): the net's 1x1 output conv (48 -> 4 channels, no activation) is computed in the epilogue of the last TDF block's second linear
+  // (tdf3_kernel's channel-grouped form, kernels_gemm3.h TdfCgMap): the 48-channel level-0 output of that block is never written to memory and
+  // read back, and the conv has no launch of its own.  0: two launches.  Only for a BatchNorm net with a bottleneck whose last block has 48
+  // channels, T % 4 == 0 and F % 128 == 0 and whose second linear runs the fp16 x 3 row GEMM.  asx_set_option("tdf_fuse_output", n).
+  int tdf_fuse_output = 1;
   // 1 (default): the 2 x 2 / stride-2 convolutions between the levels run conv_down6_kernel (kernels_updown6.h: bf16 x 6 -- exact three-way split
   // operands on the 16-bit matrix pipe, fp32 accumulation) while "gemm_bf16x6" is on; 0: the fp32-MFMA kernel conv_dma_kernel<2, 2, 2, 0, ...>.
   // ASX_DOWN6 or asx_set_option("conv_down_bf16x6", n).

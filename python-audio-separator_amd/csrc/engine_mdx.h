@@ -204,6 +204,15 @@ static int conv_pack(ConvLayer &L, const float *w, const float *b, int wino_mode
     CHK(L.w1f.ensure(w1.size() * 4));
     HIPCHK(hipMemcpy(L.w1f.p, w1.data(), w1.size() * 4, hipMemcpyHostToDevice));
   }
+  if (L.kind == CK_1X1 && L.cin == TdfCgMap::C && L.cout == 4) {
+    // any 1x1 layer of 48 -> 4 channels (196 floats; only a ConvTDFNet's output conv is ever fused) as tdf3_kernel's fused-output form reads it: w [48][4], then b [4]
+    std::vector<float> wo((size_t)TdfCgMap::C * 4 + 4, 0.f);
+    for (int oc = 0; oc < 4; ++oc)
+      for (int c = 0; c < TdfCgMap::C; ++c) wo[(size_t)c * 4 + oc] = w[(size_t)oc * TdfCgMap::C + c];
+    if (b) memcpy(wo.data() + TdfCgMap::C * 4, b, 4 * 4);
+    CHK(L.wof.ensure(wo.size() * 4));
+    HIPCHK(hipMemcpy(L.wof.p, wo.data(), wo.size() * 4, hipMemcpyHostToDevice));
+  }
   if (L.kind == CK_DOWN) {
     // bf16 x 6 image of the 2 x 2 / stride-2 conv (kernels_updown6.h); which kernel RUNS is the engine's "gemm_bf16x6" option at launch time
     std::vector<uint32_t> w6;
@@ -968,11 +977,12 @@ static int tdf3_tile_form(const asx_engine *e, const TdfDmaArgs &d) {
 
 // Will launch_tdf_dma_auto run this layer on the fp16 x 3 form of tdf3_kernel?  Only then may its x be a pair image, or its y be written as
 // one (TdfDmaArgs::xexp / yexp).  Builds (and caches) the layer's split weight image, so that the launch itself cannot fall back.
-static bool tdf3h_will_run(asx_engine *e, const TdfDmaArgs &d, hipStream_t s) {
-  const bool dbg = knobs().tdf3_abl_set || knobs().f16x3_n_set;   // bisection aids of launch_tdf3: no pair images with them
-  if (dbg || e->gemm_f16x3 <= 0 || e->pair_images <= 0 || tdf3_tile_form(e, d) == 0) return false;
+static bool tdf3h_takes(asx_engine *e, const TdfDmaArgs &d, hipStream_t s) {
+  const bool dbg = knobs().tdf3_abl_set || knobs().f16x3_n_set;   // bisection aids of launch_tdf3: no pair images, no fused output with them
+  if (dbg || e->gemm_f16x3 <= 0 || tdf3_tile_form(e, d) == 0) return false;
   return w3_image(e, d.w, d.N, d.K, s, 0, 1) != nullptr;
 }
+static bool tdf3h_will_run(asx_engine *e, const TdfDmaArgs &d, hipStream_t s) { return e->pair_images > 0 && tdf3h_takes(e, d, s); }
 // columns per exponent span of the pair image this layer writes (its column tile)
 static int tdf3_tile_cols(const asx_engine *e, const TdfDmaArgs &d) { return tdf3_tile_form(e, d) == 3 ? 192 : 128; }
 // consumer side of a pair image written in `cols`-column spans: K of the consumer = N of the producer
@@ -981,6 +991,39 @@ static void tdf3_set_xexp(TdfDmaArgs &d, const int *tab, int cols) {
   d.xexp_gs = cols / 32;
   d.xexp_n = (d.K + cols - 1) / cols;
   d.xexp_inv = (65536 + d.xexp_gs - 1) / d.xexp_gs;   // (stage * inv) >> 16 == stage / gs for every stage < 65536 / gs (gs <= 64: K < 2^21 / ... checked by the caller's K)
+}
+
+// ---- the net's last linear with the 48 -> 4 output conv in its epilogue (kernels_gemm3.h: template flag CG, TdfCgMap; option "tdf_fuse_output")
+static std::atomic<long long> g_tdf_fused_output_launches{0};
+struct TdfFusedOut {
+  const ConvLayer *fin;     // the net's output conv
+  float *out;               // its destination [B, 4, T, F]
+  bool done;                // set by tdf_pair_launch when the fused form ran: the caller skips the conv's own launch
+};
+// d: the second linear as tdf_fill_args states it.  Everything the kernel's address arithmetic relies on is checked here; any miss means the two launches.
+static bool tdf_fused_output_ok(asx_engine *e, const TdfDmaArgs &d, const TdfFusedOut &fo, hipStream_t s) {
+  const ConvLayer &L = *fo.fin;
+  const int64_t ldr = d.ldr ? d.ldr : d.N;
+  return e->tdf_fuse_output > 0 && L.kind == CK_1X1 && L.cin == TdfCgMap::C && L.cout == 4 && !L.relu && L.wof.p != nullptr && L.gn_w.p == nullptr &&
+         d.C == TdfCgMap::C && d.T > 0 && d.T % TdfCgMap::TQ == 0 && d.N % TdfCgMap::BN == 0 && d.M > 0 && d.M % ((int64_t)TdfCgMap::C * d.T) == 0 &&
+         d.relu == 1 && d.res != nullptr && d.rscale == nullptr && d.rot_tab == nullptr && d.xexp == nullptr && d.yexp == nullptr && d.lda == 0 && d.ldy == 0 &&
+         (reinterpret_cast<uintptr_t>(fo.out) & 15) == 0 && (uint64_t)4 * (uint64_t)d.T * (uint64_t)ldr * 4 < (1ull << 31) &&   // the residual's lane offset: three channels and three frames
+         tdf3h_takes(e, d, s);                           // tdf3_ok (K % 32 == 0, K >= 64, M < 2^31, alignments) and the split weight image, built now
+}
+static void launch_tdf3_cg(asx_engine *e, const TdfDmaArgs &a0, const u32x4 *w3, hipStream_t s) {
+  constexpr int LDS_BYTES = tdf3h_lds_bytes(TdfCgMap::BM);   // 52240: above the 48 KB a kernel gets unasked
+  auto kern = tdf3_kernel<2, TdfCgMap::MREP, 0, false, true, false, 4, true>;
+  grant_lds(kern, LDS_BYTES);
+  TdfDmaArgs a = a0;
+  const int64_t nbm = a.M / TdfCgMap::BM;               // M = B 48 T, T % 4 == 0: B T / 4 tiles, all full
+  const int nbn = a.N / TdfCgMap::BN;
+  const int map_env = knobs().tdf3_map;
+  a.tile_map = map_env >= 0 ? (nbn >= 8 ? map_env % 10 : map_env / 10) : (nbn < 8 ? 1 : 0);   // as launch_tdf3_abl
+  e->prof_nprod = 3;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(nbm * nbn)), dim3(256), LDS_BYTES, s, a, w3, RowGather{});
+  g_tdf3_launches.fetch_add(1);
+  g_tdf3h_launches.fetch_add(1);
+  g_tdf_fused_output_launches.fetch_add(1);
 }
 
 static void launch_tdf_dma_auto(asx_engine *e, const TdfDmaArgs &d, hipStream_t s) {
@@ -1075,8 +1118,10 @@ static int tdf_launch(asx_engine *e, const TdfLayer &L, const float *x, const fl
 // out = x + tdf1(tdf0(x)): the two linears of a TDF block with a bottleneck (modules.py:61-70).  The bottleneck activations H have one reader,
 // the second linear: when both linears run on the fp16 x 3 row GEMM the first writes H as a pair image (split once, in its epilogue; exponent
 // spans in HE) and the second multiplies the parts as they are (kernels_gemm3.h, "operands split by their producer").
+// fo != nullptr (the net's last block only): `out` has one reader, the 48 -> 4 output conv fo->fin -- where tdf_fused_output_ok() the second linear
+// computes that conv in its epilogue, writes fo->out instead of `out` and sets fo->done
 static int tdf_pair_launch(asx_engine *e, const TdfLayer &L0, const TdfLayer &L1, const float *x, float *H, int *HE, float *out, int64_t M, int T,
-                           hipStream_t s) {
+                           hipStream_t s, TdfFusedOut *fo = nullptr) {
   int *pair_tab = nullptr;
   int pair_cols = 0;
   if (M > 0 && HE != nullptr) {
@@ -1090,6 +1135,26 @@ static int tdf_pair_launch(asx_engine *e, const TdfLayer &L0, const TdfLayer &L1
     }
   }
   CHK(tdf_launch(e, L0, x, nullptr, H, M, T, s, 1, pair_tab, nullptr, pair_cols));
+  if (fo != nullptr && pair_tab == nullptr && M > 0 && L1.k % 4 == 0 && (reinterpret_cast<uintptr_t>(H) & 15) == 0 && !knobs().no_dma) {
+    TdfDmaArgs d;
+    tdf_fill_args(e, L1, H, x, out, M, T, 1, d);
+    if (tdf_fused_output_ok(e, d, *fo, s)) {
+      d.y = nullptr;
+      d.fo_w = fo->fin->wof.f();
+      d.fo_out = fo->out;
+      d.fo_bs = (int64_t)4 * T * L1.n;
+      const u32x4 *w3 = w3_image(e, d.w, d.N, d.K, s, 0, 1);   // cached by tdf3h_takes
+      if (w3 != nullptr) {
+        // the linear's work plus the output conv's; the linear's bytes without the y write, with the four output planes
+        const double bt = (double)M / TdfCgMap::C;
+        const double flops = 2.0 * (double)M * L1.n * L1.k + 2.0 * 4 * TdfCgMap::C * bt * L1.n;
+        const double bytes = 4.0 * ((double)M * L1.k + (double)M * L1.n + (double)L1.n * L1.k + 4.0 * bt * L1.n);
+        CHK(timed(e, ASX_PROF_TDF, flops, bytes, s, [&]() { launch_tdf3_cg(e, d, w3, s); }));
+        fo->done = true;
+        return ASX_OK;
+      }
+    }
+  }
   return tdf_launch(e, L1, H, x, out, M, T, s, 1, nullptr, pair_tab, pair_cols);
 }
 
@@ -1272,7 +1337,9 @@ static int gn_launch(asx_engine *e, const float *x, int B, int C, int64_t P, con
 
 // fin_x != nullptr (the net's first block only): `cur` holds nothing yet -- the first TFC conv computes the net's input conv e->first of fin_x
 // itself (conv3h_kernel's fused-input form) and writes where it would have written: the rotation through e->R is the same either way
-static int block_forward(asx_engine *e, const Block &blk, float *&cur, float *dest, int B, hipStream_t s, const float *fin_x = nullptr) {
+// fo != nullptr (the net's last block only): the block's output has one reader, the net's output conv -- tdf_pair_launch may compute it (fo->done)
+static int block_forward(asx_engine *e, const Block &blk, float *&cur, float *dest, int B, hipStream_t s, const float *fin_x = nullptr,
+                         TdfFusedOut *fo = nullptr) {
   // TFC convs rotate through e->R; the TDF output goes to `dest` (or a free R buffer when dest == nullptr)
   auto next_free = [&](const float *a, const float *b) -> float * {
     for (int i = 0; i < 3; ++i)
@@ -1338,7 +1405,7 @@ static int block_forward(asx_engine *e, const Block &blk, float *&cur, float *de
   // (A/B ASX_TDF_INPLACE=1: x + tdf(x) written over x where no skip copy is needed -- every output element depends on the
   // same element of x only)
   float *out = dest ? dest : (knobs().tdf_inplace ? cur : next_free(cur, nullptr));
-  CHK(tdf_pair_launch(e, blk.tdf0, blk.tdf1, cur, e->H.f(), reinterpret_cast<int *>(e->HE.p), out, M, blk.t, s));
+  CHK(tdf_pair_launch(e, blk.tdf0, blk.tdf1, cur, e->H.f(), reinterpret_cast<int *>(e->HE.p), out, M, blk.t, s, dest == nullptr ? fo : nullptr));
   cur = out;
   return ASX_OK;
 }
@@ -1373,7 +1440,12 @@ static int net_forward_dev(asx_engine *e, const float *spec_in, float *spec_out,
       CHK(gn_launch(e, out, B, e->ds[i].cout, (int64_t)(e->enc[i].t / 2) * (e->enc[i].f / 2), e->ds[i].gn_w, e->ds[i].gn_b, nullptr, nullptr, out, s));
     cur = out;
   }
-  CHK(block_forward(e, e->mid, cur, nullptr, B, s, n == 0 ? fin_x : nullptr));
+  // The output conv (48 -> 4 channels) is the only reader of the last block's output: where that block's second TDF linear runs tdf3_kernel's
+  // channel-grouped form it computes the conv in its epilogue (option "tdf_fuse_output") and the 48-channel tensor never reaches memory.
+  TdfFusedOut fo{&e->final_, spec_out, false};
+  const Block &last = n > 0 ? e->dec[n - 1] : e->mid;
+  const bool try_fo = !gn && last.t == T && last.f == F;
+  CHK(block_forward(e, e->mid, cur, nullptr, B, s, n == 0 ? fin_x : nullptr, n == 0 && try_fo ? &fo : nullptr));
   for (int i = 0; i < n; ++i) {
     const Block &blk = e->dec[i];
     float *out = nullptr;
@@ -1387,9 +1459,9 @@ static int net_forward_dev(asx_engine *e, const float *spec_in, float *spec_out,
     if (gn)   // norm + ReLU first, then `x *= ds_outputs[-i - 1]` (mdxnet.py:111-113)
       CHK(gn_launch(e, out, B, e->us[i].cout, (int64_t)blk.t * blk.f, e->us[i].gn_w, e->us[i].gn_b, nullptr, e->skip[n - 1 - i].f(), out, s));
     cur = out;
-    CHK(block_forward(e, blk, cur, nullptr, B, s));
+    CHK(block_forward(e, blk, cur, nullptr, B, s, nullptr, i == n - 1 && try_fo ? &fo : nullptr));
   }
-  CHK(conv_launch(e, e->final_, cur, nullptr, spec_out, B, T, F, s));
+  if (!fo.done) CHK(conv_launch(e, e->final_, cur, nullptr, spec_out, B, T, F, s));
   return ASX_OK;
 }
 

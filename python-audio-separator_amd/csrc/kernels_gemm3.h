@@ -278,10 +278,36 @@ constexpr int tdf3h_lds_bytes(int BM) { return 2 * 2 * BM * 64 + 16 * BM + 16; }
 // the accumulators are never rescaled.  Any H build WRITES a pair image when TdfDmaArgs::yexp is set (epilogue).
 // NW: waves per workgroup, 4 or 8.  Eight waves share ONE x tile between two 4-wave column halves (tile 128 x 32 NREP NW columns: 128 x 384 for
 // NREP = 3) -- half the x loads, splits and LDS stores per MFMA of the 4-wave form, one workgroup per CU instead of two.
-template <int NREP, int MREP, int ABL = 0, bool GATHER = false, bool H = false, bool PS = false, int NW = 4>
+// CG (H only, NREP = 2, MREP = 12: 192 x 128 tiles; TdfDmaArgs::fo_*): CHANNEL-GROUPED row tiles with the net's 48 -> 4 output conv in the
+// epilogue.  A plain row tile is 16 MREP consecutive rows of (b, c, t) -- frames of ONE channel -- so a sum over channels would cross
+// workgroups.  Here a tile holds all 48 channels of four consecutive frames of one batch item (TdfCgMap below): the 16 rows of accumulator
+// group m are channels 4 m .. 4 m + 3 (lane bits 0-1) of frames 4 tq .. 4 tq + 3 (lane bits 2-3), so every channel of a (b, t) sits in ONE
+// wave's registers for a given column.  The x fetch, the residual ring and the scale / shift channel go through the map; stage loop, split,
+// rescale rule and MFMA order are those of every other H build (each element of the linear sees the same products in the same order).  The
+// epilogue forms o = relu(sc (acc + bias) + sh) + res as the ReLU path does, does not store it, and adds w_out[oc][c] * o into 4 x 8 partial
+// sums per lane (fmaf, m ascending); two quad-permute steps then sum the four channel lanes of a frame, each lane giving half of its values
+// away per step ((cl0 + cl1) + (cl2 + cl3), one fixed order: two runs give the same bits), and a lane ends with the eight columns of ONE
+// output channel, stored as two float4.  No atomics, no exchange between workgroups, no pass through LDS.
+struct TdfCgMap {
+  static constexpr int C = 48, TQ = 4, MREP = 12, BM = C * TQ, BN = 128;   // channels, frames per tile; 192 rows x 128 columns
+  // local row r = 16 m + li of a tile: channel 4 m + (li & 3), frame (li >> 2) of the tile's four
+  static constexpr int chan(int r) { return (r >> 4) * 4 + (r & 3); }
+  static constexpr int frame(int r) { return (r & 15) >> 2; }
+  // tile bm_i = b * (T / 4) + tq; global row (b C + c) T + t of x / res
+  static constexpr long long row_of(long long b, int tq, int r, int T) { return (b * C + chan(r)) * T + TQ * tq + frame(r); }
+  static constexpr long long row(long long bm_i, int r, int T) { return row_of(bm_i / (T / TQ), (int)(bm_i % (T / TQ)), r, T); }
+  // after the two give-away steps lane (li, lk) of wave w holds output channel out_oc of frame out_frame, columns out_col(w, lane, j), j = 0 .. 7
+  static constexpr int out_oc(int lane) { return 2 * (lane & 1) + ((lane >> 1) & 1); }
+  static constexpr int out_frame(int lane) { return (lane & 15) >> 2; }
+  static constexpr int out_col(int wave, int lane, int j) { return wave * 32 + (j >> 2) * 16 + (lane >> 4) * 4 + (j & 3); }
+};
+// (end of TdfCgMap)
+
+template <int NREP, int MREP, int ABL = 0, bool GATHER = false, bool H = false, bool PS = false, int NW = 4, bool CG = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void tdf3_kernel(TdfDmaArgs a, const u32x4 *__restrict__ w3, RowGather gq) {
   static_assert(!PS || (H && !GATHER), "pair-image operands: fp16 x 3 arithmetic, plain row GEMM");
   static_assert(NW == 4 || (NW == 8 && MREP == 8 && !GATHER), "eight waves: 128-row tiles of the plain row GEMM");
+  static_assert(!CG || (H && !GATHER && !PS && NW == 4 && NREP == 2 && MREP == TdfCgMap::MREP && ABL == 0), "channel-grouped tiles: 192 x 128, fp16 x 3");
   constexpr int NT = 64 * NW;                         // threads
   constexpr int BM = 16 * MREP, BN = 16 * NREP * NW;
   constexpr int XC = BM * 4 / NT;                     // 8-float chunks per thread and stage (BM * 4 chunks / NT threads)
@@ -332,6 +358,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void tdf3_kernel(TdfDmaAr
   }
   const int64_t m0 = bm_i * BM;
   const int n0 = bg * BN;
+  // CG: the tile's batch item and frame quad (launcher: T % 4 == 0, M == B * 48 * T < 2^31)
+  const int cg_b = CG ? (int)((uint32_t)bm_i / (uint32_t)(a.T >> 2)) : 0;
+  const int cg_tq = CG ? (int)((uint32_t)bm_i - (uint32_t)cg_b * (uint32_t)(a.T >> 2)) : 0;
   const int64_t lda = a.lda ? a.lda : a.K, ldy = a.ldy ? a.ldy : a.N, ldr = a.ldr ? a.ldr : a.N;
   // K % 32 == 0 (launcher).  The stage loop runs PAIRS of stages: for an odd stage count the image carries one more stage of zero
   // weights, and the x loads of that stage re-read the last real one (finite data times zero).
@@ -383,6 +412,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void tdf3_kernel(TdfDmaAr
       xp[i] = a.x + b * gq.x_bs + ((int64_t)po[i] * gq.I + pi[i]) * gq.ldc + c * 8;
       if (!rok) po[i] = -(1 << 20);
     } else {
+      if constexpr (CG) r = TdfCgMap::row_of(cg_b, cg_tq, row, a.T);   // every row of a channel-grouped tile exists
       r = r < a.M ? r : a.M - 1;
       xp[i] = a.x + r * lda + c * 8;
       po[i] = pi[i] = 0;
@@ -757,6 +787,99 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void tdf3_kernel(TdfDmaAr
       }
       return;
     }
+  }
+  if constexpr (CG) {
+    // ---- ReLU + residual as below (every tile is full), then the 48 -> 4 output conv over the tile's channels instead of the store
+    const int cl = li & 3, tl = li >> 2;
+    f32x4 bz[NREP];
+#pragma unroll
+    for (int n = 0; n < NREP; ++n)
+      bz[n] = (a.bias != nullptr) ? *reinterpret_cast<const f32x4 *>(a.bias + n0 + wave * 16 * NREP + n * 16 + lk * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    // residual: row group m starts 4 m channels behind the tile's first row; a lane's row is cl channels and tl frames further (launcher:
+    // 4 T ldr 4 bytes < 2^31)
+    const uint32_t voff_r = (uint32_t)(((cl * a.T + tl) * (int)ldr + wave * 16 * NREP + lk * 4) * 4);
+    const char *rb0 = reinterpret_cast<const char *>(a.res) + ((((int64_t)cg_b * TdfCgMap::C) * a.T + TdfCgMap::TQ * cg_tq) * ldr + n0) * 4;
+    const int64_t rstep = (int64_t)4 * a.T * ldr * 4;  // bytes between channel quads
+    constexpr int RING = 4;
+    f32x4 rs[RING][NREP];
+    auto fetch = [&](int m) {
+      const char *rb = rb0 + m * rstep;
+#pragma unroll
+      for (int n = 0; n < NREP; ++n)
+        rs[m % RING][n] = (a.res == nullptr) ? (f32x4){0.f, 0.f, 0.f, 0.f}
+                          : ((a.nt & 2) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(rb + voff_r + n * 64))
+                                        : *reinterpret_cast<const f32x4 *>(rb + voff_r + n * 64));
+    };
+#pragma unroll
+    for (int m = 0; m < RING; ++m) fetch(m);
+    const f32x4 *wq = reinterpret_cast<const f32x4 *>(a.fo_w) + cl;   // w_out[0 .. 3][c] of channel c = 4 m + cl at wq[4 m]
+    float p[4][4 * NREP];                              // partial sums: output channel x this lane's eight columns
+#pragma unroll
+    for (int oc = 0; oc < 4; ++oc)
+#pragma unroll
+      for (int j = 0; j < 4 * NREP; ++j) p[oc][j] = 0.f;
+    // the channel's scale / shift / w_out column travel one row group ahead of their use
+    f32x4 w4n = wq[0];
+    float scn = a.scale ? a.scale[cl] : 1.f, shn = a.shift ? a.shift[cl] : 0.f;
+#pragma unroll
+    for (int m = 0; m < MREP; ++m) {
+      const float sc = scn, sh = shn;
+      const float wv[4] = {w4n.x, w4n.y, w4n.z, w4n.w};
+      if (m + 1 < MREP) {
+        const int c = (m + 1) * 4 + cl;
+        w4n = wq[(m + 1) * 4];
+        scn = a.scale ? a.scale[c] : 1.f;
+        shn = a.shift ? a.shift[c] : 0.f;
+      }
+#pragma unroll
+      for (int n = 0; n < NREP; ++n) {
+        const f32x4 v = acc[n][m];
+        const f32x4 r = rs[m % RING][n];
+        float o[4];
+        o[0] = fmaxf(sc * (v.x + bz[n].x) + sh, 0.f) + r.x;
+        o[1] = fmaxf(sc * (v.y + bz[n].y) + sh, 0.f) + r.y;
+        o[2] = fmaxf(sc * (v.z + bz[n].z) + sh, 0.f) + r.z;
+        o[3] = fmaxf(sc * (v.w + bz[n].w) + sh, 0.f) + r.w;
+#pragma unroll
+        for (int oc = 0; oc < 4; ++oc) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) p[oc][n * 4 + j] = __fmaf_rn(wv[oc], o[j], p[oc][n * 4 + j]);
+          // nothing is stored until the end: without an anchor per group the arithmetic of all twelve sinks below the loads of all twelve
+          asm volatile("" : "+v"(p[oc][n * 4 + 0]), "+v"(p[oc][n * 4 + 1]), "+v"(p[oc][n * 4 + 2]), "+v"(p[oc][n * 4 + 3]));
+        }
+      }
+      if (m + RING < MREP) fetch(m + RING);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // sum over the four channel lanes cl of a frame.  Step 1 (partner cl ^ 1): a lane with cl & 1 == 0 keeps output channels 0 / 1 and gives 2 / 3
+    // away, its partner the other way round.  Step 2 (partner cl ^ 2): of the two kept, cl & 2 == 0 keeps the first.  TdfCgMap::out_oc is the result.
+    auto quad_xor1 = [](float v) { return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0xB1, 0xf, 0xf, false)); };   // quad_perm [1, 0, 3, 2]
+    auto quad_xor2 = [](float v) { return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x4E, 0xf, 0xf, false)); };   // quad_perm [2, 3, 0, 1]
+    const bool b0 = (cl & 1) != 0, b1 = (cl & 2) != 0;
+    float q[2][4 * NREP];
+#pragma unroll
+    for (int o2 = 0; o2 < 2; ++o2)
+#pragma unroll
+      for (int j = 0; j < 4 * NREP; ++j) {
+        const float keep = b0 ? p[2 + o2][j] : p[o2][j];
+        const float give = b0 ? p[o2][j] : p[2 + o2][j];
+        q[o2][j] = keep + quad_xor1(give);
+      }
+    const int oc = TdfCgMap::out_oc(lane);
+    const float bo = a.fo_w[4 * TdfCgMap::C + oc];
+    float *ob = a.fo_out + (int64_t)cg_b * a.fo_bs + ((int64_t)oc * a.T + TdfCgMap::TQ * cg_tq + tl) * a.N + n0 + wave * 16 * NREP + lk * 4;
+#pragma unroll
+    for (int n = 0; n < NREP; ++n) {
+      float r4[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float keep = b1 ? q[1][n * 4 + j] : q[0][n * 4 + j];
+        const float give = b1 ? q[0][n * 4 + j] : q[1][n * 4 + j];
+        r4[j] = (keep + quad_xor2(give)) + bo;
+      }
+      *reinterpret_cast<f32x4 *>(ob + n * 16) = (f32x4){r4[0], r4[1], r4[2], r4[3]};
+    }
+    return;
   }
 #ifdef ASX_EXPERIMENTAL_KERNELS
   if constexpr (H && !GATHER) {

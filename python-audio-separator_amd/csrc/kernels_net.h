@@ -840,6 +840,12 @@ struct TdfDmaArgs {
   int xexp_inv;             // ceil(65536 / xexp_gs): stage -> span as (stage * xexp_inv) >> 16 (the launcher checks every stage of K)
   int *yexp;                // != nullptr: y is WRITTEN as a pair image, one span per column tile of the launch: yexp[row * yexp_n + tile]
   int yexp_n;               // (no residual, no rotary epilogue; N % 32 == 0)
+  // FUSED OUTPUT CONV (tdf3_kernel's channel-grouped form, template flag CG; kernels_gemm3.h TdfCgMap): the net's last linear, whose only reader is
+  // the 48 -> 4 1x1 output conv.  y is NOT written: the epilogue sums w_out[oc][c] * (relu(...) + res) over the 48 channels of every (b, t) and
+  // stores the four output planes.  C == 48, T % 4 == 0, N % 128 == 0, M == B * 48 * T (launcher).
+  const float *fo_w;        // w_out as [c 48][oc 4], then b_out [4]: 196 floats (ConvLayer::wof)
+  float *fo_out;            // [B, 4, T, N]
+  int64_t fo_bs;            // floats per batch item of fo_out
 };
 
 // rotary step of the row-GEMM epilogues on the float4 (row, col .. col + 3), col % 4 == 0.  Every product and sum is rounded

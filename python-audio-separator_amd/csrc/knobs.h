@@ -131,6 +131,7 @@ struct EngineKnobs {
   int wino6 = knob::clamped("ASX_WINO6", 144, 0);                 // "winograd_bf16x6"
   int conv3h = knob::clamped("ASX_CONV3H", 144, 0);               // "conv_direct_f16x3"
   int conv_fuse_input = 1;                                        // "conv_fuse_input": an option only -- tests/test_host_knobs.py pins the set of environment names this header reads
+  int tdf_fuse_output = 1;                                        // "tdf_fuse_output": an option only, as the one above
   int conv3h_ps = 1;                                              // "conv3h_partial_scratch": an option only, as the one above
   int conv3h_walk = 1;                                            // "conv3h_walk": an option only, too
   int conv3h_tiled = 1;                                           // "conv3h_tiled": an option only, too

@@ -3,6 +3,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/proto_gemm3 tools/proto_gemm3.hip && tools/proto_gemm3 [abl] [first] [last] [tile_map] [h]
 // h = 1: the fp16 x 3 arithmetic (tdf3_kernel<..., H = true>) in the tdf3 column; the "spread" shapes give x a 2^-20 decay along k (and
 // weights that look at the quiet half only in the first 16 columns): the case a block exponent has to survive.
+// argv[8] = 1: a TDF block's two linears through a pair image (run_chain); 2: the last linear with the output conv in its epilogue (run_cg).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -427,6 +428,127 @@ static void run_chain(const char *name, int64_t M, int F, int F8, int C, int T, 
     CK(hipFree(p));
 }
 
+// ---- the net's last linear with the 48 -> 4 output conv in its epilogue (argv[8] = 2): tdf3_kernel<2, 12, ..., CG> on channel-grouped row
+// tiles against the 128 x 192 tile that writes y, and the 192 x 128 tile on plain rows (the tile shape alone); the fused output against a
+// float64 output conv of the y the 128 x 192 launch wrote, on sampled (b, t)
+static void launch3h_cg(const TdfDmaArgs &a, const u32x4 *w3, hipStream_t s) {
+  constexpr int LDS = tdf3h_lds_bytes(TdfCgMap::BM);
+  static bool done = false;
+  if (!done) {
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&tdf3_kernel<2, 12, 0, false, true, false, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&tdf3_kernel<2, 12, 0, false, true, false, 4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    done = true;
+  }
+  const unsigned grid = (unsigned)((a.M / TdfCgMap::BM) * (a.N / TdfCgMap::BN));
+  if (a.fo_out) hipLaunchKernelGGL((tdf3_kernel<2, 12, 0, false, true, false, 4, true>), dim3(grid), dim3(256), LDS, s, a, w3, RowGather{});
+  else hipLaunchKernelGGL((tdf3_kernel<2, 12, 0, false, true, false, 4, false>), dim3(grid), dim3(256), LDS, s, a, w3, RowGather{});
+}
+static void run_cg(const char *name, int B, int T, int N, int K, int reps) {
+  const int C = TdfCgMap::C;
+  const int64_t M = (int64_t)B * C * T;
+  if (T % 4 || N % 128 || K % 32) { fprintf(stderr, "run_cg: shape\n"); exit(2); }
+  std::mt19937 rng(7 + N + T);
+  std::normal_distribution<float> nd(0.f, 1.f);
+  const int64_t HB = std::min<int64_t>(M, 4096);
+  std::vector<float> hx((size_t)HB * K), hw((size_t)N * K), hsc(C), hsh(C), hr((size_t)HB * N), hwo(4 * C + 4), hwt(4 * C + 4);
+  for (int64_t r = 0; r < HB; ++r) {
+    const float rowmag = std::ldexp(1.0f, (int)(r % 5) * 3 - 6);
+    for (int k = 0; k < K; ++k) hx[(size_t)r * K + k] = nd(rng) * rowmag;
+  }
+  for (auto &v : hw) v = nd(rng) / std::sqrt((float)K);
+  for (auto &v : hsc) v = 0.5f + 0.5f * std::fabs(nd(rng));
+  for (auto &v : hsh) v = 0.2f * nd(rng);
+  for (auto &v : hr) v = nd(rng);
+  for (auto &v : hwo) v = nd(rng) / std::sqrt((float)C);       // w_out [4][48], b_out [4]
+  for (int oc = 0; oc < 4; ++oc)
+    for (int c = 0; c < C; ++c) hwt[c * 4 + oc] = hwo[oc * C + c];
+  for (int oc = 0; oc < 4; ++oc) hwt[4 * C + oc] = hwo[4 * C + oc];
+  float *dx, *dw, *dsc, *dsh, *dr, *dy, *dwo, *dout;
+  u32x4 *dw3;
+  CK(hipMalloc(&dx, (size_t)M * K * 4));
+  CK(hipMalloc(&dw, hw.size() * 4));
+  CK(hipMalloc(&dsc, C * 4));
+  CK(hipMalloc(&dsh, C * 4));
+  CK(hipMalloc(&dr, (size_t)M * N * 4));
+  CK(hipMalloc(&dy, (size_t)M * N * 4));
+  CK(hipMalloc(&dwo, hwt.size() * 4));
+  CK(hipMalloc(&dout, (size_t)B * 4 * T * N * 4));
+  for (int64_t r0 = 0; r0 < M; r0 += HB) {
+    const int64_t n = std::min<int64_t>(HB, M - r0);
+    CK(hipMemcpy(dx + r0 * K, hx.data(), (size_t)n * K * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dr + r0 * N, hr.data(), (size_t)n * N * 4, hipMemcpyHostToDevice));
+  }
+  CK(hipMemcpy(dw, hw.data(), hw.size() * 4, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dsc, hsc.data(), C * 4, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dsh, hsh.data(), C * 4, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dwo, hwt.data(), hwt.size() * 4, hipMemcpyHostToDevice));
+  CK(hipMemset(dout, 0xff, (size_t)B * 4 * T * N * 4));
+  const int ntiles = (N + 15) / 16, nk = ((K + 63) / 64) * 2;
+  CK(hipMalloc(&dw3, (size_t)ntiles * nk * 2 * 1024 + (size_t)ntiles * 16));
+  hipLaunchKernelGGL(w3h_split_kernel, dim3((unsigned)ntiles), dim3(256), 0, 0, dw, dw3, N, K, ntiles);
+  CK(hipDeviceSynchronize());
+  TdfDmaArgs a{};
+  a.x = dx; a.w = dw; a.scale = dsc; a.shift = dsh; a.res = dr; a.y = dy; a.M = M; a.N = N; a.K = K; a.C = C; a.T = T; a.relu = 1;
+  a.tile_map = (N + 127) / 128 < 8 ? 1 : 0;
+  TdfDmaArgs f = a;
+  f.y = nullptr; f.fo_w = dwo; f.fo_out = dout; f.fo_bs = (int64_t)4 * T * N;
+  hipEvent_t e0, e1;
+  CK(hipEventCreate(&e0));
+  CK(hipEventCreate(&e1));
+  auto time_it = [&](auto &&fn) {
+    fn();
+    CK(hipDeviceSynchronize());
+    CK(hipEventRecord(e0, 0));
+    for (int i = 0; i < reps; ++i) fn();
+    CK(hipEventRecord(e1, 0));
+    CK(hipEventSynchronize(e1));
+    float ms;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    return (double)ms / reps;
+  };
+  const double t_cg = time_it([&]() { launch3h_cg(f, dw3, 0); });
+  const double t_212 = time_it([&]() { launch3h_cg(a, dw3, 0); });
+  const double t_38 = time_it([&]() { launch3h<3, 8>(a, dw3, 0); });     // last: dy holds ITS y below
+  CK(hipGetLastError());
+  // second fused run into another buffer: bit for bit
+  float *dout2;
+  CK(hipMalloc(&dout2, (size_t)B * 4 * T * N * 4));
+  f.fo_out = dout2;
+  launch3h_cg(f, dw3, 0);
+  CK(hipDeviceSynchronize());
+  const int nsamp = 32;
+  std::vector<float> yrow(N), o1(N), o2(N);
+  std::vector<double> ref((size_t)4 * N);
+  double err = 0, nrm = 0;
+  long long ndiff = 0, nonfin = 0;
+  for (int si = 0; si < nsamp; ++si) {
+    const int b = (int)((int64_t)si * B / nsamp), t = (si * 37 + 3) % T;
+    std::fill(ref.begin(), ref.end(), 0.0);
+    for (int c = 0; c < C; ++c) {
+      CK(hipMemcpy(yrow.data(), dy + (((int64_t)b * C + c) * T + t) * N, N * 4, hipMemcpyDeviceToHost));
+      for (int oc = 0; oc < 4; ++oc)
+        for (int n = 0; n < N; ++n) ref[(size_t)oc * N + n] += (double)hwo[oc * C + c] * yrow[n];
+    }
+    for (int oc = 0; oc < 4; ++oc) {
+      const int64_t off = (((int64_t)b * 4 + oc) * T + t) * N;
+      CK(hipMemcpy(o1.data(), dout + off, N * 4, hipMemcpyDeviceToHost));
+      CK(hipMemcpy(o2.data(), dout2 + off, N * 4, hipMemcpyDeviceToHost));
+      for (int n = 0; n < N; ++n) {
+        const double v = ref[(size_t)oc * N + n] + hwo[4 * C + oc];
+        if (!std::isfinite(o1[n])) ++nonfin;
+        if (memcmp(&o1[n], &o2[n], 4) != 0) ++ndiff;
+        err += (o1[n] - v) * (o1[n] - v);
+        nrm += v * v;
+      }
+    }
+  }
+  printf("%-14s B=%d T=%d N=%d K=%d | 128x192 (writes y) %.3f ms | 192x128 plain rows (writes y) %.3f ms | 192x128 channel-grouped + output conv %.3f ms\n"
+         "    fused output vs float64 conv of the 128x192 y: rel rms %.2e, nonfinite %lld, two fused runs differ in %lld of the sampled elements\n",
+         name, B, T, N, K, t_38, t_212, t_cg, std::sqrt(err / nrm), nonfin, ndiff);
+  fflush(stdout);
+  for (void *p : {(void *)dx, (void *)dw, (void *)dsc, (void *)dsh, (void *)dr, (void *)dy, (void *)dwo, (void *)dout, (void *)dout2, (void *)dw3}) CK(hipFree(p));
+}
+
 static int g_habl = 0;  // ablation of the fp16 x 3 launches (argv[1] when h = 1): 1 no split, 4 no epilogue traffic, 8 no weight loads, 16 no rescale, sums
 static void launch3h_sel(const TdfDmaArgs &a, const u32x4 *w3, hipStream_t s) {
   if (g_tile == 0 && g_habl) {
@@ -476,6 +598,11 @@ int main(int argc, char **argv) {
     run_chain("tdf L0 block", 675840, 3072, 384, 48, 256, 5);
     run_chain("tdf L1 block", 675840, 1536, 192, 96, 128, 5);
     run_chain("tdf L2 block", 506880, 768, 96, 144, 64, 5);
+    return 0;
+  }
+  if (argc > 8 && atoi(argv[8]) == 2) {
+    run_cg("small", 3, 12, 768, 96, 3);
+    run_cg("tdf L0 gemm2", 55, 256, 3072, 384, 5);
     return 0;
   }
   std::vector<Shape> shapes = {
