@@ -813,6 +813,8 @@ int asx_invert_stem_batch_dev(asx_engine *e, asx_invert_song *songs, int32_t n_s
  * "conv3h_fin_launches" (those of them in the fused-input form, option "conv_fuse_input": one per net pass where it applies),
  * "tdf_fused_output_launches" (additive: the tdf3_kernel launches in the fused-output form, option "tdf_fuse_output": one per net pass where it applies),
  * "conv3h_tiled_launches" (additive: those of them with a tile-order input or output, option "conv3h_tiled"),
+ * "conv3h_merged_dispatches" (additive: dispatches of conv3h_kernel that ran all n output slices of a layer on one input slice, option
+ * "conv3h_merge_out"; "conv3h_launches" and "conv3h_tiled_launches" count such a dispatch as its n (output slice, input slice) pairs),
  * "down6_launches" / "up6_launches" (ABI 7: conv_down6_kernel / conv_up6_kernel, the level-change convs on the 16-bit matrix pipe),
  * "hd_rounds" (ABI 7: rounds of chunk groups the Demucs v3 forward has run -- the groups of a round share the BLSTM launches),
  * "vr_net_passes" (ABI 7, additive: passes of the VR net, CascadedASPPNet or CascadedNet, on a batch of patches -- asx_vr_separate_batch_dev runs
@@ -1004,7 +1006,7 @@ int asx_op_dconv(asx_engine *e, float *y_host, int32_t b, int32_t o, int32_t i, 
  * waves' fragment order (every lane stores and re-loads its own accumulator quads, 1 KB contiguous per instruction; only the last launch of a
  * slice writes the planar output); 0 = through the output tensor itself, in the planar layout.  The values and the order of the additions are
  * the same: results are equal bit for bit, and "conv3h_launches" counts n x n per layer either way.  The scratch (24576 bytes per 4 x 32 tile of
- * the largest sliced layer, times the batch) is allocated with the engine's workspaces, never at a launch.
+ * the largest sliced layer, times the batch, times its n output slices: "conv3h_merge_out") is allocated with the engine's workspaces, never at a launch.
  * "conv3h_walk" (an option only, no environment variable): how conv3h_kernel's 256 persistent workgroups share the (batch item, band of strips,
  * tile rows) of a launch -- a table planned on the host (csrc/conv3h_walk_plan.h) and uploaded with the engine's workspaces, never at a launch.
  * 1 (default) = balanced: whole planes to every group of workgroups while whole rounds remain, the leftover items cut into equal shares of tile
@@ -1015,6 +1017,14 @@ int asx_op_dconv(asx_engine *e, float *y_host, int32_t b, int32_t o, int32_t i, 
  * consumer waves' own lane order, so a store instruction is 1 KB contiguous and a producer item one 128-byte line -- wherever the kernel runs both
  * layers, T % 4 == 0 and no GroupNorm pass stands between them; 0 = planar.  The block's input and output, every other level and kernel, and the
  * TFC-TDF v3 nets stay planar.  Same accumulators and values, another address: the results are equal bit for bit.  No buffer grows.
+ * "conv3h_merge_out" (an option only, no environment variable): the largest channel count whose conv3h_kernel layers run ONE dispatch per
+ * 48-channel input slice with the n output slices side by side -- the groups of workgroups dealt into walkers of n groups that take the same
+ * tiles at the same time, each group with its own weight image, bias, output slice and partial-sum scratch -- so a layer is n dispatches
+ * instead of n x n and an input slice is fetched from memory once instead of n times.  Default 144 (96- and 144-channel layers); 96 = the
+ * 96-channel layers only; 0 = n x n launches.  Needs "conv3h_partial_scratch" = 1: with 0 a layer runs n x n launches whatever this option
+ * says.  A lane adds the same values in the same order: the results are equal bit for bit.  "conv3h_launches" keeps counting (output slice,
+ * input slice) pairs, n x n per layer either way; "conv3h_merged_dispatches" counts the merged dispatches, n per merged layer.  The scratch is
+ * one per output slice (n times 24576 bytes per 4 x 32 tile of the largest sliced layer, times the batch) whatever the option says.
  * "conv_down_bf16x6" / "conv_up_bf16x6" (ABI 7; also ASX_DOWN6 / ASX_UP6): 1 (default) = the 2 x 2 / stride-2 convolutions between the levels
  * (mdxnet.py:66-72) and the transposed ones of the decoder with their `x *= skip` (mdxnet.py:80-86, 113) run conv_down6_kernel / conv_up6_kernel
  * (csrc/kernels_updown6.h) while "gemm_bf16x6" is on: the arithmetic of that option -- both fp32 operands split EXACTLY into three bf16 parts, six

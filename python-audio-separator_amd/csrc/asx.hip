@@ -100,6 +100,7 @@ static const struct EngineOption {
     {"conv3h_partial_scratch", &asx_engine::conv3h_ps, &EngineKnobs::conv3h_ps, opt_onoff},
     {"conv3h_walk", &asx_engine::conv3h_walk, &EngineKnobs::conv3h_walk, opt_onoff},
     {"conv3h_tiled", &asx_engine::conv3h_tiled, &EngineKnobs::conv3h_tiled, opt_onoff},
+    {"conv3h_merge_out", &asx_engine::conv3h_merge, &EngineKnobs::conv3h_merge, opt_nonneg},
     {"conv_down_bf16x6", &asx_engine::down6, &EngineKnobs::down6, opt_onoff},
     {"conv_up_bf16x6", &asx_engine::up6, &EngineKnobs::up6, opt_onoff},
     {"gemm_pair_images", &asx_engine::pair_images, &EngineKnobs::pair_images, opt_onoff,
@@ -2851,6 +2852,7 @@ int asx_counter(const asx_engine *e, const char *name, int64_t *out) {
   else if (nm == "conv3h_launches") *out = (int64_t)g_conv3h_launches.load();
   else if (nm == "conv3h_fin_launches") *out = (int64_t)g_conv3h_fin_launches.load();
   else if (nm == "conv3h_tiled_launches") *out = (int64_t)g_conv3h_tiled_launches.load();
+  else if (nm == "conv3h_merged_dispatches") *out = (int64_t)g_conv3h_merged_dispatches.load();
   else if (nm == "tdf_fused_output_launches") *out = (int64_t)g_tdf_fused_output_launches.load();
   else if (nm == "tdf3_pair_image_launches") *out = (int64_t)g_tdf3ps_launches.load();
   else if (nm == "down6_launches") *out = (int64_t)g_down6_launches.load();

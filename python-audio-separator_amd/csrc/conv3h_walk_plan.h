@@ -14,6 +14,14 @@
 // end, into one equal share of tile rows per group (a share touches one item, or two or three where it crosses their ends), every piece on a
 // multiple of `gran` tile rows -- what the kernel's block exponent allows: 1, the exponent of a block is a function of the block alone.  Of
 // the three band widths it keeps the one with the shortest longest list (the wider one on a tie) and, with gran = 1, never returns a longer one than mode 0.
+//
+// Merged output slices (nob > 1; a layer of 48 nob channels, one launch per INPUT slice): the groups are dealt into WALKERS of nob groups, group k
+// of a walker on output slice k, all nob on the same row of the table -- the same units in the same order at the same time, so one group fetches
+// a line of x from memory and the others find it in a cache.  The plan is dealt to (256 / bw) / nob lists instead of 256 / bw; groups beyond
+// walkers * nob (nob = 3: two of 32 at bw = 8) stay idle.  conv3h_walk_wg is the map workgroup -> (table row, output slice), shared with the
+// kernel.  Mode 0 with nob > 1 deals whole planes round robin to the walkers (no segments of T: 32 / bw groups of an XCD are not a multiple
+// of every nob); on a tie of the longest list the NARROWER band wins there: bw = 8 keeps the groups of a walker on one XCD for nob = 2 and 4.
+// nob = 1 is the plan described above, entry for entry.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -25,7 +33,8 @@ struct Conv3hUnit {
 
 struct Conv3hWalkPlan {
   int bw = 32, tps = 0;                    // strips per band; mode 0's tile rows per segment (0 in a balanced plan)
-  int ngroups = 8;                         // 256 / bw: group g = XCD g / (32 / bw), segment g % (32 / bw)
+  int ngroups = 8;                         // lists (rows of the table): 256 / bw, group g = XCD g / (32 / bw), segment g % (32 / bw); nob > 1: the walkers, (256 / bw) / nob
+  int nob = 1;                             // output slices side by side: groups per walker
   std::vector<std::vector<Conv3hUnit>> units;   // [ngroups], in walk order
   int steps(int g) const {
     int n = 0;
@@ -78,11 +87,34 @@ static inline Conv3hWalkPlan conv3h_walk_arith(int B, int tilesT, int tilesF, in
 }
 static inline Conv3hWalkPlan conv3h_walk_plan0(int B, int tilesT, int tilesF) { return conv3h_walk_arith(B, tilesT, tilesF, conv3h_walk_bw0(B, tilesT, tilesF)); }
 
-static inline Conv3hWalkPlan conv3h_walk_balanced(int B, int tilesT, int tilesF, int gran, int bw) {
+#if defined(__HIPCC__)
+#define CONV3H_WALK_HD __host__ __device__
+#else
+#define CONV3H_WALK_HD
+#endif
+// Workgroup wg of the 256 -> row of the walk table (-1: the group is idle and leaves at once) and output slice ob; its strip inside the band
+// is (wg >> 3) % bw whatever nob.  Where the 32 / bw groups of an XCD are a multiple of nob, the groups of a walker sit on ONE XCD (they share
+// x through its L2): nob = 2 at bw <= 16, nob = 4 at bw = 8.  Otherwise walker = g / nob, ob = g % nob over the global group index g.
+CONV3H_WALK_HD static inline void conv3h_walk_wg(int wg, int bw, int nob, int &row, int &ob) {
+  const int gx = 32 / bw, x = wg & 7, seg = (wg >> 3) / bw;
+  if (nob < 1) nob = 1;                    // (arguments that never heard of the field: 0)
+  if (gx % nob == 0) {
+    row = x * (gx / nob) + seg / nob;
+    ob = seg % nob;
+  } else {
+    const int g = x * gx + seg;
+    row = g / nob;
+    ob = g % nob;
+    if (row >= (8 * gx) / nob) row = -1;
+  }
+}
+
+static inline Conv3hWalkPlan conv3h_walk_balanced(int B, int tilesT, int tilesF, int gran, int bw, int nob = 1) {
   Conv3hWalkPlan p;
   p.bw = bw;
   p.tps = 0;
-  p.ngroups = 256 / bw;
+  p.nob = nob;
+  p.ngroups = (256 / bw) / nob;
   p.units.assign((size_t)p.ngroups, {});
   const int G = p.ngroups, nbands = (tilesF + bw - 1) / bw, items = B * nbands;
   const int rounds = items / G, left = items - rounds * G;
@@ -111,8 +143,36 @@ static inline Conv3hWalkPlan conv3h_walk_balanced(int B, int tilesT, int tilesF,
   return p;
 }
 
-// mode 0: the arithmetic walk; mode 1: balanced.  gran: a unit may start on multiples of gran tile rows only (mode 1; >= 1)
-static inline Conv3hWalkPlan conv3h_walk_plan(int B, int tilesT, int tilesF, int gran, int mode) {
+// nob > 1, mode 0: whole planes round robin, walker w takes the items (b, band) w, w + walkers, ...
+static inline Conv3hWalkPlan conv3h_walk_dealt(int B, int tilesT, int tilesF, int bw, int nob) {
+  Conv3hWalkPlan p;
+  p.bw = bw;
+  p.tps = tilesT;
+  p.nob = nob;
+  p.ngroups = (256 / bw) / nob;
+  p.units.assign((size_t)p.ngroups, {});
+  const int nbands = (tilesF + bw - 1) / bw, items = B * nbands;
+  for (int item = 0; item < items; ++item) p.units[(size_t)(item % p.ngroups)].push_back({item / nbands, item % nbands, 0, tilesT});
+  return p;
+}
+
+// mode 0: the arithmetic walk; mode 1: balanced.  gran: a unit may start on multiples of gran tile rows only (mode 1; >= 1).  nob: output
+// slices side by side (1 .. 4)
+static inline Conv3hWalkPlan conv3h_walk_plan(int B, int tilesT, int tilesF, int gran, int mode, int nob = 1) {
+  if (nob > 1) {
+    if (gran < 1) gran = 1;
+    Conv3hWalkPlan best;
+    int nbest = INT32_MAX;
+    for (int bw : {32, 16, 8}) {
+      Conv3hWalkPlan c = mode == 0 ? conv3h_walk_dealt(B, tilesT, tilesF, bw, nob) : conv3h_walk_balanced(B, tilesT, tilesF, gran, bw, nob);
+      const int n = c.longest();
+      if (n <= nbest) {
+        nbest = n;
+        best = std::move(c);
+      }
+    }
+    return best;
+  }
   Conv3hWalkPlan best = conv3h_walk_plan0(B, tilesT, tilesF);
   if (mode == 0) return best;
   if (gran < 1) gran = 1;
@@ -129,7 +189,7 @@ static inline Conv3hWalkPlan conv3h_walk_plan(int B, int tilesT, int tilesF, int
   return best;
 }
 
-// The table the kernel reads, 16-byte entries: row g (group g) at g * stride entries = {steps of the group, units, 0, 0}, its units {b, band, t0,
+// The table the kernel reads, 16-byte entries: row g (group g; nob > 1: walker g) at g * stride entries = {steps of the group, units, 0, 0}, its units {b, band, t0,
 // tiles}, then one closing unit of 2^30 tile rows that the walk never leaves (the producers look four blocks ahead of the last step).
 // Returns stride.
 static inline int conv3h_walk_table(const Conv3hWalkPlan &p, std::vector<int32_t> &tab) {

@@ -156,6 +156,7 @@ struct RsTable {
 // one uploaded walk table of conv3h_kernel and what it was planned for
 struct Conv3hWalkTab {
   int B, tilesT, tilesF, mode;   // mode: option "conv3h_walk"
+  int nob;                       // output slices side by side (1: one launch per (output slice, input slice) pair)
   int bw, stride;
   DevBuf tab;
 };
@@ -229,8 +230,8 @@ struct asx_engine {
   // the per-song fold table (PoolSong), the dividers of the distinct song lengths, one peak word per song
   DevBuf pool_wave, pool_nsong, pool_songs, pool_div, pool_peak;
   DevBuf c3h_ps;     // conv3h_kernel's partial sums between the slice launches of a 96- / 144-channel layer (Conv3hCfg::ps_bytes of the largest such
-                     // layer and batch); sized with the workspaces, never at a launch: a captured graph holds the pointer
-  // conv3h_kernel's walk tables (conv3h_walk_plan.h), one per (batch, tile rows, strips, schedule): built and uploaded with the workspaces
+                     // layer and batch, one per output slice: conv3h_ps_need); sized with the workspaces, never at a launch: a captured graph holds the pointer
+  // conv3h_kernel's walk tables (conv3h_walk_plan.h), one per (batch, tile rows, strips, schedule, merged output slices): built and uploaded with the workspaces
   // (conv3h_walk_ensure, engine_mdx.h), never at a launch, and kept until the engine goes (the entries never move: a captured graph holds the pointer)
   std::vector<Conv3hWalkTab *> c3h_walks;
   DevBuf gn_part;    // per-plane float64 (sum, sum of squares) of the GroupNorm variant of the net (asx_net_config.norm == 1)
@@ -255,7 +256,7 @@ struct asx_engine {
   hipEvent_t div_ev = nullptr;       // recorded behind the kernel that built d_div; a call on ANOTHER stream waits for it
   hipStream_t div_stream = nullptr;
   std::vector<DevBuf> skip;
-  // The twelve engine options (asx_set_option / asx_get_option; asx_engine_create sets them from EngineKnobs, knobs.h).
+  // The engine options (asx_set_option / asx_get_option; asx_engine_create sets them from EngineKnobs, knobs.h).
   // 3x3 / pad-1 convs of the ConvTDFNet and TFC-TDF-v3 nets: 3 = Winograd F(2x2,3x3) (conv_wino3_kernel, the default), 0 = the
   // direct kernel (conv_dma_kernel), 1 / 2 = the earlier Winograd generations (kept for A/B runs; experimental builds only).
   // ASX_WINOGRAD or asx_set_option("winograd", n).
@@ -301,6 +302,13 @@ struct asx_engine {
   // kernel runs both layers, T % 4 == 0 and no GroupNorm pass stands between them.  0: planar, as every other tensor.  Same accumulators, same
   // values, another address: the results are equal bit for bit.  asx_set_option("conv3h_tiled", n); no environment variable.
   int conv3h_tiled = 1;
+  // The largest channel count whose conv3h layers run ONE launch per 48-channel input slice, the n output slices side by side (Conv3hArgs::nob:
+  // the groups of workgroups dealt into walkers of n groups that take the same tiles at the same time, each group its own weight image, bias,
+  // output slice and partial-sum scratch): n launches per layer instead of n x n, and an input slice fetched from memory once instead of n
+  // times.  0: n x n launches.  Only with "conv3h_partial_scratch" on (the planar accumulate mode has no merged form: such a layer runs n x n
+  // launches).  Same values, same order of additions: the results are equal bit for bit.  asx_set_option("conv3h_merge_out", n); no
+  // environment variable.
+  int conv3h_merge = 144;
   // 1 (default): the net's 1x1 input conv (4 -> 48 channels, folded BatchNorm, ReLU) is computed by the producer waves of the first TFC conv's
   // conv3h_kernel launch (its fused-input form) instead of in a launch of its own: the 48-channel level-0 activation is never written to
   // memory and read back.  0: two launches.  Only where the first 3x3 layer runs conv3h_kernel at 48 channels and the net uses BatchNorm.

@@ -252,6 +252,7 @@ static std::atomic<long long> g_wino6h_launches{0};  // ... of which on the fp16
 static std::atomic<long long> g_conv3h_launches{0};  // launches of conv3h_kernel (kernels_conv3h.h)
 static std::atomic<long long> g_conv3h_fin_launches{0};   // ... of which in the fused-input form (the net's 1x1 input conv computed by the producers)
 static std::atomic<long long> g_conv3h_tiled_launches{0}; // ... of which with a tile-order input or output (option "conv3h_tiled")
+static std::atomic<long long> g_conv3h_merged_dispatches{0};   // dispatches that ran all output slices of a layer on one input slice (option "conv3h_merge_out"); g_conv3h_launches counts each as its (output slice, input slice) pairs
 static std::atomic<long long> g_down6_launches{0};   // launches of conv_down6_kernel (kernels_updown6.h)
 static std::atomic<long long> g_up6_launches{0};     // launches of conv_up6_kernel
 
@@ -288,27 +289,30 @@ static bool conv3h_takes(const asx_engine *e, const ConvLayer &L, bool dma, cons
 static bool conv3h_tiled_ok(const asx_engine *e, const ConvLayer &L, int T) { return T % 4 == 0 && (L.cin == Conv3hCfg::C || e->conv3h_ps > 0); }
 
 // bytes of partial-sum scratch (asx_engine::c3h_ps) a conv_launch of this layer on B items of T x F may use: whoever sizes the workspaces of a
-// net asks for every 3x3 layer and keeps the maximum (whatever the options say at that moment: they may change between two forwards)
+// net asks for every 3x3 layer and keeps the maximum (whatever the options say at that moment: they may change between two forwards).  One
+// scratch per output slice: the merged form (option "conv3h_merge_out") has all of them in flight between two launches.
 static size_t conv3h_ps_need(const ConvLayer &L, int B, int T, int F) {
   if (L.kind != CK_3X3 || L.w3h.p == nullptr || L.cin <= Conv3hCfg::C || F % 32 != 0 || B <= 0 || T <= 0) return 0;
-  return (size_t)Conv3hCfg::ps_bytes(B, (T + 3) / 4, F / 32);
+  return (size_t)(L.cin / Conv3hCfg::C) * (size_t)Conv3hCfg::ps_bytes(B, (T + 3) / 4, F / 32);
 }
 
 // The walk tables (conv3h_walk_plan.h) a conv_launch of this layer on B items of T x F may read -- both schedules, since option "conv3h_walk" may
-// change between two forwards: planned, uploaded and kept.  Called wherever c3h_ps is sized, for every batch size a pass will launch with.
-static const Conv3hWalkTab *conv3h_walk_find(const asx_engine *e, int B, int tilesT, int tilesF, int mode) {
+// change between two forwards, and for a layer of n > 1 slices both the n x n form (nob = 1) and the merged one (nob = n), since option
+// "conv3h_merge_out" may, too: planned, uploaded and kept.  Called wherever c3h_ps is sized, for every batch size a pass will launch with.
+static const Conv3hWalkTab *conv3h_walk_find(const asx_engine *e, int B, int tilesT, int tilesF, int mode, int nob) {
   for (const Conv3hWalkTab *t : e->c3h_walks)
-    if (t->B == B && t->tilesT == tilesT && t->tilesF == tilesF && t->mode == mode) return t;
+    if (t->B == B && t->tilesT == tilesT && t->tilesF == tilesF && t->mode == mode && t->nob == nob) return t;
   return nullptr;
 }
 static int conv3h_walk_ensure(asx_engine *e, const ConvLayer &L, int B, int T, int F) {
   if (L.kind != CK_3X3 || L.w3h.p == nullptr || F % 32 != 0 || B <= 0 || T <= 0) return ASX_OK;
-  const int tilesT = (T + 3) / 4, tilesF = F / 32;
-  for (int mode = 0; mode < 2; ++mode) {
-    if (conv3h_walk_find(e, B, tilesT, tilesF, mode)) continue;
-    const Conv3hWalkPlan plan = conv3h_walk_plan(B, tilesT, tilesF, 1, mode);   // granularity 1: a block's exponent does not depend on the walk
+  const int tilesT = (T + 3) / 4, tilesF = F / 32, nb = L.cin / Conv3hCfg::C;
+  for (int k = 0; k < (nb > 1 ? 4 : 2); ++k) {
+    const int mode = k & 1, nob = k < 2 ? 1 : nb;
+    if (conv3h_walk_find(e, B, tilesT, tilesF, mode, nob)) continue;
+    const Conv3hWalkPlan plan = conv3h_walk_plan(B, tilesT, tilesF, 1, mode, nob);   // granularity 1: a block's exponent does not depend on the walk
     std::vector<int32_t> tab;
-    Conv3hWalkTab *t = new Conv3hWalkTab{B, tilesT, tilesF, mode, plan.bw, conv3h_walk_table(plan, tab), DevBuf()};
+    Conv3hWalkTab *t = new Conv3hWalkTab{B, tilesT, tilesF, mode, nob, plan.bw, conv3h_walk_table(plan, tab), DevBuf()};
     int rc = t->tab.ensure(tab.size() * 4);
     if (rc == ASX_OK && hipMemcpy(t->tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
       set_err("conv3h_walk_ensure: the upload of a walk table failed");
@@ -433,11 +437,15 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     // the scratch e->c3h_ps in fragment order (option "conv3h_partial_scratch"; only the last launch writes y) or through y itself (a.prev = y).
     // One scratch serves every output slice: on the one stream, launch (ob, nb - 1) has consumed it before (ob + 1, 0) writes.  The walk
     // arguments of all n x n launches are built HERE, once: the scratch forms rely on identical walks (kernels_conv3h.h, PS).
+    // Merged output slices (option "conv3h_merge_out" >= the layer's channels, scratch form only): ONE launch per input slice runs the n
+    // output slices side by side (Conv3hArgs::nob), each on its own scratch -- n launches, every input slice fetched once.
     const int nb = L.cin / Conv3hCfg::C;
     const int tilesT = (T + 3) / 4, tilesF = F / 32;
+    const bool ps = e->conv3h_ps > 0 && nb > 1;
+    const bool merged = ps && L.cin <= e->conv3h_merge;
     // the walk of the 256 workgroups over (item, band of strips, tile rows): a table planned with the workspaces (option "conv3h_walk": 1 = balanced,
     // 0 = the arithmetic walk), never built here -- a launch allocates and copies nothing
-    const Conv3hWalkTab *wt = conv3h_walk_find(e, B, tilesT, tilesF, e->conv3h_walk > 0 ? 1 : 0);
+    const Conv3hWalkTab *wt = conv3h_walk_find(e, B, tilesT, tilesF, e->conv3h_walk > 0 ? 1 : 0, merged ? nb : 1);
     REQUIRE(wt != nullptr, "conv3h_kernel: no walk table for %d x %d x %d (the workspace set-up plans them)", B, T, F);
     grant_lds(&conv3h_kernel<0, false>, Conv3hCfg::LDS_BYTES);
     grant_lds(&conv3h_kernel<0, true>, Conv3hCfg::LDS_BYTES);
@@ -465,10 +473,9 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
         else if (yt) one(&conv3h_kernel<0, false, false, PS, false, true>);
         else one(&conv3h_kernel<0, false, false, PS>);
       }
-      if (v.x_tiled || yt) g_conv3h_tiled_launches.fetch_add(1);
+      if (v.x_tiled || yt) g_conv3h_tiled_launches.fetch_add(ca.nob);   // (a merged dispatch: its nob (output slice, input slice) pairs)
     };
     const int64_t plane = (int64_t)T * F;
-    const bool ps = e->conv3h_ps > 0 && nb > 1;
     const int64_t ps_item = Conv3hCfg::ps_item_bytes(tilesT, tilesF);
     REQUIRE(!ps || (ps_item < ((int64_t)1 << 32) && e->c3h_ps.p != nullptr && e->c3h_ps.bytes >= conv3h_ps_need(L, B, T, F)),
             "conv3h_kernel: the partial-sum scratch is not sized for %d x %d x %d (the workspace set-up sizes it)", B, T, F);
@@ -485,6 +492,29 @@ static int conv_launch(asx_engine *e, const ConvLayer &L, const float *x, const 
     walk.walk_stride = wt->stride;
     walk.ps = ps ? e->c3h_ps.p : nullptr;
     walk.ps_bstride = ps_item;
+    walk.nob = 1;
+    if (merged)
+      return timed(e, cls, flops, bytes, s, [&]() {
+        e->prof_nprod = 3;
+        for (int ib = 0; ib < nb; ++ib) {
+          Conv3hArgs ca = walk;                        // output slice 0's pointers; slice ob's lie ob strides further
+          ca.nob = nb;
+          ca.x = x + (int64_t)ib * Conv3hCfg::C * plane;
+          ca.y = y;
+          ca.y_ostride = (int64_t)Conv3hCfg::C * plane;
+          ca.wimg = reinterpret_cast<const u32x4 *>(reinterpret_cast<const uint32_t *>(L.w3h.p) + (size_t)ib * Conv3hCfg::IMG_U32);
+          ca.wimg_ostride = (int64_t)nb * (Conv3hCfg::IMG_U32 / 4);
+          ca.bias = ib == 0 ? L.b.f() : nullptr;
+          ca.bias_ostride = Conv3hCfg::C;
+          ca.ps_ostride = Conv3hCfg::ps_bytes(B, tilesT, tilesF);
+          ca.act = ib == nb - 1 ? a.act : ACT_NONE;
+          if (ib == 0) go(std::false_type{}, IntC<2>{}, ca, false);
+          else if (ib < nb - 1) go(std::false_type{}, IntC<3>{}, ca, false);
+          else go(std::false_type{}, IntC<1>{}, ca, v.y_tiled);
+          g_conv3h_launches.fetch_add(nb);             // (output slice, input slice) pairs, whatever the number of dispatches
+          g_conv3h_merged_dispatches.fetch_add(1);
+        }
+      });
     return timed(e, cls, flops, bytes, s, [&]() {
       e->prof_nprod = 3;
       for (int ob = 0; ob < nb; ++ob)

@@ -4,8 +4,9 @@
 // slices: for every output slice the input slices one after the other, each launch adding its sum to the partial sum of those before it.  The
 // partial sum travels between two consecutive launches through a private scratch buffer in FRAGMENT order (template parameter PS: every lane
 // stores and re-loads its own six accumulator quads, 1 KB contiguous per instruction), or -- engine option "conv3h_partial_scratch" = 0 --
-// through the output tensor itself in the planar layout (accumulate mode, ACC).  DESIGN.md 6k has the design record and the measurements
-// behind every choice below.
+// through the output tensor itself in the planar layout (accumulate mode, ACC).  With the scratch, the launches of the output slices that
+// share an input slice can be ONE launch (Conv3hArgs::nob, engine option "conv3h_merge_out"): 2 / 3 launches per layer, the output slices side
+// by side on groups of workgroups that walk together.  DESIGN.md 6k has the design record and the measurements behind every choice below.
 // Fused-input form (template flag FIN, engine option "conv_fuse_input"): for the net's FIRST 3x3 layer, x is relu(b1 + w1 xin), the 4 -> 48 1x1
 // input conv of the net -- the producers fetch the four planes of xin (four loads per item instead of eight) and form their eight channels in
 // registers in a fixed fma order; pixels outside the plane enter the ring as 0 (the padding is of the 48-channel activation).  The 1x1 conv's
@@ -66,6 +67,12 @@ struct Conv3hArgs {
   // partial-sum scratch (PS): [B][tilesF][tilesT][wave 4][store 6][lane 64] x 16 bytes (Conv3hCfg::ps_off), ps_bstride BYTES between batch items
   void *ps;
   int64_t ps_bstride;
+  // merged output slices (the PS forms alone; nob <= 1 elsewhere): the launch runs nob output slices side by side on ONE input slice -- the
+  // groups of the grid dealt into walkers of nob groups (conv3h_walk_plan.h, conv3h_walk_wg), group k of a walker on output slice k.  wimg, bias,
+  // y and ps above are output slice 0's; slice ob's lie ob strides further
+  int nob;
+  int64_t wimg_ostride, bias_ostride, y_ostride;   // in 16-byte entries / floats / floats
+  int64_t ps_ostride;                              // bytes: one whole scratch (Conv3hCfg::ps_bytes) per output slice
 };
 
 struct Conv3hCfg {
@@ -281,14 +288,23 @@ __device__ __forceinline__ void conv3h_walk_unit(const Conv3hArgs &a, int wg, Co
   w.t0 = __builtin_amdgcn_readfirstlane((int)un.z);
   w.tiles = __builtin_amdgcn_readfirstlane((int)un.w);
 }
+// MO (the kernel's PS forms): the launch may run a.nob output slices side by side -- the row is the group's WALKER's (conv3h_walk_wg)
+template <bool MO>
 __device__ __forceinline__ int conv3h_walk_row(const Conv3hArgs &a, int wg) {   // first entry of the group's row (bw is a power of two)
+  if constexpr (MO) {
+    int row, ob;
+    conv3h_walk_wg(wg, a.bw, a.nob, row, ob);
+    return row * a.walk_stride;
+  }
   const int sh = __builtin_ctz((unsigned)a.bw);
   return ((wg & 7) * (32 >> sh) + ((wg >> 3) >> sh)) * a.walk_stride;
 }
 __device__ __forceinline__ int conv3h_row0(const Conv3hWalk &w) { return w.t0 * 4; }   // first row of the unit
-__device__ __forceinline__ int conv3h_nblocks(const Conv3hArgs &a, int wg) { return (int)a.walk[conv3h_walk_row(a, wg)].x; }
+template <bool MO>
+__device__ __forceinline__ int conv3h_nblocks(const Conv3hArgs &a, int wg) { return (int)a.walk[conv3h_walk_row<MO>(a, wg)].x; }
+template <bool MO>
 __device__ __forceinline__ void conv3h_walk_init(const Conv3hArgs &a, int wg, Conv3hWalk &w) {
-  w.u = conv3h_walk_row(a, wg) + 1;
+  w.u = conv3h_walk_row<MO>(a, wg) + 1;
   w.j = -1;
   conv3h_walk_unit(a, wg, w);
 }
@@ -344,6 +360,10 @@ struct Conv3hFinRegs<true> {
 // INVARIANT: a launch with both bits reads and writes the SAME scratch in place, and a launch reads what the one before it wrote.  That is
 // safe because a lane only ever touches its own 16 bytes per (tile, store) -- loaded behind stage 7 of the tile, overwritten a step later --
 // and because the launches of one output slice walk identically: same B, T, F, tilesT, tilesF, bw and walk table (the launcher builds them from one place).
+// Merged output slices (a.nob > 1, engine option "conv3h_merge_out"): ONE launch per input slice runs all output slices side by side, each
+// group of workgroups on the slice conv3h_walk_wg gives it, with its own weight image, bias, y slice and scratch -- a layer is n launches
+// instead of n x n and an input slice is fetched from memory once, not n times (the n groups of a walker read the same lines at the same
+// time).  The invariant holds per output slice: the n launches of a layer share nob and the table, so a group meets its own scratch again.
 // XT / YT: the input slice a.x / the final output slice a.y is in TILE ORDER (Conv3hCfg::tl_off) instead of planar -- for the tensors between the
 // 3x3 convs of one TFC block, which nothing but this kernel touches (compile-time for the reason given at ACC).  Same accumulators, same lanes,
 // same values, another address.  XT changes `fetch` alone: the lane's item is what it was, its eight channels lie TL_PIECE bytes apart (one
@@ -356,6 +376,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   using CFG = Conv3hCfg;
   constexpr bool PIN = (PS & 1) != 0, POUT = (PS & 2) != 0;
   constexpr bool OWNQ = POUT || YT;                    // the epilogue stores the lane's own accumulator quads (no lane swap)
+  constexpr bool MO = PS != 0;                         // merged output slices (a.nob): only a layer of several slices has them, and it runs the PS forms
   static_assert(!(PS != 0 && (ACC || FIN)), "partial sums through the scratch: neither the planar accumulate mode nor the fused input");
   static_assert(!(XT && (FIN || ACC)) && !(YT && (ACC || POUT)), "tile order: never the accumulate mode; the fused input has no input slice, a partial-out launch no final output");
   extern __shared__ float lds_f[];
@@ -366,6 +387,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int wg = blockIdx.x;
   float *maxtab = reinterpret_cast<float *>(lds + CFG::TAB_OFF);   // [2][4]: block parity, producer wave
   int *exps = reinterpret_cast<int *>(lds + CFG::TAB_OFF + 32);    // [3]: block % 3
+  if constexpr (MO) {
+    // the group's output slice: everything that depends on it moves HERE, once -- the rest of the kernel is what it is for one slice
+    int row, ob;
+    conv3h_walk_wg(wg, a.bw, a.nob, row, ob);
+    if (row < 0) return;                               // a group beyond walkers * nob (the whole workgroup, in front of the first barrier)
+    a.wimg += ob * a.wimg_ostride;
+    if (a.bias) a.bias += ob * a.bias_ostride;
+    a.y += ob * a.y_ostride;
+    a.ps = static_cast<char *>(a.ps) + ob * a.ps_ostride;
+  }
 
   // ---- weights: global image -> LDS, once
   {
@@ -374,7 +405,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i = tid; i < CFG::WBYTES / 16; i += 512) dst[i] = src[i];
   }
   const int64_t TF = (int64_t)a.T * a.F;
-  const int NB = __builtin_amdgcn_readfirstlane(conv3h_nblocks(a, wg));
+  const int NB = __builtin_amdgcn_readfirstlane(conv3h_nblocks<MO>(a, wg));
   const unsigned plane_bytes = (unsigned)(CFG::C * TF * 4);
 
   if (wave >= 4) {
@@ -422,7 +453,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 
     Conv3hWalk wk;
-    conv3h_walk_init(a, wg, wk);
+    conv3h_walk_init<MO>(a, wg, wk);
     int nf = 0;                                        // blocks fetched so far
     auto fetch = [&](auto setc) {                      // the next block of the walk (nothing past the last one: every offset out of range)
       constexpr int S = decltype(setc)::value;
@@ -698,7 +729,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     __syncthreads();                                   // (P0)
     __syncthreads();                                   // (P1)
     Conv3hWalk wk;
-    conv3h_walk_init(a, wg, wk);
+    conv3h_walk_init<MO>(a, wg, wk);
     int s3 = 0;                                        // s % 3
     for (int s = 0; s < NB; ++s) {
       const int tb = wk.b, j = wk.j, wk_strip = wk.strip, wk_t0 = wk.t0, f0 = wk_strip * 32;

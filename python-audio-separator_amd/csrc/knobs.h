@@ -135,6 +135,7 @@ struct EngineKnobs {
   int conv3h_ps = 1;                                              // "conv3h_partial_scratch": an option only, as the one above
   int conv3h_walk = 1;                                            // "conv3h_walk": an option only, too
   int conv3h_tiled = 1;                                           // "conv3h_tiled": an option only, too
+  int conv3h_merge = 144;                                         // "conv3h_merge_out": an option only, too
   int down6 = knob::num("ASX_DOWN6", 1);                          // "conv_down_bf16x6"
   int up6 = knob::num("ASX_UP6", 1);                              // "conv_up_bf16x6"
   bool fft3 = knob::on_unless_0("ASX_FFT3");                      // the fast FFT path where the geometry allows it (n_fft 6144 / hop 1024)

@@ -1,7 +1,7 @@
 // Stand-alone harness of the direct fp16 x 3 convolution kernel (python-audio-separator_amd/csrc/kernels_conv3h.h): a float64 direct
 // convolution on small shapes (borders, ragged sizes) and on sampled outputs of the HQ_3 level-0 shape, then time per launch.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/proto_conv3h tools/proto_conv3h.hip
-//   tools/proto_conv3h [abl] [order] [B of the timing shape] [reps] [quick] [alias] [bw] [partial sums through the scratch: 1 / 0] [tile order: 1 = also the XT / YT forms]
+//   tools/proto_conv3h [abl] [order] [B of the timing shape] [reps] [quick] [alias] [bw] [partial sums through the scratch: 1 / 0] [tile order: 1 = also the XT / YT forms] [merged: 1 = the 96 -> 96 layer as two launches, the output slices side by side]
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -112,8 +112,9 @@ static double ref_at(const std::vector<float> &x, const std::vector<float> &w, c
 static int g_bw = 32;      // strips per band of the arithmetic walk (argv[7]: 32, 16, 8), or 0: the balanced walk (conv3h_walk_plan.h)
 
 // plans the walk of a launch (g_bw), uploads its table (kept until the process ends) and fills the walk arguments
-static void set_walk(Conv3hArgs &a) {
-  const Conv3hWalkPlan plan = g_bw > 0 ? conv3h_walk_arith(a.B, a.tilesT, a.tilesF, g_bw) : conv3h_walk_plan(a.B, a.tilesT, a.tilesF, 1, 1);
+static void set_walk(Conv3hArgs &a, int nob = 1) {
+  const Conv3hWalkPlan plan = nob > 1 ? conv3h_walk_plan(a.B, a.tilesT, a.tilesF, 1, 1, nob)   // merged output slices: always the balanced plan over walkers of nob groups
+                                      : (g_bw > 0 ? conv3h_walk_arith(a.B, a.tilesT, a.tilesF, g_bw) : conv3h_walk_plan(a.B, a.tilesT, a.tilesF, 1, 1));
   std::vector<int32_t> tab;
   a.walk_stride = conv3h_walk_table(plan, tab);
   a.bw = plan.bw;
@@ -123,6 +124,7 @@ static void set_walk(Conv3hArgs &a) {
   a.walk = reinterpret_cast<const u32x4 *>(d);
 }
 static int g_ps = 1;       // 96 -> 96 layer: partial sums through the fragment-order scratch (argv[8]; 0: through the output, planar)
+static int g_merged = 0;   // argv[10]: 1 = run_shape96 as two launches, one per input slice, both output slices side by side (Conv3hArgs::nob = 2; needs g_ps)
 static int g_tiled = 0;    // argv[9]: 1 = the chain planar -> tile order -> tile order -> planar against three planar launches, bit for bit, and the forms' times
 static int g_alias = 0;   // 1: every batch item reads item 0's planes, 2: and writes item 0's output (cache-resident traffic: is the launch DRAM- or CU-bound?)
 static int run_shape(const Shape &sh, int abl, int order, int reps) {
@@ -349,7 +351,8 @@ static int run_shape96(const Shape &sh, int reps) {
   CK(hipMemset(dy, 0xff, n * 4));
   for (int b = 0; b < sh.B; ++b) CK(hipMemcpy(dx + (size_t)b * nb, x.data(), nb * 4, hipMemcpyHostToDevice));
   CK(hipMemcpy(dbias, bias.data(), C * 4, hipMemcpyHostToDevice));
-  uint32_t *dimg[2][2];
+  uint32_t *dimg[2][2], *dall = nullptr;               // the four images in one buffer, output slice major (the merged form strides over it)
+  CK(hipMalloc(&dall, 4 * Conv3hCfg::IMG_U32 * 4));
   for (int ob = 0; ob < 2; ++ob)
     for (int ib = 0; ib < 2; ++ib) {
       std::vector<float> ws((size_t)48 * 48 * 9);
@@ -358,20 +361,51 @@ static int run_shape96(const Shape &sh, int reps) {
           for (int k = 0; k < 9; ++k) ws[((size_t)co * 48 + ci) * 9 + k] = w[((size_t)(ob * 48 + co) * C + ib * 48 + ci) * 9 + k];
       std::vector<uint32_t> img;
       conv3h_pack(ws.data(), img);
-      CK(hipMalloc(&dimg[ob][ib], img.size() * 4));
+      dimg[ob][ib] = dall + (size_t)(ob * 2 + ib) * Conv3hCfg::IMG_U32;
       CK(hipMemcpy(dimg[ob][ib], img.data(), img.size() * 4, hipMemcpyHostToDevice));
     }
   long long *ddbg = nullptr;
   CK(hipMalloc(&ddbg, (512 + 4 * 2048) * 8));
   void *dps = nullptr;
   const int64_t ps_item = Conv3hCfg::ps_item_bytes((sh.T + 3) / 4, sh.F / 32);
-  CK(hipMalloc(&dps, (size_t)Conv3hCfg::ps_bytes(sh.B, (sh.T + 3) / 4, sh.F / 32)));
+  const int64_t ps_all = Conv3hCfg::ps_bytes(sh.B, (sh.T + 3) / 4, sh.F / 32);
+  const bool merged = g_merged && g_ps;
+  CK(hipMalloc(&dps, (size_t)ps_all * 2));            // one scratch per output slice (the four-launch form uses the first)
   Conv3hArgs wk{};                                     // the walk all four launches share
   wk.B = sh.B;
   wk.tilesT = (sh.T + 3) / 4;
   wk.tilesF = sh.F / 32;
-  set_walk(wk);
+  set_walk(wk, merged ? 2 : 1);
   auto go = [&]() {
+    if (merged) {                                      // one launch per input slice, group k of a walker on output slice k
+      for (int ib = 0; ib < 2; ++ib) {
+        Conv3hArgs a{};
+        a.x = dx + (size_t)ib * 48 * sh.T * sh.F;
+        a.y = dy;
+        a.ps = dps;
+        a.ps_bstride = ps_item;
+        a.wimg = reinterpret_cast<const u32x4 *>(dimg[0][ib]);
+        a.bias = ib ? nullptr : dbias;
+        a.nob = 2;
+        a.wimg_ostride = 2 * (int64_t)(Conv3hCfg::IMG_U32 / 4);
+        a.bias_ostride = 48;
+        a.y_ostride = (int64_t)48 * sh.T * sh.F;
+        a.ps_ostride = ps_all;
+        a.B = sh.B;
+        a.T = sh.T;
+        a.F = sh.F;
+        a.x_bstride = a.y_bstride = (int64_t)nb;
+        a.act = ib ? sh.act : ACT_NONE;
+        a.tilesT = (sh.T + 3) / 4;
+        a.tilesF = sh.F / 32;
+        a.bw = wk.bw;
+        a.walk = wk.walk;
+        a.walk_stride = wk.walk_stride;
+        a.dbg = ddbg;
+        launch_ps(ib ? 1 : 2, a, 0);
+      }
+      return;
+    }
     for (int ob = 0; ob < 2; ++ob)
       for (int ib = 0; ib < 2; ++ib) {
         Conv3hArgs a{};
@@ -439,8 +473,8 @@ static int run_shape96(const Shape &sh, int reps) {
     std::mt19937 r2(99);
     for (int i = 0; i < 20000; ++i) check((int)(r2() % C), (int)(r2() % sh.T), (int)(r2() % sh.F));
   }
-  printf("  %s (96 channels, four launches): %zu outputs checked, rel RMS %.3e, worst |d| / sum |w x| %.3e, %s\n", sh.name, cnt, std::sqrt(num / std::max(den, 1e-300)), worst,
-         bad ? "FAIL" : "ok");
+  printf("  %s (96 channels, %s launches): %zu outputs checked, rel RMS %.3e, worst |d| / sum |w x| %.3e, %s\n", sh.name, merged ? "two merged" : "four", cnt, std::sqrt(num / std::max(den, 1e-300)),
+         worst, bad ? "FAIL" : "ok");
   if (reps > 0) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
@@ -452,11 +486,12 @@ static int run_shape96(const Shape &sh, int reps) {
     CK(hipEventSynchronize(e1));
     float ms = 0;
     CK(hipEventElapsedTime(&ms, e0, e1));
-    printf("  %s: %.3f ms per 96 -> 96 layer (four launches), bw %d, partial sums %s\n", sh.name, ms / reps, g_bw, g_ps ? "scratch" : "planar");
+    printf("  %s: %.3f ms per 96 -> 96 layer (%s launches), bw %d, partial sums %s\n", sh.name, ms / reps, merged ? "two merged" : "four", wk.bw, g_ps ? "scratch" : "planar");
   }
   CK(hipFree(dx));
   CK(hipFree(dy));
   CK(hipFree(dps));
+  CK(hipFree(dall));
   return bad;
 }
 
@@ -470,6 +505,7 @@ int main(int argc, char **argv) {
   g_bw = argc > 7 ? atoi(argv[7]) : 32;
   g_ps = argc > 8 ? atoi(argv[8]) : 1;
   g_tiled = argc > 9 ? atoi(argv[9]) : 0;
+  g_merged = argc > 10 ? atoi(argv[10]) : 0;
   int bad = 0;
   if (abl == 0 && !quick) {
     const Shape small[] = {
