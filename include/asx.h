@@ -576,6 +576,22 @@ int asx_resample_rational_dev(asx_engine *e, const float *x_dev, int32_t channel
 int asx_resample_rational(asx_engine *e, const float *x_host, int32_t channels, int64_t n_in, int32_t sr_in, int32_t sr_out, float *y_host,
                           int64_t n_out);
 
+/* The writer-side form of the converter: stems back at the input file's sample rate and frame count (the plugins' opt-in
+ * "asx_output_rate" = "input"; the reference writes every stem at the model's rate).
+ * x: layout 0 = planar [channels, n_in], layout 1 = rows [n_in, channels] (the MDX stem layout); y: planar [channels, n_out].
+ * Same definition, taps and summation order as asx_resample_rational_dev: y[m] = sum_i x[i] h[m M - i L], zero history at both ends.
+ * n_out is FREE (1 .. 2^40): outputs past the plan's length follow from the definition (they reach exactly 0 once the filter
+ * has left the input); a shorter n_out simply stops earlier.  One launch on `stream`, grid (tiles of n_out, channels) -- all S stems of a
+ * planar [S, 2, N] tensor go in one call with channels = 2 S; only enqueues (but for the first call of a pair, which builds its table).
+ * Bits: planar input gives, for m < the plan's n_out, the bits of asx_resample_rational_dev; rows input gives the bits of planar input of
+ * the transposed data; a result does not depend on the launch.
+ * Checked before anything is enqueued, ASX_ERR_INVALID + asx_last_error() naming the argument: null pointers, a layout other than 0 or 1,
+ * channels outside 1 .. 65535, n_in or n_out outside 1 .. 2^40, equal rates, a pair the plan refuses.  Additive within ABI 7. */
+int asx_resample_rational_stem_dev(asx_engine *e, const float *x_dev, int32_t layout, int32_t channels, int64_t n_in,
+                                   int32_t sr_in, int32_t sr_out, float *y_dev, int64_t n_out, void *stream);
+int asx_resample_rational_stem(asx_engine *e, const float *x_host, int32_t layout, int32_t channels, int64_t n_in,
+                               int32_t sr_in, int32_t sr_out, float *y_host, int64_t n_out);   /* host arrays, same kernel */
+
 /* BagOfModels on the device (uvr_lib_v5/demucs/apply.py:169-196 + demucs_separator.py:171-189; ABI 4).  Every member of a
  * bag keeps its own engine (weights resident across files); the caller demixes the STANDARDISED mix with each member
  * (flags 0) and combines without a host round trip:

@@ -30,6 +30,10 @@ class VRSeparator(CommonSeparator):
     # ``asx_input_resample`` = "device" does not reach this plugin: the reference decodes a VR input with the top band's own res_type
     # (vr_separator.py:255-291), not with librosa.load's soxr_hq, so a file at another rate keeps going to ``_host_mix``
     _resamples_input_files = False
+    # for the same reason the way back is out of scope here: this plugin brings a file at another rate in on the host, with the band's own
+    # res_type, and a writer-side conversion would have to answer to that converter
+    _output_rate_refusal = ("its inputs at other rates are converted on the host with the band's own res_type, which the writer-side "
+                            "converter does not mirror (a follow-up); leave asx_output_rate at 'model'")
 
     def __init__(self, common_config, arch_config: dict):
         super().__init__(config=common_config)

@@ -77,6 +77,7 @@ class CommonSeparator:
         self.asx_profile_file = bool(config.get("asx_profile_file"))   # per-phase wall times of separate() in file_timings
         self.asx_input_resample = self._input_resample_mode(config)    # who converts a file at another rate than the model's
         self.asx_output_encoder = self._output_encoder_mode(config)    # who compresses a .flac stem when pydub is installed
+        self.asx_output_rate = self._output_rate_mode(config)          # the rate and frame count stems are written at
         self.file_timings = {}
         self._pending_writes = []                # (thread, error box) of container writes in flight
         # how the last stem reached its encoder: "flac_device_resident" | "flac_device_upload" (.flac), "wav_device_resident" (a .wav of
@@ -151,6 +152,23 @@ class CommonSeparator:
             raise ValueError(f"asx_output_encoder must be one of {cls.OUTPUT_ENCODER_MODES}, not {mode!r}")
         return mode
 
+    # ``common_config["asx_output_rate"]``: "model" (the default) writes every stem at ``sample_rate``, as the reference does; "input" writes
+    # it at the input file's own sample rate with exactly its frame count: ``write_audio`` converts the stem with the engine's rational
+    # polyphase converter (asx_resample_rational_stem: this project's own filter, parity against soxr unpinned -- hence opt-in) before the
+    # normalise / quantise pass.  ``primary_source`` / ``secondary_source`` and what ``stems_dev`` returns stay at the model's rate.  There
+    # is no environment override: the plugins named below refuse "input", and a process-wide switch would break them.
+    OUTPUT_RATE_MODES = ("model", "input")
+    _output_rate_refusal = None        # (a plugin that cannot write at the input's rate says why)
+
+    @classmethod
+    def _output_rate_mode(cls, config) -> str:
+        mode = config.get("asx_output_rate") or "model"
+        if mode not in cls.OUTPUT_RATE_MODES:
+            raise ValueError(f"asx_output_rate must be one of {cls.OUTPUT_RATE_MODES}, not {mode!r}")
+        if mode == "input" and cls._output_rate_refusal:
+            raise ValueError(f"asx_output_rate='input' is not supported by {cls.__name__}: {cls._output_rate_refusal}")
+        return mode
+
     def _resample_plan(self, file_rate):
         """(n_out for n_in) -> callable when ``asx_input_resample`` is "device" and the engine's converter takes ``file_rate`` ->
         ``sample_rate``; None otherwise (the setting is "host", the rates are equal, the pair is refused: behave as before)."""
@@ -176,6 +194,9 @@ class CommonSeparator:
             setattr(self, name, None)
         self._dev_stems = {}          # id(host array) -> (host array, device tensor [N, 2]): stems that never left HBM
         self._file_seconds = None     # duration of the current input, probed once per file
+        self._file_rate = self._file_frames = None     # the input's own sample rate and frame count, where its header was read
+        self._out_rate_group = None   # asx_output_rate = "input": (planar device stems [S, 2, N], the same at the file's rate)
+        self._out_rate_warned = False
 
     # ---- steps every architecture's separate() shares ---------------------------------------------------------------
     def _read_options(self, arch_config: dict, table):
@@ -194,13 +215,17 @@ class CommonSeparator:
         self.audio_file_base = os.path.splitext(os.path.basename(audio_file_path))[0]
         self._dev_stems = {}
         self._file_seconds = None
+        self._file_rate = self._file_frames = None
+        self._out_rate_group = None
+        self._out_rate_warned = False
         self.file_timings = {}        # seconds per phase of this file when ``asx_profile_file`` is set (bench.py file_level)
 
     # ---- device-resident file path (load / normalise / write edges without host round trips) -----------------
     # ---- concurrent container writes -----------------------------------------------------------------------------
     def _write_wav_async(self, stem_path, pcm, subtype):
         """audio_io.write_wav on a worker thread (the file write releases the GIL); drained before ``separate`` returns."""
-        self._write_async(lambda: audio_io.write_wav(stem_path, pcm, self.sample_rate, subtype))
+        rate = self._container_rate()
+        self._write_async(lambda: audio_io.write_wav(stem_path, pcm, rate, subtype))
 
     def _write_async(self, write):
         """``write()`` -- one container write -- on a worker thread; drained before ``separate`` returns."""
@@ -313,6 +338,7 @@ class CommonSeparator:
         self.input_subtype = st = info["subtype"]
         self.input_bit_depth = 16 if st == "PCM_16" else (24 if st == "PCM_24" else 32)
         self._file_seconds = info["frames"] / float(info["samplerate"])
+        self._file_rate, self._file_frames = info["samplerate"], info["frames"]
         frames, ch = info["frames"], info["channels"]
         nbytes = frames * ch * info["bits"] // 8
         staged = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
@@ -385,6 +411,7 @@ class CommonSeparator:
         self.input_subtype = "PCM_16" if info["bits_per_sample"] == 16 else "PCM_24"
         self.input_bit_depth = info["bits_per_sample"]
         self._file_seconds = frames / float(info["samplerate"])
+        self._file_rate, self._file_frames = info["samplerate"], frames      # (the scanned count: STREAMINFO's is a hint)
         mix = torch.empty((2, frames), dtype=torch.float32, device=dev)
         peak = self.engine.flac_decode_finish_dev(mix.data_ptr(), frames, stream=self._stream())
         t0 = self._tick("flac_decode", t0)
@@ -454,7 +481,7 @@ class CommonSeparator:
         views = []
         for i in range(arr.shape[0]):
             v = arr[i].T
-            self._dev_stems[id(v)] = (v, dev_stems[i], host, "planar")
+            self._dev_stems[id(v)] = (v, dev_stems[i], host, "planar", (dev_stems, i))
             views.append(v)
         return arr, views
 
@@ -496,7 +523,7 @@ class CommonSeparator:
     # one) publishes the shell as ``separate_many``; the others have no such attribute.  With the hook ``_stems_of`` it also publishes
     # ``_stems_dev_many`` as ``stems_dev_many``: the same pool, the stems left on the device instead of written (ensemble.py).  ``_PER_FILE`` lists what loading a file leaves
     # for its writer; a plugin that records more extends it.
-    _PER_FILE = ("audio_file_path", "audio_file_base", "input_bit_depth", "input_subtype", "_file_seconds")
+    _PER_FILE = ("audio_file_path", "audio_file_base", "input_bit_depth", "input_subtype", "_file_seconds", "_file_rate", "_file_frames")
 
     def _prepare_model(self):
         """Hook: what has to be ready before the first file is loaded."""
@@ -652,6 +679,23 @@ class CommonSeparator:
             self.logger.warning(f"no container info for {path} ({e}): stems will be written as 16-bit PCM")
             self.input_bit_depth, self.input_subtype = 16, "PCM_16"
 
+    def _probe_file_rate(self, path):
+        """``_file_rate`` / ``_file_frames`` of a file the host decodes, from its own header (RIFF/WAVE, or a native FLAC stream whose
+        STREAMINFO states its length); another container leaves them unknown."""
+        self._file_rate = self._file_frames = None
+        if not isinstance(path, str):
+            return
+        try:
+            info = audio_io.wav_info(path)
+            self._file_rate, self._file_frames = info["samplerate"], info["frames"]
+        except (audio_io.AudioIOError, OSError):
+            try:
+                info = audio_io.flac_stream(path) if audio_io.is_flac(path) else None
+            except (audio_io.AudioIOError, OSError):
+                info = None
+            if info and info["total_samples"] > 0:
+                self._file_rate, self._file_frames = info["samplerate"], info["total_samples"]
+
     def _load_resampled(self, path):
         """The host-array form of ``_device_mix``'s conversion, for a file the device decoder does not get (ASX_FILE_FASTPATH=0, a plugin
         option that keeps the arrays on the host): audio_io.read_wav, then Engine.resample_rational -- the bits ``_device_mix`` produces.
@@ -677,6 +721,7 @@ class CommonSeparator:
         audio_path = mix
         if not isinstance(mix, np.ndarray):
             self._probe_bit_depth(mix)
+            self._probe_file_rate(mix)
             mix, sr = self._load_resampled(mix) or audio_io.load(mix, mono=False, sr=self.sample_rate)
             self.logger.debug(f"decoded {audio_path}: {mix.shape[-1]} samples x {mix.shape[0] if mix.ndim > 1 else 1} channel(s) at {sr} Hz")
         else:
@@ -705,10 +750,100 @@ class CommonSeparator:
                 self._file_seconds = audio_io.duration(self.audio_file_path)
             secs = self._file_seconds
             self.logger.info(f"Audio duration is {secs / 3600:.2f} hours ({secs:.2f} seconds).")
-        if self.use_soundfile:
-            self.write_audio_soundfile(stem_path, stem_source)
+        self._write_rate, stem_source = self._at_output_rate(stem_path, stem_source)
+        try:
+            if self.use_soundfile:
+                self.write_audio_soundfile(stem_path, stem_source)
+            else:
+                self.write_audio_pydub(stem_path, stem_source)
+        finally:
+            self._write_rate = None
+
+    _write_rate = None       # the rate of the stem write_audio is writing, when it is not ``sample_rate``
+
+    def _container_rate(self) -> int:
+        return self._write_rate or self.sample_rate
+
+    def _output_rate_target(self):
+        """(file rate, file frames) when ``asx_output_rate`` = "input" has this file's stems converted; None when they are written as
+        they are: the knob is off, the file is at the model's rate, or -- with one warning per file -- its rate is unknown or the
+        converter refuses the pair."""
+        if getattr(self, "asx_output_rate", "model") != "input" or self.engine is None or not self.sample_rate:
+            return None
+        rate, frames = self._file_rate, self._file_frames
+        if rate == self.sample_rate:
+            return None
+        why = None
+        if not rate or not frames:
+            why = "its own sample rate is unknown (no RIFF/WAVE or FLAC header was read)"
         else:
-            self.write_audio_pydub(stem_path, stem_source)
+            try:
+                self.engine.resample_rational_plan(self.sample_rate, rate, 1)
+            except Exception as e:
+                why = f"no converter for {self.sample_rate} -> {rate} Hz ({e})"
+        if why is None:
+            return rate, frames
+        if not self._out_rate_warned:
+            self._out_rate_warned = True
+            self.logger.warning(f"{self.audio_file_path}: asx_output_rate='input', but {why}: the stems are written at {self.sample_rate} Hz")
+        return None
+
+    def _soundfile_on_device(self, stem_path: str) -> bool:
+        """whether ``_write_soundfile_device`` takes a stem of this name that is still in HBM"""
+        sf = audio_io._optional("soundfile")
+        if sf is not None and hasattr(sf, "write") and getattr(self, "asx_output_encoder", "host") != "device":
+            return False
+        return stem_path.lower().split(".")[-1] in ("wav", "flac") and self._output_subtype() in self._DEVICE_WAV_SUBTYPES
+
+    def _at_output_rate(self, stem_path: str, stem_source):
+        """``asx_output_rate`` = "input": the stem [n, 2] at ``sample_rate`` -> (file rate, the stem at the file's rate), n_out =
+        min(file frames, ceil(n * file rate / sample_rate)) frames -- a full-length stem gets exactly the file's frame count, a shorter
+        one (MDX ``invert_using_spec``) its share.  A stem that is still in HBM, and that its writer takes from there, is converted there
+        (rows or planar; the planar stems of one file in ONE launch at the first of them) and handed on as a device entry under a
+        zero-stride stand-in of the new shape; any other goes through Engine.resample_rational_stem.  (``sample_rate``, the stem itself)
+        when nothing is converted."""
+        target = self._output_rate_target()
+        if target is None:
+            return self.sample_rate, stem_source
+        a = np.asarray(stem_source)
+        if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] == 0 or a.dtype == np.int16:
+            return self.sample_rate, stem_source
+        rate, frames = target
+        n = a.shape[0]
+        n_out = min(int(frames), -(-n * int(rate) // int(self.sample_rate)))
+        t0 = self._now()
+        entry = self._device_stem_entry(stem_source)
+        on_device = entry is not None and (self._soundfile_on_device(stem_path) if self.use_soundfile else True)
+        if on_device:
+            import torch
+            dev_stem = entry[1]
+            group, index = entry[4] if len(entry) > 4 else (None, 0)
+            if group is not None and group.is_contiguous():
+                if self._out_rate_group is None or self._out_rate_group[0] is not group:
+                    y = torch.empty((group.shape[0], 2, n_out), dtype=torch.float32, device=group.device)
+                    self.engine.resample_rational_stem_dev(group.data_ptr(), "planar", 2 * group.shape[0], n, self.sample_rate, rate, y.data_ptr(),
+                                                           n_out, stream=self._stream())
+                    self._out_rate_group = (group, y)
+                converted = self._out_rate_group[1][index]
+            else:
+                dev_stem = dev_stem.contiguous()
+                converted = torch.empty((2, n_out), dtype=torch.float32, device=dev_stem.device)
+                self.engine.resample_rational_stem_dev(dev_stem.data_ptr(), entry[3], 2, n, self.sample_rate, rate, converted.data_ptr(), n_out,
+                                                       stream=self._stream())
+            out = np.broadcast_to(np.float32(0), (n_out, 2))      # stands for the shape only: the writers read the device tensor
+            self._dev_stems.pop(id(stem_source), None)
+            if group is not None and not any(len(e) > 4 and e[4][0] is group for e in self._dev_stems.values()):
+                self._out_rate_group = None                        # (the file's last stem: the view keeps the storage until it is written)
+            self._dev_stems[id(out)] = (out, converted, None, "planar")
+        else:
+            if entry is not None:
+                self._sync()                                       # (the pinned mirror is filled by an asynchronous copy)
+                self._dev_stems.pop(id(stem_source), None)
+            out = self.engine.resample_rational_stem(np.ascontiguousarray(a, np.float32), self.sample_rate, rate, n_out, layout="rows").T
+        if getattr(self, "asx_profile_file", False):
+            self._sync()
+        self.file_timings["resample_out"] = self.file_timings.get("resample_out", 0.0) + (self._now() - t0)
+        return rate, out
 
     def _stereo_rows(self, stem_source):
         a = np.asarray(stem_source)
@@ -739,7 +874,7 @@ class CommonSeparator:
             plan = eng.flac_plan(n, 2, bits, block)
             out = torch.empty(plan["max_bytes"], dtype=torch.uint8, device=pcm_dev.device)
             sizes = torch.empty(plan["n_blocks"], dtype=torch.int32, device=pcm_dev.device)
-            total = eng.flac_encode_dev(pcm_dev.data_ptr(), n, self.sample_rate, bits, block, out.data_ptr(), plan["max_bytes"], sizes.data_ptr(),
+            total = eng.flac_encode_dev(pcm_dev.data_ptr(), n, self._container_rate(), bits, block, out.data_ptr(), plan["max_bytes"], sizes.data_ptr(),
                                         stream=self._stream())
             frames_host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
             sizes_host = torch.empty(plan["n_blocks"], dtype=torch.int32, pin_memory=True)
@@ -749,10 +884,10 @@ class CommonSeparator:
             frames, frame_sizes = frames_host.numpy(), sizes_host.numpy()
             self.last_write_path = "flac_device_resident"
         else:
-            frames, frame_sizes = eng.flac_encode(pcm_host, self.sample_rate, bits, block)
+            frames, frame_sizes = eng.flac_encode(pcm_host, self._container_rate(), bits, block)
             self.last_write_path = "flac_device_upload"
         self.file_timings["flac_encode"] = self.file_timings.get("flac_encode", 0.0) + (self._now() - t0)
-        rate = self.sample_rate
+        rate = self._container_rate()
 
         def write():
             md5 = None
@@ -820,7 +955,7 @@ class CommonSeparator:
             return
         pydub = audio_io._optional("pydub")
         if pydub is not None and hasattr(pydub, "AudioSegment") and hasattr(pydub.AudioSegment, "export"):
-            seg = pydub.AudioSegment(pcm.reshape(-1).tobytes(), frame_rate=self.sample_rate, sample_width=2, channels=2)
+            seg = pydub.AudioSegment(pcm.reshape(-1).tobytes(), frame_rate=self._container_rate(), sample_width=2, channels=2)
             fmt = {"m4a": "mp4", "mka": "matroska"}.get(file_format, file_format)
             params = {"format": fmt}
             bitrate = "320k" if fmt == "mp3" and self.output_bitrate is None else self.output_bitrate
@@ -859,14 +994,11 @@ class CommonSeparator:
         sample format there (asx_pcm_encode_dev), bring back the file's bytes -- or, for a ``.flac`` name, its compressed frames
         (asx_flac_encode_pcm_dev: a PCM_24 input keeps 24 real bits) -- and write the container on the writer threads.  False: not a case
         of this path (another container, a subtype without a device encoder, soundfile installed and not overruled); the caller goes on."""
-        sf = audio_io._optional("soundfile")
-        if sf is not None and hasattr(sf, "write") and getattr(self, "asx_output_encoder", "host") != "device":
+        if not self._soundfile_on_device(stem_path):
             return False
         eng = self.engine
         file_format = stem_path.lower().split(".")[-1]
         subtype = self._output_subtype()
-        if file_format not in ("wav", "flac") or subtype not in self._DEVICE_WAV_SUBTYPES:
-            return False
         if file_format == "flac" and subtype not in self._DEVICE_FLAC_SUBTYPES:
             # what sf.write does under the reference: libsndfile's FLAC takes neither 32-bit nor float samples
             self.logger.error(f"{stem_path}: the container write failed: FLAC holds no {subtype} samples")
@@ -892,7 +1024,7 @@ class CommonSeparator:
         if self.output_dir:
             os.makedirs(self.output_dir, exist_ok=True)
             stem_path = os.path.join(self.output_dir, stem_path)
-        rate = self.sample_rate
+        rate = self._container_rate()
         if file_format == "wav":
             body = torch.empty(dev_body.shape, dtype=torch.uint8, pin_memory=True)
             body.copy_(dev_body, non_blocking=True)
@@ -947,9 +1079,9 @@ class CommonSeparator:
         sf = audio_io._optional("soundfile")
         try:
             if sf is not None and hasattr(sf, "write"):
-                sf.write(stem_path, buf, self.sample_rate, subtype=subtype)
+                sf.write(stem_path, buf, self._container_rate(), subtype=subtype)
             else:
-                audio_io.write_wav(stem_path, buf, self.sample_rate, subtype)
+                audio_io.write_wav(stem_path, buf, self._container_rate(), subtype)
         except Exception as e:
             self.logger.error(f"{stem_path}: the container write failed: {e}")
 
@@ -958,6 +1090,7 @@ class CommonSeparator:
         """common_separator.py:463-474.  The engine's workspaces are sized once and reused across files (they are the
         point of keeping 288 GB resident); only Python garbage and torch's caching allocator are trimmed."""
         self._dev_stems = {}
+        self._out_rate_group = None
         gc.collect()
         try:
             import torch

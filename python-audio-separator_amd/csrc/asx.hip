@@ -1099,6 +1099,54 @@ int asx_resample_rational(asx_engine *e, const float *x_host, int32_t channels, 
   });
 }
 
+// The writer-side form of the converter: planar or rows input, the caller's n_out (include/asx.h)
+int asx_resample_rational_stem_dev(asx_engine *e, const float *x_dev, int32_t layout, int32_t channels, int64_t n_in, int32_t sr_in, int32_t sr_out,
+                                   float *y_dev, int64_t n_out, void *stream) {
+  REQUIRE(e, "asx_resample_rational_stem_dev: null engine");
+  REQUIRE(x_dev, "asx_resample_rational_stem_dev: x is null");
+  REQUIRE(y_dev, "asx_resample_rational_stem_dev: y is null");
+  REQUIRE(layout == 0 || layout == 1, "asx_resample_rational_stem_dev: layout = %d (0: planar [channels, n_in], 1: rows [n_in, channels])", layout);
+  REQUIRE(channels >= 1 && channels <= 65535, "asx_resample_rational_stem_dev: %d channels (1 .. 65535)", channels);
+  ResamplePlan p;
+  const std::string why = resample_plan_make(sr_in, sr_out, p);
+  REQUIRE(why.empty(), "asx_resample_rational_stem_dev: %s", why.c_str());
+  const std::string bad = resample_plan_check_stem(p, n_in, n_out);
+  REQUIRE(bad.empty(), "asx_resample_rational_stem_dev: %s", bad.c_str());
+  REQUIRE(p.K == 8 || !p.taps_in_lds, "asx_resample_rational_stem_dev: no kernel for the tile of %d -> %d Hz", sr_in, sr_out);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  const RsTable *t = nullptr;
+  CHK(rs_table(e, p, &t));
+  const float *tab = t->tab.f();
+  const bool rows = layout == 1;
+  return timed(e, ASX_PROF_MISC, 2.0 * channels * (double)n_out * (double)p.T, 4.0 * channels * ((double)n_in + (double)n_out), s, [&]() {
+    if (p.taps_in_lds) rs_stem_launch<8, true>(p, x_dev, rows, channels, n_in, tab, y_dev, n_out, s);
+    else if (p.K == 8) rs_stem_launch<8, false>(p, x_dev, rows, channels, n_in, tab, y_dev, n_out, s);
+    else if (p.K == 4) rs_stem_launch<4, false>(p, x_dev, rows, channels, n_in, tab, y_dev, n_out, s);
+    else if (p.K == 2) rs_stem_launch<2, false>(p, x_dev, rows, channels, n_in, tab, y_dev, n_out, s);
+    else rs_stem_launch<1, false>(p, x_dev, rows, channels, n_in, tab, y_dev, n_out, s);
+  });
+}
+
+int asx_resample_rational_stem(asx_engine *e, const float *x_host, int32_t layout, int32_t channels, int64_t n_in, int32_t sr_in, int32_t sr_out,
+                               float *y_host, int64_t n_out) {
+  REQUIRE(e, "asx_resample_rational_stem: null engine");
+  REQUIRE(x_host, "asx_resample_rational_stem: x is null");
+  REQUIRE(y_host, "asx_resample_rational_stem: y is null");
+  // (checked here as well: the sizes of the staging buffers follow from them)
+  REQUIRE(layout == 0 || layout == 1, "asx_resample_rational_stem: layout = %d (0: planar [channels, n_in], 1: rows [n_in, channels])", layout);
+  REQUIRE(channels >= 1 && channels <= 65535, "asx_resample_rational_stem: %d channels (1 .. 65535)", channels);
+  ResamplePlan p;
+  const std::string why = resample_plan_make(sr_in, sr_out, p);
+  REQUIRE(why.empty(), "asx_resample_rational_stem: %s", why.c_str());
+  const std::string bad = resample_plan_check_stem(p, n_in, n_out);
+  REQUIRE(bad.empty(), "asx_resample_rational_stem: %s", bad.c_str());
+  HIPCHK(hipSetDevice(e->device));
+  return host_round_trip(x_host, (size_t)channels * n_in, y_host, (size_t)channels * n_out, [&](const float *x, float *y) {
+    return asx_resample_rational_stem_dev(e, x, layout, channels, n_in, sr_in, sr_out, y, n_out, nullptr);
+  });
+}
+
 // The FLAC encoder (kernels_flac.h, engine_flac.h): the plan of a stream, pure host
 int asx_flac_plan(int64_t n_samples, int32_t channels, int32_t bits_per_sample, int32_t block_size, int64_t *n_blocks, int32_t *frame_stride,
                   int64_t *max_bytes, int64_t *scratch_bytes) {

@@ -34,3 +34,17 @@ static void rs_launch(const ResamplePlan &p, const float *x, int channels, int64
   hipLaunchKernelGGL((resample_rational_kernel<K, TAPS_LDS>), dim3(tiles, (unsigned)channels), dim3(RS_THREADS), lds, s, x, n_in, tab, (int)p.L, (int)p.M,
                      (int)p.P, (int)p.J, (int)p.span, y, n_out);
 }
+
+// the writer-side form: the tiles cover the caller's n_out, x planar or rows (kernels_resample.h resample_rational_stem_kernel)
+template <int K, bool TAPS_LDS>
+static void rs_stem_launch(const ResamplePlan &p, const float *x, bool rows, int channels, int64_t n_in, const float *tab, float *y, int64_t n_out,
+                           hipStream_t s) {
+  const size_t lds = (size_t)(p.span + (TAPS_LDS ? p.L * p.T : 0)) * sizeof(float);   // at most 64 KiB (RESAMPLE_MAX_LDS_FLOATS)
+  const dim3 grid((unsigned)((n_out + p.J * K - 1) / (p.J * K)), (unsigned)channels);
+  if (rows)
+    hipLaunchKernelGGL((resample_rational_stem_kernel<K, TAPS_LDS, true>), grid, dim3(RS_THREADS), lds, s, x, channels, n_in, tab, (int)p.L, (int)p.M,
+                       (int)p.P, (int)p.J, (int)p.span, y, n_out);
+  else
+    hipLaunchKernelGGL((resample_rational_stem_kernel<K, TAPS_LDS, false>), grid, dim3(RS_THREADS), lds, s, x, channels, n_in, tab, (int)p.L, (int)p.M,
+                       (int)p.P, (int)p.J, (int)p.span, y, n_out);
+}

@@ -21,25 +21,11 @@ namespace asx {
 
 constexpr int RS_THREADS = 256;   // RESAMPLE_THREADS of resample_plan.h
 
+// the outputs of one tile from its staged span: xs[u] = x[i0 + u] (0 outside the input), cs the table in LDS when TAPS_LDS
 template <int K, bool TAPS_LDS>
-__global__ __launch_bounds__(RS_THREADS) void resample_rational_kernel(const float *__restrict__ x, int64_t n_in, const float *__restrict__ tab,
-                                                                        int L, int M, int P, int J, int span, float *__restrict__ y,
-                                                                        int64_t n_out) {
-  extern __shared__ float rs_lds[];
-  float *xs = rs_lds;          // [span]: x[q0 - P + u]
-  float *cs = rs_lds + span;   // TAPS_LDS: the table [2 P + 1][L]
+__device__ __forceinline__ void rs_tile_outputs(const float *xs, const float *cs, const float *__restrict__ tab, int L, int M, int P, int J, int64_t first,
+                                                float *__restrict__ yc, int64_t n_out) {
   const int tid = (int)threadIdx.x;
-  const int64_t first = (int64_t)blockIdx.x * J * K;   // a multiple of L
-  const int64_t i0 = first / L * M - P;                // the input sample behind xs[0]
-  const float *xc = x + (int64_t)blockIdx.y * n_in;
-  float *yc = y + (int64_t)blockIdx.y * n_out;
-  for (int u = tid; u < span; u += RS_THREADS) {
-    const int64_t i = i0 + u;
-    xs[u] = (i >= 0 && i < n_in) ? xc[i] : 0.f;
-  }
-  if (TAPS_LDS)
-    for (int u = tid; u < (2 * P + 1) * L; u += RS_THREADS) cs[u] = tab[u];
-  __syncthreads();
   const int step = J / L * M;   // the input base of period k + 1 over that of period k
   for (int j = tid; j < J; j += RS_THREADS) {
     const int64_t m = first + j;
@@ -65,6 +51,61 @@ __global__ __launch_bounds__(RS_THREADS) void resample_rational_kernel(const flo
       if (mk < n_out) yc[mk] = fmaf(c_mid, xb[P + k * step], lo[k] + hi[k]);
     }
   }
+}
+
+template <int K, bool TAPS_LDS>
+__global__ __launch_bounds__(RS_THREADS) void resample_rational_kernel(const float *__restrict__ x, int64_t n_in, const float *__restrict__ tab,
+                                                                        int L, int M, int P, int J, int span, float *__restrict__ y,
+                                                                        int64_t n_out) {
+  extern __shared__ float rs_lds[];
+  float *xs = rs_lds;          // [span]: x[q0 - P + u]
+  float *cs = rs_lds + span;   // TAPS_LDS: the table [2 P + 1][L]
+  const int tid = (int)threadIdx.x;
+  const int64_t first = (int64_t)blockIdx.x * J * K;   // a multiple of L
+  const int64_t i0 = first / L * M - P;                // the input sample behind xs[0]
+  const float *xc = x + (int64_t)blockIdx.y * n_in;
+  for (int u = tid; u < span; u += RS_THREADS) {
+    const int64_t i = i0 + u;
+    xs[u] = (i >= 0 && i < n_in) ? xc[i] : 0.f;
+  }
+  if (TAPS_LDS)
+    for (int u = tid; u < (2 * P + 1) * L; u += RS_THREADS) cs[u] = tab[u];
+  __syncthreads();
+  rs_tile_outputs<K, TAPS_LDS>(xs, cs, tab, L, M, P, J, first, y + (int64_t)blockIdx.y * n_out, n_out);
+}
+
+// The writer-side form (asx_resample_rational_stem): the same tile, taps and FMA chains, so y[c][m] carries the bits of the kernel above wherever both
+// compute it, with two freedoms.  ROWS: x is [n_in, channels] (the MDX stem layout) and channel blockIdx.y is staged with a stride of `channels`
+// floats -- for stereo the two workgroups of a tile read the same lines, one from HBM and one from L2; the staging is span loads against
+// T J K LDS reads and FMAs of the tile, which is why the channels are not folded into one workgroup (that would double the span in LDS, past
+// 64 KiB for 44.1 -> 32 kHz, to save under 1 % of the tile's work).  n_out is the caller's: the grid covers it, and a tile whose span starts at or
+// past n_in -- the filter has left the input -- stores zeros without staging or reading anything.
+template <int K, bool TAPS_LDS, bool ROWS>
+__global__ __launch_bounds__(RS_THREADS) void resample_rational_stem_kernel(const float *__restrict__ x, int channels, int64_t n_in,
+                                                                             const float *__restrict__ tab, int L, int M, int P, int J, int span,
+                                                                             float *__restrict__ y, int64_t n_out) {
+  extern __shared__ float rs_lds[];
+  float *xs = rs_lds;          // [span]: x[i0 + u]
+  float *cs = rs_lds + span;   // TAPS_LDS: the table [2 P + 1][L]
+  const int tid = (int)threadIdx.x;
+  const int64_t first = (int64_t)blockIdx.x * J * K;   // a multiple of L
+  const int64_t i0 = first / L * M - P;                // the input sample behind xs[0]
+  float *yc = y + (int64_t)blockIdx.y * n_out;
+  if (i0 >= n_in) {   // (the same for every thread of the workgroup)
+    const int64_t end = first + (int64_t)J * K < n_out ? first + (int64_t)J * K : n_out;
+    for (int64_t m = first + tid; m < end; m += RS_THREADS) yc[m] = 0.f;
+    return;
+  }
+  const float *xc = ROWS ? x + blockIdx.y : x + (int64_t)blockIdx.y * n_in;
+  const int64_t stride = ROWS ? channels : 1;
+  for (int u = tid; u < span; u += RS_THREADS) {
+    const int64_t i = i0 + u;
+    xs[u] = (i >= 0 && i < n_in) ? xc[i * stride] : 0.f;
+  }
+  if (TAPS_LDS)
+    for (int u = tid; u < (2 * P + 1) * L; u += RS_THREADS) cs[u] = tab[u];
+  __syncthreads();
+  rs_tile_outputs<K, TAPS_LDS>(xs, cs, tab, L, M, P, J, first, yc, n_out);
 }
 
 }  // namespace asx

@@ -125,6 +125,15 @@ static inline std::string resample_plan_check_n(const ResamplePlan &p, int64_t n
   return "";
 }
 
+// the same for the writer-side form, whose n_out is the caller's (asx_resample_rational_stem): outputs at or past resample_plan_n_out follow from
+// the definition and are exactly 0 from m = ceil(((n_in - 1) L + half + 1) / M) on, where the filter has left the input
+static inline std::string resample_plan_check_stem(const ResamplePlan &p, int64_t n_in, int64_t n_out) {
+  if (n_in < 1 || n_in > RESAMPLE_MAX_N) return "n_in = " + std::to_string(n_in) + " (1 .. 2^40)";
+  if (n_out < 1 || n_out > RESAMPLE_MAX_N) return "n_out = " + std::to_string(n_out) + " (1 .. 2^40)";
+  if ((n_out + p.J * p.K - 1) / (p.J * p.K) > 2147483647) return "n_out = " + std::to_string(n_out) + ": too many tiles for one launch";
+  return "";
+}
+
 // h[n + half], n = -half .. half, float64
 static inline void resample_plan_taps(const ResamplePlan &p, std::vector<double> &h) {
   h.assign((size_t)(2 * p.half + 1), 0.0);

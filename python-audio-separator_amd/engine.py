@@ -281,7 +281,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_op_vr_lstm_layout", "asx_flac_plan", "asx_flac_encode", "asx_flac_encode_dev",
            "asx_flac_decode_plan", "asx_flac_decode_scan_dev", "asx_flac_decode_finish_dev", "asx_flac_decode",
            "asx_flac_plan_pcm", "asx_flac_encode_pcm", "asx_flac_encode_pcm_dev", "asx_pcm_encode", "asx_pcm_encode_dev",
-           "asx_invert_stem_dev", "asx_invert_stem_batch_dev", "asx_op_gconv", "asx_op_dconv", "asx_resample_sinc_batch_dev"]
+           "asx_invert_stem_dev", "asx_invert_stem_batch_dev", "asx_op_gconv", "asx_op_dconv", "asx_resample_sinc_batch_dev",
+           "asx_resample_rational_stem", "asx_resample_rational_stem_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -447,6 +448,8 @@ def load_library():
     lib.asx_resample_rational_plan.argtypes = [i32, i32, i64, C.POINTER(i64), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.asx_resample_rational.argtypes = [vp, _FP, i32, i64, i32, i32, _FP, i64]
     lib.asx_resample_rational_dev.argtypes = [vp, vp, i32, i64, i32, i32, vp, i64, vp]
+    lib.asx_resample_rational_stem.argtypes = [vp, _FP, i32, i32, i64, i32, i32, _FP, i64]
+    lib.asx_resample_rational_stem_dev.argtypes = [vp, vp, i32, i32, i64, i32, i32, vp, i64, vp]
     lib.asx_flac_plan.argtypes = [i64, i32, i32, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
     lib.asx_flac_encode.argtypes = [vp, C.POINTER(C.c_int16), i64, i32, i32, i32, C.POINTER(C.c_uint8), i64, C.POINTER(i32), C.POINTER(i64)]
     lib.asx_flac_encode_dev.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, vp, C.POINTER(i64), vp]
@@ -926,6 +929,31 @@ class Engine:
     def resample_rational_dev(self, x_ptr: int, channels: int, n_in: int, sr_in: int, sr_out: int, y_ptr: int, n_out: int, stream: int = 0):
         self._check(self._lib.asx_resample_rational_dev(self._h, x_ptr, int(channels), int(n_in), int(sr_in), int(sr_out), y_ptr, int(n_out),
                                                         stream or None))
+
+    RESAMPLE_LAYOUTS = {"planar": 0, "rows": 1}     # asx_resample_rational_stem: x [channels, n] | [n, channels]
+
+    def resample_rational_stem(self, x: np.ndarray, sr_in: int, sr_out: int, n_out: int, layout: str = "planar") -> np.ndarray:
+        """The writer-side form of the converter (asx_resample_rational_stem): x [C, n] ("planar"; [n] is one channel) or [n, C]
+        ("rows", the MDX stem layout) at ``sr_in`` Hz -> planar [C, n_out] at ``sr_out`` Hz with the caller's ``n_out`` -- the definition
+        of ``resample_rational`` carried on past, or cut before, its ceil(n * sr_out / sr_in) outputs (zeros once the filter has left
+        the input)."""
+        if layout not in self.RESAMPLE_LAYOUTS:
+            raise ValueError(f"layout must be one of {tuple(self.RESAMPLE_LAYOUTS)}, not {layout!r}")
+        x = _f32(x)
+        one = x.ndim == 1 and layout == "planar"
+        x2 = np.ascontiguousarray(x[None] if one else x)
+        if x2.ndim != 2 or min(x2.shape) < 1:
+            raise ValueError(f"resample_rational_stem expects {'[channels, n]' if layout == 'planar' else '[n, channels]'}, got {x.shape}")
+        ch, n_in = x2.shape if layout == "planar" else x2.shape[::-1]
+        y = np.empty((ch, max(int(n_out), 0)), np.float32)
+        self._check(self._lib.asx_resample_rational_stem(self._h, _ptr(x2), self.RESAMPLE_LAYOUTS[layout], ch, n_in, int(sr_in), int(sr_out),
+                                                         _ptr(y), int(n_out)))
+        return y[0] if one else y
+
+    def resample_rational_stem_dev(self, x_ptr: int, layout: str, channels: int, n_in: int, sr_in: int, sr_out: int, y_ptr: int, n_out: int,
+                                   stream: int = 0):
+        self._check(self._lib.asx_resample_rational_stem_dev(self._h, x_ptr, self.RESAMPLE_LAYOUTS[layout], int(channels), int(n_in), int(sr_in),
+                                                             int(sr_out), y_ptr, int(n_out), stream or None))
 
     def vr_flops(self) -> float:
         return float(self._lib.asx_vr_flops(self._h))

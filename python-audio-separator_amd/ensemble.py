@@ -137,6 +137,10 @@ class EnsembleSeparator:
         if any(v != modes[0] for v in modes):
             # a file at another rate would reach the members through different converters (or fail in some of them only)
             raise ValueError(f"ensemble members differ in asx_input_resample: {modes}")
+        if any(getattr(m, "asx_output_rate", "model") == "input" for m in self.members):
+            # the pooled combine quantises on the device without passing the members' writer, where that conversion lives
+            raise ValueError("asx_output_rate='input' is not supported in an ensemble: the combined stems are quantised on the device "
+                             "without passing write_audio's conversion (a follow-up); leave the members at 'model'")
         if model_filenames is not None and len(model_filenames) != len(self.members):
             raise ValueError(f"{len(model_filenames)} model file names for {len(self.members)} members")
         self.algorithm, self.weights, self.preset = algorithm, weights, preset
