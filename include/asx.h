@@ -47,7 +47,7 @@ extern "C" {
 #define ASX_ERR_HIP 2     /* a HIP runtime call failed (no GPU, OOM, launch) */
 #define ASX_ERR_STATE 3   /* call order violated (e.g. demix before commit)  */
 
-#define ASX_ABI_VERSION 7
+#define ASX_ABI_VERSION 8
 
 /* flags of asx_demix*(): */
 #define ASX_FLAG_MATCH_MIX 1u /* demix(mix, is_match_mix=True): overlap 0.02, no net (mdx_separator.py:308-313, :429-432) */
@@ -982,6 +982,49 @@ int asx_op_gconv(asx_engine *e, const asx_gconv_desc *d, const float *x_host, co
 int asx_op_dconv(asx_engine *e, float *y_host, int32_t b, int32_t o, int32_t i, int32_t c, int32_t hid, int32_t along_outer, int32_t d,
                  int32_t part, const float *w1, const float *b1, const float *g1w, const float *g1b, const float *w2, const float *b2,
                  const float *g2w, const float *g2b, const float *ls, float *h_host, int32_t *ticket_left);
+/* (ABI 8) Single launches of the STFT / iSTFT kernels, through the engines' own launch helpers (stft_launch; istft_launch + ola_launch
+ * or istft_ola_launch, csrc/engine_mdx.h) and the argument builders the nets use (csrc/engine_v3.h, csrc/engine_rof.h) -- single-op
+ * test hooks like asx_op_gconv: host buffers in and out; the output buffer is uploaded first, so elements the launch does not own keep
+ * their contents.  n_fft, hop_length, dim_f, win_length, the window (asx_set_stft_window) and whether the 6144 / 1024 fast path is on
+ * come from the engine; the descriptor carries the rest:
+ *   b, t: chunks and frames per chunk; c: samples per chunk (n_fft / 2 < c, and (t - 1) hop + n_fft / 2 - 1 <= 2 (c - 1) so that one
+ *     reflection suffices, forward; 1 <= c <= hop (t - 1), inverse).
+ *   layout: 0 = [b, 4, F, t]; 1 = [b, 4, t, F]; 2 = the Roformers' `b t (f s c)` (the inverse multiplies by mask_host [b, n_inst, t, F, 2, 2]).
+ *   subbands (layout 1): 0 = the MDX chunk loop's launch, which takes the fast path where the engine has it; k >= 1 = the TFC-TDF v3
+ *     launch: plane p of k F / k-bin subbands, always the generic kernels.  bstride: floats between batch items of the spectrum
+ *     (layout 1 with subbands >= 1; 0 = dense).  n_inst (inverse): S stems per batch item, b * S spectra in all.
+ *   zero_low, sign (forward); combine (inverse: 1 = 0.5 spec[i] - 0.5 spec[i + b], the spectrum holds 2 b items).
+ *   stft_normalized (layout 2): the forward scales by n_fft^-1/2 and the inverse takes the synthesis window x n_fft^1/2.
+ *   mode (forward): 0 = wave_host is [b, 2, c]; 1 = one song [2, song_len[0]], chunk i starting at padded position starts[i], `front`
+ *     zeros in front of the song; 2 = a pool of n_songs songs, wave_host their [2, song_len[s]] arrays one after the other, chunk i a
+ *     window of song song_of[i] (the *_pool_kernel twins).
+ *   n_act (inverse; NULL = none): per chunk, >= 0 = np.hanning(n_act) over the first n_act samples and zeros behind them, < 0 = none.
+ *   spec_floats: floats of spec_host.
+ * resolved (optional, 2 ints): {what ran -- 1 stft, 2 stft_pool, 3 stft3, 4 stft3_pool, 5 stft3p, 6 stft3p_pool, 7 istft + ola,
+ * 8 istft3, 9 istft3p --, seam3_kernel launches}. */
+typedef struct asx_stft_desc {
+  int32_t b, t;
+  int32_t layout, subbands, zero_low, n_inst, combine, stft_normalized;
+  int32_t mode, front, n_songs;
+  float sign;
+  int64_t c, bstride, spec_floats;
+  const int64_t *starts;
+  const int32_t *song_of;
+  const int64_t *song_len;
+  const int64_t *n_act;
+} asx_stft_desc;
+int asx_op_stft(asx_engine *e, const asx_stft_desc *d, const float *wave_host, float *spec_host, int32_t *resolved);
+/* wave_host [b * max(n_inst, 1), 2, c] */
+int asx_op_istft(asx_engine *e, const asx_stft_desc *d, const float *spec_host, const float *mask_host, float *wave_host, int32_t *resolved);
+/* (ABI 8) The spectrogram launches of the Demucs nets (csrc/kernels_ht.h), as csrc/engine_ht.h / engine_hd.h launch them -- plan, window,
+ * per-hop envelope and LDS grant from the same builders; no network needs to be loaded.  asx_op_ht_spec: one ht_stft_kernel launch,
+ * seg_host [b, 2, l] -> spec_host [b, t = ceil(l / hop), nfft / 2, 2, 2] with hop = nfft / 4; el / lv: pad1d's zero extension (el zeros
+ * in front, lv samples in all; 0 / l for none).  asx_op_ht_ispec: ht_istft_kernel + ht_ola_kernel, x_host [b, t, nfft / 2, 4 s] and
+ * xt_host [b, l, 2 s] -> out_host [b, s, 2, l]; acc_f / acc_t [b, 2]: the float64 (sum, sum of squares) pairs the kernels de-standardise
+ * with, over n_stat values of the spectrogram and 2 l samples of the waveform. */
+int asx_op_ht_spec(asx_engine *e, int32_t nfft, const float *seg_host, int32_t b, int64_t l, int64_t el, int64_t lv, float *spec_host);
+int asx_op_ht_ispec(asx_engine *e, int32_t nfft, const float *x_host, int32_t b, int32_t t, int32_t s, const double *acc_f, double n_stat,
+                    const float *xt_host, const double *acc_t, int64_t l, float *out_host);
 
 /* ---- options ------------------------------------------------------------ */
 /* Engine options.  Each engine takes its defaults from the environment variable named beside the option when it is created (values go

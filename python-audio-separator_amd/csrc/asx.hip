@@ -2028,6 +2028,217 @@ int asx_op_dconv(asx_engine *e, float *y_host, int32_t B, int32_t O, int32_t I, 
   return rc;
 }
 
+// ---- single STFT / iSTFT launches ------------------------------------------------------
+static int table_to_dev(DevBuf &d, const void *h, size_t bytes) {
+  CHK(d.ensure(bytes));
+  HIPCHK(hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice));
+  return ASX_OK;
+}
+
+// the checks both directions share; *need = the floats of the spectrum the launch touches
+static int op_stft_check(const asx_engine *e, const asx_stft_desc *d, bool inverse, int64_t *need) {
+  const int64_t F = e->cfg.dim_f, T = d->t;
+  const int S = d->n_inst > 1 ? d->n_inst : 1;
+  REQUIRE(d->b > 0 && d->t >= (inverse ? 2 : 1) && d->c > 0 && d->b <= 64 && d->t <= 4096, "asx_op_stft / istft: b %d, t %d, c %lld", d->b, d->t,
+          (long long)d->c);
+  REQUIRE(d->layout >= 0 && d->layout <= 2 && d->subbands >= 0 && d->n_inst >= 0 && d->bstride >= 0, "asx_op_stft / istft: layout %d, subbands %d",
+          d->layout, d->subbands);
+  if (d->subbands >= 1) REQUIRE(d->layout == 1 && F % d->subbands == 0, "asx_op_stft / istft: %d subbands need layout 1 and divide dim_f", d->subbands);
+  else REQUIRE(d->bstride == 0 && (d->n_inst <= 1 || d->layout == 2), "asx_op_stft / istft: batch strides and stems need subbands >= 1 (or layout 2)");
+  if (!inverse) REQUIRE(d->n_inst == 0 && d->combine == 0, "asx_op_stft: n_inst / combine belong to the inverse");
+  if (d->combine) REQUIRE(d->combine == 1 && S == 1 && d->layout != 2, "asx_op_istft: combine takes one stem per item and layout 0 / 1");
+  if (d->stft_normalized) REQUIRE(d->layout == 2, "asx_op_stft / istft: stft_normalized belongs to layout 2");
+  const int64_t item = (int64_t)S * 4 * T * F, items = (int64_t)d->b * (d->combine ? 2 : 1);
+  if (d->layout == 2) *need = (int64_t)d->b * T * F * 4;
+  else {
+    REQUIRE(d->bstride == 0 || d->bstride >= item, "asx_op_stft / istft: bstride %lld below an item of %lld floats", (long long)d->bstride, (long long)item);
+    *need = (items - 1) * (d->bstride ? d->bstride : item) + item;
+  }
+  REQUIRE(d->spec_floats >= *need && d->spec_floats < (1ll << 28), "asx_op_stft / istft: spec_floats %lld, the launch touches %lld", (long long)d->spec_floats,
+          (long long)*need);
+  return ASX_OK;
+}
+
+int asx_op_stft(asx_engine *e, const asx_stft_desc *d, const float *wave_host, float *spec_host, int32_t *resolved) {
+  REQUIRE(e && d && wave_host && spec_host, "asx_op_stft: null argument");
+  int64_t need = 0;
+  CHK(op_stft_check(e, d, false, &need));
+  const int n = e->cfg.n_fft, hop = e->cfg.hop_length, B = d->b, T = d->t;
+  const int64_t C = d->c;
+  REQUIRE(C > n / 2 && (int64_t)(T - 1) * hop + n / 2 - 1 <= 2 * (C - 1), "asx_op_stft: c %lld too short for %d frames (one reflection)", (long long)C, T);
+  REQUIRE(d->sign == 1.0f || d->sign == -1.0f, "asx_op_stft: sign must be +1 or -1");
+  REQUIRE(d->zero_low >= 0 && d->mode >= 0 && d->mode <= 2 && d->front >= 0, "asx_op_stft: zero_low / mode / front");
+  const int n_songs = d->mode == 2 ? d->n_songs : 1;
+  int64_t n_wave = (int64_t)B * 2 * C;
+  std::vector<int64_t> song_off;
+  if (d->mode) {
+    REQUIRE(d->starts && d->song_len && n_songs >= 1 && n_songs <= 64 && (d->mode == 1 || d->song_of), "asx_op_stft: song tables missing");
+    n_wave = 0;
+    for (int i = 0; i < n_songs; ++i) {
+      REQUIRE(d->song_len[i] >= 1, "asx_op_stft: song %d is empty", i);
+      song_off.push_back(n_wave);
+      n_wave += 2 * d->song_len[i];
+    }
+    for (int i = 0; i < B; ++i) REQUIRE(d->mode == 1 || (d->song_of[i] >= 0 && d->song_of[i] < n_songs), "asx_op_stft: chunk %d names song %d", i, d->song_of[i]);
+  }
+  REQUIRE(n_wave < (1ll << 28), "asx_op_stft: the case is too large for a single-op test");
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dw, dsp, dst, dptr, dlen;
+  BufGuard guard{{&dw, &dsp, &dst, &dptr, &dlen}};
+  CHK(to_dev(dw, wave_host, (size_t)n_wave));
+  CHK(to_dev(dsp, spec_host, (size_t)d->spec_floats));
+  PoolChunks pc{};
+  if (d->mode) CHK(table_to_dev(dst, d->starts, (size_t)B * 8));
+  if (d->mode == 2) {
+    std::vector<const float *> ptr(B);
+    std::vector<int64_t> len(B);
+    for (int i = 0; i < B; ++i) {
+      ptr[i] = dw.f() + song_off[d->song_of[i]];
+      len[i] = d->song_len[d->song_of[i]];
+    }
+    CHK(table_to_dev(dptr, ptr.data(), ptr.size() * sizeof(ptr[0])));
+    CHK(table_to_dev(dlen, len.data(), len.size() * 8));
+    pc.wave = reinterpret_cast<const float *const *>(dptr.p);
+    pc.n_song = reinterpret_cast<const int64_t *>(dlen.p);
+  }
+  StftGeom g;
+  if (d->layout == 2) g = rof_stft_geom(e, d->stft_normalized != 0);
+  else if (d->subbands >= 1) g = v3_stft_geom(d->subbands, d->bstride, 0);
+  else g.tf_layout = d->layout;
+  g.trim = d->front;
+  g.zero_low = d->zero_low;
+  g.sign *= d->sign;
+  e->fft_ran[0] = e->fft_ran[1] = 0;
+  const float *wave = dw.f();                          // mode 0: explicit chunks [b, 2, c]
+  const int64_t *starts = nullptr;
+  int64_t n_song = -1;
+  const PoolChunks *pool = nullptr;
+  switch (d->mode) {
+    case 1:                                            // one song: chunks are windows of it
+      starts = reinterpret_cast<const int64_t *>(dst.p);
+      n_song = d->song_len[0];
+      break;
+    case 2:                                            // a pool: song and length per chunk from the tables
+      wave = nullptr;
+      starts = reinterpret_cast<const int64_t *>(dst.p);
+      n_song = 0;
+      pool = &pc;
+      break;
+    default:
+      break;
+  }
+  int rc = stft_launch(e, wave, starts, n_song, B, C, T, dsp.f(), g, nullptr, pool);
+  if (rc == ASX_OK) rc = to_host(spec_host, dsp, (size_t)d->spec_floats);
+  else (void)hipDeviceSynchronize();
+  if (resolved) {
+    resolved[0] = e->fft_ran[0];
+    resolved[1] = e->fft_ran[1];
+  }
+  return rc;
+}
+
+int asx_op_istft(asx_engine *e, const asx_stft_desc *d, const float *spec_host, const float *mask_host, float *wave_host, int32_t *resolved) {
+  REQUIRE(e && d && spec_host && wave_host, "asx_op_istft: null argument");
+  int64_t need = 0;
+  CHK(op_stft_check(e, d, true, &need));
+  const int n = e->cfg.n_fft, hop = e->cfg.hop_length, B = d->b, T = d->t, S = d->n_inst > 1 ? d->n_inst : 1;
+  const int64_t C = d->c, F = e->cfg.dim_f;
+  REQUIRE(C <= (int64_t)hop * (T - 1), "asx_op_istft: c %lld beyond hop (t - 1) = %lld", (long long)C, (long long)hop * (T - 1));
+  REQUIRE((d->layout == 2) == (mask_host != nullptr), "asx_op_istft: the mask belongs to layout 2");
+  const size_t n_out = (size_t)B * S * 2 * C, n_frames = (size_t)B * S * 2 * T * n;
+  REQUIRE(n_frames < (1ull << 28), "asx_op_istft: the case is too large for a single-op test");
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dsp, dmask, dout, denv, dfr, dna, dwin;
+  BufGuard guard{{&dsp, &dmask, &dout, &denv, &dfr, &dna, &dwin}};
+  CHK(to_dev(dsp, spec_host, (size_t)d->spec_floats));
+  if (mask_host) CHK(to_dev(dmask, mask_host, (size_t)B * S * T * F * 4));
+  CHK(to_dev(dout, wave_host, n_out));
+  std::vector<float> env;
+  host_env(n, hop, T, env, e->cfg.win_length, &e->custom_window);
+  CHK(to_dev(denv, env.data(), env.size()));
+  if (d->n_act) CHK(table_to_dev(dna, d->n_act, (size_t)B * S * 8));
+  const int64_t *dn = d->n_act ? reinterpret_cast<const int64_t *>(dna.p) : nullptr;
+  e->fft_ran[0] = e->fft_ran[1] = 0;
+  int rc;
+  if (d->layout == 1 && d->subbands == 0) {
+    // the MDX chunk loop's inverse: the fused fast path where the engine has it and the chunk fits it
+    rc = e->frames.ensure(n_frames * 4);
+    if (rc == ASX_OK) rc = istft_ola_launch(e, dsp.f(), B, T, d->combine ? B : 0, dn, C, dout.f(), nullptr, denv.f());
+  } else {
+    IstftGeom g;
+    if (d->layout == 2) {
+      rc = d->stft_normalized ? rof_win_synth(e, dwin) : ASX_OK;
+      g = rof_istft_geom(dmask.f(), S, d->stft_normalized ? dwin.f() : nullptr);
+    } else {
+      rc = ASX_OK;
+      if (d->subbands >= 1) g = v3_istft_geom(d->subbands, S, d->bstride);
+      g.tf_layout = d->layout;
+      g.combine = d->combine ? B : 0;
+    }
+    if (rc == ASX_OK) rc = dfr.ensure(n_frames * 4);
+    if (rc == ASX_OK) rc = istft_launch(e, dsp.f(), B, T, g, dfr.f(), nullptr);
+    if (rc == ASX_OK) rc = ola_launch(e, dfr.f(), denv.f(), dn, B * S, T, C, dout.f(), nullptr);
+  }
+  if (rc == ASX_OK) rc = to_host(wave_host, dout, n_out);
+  else (void)hipDeviceSynchronize();
+  if (resolved) {
+    resolved[0] = e->fft_ran[0];
+    resolved[1] = e->fft_ran[1];
+  }
+  return rc;
+}
+
+// the largest transform whose two LDS buffers (+ 1 element, ht_istft_lds) fit the 160 KB of a CU: 8 bytes x (nfft + 1) <= 160 KB
+static const int HT_OP_MAX_NFFT = 16384;
+
+int asx_op_ht_spec(asx_engine *e, int32_t nfft, const float *seg_host, int32_t B, int64_t L, int64_t el, int64_t Lv, float *spec_host) {
+  REQUIRE(e && seg_host && spec_host && B > 0 && B <= 64 && L >= 1 && L < (1 << 24), "asx_op_ht_spec: bad argument");
+  FftPlan plan{};
+  REQUIRE(nfft >= 16 && nfft <= HT_OP_MAX_NFFT && nfft % 4 == 0 && make_plan(nfft, &plan), "asx_op_ht_spec: nfft %d", nfft);
+  const int hop = nfft / 4, T = (int)((L + hop - 1) / hop);
+  REQUIRE(el >= 0 && Lv >= el + L && Lv > hop / 2 * 3 && (int64_t)(T - 1) * hop + nfft - 1 - hop / 2 * 3 + el <= 2 * (Lv - 1),
+          "asx_op_ht_spec: the extension el %lld / lv %lld does not carry the reflect padding", (long long)el, (long long)Lv);
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf win, tw, env, dseg, dsp;
+  BufGuard guard{{&win, &tw, &env, &dseg, &dsp}};
+  CHK(ht_fft_tables(nfft, win, tw, env));
+  ht_fft_grant_lds(plan);
+  const size_t ns = (size_t)B * T * plan.nh * 4;
+  CHK(to_dev(dseg, seg_host, (size_t)B * 2 * L));
+  CHK(to_dev(dsp, spec_host, ns));
+  int rc = ht_spec_launch(e, plan, win.f(), tw.p, dseg.f(), B, L, el, Lv, T, dsp.f(), nullptr);
+  if (rc == ASX_OK) rc = to_host(spec_host, dsp, ns);
+  else (void)hipDeviceSynchronize();
+  return rc;
+}
+
+int asx_op_ht_ispec(asx_engine *e, int32_t nfft, const float *x_host, int32_t B, int32_t T, int32_t S, const double *acc_f, double n_stat,
+                    const float *xt_host, const double *acc_t, int64_t L, float *out_host) {
+  REQUIRE(e && x_host && acc_f && xt_host && acc_t && out_host && B > 0 && B <= 64 && T >= 1 && T <= 4096 && S >= 1 && S <= 16 && n_stat > 1.0,
+          "asx_op_ht_ispec: bad argument");
+  FftPlan plan{};
+  REQUIRE(nfft >= 16 && nfft <= HT_OP_MAX_NFFT && nfft % 4 == 0 && make_plan(nfft, &plan), "asx_op_ht_ispec: nfft %d", nfft);
+  const int hop = nfft / 4;
+  REQUIRE(L >= 1 && L <= (int64_t)T * hop, "asx_op_ht_ispec: l %lld beyond t hop = %lld", (long long)L, (long long)T * hop);
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf win, tw, env, dx, dxt, dfr, daf, dat, dout;
+  BufGuard guard{{&win, &tw, &env, &dx, &dxt, &dfr, &daf, &dat, &dout}};
+  CHK(ht_fft_tables(nfft, win, tw, env));
+  ht_fft_grant_lds(plan);
+  const size_t no = (size_t)B * S * 2 * L;
+  CHK(to_dev(dx, x_host, (size_t)B * T * plan.nh * 4 * S));
+  CHK(to_dev(dxt, xt_host, (size_t)B * L * 2 * S));
+  CHK(table_to_dev(daf, acc_f, (size_t)B * 16));
+  CHK(table_to_dev(dat, acc_t, (size_t)B * 16));
+  CHK(dfr.ensure((size_t)B * S * 2 * T * nfft * 4));
+  CHK(to_dev(dout, out_host, no));
+  int rc = ht_ispec_launch(e, plan, win.f(), tw.p, env.f(), dx.f(), B, T, S, reinterpret_cast<const double *>(daf.p), n_stat, dfr.f(), dxt.f(),
+                           reinterpret_cast<const double *>(dat.p), L, dout.f(), nullptr);
+  if (rc == ASX_OK) rc = to_host(out_host, dout, no);
+  else (void)hipDeviceSynchronize();
+  return rc;
+}
+
 // ---- MDXC / TFC-TDF v3 --------------------------------------------------------------
 int asx_v3_begin(asx_engine *e, const asx_v3_config *cfg) {
   w3_flush(e);

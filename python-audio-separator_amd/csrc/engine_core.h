@@ -209,6 +209,9 @@ struct asx_engine {
   DevBuf d_tw3, seam3;           // fast FFT path (kernels_fft3.h): twiddles [16][12] + [16][192]; seam partial sums
   bool fft3 = false;             // n_fft == 6144 && hop == 1024 (and ASX_FFT3 != 0)
   bool fft3p = false;            // inverse with the LDS-DMA spectrum prefetch (ASX_FFT3P != 0)
+  // what the last stft_launch / istft_launch / istft_ola_launch ran (asx_op_stft / asx_op_istft report it): {FFT_RAN_* of engine_mdx.h,
+  // seam3_kernel launches}
+  int fft_ran[2] = {0, 0};
   DevBuf d_zeros;                // zero page: source of out-of-range DMA slots
   // test-only selector of ht_gg (engine_ht.h), set by asx_op_gconv alone: 0 = the engine's rule (every other caller), 1 / 2 / 3 = only
   // gg_kernel / the halo-tile kernel / the GATHER row GEMM may run, and a launch the chosen one does not take is ASX_ERR_INVALID.

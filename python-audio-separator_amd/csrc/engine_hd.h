@@ -234,10 +234,7 @@ static int hd_commit(asx_engine *e) {
   CHK(hd_norm_load(e, h.dAn2, "decoder.1.norm2", CD));
   CHK(ht_pack_convtr(e, h.tdecA_tr, "tdecoder.0.conv_tr", CA, CD, c.kernel_size, c.stride));
   CHK(hd_norm_load(e, h.tdAn2, "tdecoder.0.norm2", CD));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ht_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)stft_lds(n.plan));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ht_istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)ht_istft_lds(n.plan));
+  ht_fft_grant_lds(n.plan);
   h.ready = true;
   return ASX_OK;
 }
@@ -526,19 +523,9 @@ static int hd_phase_front(asx_engine *e, const HdGroup &gr, hipStream_t s) {
   const int F0 = n.F[0], CA = h.CA, CD = h.CD;
   const int64_t Lp = (L + 1) & ~(int64_t)1;
   // spectrogram + standardisation of both branches (hdemucs.py:680-704); pad1d's zero extension of short inputs (:21-34)
-  int64_t el = 0, Lv = L;
-  {
-    const int64_t left = hop / 2 * 3, right = left + (int64_t)T * hop - L, mx = std::max(left, right);
-    if (L <= mx) {
-      const int64_t extra = mx - L + 1, er = std::min(right, extra);
-      el = extra - er;
-      Lv = L + extra;
-    }
-  }
-  CHK(timed(e, ASX_PROF_STFT, 0.0, 4.0 * (double)B * (2.0 * L + 4.0 * T * F0), s, [&]() {
-    hipLaunchKernelGGL(ht_stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(n.plan), s, seg, L, el, Lv, hop, T, b.xf0, n.window.f(),
-                       reinterpret_cast<const float2 *>(n.tw.p), n.plan);
-  }));
+  int64_t el, Lv;
+  ht_spec_extension(L, T, hop, &el, &Lv);
+  CHK(ht_spec_launch(e, n.plan, n.window.f(), n.tw.p, seg, B, L, el, Lv, T, b.xf0, s));
   const int64_t nf = (int64_t)T * F0 * 4;
   CHK(ht_stats(e, b.xf0, B, T, (int64_t)F0 * 4, (int64_t)F0 * 4, 4, 4, 1, b.acc_f, s));
   CHK(timed(e, ASX_PROF_MISC, 0.0, 8.0 * (double)B * nf, s, [&]() {
@@ -673,14 +660,8 @@ static int hd_phase_after(asx_engine *e, const HdGroup &gr, bool levelZ, size_t 
   for (int i = D - 1; i >= 0; --i) CHK(ht_dec_level(e, i, B, s));
   // CaC -> iSTFT, + waveform branch (hdemucs.py:760-781)
   const int64_t nf = (int64_t)T * F0 * 4;
-  CHK(timed(e, ASX_PROF_ISTFT, 0.0, 4.0 * (double)B * S * 2 * T * (2.0 * F0 + c.nfft), s, [&]() {
-    hipLaunchKernelGGL(ht_istft_kernel, dim3(T, S * 2, B), dim3(256), ht_istft_lds(n.plan), s, b.df[0], T, 4 * S, b.acc_f, (double)nf, b.frames,
-                       n.window.f(), reinterpret_cast<const float2 *>(n.tw.p), n.plan);
-  }));
-  return timed(e, ASX_PROF_OLA, 0.0, 4.0 * (double)B * S * 2 * (T * (double)c.nfft + 2.0 * L), s, [&]() {
-    hipLaunchKernelGGL(ht_ola_kernel, dim3((unsigned)((L + 255) / 256), S * 2, B), dim3(256), 0, s, b.frames, n.env_hop.f(), c.nfft, hop, T, L,
-                       b.dt[0], 2 * S, b.acc_t, gr.out);
-  });
+  return ht_ispec_launch(e, n.plan, n.window.f(), n.tw.p, n.env_hop.f(), b.df[0], B, T, S, b.acc_f, (double)nf, b.frames, b.dt[0], b.acc_t, L,
+                         gr.out, s);
 }
 
 // all groups, phase by phase (G[0] must be the engine's own nets)

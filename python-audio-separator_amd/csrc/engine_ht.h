@@ -331,27 +331,75 @@ static void ht_sin_2d(int C, int Fr, int T1, std::vector<float> &t) {   // rows 
   }
 }
 
+// The spectrogram side of the Demucs nets (HTDemucs / HDemucs _spec and _ispec), apart from any network: its tables, the dynamic-LDS grant
+// of its kernels and its launches.  engine_ht.h, engine_hd.h and the single-launch hooks (asx_op_ht_spec / asx_op_ht_ispec) all come here.
+static int ht_fft_tables(int nfft, DevBuf &window, DevBuf &tw_d, DevBuf &env_hop) {
+  const int hop = nfft / 4;
+  std::vector<float> w;
+  host_window(nfft, w);
+  CHK(ht_up(window, w));
+  std::vector<float> tw((size_t)nfft * 2);
+  for (int j = 0; j < nfft; ++j) {
+    const double ang = -2.0 * M_PI * (double)j / (double)nfft;
+    tw[2 * j] = (float)cos(ang);
+    tw[2 * j + 1] = (float)sin(ang);
+  }
+  CHK(ht_up(tw_d, tw));
+  std::vector<float> env((size_t)hop, 0.f);
+  for (int r = 0; r < hop; ++r)
+    for (int i = nfft / hop - 1; i >= 0; --i) env[r] += w[r + i * hop] * w[r + i * hop];   // frame order of torch's fold
+  return ht_up(env_hop, env);
+}
+static void ht_fft_grant_lds(const FftPlan &plan) {
+  // per engine (= per device), as every commit has always set it: not through the process-wide record of grant_lds
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ht_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)stft_lds(plan));
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ht_istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)ht_istft_lds(plan));
+}
+// pad1d's zero extension of inputs no longer than the reflect pad (hdemucs.py:21-34): el zeros in front, Lv samples in all
+static void ht_spec_extension(int64_t L, int T, int hop, int64_t *el, int64_t *Lv) {
+  *el = 0;
+  *Lv = L;
+  const int64_t left = hop / 2 * 3, right = left + (int64_t)T * hop - L, mx = std::max(left, right);
+  if (L <= mx) {
+    const int64_t extra = mx - L + 1, er = std::min(right, extra);
+    *el = extra - er;
+    *Lv = L + extra;
+  }
+}
+// seg [B, 2, L] -> spec [B, T, nfft / 2, 4]
+static int ht_spec_launch(asx_engine *e, const FftPlan &plan, const float *window, const void *tw, const float *seg, int B, int64_t L,
+                          int64_t el, int64_t Lv, int T, float *spec, hipStream_t s) {
+  const int hop = plan.n_fft / 4;
+  return timed(e, ASX_PROF_STFT, 0.0, 4.0 * (double)B * (2.0 * L + 4.0 * T * plan.nh), s, [&]() {
+    hipLaunchKernelGGL(ht_stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(plan), s, seg, L, el, Lv, hop, T, spec, window,
+                       reinterpret_cast<const float2 *>(tw), plan);
+  });
+}
+// CaC x [B, T, nfft / 2, 4 S] (de-standardised by acc_f over n_stat values) -> frames -> out [B, S, 2, L] = overlap-add + the waveform
+// branch xt [B, L, 2 S] (de-standardised by acc_t)
+static int ht_ispec_launch(asx_engine *e, const FftPlan &plan, const float *window, const void *tw, const float *env_hop, const float *x, int B,
+                           int T, int S, const double *acc_f, double n_stat, float *frames, const float *xt, const double *acc_t, int64_t L,
+                           float *out, hipStream_t s) {
+  const int nfft = plan.n_fft, hop = nfft / 4;
+  CHK(timed(e, ASX_PROF_ISTFT, 0.0, 4.0 * (double)B * S * 2 * T * (2.0 * plan.nh + nfft), s, [&]() {
+    hipLaunchKernelGGL(ht_istft_kernel, dim3(T, S * 2, B), dim3(256), ht_istft_lds(plan), s, x, T, 4 * S, acc_f, n_stat, frames, window,
+                       reinterpret_cast<const float2 *>(tw), plan);
+  }));
+  return timed(e, ASX_PROF_OLA, 0.0, 4.0 * (double)B * S * 2 * (T * (double)nfft + 2.0 * L), s, [&]() {
+    hipLaunchKernelGGL(ht_ola_kernel, dim3((unsigned)((L + 255) / 256), S * 2, B), dim3(256), 0, s, frames, env_hop, nfft, hop, T, L, xt,
+                       2 * S, acc_t, out);
+  });
+}
+
 // STFT tables and the triangular transition window of apply_model (apply.py:226-231) for segments of TL samples
 static int ht_commit_tables(asx_engine *e, int64_t TL) {
   HtNet &n = *e->ht;
   const asx_ht_config &c = n.cfg;
-  const int hop = c.nfft / 4;
   // tables
   {
-    std::vector<float> w;
-    host_window(c.nfft, w);
-    CHK(ht_up(n.window, w));
-    std::vector<float> tw((size_t)c.nfft * 2);
-    for (int j = 0; j < c.nfft; ++j) {
-      const double ang = -2.0 * M_PI * (double)j / (double)c.nfft;
-      tw[2 * j] = (float)cos(ang);
-      tw[2 * j + 1] = (float)sin(ang);
-    }
-    CHK(ht_up(n.tw, tw));
-    std::vector<float> env((size_t)hop, 0.f);
-    for (int r = 0; r < hop; ++r)
-      for (int i = c.nfft / hop - 1; i >= 0; --i) env[r] += w[r + i * hop] * w[r + i * hop];   // frame order of torch's fold
-    CHK(ht_up(n.env_hop, env));
+    CHK(ht_fft_tables(c.nfft, n.window, n.tw, n.env_hop));
     // triangular transition window (apply.py:226-231), float32 like torch
     std::vector<float> fw((size_t)TL);
     const int64_t h1 = TL / 2, h2 = TL - TL / 2;
@@ -475,10 +523,7 @@ static int ht_commit(asx_engine *e) {
       CHK(ht_load_tlayer(e, n.lay_t[i], "crosstransformer.layers_t." + std::to_string(i), i % 2 == 1, Ct, n.hidden));
     }
   }
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ht_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)stft_lds(n.plan));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ht_istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)ht_istft_lds(n.plan));
+  ht_fft_grant_lds(n.plan);
   n.ready = true;
   return ASX_OK;
 }
@@ -1129,10 +1174,7 @@ static int ht_forward_dev(asx_engine *e, const float *seg, int B, float *out, hi
   const int64_t TL = n.L[0];
   const int F0 = n.F[0];
   // spectrogram + per-sample standardisation of both branches (htdemucs.py:505-519)
-  CHK(timed(e, ASX_PROF_STFT, 0.0, 4.0 * (double)B * (2.0 * TL + 4.0 * T * F0), s, [&]() {
-    hipLaunchKernelGGL(ht_stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(n.plan), s, seg, TL, (int64_t)0, TL, hop, T, b.xf0, n.window.f(),
-                       reinterpret_cast<const float2 *>(n.tw.p), n.plan);
-  }));
+  CHK(ht_spec_launch(e, n.plan, n.window.f(), n.tw.p, seg, B, TL, 0, TL, T, b.xf0, s));
   const int64_t nf = (int64_t)T * F0 * 4;
   CHK(ht_stats(e, b.xf0, B, T, (int64_t)F0 * 4, (int64_t)F0 * 4, 4, 4, 1, b.acc_f, s));
   CHK(timed(e, ASX_PROF_MISC, 0.0, 8.0 * (double)B * nf, s, [&]() {
@@ -1195,14 +1237,8 @@ static int ht_forward_dev(asx_engine *e, const float *seg, int B, float *out, hi
   // decoders, deepest first (hdemucs.py:303-330); the input already holds x + skip
   for (int i = D - 1; i >= 0; --i) CHK(ht_dec_level(e, i, B, s));
   // CaC -> iSTFT, + waveform branch (htdemucs.py:589-612)
-  CHK(timed(e, ASX_PROF_ISTFT, 0.0, 4.0 * (double)B * S * 2 * T * (2.0 * F0 + c.nfft), s, [&]() {
-    hipLaunchKernelGGL(ht_istft_kernel, dim3(T, S * 2, B), dim3(256), ht_istft_lds(n.plan), s, b.df[0], T, 4 * S, b.acc_f,
-                       (double)nf, b.frames, n.window.f(), reinterpret_cast<const float2 *>(n.tw.p), n.plan);
-  }));
-  return timed(e, ASX_PROF_OLA, 0.0, 4.0 * (double)B * S * 2 * (T * (double)c.nfft + 2.0 * TL), s, [&]() {
-    hipLaunchKernelGGL(ht_ola_kernel, dim3((unsigned)((TL + 255) / 256), S * 2, B), dim3(256), 0, s, b.frames,
-                       n.env_hop.f(), c.nfft, hop, T, TL, b.dt[0], 2 * S, b.acc_t, out);
-  });
+  return ht_ispec_launch(e, n.plan, n.window.f(), n.tw.p, n.env_hop.f(), b.df[0], B, T, S, b.acc_f, (double)nf, b.frames, b.dt[0], b.acc_t,
+                         TL, out, s);
 }
 
 // 2*MAC per segment of the GEMM-shaped work

@@ -1212,27 +1212,52 @@ static int tdf_pack(TdfLayer &L, int n, int k, int c, const float *w, const floa
 // ----------------------------------------------------------------------------
 // STFT / iSTFT launch helpers (device buffers)
 // ----------------------------------------------------------------------------
-// pc != nullptr: a pool of songs -- chunk b reads the song pc->wave[b] / pc->n_song[b] (`wave` / `n_song` unused; the *_pool_kernel twins)
-static int stft_launch(asx_engine *e, const float *wave, const int64_t *d_starts, int64_t n_song, int B, int64_t C,
-                       int T, float *spec, int tf_layout, int zero_low, float sign, hipStream_t s, const PoolChunks *pc = nullptr) {
+// what a launch helper below ran, kept in asx_engine::fft_ran[0] for the single-launch hooks (asx_op_stft / asx_op_istft)
+enum { FFT_RAN_STFT = 1, FFT_RAN_STFT_POOL, FFT_RAN_STFT3, FFT_RAN_STFT3_POOL, FFT_RAN_STFT3P, FFT_RAN_STFT3P_POOL, FFT_RAN_ISTFT_OLA,
+       FFT_RAN_ISTFT3, FFT_RAN_ISTFT3P };
+
+// what a forward launch carries beyond the engine's geometry and tables.  The defaults are the MDX chunk loop's; subbands / out_bstride
+// are those of the TFC-TDF v3 nets (engine_v3.h), tf_layout 2 / trim 0 / the n_fft^-1/2 scale in `sign` those of the Roformers (engine_rof.h)
+struct StftGeom {
+  int tf_layout = 1;
+  int zero_low = 0;
+  float sign = 1.0f;
+  int subbands = 0;
+  int64_t out_bstride = 0;
+  int trim = -1;              // song mode: zeros in front of the song in the padded domain; < 0: n_fft / 2
+};
+
+// the StftArgs of one launch: every caller of stft_kernel / stft_pool_kernel fills them here
+static StftArgs stft_args(const asx_engine *e, const float *wave, const int64_t *d_starts, int64_t n_song, int64_t C, int T, float *spec,
+                          const StftGeom &g) {
   StftArgs a{};
   a.wave = wave;
   a.chunk_start = d_starts;
   a.n_song = n_song;
-  a.trim = e->cfg.n_fft / 2;
+  a.trim = g.trim >= 0 ? g.trim : e->cfg.n_fft / 2;
   a.C = C;
   a.hop = e->cfg.hop_length;
   a.T = T;
   a.dim_f = e->cfg.dim_f;
-  a.zero_low = zero_low;
-  a.tf_layout = tf_layout;
+  a.zero_low = g.zero_low;
+  a.tf_layout = g.tf_layout;
   a.spec = spec;
   a.window = e->d_window.f();
   a.tw = reinterpret_cast<const float2 *>(e->d_tw.p);
-  a.sign = sign;
+  a.sign = g.sign;
+  a.subbands = g.subbands;
+  a.out_bstride = g.out_bstride;
+  return a;
+}
+
+// pc != nullptr: a pool of songs -- chunk b reads the song pc->wave[b] / pc->n_song[b] (`wave` / `n_song` unused; the *_pool_kernel twins)
+static int stft_launch(asx_engine *e, const float *wave, const int64_t *d_starts, int64_t n_song, int B, int64_t C, int T, float *spec,
+                       const StftGeom &g, hipStream_t s, const PoolChunks *pc = nullptr) {
+  const StftArgs a = stft_args(e, wave, d_starts, n_song, C, T, spec, g);
   const double bytes = 4.0 * ((double)B * 2 * C + (double)B * 4 * T * e->cfg.dim_f);
   FftPlan p = e->plan;
-  if (e->fft3 && tf_layout == 1 && e->cfg.dim_f <= f3::NH) {
+  e->fft_ran[1] = 0;
+  if (e->fft3 && g.tf_layout == 1 && g.subbands == 0 && g.out_bstride == 0 && e->cfg.dim_f <= f3::NH) {
     // n_fft 6144 / hop 1024, engine-internal [B, 4, T, F] layout: three-pass register FFT (kernels_fft3.h)
     f3::Stft3Args f{};
     f.wave = wave;
@@ -1242,49 +1267,99 @@ static int stft_launch(asx_engine *e, const float *wave, const int64_t *d_starts
     f.C = C;
     f.T = T;
     f.dim_f = a.dim_f;
-    f.zero_low = zero_low;
+    f.zero_low = a.zero_low;
     f.spec = spec;
     f.window = a.window;
     f.tw = reinterpret_cast<const f3::cplx *>(a.tw);
     f.twB = reinterpret_cast<const f3::cplx *>(e->d_tw3.p);
     f.twC = f.twB + 16 * 12;
-    f.sign = sign;
+    f.sign = a.sign;
     // ~16 frames per workgroup, in even shares: many short workgroups balance better over the CUs than two or three rounds
     // of long ones (measured: 8 / 16 frames 0.257 / 0.253 ms, 20 frames in exactly two rounds 0.368 ms)
     f.n_groups = std::max(1, T / knobs().fft3_gs);
     return timed(e, ASX_PROF_STFT, 0.0, bytes, s, [&]() {
-      if (pc && e->fft3p)
+      if (pc && e->fft3p) {
         hipLaunchKernelGGL(f3::stft3p_pool_kernel, dim3(f.n_groups, 2, B), dim3(256), f3::STFT3P_LDS_BYTES, s, f, *pc);
-      else if (pc)
+        e->fft_ran[0] = FFT_RAN_STFT3P_POOL;
+      } else if (pc) {
         hipLaunchKernelGGL(f3::stft3_pool_kernel, dim3(T, 2, B), dim3(256), f3::STFT3_LDS_BYTES, s, f, *pc);
-      else if (e->fft3p)
+        e->fft_ran[0] = FFT_RAN_STFT3_POOL;
+      } else if (e->fft3p) {
         hipLaunchKernelGGL(f3::stft3p_kernel, dim3(f.n_groups, 2, B), dim3(256), f3::STFT3P_LDS_BYTES, s, f);
-      else
+        e->fft_ran[0] = FFT_RAN_STFT3P;
+      } else {
         hipLaunchKernelGGL(f3::stft3_kernel, dim3(T, 2, B), dim3(256), f3::STFT3_LDS_BYTES, s, f);
+        e->fft_ran[0] = FFT_RAN_STFT3;
+      }
     });
   }
   return timed(e, ASX_PROF_STFT, 0.0, bytes, s, [&]() {
-    if (pc) hipLaunchKernelGGL(stft_pool_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p, *pc);
-    else hipLaunchKernelGGL(stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p);
+    if (pc) {
+      hipLaunchKernelGGL(stft_pool_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p, *pc);
+      e->fft_ran[0] = FFT_RAN_STFT_POOL;
+    } else {
+      hipLaunchKernelGGL(stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p);
+      e->fft_ran[0] = FFT_RAN_STFT;
+    }
   });
 }
+static int stft_launch(asx_engine *e, const float *wave, const int64_t *d_starts, int64_t n_song, int B, int64_t C,
+                       int T, float *spec, int tf_layout, int zero_low, float sign, hipStream_t s, const PoolChunks *pc = nullptr) {
+  StftGeom g;
+  g.tf_layout = tf_layout;
+  g.zero_low = zero_low;
+  g.sign = sign;
+  return stft_launch(e, wave, d_starts, n_song, B, C, T, spec, g, s, pc);
+}
 
-static int istft_launch(asx_engine *e, const float *spec, int B, int T, int tf_layout, int combine, float *frames,
-                        hipStream_t s) {
+// what an inverse launch carries beyond the engine's geometry and tables; the defaults are the MDX chunk loop's
+struct IstftGeom {
+  int tf_layout = 1;
+  int combine = 0;
+  int subbands = 0;
+  int n_inst = 0;               // S stems per batch item: the launch covers B * S spectra
+  int64_t in_bstride = 0;
+  const float *mask = nullptr;  // tf_layout 2
+  const float *window = nullptr;   // synthesis window; nullptr: the engine's analysis window
+};
+
+// the IstftArgs of one launch: every caller of istft_kernel fills them here
+static IstftArgs istft_args(const asx_engine *e, const float *spec, int T, float *frames, const IstftGeom &g) {
   IstftArgs a{};
   a.spec = spec;
   a.T = T;
   a.dim_f = e->cfg.dim_f;
-  a.tf_layout = tf_layout;
-  a.combine = combine;
+  a.tf_layout = g.tf_layout;
+  a.combine = g.combine;
   a.frames = frames;
-  a.window = e->d_window.f();
+  a.window = g.window ? g.window : e->d_window.f();
   a.tw = reinterpret_cast<const float2 *>(e->d_tw.p);
-  const double bytes = 4.0 * ((double)B * 4 * T * e->cfg.dim_f * (combine ? 2 : 1) + (double)B * 2 * T * e->cfg.n_fft);
+  a.subbands = g.subbands;
+  a.n_inst = g.n_inst;
+  a.in_bstride = g.in_bstride;
+  a.mask = g.mask;
+  return a;
+}
+
+static int istft_launch(asx_engine *e, const float *spec, int B, int T, const IstftGeom &g, float *frames, hipStream_t s) {
+  const IstftArgs a = istft_args(e, spec, T, frames, g);
+  const int S = g.n_inst > 1 ? g.n_inst : 1;
+  // the spectra read once -- with a mask, one spectrum per item and S masks -- and the frames written once
+  const double spectra = g.mask ? (double)B * (1 + S) : (double)B * S * (g.combine ? 2 : 1);
+  const double bytes = 4.0 * (spectra * 4 * T * e->cfg.dim_f + (double)B * S * 2 * T * e->cfg.n_fft);
   FftPlan p = e->plan;
+  e->fft_ran[1] = 0;
   return timed(e, ASX_PROF_ISTFT, 0.0, bytes, s, [&]() {
-    hipLaunchKernelGGL(istft_kernel, dim3(T, 2, B), dim3(256), istft_lds(p), s, a, p);
+    hipLaunchKernelGGL(istft_kernel, dim3(T, 2, B * S), dim3(256), istft_lds(p), s, a, p);
+    e->fft_ran[0] = FFT_RAN_ISTFT_OLA;
   });
+}
+static int istft_launch(asx_engine *e, const float *spec, int B, int T, int tf_layout, int combine, float *frames,
+                        hipStream_t s) {
+  IstftGeom g;
+  g.tf_layout = tf_layout;
+  g.combine = combine;
+  return istft_launch(e, spec, B, T, g, frames, s);
 }
 
 static int ola_launch(asx_engine *e, const float *frames, const float *env, const int64_t *d_nact, int B, int T,
@@ -1299,12 +1374,14 @@ static int ola_launch(asx_engine *e, const float *frames, const float *env, cons
 
 // STFT.inverse + the chunk's Hann window: the fast path (n_fft 6144 / hop 1024) inverse-transforms, overlap-adds in an LDS
 // ring and writes the chunk directly (kernels_fft3.h); every other geometry runs istft_kernel -> frames -> ola_kernel.
+// env: the window envelope for T frames (nullptr: the engine's, for T = segment_size)
 static int istft_ola_launch(asx_engine *e, const float *spec, int B, int T, int combine, const int64_t *d_nact, int64_t C,
-                            float *out, hipStream_t s) {
+                            float *out, hipStream_t s, const float *env = nullptr) {
+  if (!env) env = e->d_env.f();
   // emit_hop / emit_finish / seam3_kernel store float4: `out` (the caller's chunk buffer + a chunk offset) must be 16-byte aligned
   if (!(e->fft3 && e->cfg.dim_f <= f3::NH && C == (int64_t)f3::HOP * (T - 1) && (reinterpret_cast<uintptr_t>(out) & 15) == 0)) {
     CHK(istft_launch(e, spec, B, T, 1, combine, e->frames.f(), s));
-    return ola_launch(e, e->frames.f(), e->d_env.f(), d_nact, B, T, C, out, s);
+    return ola_launch(e, e->frames.f(), env, d_nact, B, T, C, out, s);
   }
   // >= 16 frames per workgroup, in even shares.  The grouping depends on T only: a hop on a seam is summed as
   // (tail partial) + (head partial), so results stay bit-identical whatever the batch size.
@@ -1319,7 +1396,7 @@ static int istft_ola_launch(asx_engine *e, const float *spec, int B, int T, int 
   f.tw = reinterpret_cast<const f3::cplx *>(e->d_tw.p);
   f.twB = reinterpret_cast<const f3::cplx *>(e->d_tw3.p);
   f.twC = f.twB + 16 * 12;
-  f.env = e->d_env.f();
+  f.env = env;
   f.n_act = d_nact;
   f.C = C;
   f.out = out;
@@ -1328,19 +1405,26 @@ static int istft_ola_launch(asx_engine *e, const float *spec, int B, int T, int 
   f.hann = (C == (int64_t)e->cfg.hop_length * (e->cfg.segment_size - 1) && e->d_hann3.p) ? reinterpret_cast<const double *>(e->d_hann3.p) : nullptr;
   // algorithmic bytes: the spectrogram read once, the chunk written once (the seam buffer's round trip is overhead, not counted)
   const double bytes = 4.0 * ((double)B * 4 * T * e->cfg.dim_f * (combine ? 2 : 1) + (double)B * 2 * C);
+  const bool aligned = e->cfg.dim_f % 4 == 0 && (reinterpret_cast<uintptr_t>(spec) & 15) == 0;
+  e->fft_ran[1] = 0;
   return timed(e, ASX_PROF_ISTFT, 0.0, bytes, s, [&]() {
-    const bool aligned = e->cfg.dim_f % 4 == 0 && (reinterpret_cast<uintptr_t>(spec) & 15) == 0;
     if (e->fft3p && combine == 0 && aligned)
     {
+      e->fft_ran[0] = FFT_RAN_ISTFT3P;
       const int abl = knobs().istft_abl;
       if (abl == 1) hipLaunchKernelGGL(f3::istft3p_kernel<1>, dim3(ng, 2, B), dim3(256), f3::ISTFT3P_LDS_BYTES, s, f);
       else if (abl == 2) hipLaunchKernelGGL(f3::istft3p_kernel<2>, dim3(ng, 2, B), dim3(256), f3::ISTFT3P_LDS_BYTES, s, f);
       else if (abl == 3) hipLaunchKernelGGL(f3::istft3p_kernel<3>, dim3(ng, 2, B), dim3(256), f3::ISTFT3P_LDS_BYTES, s, f);
       else hipLaunchKernelGGL(f3::istft3p_kernel<0>, dim3(ng, 2, B), dim3(256), f3::ISTFT3P_LDS_BYTES, s, f);
     }
-    else
+    else {
       hipLaunchKernelGGL(f3::istft3_kernel, dim3(ng, 2, B), dim3(256), f3::ISTFT3_LDS_BYTES, s, f);
-    if (ng > 1) hipLaunchKernelGGL(f3::seam3_kernel, dim3(5, ng - 1, B * 2), dim3(256), 0, s, f);
+      e->fft_ran[0] = FFT_RAN_ISTFT3;
+    }
+    if (ng > 1) {
+      hipLaunchKernelGGL(f3::seam3_kernel, dim3(5, ng - 1, B * 2), dim3(256), 0, s, f);
+      e->fft_ran[1] = 1;
+    }
   });
 }
 

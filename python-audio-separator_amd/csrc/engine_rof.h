@@ -384,17 +384,38 @@ static int rof_transformer(asx_engine *e, std::vector<RofLayer> &layers, bool ti
 
 // torch.istft(normalized=True) multiplies the spectrum by sqrt(n_fft) before the inverse transform: folded into the synthesis window
 // (the fold's envelope keeps the plain window squared)
-static int rof_build_win_synth(asx_engine *e) {
-  RofNet &n = *e->rof;
-  if (!n.cfg.stft_normalized || n.win_synth.p) return ASX_OK;
+static int rof_win_synth(const asx_engine *e, DevBuf &dst) {
   std::vector<float> w;
   if ((int)e->custom_window.size() == e->cfg.n_fft) w = e->custom_window;
   else host_window(e->cfg.n_fft, w, e->cfg.win_length);
   const float sc = (float)sqrt((double)e->cfg.n_fft);
   for (auto &v : w) v *= sc;
-  CHK(n.win_synth.ensure(w.size() * 4));
-  HIPCHK(hipMemcpy(n.win_synth.p, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+  CHK(dst.ensure(w.size() * 4));
+  HIPCHK(hipMemcpy(dst.p, w.data(), w.size() * 4, hipMemcpyHostToDevice));
   return ASX_OK;
+}
+static int rof_build_win_synth(asx_engine *e) {
+  RofNet &n = *e->rof;
+  if (!n.cfg.stft_normalized || n.win_synth.p) return ASX_OK;
+  return rof_win_synth(e, n.win_synth);
+}
+
+// the Roformers' STFT / iSTFT (bs_roformer.py:455-459, 503-511): `b t (f s c)` rows, no front padding, the complex mask folded into the
+// inverse's loads.  torch.stft(normalized=True) (bs_roformer.py:332, 384): the spectrum times n_fft^-1/2
+static StftGeom rof_stft_geom(const asx_engine *e, bool normalized) {
+  StftGeom g;
+  g.tf_layout = 2;
+  g.trim = 0;
+  g.sign = normalized ? (float)(1.0 / sqrt((double)e->cfg.n_fft)) : 1.0f;
+  return g;
+}
+static IstftGeom rof_istft_geom(const float *mask, int S, const float *win_synth) {
+  IstftGeom g;
+  g.tf_layout = 2;
+  g.mask = mask;
+  g.n_inst = S;
+  g.window = win_synth;
+  return g;
 }
 
 static int rof_ensure_workspace(asx_engine *e, int B) {
@@ -440,27 +461,7 @@ static int rof_chunks_dev(asx_engine *e, const float *wave, const int64_t *d_sta
   const int64_t BT = (int64_t)B * T, M = BT * Fb;
   CHK(rof_ensure_workspace(e, B));
   {
-    StftArgs a{};
-    a.wave = wave;
-    a.chunk_start = d_starts;
-    a.n_song = n_song;
-    a.trim = 0;
-    a.C = C;
-    a.hop = e->cfg.hop_length;
-    a.T = T;
-    a.dim_f = e->cfg.dim_f;
-    a.zero_low = 0;
-    a.tf_layout = 2;
-    a.spec = n.X0.f();
-    a.window = e->d_window.f();
-    a.tw = reinterpret_cast<const float2 *>(e->d_tw.p);
-    // torch.stft(normalized=True) (bs_roformer.py:332, 384): the spectrum times n_fft^-1/2
-    a.sign = c.stft_normalized ? (float)(1.0 / sqrt((double)e->cfg.n_fft)) : 1.0f;
-    FftPlan p = e->plan;
-    CHK(timed(e, ASX_PROF_STFT, 0.0, 4.0 * ((double)B * 2 * C + (double)BT * n.W), s, [&]() {
-      if (pc) hipLaunchKernelGGL(stft_pool_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p, *pc);
-      else hipLaunchKernelGGL(stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p);
-    }));
+    CHK(stft_launch(e, wave, d_starts, n_song, B, C, T, n.X0.f(), rof_stft_geom(e, c.stft_normalized), s, pc));
   }
   // band split (bs_roformer.py:163-185): per band RMSNorm + Linear -> TOK[(b t), band, :]
   for (int j = 0; j < Fb; ++j) {
@@ -511,20 +512,7 @@ static int rof_chunks_dev(asx_engine *e, const float *wave, const int64_t *d_sta
     }));
   }
   {
-    IstftArgs a{};
-    a.spec = n.X0.f();
-    a.mask = n.MASK.f();
-    a.T = T;
-    a.dim_f = e->cfg.dim_f;
-    a.tf_layout = 2;
-    a.combine = 0;
-    a.frames = n.frames.f();
-    a.window = c.stft_normalized ? n.win_synth.f() : e->d_window.f();
-    a.tw = reinterpret_cast<const float2 *>(e->d_tw.p);
-    a.n_inst = S;
-    FftPlan p = e->plan;
-    CHK(timed(e, ASX_PROF_ISTFT, 0.0, 4.0 * ((double)BT * n.W * (1 + S) + (double)B * S * 2 * T * e->cfg.n_fft), s,
-              [&]() { hipLaunchKernelGGL(istft_kernel, dim3(T, 2, B * S), dim3(256), istft_lds(p), s, a, p); }));
+    CHK(istft_launch(e, n.X0.f(), B, T, rof_istft_geom(n.MASK.f(), S, c.stft_normalized ? n.win_synth.f() : nullptr), n.frames.f(), s));
   }
   CHK(ola_launch(e, n.frames.f(), e->d_env.f(), nullptr, B * S, T, C, out, s));
   return ASX_OK;

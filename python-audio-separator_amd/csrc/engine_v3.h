@@ -351,6 +351,23 @@ static int v3_core_dev(asx_engine *e, int B, hipStream_t s) {
   return ASX_OK;
 }
 
+// the TFC-TDF v3 nets' STFT / iSTFT: [B, 4, T, F] planes cut into k subbands (cac2cws / cws2cac, tfc_tdf_v3.py:216-223), the forward
+// writing into the first dim_c planes of a wider tensor (`bstride` floats per batch item), the inverse reading S stems per item
+static StftGeom v3_stft_geom(int k, int64_t bstride, int front) {
+  StftGeom g;
+  g.subbands = k;
+  g.out_bstride = bstride;
+  g.trim = front;
+  return g;
+}
+static IstftGeom v3_istft_geom(int k, int S, int64_t bstride) {
+  IstftGeom g;
+  g.subbands = k;
+  g.n_inst = S;
+  g.in_bstride = bstride;
+  return g;
+}
+
 // chunk waves -> separated chunk waves [B, S, 2, C]; input either explicit chunks [B,2,C] (n_song < 0)
 // or windows of the resident mix (song mode, front zeros = `front`); pc: a pass over a pool of songs -- chunk b is a window of ITS
 // song (stft_pool_kernel), everything behind the STFT is the same code
@@ -366,49 +383,11 @@ static int v3_chunks_dev(asx_engine *e, const float *wave, const int64_t *d_star
   const int64_t C = (int64_t)e->cfg.hop_length * (T - 1);
   const int64_t P0 = (int64_t)T * Fs;
   CHK(v3_ensure_workspace(e, B));
-  {
-    StftArgs a{};
-    a.wave = wave;
-    a.chunk_start = d_starts;
-    a.n_song = n_song;
-    a.trim = front;
-    a.C = C;
-    a.hop = e->cfg.hop_length;
-    a.T = T;
-    a.dim_f = e->cfg.dim_f;
-    a.zero_low = 0;
-    a.tf_layout = 1;
-    a.spec = n.cat0.f();
-    a.window = e->d_window.f();
-    a.tw = reinterpret_cast<const float2 *>(e->d_tw.p);
-    a.sign = 1.0f;
-    a.subbands = k;
-    a.out_bstride = (int64_t)(dim_c + cf.num_channels_model) * P0;
-    FftPlan p = e->plan;
-    CHK(timed(e, ASX_PROF_STFT, 0.0, 4.0 * ((double)B * 2 * C + (double)B * 4 * T * e->cfg.dim_f), s, [&]() {
-      if (pc) hipLaunchKernelGGL(stft_pool_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p, *pc);
-      else hipLaunchKernelGGL(stft_kernel, dim3(T, 2, B), dim3(256), stft_lds(p), s, a, p);
-    }));
-  }
+  CHK(stft_launch(e, wave, d_starts, n_song, B, C, T, n.cat0.f(), v3_stft_geom(k, (int64_t)(dim_c + cf.num_channels_model) * P0, front), s,
+                  pc));
   CHK(v3_core_dev(e, B, s));
   const int S = cf.num_targets;
-  {
-    IstftArgs a{};
-    a.spec = n.out_spec.f();
-    a.T = T;
-    a.dim_f = e->cfg.dim_f;
-    a.tf_layout = 1;
-    a.combine = 0;
-    a.frames = n.frames.f();
-    a.window = e->d_window.f();
-    a.tw = reinterpret_cast<const float2 *>(e->d_tw.p);
-    a.subbands = k;
-    a.n_inst = S;
-    a.in_bstride = (int64_t)S * dim_c * P0;
-    FftPlan p = e->plan;
-    CHK(timed(e, ASX_PROF_ISTFT, 0.0, 4.0 * ((double)B * S * 4 * T * e->cfg.dim_f + (double)B * S * 2 * T * e->cfg.n_fft),
-              s, [&]() { hipLaunchKernelGGL(istft_kernel, dim3(T, 2, B * S), dim3(256), istft_lds(p), s, a, p); }));
-  }
+  CHK(istft_launch(e, n.out_spec.f(), B, T, v3_istft_geom(k, S, (int64_t)S * dim_c * P0), n.frames.f(), s));
   CHK(ola_launch(e, n.frames.f(), e->d_env.f(), nullptr, B * S, T, C, out, s));
   return ASX_OK;
 }

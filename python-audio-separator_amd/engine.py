@@ -254,7 +254,7 @@ class HDConfig:
 _FP = C.POINTER(C.c_float)
 _lib = None
 
-ABI_VERSION = 7   # ASX_ABI_VERSION of include/asx.h the structures below mirror
+ABI_VERSION = 8   # ASX_ABI_VERSION of include/asx.h the structures below mirror
 
 # every symbol include/asx.h declares
 SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_create", "asx_engine_destroy",
@@ -282,7 +282,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_flac_decode_plan", "asx_flac_decode_scan_dev", "asx_flac_decode_finish_dev", "asx_flac_decode",
            "asx_flac_plan_pcm", "asx_flac_encode_pcm", "asx_flac_encode_pcm_dev", "asx_pcm_encode", "asx_pcm_encode_dev",
            "asx_invert_stem_dev", "asx_invert_stem_batch_dev", "asx_op_gconv", "asx_op_dconv", "asx_resample_sinc_batch_dev",
-           "asx_resample_rational_stem", "asx_resample_rational_stem_dev"]
+           "asx_resample_rational_stem", "asx_resample_rational_stem_dev", "asx_op_stft", "asx_op_istft", "asx_op_ht_spec",
+           "asx_op_ht_ispec"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -297,6 +298,19 @@ class _GconvDesc(C.Structure):     # struct asx_gconv_desc
     _fields_ = [(n, C.c_int32) for n in ("B", "O", "I", "Cin", "ldc", "Cout", "ldy", "KO", "KI", "DO", "DI", "PO", "PI", "SO", "SI", "OR",
                                          "IR", "x_col0", "y_col0", "mode", "act", "res", "ldr", "res_mod", "Iout", "crop", "So",
                                          "no_halo")] + [("x_bs", C.c_int64), ("y_bs", C.c_int64)]
+
+
+# asx_op_stft / asx_op_istft: resolved[0] as an index (0: nothing ran)
+STFT_KERNELS = (None, "stft", "stft_pool", "stft3", "stft3_pool", "stft3p", "stft3p_pool", "istft+ola", "istft3", "istft3p")
+STFT_MODES = {"chunks": 0, "song": 1, "pool": 2}
+
+
+class _StftDesc(C.Structure):      # struct asx_stft_desc
+    _fields_ = [(n, C.c_int32) for n in ("b", "t", "layout", "subbands", "zero_low", "n_inst", "combine", "stft_normalized", "mode", "front",
+                                         "n_songs")] + [("sign", C.c_float), ("c", C.c_int64), ("bstride", C.c_int64),
+                                                        ("spec_floats", C.c_int64), ("starts", C.POINTER(C.c_int64)),
+                                                        ("song_of", C.POINTER(C.c_int32)), ("song_len", C.POINTER(C.c_int64)),
+                                                        ("n_act", C.POINTER(C.c_int64))]
 
 
 class _LaunchRec(C.Structure):     # struct asx_launch_rec
@@ -401,6 +415,11 @@ def load_library():
     lib.asx_op_vr_lstm.argtypes = [vp, _FP, _FP, i32, i32, i32, _FP]
     lib.asx_op_vr_lstm_layout.argtypes = [vp, i32, _FP, i32, i32, i32, i32, i32, _FP]
     lib.asx_op_gconv.argtypes = [vp, C.POINTER(_GconvDesc), _FP, _FP, _FP, _FP, C.c_char_p, _FP, C.POINTER(i32)]
+    lib.asx_op_stft.argtypes = [vp, C.POINTER(_StftDesc), _FP, _FP, C.POINTER(i32)]
+    lib.asx_op_istft.argtypes = [vp, C.POINTER(_StftDesc), _FP, _FP, _FP, C.POINTER(i32)]
+    _DP = C.POINTER(C.c_double)
+    lib.asx_op_ht_spec.argtypes = [vp, i32, _FP, i32, i64, i64, i64, _FP]
+    lib.asx_op_ht_ispec.argtypes = [vp, i32, _FP, i32, i32, i32, _DP, C.c_double, _FP, _DP, i64, _FP]
     lib.asx_op_dconv.argtypes = [vp, _FP, i32, i32, i32, i32, i32, i32, i32, i32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                                  C.POINTER(i32)]
     lib.asx_v3_begin.argtypes = [vp, C.POINTER(_V3Cfg)]
@@ -1820,6 +1839,96 @@ class Engine:
         ran = (C.c_int32 * 3)(0, 0, 0)
         self._check(self._lib.asx_op_gconv(self._h, C.byref(d), _ptr(x), _ptr(w), _ptr(b), _optptr(res), variant.encode(), _ptr(y), ran))
         return y, (GCONV_VARIANTS[ran[0]] if ran[0] else None, int(ran[1]), int(ran[2]))
+
+    def _stft_desc(self, keep, **kw):
+        """asx_stft_desc from keywords (fields left out are 0, sign 1; mode as "chunks" / "song" / "pool" or its number; starts / song_of /
+        song_len / n_act as sequences).  `keep` collects the arrays the descriptor points into."""
+        d = _StftDesc()
+        d.sign = 1.0
+        for k, v in kw.items():
+            if not hasattr(d, k):
+                raise AsxError(f"asx_stft_desc has no field {k!r}")
+            if k in ("starts", "song_len", "n_act", "song_of"):
+                if v is None:
+                    continue
+                a = np.ascontiguousarray(v, dtype=np.int32 if k == "song_of" else np.int64)
+                keep[k] = a
+                setattr(d, k, a.ctypes.data_as(C.POINTER(C.c_int32 if k == "song_of" else C.c_int64)))
+            elif k == "sign":
+                d.sign = float(v)
+            else:
+                setattr(d, k, int(STFT_MODES[v] if k == "mode" and isinstance(v, str) else v))
+        return d
+
+    def op_stft(self, wave, spec, **desc):
+        """One forward STFT launch (asx_op_stft, include/asx.h): `desc` holds the fields of asx_stft_desc (spec_floats is taken from
+        `spec`), `wave` the flat host samples the mode asks for.  `spec` is uploaded before the launch and returned updated.
+        Returns (spec, (kernel name, seam launches))."""
+        wave = _f32(wave).reshape(-1)
+        spec = np.array(spec, np.float32, order="C")
+        keep = {}
+        d = self._stft_desc(keep, spec_floats=spec.size, **desc)
+        if d.mode == 0:
+            want = d.b * 2 * d.c
+        else:
+            lens = keep.get("song_len")
+            if lens is None or lens.size != (1 if d.mode == 1 else d.n_songs) or "starts" not in keep or keep["starts"].size != d.b or \
+                    (d.mode == 2 and ("song_of" not in keep or keep["song_of"].size != d.b)):
+                raise AsxError(f"op_stft: mode {d.mode} needs song_len [{1 if d.mode == 1 else d.n_songs}], starts [b]" +
+                               (" and song_of [b]" if d.mode == 2 else ""))
+            want = 2 * int(lens.sum())
+        if wave.size != want:
+            raise AsxError(f"op_stft: wave holds {wave.size} floats, the descriptor wants {want}")
+        ran = (C.c_int32 * 2)(0, 0)
+        self._check(self._lib.asx_op_stft(self._h, C.byref(d), _ptr(wave), _ptr(spec), ran))
+        return spec, (STFT_KERNELS[ran[0]], int(ran[1]))
+
+    def op_istft(self, spec, wave, mask=None, **desc):
+        """One inverse launch (asx_op_istft: istft_kernel + ola_kernel, or the fused fast path): `spec` the flat host spectrum, `mask`
+        [b, n_inst, t, dim_f, 2, 2] for layout 2, `wave` [b * max(n_inst, 1), 2, c] uploaded first and returned updated.
+        Returns (wave, (kernel name, seam launches))."""
+        spec = _f32(spec).reshape(-1)
+        wave = np.array(wave, np.float32, order="C")
+        mask = _f32(mask).reshape(-1) if mask is not None else None
+        keep = {}
+        d = self._stft_desc(keep, spec_floats=spec.size, **desc)
+        S = max(d.n_inst, 1)
+        if wave.size != d.b * S * 2 * d.c or (mask is not None and mask.size != d.b * S * d.t * self.cfg.dim_f * 4):
+            raise AsxError(f"op_istft: wave {wave.size} / mask {None if mask is None else mask.size} floats do not fit the descriptor")
+        if "n_act" in keep and keep["n_act"].size != d.b * S:
+            raise AsxError("op_istft: n_act needs one entry per output chunk")
+        ran = (C.c_int32 * 2)(0, 0)
+        self._check(self._lib.asx_op_istft(self._h, C.byref(d), _ptr(spec), _optptr(mask), _ptr(wave), ran))
+        return wave, (STFT_KERNELS[ran[0]], int(ran[1]))
+
+    def op_ht_spec(self, nfft, seg, el=0, lv=None, spec=None):
+        """One ht_stft_kernel launch (asx_op_ht_spec): seg [B, 2, L] -> [B, T = ceil(L / hop), nfft / 2, 2 (channel), 2 (re, im)];
+        el / lv: pad1d's zero extension (default none).  `spec` (default NaN) is uploaded first."""
+        seg = _f32(seg)
+        B, _, L = seg.shape
+        hop = nfft // 4
+        shape = (B, -(-L // hop), nfft // 2, 2, 2)
+        spec = np.full(shape, np.nan, np.float32) if spec is None else np.array(spec, np.float32, order="C")
+        if seg.shape[1] != 2 or spec.shape != shape:
+            raise AsxError(f"op_ht_spec: seg {seg.shape} / spec {spec.shape}, expected [B, 2, L] / {shape}")
+        self._check(self._lib.asx_op_ht_spec(self._h, int(nfft), _ptr(seg), B, L, int(el), int(L if lv is None else lv), _ptr(spec)))
+        return spec
+
+    def op_ht_ispec(self, nfft, x, acc_f, n_stat, xt, acc_t, out=None):
+        """ht_istft_kernel + ht_ola_kernel (asx_op_ht_ispec): x [B, T, nfft / 2, 4 S], xt [B, L, 2 S] -> out [B, S, 2, L]; acc_f / acc_t
+        [B, 2] float64 (sum, sum of squares) over n_stat spectrogram values / 2 L samples.  `out` (default NaN) is uploaded first."""
+        x, xt = _f32(x), _f32(xt)
+        B, T, nh, c4 = x.shape
+        S, L = c4 // 4, xt.shape[1]
+        acc_f = np.ascontiguousarray(acc_f, np.float64)
+        acc_t = np.ascontiguousarray(acc_t, np.float64)
+        out = np.full((B, S, 2, L), np.nan, np.float32) if out is None else np.array(out, np.float32, order="C")
+        if nh != nfft // 2 or c4 != 4 * S or xt.shape != (B, L, 2 * S) or acc_f.shape != (B, 2) or acc_t.shape != (B, 2) or out.shape != (B, S, 2, L):
+            raise AsxError(f"op_ht_ispec: x {x.shape} / xt {xt.shape} / acc {acc_f.shape} {acc_t.shape} / out {out.shape} do not fit")
+        dp = C.POINTER(C.c_double)
+        self._check(self._lib.asx_op_ht_ispec(self._h, int(nfft), _ptr(x), B, T, S, acc_f.ctypes.data_as(dp), float(n_stat), _ptr(xt),
+                                              acc_t.ctypes.data_as(dp), L, _ptr(out)))
+        return out
 
     def op_dconv(self, y, p, along_outer, d, part=3, h=None):
         """One DConv layer (asx_op_dconv) on y [B, O, I, C] channels-last; p: dict of the layer's torch tensors w1 [hid, C, 3], b1, g1w,

@@ -32,7 +32,7 @@ def test_header_symbols_exported(lib):
 def test_abi_version(lib):
     hdr = open(os.path.join(ROOT, "include", "asx.h")).read()
     declared = int(re.search(r"#define\s+ASX_ABI_VERSION\s+(\d+)", hdr).group(1))
-    assert lib.asx_abi_version() == declared == E.ABI_VERSION == 7
+    assert lib.asx_abi_version() == declared == E.ABI_VERSION == 8
 
 
 def test_binding_refuses_a_library_of_another_abi(monkeypatch):
@@ -85,7 +85,7 @@ def test_header_is_plain_c_and_struct_layouts_match(tmp_path):
     pairs = [("asx_mdx_config", E._MdxCfg), ("asx_net_config", E._NetCfg), ("asx_plan", E._Plan), ("asx_profile", E._Profile),
              ("asx_v3_config", E._V3Cfg), ("asx_rof_config", E._RofCfg), ("asx_ht_config", E._HtCfg), ("asx_hd_config", E._HdCfg), ("asx_vr_band", E._VrBand),
              ("asx_vr_config", E._VrCfg), ("asx_vr_params", E._VrParams), ("asx_launch_rec", E._LaunchRec),
-             ("asx_gconv_desc", E._GconvDesc)]
+             ("asx_gconv_desc", E._GconvDesc), ("asx_stft_desc", E._StftDesc)]
     src = '#include <stdio.h>\n#include "asx.h"\nint main(void) {\n' + \
           "".join(f'  printf("{n} %zu\\n", sizeof({n}));\n' for n, _ in pairs) + "  return 0;\n}\n"
     c = tmp_path / "sizes.c"

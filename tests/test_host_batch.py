@@ -164,7 +164,7 @@ def test_header_declares_and_binding_matches():
         fields = [re.sub(r"[\s\*]", " ", f).split()[-1] for f in m.group(1).split(";") if f.strip()]
         assert fields == [n for n, _ in mirror._fields_], (struct, fields)
         assert C.sizeof(mirror) == 8 * len(fields)
-    assert lib.asx_abi_version() == 7
+    assert lib.asx_abi_version() == 8
     # the entry points validate before they touch the engine
     assert lib.asx_demix_batch_dev(None, None, 0, 0, None) != 0 and lib.asx_separate_batch_dev(None, None, 0, 0.9, 0.0, 0, 1.0, None) != 0
 

@@ -355,6 +355,6 @@ def test_header_is_plain_c_with_the_job_struct(tmp_path):
                    check=True)
     assert C.sizeof(E._EnsJob) == 224 and E._EnsJob.out_dev.offset == 168 and E._EnsJob.peak_after.offset == 192
     assert [n for n, _ in E._EnsJob._fields_] == ["k", "live", "stem_dev", "n_samples", "layout", "out_dev", "out_capacity", "n_out", "peak_after"]
-    assert E.ABI_VERSION == 7 and "asx_ensemble_batch_dev" in E.SYMBOLS and E.ENS_MAX_K == 8
+    assert E.ABI_VERSION == 8 and "asx_ensemble_batch_dev" in E.SYMBOLS and E.ENS_MAX_K == 8
     header = open(os.path.join(ROOT, "include", "asx.h")).read()
-    assert "#define ASX_ENS_MAX_K 8" in header and "#define ASX_ABI_VERSION 7" in header
+    assert "#define ASX_ENS_MAX_K 8" in header and "#define ASX_ABI_VERSION 8" in header

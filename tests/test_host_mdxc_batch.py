@@ -322,6 +322,6 @@ def test_header_is_plain_c_with_the_mdxc_song_struct(tmp_path):
     subprocess.run([gcc, "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(c), "-o",
                     str(tmp_path / "song.o")], check=True)
     assert C.sizeof(E._MdxcSong) == 24 and [n for n, _ in E._MdxcSong._fields_] == ["mix_dev", "out_dev", "n_samples"]
-    assert E.ABI_VERSION == 7 and {"asx_mdxc_demix_batch_dev", "asx_rof_demix_batch_dev"} <= set(E.SYMBOLS)
+    assert E.ABI_VERSION == 8 and {"asx_mdxc_demix_batch_dev", "asx_rof_demix_batch_dev"} <= set(E.SYMBOLS)
     for name in ("mdxc_demix_batch", "mdxc_demix_batch_dev", "rof_demix_batch", "rof_demix_batch_dev"):
         assert callable(getattr(E.Engine, name)), name

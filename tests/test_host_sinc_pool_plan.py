@@ -134,7 +134,7 @@ def test_header_is_plain_c_with_the_sinc_job_struct(tmp_path):
     subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c_file), "-o", exe], check=True)
     got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
     J = E._SincJob
-    assert got == [C.sizeof(J), J.x_dev.offset, J.y_dev.offset, J.n_in.offset, J.n_out.offset, J.channels.offset, J.reserved.offset, 7]
+    assert got == [C.sizeof(J), J.x_dev.offset, J.y_dev.offset, J.n_in.offset, J.n_out.offset, J.channels.offset, J.reserved.offset, 8]
     assert "asx_resample_sinc_batch_dev" in E.SYMBOLS and callable(E.Engine.resample_sinc_batch_dev)
 
 

@@ -173,5 +173,5 @@ def test_header_is_plain_c_with_the_song_struct(tmp_path):
     subprocess.run([gcc, "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(c), "-o", str(obj)],
                    check=True)
     assert C.sizeof(E._VrSong) == 32 and [n for n, _ in E._VrSong._fields_] == ["wave_dev", "n_samples", "primary_dev", "secondary_dev"]
-    assert E.ABI_VERSION == 7 and "asx_vr_separate_batch_dev" in E.SYMBOLS
+    assert E.ABI_VERSION == 8 and "asx_vr_separate_batch_dev" in E.SYMBOLS
     assert E.VR_POOL_SEGMENTS == int(__import__("re").search(r"#define\s+ASX_VR_POOL_SEGMENTS\s+(\d+)", open(os.path.join(ROOT, "include", "asx.h")).read()).group(1))
