@@ -749,13 +749,25 @@ int asx_invert_stem(asx_engine *e, const float *mix_host, const float *stem_host
  *   mode       ASX_SLOT_PCM16:   slot[c, i] = (float)q[i, c] / 32768 with q the int16 asx_pcm16_dev / asx_pcm16_rows_dev write
  *                                for the same stem and thresholds (bit for bit); *peak_after as those calls return it
  *              ASX_SLOT_FLOAT32: slot[c, i] = stem value, no normalisation, no quantisation; *peak_after = max |stem|
+ *              ASX_SLOT_FILE_PCM16 / _PCM24 / _PCM32 / _FLOAT: the round trip of a member that writes with soundfile
+ *                                (write_audio_soundfile + audio_io.load): slot = the float32 array asx_pcm_decode_dev returns for the
+ *                                bytes asx_pcm_encode_dev writes for the same stem, layout and thresholds in that sample format, bit
+ *                                for bit -- spec_utils.normalize, then clip(rint((double)x * (2^(b-1) - 1))) read back as
+ *                                int / 2^(b-1), or the normalised float itself; *peak_after as asx_pcm_encode_dev reports it.  The
+ *                                values are that call's sample_format codes.  ASX_SLOT_FILE_PCM16 rounds where ASX_SLOT_PCM16
+ *                                (pydub's writer) truncates: they are different modes.
  *   padding    slot[c, i] = 0 for n <= i < n_max, written by this call: the stack need not be cleared
  * Requires 0 <= n <= n_max (stem_dev may be NULL when n == 0), n_max >= 1, k >= 0; the caller owns a stack of at least
- * (k + 1) * 2 * n_max floats.  peak_after may be NULL (then the call only enqueues work).  Additive to ABI 7. */
+ * (k + 1) * 2 * n_max floats.  peak_after may be NULL (then the call only enqueues work).  Additive to ABI 7; the file modes are
+ * additive within ABI 8. */
 #define ASX_STEM_PLANAR 0
 #define ASX_STEM_ROWS 1
 #define ASX_SLOT_PCM16 0
 #define ASX_SLOT_FLOAT32 1
+#define ASX_SLOT_FILE_PCM16 16
+#define ASX_SLOT_FILE_PCM24 24
+#define ASX_SLOT_FILE_PCM32 32
+#define ASX_SLOT_FILE_FLOAT 0x120
 int asx_ensemble_slot_dev(asx_engine *e, const float *stem_dev, int64_t n_samples, int32_t layout, float max_peak, float min_peak,
                           int32_t has_min, int32_t mode, float *stack_dev, int32_t k, int64_t n_max, float *peak_after, void *stream);
 
@@ -771,7 +783,14 @@ int asx_ensemble_slot_dev(asx_engine *e, const float *stem_dev, int64_t n_sample
  *   weights    [n_weights] or NULL, for avg_* only: a job with live == n_weights gives weights[i] to its i-th live contributor,
  *              any other job uses equal weights -- what Ensembler.ensemble does with a weights list (ensembler.py:32-44)
  * Every argument of every job is checked before anything is enqueued; the message names the job.  n_jobs == 0 does nothing.
- * At most ASX_ENS_MAX_JOBS jobs per call.  Additive to ABI 7. */
+ * At most ASX_ENS_MAX_JOBS jobs per call.  Additive to ABI 7.
+ *
+ * asx_ensemble_batch_modes_dev: the same call with the slot mode a property of each contributor -- the members of one ensemble can
+ * write the same file's stems in different formats (one with soundfile beside one without: PCM_24 beside pcm16; a FLOAT input that
+ * one member writes as FLOAT and another as PCM_32).  modes[j * ASX_ENS_MAX_K + c] is the ASX_SLOT_* mode of contributor c of job j
+ * (entries from k on are not read); peak_after[c] and the silent_below rule follow that contributor's own mode.  An unknown mode
+ * is refused before anything is enqueued, naming the job and the contributor.  asx_ensemble_batch_dev is this call with every
+ * mode equal to `mode`.  Additive within ABI 8. */
 #define ASX_ENS_MAX_K 8
 #define ASX_ENS_MAX_JOBS 8191
 typedef struct asx_ens_job {
@@ -787,6 +806,8 @@ typedef struct asx_ens_job {
 } asx_ens_job;
 int asx_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int32_t n_jobs, int32_t algorithm, const double *weights, int32_t n_weights,
                            int32_t mode, float max_peak, float min_peak, int32_t has_min, double silent_below, void *stream);
+int asx_ensemble_batch_modes_dev(asx_engine *e, asx_ens_job *jobs, int32_t n_jobs, const int32_t *modes, int32_t algorithm, const double *weights,
+                                 int32_t n_weights, float max_peak, float min_peak, int32_t has_min, double silent_below, void *stream);
 
 /* asx_invert_stem with every array in HBM: spec_utils.invert_stem(mix, stem * stem_scale).
  *   mix_dev      planar [2, n_samples], float32, only read

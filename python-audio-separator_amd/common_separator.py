@@ -760,6 +760,7 @@ class CommonSeparator:
             self._write_rate = None
 
     _write_rate = None       # the rate of the stem write_audio is writing, when it is not ``sample_rate``
+    _output_rate_override = None   # (file rate, file frames) for the write_audio call in progress: see _output_rate_target
 
     def _container_rate(self) -> int:
         return self._write_rate or self.sample_rate
@@ -767,10 +768,12 @@ class CommonSeparator:
     def _output_rate_target(self):
         """(file rate, file frames) when ``asx_output_rate`` = "input" has this file's stems converted; None when they are written as
         they are: the knob is off, the file is at the model's rate, or -- with one warning per file -- its rate is unknown or the
-        converter refuses the pair."""
-        if getattr(self, "asx_output_rate", "model") != "input" or self.engine is None or not self.sample_rate:
+        converter refuses the pair.  ``_output_rate_override`` = (rate, frames), set around one ``write_audio`` call by a caller that writes
+        through this plugin (EnsembleSeparator's ``output_rate`` = "input"), stands for the knob and the file's header for that call."""
+        override = self._output_rate_override
+        if (override is None and getattr(self, "asx_output_rate", "model") != "input") or self.engine is None or not self.sample_rate:
             return None
-        rate, frames = self._file_rate, self._file_frames
+        rate, frames = override if override is not None else (self._file_rate, self._file_frames)
         if rate == self.sample_rate:
             return None
         why = None
@@ -785,7 +788,8 @@ class CommonSeparator:
             return rate, frames
         if not self._out_rate_warned:
             self._out_rate_warned = True
-            self.logger.warning(f"{self.audio_file_path}: asx_output_rate='input', but {why}: the stems are written at {self.sample_rate} Hz")
+            knob = "asx_output_rate='input'" if override is None else "output_rate='input'"
+            self.logger.warning(f"{self.audio_file_path}: {knob}, but {why}: the stems are written at {self.sample_rate} Hz")
         return None
 
     def _soundfile_on_device(self, stem_path: str) -> bool:

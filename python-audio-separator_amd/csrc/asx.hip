@@ -3209,7 +3209,8 @@ int asx_ensemble_dev(asx_engine *e, const float *waves_dev, int32_t K, int64_t N
 }
 
 // One member stem -> slot k of the [K, 2, n_max] stack asx_ensemble_dev reads, through the member's file round trip
-// (write_audio's normalise + int16, librosa.load's / 32768, the Ensembler's zero padding): ens_slot_kernel.
+// (write_audio's normalise + int16, librosa.load's / 32768, the Ensembler's zero padding; or the soundfile writer's file of the
+// mode's sample format and its decode): ens_slot_kernel.
 int asx_ensemble_slot_dev(asx_engine *e, const float *stem_dev, int64_t n, int32_t layout, float max_peak, float min_peak,
                           int32_t has_min, int32_t mode, float *stack_dev, int32_t k, int64_t n_max, float *peak_after, void *stream) {
   REQUIRE(e && stack_dev && (stem_dev || n == 0), "asx_ensemble_slot_dev: bad argument");
@@ -3217,7 +3218,11 @@ int asx_ensemble_slot_dev(asx_engine *e, const float *stem_dev, int64_t n, int32
           "asx_ensemble_slot_dev: need 0 <= n <= n_max, 1 <= n_max <= 2^38 and k >= 0 (n %lld, n_max %lld, k %d)",
           (long long)n, (long long)n_max, (int)k);
   REQUIRE(layout == ASX_STEM_PLANAR || layout == ASX_STEM_ROWS, "asx_ensemble_slot_dev: layout %d (0 planar [2, n], 1 rows [n, 2])", (int)layout);
-  REQUIRE(mode == ASX_SLOT_PCM16 || mode == ASX_SLOT_FLOAT32, "asx_ensemble_slot_dev: mode %d (0 pcm16 round trip, 1 float32 copy)", (int)mode);
+  static_assert(ASX_SLOT_PCM16 == ENS_SLOT_PCM16 && ASX_SLOT_FLOAT32 == ENS_SLOT_FLOAT32 && ASX_SLOT_FILE_PCM16 == ENS_SLOT_FILE_PCM16 &&
+                    ASX_SLOT_FILE_PCM24 == ENS_SLOT_FILE_PCM24 && ASX_SLOT_FILE_PCM32 == ENS_SLOT_FILE_PCM32 && ASX_SLOT_FILE_FLOAT == ENS_SLOT_FILE_FLOAT &&
+                    ASX_SLOT_FILE_PCM16 == PCMENC_S16 && ASX_SLOT_FILE_PCM24 == PCMENC_S24 && ASX_SLOT_FILE_PCM32 == PCMENC_S32 &&
+                    ASX_SLOT_FILE_FLOAT == PCMENC_F32, "asx.h, the slot kernel and the PCM encoder disagree");
+  REQUIRE(ens_slot_mode_known(mode), "asx_ensemble_slot_dev: mode %d (" ENS_SLOT_MODE_TEXT ")", (int)mode);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   HIPCHK(hipSetDevice(e->device));
   CHK(e->d_peak.ensure(256));
@@ -3231,18 +3236,13 @@ int asx_ensemble_slot_dev(asx_engine *e, const float *stem_dev, int64_t n, int32
   float *slot = stack_dev + (size_t)k * 2 * (size_t)n_max;
   CHK(timed(e, ASX_PROF_MISC, 0.0, 4.0 * (n2 + 2.0 * n_max), s, [&]() {
     hipLaunchKernelGGL(ens_slot_kernel, dim3((unsigned)((n_max + 255) / 256)), dim3(256), 0, s, stem_dev, n, (int)(layout == ASX_STEM_ROWS), pk,
-                       max_peak, min_peak, (int)has_min, (int)(mode == ASX_SLOT_PCM16), slot, n_max);
+                       max_peak, min_peak, (int)has_min, (int)mode, slot, n_max);
   }));
   if (peak_after) {
     float maxv = 0.f;
     HIPCHK(hipMemcpyAsync(&maxv, pk, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    float scale = 1.0f;
-    if (mode == ASX_SLOT_PCM16) {
-      if (maxv > max_peak) scale = max_peak / maxv;
-      else if (has_min && maxv < min_peak) scale = min_peak / maxv;
-    }
-    *peak_after = maxv * scale;
+    *peak_after = ens_peak_after(maxv, mode, max_peak, min_peak, has_min);
   }
   return ASX_OK;
 }
@@ -3252,8 +3252,19 @@ int asx_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int32_t n_jobs, int
   REQUIRE(e, "asx_ensemble_batch_dev: null engine");
   static_assert(ASX_ENS_MAX_K == ENS_MAX_K && ASX_ENS_MAX_K == ENS_PLAN_MAX_K && ASX_ENS_MAX_JOBS == ENS_PLAN_MAX_JOBS, "asx.h and the plan disagree");
   HIPCHK(hipSetDevice(e->device));
-  return ens_ensemble_batch_dev(e, jobs, n_jobs, algorithm, weights, n_weights, mode, max_peak, min_peak, has_min, silent_below,
-                                reinterpret_cast<hipStream_t>(stream));
+  return ens_ensemble_batch_dev(e, "asx_ensemble_batch_dev", jobs, n_jobs, nullptr, algorithm, weights, n_weights, mode, max_peak, min_peak, has_min,
+                                silent_below, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the same with the slot mode of every contributor: modes [n_jobs][ASX_ENS_MAX_K]
+int asx_ensemble_batch_modes_dev(asx_engine *e, asx_ens_job *jobs, int32_t n_jobs, const int32_t *modes, int32_t algorithm, const double *weights,
+                                 int32_t n_weights, float max_peak, float min_peak, int32_t has_min, double silent_below, void *stream) {
+  REQUIRE(e, "asx_ensemble_batch_modes_dev: null engine");
+  REQUIRE(modes || n_jobs <= 0, "asx_ensemble_batch_modes_dev: null modes");
+  HIPCHK(hipSetDevice(e->device));
+  static const int32_t none[1] = {0};
+  return ens_ensemble_batch_dev(e, "asx_ensemble_batch_modes_dev", jobs, n_jobs, modes ? modes : none, algorithm, weights, n_weights, ASX_SLOT_PCM16,
+                                max_peak, min_peak, has_min, silent_below, reinterpret_cast<hipStream_t>(stream));
 }
 
 int asx_invert_stem(asx_engine *e, const float *mix_host, const float *stem_host, int64_t N, float *out_host, int64_t *n_out) {

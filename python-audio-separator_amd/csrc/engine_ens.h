@@ -260,18 +260,22 @@ static int ens_invert_stem_batch_dev(asx_engine *e, asx_invert_song *songs, int 
 // been checked.
 static float ens_peak_after(float maxv, int mode, float max_peak, float min_peak, int has_min) {   // asx_ensemble_slot_dev's report
   float scale = 1.0f;
-  if (mode == ASX_SLOT_PCM16) {
+  if (mode != ASX_SLOT_FLOAT32) {   // every round trip normalises; asx_pcm_encode_dev reports the same product
     if (maxv > max_peak) scale = max_peak / maxv;
     else if (has_min && maxv < min_peak) scale = min_peak / maxv;
   }
   return maxv * scale;
 }
 
-static int ens_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int n_jobs, int alg, const double *weights, int n_weights, int mode,
-                                  float max_peak, float min_peak, int has_min, double silent_below, hipStream_t s) {
-  const char *fn = "asx_ensemble_batch_dev";
+#define ENS_SLOT_MODE_TEXT "0 pcm16 round trip, 1 float32 copy, 16 / 24 / 32 / 0x120 the soundfile writer's PCM_16 / PCM_24 / PCM_32 / FLOAT file"
+
+// modes: [n_jobs][ENS_MAX_K], the slot mode of every contributor (asx_ensemble_batch_modes_dev), or NULL: `mode` for all of them
+// (asx_ensemble_batch_dev).  `fn` names the entry point in the messages.
+static int ens_ensemble_batch_dev(asx_engine *e, const char *fn, asx_ens_job *jobs, int n_jobs, const int32_t *modes, int alg, const double *weights,
+                                  int n_weights, int mode, float max_peak, float min_peak, int has_min, double silent_below, hipStream_t s) {
   REQUIRE(n_jobs >= 0 && (jobs || n_jobs == 0), "%s: bad argument (jobs %p, n_jobs %d)", fn, (void *)jobs, n_jobs);
-  REQUIRE(mode == ASX_SLOT_PCM16 || mode == ASX_SLOT_FLOAT32, "%s: mode %d (0 pcm16 round trip, 1 float32 copy)", fn, mode);
+  REQUIRE(modes || ens_slot_mode_known(mode), "%s: mode %d (" ENS_SLOT_MODE_TEXT ")", fn, mode);
+  auto mode_of = [&](int j, int c) { return modes ? (int)modes[(size_t)j * ENS_MAX_K + c] : mode; };
   REQUIRE(n_weights >= 0 && n_weights <= ENS_MAX_K && (weights || n_weights == 0), "%s: %d weights (0 .. %d)", fn, n_weights, ENS_MAX_K);
   std::vector<EnsPlanJobIn> in((size_t)n_jobs);
   int total_src = 0;
@@ -289,6 +293,7 @@ static int ens_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int n_jobs, 
       REQUIRE(jb.stem_dev[c] || jb.n_samples[c] == 0, "%s: job %d: contributor %d has a null stem with n = %lld", fn, j, c, (long long)jb.n_samples[c]);
       REQUIRE(jb.layout[c] == ASX_STEM_PLANAR || jb.layout[c] == ASX_STEM_ROWS, "%s: job %d: contributor %d has layout %d (0 planar [2, n], 1 rows [n, 2])",
               fn, j, c, (int)jb.layout[c]);
+      REQUIRE(ens_slot_mode_known(mode_of(j, c)), "%s: job %d: contributor %d has mode %d (" ENS_SLOT_MODE_TEXT ")", fn, j, c, mode_of(j, c));
       n_job = std::max<int64_t>(n_job, jb.n_samples[c]);
     }
     REQUIRE(jb.out_dev, "%s: job %d: null output", fn, j);
@@ -315,7 +320,7 @@ static int ens_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int n_jobs, 
   std::vector<int> first_src((size_t)n_jobs);
   for (int j = 0, q = 0; j < n_jobs; ++j) {
     first_src[j] = q;
-    for (int k = 0; k < jobs[j].k; ++k, ++q) h_src[q] = EnsPoolSrc{jobs[j].stem_dev[k], jobs[j].n_samples[k], (int32_t)(jobs[j].layout[k] == ASX_STEM_ROWS), q};
+    for (int k = 0; k < jobs[j].k; ++k, ++q) h_src[q] = EnsPoolSrc{jobs[j].stem_dev[k], jobs[j].n_samples[k], (int32_t)(jobs[j].layout[k] == ASX_STEM_ROWS), q, (int32_t)mode_of(j, k), 0};
   }
   unsigned int *d_peak = reinterpret_cast<unsigned int *>(c.ppeaks.p);
   HIPCHK(hipMemcpyAsync(c.psrcs.p, h_src, src_bytes, hipMemcpyHostToDevice, s));
@@ -334,7 +339,7 @@ static int ens_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int n_jobs, 
     for (int k = 0; k < jobs[j].k; ++k) {
       float maxv;
       memcpy(&maxv, &h_peak[first_src[j] + k], 4);
-      in[j].peak_after[k] = jobs[j].peak_after[k] = ens_peak_after(maxv, mode, max_peak, min_peak, has_min);
+      in[j].peak_after[k] = jobs[j].peak_after[k] = ens_peak_after(maxv, mode_of(j, k), max_peak, min_peak, has_min);
     }
   EnsPoolPlan pp;
   ens_pool_build(in.data(), n_jobs, alg, silent_below, pp);
@@ -376,7 +381,7 @@ static int ens_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int n_jobs, 
 
   // ---- one launch per stage ---------------------------------------------------------------------------------------------------
   const EnsPoolJob *dj = reinterpret_cast<const EnsPoolJob *>(c.pjobs.p);
-  const EnsSlotEdge ed{d_peak, max_peak, min_peak, has_min, (int32_t)(mode == ASX_SLOT_PCM16)};
+  const EnsSlotEdge ed{d_peak, max_peak, min_peak, has_min, 0};
   if (pp.picks)
     CHK(timed(e, ASX_PROF_MISC, 0.0, 0.0, s, [&]() {
       hipLaunchKernelGGL(ens_pool_abssum_kernel, dim3((unsigned)(ENS_ABS_BLOCKS * n_jobs), 2 * ENS_MAX_K), dim3(256), 0, s, dj, ed,

@@ -114,9 +114,27 @@ __global__ __launch_bounds__(256) void ens_take_kernel(const float *__restrict__
 // (int16 / 32768 as float32), and Ensembler.ensemble zero-pads it to the longest wave (ensembler.py:29-30).  One pass, no
 // int16 array: stem = planar [2, n] or rows [n, 2] -> slot [2, n_max] of the stack ens_*_kernel read.  The quantiser is
 // pcm16_kernel's, operation for operation (float32, one rounding each, C truncation), so slot * 32768 IS the int16 that
-// kernel writes; int16 -> float and the division by 2^15 are exact.  quantise == 0: plain copy (+ transpose) and pad.
+// kernel writes; int16 -> float and the division by 2^15 are exact.  ENS_SLOT_FLOAT32: plain copy (+ transpose) and pad.
+// The file modes are the same edge for a member that writes with soundfile (write_audio_soundfile, common_separator.py:399-461):
+// the slot holds what pcm_decode_kernel reads out of the bytes pcm_encode_kernel writes for the stem -- the same normalisation,
+// then clip(rint((double)x * (2^(b-1) - 1))) of pcmenc_quant and the int / 2^(b-1) of the decoder (PCM_32 through double, as
+// there), or the normalised float itself.  The mode numbers of the file modes are the sample format codes of those kernels.
 // Every element of the slot is written: the stack needs no clearing.
-__device__ __forceinline__ float ens_slot_quantise(float x, float maxv, float max_peak, float min_peak, int has_min) {
+enum { ENS_SLOT_PCM16 = 0, ENS_SLOT_FLOAT32 = 1, ENS_SLOT_FILE_PCM16 = 16, ENS_SLOT_FILE_PCM24 = 24, ENS_SLOT_FILE_PCM32 = 32,
+       ENS_SLOT_FILE_FLOAT = 0x120 };
+static inline bool ens_slot_mode_known(int mode) {
+  return mode == ENS_SLOT_PCM16 || mode == ENS_SLOT_FLOAT32 || mode == ENS_SLOT_FILE_PCM16 || mode == ENS_SLOT_FILE_PCM24 ||
+         mode == ENS_SLOT_FILE_PCM32 || mode == ENS_SLOT_FILE_FLOAT;
+}
+// the integer sample of BITS bits audio_io.write_wav (and pcm_encode_kernel) stores for the normalised x: float64 product, ties to even
+template <int BITS>
+__device__ __forceinline__ int ens_slot_file_int(float x) {
+  constexpr double full = (double)((1ll << (BITS - 1)) - 1);
+  return (int)fmin(fmax(rint((double)x * full), -full - 1.0), full);
+}
+// mode: any but ENS_SLOT_FLOAT32.  In every mode the last operation is a multiplication (by a power of two after an integer, by the
+// normalisation's scale for ENS_SLOT_FILE_FLOAT) formed with contraction off, or no operation at all.
+__device__ __forceinline__ float ens_slot_quantise(float x, float maxv, float max_peak, float min_peak, int has_min, int mode) {
 #pragma clang fp contract(off)
   float scale = 1.0f;
   bool scaled = false;
@@ -128,24 +146,30 @@ __device__ __forceinline__ float ens_slot_quantise(float x, float maxv, float ma
     scaled = true;
   }
   if (scaled) x = x * scale;
-  const float q = x * 32767.0f;
-  return (float)(short)(int)q * (1.0f / 32768.0f);
+  if (mode == ENS_SLOT_PCM16) {
+    const float q = x * 32767.0f;
+    return (float)(short)(int)q * (1.0f / 32768.0f);
+  }
+  if (mode == ENS_SLOT_FILE_PCM16) return (float)(short)ens_slot_file_int<16>(x) * (1.0f / 32768.0f);
+  if (mode == ENS_SLOT_FILE_PCM24) return (float)ens_slot_file_int<24>(x) * (1.0f / 8388608.0f);
+  if (mode == ENS_SLOT_FILE_PCM32) return (float)((double)ens_slot_file_int<32>(x) * (1.0 / 2147483648.0));
+  return x;   // ENS_SLOT_FILE_FLOAT
 }
 // sample i of channel ch of a stem of n samples as its slot holds it (zero from n on)
 __device__ __forceinline__ float ens_slot_value(const float *__restrict__ stem, int64_t n, int rows, int ch, int64_t i, float maxv,
-                                                float max_peak, float min_peak, int has_min, int quantise) {
+                                                float max_peak, float min_peak, int has_min, int mode) {
   if (i >= n) return 0.f;
   const float x = rows ? stem[2 * i + ch] : stem[(int64_t)ch * n + i];
-  return quantise ? ens_slot_quantise(x, maxv, max_peak, min_peak, has_min) : x;
+  return mode != ENS_SLOT_FLOAT32 ? ens_slot_quantise(x, maxv, max_peak, min_peak, has_min, mode) : x;
 }
 __global__ __launch_bounds__(256) void ens_slot_kernel(const float *__restrict__ stem, int64_t n, int rows,
                                                        const unsigned int *peak_bits, float max_peak, float min_peak, int has_min,
-                                                       int quantise, float *__restrict__ slot, int64_t n_max) {
+                                                       int mode, float *__restrict__ slot, int64_t n_max) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_max) return;
-  const float maxv = (quantise && i < n) ? __uint_as_float(*peak_bits) : 0.f;
-  slot[i] = ens_slot_value(stem, n, rows, 0, i, maxv, max_peak, min_peak, has_min, quantise);
-  slot[n_max + i] = ens_slot_value(stem, n, rows, 1, i, maxv, max_peak, min_peak, has_min, quantise);
+  const float maxv = (mode != ENS_SLOT_FLOAT32 && i < n) ? __uint_as_float(*peak_bits) : 0.f;
+  slot[i] = ens_slot_value(stem, n, rows, 0, i, maxv, max_peak, min_peak, has_min, mode);
+  slot[n_max + i] = ens_slot_value(stem, n, rows, 1, i, maxv, max_peak, min_peak, has_min, mode);
 }
 
 // librosa.stft frame t of one channel of n samples (centre, zero padding) -> X[0 .. nh] in LDS.  ld(q): sample q, 0 <= q < n.
@@ -316,13 +340,16 @@ __global__ __launch_bounds__(256) void ens_invert_kernel(const float *__restrict
 // functions above -- the ones the single-job kernels run.  No [K, 2, n_max] stack exists: a contributor's sample is read from
 // the member's stem and goes through ens_slot_value, the function ens_slot_kernel stores the stack with, so what a combine
 // reads is the float that kernel would have stored and a load would have returned (a float32 store and load change no bit, and
-// no arithmetic of the combine can be contracted with the quantiser's: its last operation is a multiplication whose result is
-// only ever multiplied, converted or compared next).
+// no arithmetic of the combine can be contracted with the quantiser's: its last operation is a multiplication formed with
+// contraction off -- exact, by a power of two, in the integer modes -- whose result is a value like a loaded one to the combine).
+// The slot mode belongs to the contributor: the members of one ensemble can write the same file's stems in different formats.
 struct EnsPoolSrc {
   const float *stem;   // planar [2, n] or rows [n, 2]
   int64_t n;
   int32_t rows;
   int32_t peak;        // its word of the peak array
+  int32_t mode;        // ENS_SLOT_*: its member's file round trip
+  int32_t pad_;
 };
 struct EnsPoolJob {
   EnsPoolSrc src[ENS_MAX_K];   // the contributors that take part, in order
@@ -336,12 +363,12 @@ struct EnsPoolJob {
 struct EnsSlotEdge {           // the member -> Ensembler edge of the call
   const unsigned int *peaks;   // max |stem| of every contributor, float bits
   float max_peak, min_peak;
-  int32_t has_min, quantise;
+  int32_t has_min, pad_;
 };
 
 __device__ __forceinline__ float ens_pool_load(const EnsPoolSrc &s, const EnsSlotEdge &ed, int ch, int64_t i) {
-  const float maxv = (ed.quantise && i < s.n) ? __uint_as_float(ed.peaks[s.peak]) : 0.f;
-  return ens_slot_value(s.stem, s.n, s.rows, ch, i, maxv, ed.max_peak, ed.min_peak, ed.has_min, ed.quantise);
+  const float maxv = (s.mode != ENS_SLOT_FLOAT32 && i < s.n) ? __uint_as_float(ed.peaks[s.peak]) : 0.f;
+  return ens_slot_value(s.stem, s.n, s.rows, ch, i, maxv, ed.max_peak, ed.min_peak, ed.has_min, s.mode);
 }
 
 // the last job whose first workgroup (or frame) of this stage is <= x

@@ -283,7 +283,7 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_flac_plan_pcm", "asx_flac_encode_pcm", "asx_flac_encode_pcm_dev", "asx_pcm_encode", "asx_pcm_encode_dev",
            "asx_invert_stem_dev", "asx_invert_stem_batch_dev", "asx_op_gconv", "asx_op_dconv", "asx_resample_sinc_batch_dev",
            "asx_resample_rational_stem", "asx_resample_rational_stem_dev", "asx_op_stft", "asx_op_istft", "asx_op_ht_spec",
-           "asx_op_ht_ispec"]
+           "asx_op_ht_ispec", "asx_ensemble_batch_modes_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -489,6 +489,8 @@ def load_library():
     lib.asx_invert_stem_batch_dev.argtypes = [vp, C.POINTER(_InvertSong), i32, C.c_float, vp]
     lib.asx_ensemble_batch_dev.argtypes = [vp, C.POINTER(_EnsJob), i32, i32, C.POINTER(C.c_double), i32, i32, C.c_float, C.c_float, i32,
                                            C.c_double, vp]
+    lib.asx_ensemble_batch_modes_dev.argtypes = [vp, C.POINTER(_EnsJob), i32, C.POINTER(i32), i32, C.POINTER(C.c_double), i32, C.c_float, C.c_float,
+                                                 i32, C.c_double, vp]
     lib.asx_ensemble_slot_dev.argtypes = [vp, vp, i64, i32, C.c_float, C.c_float, i32, i32, vp, i32, i64, _FP, vp]
     lib.asx_pcm16.argtypes = [vp, _FP, i64, C.c_float, C.c_float, i32, C.POINTER(C.c_int16), _FP]
     lib.asx_normalize.argtypes = [vp, _FP, i64, C.c_float, C.c_float, i32, _FP]
@@ -1425,17 +1427,28 @@ class Engine:
         return [float(v) for v in w]
 
     SLOT_LAYOUTS = {"planar": 0, "rows": 1}
-    SLOT_MODES = {"pcm16": 0, "float32": 1}
+    # "pcm16" / "float32": the reference's 16-bit intermediate (pydub's truncating writer) / no round trip; the subtype names: the file a
+    # member writes with soundfile, as asx_pcm_encode_dev writes and asx_pcm_decode_dev reads it ("PCM_16" rounds, "pcm16" truncates)
+    SLOT_MODES = {"pcm16": 0, "float32": 1, "PCM_16": 16, "PCM_24": 24, "PCM_32": 32, "FLOAT": 0x120}
+
+    @classmethod
+    def _slot_mode(cls, mode) -> int:
+        if not isinstance(mode, str) or mode not in cls.SLOT_MODES:
+            raise ValueError(f"unknown slot mode {mode!r} (one of {tuple(cls.SLOT_MODES)})")
+        return cls.SLOT_MODES[mode]
 
     def ensemble_slot_dev(self, stem_ptr: int, n_samples: int, layout: str, max_peak: float, min_peak, stack_ptr: int, k: int,
                           n_max: int, mode: str = "pcm16", stream: int = 0, want_peak: bool = True):
         """asx_ensemble_slot_dev: a device stem (``layout`` "planar" [2, n] or "rows" [n, 2]) -> slot ``k`` of the device stack
         [K, 2, n_max] through the member's file round trip (``mode`` "pcm16": normalise, int16, / 32768 -- bit-exact to
-        pcm16_*_dev followed by librosa.load) or as it is ("float32"); zero padded to ``n_max``.  Returns the peak after
-        normalisation (the raw peak for "float32"; synchronises the stream) or None."""
+        pcm16_*_dev followed by librosa.load), as it is ("float32"), or through the file of that subtype a soundfile writer leaves
+        ("PCM_16", "PCM_24", "PCM_32", "FLOAT": bit-exact to pcm_encode_dev followed by pcm_decode_dev); zero padded to ``n_max``.
+        Returns the peak after normalisation (the raw peak for "float32"; synchronises the stream) or None.  An unknown ``mode``
+        raises ValueError."""
+        mode_code = self._slot_mode(mode)
         pk = C.c_float()
         self._check(self._lib.asx_ensemble_slot_dev(self._h, stem_ptr or None, n_samples, self.SLOT_LAYOUTS[layout], float(max_peak),
-                                                    float(min_peak or 0.0), int(min_peak is not None), self.SLOT_MODES[mode],
+                                                    float(min_peak or 0.0), int(min_peak is not None), mode_code,
                                                     stack_ptr or None, k, n_max, C.byref(pk) if want_peak else None, stream or None))
         return pk.value if want_peak else None
 
@@ -1452,13 +1465,15 @@ class Engine:
         return int(n_out.value)
 
     def ensemble_batch_dev(self, jobs, algorithm, weights, max_peak: float, min_peak, silent_below: float = 1e-6, mode: str = "pcm16",
-                           stream: int = 0):
+                           stream: int = 0, modes=None):
         """asx_ensemble_batch_dev: the ensembles of many (file, stem group) jobs in one call.  ``jobs``: a list of
         ``(contributors, out_ptr, out_capacity)`` with ``contributors`` = [(stem_ptr, n_samples, "planar" | "rows")], 1 .. 8 of them,
         and ``out`` a device buffer of 2 * out_capacity floats, out_capacity >= the longest contributor.  Per job, bit for bit what
         ``ensemble_slot_dev`` per contributor (dropping those whose peak is below ``silent_below`` and padding the rest to the
         longest left) followed by ``ensemble_dev`` gives; a lone contributor left comes out as its slot image.  ``weights`` as
         Ensembler.ensemble treats them: used by a job with exactly that many contributors left, equal weights otherwise.
+        ``mode``: the slot mode of every contributor; ``modes`` (asx_ensemble_batch_modes_dev): per job the list of its contributors'
+        modes instead -- members of one ensemble can write the same file in different formats.  An unknown name raises ValueError.
         Returns per job ``(n_out, live, [peak_after per contributor])``: ``out`` holds planar [2, n_out]; n_out == 0: no result,
         nothing written.  Synchronises the stream once (for the peaks); the combine itself is only enqueued."""
         if isinstance(algorithm, str):
@@ -1466,6 +1481,17 @@ class Engine:
                 raise ValueError(f"Unknown ensemble algorithm: {algorithm}")
             algorithm = self.ENSEMBLE_ALGORITHMS.index(algorithm)
         jobs = list(jobs)
+        mode_code, mode_table = self._slot_mode(mode), None
+        if modes is not None:
+            modes = [list(m) for m in modes]
+            if len(modes) != len(jobs) or any(len(m) != len(list(job[0])) for m, job in zip(modes, jobs)):
+                raise ValueError("modes must hold one mode per contributor of every job")
+            mode_table = (C.c_int32 * (ENS_MAX_K * max(1, len(jobs))))()
+            for j, m in enumerate(modes):
+                for c, name in enumerate(m):
+                    code = self._slot_mode(name)
+                    if c < ENS_MAX_K:
+                        mode_table[j * ENS_MAX_K + c] = code
         w = self.ensemble_weights(weights, len(weights)) if weights is not None and 0 < len(weights) <= ENS_MAX_K else None
         wt = (C.c_double * len(w))(*w) if w is not None else None
         arr = (_EnsJob * max(1, len(jobs)))()
@@ -1475,9 +1501,14 @@ class Engine:
             for c, (ptr, n, layout) in enumerate(contributors[:ENS_MAX_K]):
                 arr[j].stem_dev[c], arr[j].n_samples[c], arr[j].layout[c] = ptr or None, int(n), self.SLOT_LAYOUTS[layout]
             arr[j].out_dev, arr[j].out_capacity = out_ptr or None, int(capacity)
-        self._check(self._lib.asx_ensemble_batch_dev(self._h, arr, len(jobs), int(algorithm), wt, len(w) if w is not None else 0,
-                                                     self.SLOT_MODES[mode], float(max_peak), float(min_peak or 0.0), int(min_peak is not None),
-                                                     float(silent_below), stream or None))
+        if mode_table is not None:
+            self._check(self._lib.asx_ensemble_batch_modes_dev(self._h, arr, len(jobs), mode_table, int(algorithm), wt, len(w) if w is not None else 0,
+                                                               float(max_peak), float(min_peak or 0.0), int(min_peak is not None),
+                                                               float(silent_below), stream or None))
+        else:
+            self._check(self._lib.asx_ensemble_batch_dev(self._h, arr, len(jobs), int(algorithm), wt, len(w) if w is not None else 0,
+                                                         mode_code, float(max_peak), float(min_peak or 0.0), int(min_peak is not None),
+                                                         float(silent_below), stream or None))
         return [(int(arr[j].n_out), int(arr[j].live), [float(arr[j].peak_after[c]) for c in range(min(arr[j].k, ENS_MAX_K))])
                 for j in range(len(jobs))]
 

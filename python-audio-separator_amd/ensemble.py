@@ -11,7 +11,9 @@ directory as a 16-bit file, reading the files back with librosa and combining eq
   ``stems_dev`` leaves its stems in HBM, ``asx_ensemble_slot_dev`` applies what the file round trip does to the samples
   (spec_utils.normalize, ``* 32767 -> int16``, ``/ 32768``, zero padding to the longest contributor) while filling the stack
   ``asx_ensemble_dev`` reads, and the result is registered as a device stem so that ``write_audio`` quantises it there.
-  Outputs are byte-identical to the file path.
+  Outputs are byte-identical to the file path.  ``intermediate="writer"`` gives every contributor the round trip of its own
+  member's writer (the soundfile writer's PCM_16 / PCM_24 / PCM_32 / FLOAT files included), so members with ``use_soundfile`` stay
+  on this path; ``output_rate="input"`` has the last member's writer convert the combined result to the input file's rate.
 
 ``Ensembler`` is the drop-in for the reference class of that name (``plugin.install(ensembler=True)``).
 """
@@ -109,22 +111,39 @@ class EnsembleSeparator:
     ALGORITHMS = ("avg_wave", "median_wave", "min_wave", "max_wave", "avg_fft", "median_fft", "min_fft", "max_fft",
                   "uvr_max_spec", "uvr_min_spec", "ensemble_wav")
 
+    INTERMEDIATES = ("pcm16", "float32", "writer")
+    OUTPUT_RATES = ("model", "input")
+    # the sample formats a soundfile member's intermediate file can carry on the device path (Engine.SLOT_MODES, asx_pcm_encode_dev)
+    _WRITER_SUBTYPES = ("PCM_16", "PCM_24", "PCM_32", "FLOAT")
+
     def __init__(self, members, algorithm="avg_wave", weights=None, preset=None, model_filenames=None, intermediate="pcm16",
-                 via_files=False, logger=None, pool_files=None):
+                 via_files=False, logger=None, pool_files=None, output_rate="model"):
         """``members``: loaded plugin instances (MDXSeparator / MDXCSeparator / DemucsSeparator / VRSeparator, any mix); they
         and their engines stay resident across files.  ``algorithm`` / ``weights``: Ensembler's.  ``preset`` only names the
         outputs (``..._preset_<preset>``); ``model_filenames`` (default: each member's model file basename) name them
-        otherwise.  ``intermediate``: "pcm16" (what the reference's 16-bit intermediate files carry, the default) or
-        "float32" (unquantised stems between members and combine; device path only).  ``via_files``: the literal flow.
-        ``pool_files``: files per pooled run of ``separate_many`` (None: as many as the memory rule allows)."""
+        otherwise.  ``intermediate``: "pcm16" (what the reference's 16-bit intermediate files carry, the default),
+        "float32" (unquantised stems between members and combine; device path only) or "writer" (every contributor's stem takes
+        the round trip its OWN member's writer and audio_io.load give it for this file: pcm16 for a member without
+        ``use_soundfile``, the file's own PCM_16 / PCM_24 / PCM_32 / FLOAT for one with it -- so soundfile members stay on the
+        device path).  ``via_files``: the literal flow.  ``pool_files``: files per pooled run of ``separate_many`` (None: as many
+        as the memory rule allows).  ``output_rate``: "model" (the default) or "input": the combined result -- and only it; members,
+        intermediates and the combine stay at the model's rate -- is written at the input file's sample rate and frame count,
+        converted inside the last member's ``write_audio`` as ``asx_output_rate`` = "input" converts a single plugin's stems."""
         self.members = list(members)
         if not self.members:
             raise ValueError("an ensemble needs at least one member")
         if algorithm not in self.ALGORITHMS:
             raise ValueError(f"Unknown ensemble algorithm: {algorithm}")
-        if intermediate not in ("pcm16", "float32"):
-            raise ValueError(f"intermediate must be 'pcm16' or 'float32', not {intermediate!r}")
-        if intermediate == "float32" and via_files:
+        if intermediate not in self.INTERMEDIATES:
+            raise ValueError(f"intermediate must be 'pcm16', 'float32' or 'writer', not {intermediate!r}")
+        if output_rate not in self.OUTPUT_RATES:
+            raise ValueError(f"output_rate must be one of {self.OUTPUT_RATES}, not {output_rate!r}")
+        if output_rate == "input":
+            for m in self.members:
+                if getattr(m, "_output_rate_refusal", None):
+                    # the knob's own refusal (CommonSeparator._output_rate_mode): a member that cannot line up with the file at its rate
+                    raise ValueError(f"output_rate='input' is not supported with a {type(m).__name__} member: {m._output_rate_refusal}")
+        if intermediate == "float32" and via_files:   # ("writer" with via_files is the literal flow itself)
             raise ValueError("intermediate='float32' is an option of the device path (via_files=False): the file path's "
                              "intermediates are the 16-bit files")
         first = self.members[0]
@@ -138,13 +157,14 @@ class EnsembleSeparator:
             # a file at another rate would reach the members through different converters (or fail in some of them only)
             raise ValueError(f"ensemble members differ in asx_input_resample: {modes}")
         if any(getattr(m, "asx_output_rate", "model") == "input" for m in self.members):
-            # the pooled combine quantises on the device without passing the members' writer, where that conversion lives
-            raise ValueError("asx_output_rate='input' is not supported in an ensemble: the combined stems are quantised on the device "
-                             "without passing write_audio's conversion (a follow-up); leave the members at 'model'")
+            # the intermediates and the combine live at the model's rate: a member at "input" would hand the file path stems at another
+            raise ValueError("asx_output_rate='input' is not supported in an ensemble: the intermediates and the combine stay at the "
+                             "model's rate; leave the members at 'model' and pass output_rate='input' to EnsembleSeparator, which "
+                             "converts the combined result")
         if model_filenames is not None and len(model_filenames) != len(self.members):
             raise ValueError(f"{len(model_filenames)} model file names for {len(self.members)} members")
         self.algorithm, self.weights, self.preset = algorithm, weights, preset
-        self.intermediate, self.via_files = intermediate, bool(via_files)
+        self.intermediate, self.via_files, self.output_rate = intermediate, bool(via_files), output_rate
         self.model_filenames = list(model_filenames) if model_filenames is not None else [
             os.path.basename(m.model_path) if m.model_path else str(m.model_name) for m in self.members]
         self.logger = logger or first.logger or logging.getLogger("audio_separator_amd")
@@ -163,22 +183,64 @@ class EnsembleSeparator:
         """The ensemble group of each stem ``member`` produced for the current file, from the file names it gives them."""
         return canonical_stem_names([raw_stem_name(member.get_stem_output_path(n, None)) for n in stem_names])
 
-    def _write(self, path, stem_name, source, custom_output_names):
-        """separator.py:1350-1381: name the result, let the last member write it; ``source`` is [N, 2]."""
+    def _write(self, path, stem_name, source, custom_output_names, file_rate=None):
+        """separator.py:1350-1381: name the result, let the last member write it; ``source`` is [N, 2].  ``file_rate``: what
+        ``_file_rate_of`` returned for this file -- under ``output_rate`` = "input" the writer converts the result to it, for this
+        call only (``CommonSeparator._output_rate_override``); its own ``asx_output_rate`` is not touched."""
         writer = self.members[-1]
         base_name = os.path.splitext(os.path.basename(path))[0]
         name = ensemble_output_name(base_name, stem_name, custom_output_names, self.preset, self.model_filenames)
         output_path = f"{name}.{self.output_format.lower()}"
         writer.audio_file_path = path
         writer.output_dir = self.output_dir
-        writer.write_audio(output_path, source)
+        writer._output_rate_override = file_rate
+        try:
+            writer.write_audio(output_path, source)
+        finally:
+            writer._output_rate_override = None
         return os.path.join(self.output_dir, output_path) if self.output_dir else output_path
+
+    def _file_rate_of(self, member, path):
+        """Under ``output_rate`` = "input": (sample rate, frames) of the file ``member`` has just loaded -- what its decoder recorded,
+        or the file's own header where it recorded nothing; (None, None) when neither is known (the writer then warns once and
+        writes at the model's rate).  None under "model": no override."""
+        if self.output_rate != "input":
+            return None
+        rate, frames = getattr(member, "_file_rate", None), getattr(member, "_file_frames", None)
+        if rate and frames:
+            return rate, frames
+        try:
+            info = audio_io.wav_info(path)
+            return info["samplerate"], info["frames"]
+        except Exception:
+            try:
+                info = audio_io.flac_stream(path)
+                return (info["samplerate"], info["total_samples"]) if info["total_samples"] > 0 else (None, None)
+            except Exception:
+                return None, None
+
+    def _slot_mode(self, member):
+        """(slot mode, None) of the stems ``member`` produced for the file it has just loaded -- ``Engine.SLOT_MODES``' name of the round
+        trip its writer plus audio_io.load would give them -- or (None, why) when only its real intermediate file tells."""
+        if self.intermediate != "writer":
+            return self.intermediate, None
+        if not member.use_soundfile:
+            return "pcm16", None                    # write_audio_pydub: the reference's 16-bit samples
+        subtype = member._output_subtype()
+        fmt = str(member.output_format).lower()
+        if subtype not in self._WRITER_SUBTYPES:
+            return None, f"writes {subtype} intermediates, which have no device round trip"
+        if fmt == "flac" and subtype in ("PCM_32", "FLOAT"):
+            return None, f"writes no intermediate at all: FLAC holds no {subtype} samples"
+        if not member._soundfile_on_device(f"stem.{fmt}"):
+            return None, "writes its intermediates with soundfile on the host"
+        return subtype, None
 
     def _device_path_refusal(self):
         """Why an input cannot take the device path, or None."""
         if self.via_files:
             return "via_files=True"
-        if any(m.use_soundfile for m in self.members):
+        if self.intermediate != "writer" and any(m.use_soundfile for m in self.members):
             return "a member writes with soundfile (float intermediates, not the 16-bit round trip)"
         if str(self.output_format).lower() not in _LOSSLESS_16:
             return f"output_format {self.output_format} is not one of {_LOSSLESS_16} (the intermediates would not be lossless 16-bit)"
@@ -218,6 +280,7 @@ class EnsembleSeparator:
                 try:
                     # no custom names for the intermediates: their default names carry the stem labels (separator.py:1282-1286)
                     model_stems = member.separate(path, None)
+                    file_rate = self._file_rate_of(member, path)          # (the last member's is the writer's)
                     member.clear_gpu_cache()
                     member.clear_file_specific_paths()
                 finally:
@@ -249,7 +312,7 @@ class EnsembleSeparator:
                 ensembled = engine.ensemble(waveforms, self.algorithm, self.weights)
                 if original_channels == 1 and ensembled.shape[0] > 1:
                     ensembled = ensembled[:1, :]
-                outputs.append(self._write(path, stem_name, ensembled.T, custom_output_names))
+                outputs.append(self._write(path, stem_name, ensembled.T, custom_output_names, file_rate))
             return outputs
         finally:
             shutil.rmtree(temp_dir, ignore_errors=True)
@@ -267,11 +330,16 @@ class EnsembleSeparator:
                 member.clear_file_specific_paths()
                 return None
             names = self._group_names(member, [name for name, _, _ in stems])
+            mode, why = self._slot_mode(member)
+            file_rate = self._file_rate_of(member, path)                  # (the last member's is the writer's)
             member.clear_file_specific_paths()
+            if mode is None:
+                self.logger.info(f"{path}: ensemble through intermediate files (member {index}, {member.model_name}, {why})")
+                return None
             for (_, tensor, layout), group in zip(stems, names):
-                groups.setdefault(group, []).append((index, tensor, layout))
+                groups.setdefault(group, []).append((index, tensor, layout, mode))
         engine = writer.engine
-        if any(t.device.index != engine.device for contributors in groups.values() for _, t, _ in contributors):
+        if any(t.device.index != engine.device for contributors in groups.values() for _, t, _, _ in contributors):
             self.logger.info(f"{path}: ensemble through intermediate files (members sit on different devices)")
             return None
         thr, amp = writer.normalization_threshold, writer.amplification_threshold
@@ -282,19 +350,19 @@ class EnsembleSeparator:
             stack = None
             while live:
                 # Ensembler.ensemble pads to the longest wave it is GIVEN: a silent stem (no file in the reference) counts for neither
-                n_max = max(t.shape[1] if layout == "planar" else t.shape[0] for _, t, layout in live)
+                n_max = max(t.shape[1] if layout == "planar" else t.shape[0] for _, t, layout, _ in live)
                 stack = torch.empty((len(live), 2, n_max), dtype=torch.float32, device=live[0][1].device)
                 peaks = []
-                for k, (_, t, layout) in enumerate(live):
+                for k, (_, t, layout, mode) in enumerate(live):
                     if not t.is_contiguous():
                         t = t.contiguous()
                     n = t.shape[1] if layout == "planar" else t.shape[0]
                     peaks.append(engine.ensemble_slot_dev(t.data_ptr(), n, layout, thr, amp, stack.data_ptr(), k, n_max,
-                                                          mode=self.intermediate, stream=stream))
+                                                          mode=mode, stream=stream))
                 silent = [c for c, p in zip(live, peaks) if p < _SILENT]
                 if not silent:
                     break
-                for index, _, _ in silent:
+                for index, _, _, _ in silent:
                     self.logger.warning(f"{stem_name}: the stem of member {index} ({self.members[index].model_name}) is silent, left out of the ensemble")
                 live = [c for c, p in zip(live, peaks) if not p < _SILENT]
             if not live:
@@ -309,7 +377,7 @@ class EnsembleSeparator:
                 result = out[: 2 * n_out].view(1, 2, n_out)
             _, views = writer._host_planar_stems(result)
             writer._sync()
-            outputs.append(self._write(path, stem_name, views[0], custom_output_names))
+            outputs.append(self._write(path, stem_name, views[0], custom_output_names, file_rate))
         return outputs
 
     # ---- a batch of files: every member pools its files, one pooled combine ----------------------------------------------------
@@ -367,7 +435,9 @@ class EnsembleSeparator:
         * A file some member raised for fails alone: its result is an empty list, the exception is kept in
           ``self.batch_errors[index]`` and logged.
         * ``last_paths_taken[index]`` is "device", "files" or "failed".
-        * What keeps the whole call off the device path (``via_files``, a soundfile writer, a lossy output format, a member without
+        * A file whose stems some soundfile member would write in a format without a device round trip (``intermediate="writer"``:
+          DOUBLE, PCM_U8, ...) goes through the intermediate-file path alone too.
+        * What keeps the whole call off the device path (``via_files``, a soundfile writer unless ``intermediate="writer"``, a lossy output format, a member without
           ``stems_dev_many``) makes it the loop of ``separate`` per path.
         * Memory: the stems of all members for all files of a run are alive at once; ``paths`` is cut into consecutive runs (``_runs``).
         * Members see the files in list order, so the MDXC short-file rule evolves as in the loop.  Demucs members with
@@ -417,13 +487,21 @@ class EnsembleSeparator:
                 self.logger.info(f"{paths[i]}: ensemble through intermediate files (member {index}, {self.members[index].model_name}, needs the host decoder)")
                 via_files.append(pos)
                 continue
-            groups = {}                            # group name -> [(member index, device stem, layout)], first-seen order
+            groups, refused = {}, None             # group name -> [(member index, device stem, layout, slot mode)], first-seen order
             for index, (member, stems) in enumerate(zip(self.members, entries)):
                 member._restore_file(pooled[index][1][pos])
                 names = self._group_names(member, [name for name, _, _ in stems])
+                mode, why = self._slot_mode(member)        # of the state its own pass over this file left
+                if mode is None:
+                    refused = f"member {index}, {member.model_name}, {why}"
+                    break
                 for (_, tensor, layout), group in zip(stems, names):
-                    groups.setdefault(group, []).append((index, tensor if tensor.is_contiguous() else tensor.contiguous(), layout))
-            if any(t.device.index != engine.device for contributors in groups.values() for _, t, _ in contributors):
+                    groups.setdefault(group, []).append((index, tensor if tensor.is_contiguous() else tensor.contiguous(), layout, mode))
+            if refused is not None:
+                self.logger.info(f"{paths[i]}: ensemble through intermediate files ({refused})")
+                via_files.append(pos)
+                continue
+            if any(t.device.index != engine.device for contributors in groups.values() for _, t, _, _ in contributors):
                 self.logger.info(f"{paths[i]}: ensemble through intermediate files (members sit on different devices)")
                 via_files.append(pos)
                 continue
@@ -431,33 +509,37 @@ class EnsembleSeparator:
         for member in self.members:
             member._reset_file_state()
         # one pooled combine for every (file, group)
-        jobs, outs = [], []
+        jobs, outs, modes = [], [], []
         for pos, groups in on_device:
             for stem_name, contributors in groups.items():
-                lengths = [t.shape[1] if layout == "planar" else t.shape[0] for _, t, layout in contributors]
+                lengths = [t.shape[1] if layout == "planar" else t.shape[0] for _, t, layout, _ in contributors]
                 out = self._result_buffer(contributors[0][1], 2 * max(lengths))
                 outs.append(out)
-                jobs.append(([(t.data_ptr(), n, layout) for (_, t, layout), n in zip(contributors, lengths)], out.data_ptr(), max(lengths)))
+                jobs.append(([(t.data_ptr(), n, layout) for (_, t, layout, _), n in zip(contributors, lengths)], out.data_ptr(), max(lengths)))
+                modes.append([mode for _, _, _, mode in contributors])
         stream = writer._stream() if jobs else 0
+        # "writer": the mode is each contributor's own (asx_ensemble_batch_modes_dev); otherwise one mode for the call, as ever
+        how = {"modes": modes} if self.intermediate == "writer" else {"mode": self.intermediate}
         done = engine.ensemble_batch_dev(jobs, self.algorithm, self.weights, writer.normalization_threshold, writer.amplification_threshold,
-                                         silent_below=_SILENT, mode=self.intermediate, stream=stream) if jobs else []
+                                         silent_below=_SILENT, stream=stream, **how) if jobs else []
         with writer._writing():
             j = 0
             for pos, groups in on_device:
                 i = run[pos]
-                writer._restore_file(pooled[-1][1][pos])      # what its own pass over this file left for the writer (bit depth, subtype)
+                writer._restore_file(pooled[-1][1][pos])      # what its own pass over this file left for the writer (bit depth, subtype, rate)
+                file_rate = self._file_rate_of(writer, paths[i])
                 outputs = []
                 for stem_name, contributors in groups.items():
                     (n_out, live, peaks), out = done[j], outs[j]
                     j += 1
-                    for (index, _, _), peak in zip(contributors, peaks):
+                    for (index, _, _, _), peak in zip(contributors, peaks):
                         if peak < _SILENT:
                             self.logger.warning(f"{stem_name}: the stem of member {index} ({self.members[index].model_name}) is silent, left out of the ensemble")
                     if live == 0:
                         continue
                     self.logger.info(f"Ensembling {live} stems for type: {stem_name}")
                     _, views = writer._host_planar_stems(out[: 2 * n_out].view(1, 2, n_out))
-                    outputs.append(self._write(paths[i], stem_name, views[0], custom_output_names))
+                    outputs.append(self._write(paths[i], stem_name, views[0], custom_output_names, file_rate))
                 results[i] = outputs
                 self.last_paths_taken[i] = self.last_path_taken = "device"
         writer._reset_file_state()
