@@ -592,6 +592,35 @@ int asx_resample_rational_stem_dev(asx_engine *e, const float *x_dev, int32_t la
 int asx_resample_rational_stem(asx_engine *e, const float *x_host, int32_t layout, int32_t channels, int64_t n_in,
                                int32_t sr_in, int32_t sr_out, float *y_host, int64_t n_out);   /* host arrays, same kernel */
 
+/* The complement form of the writer-side converter (the plugins' opt-in "asx_complement_rate" = "input"): the complement stem of a file
+ * formed at the FILE's rate, against the file's own mix, inside the converter's pass.  With y[ch][m] exactly what
+ * asx_resample_rational_stem_dev gives for the same x, layout, channels, n_in, rates and n_out (bit for bit), one launch writes
+ *   y                (when y is not NULL), and
+ *   c[ch][m] = fl( fl(mix_scale * mix[ch * mix_stride + m]) - fl(stem_scale * y[ch][m]) ),  0 <= m < n_out,
+ * fl one float32 rounding each, never contracted into an FMA.  Outputs whose tile lies past the input (y = 0) give c = fl(mix_scale * mix).
+ *   mix   planar [channels, mix_stride] at sr_out Hz, mix_stride >= n_out (the decoded file: its frame count)
+ *   c     planar [channels, n_out];  y: planar [channels, n_out] or NULL
+ * mix, y and c must not overlap.  One launch on `stream`, grid (tiles of n_out, channels); only enqueues (but for the first call of a
+ * pair, which builds its table).  Checked before anything is enqueued, ASX_ERR_INVALID + asx_last_error() naming the argument: everything
+ * asx_resample_rational_stem_dev checks (y excepted), a null mix or c, mix_stride < n_out, a scale that is not finite.
+ * Additive within ABI 8. */
+int asx_resample_rational_complement_dev(asx_engine *e, const float *x_dev, int32_t layout, int32_t channels, int64_t n_in,
+                                         int32_t sr_in, int32_t sr_out, const float *mix_dev, int64_t mix_stride,
+                                         float mix_scale, float stem_scale, float *y_dev /* may be NULL */, float *c_dev,
+                                         int64_t n_out, void *stream);
+int asx_resample_rational_complement(asx_engine *e, const float *x_host, int32_t layout, int32_t channels, int64_t n_in,
+                                     int32_t sr_in, int32_t sr_out, const float *mix_host, int64_t mix_stride,
+                                     float mix_scale, float stem_scale, float *y_host /* may be NULL */, float *c_host,
+                                     int64_t n_out);   /* host arrays, same kernel */
+
+/* *scale = the float32 factor asx_normalize_dev(wave_dev, numel, max_peak, min_peak, has_min) would multiply the array by -- max_peak / peak,
+ * min_peak / peak, or 1 where it leaves the array alone (the mix_scale of the entry above for a mix that is about to be normalised, which
+ * is also what asx_separate_dev / asx_separate_batch_dev apply to their mix).  The array is only read; four bytes come back, so the
+ * call waits for `stream`.  ASX_ERR_INVALID + asx_last_error() naming the argument: a null engine, wave or scale, numel < 1, a threshold
+ * that is not finite, and a silent array under a minimum peak (the factor would be infinite).  Additive within ABI 8. */
+int asx_normalize_scale_dev(asx_engine *e, const float *wave_dev, int64_t numel, float max_peak, float min_peak, int32_t has_min,
+                            float *scale, void *stream);
+
 /* BagOfModels on the device (uvr_lib_v5/demucs/apply.py:169-196 + demucs_separator.py:171-189; ABI 4).  Every member of a
  * bag keeps its own engine (weights resident across files); the caller demixes the STANDARDISED mix with each member
  * (flags 0) and combines without a host round trip:

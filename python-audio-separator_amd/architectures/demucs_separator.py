@@ -23,6 +23,8 @@ DEMUCS_6_SOURCE_MAPPER = {CommonSeparator.BASS_STEM: 0, CommonSeparator.DRUM_STE
 
 
 class DemucsSeparator(CommonSeparator):
+    _complement_rate_refusal = "every stem is an output of the model; none of them is formed as the mix minus another stem"
+
     def __init__(self, common_config, arch_config):
         super().__init__(config=common_config)
         self._read_options(arch_config, (("segment_size", "Default"), ("shifts", 2), ("overlap", 0.25), ("segments_enabled", True)))

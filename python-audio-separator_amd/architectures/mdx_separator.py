@@ -26,6 +26,9 @@ class MDXSeparator(CommonSeparator):
         self.dim_t = 2 ** md["mdx_dim_t_set"]
         self.config_yaml = md.get("config_yaml")
         self._keep_configs(common_config, arch_config)
+        if self.asx_complement_rate == "input" and self.invert_using_spec:
+            raise ValueError("asx_complement_rate='input' is not supported with invert_using_spec: the secondary stem is then a spectral "
+                             "inversion, not the difference mix - compensate * primary")
 
         self.load_model()
 
@@ -88,6 +91,10 @@ class MDXSeparator(CommonSeparator):
             self.logger.error(msg)
             raise ValueError(msg)
 
+    def _complement_stem_name(self):
+        """The secondary stem, ``mix - compensate * primary`` -- unless ``invert_using_spec`` makes it a spectral inversion."""
+        return None if self.invert_using_spec else self.secondary_stem_name
+
     def _device_stems(self, mix):
         """The stems of a mix decoded on the device (CUDA tensor [2, N]) with every array in HBM: asx_separate_dev.  Returns
         (primary, secondary), CUDA tensors [N, 2].  ``invert_using_spec``: the steps of MDXDemixer.separate_stems on the same stream --
@@ -120,7 +127,11 @@ class MDXSeparator(CommonSeparator):
         (the condition under which ``_device_decode`` returns None).  Writes nothing.  With ``invert_using_spec`` the secondary stem
         has 1024 * (N // 1024) rows, and is not in the list below 1024 samples."""
         self._begin_file(audio_file_path)
-        mix = self._device_decode(self.audio_file_path)
+        self._stems_only = True                           # (nothing is written: asx_complement_rate has no use for the file's mix)
+        try:
+            mix = self._device_decode(self.audio_file_path)
+        finally:
+            self._stems_only = False
         if mix is None:
             return None
         return self._stems_of(self._device_stems(mix))
@@ -141,9 +152,14 @@ class MDXSeparator(CommonSeparator):
         mirror = (lambda stem: self._host_stem(stem) if stem.shape[0] else self._to_host(stem)) if on_device else self._to_host
         # a primary_source / secondary_source set before separate() is honoured: unlike MDXC and VR, separate() here does not
         # reset the file state first (separate_many does, per file)
+        made = 0
         for which, stem in zip(("primary", "secondary"), stems):
             if not isinstance(getattr(self, f"{which}_source"), np.ndarray):
                 setattr(self, f"{which}_source", mirror(stem))
+                made += 1
+        # asx_complement_rate = "input": the secondary file is written from s * (the file's mix) - compensate * (the converted primary)
+        self._register_complement(self.secondary_source if made == 2 else None, self.primary_source, self.compensate, False,
+                                  model_wanted=self._wanted(self.primary_stem_name))
         if on_device:
             self._sync()                 # the host mirrors are complete before anyone can read primary_source / secondary_source
             self._tick("stems_d2h", t0)
@@ -153,6 +169,7 @@ class MDXSeparator(CommonSeparator):
         """mdx_separator.py:135-203."""
         self._begin_file(audio_file_path)
         dev_mix, host_mix = self._load_mix(self.audio_file_path)
+        self._mix_scale = self._mix_factor(dev_mix, host_mix)      # (before the stem call normalises the mix in place)
         if dev_mix is not None:
             stems = self._device_stems(dev_mix)
         else:
@@ -172,6 +189,7 @@ class MDXSeparator(CommonSeparator):
             return self._dm.separate_stems_many([h for _, h in mixes])
         import torch
         mixes = self._device_mixes(mixes)
+        self._pool_mix_scales = [self._mix_factor(m, None, kept) for m, kept in zip(mixes, self._pool_kept)]
         prim = [torch.empty((m.shape[1], 2), dtype=torch.float32, device=m.device) for m in mixes]
         sec = [torch.empty_like(p) for p in prim]
         self.engine.separate_batch_dev([(m.data_ptr(), p.data_ptr(), s.data_ptr(), m.shape[1]) for m, p, s in zip(mixes, prim, sec)],

@@ -87,6 +87,12 @@ class MDXCSeparator(CommonSeparator):
             self.logger.warning(f"{seconds:.2f} s of audio (< 10 s): switching to the configured segment size "
                                 "(override_model_segment_size), as the reference does for short files")
 
+    def _complement_stem_name(self):
+        """The residual row of a single-target model, ``mix - primary`` (also with ``pitch_shift``: it is taken against the original mix);
+        a model without ``target_instrument`` has none."""
+        training = self.model_data.get("training", {}) or {}
+        return self.secondary_stem_name if training.get("target_instrument") else None
+
     def _stem_plan(self, names):
         """What ``separate`` writes of a demix that produced the stems ``names`` (``[None]``: the one array of a single-target
         model without residual): (kind, [(stem name, key into the demix)]) in the order written.  "single": the primary stem;
@@ -117,6 +123,7 @@ class MDXCSeparator(CommonSeparator):
         t0 = self._now()
         eng, st = dm.engine, self._stream()
         thr, amp = self.normalization_threshold, self.amplification_threshold
+        self._mix_scale = self._mix_factor(mix_d, None)
         eng.normalize_dev(mix_d.data_ptr(), 2 * n, thr, amp, stream=st)
         names, stems_d = dm.demix_dev(mix_d)
         kind, entries = self._stem_plan(names)
@@ -133,7 +140,11 @@ class MDXCSeparator(CommonSeparator):
         residual stem of a single-target model.  None when the file needs the host decoder.  Writes nothing."""
         self._reset_file_state()
         self._begin_file(audio_file_path)
-        got = self._device_stems()
+        self._stems_only = True                           # (nothing is written: asx_complement_rate has no use for the file's mix)
+        try:
+            got = self._device_stems()
+        finally:
+            self._stems_only = False
         return None if got is None else self._stems_of(got)
 
     def _stems_of(self, got):
@@ -151,11 +162,19 @@ class MDXCSeparator(CommonSeparator):
         """``_stem_plan`` -> files; ``fetch(key)`` is the [N, 2] array of one stem, called once per stem.  ``separate`` has reset
         the file state, so ``primary_source`` / ``secondary_source`` are always this file's."""
         files = []
+        if kind != "pair" or self._complement_stem_name() is None:
+            self._note_no_complement(f"no stem of {self.model_name} is a residual against the mix")
+            self._file_mix = None
         if kind == "all":
             for name, key in entries:
                 self._emit_stem(name, fetch(key), custom_output_names, files)
         elif kind == "pair":
             self.primary_source, self.secondary_source = fetch(entries[1][1]), fetch(entries[0][1])
+            if self._complement_stem_name() is not None:
+                # asx_complement_rate = "input": the residual's file is written from s * (the file's mix) - (the converted primary), then
+                # normalised like every stem of this plugin
+                self._register_complement(self.secondary_source, self.primary_source, 1.0, True,
+                                          model_wanted=self._wanted(self.primary_stem_name))
             files = self._emit_pair(custom_output_names)
         elif self._wanted(self.primary_stem_name):        # "single" (mdxc_separator.py:213-225)
             self.primary_source = fetch(entries[0][1])
@@ -178,6 +197,7 @@ class MDXCSeparator(CommonSeparator):
         mix = self.prepare_mix(self.audio_file_path)
         self._short_file_rule(mix.shape[1] / self.sample_rate)
         dm = self._demixer()
+        self._mix_scale = self._mix_factor(None, mix)
         norm = lambda w: dm.engine.normalize(w, self.normalization_threshold, self.amplification_threshold)   # noqa: E731
         source = dm.demix(norm(np.ascontiguousarray(mix, np.float32)))
         kind, entries = self._stem_plan(list(source) if isinstance(source, dict) else [None])
@@ -219,7 +239,9 @@ class MDXCSeparator(CommonSeparator):
         sees the pitched mixes: the chunks are counted from their lengths, and the temporaries of the round trip -- the pitched mix
         [2, n'] and the stems at the pitched rate [rows, 2, n'] of every song of a run -- count against the HBM budget, in chunks
         (``asx_pool_chunks`` counts chunks alone; the result rows [rows + 1, 2, N] are the caller's and are not charged, with or without
-        the option).  tests/test_gpu_mdxc_pitch_dev.py holds the charge against the allocator's peak beside the results."""
+        the option).  tests/test_gpu_mdxc_pitch_dev.py holds the charge against the allocator's peak beside the results.  The file-rate
+        mixes that ``asx_complement_rate`` = "input" keeps per song (8 bytes a frame) are resident when the free HBM is read here, so the
+        HBM budget is already net of them; ``asx_pool_chunks`` counts chunks alone and so counts neither them nor the pitch temporaries."""
         extra = [0] * len(lengths)
         if self.pitch_shift != 0:
             lengths = [dm.pitched_len(n) for n in lengths]
@@ -260,6 +282,8 @@ class MDXCSeparator(CommonSeparator):
         keys, self._pool_keys = self._pool_keys, []
         thr, amp = self.normalization_threshold, self.amplification_threshold
         out = [None] * len(mixes)
+        kept = getattr(self, "_pool_kept", None) or [False] * len(mixes)
+        scales = self._pool_mix_scales = [1.0] * len(mixes)       # the factor of each mix's normalise, read before it runs
         host_only = not self._fast_file_path_enabled()
         for key in (False, True):
             idx = [i for i, k in enumerate(keys) if k == key]
@@ -270,12 +294,16 @@ class MDXCSeparator(CommonSeparator):
             if host_only and self.pitch_shift != 0:
                 for i in idx:
                     try:
+                        scales[i] = self._mix_factor(None, mixes[i][1], kept[i])
                         out[i] = ("host", eng, dm.demix(eng.normalize(mixes[i][1], thr, amp)))
                     except Exception as e:                   # this file only: raised again where its files would be written
                         out[i] = e
                 continue
             if host_only:
-                host = [eng.normalize(mixes[i][1] if mixes[i][1] is not None else mixes[i][0].cpu().numpy(), thr, amp) for i in idx]
+                host = [mixes[i][1] if mixes[i][1] is not None else mixes[i][0].cpu().numpy() for i in idx]
+                for i, m in zip(idx, host):
+                    scales[i] = self._mix_factor(None, m, kept[i])
+                host = [eng.normalize(m, thr, amp) for m in host]
                 for run in self._sub_pools(dm, [m.shape[1] for m in host]):
                     for j, source in zip(run, dm.demix_many([host[j] for j in run])):
                         out[idx[j]] = ("host", eng, source)
@@ -283,7 +311,8 @@ class MDXCSeparator(CommonSeparator):
             t0 = self._now()
             st = self._stream()
             dev = self._device_mixes([mixes[i] for i in idx])
-            for m in dev:
+            for i, m in zip(idx, dev):
+                scales[i] = self._mix_factor(m, None, kept[i])
                 eng.normalize_dev(m.data_ptr(), 2 * m.shape[1], thr, amp, stream=st)
             for run in self._sub_pools(dm, [m.shape[1] for m in dev]):
                 for j, (names, stems_d) in zip(run, dm.demix_many_dev([dev[j] for j in run])):

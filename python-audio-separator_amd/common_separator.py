@@ -78,6 +78,8 @@ class CommonSeparator:
         self.asx_input_resample = self._input_resample_mode(config)    # who converts a file at another rate than the model's
         self.asx_output_encoder = self._output_encoder_mode(config)    # who compresses a .flac stem when pydub is installed
         self.asx_output_rate = self._output_rate_mode(config)          # the rate and frame count stems are written at
+        self.asx_complement_rate = self._complement_rate_mode(config, self.asx_output_rate)   # the rate the complement stem is formed at
+        self._complement_noted = False           # (the "nothing to do for this model" note: once per instance)
         self.file_timings = {}
         self._pending_writes = []                # (thread, error box) of container writes in flight
         # how the last stem reached its encoder: "flac_device_resident" | "flac_device_upload" (.flac), "wav_device_resident" (a .wav of
@@ -169,6 +171,87 @@ class CommonSeparator:
             raise ValueError(f"asx_output_rate='input' is not supported by {cls.__name__}: {cls._output_rate_refusal}")
         return mode
 
+    # ``common_config["asx_complement_rate"]``: "model" (the default) forms the complement stem -- the MDX secondary ``mix - compensate *
+    # primary``, the residual row of a single-target MDXC / Roformer model -- at the model's rate and converts it like every other stem, so
+    # with ``asx_output_rate`` = "input" it carries nothing above the converter's pass band.  "input" (needs ``asx_output_rate`` = "input" on
+    # the same plugin) forms the complement FILE at the file's rate against the file's own decoded mix, inside the stem converter's pass
+    # (asx_resample_rational_complement): c_f = fl(fl(s * mix_f) - fl(k * r)), r the converted model stem, s the factor the mix normalise
+    # applied, k ``compensate`` (MDX) or 1 -- the two stems then sum to s * the file.  ``primary_source`` / ``secondary_source``, what
+    # ``write_audio`` is handed and ``stems_dev`` stay at the model's rate.  No environment override, as for ``asx_output_rate``.
+    COMPLEMENT_RATE_MODES = ("model", "input")
+    _complement_rate_refusal = None    # (a plugin none of whose stems is a difference against the mix says why)
+
+    @classmethod
+    def _complement_rate_mode(cls, config, output_rate="model") -> str:
+        mode = config.get("asx_complement_rate") or "model"
+        if mode not in cls.COMPLEMENT_RATE_MODES:
+            raise ValueError(f"asx_complement_rate must be one of {cls.COMPLEMENT_RATE_MODES}, not {mode!r}")
+        if mode == "input" and cls._complement_rate_refusal:
+            raise ValueError(f"asx_complement_rate='input' is not supported by {cls.__name__}: {cls._complement_rate_refusal}")
+        if mode == "input" and output_rate != "input":
+            raise ValueError("asx_complement_rate='input' requires asx_output_rate='input' on the same plugin: the complement is formed at "
+                             "the file's rate only where the stems are written at it")
+        return mode
+
+    def _complement_stem_name(self):
+        """Hook: the name of the stem this plugin forms as ``s * mix - k * (its model stem)`` under the current options, None when it has
+        none (the base class, a multi-stem model, a spectral inversion)."""
+        return None
+
+    def _keeps_file_mix(self) -> bool:
+        """whether the decoded mix of a file that is being converted to the model's rate is kept for the complement's write"""
+        if getattr(self, "asx_complement_rate", "model") != "input" or getattr(self, "_stems_only", False):
+            return False                   # (``_stems_only``: stems_dev / stems_dev_many write nothing)
+        name = self._complement_stem_name()
+        return name is not None and self._wanted(name)
+
+    def _note_no_complement(self, why: str):
+        if getattr(self, "asx_complement_rate", "model") == "input" and not self._complement_noted:
+            self._complement_noted = True
+            self.logger.info(f"asx_complement_rate='input' does nothing here: {why}")
+
+    def _normalize_factor(self, peak) -> float:
+        """The float32 factor ``Engine.normalize`` with the plugin's thresholds applies to an array of this peak (1.0: none) -- the rule of
+        spec_utils.normalize as csrc/kernels_fft.h normalize_kernel restates it."""
+        peak, thr, amp = np.float32(peak), np.float32(self.normalization_threshold), self.amplification_threshold
+        if peak > thr:
+            return float(thr / peak)
+        if amp is not None and peak < np.float32(amp):
+            return float(np.float32(amp) / peak)
+        return 1.0
+
+    def _mix_factor(self, dev_mix, host_mix, kept=None) -> float:
+        """``s``: what the in-place normalise of the model-rate mix is about to multiply it by; 1.0 where nobody will ask (no kept mix --
+        ``kept`` says so for a file of a pool, the current file's state otherwise)."""
+        if not (self._file_mix is not None if kept is None else kept):
+            return 1.0
+        if dev_mix is not None:
+            return self.engine.normalize_scale_dev(dev_mix.data_ptr(), dev_mix.numel(), self.normalization_threshold, self.amplification_threshold,
+                                                   stream=self._stream())
+        return self._normalize_factor(np.abs(host_mix).max())
+
+    def _register_complement(self, complement_source, model_source, stem_scale: float, normalise: bool, model_wanted: bool = True):
+        """The plugin, when it emits a file's stems: ``complement_source`` (the array it hands to write_audio for the complement stem) is
+        ``_mix_scale * mix - stem_scale * model_source``; ``normalise``: the per-stem normalise follows (MDXC); ``model_wanted``: the model
+        stem is written as well.  Without a kept mix, or when the complement is not written, nothing is registered and the kept mix is
+        released."""
+        self._complement = None
+        if self._file_mix is None:
+            # the stems of this file are converted, the complement is wanted, and no decode left the file's own mix behind (a container
+            # only librosa reads, a decode that disagrees with the header): said once per file, not passed over in silence
+            name = self._complement_stem_name()
+            if (getattr(self, "asx_complement_rate", "model") == "input" and complement_source is not None and name is not None
+                    and self._wanted(name) and self._output_rate_target() is not None):
+                self.logger.warning(f"{self.audio_file_path}: asx_complement_rate='input', but the file's own mix was not kept by its decoder: "
+                                    f"the {name} stem is written from the difference at {self.sample_rate} Hz")
+            return
+        name = self._complement_stem_name()
+        if complement_source is None or name is None or not self._wanted(name) or self._output_rate_target() is None:
+            self._file_mix = None
+            return
+        self._complement = {"complement": complement_source, "model": model_source, "k": float(stem_scale), "normalise": bool(normalise),
+                            "model_wanted": bool(model_wanted), "complement_wanted": True, "converted": None}
+
     def _resample_plan(self, file_rate):
         """(n_out for n_in) -> callable when ``asx_input_resample`` is "device" and the engine's converter takes ``file_rate`` ->
         ``sample_rate``; None otherwise (the setting is "host", the rates are equal, the pair is refused: behave as before)."""
@@ -197,6 +280,9 @@ class CommonSeparator:
         self._file_rate = self._file_frames = None     # the input's own sample rate and frame count, where its header was read
         self._out_rate_group = None   # asx_output_rate = "input": (planar device stems [S, 2, N], the same at the file's rate)
         self._out_rate_warned = False
+        # asx_complement_rate = "input": the file's own decoded mix [2, F] (a CUDA tensor, or a host array on the host route) while the
+        # complement is still to be written, the factor the mix normalise applied, and what the plugin registered (_register_complement)
+        self._file_mix, self._mix_scale, self._complement = None, 1.0, None
 
     # ---- steps every architecture's separate() shares ---------------------------------------------------------------
     def _read_options(self, arch_config: dict, table):
@@ -218,6 +304,7 @@ class CommonSeparator:
         self._file_rate = self._file_frames = None
         self._out_rate_group = None
         self._out_rate_warned = False
+        self._file_mix, self._mix_scale, self._complement = None, 1.0, None
         self.file_timings = {}        # seconds per phase of this file when ``asx_profile_file`` is set (bench.py file_level)
 
     # ---- device-resident file path (load / normalise / write edges without host round trips) -----------------
@@ -362,6 +449,8 @@ class CommonSeparator:
             at_rate = torch.empty((2, n_out), dtype=torch.float32, device=dev)
             self.engine.resample_rational_dev(mix.data_ptr(), 2, frames, info["samplerate"], self.sample_rate, at_rate.data_ptr(), n_out,
                                               stream=self._stream())
+            if self._keeps_file_mix():
+                self._file_mix = mix       # 8 * frames bytes of HBM, until the complement stem is written
             mix = at_rate
             self._tick("resample", t0)
         return mix
@@ -424,6 +513,8 @@ class CommonSeparator:
             at_rate = torch.empty((2, n_out), dtype=torch.float32, device=dev)
             self.engine.resample_rational_dev(mix.data_ptr(), 2, frames, info["samplerate"], self.sample_rate, at_rate.data_ptr(), n_out,
                                               stream=self._stream())
+            if self._keeps_file_mix():
+                self._file_mix = mix       # 8 * frames bytes of HBM, until the complement stem is written
             mix = at_rate
             self._tick("resample", t0)
         return mix
@@ -523,7 +614,8 @@ class CommonSeparator:
     # one) publishes the shell as ``separate_many``; the others have no such attribute.  With the hook ``_stems_of`` it also publishes
     # ``_stems_dev_many`` as ``stems_dev_many``: the same pool, the stems left on the device instead of written (ensemble.py).  ``_PER_FILE`` lists what loading a file leaves
     # for its writer; a plugin that records more extends it.
-    _PER_FILE = ("audio_file_path", "audio_file_base", "input_bit_depth", "input_subtype", "_file_seconds", "_file_rate", "_file_frames")
+    _PER_FILE = ("audio_file_path", "audio_file_base", "input_bit_depth", "input_subtype", "_file_seconds", "_file_rate", "_file_frames",
+                 "_file_mix", "_mix_scale")
 
     def _prepare_model(self):
         """Hook: what has to be ready before the first file is loaded."""
@@ -561,7 +653,13 @@ class CommonSeparator:
         if not loaded:
             self._reset_file_state()
             return [], left_out
+        self._pool_mix_scales = None                  # (a plugin with a complement stem leaves one factor per loaded file here)
+        self._pool_kept = [state["_file_mix"] is not None for _, state, _, _ in loaded]
         stems = self._pooled_stems([(d, h) for _, _, d, h in loaded])
+        if self._pool_mix_scales is not None:
+            for (_, state, _, _), scale in zip(loaded, self._pool_mix_scales):
+                state["_mix_scale"] = scale
+            self._pool_mix_scales = None
         return [(i, state, dev_mix, file_stems) for (i, state, dev_mix, _), file_stems in zip(loaded, stems)], left_out
 
     def _file_failed(self, i, path, e):                # this file only
@@ -572,6 +670,8 @@ class CommonSeparator:
         self._reset_file_state()
         for k, v in state.items():
             setattr(self, k, v)
+        if state.get("_file_mix") is not None:
+            state["_file_mix"] = None                 # the plugin holds the kept mix now, and releases it when the complement is written
 
     def _separate_many(self, paths, custom_output_names=None):
         """``separate`` for a list of files with ONE pooled engine call: every file is loaded as ``separate`` loads it
@@ -612,7 +712,11 @@ class CommonSeparator:
         MDXC short-file rule (at most two pools), the Demucs shift offsets (drawn from ``random`` in file order)."""
         paths = list(paths)
         stems, states = [None] * len(paths), [None] * len(paths)
-        pooled, _ = self._pool_files(paths, device_only=True)
+        self._stems_only = True                       # nothing is written: no file-rate mix is kept, no peak is read back
+        try:
+            pooled, _ = self._pool_files(paths, device_only=True)
+        finally:
+            self._stems_only = False
         for i, state, _, file_stems in pooled:
             self._restore_file(state)
             try:
@@ -713,7 +817,28 @@ class CommonSeparator:
         t0 = self._tick("read", t0)
         y = self.engine.resample_rational(x, file_rate, self.sample_rate)
         self._tick("resample", t0)
+        if self._keeps_file_mix():         # (a mono file is duplicated, as the decoder on the device does)
+            self._file_mix = np.ascontiguousarray(np.broadcast_to(x, (2, x.shape[1])) if x.shape[0] == 1 else x[:2], np.float32)
         return (y[0] if y.shape[0] == 1 else y), self.sample_rate
+
+    def _keep_host_decoded_mix(self, path):
+        """``asx_complement_rate`` = "input" for a file that the host decoder brought to the model's rate (``asx_input_resample`` = "host",
+        a FLAC file without the device file path): its stems are converted back all the same (``_probe_file_rate`` read the header), so the
+        file is decoded once more at its own rate and kept.  The complement's algebra does not ask how the model-rate mix was made.  A
+        decode that does not give the header's rate and frame count keeps nothing; ``_register_complement`` then says so."""
+        if not self._keeps_file_mix() or not self._file_rate or not self._file_frames or self._file_rate == self.sample_rate:
+            return
+        try:
+            x, rate = audio_io.load(path, mono=False, sr=None)
+        except Exception as e:
+            self.logger.debug(f"{path}: no decode at the file's own rate ({e})")
+            return
+        x = np.asarray(x, np.float32)
+        x = x[None] if x.ndim == 1 else x
+        if rate != self._file_rate or x.shape[1] != self._file_frames or x.shape[0] > 2:
+            self.logger.debug(f"{path}: decoded as {x.shape} at {rate} Hz, the header says {self._file_frames} frames at {self._file_rate} Hz")
+            return
+        self._file_mix = np.ascontiguousarray(np.broadcast_to(x, (2, x.shape[1])) if x.shape[0] == 1 else x, np.float32)
 
     def prepare_mix(self, mix):
         """common_separator.py:217-282: path -> float32 [2, N] at ``sample_rate``; an ndarray [N, ch] is transposed;
@@ -722,7 +847,11 @@ class CommonSeparator:
         if not isinstance(mix, np.ndarray):
             self._probe_bit_depth(mix)
             self._probe_file_rate(mix)
-            mix, sr = self._load_resampled(mix) or audio_io.load(mix, mono=False, sr=self.sample_rate)
+            got = self._load_resampled(mix)
+            if got is None:
+                got = audio_io.load(mix, mono=False, sr=self.sample_rate)
+                self._keep_host_decoded_mix(audio_path)
+            mix, sr = got
             self.logger.debug(f"decoded {audio_path}: {mix.shape[-1]} samples x {mix.shape[0] if mix.ndim > 1 else 1} channel(s) at {sr} Hz")
         else:
             if self.input_bit_depth is None:
@@ -805,7 +934,8 @@ class CommonSeparator:
         one (MDX ``invert_using_spec``) its share.  A stem that is still in HBM, and that its writer takes from there, is converted there
         (rows or planar; the planar stems of one file in ONE launch at the first of them) and handed on as a device entry under a
         zero-stride stand-in of the new shape; any other goes through Engine.resample_rational_stem.  (``sample_rate``, the stem itself)
-        when nothing is converted."""
+        when nothing is converted.  The two stems ``_register_complement`` named (``asx_complement_rate`` = "input") take
+        ``_pair_at_output_rate`` instead."""
         target = self._output_rate_target()
         if target is None:
             return self.sample_rate, stem_source
@@ -818,7 +948,11 @@ class CommonSeparator:
         t0 = self._now()
         entry = self._device_stem_entry(stem_source)
         on_device = entry is not None and (self._soundfile_on_device(stem_path) if self.use_soundfile else True)
-        if on_device:
+        pair = self._complement
+        role = None if pair is None else ("complement" if stem_source is pair["complement"] else "model" if stem_source is pair["model"] else None)
+        if role is not None:
+            out = self._pair_at_output_rate(stem_path, stem_source, role, n, n_out, rate)
+        elif on_device:
             import torch
             dev_stem = entry[1]
             group, index = entry[4] if len(entry) > 4 else (None, 0)
@@ -848,6 +982,60 @@ class CommonSeparator:
             self._sync()
         self.file_timings["resample_out"] = self.file_timings.get("resample_out", 0.0) + (self._now() - t0)
         return rate, out
+
+    def _pair_at_output_rate(self, stem_path, stem_source, role, n, n_out, rate):
+        """``_at_output_rate`` for the two stems ``_register_complement`` named, ``asx_complement_rate`` = "input": ONE fused launch
+        (asx_resample_rational_complement) at whichever of them is written first converts the model stem -- the bits of the plain
+        conversion -- and forms the complement against the kept file-rate mix; the other one's tensor (or array) waits in the registration
+        for its own write, so neither the model stem's device tensor nor the kept mix has to outlive this call."""
+        pair = self._complement
+        other = "model" if role == "complement" else "complement"
+        if pair["converted"] is not None:                      # the second of the two: converted at the first
+            where, kept = pair["converted"]
+            self._complement = None
+            self._dev_stems.pop(id(stem_source), None)
+        else:
+            eng = self.engine
+            thr, amp = self.normalization_threshold, self.amplification_threshold
+            model_entry = self._device_stem_entry(pair["model"])
+            mix, self._file_mix = self._file_mix, None          # released with this call
+            takes_device = self._soundfile_on_device(stem_path) if self.use_soundfile else True
+            other_wanted = pair[f"{other}_wanted"]
+            want_y = role == "model" or other_wanted
+            if model_entry is not None and takes_device:
+                import torch
+                where = "device"
+                x = model_entry[1].contiguous()
+                if isinstance(mix, np.ndarray):
+                    mix = torch.from_numpy(mix).to(x.device)
+                y = torch.empty((2, n_out), dtype=torch.float32, device=x.device) if want_y else None
+                c = torch.empty((2, n_out), dtype=torch.float32, device=x.device)
+                eng.resample_rational_complement_dev(x.data_ptr(), model_entry[3], 2, n, self.sample_rate, rate, mix.data_ptr(), mix.shape[1],
+                                                     self._mix_scale, pair["k"], y.data_ptr() if want_y else 0, c.data_ptr(), n_out,
+                                                     stream=self._stream())
+                if pair["normalise"]:
+                    eng.normalize_dev(c.data_ptr(), 2 * n_out, thr, amp, stream=self._stream())
+            else:
+                where = "host"
+                if self._device_stem_entry(pair["model"]) is not None or self._device_stem_entry(pair["complement"]) is not None:
+                    self._sync()                                # (the pinned mirrors are filled by asynchronous copies)
+                if not isinstance(mix, np.ndarray):
+                    mix = mix.cpu().numpy()
+                y, c = eng.resample_rational_complement(np.ascontiguousarray(np.asarray(pair["model"]), np.float32), self.sample_rate, rate,
+                                                        n_out, mix, self._mix_scale, pair["k"], layout="rows", want_stem=want_y)
+                if pair["normalise"]:
+                    c = eng.normalize(c, thr, amp)
+            for source in (pair["model"], pair["complement"]):
+                self._dev_stems.pop(id(source), None)
+            kept, waiting = (c, y) if role == "complement" else (y, c)
+            pair["converted"] = (where, waiting)
+            if not other_wanted:
+                self._complement = None
+        if where == "host":
+            return kept.T
+        out = np.broadcast_to(np.float32(0), (n_out, 2))          # stands for the shape only: the writers read the device tensor
+        self._dev_stems[id(out)] = (out, kept, None, "planar")
+        return out
 
     def _stereo_rows(self, stem_source):
         a = np.asarray(stem_source)
@@ -1095,6 +1283,7 @@ class CommonSeparator:
         point of keeping 288 GB resident); only Python garbage and torch's caching allocator are trimmed."""
         self._dev_stems = {}
         self._out_rate_group = None
+        self._file_mix, self._complement = None, None
         gc.collect()
         try:
             import torch

@@ -1147,6 +1147,103 @@ int asx_resample_rational_stem(asx_engine *e, const float *x_host, int32_t layou
   });
 }
 
+// The complement form of the writer-side converter: y (optional) and c = fl(fl(mix_scale mix) - fl(stem_scale y)) in one launch (include/asx.h)
+static int rs_complement_check(const char *fn, asx_engine *e, const float *x, int32_t layout, int32_t channels, int64_t n_in, int32_t sr_in,
+                               int32_t sr_out, const float *mix, int64_t mix_stride, float mix_scale, float stem_scale, float *c, int64_t n_out,
+                               ResamplePlan &p) {
+  REQUIRE(e, "%s: null engine", fn);
+  REQUIRE(x, "%s: x is null", fn);
+  REQUIRE(mix, "%s: mix is null", fn);
+  REQUIRE(c, "%s: c is null", fn);
+  REQUIRE(layout == 0 || layout == 1, "%s: layout = %d (0: planar [channels, n_in], 1: rows [n_in, channels])", fn, layout);
+  REQUIRE(channels >= 1 && channels <= 65535, "%s: %d channels (1 .. 65535)", fn, channels);
+  const std::string why = resample_plan_make(sr_in, sr_out, p);
+  REQUIRE(why.empty(), "%s: %s", fn, why.c_str());
+  const std::string bad = resample_plan_check_stem(p, n_in, n_out);
+  REQUIRE(bad.empty(), "%s: %s", fn, bad.c_str());
+  REQUIRE(mix_stride >= n_out && mix_stride <= ((int64_t)1 << 40), "%s: mix_stride = %lld (n_out = %lld .. 2^40)", fn, (long long)mix_stride,
+          (long long)n_out);
+  REQUIRE(std::isfinite(mix_scale), "%s: mix_scale is not finite", fn);
+  REQUIRE(std::isfinite(stem_scale), "%s: stem_scale is not finite", fn);
+  REQUIRE(p.K == 8 || !p.taps_in_lds, "%s: no kernel for the tile of %d -> %d Hz", fn, sr_in, sr_out);
+  return ASX_OK;
+}
+
+int asx_resample_rational_complement_dev(asx_engine *e, const float *x_dev, int32_t layout, int32_t channels, int64_t n_in, int32_t sr_in,
+                                         int32_t sr_out, const float *mix_dev, int64_t mix_stride, float mix_scale, float stem_scale,
+                                         float *y_dev, float *c_dev, int64_t n_out, void *stream) {
+  ResamplePlan p;
+  CHK(rs_complement_check("asx_resample_rational_complement_dev", e, x_dev, layout, channels, n_in, sr_in, sr_out, mix_dev, mix_stride, mix_scale,
+                          stem_scale, c_dev, n_out, p));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  const RsTable *t = nullptr;
+  CHK(rs_table(e, p, &t));
+  const float *tab = t->tab.f();
+  const bool rows = layout == 1;
+  const double bytes = 4.0 * channels * ((double)n_in + (double)n_out * (y_dev ? 3.0 : 2.0));
+  return timed(e, ASX_PROF_MISC, 2.0 * channels * (double)n_out * (double)p.T, bytes, s, [&]() {
+    if (p.taps_in_lds)
+      rs_complement_launch<8, true>(p, x_dev, rows, channels, n_in, tab, y_dev, n_out, mix_dev, mix_stride, mix_scale, stem_scale, c_dev, s);
+    else if (p.K == 8)
+      rs_complement_launch<8, false>(p, x_dev, rows, channels, n_in, tab, y_dev, n_out, mix_dev, mix_stride, mix_scale, stem_scale, c_dev, s);
+    else if (p.K == 4)
+      rs_complement_launch<4, false>(p, x_dev, rows, channels, n_in, tab, y_dev, n_out, mix_dev, mix_stride, mix_scale, stem_scale, c_dev, s);
+    else if (p.K == 2)
+      rs_complement_launch<2, false>(p, x_dev, rows, channels, n_in, tab, y_dev, n_out, mix_dev, mix_stride, mix_scale, stem_scale, c_dev, s);
+    else
+      rs_complement_launch<1, false>(p, x_dev, rows, channels, n_in, tab, y_dev, n_out, mix_dev, mix_stride, mix_scale, stem_scale, c_dev, s);
+  });
+}
+
+int asx_resample_rational_complement(asx_engine *e, const float *x_host, int32_t layout, int32_t channels, int64_t n_in, int32_t sr_in,
+                                     int32_t sr_out, const float *mix_host, int64_t mix_stride, float mix_scale, float stem_scale,
+                                     float *y_host, float *c_host, int64_t n_out) {
+  // (checked here as well: the sizes of the staging buffers follow from the arguments)
+  ResamplePlan p;
+  CHK(rs_complement_check("asx_resample_rational_complement", e, x_host, layout, channels, n_in, sr_in, sr_out, mix_host, mix_stride, mix_scale,
+                          stem_scale, c_host, n_out, p));
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dx, dmix, dy, dc;
+  BufGuard g{{&dx, &dmix, &dy, &dc}};
+  CHK(to_dev(dx, x_host, (size_t)channels * n_in));
+  CHK(to_dev(dmix, mix_host, (size_t)channels * mix_stride));
+  if (y_host) CHK(dy.ensure((size_t)channels * n_out * 4));
+  CHK(dc.ensure((size_t)channels * n_out * 4));
+  CHK(asx_resample_rational_complement_dev(e, dx.f(), layout, channels, n_in, sr_in, sr_out, dmix.f(), mix_stride, mix_scale, stem_scale,
+                                           y_host ? dy.f() : nullptr, dc.f(), n_out, nullptr));
+  if (y_host) CHK(to_host(y_host, dy, (size_t)channels * n_out));
+  return to_host(c_host, dc, (size_t)channels * n_out);
+}
+
+// the factor asx_normalize_dev would multiply wave_dev by (1 where it leaves the array alone): the peak word comes to the host, nothing else
+int asx_normalize_scale_dev(asx_engine *e, const float *wave_dev, int64_t numel, float max_peak, float min_peak, int32_t has_min, float *scale,
+                            void *stream) {
+  REQUIRE(e, "asx_normalize_scale_dev: null engine");
+  REQUIRE(wave_dev, "asx_normalize_scale_dev: wave is null");
+  REQUIRE(scale, "asx_normalize_scale_dev: scale is null");
+  REQUIRE(numel >= 1, "asx_normalize_scale_dev: numel = %lld (>= 1)", (long long)numel);
+  REQUIRE(std::isfinite(max_peak) && (!has_min || std::isfinite(min_peak)), "asx_normalize_scale_dev: a threshold is not finite");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  HIPCHK(hipSetDevice(e->device));
+  CHK(e->d_peak.ensure(256));
+  unsigned int *pk = reinterpret_cast<unsigned int *>(e->d_peak.p) + 5;   // its own word (0 .. 4: see asx_normalize_dev and the decoders)
+  HIPCHK(hipMemsetAsync(pk, 0, 4, s));
+  const unsigned nb = (unsigned)std::min<int64_t>((numel + 255) / 256, 2048);
+  CHK(timed(e, ASX_PROF_MISC, 0.0, 4.0 * numel, s, [&]() { hipLaunchKernelGGL(absmax_kernel, dim3(nb), dim3(256), 0, s, wave_dev, numel, pk); }));
+  float maxv = 0.f;
+  HIPCHK(hipMemcpyAsync(&maxv, pk, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  // normalize_kernel's branches; a float32 division on the host rounds as __fdiv_rn does (the operands and the result are floats)
+  float q = 1.f;
+  if (maxv > max_peak) q = max_peak / maxv;
+  else if (has_min && maxv < min_peak) q = min_peak / maxv;
+  // a silent array under a minimum peak: the normalise would multiply by infinity.  Said here, not by whoever is handed the factor
+  REQUIRE(std::isfinite(q), "asx_normalize_scale_dev: wave is silent (peak %g): min_peak / peak is not finite", (double)maxv);
+  *scale = q;
+  return ASX_OK;
+}
+
 // The FLAC encoder (kernels_flac.h, engine_flac.h): the plan of a stream, pure host
 int asx_flac_plan(int64_t n_samples, int32_t channels, int32_t bits_per_sample, int32_t block_size, int64_t *n_blocks, int32_t *frame_stride,
                   int64_t *max_bytes, int64_t *scratch_bytes) {

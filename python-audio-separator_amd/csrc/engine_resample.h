@@ -48,3 +48,17 @@ static void rs_stem_launch(const ResamplePlan &p, const float *x, bool rows, int
     hipLaunchKernelGGL((resample_rational_stem_kernel<K, TAPS_LDS, false>), grid, dim3(RS_THREADS), lds, s, x, channels, n_in, tab, (int)p.L, (int)p.M,
                        (int)p.P, (int)p.J, (int)p.span, y, n_out);
 }
+
+// the complement form of the same launch: y (may be null) and c = fl(fl(mix_scale mix) - fl(stem_scale y)) from one pass over the tiles
+template <int K, bool TAPS_LDS>
+static void rs_complement_launch(const ResamplePlan &p, const float *x, bool rows, int channels, int64_t n_in, const float *tab, float *y, int64_t n_out,
+                                 const float *mix, int64_t mix_stride, float mix_scale, float stem_scale, float *c, hipStream_t s) {
+  const size_t lds = (size_t)(p.span + (TAPS_LDS ? p.L * p.T : 0)) * sizeof(float);   // at most 64 KiB (RESAMPLE_MAX_LDS_FLOATS)
+  const dim3 grid((unsigned)((n_out + p.J * K - 1) / (p.J * K)), (unsigned)channels);
+  if (rows)
+    hipLaunchKernelGGL((resample_rational_stem_kernel<K, TAPS_LDS, true, true>), grid, dim3(RS_THREADS), lds, s, x, channels, n_in, tab, (int)p.L,
+                       (int)p.M, (int)p.P, (int)p.J, (int)p.span, y, n_out, mix, mix_stride, mix_scale, stem_scale, c);
+  else
+    hipLaunchKernelGGL((resample_rational_stem_kernel<K, TAPS_LDS, false, true>), grid, dim3(RS_THREADS), lds, s, x, channels, n_in, tab, (int)p.L,
+                       (int)p.M, (int)p.P, (int)p.J, (int)p.span, y, n_out, mix, mix_stride, mix_scale, stem_scale, c);
+}

@@ -22,9 +22,11 @@ namespace asx {
 constexpr int RS_THREADS = 256;   // RESAMPLE_THREADS of resample_plan.h
 
 // the outputs of one tile from its staged span: xs[u] = x[i0 + u] (0 outside the input), cs the table in LDS when TAPS_LDS
-template <int K, bool TAPS_LDS>
+// COMP (the complement form, below): r goes to yc when that is not null, and cc[m] = fl(fl(ms mixc[m]) - fl(ss r))
+template <int K, bool TAPS_LDS, bool COMP = false>
 __device__ __forceinline__ void rs_tile_outputs(const float *xs, const float *cs, const float *__restrict__ tab, int L, int M, int P, int J, int64_t first,
-                                                float *__restrict__ yc, int64_t n_out) {
+                                                float *__restrict__ yc, int64_t n_out, const float *__restrict__ mixc = nullptr,
+                                                float *__restrict__ cc = nullptr, float ms = 1.f, float ss = 1.f) {
   const int tid = (int)threadIdx.x;
   const int step = J / L * M;   // the input base of period k + 1 over that of period k
   for (int j = tid; j < J; j += RS_THREADS) {
@@ -48,7 +50,15 @@ __device__ __forceinline__ void rs_tile_outputs(const float *xs, const float *cs
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int64_t mk = m + (int64_t)k * J;
-      if (mk < n_out) yc[mk] = fmaf(c_mid, xb[P + k * step], lo[k] + hi[k]);
+      if (mk >= n_out) continue;
+      const float r = fmaf(c_mid, xb[P + k * step], lo[k] + hi[k]);
+      if (COMP) {
+        const float w = mixc[mk];   // (the lanes of a pass: consecutive mk, like the stores)
+        if (yc) yc[mk] = r;
+        cc[mk] = __fsub_rn(__fmul_rn(ms, w), __fmul_rn(ss, r));   // two roundings and a third: hipcc would contract a*b - c*d
+      } else {
+        yc[mk] = r;
+      }
     }
   }
 }
@@ -80,20 +90,32 @@ __global__ __launch_bounds__(RS_THREADS) void resample_rational_kernel(const flo
 // T J K LDS reads and FMAs of the tile, which is why the channels are not folded into one workgroup (that would double the span in LDS, past
 // 64 KiB for 44.1 -> 32 kHz, to save under 1 % of the tile's work).  n_out is the caller's: the grid covers it, and a tile whose span starts at or
 // past n_in -- the filter has left the input -- stores zeros without staging or reading anything.
-template <int K, bool TAPS_LDS, bool ROWS>
+//
+// COMP, the complement form (asx_resample_rational_complement): with r the output above, the epilogue also loads the file-rate mix
+// mix[ch mix_stride + m] and stores c[ch][m] = fl(fl(mix_scale mix) - fl(stem_scale r)) -- three float32 roundings, no FMA -- beside r
+// (y may be null: only c is stored).  No LDS and no barrier of its own; a tile past the input stores c = fl(mix_scale mix) - fl(stem_scale 0).
+template <int K, bool TAPS_LDS, bool ROWS, bool COMP = false>
 __global__ __launch_bounds__(RS_THREADS) void resample_rational_stem_kernel(const float *__restrict__ x, int channels, int64_t n_in,
                                                                              const float *__restrict__ tab, int L, int M, int P, int J, int span,
-                                                                             float *__restrict__ y, int64_t n_out) {
+                                                                             float *__restrict__ y, int64_t n_out,
+                                                                             const float *__restrict__ mix = nullptr, int64_t mix_stride = 0,
+                                                                             float mix_scale = 1.f, float stem_scale = 1.f,
+                                                                             float *__restrict__ c = nullptr) {
   extern __shared__ float rs_lds[];
   float *xs = rs_lds;          // [span]: x[i0 + u]
   float *cs = rs_lds + span;   // TAPS_LDS: the table [2 P + 1][L]
   const int tid = (int)threadIdx.x;
   const int64_t first = (int64_t)blockIdx.x * J * K;   // a multiple of L
   const int64_t i0 = first / L * M - P;                // the input sample behind xs[0]
-  float *yc = y + (int64_t)blockIdx.y * n_out;
+  float *yc = (COMP && !y) ? nullptr : y + (int64_t)blockIdx.y * n_out;
+  const float *mixc = COMP ? mix + (int64_t)blockIdx.y * mix_stride : nullptr;
+  float *cc = COMP ? c + (int64_t)blockIdx.y * n_out : nullptr;
   if (i0 >= n_in) {   // (the same for every thread of the workgroup)
     const int64_t end = first + (int64_t)J * K < n_out ? first + (int64_t)J * K : n_out;
-    for (int64_t m = first + tid; m < end; m += RS_THREADS) yc[m] = 0.f;
+    for (int64_t m = first + tid; m < end; m += RS_THREADS) {
+      if (!COMP || yc) yc[m] = 0.f;
+      if (COMP) cc[m] = __fsub_rn(__fmul_rn(mix_scale, mixc[m]), __fmul_rn(stem_scale, 0.f));
+    }
     return;
   }
   const float *xc = ROWS ? x + blockIdx.y : x + (int64_t)blockIdx.y * n_in;
@@ -105,7 +127,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_rational_stem_kernel(cons
   if (TAPS_LDS)
     for (int u = tid; u < (2 * P + 1) * L; u += RS_THREADS) cs[u] = tab[u];
   __syncthreads();
-  rs_tile_outputs<K, TAPS_LDS>(xs, cs, tab, L, M, P, J, first, yc, n_out);
+  rs_tile_outputs<K, TAPS_LDS, COMP>(xs, cs, tab, L, M, P, J, first, yc, n_out, mixc, cc, mix_scale, stem_scale);
 }
 
 }  // namespace asx

@@ -283,7 +283,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_flac_plan_pcm", "asx_flac_encode_pcm", "asx_flac_encode_pcm_dev", "asx_pcm_encode", "asx_pcm_encode_dev",
            "asx_invert_stem_dev", "asx_invert_stem_batch_dev", "asx_op_gconv", "asx_op_dconv", "asx_resample_sinc_batch_dev",
            "asx_resample_rational_stem", "asx_resample_rational_stem_dev", "asx_op_stft", "asx_op_istft", "asx_op_ht_spec",
-           "asx_op_ht_ispec", "asx_ensemble_batch_modes_dev"]
+           "asx_op_ht_ispec", "asx_ensemble_batch_modes_dev", "asx_resample_rational_complement",
+           "asx_resample_rational_complement_dev", "asx_normalize_scale_dev"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -469,6 +470,9 @@ def load_library():
     lib.asx_resample_rational_dev.argtypes = [vp, vp, i32, i64, i32, i32, vp, i64, vp]
     lib.asx_resample_rational_stem.argtypes = [vp, _FP, i32, i32, i64, i32, i32, _FP, i64]
     lib.asx_resample_rational_stem_dev.argtypes = [vp, vp, i32, i32, i64, i32, i32, vp, i64, vp]
+    lib.asx_resample_rational_complement.argtypes = [vp, _FP, i32, i32, i64, i32, i32, _FP, i64, C.c_float, C.c_float, _FP, _FP, i64]
+    lib.asx_resample_rational_complement_dev.argtypes = [vp, vp, i32, i32, i64, i32, i32, vp, i64, C.c_float, C.c_float, vp, vp, i64, vp]
+    lib.asx_normalize_scale_dev.argtypes = [vp, vp, i64, C.c_float, C.c_float, i32, C.POINTER(C.c_float), vp]
     lib.asx_flac_plan.argtypes = [i64, i32, i32, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
     lib.asx_flac_encode.argtypes = [vp, C.POINTER(C.c_int16), i64, i32, i32, i32, C.POINTER(C.c_uint8), i64, C.POINTER(i32), C.POINTER(i64)]
     lib.asx_flac_encode_dev.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, vp, C.POINTER(i64), vp]
@@ -976,6 +980,39 @@ class Engine:
         self._check(self._lib.asx_resample_rational_stem_dev(self._h, x_ptr, self.RESAMPLE_LAYOUTS[layout], int(channels), int(n_in), int(sr_in),
                                                              int(sr_out), y_ptr, int(n_out), stream or None))
 
+    def resample_rational_complement(self, x: np.ndarray, sr_in: int, sr_out: int, n_out: int, mix: np.ndarray, mix_scale: float = 1.0,
+                                     stem_scale: float = 1.0, layout: str = "planar", want_stem: bool = True):
+        """The complement form of ``resample_rational_stem`` (asx_resample_rational_complement): with y what that call gives for ``x``,
+        returns (y, c), both planar [C, n_out] -- (None, c) without ``want_stem`` -- where
+        c[ch][m] = fl(fl(mix_scale * mix[ch][m]) - fl(stem_scale * y[ch][m])), one float32 rounding each.  ``mix``: planar [C, >= n_out]
+        at ``sr_out`` Hz (a row stride beyond ``n_out`` is passed on as it is)."""
+        if layout not in self.RESAMPLE_LAYOUTS:
+            raise ValueError(f"layout must be one of {tuple(self.RESAMPLE_LAYOUTS)}, not {layout!r}")
+        x = _f32(x)
+        one = x.ndim == 1 and layout == "planar"
+        x2 = np.ascontiguousarray(x[None] if one else x)
+        if x2.ndim != 2 or min(x2.shape) < 1:
+            raise ValueError(f"resample_rational_complement expects {'[channels, n]' if layout == 'planar' else '[n, channels]'}, got {x.shape}")
+        ch, n_in = x2.shape if layout == "planar" else x2.shape[::-1]
+        m = _f32(mix)
+        m2 = np.ascontiguousarray(m[None] if m.ndim == 1 else m)
+        if m2.ndim != 2 or m2.shape[0] != ch:
+            raise ValueError(f"resample_rational_complement expects a mix of [{ch}, >= n_out], got {m.shape}")
+        y = np.empty((ch, max(int(n_out), 0)), np.float32) if want_stem else None
+        c = np.empty((ch, max(int(n_out), 0)), np.float32)
+        self._check(self._lib.asx_resample_rational_complement(self._h, _ptr(x2), self.RESAMPLE_LAYOUTS[layout], ch, n_in, int(sr_in),
+                                                               int(sr_out), _ptr(m2), m2.shape[1], float(mix_scale), float(stem_scale),
+                                                               _ptr(y) if want_stem else None, _ptr(c), int(n_out)))
+        return (y[0] if one and want_stem else y), (c[0] if one else c)
+
+    def resample_rational_complement_dev(self, x_ptr: int, layout: str, channels: int, n_in: int, sr_in: int, sr_out: int, mix_ptr: int,
+                                         mix_stride: int, mix_scale: float, stem_scale: float, y_ptr: int, c_ptr: int, n_out: int,
+                                         stream: int = 0):
+        """asx_resample_rational_complement_dev; ``y_ptr`` = 0: only the complement is stored."""
+        self._check(self._lib.asx_resample_rational_complement_dev(self._h, x_ptr, self.RESAMPLE_LAYOUTS[layout], int(channels), int(n_in),
+                                                                   int(sr_in), int(sr_out), mix_ptr, int(mix_stride), float(mix_scale),
+                                                                   float(stem_scale), y_ptr or None, c_ptr, int(n_out), stream or None))
+
     def vr_flops(self) -> float:
         return float(self._lib.asx_vr_flops(self._h))
 
@@ -1386,6 +1423,14 @@ class Engine:
     def normalize_dev(self, wave_ptr: int, numel: int, max_peak: float = 1.0, min_peak=None, stream: int = 0):
         self._check(self._lib.asx_normalize_dev(self._h, wave_ptr, numel, float(max_peak), float(min_peak or 0.0),
                                                 int(min_peak is not None), stream or None))
+
+    def normalize_scale_dev(self, wave_ptr: int, numel: int, max_peak: float = 1.0, min_peak=None, stream: int = 0) -> float:
+        """The float32 factor ``normalize_dev`` with these arguments would multiply the array by (1.0: it would leave it alone).  Reads
+        the array's peak -- four bytes -- back, so it waits for ``stream``; the array is not changed."""
+        q = C.c_float()
+        self._check(self._lib.asx_normalize_scale_dev(self._h, wave_ptr, numel, float(max_peak), float(min_peak or 0.0),
+                                                      int(min_peak is not None), C.byref(q), stream or None))
+        return q.value
 
     def residual_dev(self, mix_ptr: int, stem_ptr: int, out_ptr: int, numel: int, stream: int = 0):
         self._check(self._lib.asx_residual_dev(self._h, mix_ptr, stem_ptr, out_ptr, numel, stream or None))

@@ -4,9 +4,12 @@
   kernel  asx_resample_rational_stem_dev alone (device events over 20 launches, after a warm-up) for the stems of the song at 44.1 kHz
           -- MDX rows [N, 2], and the four Demucs stems planar [4, 2, N] in one launch -- to 48 kHz and to 96 kHz; beside it, as the
           yardstick, asx_resample_rational_dev 48 kHz -> 44.1 kHz on the same song (the input side of the same file);
-  file    ``MDXSeparator.separate(song48.wav)`` on the HQ_3 geometry, file to files on tmpfs, 48 kHz PCM_16 in: medians of 5 per child
-          process with the knob off and on, alternating; with --parent TREE (a checkout of the parent commit with its library built) the
-          knob-off run of that tree alternates with this one's, child by child;
+          and the complement form of the same launch, asx_resample_rational_complement_dev (``asx_complement_rate = "input"``), on the
+          MDX rows stem against a file-rate mix [2, F]: y and c stored, and c alone;
+  file    ``MDXSeparator.separate(song.wav)`` on the HQ_3 geometry, file to files on tmpfs, PCM_16 in at --rate (48 kHz): medians of 5 per
+          child process with ``asx_output_rate`` off and on, and with ``asx_complement_rate = "input"`` on top, alternating; with --parent
+          TREE (a checkout of the parent commit with its library built) that tree's run at --parent-knob ("off", or "on": asx_output_rate =
+          "input", the path the complement knob must not slow down) alternates with this one's, child by child;
   host    the alternative on the host: scipy.signal.resample_poly(stem, L, M, window=<the same taps>) per stereo stem -- ONE host thread.
 
 Every step runs in a fresh child process under a time limit of its own; the first one that fails ends the run.  One JSON object, also
@@ -95,6 +98,14 @@ def step_kernel(args):
             ms = timed(lambda: eng.resample_rational_stem_dev(x.data_ptr(), layout, ch, n, SR, rate, y.data_ptr(), F, stream=st))
             r[name] = {"kernel_ms": round(ms, 4), "gflop_per_s": round(2.0 * ch * F * T / ms / 1e6, 1),
                        "gb_per_s_read_plus_written": round(4.0 * ch * (n + F) / ms / 1e6, 1)}
+        if hasattr(eng, "resample_rational_complement_dev"):
+            file_mix = torch.from_numpy(song(rate, args.seconds)).to(dev)[:, :F].contiguous()      # the file's own mix [2, F]
+            c = torch.empty((2, F), dtype=torch.float32, device=dev)
+            for name, y_ptr, stores in (("complement_rows_2ch", y.data_ptr(), 2), ("complement_rows_2ch_c_only", 0, 1)):
+                ms = timed(lambda: eng.resample_rational_complement_dev(rows.data_ptr(), "rows", 2, n, SR, rate, file_mix.data_ptr(), F, 0.95,
+                                                                        1.022, y_ptr, c.data_ptr(), F, stream=st))
+                r[name] = {"kernel_ms": round(ms, 4), "gflop_per_s": round(2.0 * 2 * F * T / ms / 1e6, 1),
+                           "gb_per_s_read_plus_written": round(4.0 * 2 * (n + F * (1 + stores)) / ms / 1e6, 1)}
         out[f"{SR}->{rate}"] = r
     # the yardstick: the input side of the same 48 kHz file
     n48 = int(48000 * args.seconds)
@@ -118,8 +129,8 @@ def step_file(args):
     base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
     tmp = tempfile.mkdtemp(prefix="asx_probe_output_rate_", dir=base)
     try:
-        wav = os.path.join(tmp, "song48000.wav")
-        audio_io.write_wav(wav, np.ascontiguousarray(song(48000, args.seconds).T), 48000, "PCM_16")
+        wav = os.path.join(tmp, f"song{args.rate}.wav")
+        audio_io.write_wav(wav, np.ascontiguousarray(song(args.rate, args.seconds).T), args.rate, "PCM_16")
         d = O.NetDims()
         log = logging.getLogger("probe.output_rate")
         log.setLevel(logging.ERROR)
@@ -132,8 +143,9 @@ def step_file(args):
                   "sample_rate": SR, "use_soundfile": False, "asx_state_dict": O.make_convtdf_state(d, seed=0), "asx_net_config": A.NetConfig(),
                   "asx_profile_file": bool(args.phases), "asx_input_resample": "device"}
         arch = {"hop_length": 1024, "segment_size": 256, "overlap": 0.25, "batch_size": 1, "enable_denoise": False}
-        knobs = ["off", "on"] if args.knob == "both" else [args.knob]
-        seps = {k: MDXSeparator(dict(common, **({"asx_output_rate": "input"} if k == "on" else {})), arch) for k in knobs}
+        knobs = {"both": ["off", "on"], "all": ["off", "on", "complement"]}.get(args.knob, [args.knob])
+        over = {"off": {}, "on": {"asx_output_rate": "input"}, "complement": {"asx_output_rate": "input", "asx_complement_rate": "input"}}
+        seps = {k: MDXSeparator(dict(common, **over[k]), arch) for k in knobs}
         walls, phases = {k: [] for k in knobs}, {k: {} for k in knobs}
         for rep in range(args.calls + 1):                   # rep 0 is the warm-up: workspaces, the tables, pinned staging, page cache
             for k in knobs:
@@ -147,7 +159,7 @@ def step_file(args):
                         phases[k].setdefault(p, []).append(v)
                 sep.clear_gpu_cache()
                 sep.clear_file_specific_paths()
-        out = {"tree": "parent commit" if os.path.abspath(args.tree) != ROOT else "this commit"}
+        out = {"tree": "parent commit" if os.path.abspath(args.tree) != ROOT else "this commit", "rate": args.rate}
         for k in knobs:
             info = [audio_io.wav_info(os.path.join(common["output_dir"], n)) for n in names] if k == knobs[-1] else None
             out[k] = {"median_wall_ms": round(statistics.median(walls[k]) * 1e3, 2), "walls_ms": [round(w * 1e3, 2) for w in walls[k]],
@@ -176,7 +188,7 @@ def step_host(args):
 
 def child(step, args, tree, knob="both", limit=None):
     cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--seconds", repr(args.seconds), "--tree", tree, "--knob", knob,
-           "--calls", str(args.calls)] + (["--phases"] if args.phases else [])
+           "--calls", str(args.calls), "--rate", str(args.rate)] + (["--phases"] if args.phases else [])
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit or LIMITS[step])
     except subprocess.TimeoutExpired:
@@ -197,15 +209,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--step", choices=sorted(LIMITS), default=None, help="run one step in this process (what the driver starts)")
     ap.add_argument("--tree", default=ROOT, help="with --step: the tree whose package is imported")
-    ap.add_argument("--knob", choices=["off", "on", "both"], default="both")
+    ap.add_argument("--knob", choices=["off", "on", "complement", "both", "all"], default="all")
+    ap.add_argument("--parent-knob", choices=["off", "on"], default="off", help="what the parent tree's children run")
+    ap.add_argument("--rate", type=int, default=48000, help="file step: the input file's sample rate")
     args = ap.parse_args()
     if args.step:
         sys.path.insert(0, os.path.abspath(args.tree))
         print(json.dumps({"kernel": step_kernel, "file": step_file, "host": step_host}[args.step](args)))
         return 0
     res = {"what": f"{args.seconds:g} s of stereo stems at 44.1 kHz -> 48 / 96 kHz: asx_resample_rational_stem_dev, the file-to-files wall of "
-                   "MDXSeparator.separate on a 48 kHz PCM_16 file with asx_output_rate off / on, and scipy.signal.resample_poly with the same "
-                   "taps on one host thread", "seconds": args.seconds}
+                   f"its complement form, the file-to-files wall of MDXSeparator.separate on a {args.rate} Hz PCM_16 file with asx_output_rate off / "
+                   "on / on with asx_complement_rate = 'input', and scipy.signal.resample_poly with the same taps on one host thread",
+           "seconds": args.seconds}
     ok = True
     for step in args.steps.split(","):
         if step != "file":
@@ -213,7 +228,7 @@ def main():
         else:
             res[step] = []
             for _ in range(args.rounds):
-                for tree, knob in (((args.parent, "off"),) if args.parent else ()) + ((ROOT, "both"),):
+                for tree, knob in (((args.parent, args.parent_knob),) if args.parent else ()) + ((ROOT, args.knob),):
                     res[step].append(child("file", args, tree, knob))
                     if "error" in res[step][-1]:
                         break
