@@ -16,3 +16,4 @@ from .vr import VRDemixer, load_model_params, model_capacity  # noqa: E402,F401
 from .plugin import install, uninstall  # noqa: E402,F401
 from .common_separator import CommonSeparator  # noqa: E402,F401
 from .ensemble import EnsembleSeparator, Ensembler  # noqa: E402,F401
+from .workflow import ChainSeparator  # noqa: E402,F401

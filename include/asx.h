@@ -838,6 +838,36 @@ int asx_ensemble_batch_dev(asx_engine *e, asx_ens_job *jobs, int32_t n_jobs, int
 int asx_ensemble_batch_modes_dev(asx_engine *e, asx_ens_job *jobs, int32_t n_jobs, const int32_t *modes, int32_t algorithm, const double *weights,
                                  int32_t n_weights, float max_peak, float min_peak, int32_t has_min, double silent_below, void *stream);
 
+/* Weighted sums of stereo stems that are already in HBM -- the mix-downs of workflow.ChainSeparator ("instrumental + backing vocals").
+ * Per job, frame i < n_out and channel, a source shorter than n_out read as zeros behind its end (one longer is read up to n_out):
+ *   acc = fl(w_0 * x_0[i]);  acc = fl(acc + fl(w_k * x_k[i])), k = 1 .. K-1 in list order
+ * in float32 with one rounding per operation and no contraction: bit for bit the numpy float32 restatement.
+ *   src[k].x       float32, planar [2, n] (ASX_STEM_PLANAR) or rows [n, 2] (ASX_STEM_ROWS), 4-byte aligned, only read; may be NULL where n == 0
+ *   out            planar [2, n_out] or rows [n_out, 2] (out_layout), 4-byte aligned; must not overlap a source of another layout or offset
+ * asx_mixdown_batch_dev serves all jobs with ONE launch and only enqueues work on `stream` (it waits for the previous call's launch on this
+ * engine before it reuses the job table, and for nothing of its own).  Accesses are 16 bytes wide wherever a group of four floats is whole
+ * and 16-byte aligned; the groups are anchored at the output's alignment.  Every argument of every job is checked before anything is
+ * enqueued (ASX_ERR_INVALID + asx_last_error(): k outside 1 .. ASX_MIX_MAX_K, n_out < 1, n < 0, null or misaligned pointers, unknown layouts,
+ * a weight that is not finite); n_jobs == 0 does nothing.  asx_mixdown: one job on host arrays (upload, launch, download).
+ * Additive within ABI 8. */
+#define ASX_MIX_MAX_K 8
+typedef struct asx_mix_src {
+  const float *x;
+  int32_t layout;   /* ASX_STEM_PLANAR / ASX_STEM_ROWS */
+  int64_t n;        /* samples per channel, >= 0 */
+  float w;
+} asx_mix_src;
+typedef struct asx_mix_job {
+  asx_mix_src src[ASX_MIX_MAX_K];
+  int32_t k;        /* sources, 1 .. ASX_MIX_MAX_K */
+  float *out;
+  int32_t out_layout;
+  int64_t n_out;    /* samples per channel of the result, >= 1 */
+} asx_mix_job;
+int asx_mixdown_batch_dev(asx_engine *e, const asx_mix_job *jobs, int32_t n_jobs, void *stream);
+int asx_mixdown(asx_engine *e, const float *const *x_host, const int32_t *layouts, const int64_t *n_samples, const float *weights, int32_t k,
+                float *out_host, int32_t out_layout, int64_t n_out);
+
 /* asx_invert_stem with every array in HBM: spec_utils.invert_stem(mix, stem * stem_scale).
  *   mix_dev      planar [2, n_samples], float32, only read
  *   stem_dev     planar [2, n_samples] (ASX_STEM_PLANAR) or rows [n_samples, 2] (ASX_STEM_ROWS, as asx_separate_dev leaves the primary

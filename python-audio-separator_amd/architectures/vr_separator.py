@@ -118,7 +118,14 @@ class VRSeparator(CommonSeparator):
     _PER_FILE = CommonSeparator._PER_FILE + ("wav_subtype", "input_audio_subtype")
 
     def _probe_vr_format(self, audio_file_path):
-        """vr_separator.py:115-156: the input's sample format for the writer."""
+        """vr_separator.py:115-156: the input's sample format for the writer.  A mix handed in through the door of CommonSeparator brings
+        what this probe would have found in its file."""
+        injected = self._injected_for(audio_file_path)
+        if injected is not None and "wav_subtype" in injected[1]:
+            state = injected[1]
+            self.wav_subtype, self.input_audio_subtype, self.input_bit_depth = state["wav_subtype"], state["input_audio_subtype"], state["input_bit_depth"]
+            self.input_subtype = None
+            return
         try:
             self.input_audio_subtype = audio_io.info(audio_file_path)["subtype"]
             if "24" in self.input_audio_subtype:
@@ -134,11 +141,14 @@ class VRSeparator(CommonSeparator):
         # PCM_16 / 24 / 32 from input_bit_depth (common_separator.py:390-402); keep that
         self.input_subtype = None
 
+    def _takes_device_mix(self) -> bool:
+        bands = self.model_params["band"]
+        return bands[len(bands)]["sr"] == self.sample_rate and self.model_samplerate == 44100
+
     def _device_decode(self, path):
         """Device-resident decode (RIFF/WAVE at the top band's rate, which is also the rate the stems are written at).  None
         when the file needs the host decoder.  A silent file is not refused: the reference's VR path has no such check."""
-        bands = self.model_params["band"]
-        if not (bands[len(bands)]["sr"] == self.sample_rate and self.model_samplerate == 44100):
+        if not self._takes_device_mix():
             return None
         # _device_mix records prepare_mix's fields; VR keeps its own (input_subtype None), so they are restored around it
         keep = (self.input_subtype, self.input_bit_depth)

@@ -396,6 +396,45 @@ class CommonSeparator:
         except Exception:
             return False
 
+    # ---- the door for a caller that already holds a file's mix in HBM (workflow.ChainSeparator) ------------------------------------------
+    # ``_inject_mix(path, mix, state, peak)`` makes the next ``_device_mix(path)`` -- which ``_load_mix`` / ``_device_decode`` and the
+    # MDXC plugin's own calls all end in -- return ``mix`` (CUDA tensor [2, N] at ``sample_rate``) and record ``state`` (the per-file
+    # attributes a decode of that file would have left) instead of opening the path; ``peak`` (max |mix|) feeds the silent-file refusal.
+    # An injection is used once.  Without one nothing here does anything.
+    _injected = None
+    # a listener on ``final_process`` and the device writers, set by the same caller for the span of a call: see ``_tap_stem``
+    _writer_tap = None
+
+    def _inject_mix(self, path, mix, state, peak):
+        if self._injected is None:
+            self._injected = {}
+        self._injected[path] = (mix, dict(state), float(peak))
+
+    def _injected_for(self, path):
+        return self._injected.get(path) if self._injected and isinstance(path, str) else None
+
+    def _takes_device_mix(self) -> bool:
+        """Hook: whether ``_device_decode`` hands a device-resident mix on at all (a plugin that sends some models to the host says no)."""
+        return True
+
+    def _take_injected(self, path, check_silent):
+        mix, state, peak = self._injected.pop(path)
+        for key, value in state.items():
+            setattr(self, key, value)
+        if check_silent and not peak > 0.0:
+            msg = f"Audio file {path} is empty or not valid"
+            self.logger.error(msg)
+            raise ValueError(msg)
+        return mix
+
+    def _tap_stem(self, dev_stem, layout, n, encoded, subtype, peak):
+        """The device writers, once per stem they take from HBM: the float stem (not normalised), the buffer its samples were encoded
+        into on the device (None where the hand-off has no use for it: the int32 containers of a soundfile FLAC) with the WAV subtype a
+        reader would decode it as, and the peak after normalisation."""
+        tap = self._writer_tap
+        if tap is not None:
+            tap.encoded(self, dev_stem, layout, n, encoded, subtype, peak)
+
     def _device_mix(self, path, check_silent=True):
         """prepare_mix for a RIFF/WAVE file at the model's rate WITHOUT a host float array: the data chunk is read into pinned
         memory, copied to HBM once and converted to the planar float32 mix [2, N] on the device (asx_pcm_decode_dev: the same
@@ -406,6 +445,8 @@ class CommonSeparator:
         prepare_mix.  Raises the reference's ValueError for a silent file (:268-271) unless ``check_silent`` is False: the VR
         plugin never calls prepare_mix (vr_separator.py:255-291 loads with librosa directly), so a silent file must come out the
         same whichever decode path it took (the writer's "nothing to write" branch handles silent stems)."""
+        if self._injected_for(path) is not None:
+            return self._take_injected(path, check_silent)
         if not self._fast_file_path_enabled() or not isinstance(path, str):
             return None
         import torch
@@ -745,7 +786,15 @@ class CommonSeparator:
     def final_process(self, stem_path, source, stem_name):
         """common_separator.py:167-174."""
         self.logger.debug(f"{stem_name}: writing {stem_path}")
-        self.write_audio(stem_path, source)
+        tap = self._writer_tap
+        if tap is None:
+            self.write_audio(stem_path, source)
+            return {stem_name: source}
+        tap.begin_stem(self, stem_name, stem_path, source)
+        try:
+            self.write_audio(stem_path, source)
+        finally:
+            tap.end_stem(self)
         return {stem_name: source}
 
     # ---- source cache (common_separator.py:176-215) -----------------------
@@ -1114,6 +1163,7 @@ class CommonSeparator:
             quantise = eng.pcm16_planar_dev if planar else eng.pcm16_rows_dev
             peak = quantise(dev_stem.data_ptr(), n, self.normalization_threshold, self.amplification_threshold,
                             pcm_dev.data_ptr(), stream=self._stream())
+            self._tap_stem(dev_stem, entry[3], n, pcm_dev, "PCM_16", peak)
             pcm = None
             if not flac_dev:                                  # (the FLAC encoder reads the int16 where it is)
                 pcm_host = torch.empty((n, 2), dtype=torch.int16, pin_memory=True)
@@ -1208,6 +1258,7 @@ class CommonSeparator:
             dev_body = torch.empty((n, 2), dtype=torch.int32, device=dev_stem.device)
         peak = eng.pcm_encode_dev(dev_stem.data_ptr(), n, layout, self.normalization_threshold, self.amplification_threshold, fmt,
                                   dev_body.data_ptr(), stream=self._stream())
+        self._tap_stem(dev_stem, layout, n, dev_body if file_format == "wav" else None, subtype, peak)
         # written (or silent): the device stem and its pinned mirror are released with this entry, as in write_audio_pydub
         self._dev_stems.pop(id(stem_source), None)
         if peak < 1e-6:

@@ -63,6 +63,7 @@ static void grant_lds(K *kernel, int bytes) { grant_lds(reinterpret_cast<const v
 #include "kernels_flac.h"
 #include "kernels_pcm_encode.h"
 #include "kernels_flac_dec.h"
+#include "kernels_mix.h"
 
 using namespace asx;
 
@@ -251,6 +252,7 @@ static void hd_destroy(HdNet *n);
 static void hd_drop_clones(asx_engine *e);
 static void vr_destroy(VrNet *n);
 static void ens_destroy(EnsCtx *c);
+static void mix_destroy(MixCtx *c);
 static void free_conv(ConvLayer &L) {
   L.w.release();
   L.b.release();
@@ -344,6 +346,7 @@ void asx_engine_destroy(asx_engine *e) {
   if (e->hd) hd_destroy(e->hd);
   if (e->vr) vr_destroy(e->vr);
   if (e->ens) ens_destroy(e->ens);
+  if (e->mix) mix_destroy(e->mix);
   delete e;
 }
 
@@ -541,6 +544,7 @@ double asx_net_flops(const asx_engine *e, int32_t batch) {
 #include "engine_resample.h"
 #include "engine_flac.h"
 #include "engine_flac_dec.h"
+#include "engine_mix.h"
 extern "C" {
 
 // ---- plan ------------------------------------------------------------------
@@ -3439,6 +3443,39 @@ int asx_ht_bag_finish_dev(asx_engine *e, const float *est_dev, const float *tota
                        standardize ? reinterpret_cast<const double *>(e->ht->ref_acc.p) : nullptr, standardize,
                        (flags & ASX_HT_SWAP01) ? 1 : 0, out_dev);
   });
+}
+
+// ---- weighted sums of stems (kernels_mix.h, engine_mix.h) ---------------------------------------------------------------------------
+int asx_mixdown_batch_dev(asx_engine *e, const asx_mix_job *jobs, int32_t n_jobs, void *stream) {
+  return mix_batch_dev(e, jobs, n_jobs, reinterpret_cast<hipStream_t>(stream));
+}
+
+int asx_mixdown(asx_engine *e, const float *const *x_host, const int32_t *layouts, const int64_t *n_samples, const float *weights, int32_t k,
+                float *out_host, int32_t out_layout, int64_t n_out) {
+  REQUIRE(x_host && layouts && n_samples && weights && out_host, "asx_mixdown: null argument");
+  REQUIRE(k >= 1 && k <= ASX_MIX_MAX_K, "asx_mixdown: %d sources (1 .. %d)", (int)k, ASX_MIX_MAX_K);
+  REQUIRE(n_out >= 1 && n_out <= ((int64_t)1 << 40), "asx_mixdown: n_out = %lld (1 .. 2^40)", (long long)n_out);
+  for (int i = 0; i < k; ++i) {
+    REQUIRE(n_samples[i] >= 0 && n_samples[i] <= ((int64_t)1 << 40), "asx_mixdown: source %d has n = %lld (0 .. 2^40)", i, (long long)n_samples[i]);
+    REQUIRE(x_host[i] || n_samples[i] == 0, "asx_mixdown: source %d is null with n = %lld", i, (long long)n_samples[i]);
+  }
+  REQUIRE(e, "asx_mixdown: null engine");
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dx[ASX_MIX_MAX_K], dout;
+  BufGuard g{{&dx[0], &dx[1], &dx[2], &dx[3], &dx[4], &dx[5], &dx[6], &dx[7], &dout}};
+  asx_mix_job job;
+  memset(&job, 0, sizeof(job));
+  for (int i = 0; i < k; ++i) {
+    if (n_samples[i] > 0) CHK(to_dev(dx[i], x_host[i], (size_t)2 * n_samples[i]));
+    job.src[i] = asx_mix_src{dx[i].f(), layouts[i], n_samples[i], weights[i]};
+  }
+  CHK(dout.ensure((size_t)2 * n_out * 4));
+  job.k = k;
+  job.out = dout.f();
+  job.out_layout = out_layout;
+  job.n_out = n_out;
+  CHK(mix_batch_dev(e, &job, 1, nullptr));
+  return to_host(out_host, dout, (size_t)2 * n_out);
 }
 
 int asx_set_option(asx_engine *e, const char *key, int32_t value) {

@@ -167,6 +167,7 @@ struct HtNet;
 struct HdNet;
 struct VrNet;
 struct EnsCtx;
+struct MixCtx;
 
 // split image of one weight matrix for the bf16 x 6 kernels (kernels_gemm3.h); owned by the engine (asx_engine::w3)
 struct W3Entry {
@@ -201,6 +202,7 @@ struct asx_engine {
   DevBuf hd_lstm_ws;
   VrNet *vr = nullptr;
   EnsCtx *ens = nullptr;
+  MixCtx *mix = nullptr;   // asx_mixdown_batch_dev's job table (engine_mix.h)
   asx_mdx_config cfg{};
   FftPlan plan{};
   DevBuf d_window, d_tw, d_env;  // env for T = segment_size

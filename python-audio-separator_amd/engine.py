@@ -284,7 +284,7 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_invert_stem_dev", "asx_invert_stem_batch_dev", "asx_op_gconv", "asx_op_dconv", "asx_resample_sinc_batch_dev",
            "asx_resample_rational_stem", "asx_resample_rational_stem_dev", "asx_op_stft", "asx_op_istft", "asx_op_ht_spec",
            "asx_op_ht_ispec", "asx_ensemble_batch_modes_dev", "asx_resample_rational_complement",
-           "asx_resample_rational_complement_dev", "asx_normalize_scale_dev"]
+           "asx_resample_rational_complement_dev", "asx_normalize_scale_dev", "asx_mixdown_batch_dev", "asx_mixdown"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -341,6 +341,17 @@ class _EnsJob(C.Structure):        # struct asx_ens_job
     _fields_ = [("k", C.c_int32), ("live", C.c_int32), ("stem_dev", C.c_void_p * ENS_MAX_K), ("n_samples", C.c_int64 * ENS_MAX_K),
                 ("layout", C.c_int32 * ENS_MAX_K), ("out_dev", C.c_void_p), ("out_capacity", C.c_int64), ("n_out", C.c_int64),
                 ("peak_after", C.c_float * ENS_MAX_K)]
+
+
+MIX_MAX_K = 8                      # ASX_MIX_MAX_K: sources of one mix-down job
+
+
+class _MixSrc(C.Structure):        # struct asx_mix_src
+    _fields_ = [("x", C.c_void_p), ("layout", C.c_int32), ("n", C.c_int64), ("w", C.c_float)]
+
+
+class _MixJob(C.Structure):        # struct asx_mix_job
+    _fields_ = [("src", _MixSrc * MIX_MAX_K), ("k", C.c_int32), ("out", C.c_void_p), ("out_layout", C.c_int32), ("n_out", C.c_int64)]
 
 
 class _InvertSong(C.Structure):    # struct asx_invert_song
@@ -473,6 +484,8 @@ def load_library():
     lib.asx_resample_rational_complement.argtypes = [vp, _FP, i32, i32, i64, i32, i32, _FP, i64, C.c_float, C.c_float, _FP, _FP, i64]
     lib.asx_resample_rational_complement_dev.argtypes = [vp, vp, i32, i32, i64, i32, i32, vp, i64, C.c_float, C.c_float, vp, vp, i64, vp]
     lib.asx_normalize_scale_dev.argtypes = [vp, vp, i64, C.c_float, C.c_float, i32, C.POINTER(C.c_float), vp]
+    lib.asx_mixdown_batch_dev.argtypes = [vp, C.POINTER(_MixJob), i32, vp]
+    lib.asx_mixdown.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(i64), C.POINTER(C.c_float), i32, _FP, i32, i64]
     lib.asx_flac_plan.argtypes = [i64, i32, i32, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
     lib.asx_flac_encode.argtypes = [vp, C.POINTER(C.c_int16), i64, i32, i32, i32, C.POINTER(C.c_uint8), i64, C.POINTER(i32), C.POINTER(i64)]
     lib.asx_flac_encode_dev.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, vp, C.POINTER(i64), vp]
@@ -1556,6 +1569,42 @@ class Engine:
                                                          float(silent_below), stream or None))
         return [(int(arr[j].n_out), int(arr[j].live), [float(arr[j].peak_after[c]) for c in range(min(arr[j].k, ENS_MAX_K))])
                 for j in range(len(jobs))]
+
+    def mixdown_batch_dev(self, jobs, stream: int = 0):
+        """asx_mixdown_batch_dev: weighted sums of device-resident stems, all jobs in one launch.  ``jobs``: a list of
+        ``(sources, out_ptr, out_layout, n_out)`` with ``sources`` = [(ptr, "planar" | "rows", n_samples, weight)], 1 .. 8 of them; ``out``
+        a device buffer of 2 * n_out floats.  Per sample acc = fl(w_0 x_0), acc = fl(acc + fl(w_k x_k)) in list order, float32, a source
+        shorter than n_out zero-extended.  Only enqueues work on ``stream``."""
+        jobs = list(jobs)
+        arr = (_MixJob * max(1, len(jobs)))()
+        for j, (sources, out_ptr, out_layout, n_out) in enumerate(jobs):
+            sources = list(sources)
+            if not 1 <= len(sources) <= MIX_MAX_K:
+                raise ValueError(f"a mix-down takes 1 .. {MIX_MAX_K} sources, not {len(sources)}")
+            arr[j].k = len(sources)
+            for k, (ptr, layout, n, w) in enumerate(sources):
+                arr[j].src[k].x, arr[j].src[k].layout, arr[j].src[k].n, arr[j].src[k].w = ptr or None, self.STEM_LAYOUTS[layout], int(n), float(w)
+            arr[j].out, arr[j].out_layout, arr[j].n_out = out_ptr or None, self.STEM_LAYOUTS[out_layout], int(n_out)
+        self._check(self._lib.asx_mixdown_batch_dev(self._h, arr, len(jobs), stream or None))
+
+    def mixdown(self, sources, n_out: int = None, out_layout: str = "planar") -> np.ndarray:
+        """asx_mixdown: one job of ``mixdown_batch_dev`` on host arrays.  ``sources``: [(float32 array [2, n] or [n, 2], "planar" | "rows",
+        weight)]; returns [2, n_out] or [n_out, 2] (``n_out``: the longest source unless given)."""
+        sources = [(np.ascontiguousarray(a, np.float32), layout, float(w)) for a, layout, w in sources]
+        if not 1 <= len(sources) <= MIX_MAX_K:
+            raise ValueError(f"a mix-down takes 1 .. {MIX_MAX_K} sources, not {len(sources)}")
+        for a, layout, _ in sources:
+            if a.ndim != 2 or a.shape[1 if layout == "rows" else 0] != 2:
+                raise ValueError(f"mixdown expects {'[n, 2]' if layout == 'rows' else '[2, n]'} sources, got {a.shape}")
+        ns = [a.shape[0 if layout == "rows" else 1] for a, layout, _ in sources]
+        n_out = max(ns) if n_out is None else int(n_out)
+        k = len(sources)
+        out = np.empty((n_out, 2) if out_layout == "rows" else (2, n_out), np.float32)
+        ptrs = (C.c_void_p * k)(*[a.ctypes.data if a.size else None for a, _, _ in sources])
+        self._check(self._lib.asx_mixdown(self._h, ptrs, (C.c_int32 * k)(*[self.STEM_LAYOUTS[layout] for _, layout, _ in sources]),
+                                          (C.c_int64 * k)(*ns), (C.c_float * k)(*[w for _, _, w in sources]), k, _ptr(out),
+                                          self.STEM_LAYOUTS[out_layout], n_out))
+        return out
 
     def invert_stem(self, mixture: np.ndarray, stem: np.ndarray) -> np.ndarray:
         """spec_utils.invert_stem(mixture [2, N], stem [2, N]) -> [N', 2]."""
