@@ -17,3 +17,4 @@ from .plugin import install, uninstall  # noqa: E402,F401
 from .common_separator import CommonSeparator  # noqa: E402,F401
 from .ensemble import EnsembleSeparator, Ensembler  # noqa: E402,F401
 from .workflow import ChainSeparator  # noqa: E402,F401
+from .phasefix import PhaseFixSeparator  # noqa: E402,F401

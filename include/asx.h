@@ -899,6 +899,43 @@ int asx_invert_stem_dev(asx_engine *e, const float *mix_dev, const float *stem_d
                         float *out_dev, int64_t out_capacity, int64_t *n_out, void *stream);
 int asx_invert_stem_batch_dev(asx_engine *e, asx_invert_song *songs, int32_t n_songs, float stem_scale, void *stream);
 
+/* Phase fix ("phase swapper"): the STFT magnitudes of a target stem on phases blended towards a source stem's, with every array in HBM.
+ * Per channel, with T and S the librosa STFTs (n_fft 2048, hop, periodic Hann, centred, zero padding, 1 + n / hop frames) of the target
+ * (n samples) and of the source zero-extended or cut to n, per frame and bin k with z = S conj(T):
+ *   delta = atan2(Im z, Re z)   (0 where z == 0);   O_k = T_k (cos(w_k delta) + j sin(w_k delta));   out = istft(O, length = n)
+ * -- the blend runs along the shorter arc from the target's phase to the source's: w = 0 keeps the target, w = 1 is |T| S / |S|, w > 1
+ * extrapolates.  Only the real parts of bins 0 and 1024 enter the inverse transform.  Im z = fl(S_i T_r) - fl(S_r T_i) without
+ * contraction, so source = -target gives delta = +pi in every bin.  A bin whose rotation angle w_k delta is zero is the target's, bit for bit.
+ *   bin_weights  host array of ASX_PHASE_BINS floats, w_k for bin k (frequency k * rate / 2048): the engine knows no cutoffs
+ *   hop          256, 512 or 1024
+ *   target_dev   planar [2, n] (ASX_STEM_PLANAR) or rows [n, 2] (ASX_STEM_ROWS), float32, 4-byte aligned, only read; n >= 1
+ *   source_dev   the same for its own n >= 0 (may be NULL where n == 0: a silent source, the result is the target's round trip)
+ *   out_dev      planar [2, n] or rows [n, 2], n the target's; must not share a byte with any input or other output of the call (the
+ *                source may be the target)
+ * asx_phase_fix_batch_dev serves all jobs with ONE launch per stage (frames, fold) and only enqueues work on `stream` (it waits for the
+ * previous phase-fix call's launches on this engine before it reuses its tables, and for nothing of its own).  The workspace is
+ * 2 * T * 2048 floats per job.  Every job's result is bit for bit that of asx_phase_fix_dev for that job alone (the single form: the same
+ * device functions, the job passed by value).  Every argument of every job is checked before anything is enqueued (ASX_ERR_INVALID +
+ * asx_last_error(): null or misaligned pointers, unknown layouts, a weight that is not finite, an unknown hop, n outside 1 .. 2^38, a
+ * source n outside 0 .. 2^38, more than ASX_ENS_MAX_JOBS jobs, an output that overlaps an input or another output); n_jobs == 0 does
+ * nothing.  asx_phase_fix: one job on host arrays (upload, the same launches, download).  Additive within ABI 8. */
+#define ASX_PHASE_BINS 1025
+typedef struct asx_phase_job {
+  const float *target_dev;
+  const float *source_dev;
+  float *out_dev;
+  int64_t n_samples;          /* of the target and of the result, >= 1 */
+  int64_t source_n_samples;   /* >= 0 */
+  int32_t target_layout;      /* ASX_STEM_PLANAR / ASX_STEM_ROWS */
+  int32_t source_layout;
+  int32_t out_layout;
+  int32_t reserved;           /* ignored */
+} asx_phase_job;
+int asx_phase_fix_batch_dev(asx_engine *e, const asx_phase_job *jobs, int32_t n_jobs, const float *bin_weights, int32_t hop, void *stream);
+int asx_phase_fix_dev(asx_engine *e, const asx_phase_job *job, const float *bin_weights, int32_t hop, void *stream);
+int asx_phase_fix(asx_engine *e, const float *target_host, int32_t target_layout, int64_t n_samples, const float *source_host,
+                  int32_t source_layout, int64_t source_n_samples, const float *bin_weights, int32_t hop, float *out_host, int32_t out_layout);
+
 /* Launch counters of this process (tests use them to prove which kernel family ran; ABI 6 -- until ABI 5 they travelled through a
  * float of asx_debug_fetch, which stops resolving single launches past 2^24): "tdf3_launches" (split-operand row GEMM, either arithmetic),
  * "tdf3h_launches" (those of them, plain or GATHER mode, that ran the fp16 x 3 arithmetic),
@@ -917,7 +954,8 @@ int asx_invert_stem_batch_dev(asx_engine *e, asx_invert_song *songs, int32_t n_s
  * fewer of them than a loop of asx_vr_separate_dev over the same songs),
  * "v3_net_passes" / "rof_net_passes" (ABI 7, additive: passes of the TFC-TDF v3 net / of the Roformer net on a batch of chunks, single-song calls
  * included -- asx_mdxc_demix_batch_dev / asx_rof_demix_batch_dev run fewer of them than a loop of the single-song call over the same songs),
- * "tdf3_pair_image_launches" (ABI 7: the tdf3_kernel launches that read their x operand as a pair image -- option "gemm_pair_images", experimental builds).
+ * "tdf3_pair_image_launches" (ABI 7: the tdf3_kernel launches that read their x operand as a pair image -- option "gemm_pair_images", experimental builds),
+ * "phasefix_launches" (additive within ABI 8: launches of the phase-fix kernels, two -- frames and fold -- per call of either form).
  * ASX_ERR_INVALID for an unknown name. */
 int asx_counter(const asx_engine *e, const char *name, int64_t *out);
 

@@ -64,6 +64,7 @@ static void grant_lds(K *kernel, int bytes) { grant_lds(reinterpret_cast<const v
 #include "kernels_pcm_encode.h"
 #include "kernels_flac_dec.h"
 #include "kernels_mix.h"
+#include "kernels_phasefix.h"
 
 using namespace asx;
 
@@ -253,6 +254,7 @@ static void hd_drop_clones(asx_engine *e);
 static void vr_destroy(VrNet *n);
 static void ens_destroy(EnsCtx *c);
 static void mix_destroy(MixCtx *c);
+static void phase_destroy(PhaseCtx *c);
 static void free_conv(ConvLayer &L) {
   L.w.release();
   L.b.release();
@@ -347,6 +349,7 @@ void asx_engine_destroy(asx_engine *e) {
   if (e->vr) vr_destroy(e->vr);
   if (e->ens) ens_destroy(e->ens);
   if (e->mix) mix_destroy(e->mix);
+  if (e->phase) phase_destroy(e->phase);
   delete e;
 }
 
@@ -545,6 +548,7 @@ double asx_net_flops(const asx_engine *e, int32_t batch) {
 #include "engine_flac.h"
 #include "engine_flac_dec.h"
 #include "engine_mix.h"
+#include "engine_phasefix.h"
 extern "C" {
 
 // ---- plan ------------------------------------------------------------------
@@ -3221,6 +3225,7 @@ int asx_counter(const asx_engine *e, const char *name, int64_t *out) {
   else if (nm == "vr_net_passes") *out = (int64_t)g_vr_net_passes.load();
   else if (nm == "v3_net_passes") *out = (int64_t)g_v3_net_passes.load();
   else if (nm == "rof_net_passes") *out = (int64_t)g_rof_net_passes.load();
+  else if (nm == "phasefix_launches") *out = (int64_t)g_phasefix_launches.load();
   else if (nm == "flac_block_cycles") *out = (int64_t)e->flac_block_cycles;
   else if (nm == "flac_crc16_cycles") *out = (int64_t)e->flac_crc16_cycles;
   else {
@@ -3476,6 +3481,43 @@ int asx_mixdown(asx_engine *e, const float *const *x_host, const int32_t *layout
   job.n_out = n_out;
   CHK(mix_batch_dev(e, &job, 1, nullptr));
   return to_host(out_host, dout, (size_t)2 * n_out);
+}
+
+// ---- phase fix: a target stem's magnitudes on phases blended towards a source stem's (kernels_phasefix.h, engine_phasefix.h) ---------
+int asx_phase_fix_batch_dev(asx_engine *e, const asx_phase_job *jobs, int32_t n_jobs, const float *bin_weights, int32_t hop, void *stream) {
+  return phase_fix_batch_dev(e, "asx_phase_fix_batch_dev", jobs, n_jobs, bin_weights, (int)hop, false, reinterpret_cast<hipStream_t>(stream));
+}
+
+int asx_phase_fix_dev(asx_engine *e, const asx_phase_job *job, const float *bin_weights, int32_t hop, void *stream) {
+  REQUIRE(job, "asx_phase_fix_dev: null job");
+  return phase_fix_batch_dev(e, "asx_phase_fix_dev", job, 1, bin_weights, (int)hop, true, reinterpret_cast<hipStream_t>(stream));
+}
+
+int asx_phase_fix(asx_engine *e, const float *target_host, int32_t target_layout, int64_t n_samples, const float *source_host, int32_t source_layout,
+                  int64_t source_n_samples, const float *bin_weights, int32_t hop, float *out_host, int32_t out_layout) {
+  REQUIRE(target_host && out_host, "asx_phase_fix: null target or output");
+  REQUIRE(n_samples >= 1 && n_samples <= ((int64_t)1 << 38), "asx_phase_fix: n_samples %lld (1 .. 2^38)", (long long)n_samples);
+  REQUIRE(source_n_samples >= 0 && source_n_samples <= ((int64_t)1 << 38), "asx_phase_fix: source_n_samples %lld (0 .. 2^38)", (long long)source_n_samples);
+  REQUIRE(source_host || source_n_samples == 0, "asx_phase_fix: the source is null with n = %lld", (long long)source_n_samples);
+  REQUIRE(e, "asx_phase_fix: null engine");
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dt, ds, dout;
+  BufGuard g{{&dt, &ds, &dout}};
+  CHK(to_dev(dt, target_host, (size_t)2 * n_samples));
+  if (source_n_samples > 0) CHK(to_dev(ds, source_host, (size_t)2 * source_n_samples));
+  CHK(dout.ensure((size_t)2 * n_samples * 4));
+  asx_phase_job job;
+  memset(&job, 0, sizeof(job));
+  job.target_dev = dt.f();
+  job.target_layout = target_layout;
+  job.n_samples = n_samples;
+  job.source_dev = ds.f();
+  job.source_layout = source_layout;
+  job.source_n_samples = source_n_samples;
+  job.out_dev = dout.f();
+  job.out_layout = out_layout;
+  CHK(phase_fix_batch_dev(e, "asx_phase_fix", &job, 1, bin_weights, (int)hop, true, nullptr));
+  return to_host(out_host, dout, (size_t)2 * n_samples);
 }
 
 int asx_set_option(asx_engine *e, const char *key, int32_t value) {

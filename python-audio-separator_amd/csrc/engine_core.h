@@ -168,6 +168,7 @@ struct HdNet;
 struct VrNet;
 struct EnsCtx;
 struct MixCtx;
+struct PhaseCtx;
 
 // split image of one weight matrix for the bf16 x 6 kernels (kernels_gemm3.h); owned by the engine (asx_engine::w3)
 struct W3Entry {
@@ -203,6 +204,7 @@ struct asx_engine {
   VrNet *vr = nullptr;
   EnsCtx *ens = nullptr;
   MixCtx *mix = nullptr;   // asx_mixdown_batch_dev's job table (engine_mix.h)
+  PhaseCtx *phase = nullptr;   // asx_phase_fix_batch_dev's weight and job tables (engine_phasefix.h)
   asx_mdx_config cfg{};
   FftPlan plan{};
   DevBuf d_window, d_tw, d_env;  // env for T = segment_size

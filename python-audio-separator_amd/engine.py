@@ -284,7 +284,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_invert_stem_dev", "asx_invert_stem_batch_dev", "asx_op_gconv", "asx_op_dconv", "asx_resample_sinc_batch_dev",
            "asx_resample_rational_stem", "asx_resample_rational_stem_dev", "asx_op_stft", "asx_op_istft", "asx_op_ht_spec",
            "asx_op_ht_ispec", "asx_ensemble_batch_modes_dev", "asx_resample_rational_complement",
-           "asx_resample_rational_complement_dev", "asx_normalize_scale_dev", "asx_mixdown_batch_dev", "asx_mixdown"]
+           "asx_resample_rational_complement_dev", "asx_normalize_scale_dev", "asx_mixdown_batch_dev", "asx_mixdown",
+           "asx_phase_fix_batch_dev", "asx_phase_fix_dev", "asx_phase_fix"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -352,6 +353,16 @@ class _MixSrc(C.Structure):        # struct asx_mix_src
 
 class _MixJob(C.Structure):        # struct asx_mix_job
     _fields_ = [("src", _MixSrc * MIX_MAX_K), ("k", C.c_int32), ("out", C.c_void_p), ("out_layout", C.c_int32), ("n_out", C.c_int64)]
+
+
+PHASE_BINS = 1025                  # ASX_PHASE_BINS: bins of the phase fix's STFT (n_fft 2048), one weight each
+PHASE_HOPS = (256, 512, 1024)
+
+
+class _PhaseJob(C.Structure):      # struct asx_phase_job
+    _fields_ = [("target_dev", C.c_void_p), ("source_dev", C.c_void_p), ("out_dev", C.c_void_p), ("n_samples", C.c_int64),
+                ("source_n_samples", C.c_int64), ("target_layout", C.c_int32), ("source_layout", C.c_int32), ("out_layout", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class _InvertSong(C.Structure):    # struct asx_invert_song
@@ -486,6 +497,9 @@ def load_library():
     lib.asx_normalize_scale_dev.argtypes = [vp, vp, i64, C.c_float, C.c_float, i32, C.POINTER(C.c_float), vp]
     lib.asx_mixdown_batch_dev.argtypes = [vp, C.POINTER(_MixJob), i32, vp]
     lib.asx_mixdown.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(i64), C.POINTER(C.c_float), i32, _FP, i32, i64]
+    lib.asx_phase_fix_batch_dev.argtypes = [vp, C.POINTER(_PhaseJob), i32, _FP, i32, vp]
+    lib.asx_phase_fix_dev.argtypes = [vp, C.POINTER(_PhaseJob), _FP, i32, vp]
+    lib.asx_phase_fix.argtypes = [vp, _FP, i32, i64, _FP, i32, i64, _FP, i32, _FP, i32]
     lib.asx_flac_plan.argtypes = [i64, i32, i32, i32, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)]
     lib.asx_flac_encode.argtypes = [vp, C.POINTER(C.c_int16), i64, i32, i32, i32, C.POINTER(C.c_uint8), i64, C.POINTER(i32), C.POINTER(i64)]
     lib.asx_flac_encode_dev.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, vp, C.POINTER(i64), vp]
@@ -1604,6 +1618,56 @@ class Engine:
         self._check(self._lib.asx_mixdown(self._h, ptrs, (C.c_int32 * k)(*[self.STEM_LAYOUTS[layout] for _, layout, _ in sources]),
                                           (C.c_int64 * k)(*ns), (C.c_float * k)(*[w for _, _, w in sources]), k, _ptr(out),
                                           self.STEM_LAYOUTS[out_layout], n_out))
+        return out
+
+    @staticmethod
+    def _phase_weights(bin_weights) -> np.ndarray:
+        w = np.ascontiguousarray(bin_weights, np.float32)
+        if w.shape != (PHASE_BINS,):
+            raise ValueError(f"the phase fix takes one weight per bin, {PHASE_BINS} of them, not an array of shape {w.shape}")
+        return w
+
+    def _phase_job(self, job) -> _PhaseJob:
+        (t_ptr, t_layout, n), (s_ptr, s_layout, n_src), (o_ptr, o_layout) = job
+        return _PhaseJob(t_ptr or None, s_ptr or None, o_ptr or None, int(n), int(n_src), self.STEM_LAYOUTS[t_layout], self.STEM_LAYOUTS[s_layout],
+                         self.STEM_LAYOUTS[o_layout], 0)
+
+    def phase_fix_batch_dev(self, jobs, bin_weights, hop: int = 512, stream: int = 0):
+        """asx_phase_fix_batch_dev: the STFT magnitudes of a target stem on phases blended towards a source stem's, device-resident stems,
+        one launch per stage over all jobs.  ``jobs``: a list of ``((target_ptr, layout, n), (source_ptr, layout, n_source), (out_ptr,
+        layout))``, layouts "planar" [2, n] or "rows" [n, 2]; the source is zero-extended or cut to the target's ``n``, ``out`` holds
+        2 * n floats.  ``bin_weights``: 1025 float32, the blend per bin of the 2048-point STFT (phasefix.bin_weights).  Only enqueues work
+        on ``stream``."""
+        jobs = list(jobs)
+        w = self._phase_weights(bin_weights)
+        arr = (_PhaseJob * max(1, len(jobs)))()
+        for j, job in enumerate(jobs):
+            arr[j] = self._phase_job(job)
+        self._check(self._lib.asx_phase_fix_batch_dev(self._h, arr, len(jobs), _ptr(w), int(hop), stream or None))
+
+    def phase_fix_dev(self, target, source, out, bin_weights, hop: int = 512, stream: int = 0):
+        """asx_phase_fix_dev: one job of ``phase_fix_batch_dev`` -- ``target`` = (ptr, layout, n), ``source`` = (ptr, layout, n_source),
+        ``out`` = (ptr, layout) -- passed by value to the same device functions: the same bits."""
+        w = self._phase_weights(bin_weights)
+        job = self._phase_job((target, source, out))
+        self._check(self._lib.asx_phase_fix_dev(self._h, C.byref(job), _ptr(w), int(hop), stream or None))
+
+    def phase_fix(self, target, source, bin_weights, hop: int = 512, target_layout: str = "rows", source_layout: str = "rows",
+                  out_layout: str = "rows") -> np.ndarray:
+        """asx_phase_fix: one job on host arrays (upload, the same launches, download).  ``target`` / ``source``: float32 [n, 2] ("rows") or
+        [2, n] ("planar"); returns the result in ``out_layout`` with the target's length."""
+        w = self._phase_weights(bin_weights)
+        arrays = []
+        for a, layout, what in ((target, target_layout, "target"), (source, source_layout, "source")):
+            a = np.ascontiguousarray(a, np.float32)
+            if a.ndim != 2 or a.shape[1 if layout == "rows" else 0] != 2:
+                raise ValueError(f"phase_fix expects a {'[n, 2]' if layout == 'rows' else '[2, n]'} {what}, got {a.shape}")
+            arrays.append((a, a.shape[0 if layout == "rows" else 1]))
+        (t, n), (s, n_src) = arrays
+        out = np.empty((n, 2) if out_layout == "rows" else (2, n), np.float32)
+        self._check(self._lib.asx_phase_fix(self._h, _ptr(t) if n else None, self.STEM_LAYOUTS[target_layout], n, _ptr(s) if n_src else None,
+                                            self.STEM_LAYOUTS[source_layout], n_src, _ptr(w), int(hop), _ptr(out) if n else None,
+                                            self.STEM_LAYOUTS[out_layout]))
         return out
 
     def invert_stem(self, mixture: np.ndarray, stem: np.ndarray) -> np.ndarray:

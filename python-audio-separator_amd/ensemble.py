@@ -107,6 +107,69 @@ def effective_weights(weights, k: int, logger=None):
     return w
 
 
+def file_rate_of(member, path):
+    """(sample rate, frames) of the file ``member`` has just loaded -- what its decoder recorded, or the file's own header where it
+    recorded nothing; (None, None) when neither is known (a writer handed that as its ``_output_rate_override`` warns once and writes
+    at the model's rate)."""
+    rate, frames = getattr(member, "_file_rate", None), getattr(member, "_file_frames", None)
+    if rate and frames:
+        return rate, frames
+    try:
+        info = audio_io.wav_info(path)
+        return info["samplerate"], info["frames"]
+    except Exception:
+        try:
+            info = audio_io.flac_stream(path)
+            return (info["samplerate"], info["total_samples"]) if info["total_samples"] > 0 else (None, None)
+        except Exception:
+            return None, None
+
+
+def stems_per_file(member):
+    """Stems ``member`` keeps per file, for the memory estimate of a pooled run (an upper bound where the model decides)."""
+    if hasattr(member, "demucs_source_map") or hasattr(member, "demucs_model_instance"):
+        return 6
+    instruments = ((getattr(member, "model_data", None) or {}).get("training") or {}).get("instruments") or []
+    return len(instruments) if getattr(member, "process_all_stems", False) and len(instruments) > 2 else 2
+
+
+def free_hbm(device):
+    try:
+        import torch
+        return torch.cuda.mem_get_info(device)[0]
+    except Exception:        # no device query: one run, an allocation failure is reported where it happens
+        return None
+
+
+def pooled_runs(paths, pool_files, free, per_frame, share):
+    """``paths`` as consecutive runs of indices, in order -- the files one pooled call of resident members serves (EnsembleSeparator,
+    PhaseFixSeparator).  ``pool_files`` set: that many per run.  Else a run's estimated stem bytes -- frames (audio_io.wav_info, or a
+    FLAC stream's total_samples) x ``per_frame`` bytes -- stay within ``share`` of the free HBM (``free()``; None: one run); a run of
+    one file is always allowed."""
+    if not paths:
+        return []
+    if pool_files is not None:
+        return [list(range(i, min(i + pool_files, len(paths)))) for i in range(0, len(paths), pool_files)]
+    free = free()
+    if free is None:
+        return [list(range(len(paths)))]
+    runs, used = [[]], 0
+    for i, path in enumerate(paths):
+        try:
+            cost = audio_io.wav_info(path)["frames"] * per_frame
+        except Exception:    # not a RIFF/WAVE file: a FLAC stream by STREAMINFO's sample count where it gives one; anything else takes the
+            try:             # file path or fails, no stems are kept for it
+                cost = audio_io.flac_stream(path)["total_samples"] * per_frame
+            except Exception:
+                cost = 0
+        if runs[-1] and used + cost > share * free:
+            runs.append([])
+            used = 0
+        runs[-1].append(i)
+        used += cost
+    return runs
+
+
 class EnsembleSeparator:
     ALGORITHMS = ("avg_wave", "median_wave", "min_wave", "max_wave", "avg_fft", "median_fft", "min_fft", "max_fft",
                   "uvr_max_spec", "uvr_min_spec", "ensemble_wav")
@@ -201,23 +264,8 @@ class EnsembleSeparator:
         return os.path.join(self.output_dir, output_path) if self.output_dir else output_path
 
     def _file_rate_of(self, member, path):
-        """Under ``output_rate`` = "input": (sample rate, frames) of the file ``member`` has just loaded -- what its decoder recorded,
-        or the file's own header where it recorded nothing; (None, None) when neither is known (the writer then warns once and
-        writes at the model's rate).  None under "model": no override."""
-        if self.output_rate != "input":
-            return None
-        rate, frames = getattr(member, "_file_rate", None), getattr(member, "_file_frames", None)
-        if rate and frames:
-            return rate, frames
-        try:
-            info = audio_io.wav_info(path)
-            return info["samplerate"], info["frames"]
-        except Exception:
-            try:
-                info = audio_io.flac_stream(path)
-                return (info["samplerate"], info["total_samples"]) if info["total_samples"] > 0 else (None, None)
-            except Exception:
-                return None, None
+        """Under ``output_rate`` = "input": ``file_rate_of(member, path)``.  None under "model": no override."""
+        return file_rate_of(member, path) if self.output_rate == "input" else None
 
     def _slot_mode(self, member):
         """(slot mode, None) of the stems ``member`` produced for the file it has just loaded -- ``Engine.SLOT_MODES``' name of the round
@@ -384,46 +432,14 @@ class EnsembleSeparator:
     HBM_SHARE = 0.4          # of the HBM free at the start of separate_many: what the stems of one run may take (estimated)
 
     def _stems_per_file(self, member):
-        """Stems ``member`` keeps per file, for the memory estimate (an upper bound where the model decides)."""
-        if hasattr(member, "demucs_source_map") or hasattr(member, "demucs_model_instance"):
-            return 6
-        instruments = ((getattr(member, "model_data", None) or {}).get("training") or {}).get("instruments") or []
-        return len(instruments) if getattr(member, "process_all_stems", False) and len(instruments) > 2 else 2
+        return stems_per_file(member)
 
     def _free_hbm(self):
-        try:
-            import torch
-            return torch.cuda.mem_get_info(self.members[-1].engine.device)[0]
-        except Exception:        # no device query: one run, an allocation failure is reported where it happens
-            return None
+        return free_hbm(self.members[-1].engine.device)
 
     def _runs(self, paths):
-        """``paths`` as consecutive runs of indices, in order.  ``pool_files`` set: that many per run.  Else a run's estimated stem
-        bytes -- frames (audio_io.wav_info, or a FLAC stream's total_samples) x 8 bytes x stems of all members -- stay within ``HBM_SHARE`` of the free HBM; a run of
-        one file is always allowed."""
-        if not paths:
-            return []
-        if self.pool_files is not None:
-            return [list(range(i, min(i + self.pool_files, len(paths)))) for i in range(0, len(paths), self.pool_files)]
-        free = self._free_hbm()
-        if free is None:
-            return [list(range(len(paths)))]
-        per_frame = 8 * sum(self._stems_per_file(m) for m in self.members)
-        runs, used = [[]], 0
-        for i, path in enumerate(paths):
-            try:
-                cost = audio_io.wav_info(path)["frames"] * per_frame
-            except Exception:    # not a RIFF/WAVE file: a FLAC stream by STREAMINFO's sample count where it gives one; anything else takes the
-                try:             # file path or fails, no stems are kept for it
-                    cost = audio_io.flac_stream(path)["total_samples"] * per_frame
-                except Exception:
-                    cost = 0
-            if runs[-1] and used + cost > self.HBM_SHARE * free:
-                runs.append([])
-                used = 0
-            runs[-1].append(i)
-            used += cost
-        return runs
+        """``pooled_runs`` over the stems of all members."""
+        return pooled_runs(paths, self.pool_files, self._free_hbm, 8 * sum(self._stems_per_file(m) for m in self.members), self.HBM_SHARE)
 
     def separate_many(self, paths, custom_output_names=None):
         """``separate`` for a list of files with every member making ONE pooled call for all of them (``stems_dev_many``: the
