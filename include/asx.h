@@ -1143,6 +1143,45 @@ int asx_op_istft(asx_engine *e, const asx_stft_desc *d, const float *spec_host, 
 int asx_op_ht_spec(asx_engine *e, int32_t nfft, const float *seg_host, int32_t b, int64_t l, int64_t el, int64_t lv, float *spec_host);
 int asx_op_ht_ispec(asx_engine *e, int32_t nfft, const float *x_host, int32_t b, int32_t t, int32_t s, const double *acc_f, double n_stat,
                     const float *xt_host, const double *acc_t, int64_t l, float *out_host);
+/* (ABI 8) Single launches of the normalisation and statistics kernels, through the engines' own launch helpers -- single-op test hooks
+ * like asx_op_dconv / asx_op_stft: host buffers in and out; the output buffer is uploaded first, so elements the launch does not own
+ * keep their contents; no network needs to be loaded; arguments the launch code would not take are ASX_ERR_INVALID, never a launch.
+ *
+ * asx_op_rownorm: one row normalisation over x_host [m, lda], by kind:
+ *   "rms"         rof_rmsnorm (csrc/engine_rof.h): y_host [m, ldy] = x / max(||x||, 1e-12) sqrt(d) gamma_host [d] on the first d columns.
+ *                 in_place: one device buffer, uploaded from x_host, is both x and y (lda == ldy); y_host receives it.
+ *   "rms_factor"  rof_rownorm: y_host [m] = sqrt(d) / max(||x||, 1e-12); gamma_host, ldy unused.
+ *   "layer"       ht_ln (csrc/engine_ht.h): LayerNorm(d), eps 1e-5, gamma_host / beta_host [d], dense rows (lda == ldy == d), plus
+ *                 pos_host [pos_mod, d] read at row % pos_mod when not NULL. */
+int asx_op_rownorm(asx_engine *e, const char *kind, const float *x_host, int64_t m, int32_t d, int64_t lda, const float *gamma_host,
+                   const float *beta_host, const float *pos_host, int64_t pos_mod, int32_t in_place, float *y_host, int64_t ldy);
+/* asx_op_group_stats: ht_stats (csrc/engine_ht.h) with its own arguments.  x_host [g1, r, p]; plane element i belongs to group
+ * i / gdiv of g2 and counts when i % ld < cn; acc_host [g1, g2, 2] receives the float64 (sum, sum of squares) pairs.  Shapes that need
+ * more than the kernel's 66 group slots per workgroup are refused. */
+int asx_op_group_stats(asx_engine *e, const float *x_host, int32_t g1, int64_t r, int64_t p, int64_t gdiv, int32_t ld, int32_t cn,
+                       int32_t g2, double *acc_host);
+/* asx_op_group_norm: statistics + apply as the nets launch them, by family (fields of the descriptor a family does not name are ignored):
+ *   "ht"       ht_stats + ht_gn mode 2, the HTDemucs norm_out: GroupNorm(1, c) per item over x_host [b, r, c] -> y_host [b, r, c].
+ *   "hd"       the core of hd_group_norm (csrc/engine_hd.h): GroupNorm(g, c) over x_host [b, rin, c] (rin = 0: rin = r), y_host
+ *              [b, r, ce] = rows [r0, r0 + r); mode 0 gelu(norm) / 1 GLU over channel halves (ce = c / 2) / 2 norm; aux_host
+ *              [b, r, ce] (optional): the skip added last.  in_place (mode 0 / 2, rin = r): one device buffer is x and y.
+ *   "std"      ht_stats + std_norm_kernel: x_host [b, r, c] (r frames of c = 4 F floats) -> (x - mean) / (1e-5 + std), unbiased.
+ *   "time"     ht_stats + time_norm_kernel: x_host [b, 2, p] -> y_host [b, p, 2], same formula over the 2 p samples of an item.
+ *   "hd_time"  ht_stats + hd_time_norm_kernel: y_host [b, p rounded up to even, 2], the pad sample zero.
+ *   "v3"       the core of v3_norm_act (csrc/engine_v3.h): norm as asx_v3_config.norm, act 0 relu / 1 gelu / 2 elu(alpha); the input is
+ *              the view of channels [c0, c0 + c) of x_host [b, ctot, p]; y_host [b, c, p]; gamma_host / beta_host [c] (BatchNorm: the
+ *              folded scale / shift; None: unused); stats_host [b, c, 2] (optional) receives the (mean, rstd) table.
+ *   "mdx"      gn_launch (csrc/engine_mdx.h): GroupNorm(2, c) + ReLU over x_host [b, c, p], then + aux_host, then * mul_host (both
+ *              optional, [b, c, p]); in_place: one device buffer is x and y. */
+typedef struct asx_group_norm_desc {
+  int32_t b, c, g, mode;
+  int32_t norm, act, ctot, c0;
+  int32_t in_place;
+  float alpha;
+  int64_t r, rin, r0, p;
+} asx_group_norm_desc;
+int asx_op_group_norm(asx_engine *e, const char *family, const asx_group_norm_desc *d, const float *x_host, const float *gamma_host,
+                      const float *beta_host, const float *aux_host, const float *mul_host, float *y_host, float *stats_host);
 
 /* ---- options ------------------------------------------------------------ */
 /* Engine options.  Each engine takes its defaults from the environment variable named beside the option when it is created (values go

@@ -296,6 +296,7 @@ void asx_engine_destroy(asx_engine *e) {
   }
   if (e->div_ev) (void)hipEventDestroy(e->div_ev);
   e->sinc_tab.release();
+  e->gstats_part.release();
   e->sinc_jobs.release();
   e->flac_frames.release();
   e->flac_cycles.release();
@@ -2341,6 +2342,188 @@ int asx_op_ht_ispec(asx_engine *e, int32_t nfft, const float *x_host, int32_t B,
                            reinterpret_cast<const double *>(dat.p), L, dout.f(), nullptr);
   if (rc == ASX_OK) rc = to_host(out_host, dout, no);
   else (void)hipDeviceSynchronize();
+  return rc;
+}
+
+// ---- single normalisation / statistics launches ------------------------------------------
+static const int64_t OP_NORM_MAX = 1ll << 28;   // floats of the largest tensor a single-op case may hold
+
+// after the launch helpers returned rc: a launch error becomes ASX_ERR_HIP, and a failed case leaves nothing in flight
+static int op_norm_done(int rc, const char *what) {
+  if (rc == ASX_OK && hipGetLastError() != hipSuccess) {
+    set_err("%s: launch failed", what);
+    rc = ASX_ERR_HIP;
+  }
+  if (rc != ASX_OK) (void)hipDeviceSynchronize();
+  return rc;
+}
+
+int asx_op_rownorm(asx_engine *e, const char *kind, const float *x_host, int64_t M, int32_t d, int64_t lda, const float *gamma_host,
+                   const float *beta_host, const float *pos_host, int64_t pos_mod, int32_t in_place, float *y_host, int64_t ldy) {
+  REQUIRE(e && kind && x_host && y_host, "asx_op_rownorm: null argument");
+  const bool rms = strcmp(kind, "rms") == 0, fac = strcmp(kind, "rms_factor") == 0, ln = strcmp(kind, "layer") == 0;
+  REQUIRE(rms || fac || ln, "asx_op_rownorm: unknown kind '%s'", kind);
+  REQUIRE(M > 0 && d > 0 && lda >= d && M < OP_NORM_MAX && lda < OP_NORM_MAX && M * lda < OP_NORM_MAX,
+          "asx_op_rownorm: m %lld rows of d %d floats in lda %lld", (long long)M, d, (long long)lda);
+  if (rms)
+    REQUIRE(gamma_host && ldy >= d && ldy < OP_NORM_MAX && M * ldy < OP_NORM_MAX && (!in_place || lda == ldy),
+            "asx_op_rownorm(rms): gamma, ldy %lld >= d %d, and lda == ldy in place", (long long)ldy, d);
+  if (fac) REQUIRE(!in_place, "asx_op_rownorm(rms_factor): the factors have a buffer of their own");
+  if (ln)
+    REQUIRE(gamma_host && beta_host && lda == d && ldy == d && !in_place && (!pos_host || (pos_mod >= 1 && pos_mod * d < OP_NORM_MAX)),
+            "asx_op_rownorm(layer): gamma, beta, dense rows (lda %lld, ldy %lld, d %d), pos_mod %lld", (long long)lda, (long long)ldy, d,
+            (long long)pos_mod);
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dx, dy, dg, db, dp;
+  BufGuard guard{{&dx, &dy, &dg, &db, &dp}};
+  const size_t ny = fac ? (size_t)M : (size_t)(M * ldy);
+  CHK(to_dev(dx, x_host, (size_t)(M * lda)));
+  if (!fac) CHK(to_dev(dg, gamma_host, (size_t)d));
+  if (ln) CHK(to_dev(db, beta_host, (size_t)d));
+  if (ln && pos_host) CHK(to_dev(dp, pos_host, (size_t)(pos_mod * d)));
+  if (!in_place) CHK(to_dev(dy, y_host, ny));
+  DevBuf &out = in_place ? dx : dy;
+  int rc;
+  if (rms) rc = rof_rmsnorm(e, dx.f(), lda, d, dg.f(), out.f(), ldy, M, nullptr);
+  else if (fac) rc = rof_rownorm(e, dx.f(), lda, d, out.f(), M, nullptr);
+  else rc = ht_ln(e, dx.f(), d, dg, db, pos_host ? dp.f() : nullptr, pos_host ? pos_mod : 1, out.f(), M, nullptr);
+  rc = op_norm_done(rc, "asx_op_rownorm");
+  if (rc == ASX_OK) rc = to_host(y_host, out, ny);
+  return rc;
+}
+
+static int op_acc_to_host(double *h, const DevBuf &d, size_t pairs) {
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(h, d.p, pairs * 16, hipMemcpyDeviceToHost));
+  return ASX_OK;
+}
+
+int asx_op_group_stats(asx_engine *e, const float *x_host, int32_t G1, int64_t R, int64_t P, int64_t gdiv, int32_t ld, int32_t Cn,
+                       int32_t G2, double *acc_host) {
+  REQUIRE(e && x_host && acc_host, "asx_op_group_stats: null argument");
+  REQUIRE(G1 > 0 && R > 0 && P > 0 && gdiv > 0 && ld > 0 && Cn > 0 && Cn <= ld && G2 > 0, "asx_op_group_stats: sizes must be positive, cn <= ld");
+  REQUIRE(R < OP_NORM_MAX && P < OP_NORM_MAX && R * P < OP_NORM_MAX && (int64_t)G1 * R * P < OP_NORM_MAX && (int64_t)G1 * G2 < (1 << 24),
+          "asx_op_group_stats: the case is too large for a single-op test");
+  REQUIRE((P - 1) / gdiv < G2, "asx_op_group_stats: a plane of %lld floats in groups of %lld does not fit g2 = %d groups", (long long)P,
+          (long long)gdiv, G2);
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dx, dacc;
+  BufGuard guard{{&dx, &dacc}};
+  const size_t pairs = (size_t)G1 * G2;
+  CHK(to_dev(dx, x_host, (size_t)((int64_t)G1 * R * P)));
+  CHK(dacc.ensure(pairs * 16));
+  int rc = op_norm_done(ht_stats(e, dx.f(), G1, R, P, gdiv, ld, Cn, G2, reinterpret_cast<double *>(dacc.p), nullptr), "asx_op_group_stats");
+  if (rc == ASX_OK) rc = op_acc_to_host(acc_host, dacc, pairs);
+  return rc;
+}
+
+int asx_op_group_norm(asx_engine *e, const char *family, const asx_group_norm_desc *d, const float *x_host, const float *gamma_host,
+                      const float *beta_host, const float *aux_host, const float *mul_host, float *y_host, float *stats_host) {
+  REQUIRE(e && family && d && x_host && y_host, "asx_op_group_norm: null argument");
+  enum { F_HT, F_HD, F_STD, F_TIME, F_HD_TIME, F_V3, F_MDX, F_N };
+  static const char *const names[F_N] = {"ht", "hd", "std", "time", "hd_time", "v3", "mdx"};
+  int fam = -1;
+  for (int i = 0; i < F_N; ++i)
+    if (strcmp(family, names[i]) == 0) fam = i;
+  REQUIRE(fam >= 0, "asx_op_group_norm: unknown family '%s'", family);
+  const int B = d->b, C = d->c;
+  const int64_t R = d->r, P = d->p;
+  REQUIRE(B > 0 && B <= 64, "asx_op_group_norm: b %d", B);
+  const bool waves = fam == F_TIME || fam == F_HD_TIME, planes = fam == F_V3 || fam == F_MDX;
+  if (waves || planes) REQUIRE(P > 0 && P < OP_NORM_MAX, "asx_op_group_norm(%s): p %lld", family, (long long)P);
+  if (!waves) REQUIRE(C > 0, "asx_op_group_norm(%s): c %d", family, C);
+  if (!waves && !planes) REQUIRE(R > 0 && R < OP_NORM_MAX, "asx_op_group_norm(%s): r %lld", family, (long long)R);
+  HIPCHK(hipSetDevice(e->device));
+  DevBuf dx, dy, dg, db, da, dm, dacc, dst, dpart;
+  BufGuard guard{{&dx, &dy, &dg, &db, &da, &dm, &dacc, &dst, &dpart}};
+  DevBuf *out = &dy;
+  size_t ny = 0;
+  int rc = ASX_OK;
+  if (fam == F_HT || fam == F_STD) {
+    // in place on x [b, r, c]
+    REQUIRE((int64_t)B * R * C < OP_NORM_MAX, "asx_op_group_norm(%s): the case is too large for a single-op test", family);
+    if (fam == F_HT) REQUIRE(gamma_host && beta_host, "asx_op_group_norm(ht): gamma and beta");
+    else REQUIRE(C % 4 == 0 && R < (1 << 24), "asx_op_group_norm(std): frames of c = 4 F floats, got %d", C);
+    ny = (size_t)((int64_t)B * R * C);
+    CHK(to_dev(dx, x_host, ny));
+    CHK(dacc.ensure((size_t)B * 16));
+    out = &dx;
+    if (fam == F_HT) {
+      CHK(to_dev(dg, gamma_host, (size_t)C));
+      CHK(to_dev(db, beta_host, (size_t)C));
+      rc = ht_norm_out(e, dx.f(), B, R, C, dg.f(), db.f(), reinterpret_cast<double *>(dacc.p), nullptr);
+    } else {
+      rc = ht_spec_standardize(e, dx.f(), B, (int)R, C / 4, reinterpret_cast<double *>(dacc.p), nullptr);
+    }
+  } else if (waves) {
+    // x [b, 2, p] -> y [b, p (rounded up to even), 2]
+    REQUIRE((int64_t)B * 2 * (P + 1) < OP_NORM_MAX, "asx_op_group_norm(%s): the case is too large for a single-op test", family);
+    const int64_t Lp = fam == F_HD_TIME ? (P + 1) & ~(int64_t)1 : P;
+    ny = (size_t)((int64_t)B * Lp * 2);
+    CHK(to_dev(dx, x_host, (size_t)((int64_t)B * 2 * P)));
+    CHK(to_dev(dy, y_host, ny));
+    CHK(dacc.ensure((size_t)B * 16));
+    rc = fam == F_TIME ? ht_wave_standardize(e, dx.f(), B, P, reinterpret_cast<double *>(dacc.p), dy.f(), nullptr)
+                       : hd_wave_standardize(e, dx.f(), B, P, reinterpret_cast<double *>(dacc.p), dy.f(), nullptr);
+  } else if (fam == F_HD) {
+    const int G = d->g, mode = d->mode;
+    const int64_t Rin = d->rin ? d->rin : R, r0 = d->r0;
+    REQUIRE(gamma_host && beta_host && G > 0 && mode >= 0 && mode <= 2 && (mode != 1 || C % 2 == 0), "asx_op_group_norm(hd): g %d, mode %d, c %d", G,
+            mode, C);
+    REQUIRE(r0 >= 0 && Rin < OP_NORM_MAX && r0 + R <= Rin && (int64_t)B * Rin * C < OP_NORM_MAX,
+            "asx_op_group_norm(hd): rows %lld .. %lld of %lld", (long long)r0, (long long)(r0 + R), (long long)Rin);
+    REQUIRE(!d->in_place || (mode != 1 && Rin == R), "asx_op_group_norm(hd): in place takes mode 0 / 2 and rin == r");
+    const int Ce = mode == 1 ? C / 2 : C;
+    ny = (size_t)((int64_t)B * R * Ce);
+    CHK(to_dev(dx, x_host, (size_t)((int64_t)B * Rin * C)));
+    CHK(to_dev(dg, gamma_host, (size_t)C));
+    CHK(to_dev(db, beta_host, (size_t)C));
+    if (aux_host) CHK(to_dev(da, aux_host, ny));
+    if (d->in_place) out = &dx;
+    else CHK(to_dev(dy, y_host, ny));
+    CHK(dacc.ensure((size_t)B * G * 16));
+    rc = hd_group_norm_core(e, dx.f(), B, R, C, G, dg.f(), db.f(), reinterpret_cast<double *>(dacc.p), mode, out->f(), aux_host ? da.f() : nullptr,
+                            nullptr, Rin, r0);
+  } else if (fam == F_V3) {
+    const int norm = d->norm, Ct = d->ctot, c0 = d->c0;
+    REQUIRE(v3_norm_valid(norm) && d->act >= V3_ACT_RELU && d->act <= V3_ACT_ELU, "asx_op_group_norm(v3): norm %d, act %d", norm, d->act);
+    REQUIRE(c0 >= 0 && Ct >= C && c0 <= Ct - C && (int64_t)Ct * P < OP_NORM_MAX && (int64_t)B * Ct * P < OP_NORM_MAX,
+            "asx_op_group_norm(v3): channels %d .. %d of %d", c0, c0 + C, Ct);
+    REQUIRE(norm == V3_NORM_NONE || (gamma_host && beta_host), "asx_op_group_norm(v3): gamma and beta");
+    const int G = v3_norm_groups(norm);
+    REQUIRE(G == 0 || C % G == 0, "asx_op_group_norm(v3): GroupNorm(%d) over %d channels", G, C);
+    ny = (size_t)((int64_t)B * C * P);
+    CHK(to_dev(dx, x_host, (size_t)((int64_t)B * Ct * P)));
+    CHK(to_dev(dy, y_host, ny));
+    if (norm != V3_NORM_NONE) {
+      CHK(to_dev(dg, gamma_host, (size_t)C));
+      CHK(to_dev(db, beta_host, (size_t)C));
+    }
+    // the workspaces as v3_ensure_workspace sizes them
+    if (stats_host) CHK(to_dev(dst, stats_host, (size_t)B * C * 2));
+    else CHK(dst.ensure((size_t)B * C * 8));
+    if (G > 0) CHK(dpart.ensure((size_t)B * G * V3_GN_MAX_SPLIT * sizeof(double2)));
+    rc = v3_norm_act_core(e, norm, d->act, d->alpha, dg.f(), db.f(), dst, dpart, V3View{dx.f() + (int64_t)c0 * P, (int64_t)Ct * P}, C, P, B, dy.f(),
+                          nullptr);
+  } else {
+    REQUIRE(gamma_host && beta_host && (int64_t)C * P < OP_NORM_MAX && (int64_t)B * C * P < OP_NORM_MAX,
+            "asx_op_group_norm(mdx): gamma, beta, and a case small enough for a single-op test");
+    ny = (size_t)((int64_t)B * C * P);
+    CHK(to_dev(dx, x_host, ny));
+    CHK(to_dev(dg, gamma_host, (size_t)C));
+    CHK(to_dev(db, beta_host, (size_t)C));
+    if (aux_host) CHK(to_dev(da, aux_host, ny));
+    if (mul_host) CHK(to_dev(dm, mul_host, ny));
+    if (d->in_place) out = &dx;
+    else CHK(to_dev(dy, y_host, ny));
+    CHK(dpart.ensure((size_t)B * C * 16));
+    std::swap(e->gn_part, dpart);                      // gn_launch takes its per-plane sums from the engine
+    rc = gn_launch(e, dx.f(), B, C, P, dg, db, aux_host ? da.f() : nullptr, mul_host ? dm.f() : nullptr, out->f(), nullptr);
+    std::swap(e->gn_part, dpart);
+  }
+  rc = op_norm_done(rc, "asx_op_group_norm");
+  if (rc == ASX_OK) rc = to_host(y_host, *out, ny);
+  if (rc == ASX_OK && stats_host && fam == F_V3) rc = to_host(stats_host, dst, (size_t)B * C * 2);
   return rc;
 }
 

@@ -242,6 +242,7 @@ struct asx_engine {
   // (conv3h_walk_ensure, engine_mdx.h), never at a launch, and kept until the engine goes (the entries never move: a captured graph holds the pointer)
   std::vector<Conv3hWalkTab *> c3h_walks;
   DevBuf gn_part;    // per-plane float64 (sum, sum of squares) of the GroupNorm variant of the net (asx_net_config.norm == 1)
+  DevBuf gstats_part;   // per-workgroup partial sums of the Demucs group statistics (ht_stats, engine_ht.h), grown on demand
   DevBuf d_div;      // divider of the chunk fold for div_key's plan (input-independent: built once, asx_finalize_dev)
   DivKey div_key;
   DevBuf sinc_tab;   // coefficient table of asx_resample_sinc (built on first use)

@@ -323,16 +323,32 @@ static int hd_ensure_workspace(asx_engine *e, int B, int64_t L) {
 
 // ---- stages -----------------------------------------------------------------------------------------------------
 // GroupNorm(G, C) over x [B, Rin, C] -> dst [B, R, C] = rows [r0, r0 + R) (hd_gn_kernel modes); Rin = 0: Rin = R
-static int hd_group_norm(asx_engine *e, const float *x, int B, int64_t R, int C, const HdNorm &g, int mode, float *dst, const float *skip,
-                         hipStream_t s, int64_t Rin = 0, int64_t r0 = 0) {
-  HtNet &n = *e->ht;
-  const int G = e->hd->cfg.norm_groups;
+// The core takes the group count, the affine and the statistics workspace (2 B G doubles) as arguments; hd_group_norm reads
+// them from the loaded net.
+static int hd_group_norm_core(asx_engine *e, const float *x, int B, int64_t R, int C, int G, const float *gam, const float *bet, double *acc,
+                              int mode, float *dst, const float *skip, hipStream_t s, int64_t Rin, int64_t r0) {
+  REQUIRE(G > 0 && C % G == 0, "GroupNorm(%d, %d): the groups do not divide the channels", G, C);
   if (!Rin) Rin = R;
-  CHK(ht_stats(e, x, B, Rin, C, C / G, C, C, G, n.b.acc_g, s));
+  CHK(ht_stats(e, x, B, Rin, C, C / G, C, C, G, acc, s));
   const int64_t total = (int64_t)B * R * (mode == 1 ? C / 2 : C);
   return timed(e, ASX_PROF_MISC, 0.0, 4.0 * (double)B * R * C * 2, s, [&]() {
-    hipLaunchKernelGGL(hd_gn_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, Rin, r0, R, C, G, n.b.acc_g, g.w.f(), g.b.f(),
-                       mode, dst, skip, total);
+    hipLaunchKernelGGL(hd_gn_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, Rin, r0, R, C, G, acc, gam, bet, mode, dst,
+                       skip, total);
+  });
+}
+
+static int hd_group_norm(asx_engine *e, const float *x, int B, int64_t R, int C, const HdNorm &g, int mode, float *dst, const float *skip,
+                         hipStream_t s, int64_t Rin = 0, int64_t r0 = 0) {
+  return hd_group_norm_core(e, x, B, R, C, e->hd->cfg.norm_groups, g.w.f(), g.b.f(), e->ht->b.acc_g, mode, dst, skip, s, Rin, r0);
+}
+
+// waveform branch input at any length: seg [B, 2, L] -> xt [B, Lp, 2] standardised as in ht_wave_standardize, Lp = L rounded up to
+// even, the pad sample zero (hdemucs.py:700-704)
+static int hd_wave_standardize(asx_engine *e, const float *seg, int B, int64_t L, double *acc, float *xt, hipStream_t s) {
+  const int64_t Lp = (L + 1) & ~(int64_t)1;
+  CHK(ht_stats(e, seg, B, 1, 2 * L, 2 * L, 1, 1, 1, acc, s));
+  return timed(e, ASX_PROF_MISC, 0.0, 16.0 * (double)B * L, s, [&]() {
+    hipLaunchKernelGGL(hd_time_norm_kernel, dim3((unsigned)((Lp + 255) / 256), B), dim3(256), 0, s, seg, L, Lp, acc, xt);
   });
 }
 
@@ -521,20 +537,12 @@ static int hd_phase_front(asx_engine *e, const HdGroup &gr, hipStream_t s) {
   const HdDims &dm = gr.dm;
   const int D = h.D, T = dm.T, hop = c.nfft / 4;
   const int F0 = n.F[0], CA = h.CA, CD = h.CD;
-  const int64_t Lp = (L + 1) & ~(int64_t)1;
   // spectrogram + standardisation of both branches (hdemucs.py:680-704); pad1d's zero extension of short inputs (:21-34)
   int64_t el, Lv;
   ht_spec_extension(L, T, hop, &el, &Lv);
   CHK(ht_spec_launch(e, n.plan, n.window.f(), n.tw.p, seg, B, L, el, Lv, T, b.xf0, s));
-  const int64_t nf = (int64_t)T * F0 * 4;
-  CHK(ht_stats(e, b.xf0, B, T, (int64_t)F0 * 4, (int64_t)F0 * 4, 4, 4, 1, b.acc_f, s));
-  CHK(timed(e, ASX_PROF_MISC, 0.0, 8.0 * (double)B * nf, s, [&]() {
-    hipLaunchKernelGGL(std_norm_kernel, dim3((unsigned)((nf + 255) / 256), B), dim3(256), 0, s, b.xf0, nf, b.acc_f);
-  }));
-  CHK(ht_stats(e, seg, B, 1, 2 * L, 2 * L, 1, 1, 1, b.acc_t, s));
-  CHK(timed(e, ASX_PROF_MISC, 0.0, 16.0 * (double)B * L, s, [&]() {
-    hipLaunchKernelGGL(hd_time_norm_kernel, dim3((unsigned)((Lp + 255) / 256), B), dim3(256), 0, s, seg, L, Lp, b.acc_t, b.xt0);
-  }));
+  CHK(ht_spec_standardize(e, b.xf0, B, T, F0, b.acc_f, s));
+  CHK(hd_wave_standardize(e, seg, B, L, b.acc_t, b.xt0, s));
   for (int i = 0; i < D; ++i) CHK(ht_enc_level(e, i, B, s));
   // ---- level A (hdemucs.py:715-733 with HEncLayer.forward :139-170) ----
   HtGeom g;   // tencoder: bare conv, its output is injected into the spectrogram branch

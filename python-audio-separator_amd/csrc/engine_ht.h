@@ -777,7 +777,6 @@ static int ht_ln(asx_engine *e, const float *x, int C, const DevBuf &g, const De
 // statistics of x viewed as [G1, R, P]; groups of gdiv consecutive plane elements; acc must hold G1*G2*2 doubles
 static int ht_stats(asx_engine *e, const float *x, int G1, int64_t R, int64_t P, int64_t gdiv, int ld, int Cn, int G2,
                     double *acc, hipStream_t s) {
-  HIPCHK(hipMemsetAsync(acc, 0, (size_t)G1 * G2 * 16, s));
   if (R == 1 && G2 == 1 && gdiv >= P && ld == 1 && P >= 65536) {
     // one flat group per item: fold the plane into rows so that a thread sums a column instead of 256 threads
     // hammering one LDS / global atomic each (0.5 ms -> tens of microseconds for a 688 k-sample segment)
@@ -789,12 +788,22 @@ static int ht_stats(asx_engine *e, const float *x, int G1, int64_t R, int64_t P,
         break;
       }
   }
+  // gstats_kernel has at most 66 group slots per workgroup: a workgroup of 256 consecutive plane elements touches at most
+  // 255 / gdiv + 2 groups (P >= 256), one of whole short planes every group of the plane (P < 256)
+  const int64_t wg_groups = gdiv >= P ? 1 : P >= 256 ? 255 / gdiv + 2 : (P + gdiv - 1) / gdiv;
+  REQUIRE(wg_groups <= 66, "group statistics: groups of %lld floats in a plane of %lld need %lld group slots per workgroup, the kernel has 66",
+          (long long)gdiv, (long long)P, (long long)wg_groups);
   int64_t rsplit = R / 96;
   if (rsplit < 1) rsplit = 1;
   if (rsplit > 1024) rsplit = 1024;
   const unsigned gx = P >= 256 ? (unsigned)((P + 255) / 256) : 1u;
+  // the workgroups' partial sums (kernels_ht.h: no atomics, so that two runs give the same bits); every group of acc is written
+  const int nslot = (int)wg_groups;
+  CHK(e->gstats_part.ensure((size_t)G1 * rsplit * gx * nslot * sizeof(double2)));
+  double2 *part = reinterpret_cast<double2 *>(e->gstats_part.p);
   return timed(e, ASX_PROF_MISC, 0.0, 4.0 * (double)G1 * R * P, s, [&]() {
-    hipLaunchKernelGGL(gstats_kernel, dim3(gx, (unsigned)rsplit, (unsigned)G1), dim3(256), 0, s, x, R, P, gdiv, ld, Cn, G2,
+    hipLaunchKernelGGL(gstats_kernel, dim3(gx, (unsigned)rsplit, (unsigned)G1), dim3(256), 0, s, x, R, P, gdiv, ld, Cn, nslot, part);
+    hipLaunchKernelGGL(gstats_finish_kernel, dim3((unsigned)G2, (unsigned)G1), dim3(64), 0, s, part, P, gdiv, G2, (int)gx, (int)rsplit, nslot,
                        acc);
   });
 }
@@ -806,6 +815,31 @@ static int ht_gn(asx_engine *e, float *x, int G1, int64_t R, int G2, int ld, int
   return timed(e, ASX_PROF_MISC, 0.0, 8.0 * (double)total, s, [&]() {
     hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, R, G2, ld, Cn, acc, gam,
                        bet, 1e-5f, mode, dst, dst_ld, ls, total);
+  });
+}
+
+// norm_out = MyGroupNorm(1, C) over the whole (tokens, channels) sample, in place on x [B, N, C] (transformer.py:181-187, 265);
+// acc: 2 B doubles
+static int ht_norm_out(asx_engine *e, float *x, int B, int64_t N, int C, const float *gam, const float *bet, double *acc, hipStream_t s) {
+  CHK(ht_stats(e, x, B, N, C, C, C, C, 1, acc, s));
+  return ht_gn(e, x, B, N, 1, C, C, acc, gam, bet, 2, nullptr, 0, nullptr, s);
+}
+
+// per-item standardisation (x - mean) / (1e-5 + std), std unbiased; acc (2 B doubles) keeps the sums for the de-standardisation.
+// The spectrogram x [B, T, F0, 4] in place (htdemucs.py:511-513) ...
+static int ht_spec_standardize(asx_engine *e, float *x, int B, int T, int F0, double *acc, hipStream_t s) {
+  const int64_t nf = (int64_t)T * F0 * 4;
+  CHK(ht_stats(e, x, B, T, (int64_t)F0 * 4, (int64_t)F0 * 4, 4, 4, 1, acc, s));
+  return timed(e, ASX_PROF_MISC, 0.0, 8.0 * (double)B * nf, s, [&]() {
+    hipLaunchKernelGGL(std_norm_kernel, dim3((unsigned)((nf + 255) / 256), B), dim3(256), 0, s, x, nf, acc);
+  });
+}
+
+// ... and the waveform seg [B, 2, L] -> xt [B, L, 2] (htdemucs.py:516-519)
+static int ht_wave_standardize(asx_engine *e, const float *seg, int B, int64_t L, double *acc, float *xt, hipStream_t s) {
+  CHK(ht_stats(e, seg, B, 1, 2 * L, 2 * L, 1, 1, 1, acc, s));
+  return timed(e, ASX_PROF_MISC, 0.0, 16.0 * (double)B * L, s, [&]() {
+    hipLaunchKernelGGL(time_norm_kernel, dim3((unsigned)((L + 255) / 256), B), dim3(256), 0, s, seg, L, acc, xt);
   });
 }
 
@@ -1015,9 +1049,7 @@ static int ht_tlayer_ff(asx_engine *e, const HtTLayer &L, float *x, int B, int64
   CHK(ht_ln(e, x, C, nw, nb, nullptr, 1, n.b.xn, M, s));
   CHK(ht_linear(e, L.l1, n.b.xn, C, M, n.b.ffh, n.hidden, 2, nullptr, 0, s));
   CHK(ht_linear(e, L.l2, n.b.ffh, n.hidden, M, x, C, 0, x, C, s));
-  // norm_out = MyGroupNorm(1, C) over the whole (tokens, channels) sample (transformer.py:181-187, 265)
-  CHK(ht_stats(e, x, B, N, C, C, C, C, 1, n.b.acc_g, s));
-  CHK(ht_gn(e, x, B, N, 1, C, C, n.b.acc_g, L.now.f(), L.nob.f(), 2, nullptr, 0, nullptr, s));
+  CHK(ht_norm_out(e, x, B, N, C, L.now.f(), L.nob.f(), n.b.acc_g, s));
   return ASX_OK;
 }
 
@@ -1176,14 +1208,8 @@ static int ht_forward_dev(asx_engine *e, const float *seg, int B, float *out, hi
   // spectrogram + per-sample standardisation of both branches (htdemucs.py:505-519)
   CHK(ht_spec_launch(e, n.plan, n.window.f(), n.tw.p, seg, B, TL, 0, TL, T, b.xf0, s));
   const int64_t nf = (int64_t)T * F0 * 4;
-  CHK(ht_stats(e, b.xf0, B, T, (int64_t)F0 * 4, (int64_t)F0 * 4, 4, 4, 1, b.acc_f, s));
-  CHK(timed(e, ASX_PROF_MISC, 0.0, 8.0 * (double)B * nf, s, [&]() {
-    hipLaunchKernelGGL(std_norm_kernel, dim3((unsigned)((nf + 255) / 256), B), dim3(256), 0, s, b.xf0, nf, b.acc_f);
-  }));
-  CHK(ht_stats(e, seg, B, 1, 2 * TL, 2 * TL, 1, 1, 1, b.acc_t, s));
-  CHK(timed(e, ASX_PROF_MISC, 0.0, 16.0 * (double)B * TL, s, [&]() {
-    hipLaunchKernelGGL(time_norm_kernel, dim3((unsigned)((TL + 255) / 256), B), dim3(256), 0, s, seg, TL, b.acc_t, b.xt0);
-  }));
+  CHK(ht_spec_standardize(e, b.xf0, B, T, F0, b.acc_f, s));
+  CHK(ht_wave_standardize(e, seg, B, TL, b.acc_t, b.xt0, s));
   // encoders
   for (int i = 0; i < D; ++i) CHK(ht_enc_level(e, i, B, s));
   // cross transformer (transformer.py:520-548)

@@ -155,12 +155,14 @@ struct V3View {
   int64_t bstride;  // floats between batch items
 };
 
-static int v3_norm_act(asx_engine *e, const V3Norm &n, V3View x, int C, int64_t P, int B, float *y, hipStream_t s) {
-  V3Net &net = *e->v3;
-  const int norm = net.cfg.norm;
-  float2 *st = reinterpret_cast<float2 *>(net.stats.p);
+// norm -> act of one pre-activation block on a channel-slice view.  The core takes the configuration (norm / act as asx_v3_config
+// encodes them, alpha), the affine and the two workspaces (stats: 2 B C floats; gn_part: v3_gn_splits slices of every (group, item))
+// as arguments; v3_norm_act reads them from the loaded net.
+static int v3_norm_act_core(asx_engine *e, int norm, int cfg_act, float alpha, const float *gam, const float *bet, const DevBuf &stats,
+                            const DevBuf &gn_part, V3View x, int C, int64_t P, int B, float *y, hipStream_t s) {
+  float2 *st = reinterpret_cast<float2 *>(stats.p);
   // cfg.act: 0 relu, 1 gelu, 2 elu -> kernel enum (ACT_*) 1 relu, 2 gelu, 3 elu
-  const int act = net.cfg.act == V3_ACT_GELU ? ACT_GELU : net.cfg.act == V3_ACT_ELU ? ACT_ELU : ACT_RELU;
+  const int act = cfg_act == V3_ACT_GELU ? ACT_GELU : cfg_act == V3_ACT_ELU ? ACT_ELU : ACT_RELU;
   const double bytes_r = 4.0 * B * C * (double)P;
   if (norm == V3_NORM_INSTANCE) {
     CHK(timed(e, ASX_PROF_MISC, 0.0, bytes_r, s, [&]() {
@@ -170,8 +172,8 @@ static int v3_norm_act(asx_engine *e, const V3Norm &n, V3View x, int C, int64_t 
     const int G = v3_norm_groups(norm);
     const int64_t len = (int64_t)(C / G) * P;
     const int ns = v3_gn_splits(B, G, len);
-    REQUIRE(C % G == 0 && net.gn_part.bytes >= (size_t)B * G * ns * sizeof(double2), "GroupNorm%d over %d channels: workspace", G, C);
-    double2 *part = reinterpret_cast<double2 *>(net.gn_part.p);
+    REQUIRE(C % G == 0 && gn_part.bytes >= (size_t)B * G * ns * sizeof(double2), "GroupNorm%d over %d channels: workspace", G, C);
+    double2 *part = reinterpret_cast<double2 *>(gn_part.p);
     CHK(timed(e, ASX_PROF_MISC, 0.0, bytes_r, s, [&]() {
       hipLaunchKernelGGL(v3_gn_partial_kernel, dim3((unsigned)ns, (unsigned)G, (unsigned)B), dim3(256), 0, s, x.p, x.bstride, C, G, P,
                          ns, part);
@@ -180,12 +182,17 @@ static int v3_norm_act(asx_engine *e, const V3Norm &n, V3View x, int C, int64_t 
   }
   const bool has_stats = norm == V3_NORM_INSTANCE || norm > V3_NORM_GROUP;
   const unsigned gx = (unsigned)std::min<int64_t>((P / 4 + 255) / 256 + 1, 64);
-  const float *gp = norm == V3_NORM_NONE ? nullptr : n.g.f(), *bp = norm == V3_NORM_NONE ? nullptr : n.b.f();
+  const float *gp = norm == V3_NORM_NONE ? nullptr : gam, *bp = norm == V3_NORM_NONE ? nullptr : bet;
   CHK(timed(e, ASX_PROF_MISC, 0.0, 2.0 * bytes_r, s, [&]() {
     hipLaunchKernelGGL(norm_act_kernel, dim3(gx, C, B), dim3(256), 0, s, x.p, x.bstride, C, P,
-                       has_stats ? st : nullptr, gp, bp, act, net.act_alpha, y);
+                       has_stats ? st : nullptr, gp, bp, act, alpha, y);
   }));
   return ASX_OK;
+}
+
+static int v3_norm_act(asx_engine *e, const V3Norm &n, V3View x, int C, int64_t P, int B, float *y, hipStream_t s) {
+  V3Net &net = *e->v3;
+  return v3_norm_act_core(e, net.cfg.norm, net.cfg.act, net.act_alpha, n.g.f(), n.b.f(), net.stats, net.gn_part, x, C, P, B, y, s);
 }
 
 // One TFC_TDF (tfc_tdf_v3.py:110-148).  x_in: view with blocks[0].in_c channels; dest: view with c channels.

@@ -743,16 +743,18 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float *__restrict_
 // ---------------------------------------------------------------------------
 // Group statistics.  x is viewed as [G1, R, P] (P = contiguous plane of G2 groups x ld floats, of which
 // the first Cn of every ld are data); group (g1, e / gdiv) accumulates sum and sum of squares in
-// float64: acc[(g1*G2 + g2)*2 + {0,1}] (zeroed by the caller).  grid = (ceil(P/256) or 1, rsplit, G1).
+// float64: acc[(g1*G2 + g2)*2 + {0,1}].  grid = (ceil(P/256) or 1, rsplit, G1).
 //   GroupNorm(1, C) of DConv on the spectrogram branch: G1 = B, R = T, P = F*ld, gdiv = ld   (per (b, f))
 //   GroupNorm(1, C) over a whole sample / the mean-std of htdemucs.py:511,518: P = row, gdiv >= P
+// Two launches, no atomics, every sum in a fixed order, so that two runs give the same bits: gstats_kernel leaves the sums of
+// workgroup (bx, by, g1) over its nslot <= 66 local groups in part[((g1 * rsplit + by) * gx + bx) * nslot + slot] (slot = the group's
+// index minus the workgroup's first group), gstats_finish_kernel adds a group's partial sums over (by, bx) with one wave per group.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gstats_kernel(const float *__restrict__ x, int64_t R, int64_t P, int64_t gdiv,
-                                                     int ld, int Cn, int G2, double *__restrict__ acc) {
-  __shared__ double sh[66][2];
+                                                     int ld, int Cn, int nslot, double2 *__restrict__ part) {
+  __shared__ double ts[256], tq[256];
+  __shared__ int tg[256];
   const int tid = threadIdx.x;
-  for (int i = tid; i < 66 * 2; i += 256) (&sh[0][0])[i] = 0.0;
-  __syncthreads();
   int64_t e;
   int rr = 0, rpb = 1;
   if (P >= 256) {
@@ -768,26 +770,59 @@ __global__ __launch_bounds__(256) void gstats_kernel(const float *__restrict__ x
   const int64_t r0 = (int64_t)blockIdx.y * rows_per;
   const int64_t r1 = (r0 + rows_per < R) ? r0 + rows_per : R;
   const int64_t gfirst = ((int64_t)blockIdx.x * 256) / gdiv;
+  double s = 0.0, ss = 0.0;
+  int lg = -1;
   if (e < P && (int)(e % ld) < Cn) {
-    double s = 0.0, ss = 0.0;
     const float *xp = x + g1 * R * P + e;
     for (int64_t r = r0 + rr; r < r1; r += rpb) {
       const double v = (double)xp[r * P];
       s += v;
       ss += v * v;
     }
-    const int lg = (int)(e / gdiv - (P >= 256 ? gfirst : 0));
-    atomicAdd(&sh[lg][0], s);
-    atomicAdd(&sh[lg][1], ss);
+    lg = (int)(e / gdiv - (P >= 256 ? gfirst : 0));
   }
+  ts[tid] = s;
+  tq[tid] = ss;
+  tg[tid] = lg;
   __syncthreads();
-  const int64_t gbase = (P >= 256) ? gfirst : 0;
-  if (tid < 66) {
-    const int64_t g2 = gbase + tid;
-    if (g2 < G2 && (sh[tid][0] != 0.0 || sh[tid][1] != 0.0)) {
-      atomicAdd(&acc[(g1 * G2 + g2) * 2], sh[tid][0]);
-      atomicAdd(&acc[(g1 * G2 + g2) * 2 + 1], sh[tid][1]);
+  if (tid < nslot) {           // the threads of local group tid, in thread order
+    double a = 0.0, q = 0.0;
+    for (int t = 0; t < 256; ++t)
+      if (tg[t] == tid) {
+        a += ts[t];
+        q += tq[t];
+      }
+    const int64_t wg = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    part[wg * nslot + tid] = make_double2(a, q);
+  }
+}
+
+// grid = (G2, G1), one wave each: lane l adds the group's partial sums l, l + 64, ... in (by, bx) order, then the lanes fold in a fixed tree
+__global__ __launch_bounds__(64) void gstats_finish_kernel(const double2 *__restrict__ part, int64_t P, int64_t gdiv, int G2, int gx,
+                                                           int rsplit, int nslot, double *__restrict__ acc) {
+  const int64_t g2 = blockIdx.x, g1 = blockIdx.y;
+  double a = 0.0, q = 0.0;
+  const int64_t first = g2 * gdiv;                      // the group's plane elements [first, last]
+  if (first < P) {
+    const int64_t last = (first + gdiv < P ? first + gdiv : P) - 1;
+    const int bx0 = P >= 256 ? (int)(first / 256) : 0, bx1 = P >= 256 ? (int)(last / 256) : 0;
+    const int nb = bx1 - bx0 + 1;
+    for (int k = threadIdx.x; k < rsplit * nb; k += 64) {
+      const int by = k / nb, bx = bx0 + k % nb;
+      const int64_t gfirst = P >= 256 ? ((int64_t)bx * 256) / gdiv : 0;
+      const double2 v = part[(((int64_t)g1 * rsplit + by) * gx + bx) * nslot + (g2 - gfirst)];
+      a += v.x;
+      q += v.y;
     }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_xor(a, off);
+    q += __shfl_xor(q, off);
+  }
+  if (threadIdx.x == 0) {
+    acc[(g1 * G2 + g2) * 2] = a;
+    acc[(g1 * G2 + g2) * 2 + 1] = q;
   }
 }
 

@@ -13,6 +13,8 @@ namespace asx {
 
 // ---------------------------------------------------------------------------
 // RMSNorm (bs_roformer.py:42-52): y = x / max(||x||_2, 1e-12) * sqrt(d) * gamma, one wave per row.
+// rof_transformer runs the Mel-Band output norm in place (x == y): a lane re-reads only the indices it writes itself, and
+// tests/test_gpu_norm_kernels.py holds the in-place launch to the bits of the out-of-place one.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const float *__restrict__ x, int64_t lda, int d,
                                                       const float *__restrict__ gamma, float *__restrict__ y,

@@ -285,7 +285,8 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
            "asx_resample_rational_stem", "asx_resample_rational_stem_dev", "asx_op_stft", "asx_op_istft", "asx_op_ht_spec",
            "asx_op_ht_ispec", "asx_ensemble_batch_modes_dev", "asx_resample_rational_complement",
            "asx_resample_rational_complement_dev", "asx_normalize_scale_dev", "asx_mixdown_batch_dev", "asx_mixdown",
-           "asx_phase_fix_batch_dev", "asx_phase_fix_dev", "asx_phase_fix"]
+           "asx_phase_fix_batch_dev", "asx_phase_fix_dev", "asx_phase_fix", "asx_op_rownorm", "asx_op_group_stats",
+           "asx_op_group_norm"]
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
@@ -313,6 +314,29 @@ class _StftDesc(C.Structure):      # struct asx_stft_desc
                                                         ("spec_floats", C.c_int64), ("starts", C.POINTER(C.c_int64)),
                                                         ("song_of", C.POINTER(C.c_int32)), ("song_len", C.POINTER(C.c_int64)),
                                                         ("n_act", C.POINTER(C.c_int64))]
+
+
+# asx_op_rownorm: `kind`; asx_op_group_norm: `family`, the hd modes, and the norm / act codes of asx_v3_config for "v3"
+ROWNORM_KINDS = ("rms", "rms_factor", "layer")
+GROUP_NORM_FAMILIES = ("ht", "hd", "std", "time", "hd_time", "v3", "mdx")
+HD_GN_MODES = {"gelu": 0, "glu": 1, "none": 2}
+V3_ACTS = {"relu": 0, "gelu": 1, "elu": 2}
+
+
+def v3_norm_code(norm):
+    """asx_v3_config.norm of the model's norm name: None, InstanceNorm, BatchNorm or GroupNorm<g>"""
+    if norm is None or norm == "None":
+        return 0
+    if norm in ("InstanceNorm", "BatchNorm"):
+        return 1 if norm == "InstanceNorm" else 2
+    if isinstance(norm, str) and norm.startswith("GroupNorm") and norm[9:].isdigit() and int(norm[9:]) > 0:
+        return 256 + int(norm[9:])
+    raise AsxError(f"unknown norm {norm!r}")
+
+
+class _GroupNormDesc(C.Structure):  # struct asx_group_norm_desc
+    _fields_ = [(n, C.c_int32) for n in ("b", "c", "g", "mode", "norm", "act", "ctot", "c0", "in_place")] + [("alpha", C.c_float)] + \
+               [(n, C.c_int64) for n in ("r", "rin", "r0", "p")]
 
 
 class _LaunchRec(C.Structure):     # struct asx_launch_rec
@@ -445,6 +469,9 @@ def load_library():
     lib.asx_op_ht_ispec.argtypes = [vp, i32, _FP, i32, i32, i32, _DP, C.c_double, _FP, _DP, i64, _FP]
     lib.asx_op_dconv.argtypes = [vp, _FP, i32, i32, i32, i32, i32, i32, i32, i32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                                  C.POINTER(i32)]
+    lib.asx_op_rownorm.argtypes = [vp, C.c_char_p, _FP, i64, i32, i64, _FP, _FP, _FP, i64, i32, _FP, i64]
+    lib.asx_op_group_stats.argtypes = [vp, _FP, i32, i64, i64, i64, i32, i32, i32, _DP]
+    lib.asx_op_group_norm.argtypes = [vp, C.c_char_p, C.POINTER(_GroupNormDesc), _FP, _FP, _FP, _FP, _FP, _FP, _FP]
     lib.asx_v3_begin.argtypes = [vp, C.POINTER(_V3Cfg)]
     lib.asx_v3_commit.argtypes = [vp]
     lib.asx_v3_flops.argtypes = [vp, i32]
@@ -2143,6 +2170,85 @@ class Engine:
                                            _ptr(t["b1"]), _ptr(t["g1w"]), _ptr(t["g1b"]), _ptr(t["w2"]), _ptr(t["b2"]), _ptr(t["g2w"]),
                                            _ptr(t["g2b"]), _ptr(t["ls"]), _ptr(h), C.byref(left)))
         return y, h, left.value
+
+    def op_rownorm(self, kind, x, d, gamma=None, beta=None, pos=None, y=None, in_place=False):
+        """One row normalisation launch (asx_op_rownorm) over the first d columns of x [M, lda].  "rms": rof_rmsnorm into y [M, ldy]
+        (default NaN, uploaded first), or in place on one device buffer holding x; "rms_factor": rof_rownorm -> r [M]; "layer": ht_ln
+        with gamma, beta and the optional position table pos [pos_mod, d] read at row % pos_mod (dense rows, lda == d)."""
+        x = _f32(x)
+        M, lda = x.shape
+        if kind == "rms_factor":
+            y = np.full(M, np.nan, np.float32) if y is None else np.array(y, np.float32, order="C")
+            ldy, want = 0, (M,)
+        else:
+            y = np.full((M, lda if in_place else d), np.nan, np.float32) if y is None else np.array(y, np.float32, order="C")
+            ldy, want = (y.shape[1] if y.ndim == 2 else -1), (M, y.shape[-1])
+        gamma, beta, pos = (None if a is None else _f32(a) for a in (gamma, beta, pos))
+        if y.shape != want or any(a is not None and a.size != d for a in (gamma, beta)) or (pos is not None and (pos.ndim != 2 or pos.shape[1] != d)):
+            raise AsxError(f"op_rownorm: x {x.shape} / y {y.shape} / gamma, beta, pos do not fit d = {d}")
+        self._check(self._lib.asx_op_rownorm(self._h, kind.encode(), _ptr(x), M, int(d), lda, _optptr(gamma), _optptr(beta), _optptr(pos),
+                                             0 if pos is None else pos.shape[0], int(bool(in_place)), _ptr(y), ldy))
+        return y
+
+    def op_group_stats(self, x, gdiv, ld, cn, g2):
+        """One ht_stats launch (asx_op_group_stats) over x [G1, R, P]: the float64 (sum, sum of squares) pairs [G1, g2, 2] of the groups
+        of gdiv consecutive plane elements, counting the first cn of every ld."""
+        x = _f32(x)
+        G1, R, P = x.shape
+        acc = np.full((G1, int(g2), 2), np.nan, np.float64)
+        self._check(self._lib.asx_op_group_stats(self._h, _ptr(x), G1, R, P, int(gdiv), int(ld), int(cn), int(g2),
+                                                 acc.ctypes.data_as(C.POINTER(C.c_double))))
+        return acc
+
+    def op_group_norm(self, family, x, gamma=None, beta=None, aux=None, mul=None, y=None, stats=None, **desc):
+        """Statistics + apply of one normalisation as the nets launch it (asx_op_group_norm, include/asx.h): `desc` holds the fields of
+        asx_group_norm_desc the family reads (mode as "gelu" / "glu" / "none", norm as in the model's config, act by name); b and the
+        sizes the shape of x gives are taken from x.  y (default NaN) and stats are uploaded first.  Returns y, or (y, stats) for "v3"."""
+        x = _f32(x)
+        d = _GroupNormDesc()
+        for k, v in desc.items():
+            if k == "mode":
+                v = HD_GN_MODES[v] if isinstance(v, str) else v
+            elif k == "norm":
+                v = v if isinstance(v, int) else v3_norm_code(v)
+            elif k == "act":
+                v = V3_ACTS[v] if isinstance(v, str) else v
+            setattr(d, k, float(v) if k == "alpha" else int(v))
+        d.b = x.shape[0]
+        if family in ("ht", "std"):
+            _, d.r, d.c = x.shape
+            shape = x.shape
+        elif family in ("time", "hd_time"):
+            d.p = x.shape[2]
+            shape = (d.b, (d.p + 1) // 2 * 2 if family == "hd_time" else d.p, 2)
+        elif family == "hd":
+            d.c = x.shape[2]
+            if not d.r:
+                d.r = x.shape[1]
+            d.rin = x.shape[1]
+            shape = (d.b, d.r, d.c // 2 if d.mode == 1 else d.c)
+        elif family == "v3":
+            _, d.ctot, d.p = x.shape
+            if not d.c:
+                d.c = d.ctot
+            shape = (d.b, d.c, d.p)
+        elif family == "mdx":
+            _, d.c, d.p = x.shape
+            shape = x.shape
+        else:
+            raise AsxError(f"op_group_norm: unknown family {family!r}")
+        gamma, beta, aux, mul = (None if a is None else _f32(a) for a in (gamma, beta, aux, mul))
+        y = np.full(shape, np.nan, np.float32) if y is None else np.array(y, np.float32, order="C")
+        if family == "v3":
+            stats = np.full((d.b, d.c, 2), np.nan, np.float32) if stats is None else np.array(stats, np.float32, order="C")
+        else:
+            stats = None
+        if y.shape != tuple(shape) or any(a is not None and a.shape != y.shape for a in (aux, mul)) or \
+                any(a is not None and a.size != d.c for a in (gamma, beta)) or (stats is not None and stats.shape != (d.b, d.c, 2)):
+            raise AsxError(f"op_group_norm({family}): x {x.shape} / y {y.shape} / the other tensors do not fit")
+        self._check(self._lib.asx_op_group_norm(self._h, family.encode(), C.byref(d), _ptr(x), _optptr(gamma), _optptr(beta), _optptr(aux),
+                                                _optptr(mul), _ptr(y), _optptr(stats)))
+        return (y, stats) if family == "v3" else y
 
     # -- profiling --------------------------------------------------------------
     def profile_enable(self, on: bool = True):

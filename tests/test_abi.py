@@ -85,7 +85,7 @@ def test_header_is_plain_c_and_struct_layouts_match(tmp_path):
     pairs = [("asx_mdx_config", E._MdxCfg), ("asx_net_config", E._NetCfg), ("asx_plan", E._Plan), ("asx_profile", E._Profile),
              ("asx_v3_config", E._V3Cfg), ("asx_rof_config", E._RofCfg), ("asx_ht_config", E._HtCfg), ("asx_hd_config", E._HdCfg), ("asx_vr_band", E._VrBand),
              ("asx_vr_config", E._VrCfg), ("asx_vr_params", E._VrParams), ("asx_launch_rec", E._LaunchRec),
-             ("asx_gconv_desc", E._GconvDesc), ("asx_stft_desc", E._StftDesc)]
+             ("asx_gconv_desc", E._GconvDesc), ("asx_stft_desc", E._StftDesc), ("asx_group_norm_desc", E._GroupNormDesc)]
     src = '#include <stdio.h>\n#include "asx.h"\nint main(void) {\n' + \
           "".join(f'  printf("{n} %zu\\n", sizeof({n}));\n' for n, _ in pairs) + "  return 0;\n}\n"
     c = tmp_path / "sizes.c"
@@ -114,3 +114,18 @@ def test_gconv_hooks_are_additive_within_abi_7(lib):
     assert lib.asx_op_gconv(None, None, None, None, None, None, b"auto", None, None) != 0
     assert lib.asx_op_dconv(None, None, 1, 1, 1, 4, 1, 0, 0, 3, None, None, None, None, None, None, None, None, None, None, None) != 0
     assert E.GCONV_VARIANTS == ("auto", "gg", "halo", "gather") and E.GCONV_MODES == {"dense": 0, "glu": 1, "convt": 2}
+
+
+def test_norm_hooks_are_additive_within_abi_8(lib):
+    """asx_op_rownorm / asx_op_group_stats / asx_op_group_norm: the descriptor is 9 int32 + a float + 4 int64, and a null engine is an
+    error"""
+    import ctypes as C
+    assert C.sizeof(E._GroupNormDesc) == 72 and E._GroupNormDesc.alpha.offset == 36 and E._GroupNormDesc.r.offset == 40
+    assert E._GroupNormDesc.p.offset == 64 and E._GroupNormDesc.in_place.offset == 32
+    assert lib.asx_abi_version() == 8
+    assert lib.asx_op_rownorm(None, b"rms", None, 1, 8, 8, None, None, None, 0, 0, None, 8) != 0
+    assert lib.asx_op_group_stats(None, None, 1, 1, 8, 8, 8, 8, 1, None) != 0
+    assert lib.asx_op_group_norm(None, b"ht", None, None, None, None, None, None, None, None) != 0
+    assert E.ROWNORM_KINDS == ("rms", "rms_factor", "layer")
+    assert E.GROUP_NORM_FAMILIES == ("ht", "hd", "std", "time", "hd_time", "v3", "mdx") and E.HD_GN_MODES == {"gelu": 0, "glu": 1, "none": 2}
+    assert [E.v3_norm_code(n) for n in (None, "InstanceNorm", "BatchNorm", "GroupNorm4")] == [0, 1, 2, 260]
