@@ -941,6 +941,8 @@ int asx_phase_fix(asx_engine *e, const float *target_host, int32_t target_layout
  * "tdf3h_launches" (those of them, plain or GATHER mode, that ran the fp16 x 3 arithmetic),
  * "tdf3_gather_launches" (its GATHER mode: channels-last convolutions), "attn6_launches" (attention6_kernel / mha6_kernel),
  * "attn6h_launches" (those of them on the fp16 x 3 arithmetic),
+ * "tdf3s_launches" / "attn6s_launches" (additive: those on the single-product arithmetic of option "gemm_f16x1"; each such launch is counted
+ * by "tdf3h_launches" / "attn6h_launches" and "tdf3_launches" / "attn6_launches" as well),
  * "wino6_launches" (conv_wino6_kernel: Winograd F(2x2,3x3) on the 16-bit pipe), "wino6h_launches" (those on the fp16 x 3 arithmetic),
  * "conv3h_launches" (ABI 7: conv3h_kernel, the direct fp16 x 3 convolution of the 48-channel level),
  * "conv3h_fin_launches" (those of them in the fused-input form, option "conv_fuse_input": one per net pass where it applies),
@@ -1013,7 +1015,9 @@ int asx_op_tdf_block(asx_engine *e, const float *x_host, int32_t batch, int32_t 
  * "attn6" / "attn6_qw2" (attention6_kernel on the bf16 x 6 arithmetic), "attn6h" / "attn6h_qw2" (on the fp16 x 3 arithmetic), or "auto":
  * the kernel the engine picks for this sequence length under its options and environment.  resolved (optional): the index of the variant
  * that ran in the list "auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
- * "mha6_wide", "mha6h", "mha6h_wide", "hd_local".  ASX_ERR_INVALID for an unknown variant or one of the other family. */
+ * "mha6_wide", "mha6h", "mha6h_wide", "hd_local", "attn6s", "attn6s_qw2".  "attn6s" / "attn6s_qw2" (additive, appended to the list): attention6_kernel
+ * on the single-product arithmetic of option "gemm_f16x1" (reduced precision); "auto" resolves to them when and only when that option is on.
+ * ASX_ERR_INVALID for an unknown variant or one of the other family. */
 int asx_op_attention(asx_engine *e, const float *qkv_host, const float *gate_host, int64_t m, int32_t batch, int32_t t, int32_t fb,
                      int32_t axis, int32_t heads, int32_t gate_ld, int32_t exact, const char *variant, float *out_host, int32_t *resolved);
 /* (ABI 7) One multi-head attention launch of the HTDemucs transformer (self and cross attention, nq != nk allowed) or of the LocalState
@@ -1269,6 +1273,23 @@ int asx_op_group_norm(asx_engine *e, const char *family, const asx_group_norm_de
  * per 64-key tile of K, a running one per tile of V, none for the probabilities; 1.16-1.31x, profiles/r05_attention_f16x3.txt).
  * conv_wino6_kernel too (U scaled per (position, output channel) at load, V by one running exponent per (wave, tile row);
  * 1.04-1.11x, profiles/r05_wino6_f16x3.txt).  0 = bf16 x 6 (exact three-way split) in all of them.
+ * "gemm_f16x1" (an option only, no environment variable; default 0): REDUCED PRECISION, OPT-IN, not the reference's bits.  1 = "fp16 x 1":
+ * where the fp16 x 3 form of the plain row GEMM (fp32 operands; not its GATHER mode, not the fused-output form) and of the Roformer attention
+ * (attention6_kernel; not mha6_kernel) would run -- so only while "gemm_bf16x6" and "gemm_f16x3" are on -- ONE fp16 product per multiply-add
+ * instead of three.  The arithmetic contract: operands are scaled by the SAME power-of-two block exponents as fp16 x 3 (x: one running
+ * exponent per row; W: one per group of four output columns, its largest |w| in [2^14, 2^15); attention: one per query, per 64-key tile of K,
+ * a running one per tile of V, 2^14 for the probabilities); each scaled operand is rounded ONCE, round-to-nearest-even, to fp16,
+ * h = RNE_f16(v 2^e), and there is no l part; a product is wh xh on v_mfma_f32_16x16x32_f16; accumulation, exponent drops and rises, epilogue
+ * (bias, scale, shift, activation, residual, rotary, gates), softmax (online max, exp, sum) and normalisation are the fp32 code of the
+ * fp16 x 3 form, expression for expression.  Hence: an element that stays in fp16's normal range under its block exponent (every non-zero x
+ * within 2^-26 of its row's running maximum, every w within 2^-28 of its group's) enters as itself rounded to 11 significant bits
+ * (m, ex = frexp(v); ldexp(rint(m * 2048) / 2048, ex)), and for such inputs a launch gives the float64 product of the rounded operands up to
+ * fp32 accumulation; smaller elements carry an absolute error of at most 2^-25 in scaled units (below 2^-37 of the row maximum); no overflow
+ * and no flush of a whole row, unlike a plain half() cast; Inf / NaN rows poison themselves only.  In attention Q, K, V and the
+ * probabilities handed to the PV product are rounded once each (P relative to the running maximum of its key tile); logits, max, exp, sums
+ * and the rescale between key tiles stay fp32.  Activations, norms, softmax, rotary, STFT / iSTFT stay fp32 as under every setting.  The
+ * h-only weight image (half the bytes) is cached beside the two-part one per weight tensor and dropped with it.  0 (default): every launch is
+ * what it is without the option, bit for bit.  A captured hipGraph keeps the arithmetic it was captured with.
  * The split weight images these kernels read are built on the FIRST forward after a load (one small kernel + one stream
  * synchronise per weight tensor) and belong to the engine: they are freed only when this engine's weights are re-loaded or the engine
  * is destroyed, never by another engine of the process -- so a hipGraph captured after one warm-up call stays valid while other

@@ -23,6 +23,7 @@ DEMUCS_6_SOURCE_MAPPER = {CommonSeparator.BASS_STEM: 0, CommonSeparator.DRUM_STE
 
 
 class DemucsSeparator(CommonSeparator):
+    _autocast_refusal = CommonSeparator._AUTOCAST_ONLY_ROFORMER
     _complement_rate_refusal = "every stem is an output of the model; none of them is formed as the mix minus another stem"
 
     def __init__(self, common_config, arch_config):

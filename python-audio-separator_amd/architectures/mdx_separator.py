@@ -15,6 +15,8 @@ from ..mdx import MDXDemixer
 
 
 class MDXSeparator(CommonSeparator):
+    _autocast_refusal = CommonSeparator._AUTOCAST_ONLY_ROFORMER
+
     def __init__(self, common_config, arch_config):
         super().__init__(config=common_config)
         self._read_options(arch_config, (("segment_size", None), ("overlap", None), ("batch_size", 1), ("hop_length", None),

@@ -29,6 +29,11 @@ class MDXCSeparator(CommonSeparator):
         self.logger.debug(f"MDXC arch params: batch_size={self.batch_size}, segment_size={self.segment_size}, overlap={self.overlap}, "
                           f"override_model_segment_size={self.override_model_segment_size}, pitch_shift={self.pitch_shift}")
         self.is_roformer = getattr(self, "is_roformer_model", False)
+        if not self.is_roformer:                # TFC-TDF v3: convs and the fused TDF, no single-product kernels (common_separator.py: asx_autocast)
+            if self.asx_autocast == "fp16":
+                raise ValueError(f"asx_autocast='fp16' is not supported by {type(self).__name__} with a TFC-TDF v3 model: {self._AUTOCAST_ONLY_ROFORMER}")
+            if self.asx_autocast == "follow":
+                self.logger.info(f"asx_autocast='follow' does nothing for a TFC-TDF v3 model: {self._AUTOCAST_ONLY_ROFORMER}")
         self._keep_configs(common_config, arch_config)
         self._demixers = {}                 # one engine per chunk geometry (override_model_segment_size may flip per file)
 
@@ -126,6 +131,7 @@ class MDXCSeparator(CommonSeparator):
         self._mix_scale = self._mix_factor(mix_d, None)
         eng.normalize_dev(mix_d.data_ptr(), 2 * n, thr, amp, stream=st)
         names, stems_d = dm.demix_dev(mix_d)
+        self.last_arithmetic = dm.last_arithmetic
         kind, entries = self._stem_plan(names)
         entries = [(name, names.index(key)) for name, key in entries]
         if kind != "single":
@@ -200,6 +206,7 @@ class MDXCSeparator(CommonSeparator):
         self._mix_scale = self._mix_factor(None, mix)
         norm = lambda w: dm.engine.normalize(w, self.normalization_threshold, self.amplification_threshold)   # noqa: E731
         source = dm.demix(norm(np.ascontiguousarray(mix, np.float32)))
+        self.last_arithmetic = dm.last_arithmetic
         kind, entries = self._stem_plan(list(source) if isinstance(source, dict) else [None])
         # (the one array of a "single" plan goes to the writer as it is; every other stem is normalised when it is fetched)
         return self._emit_plan(kind, entries, lambda key: source.T if key is None else norm(source[key]).T, custom_output_names)
@@ -291,6 +298,8 @@ class MDXCSeparator(CommonSeparator):
                 continue
             dm = self._demixer(key)
             eng = dm.engine
+            dm._set_arithmetic()                         # one arithmetic per pooled call (every demix below sets the same again)
+            self._pool_arithmetic = dm.last_arithmetic   # -> every file's per-file state (CommonSeparator._pool_files)
             if host_only and self.pitch_shift != 0:
                 for i in idx:
                     try:

@@ -35,6 +35,7 @@ class VRSeparator(CommonSeparator):
     _output_rate_refusal = ("its inputs at other rates are converted on the host with the band's own res_type, which the writer-side "
                             "converter does not mirror (a follow-up); leave asx_output_rate at 'model'")
     _complement_rate_refusal = "this plugin writes every stem at the model's rate (it refuses asx_output_rate='input')"
+    _autocast_refusal = CommonSeparator._AUTOCAST_ONLY_ROFORMER
 
     def __init__(self, common_config, arch_config: dict):
         super().__init__(config=common_config)

@@ -80,6 +80,9 @@ class CommonSeparator:
         self.asx_output_rate = self._output_rate_mode(config)          # the rate and frame count stems are written at
         self.asx_complement_rate = self._complement_rate_mode(config, self.asx_output_rate)   # the rate the complement stem is formed at
         self._complement_noted = False           # (the "nothing to do for this model" note: once per instance)
+        self.asx_autocast = self._autocast_mode(config)                # whether the Roformer engine runs its single-product kernels
+        if self.asx_autocast == "follow" and self._autocast_refusal:
+            self.logger.info(f"asx_autocast='follow' does nothing on {type(self).__name__}: {self._autocast_refusal}")
         self.file_timings = {}
         self._pending_writes = []                # (thread, error box) of container writes in flight
         # how the last stem reached its encoder: "flac_device_resident" | "flac_device_upload" (.flac), "wav_device_resident" (a .wav of
@@ -193,6 +196,38 @@ class CommonSeparator:
                              "the file's rate only where the stems are written at it")
         return mode
 
+    # ``common_config["asx_autocast"]``: the arithmetic of the Roformer engine's linears and attention.  "off" (the default): the fp32-grade
+    # fp16 x 3 kernels, and the engine option is never touched -- also inside an ambient ``torch.autocast`` context.  "fp16": every engine call
+    # of the plugin runs the single-product kernels (engine option "gemm_f16x1", include/asx.h: REDUCED PRECISION, opt-in, not the reference's
+    # bits; activations, norms, softmax, rotary, STFT / iSTFT stay fp32, which the reference's autocast does not guarantee).  "follow": as
+    # "fp16" for a call made while ``torch.is_autocast_enabled("cuda")`` is true and as "off" otherwise -- this is how the orchestrator's
+    # ``use_autocast`` (it wraps ``separate`` in ``torch.autocast``) reaches a plugin.  Only the Roformer engine has single-product kernels:
+    # the plugins that say so in ``_autocast_refusal`` refuse "fp16" and accept "follow" without effect (one info line), so an orchestrator
+    # that passes "follow" to every model keeps working.  The option is per engine and set before every engine call; a captured graph
+    # (sharding.ShardWorkspace: its graph keys do not include engine options) keeps the arithmetic it was captured with.  No environment override.
+    AUTOCAST_MODES = ("off", "fp16", "follow")
+    _autocast_refusal = None           # (a plugin whose engine has no single-product kernels says so)
+    _AUTOCAST_ONLY_ROFORMER = "only the Roformer engine has single-product kernels"
+
+    @classmethod
+    def _autocast_mode(cls, config) -> str:
+        mode = config.get("asx_autocast") or "off"
+        if mode not in cls.AUTOCAST_MODES:
+            raise ValueError(f"asx_autocast must be one of {cls.AUTOCAST_MODES}, not {mode!r}")
+        if mode == "fp16" and cls._autocast_refusal:
+            raise ValueError(f"asx_autocast='fp16' is not supported by {cls.__name__}: {cls._autocast_refusal}")
+        return mode
+
+    @staticmethod
+    def _autocast_active(mode) -> bool:
+        """Whether a call made now runs the single-product kernels under ``mode``."""
+        if mode == "fp16":
+            return True
+        if mode == "follow":
+            import torch
+            return bool(torch.is_autocast_enabled("cuda"))
+        return False
+
     def _complement_stem_name(self):
         """Hook: the name of the stem this plugin forms as ``s * mix - k * (its model stem)`` under the current options, None when it has
         none (the base class, a multi-stem model, a spectral inversion)."""
@@ -283,6 +318,7 @@ class CommonSeparator:
         # asx_complement_rate = "input": the file's own decoded mix [2, F] (a CUDA tensor, or a host array on the host route) while the
         # complement is still to be written, the factor the mix normalise applied, and what the plugin registered (_register_complement)
         self._file_mix, self._mix_scale, self._complement = None, 1.0, None
+        self.last_arithmetic = None   # "fp16x3" | "fp16x1": what the Roformer engine ran this file's linears and attention on (asx_autocast)
 
     # ---- steps every architecture's separate() shares ---------------------------------------------------------------
     def _read_options(self, arch_config: dict, table):
@@ -701,6 +737,10 @@ class CommonSeparator:
             for (_, state, _, _), scale in zip(loaded, self._pool_mix_scales):
                 state["_mix_scale"] = scale
             self._pool_mix_scales = None
+        if getattr(self, "_pool_arithmetic", None) is not None:       # (a plugin that records the arithmetic of its pooled call: one per call)
+            for _, state, _, _ in loaded:
+                state["last_arithmetic"] = self._pool_arithmetic
+            self._pool_arithmetic = None
         return [(i, state, dev_mix, file_stems) for (i, state, dev_mix, _), file_stems in zip(loaded, stems)], left_out
 
     def _file_failed(self, i, path, e):                # this file only

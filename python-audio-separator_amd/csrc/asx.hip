@@ -96,6 +96,7 @@ static const struct EngineOption {
     {"winograd_bf16x6", &asx_engine::wino6, &EngineKnobs::wino6, opt_nonneg},
     {"gemm_bf16x6", &asx_engine::gemm_bf16x6, &EngineKnobs::gemm_bf16x6, opt_onoff},   // this engine only (round 5; it was process-wide before)
     {"gemm_f16x3", &asx_engine::gemm_f16x3, &EngineKnobs::gemm_f16x3, opt_onoff},
+    {"gemm_f16x1", &asx_engine::gemm_f16x1, &EngineKnobs::gemm_f16x1, opt_onoff},   // opt-in reduced precision: one fp16 product per multiply-add (include/asx.h)
     {"conv_direct_f16x3", &asx_engine::conv3h, &EngineKnobs::conv3h, opt_nonneg},
     {"conv_fuse_input", &asx_engine::conv_fuse_input, &EngineKnobs::conv_fuse_input, opt_onoff},
     {"tdf_fuse_output", &asx_engine::tdf_fuse_output, &EngineKnobs::tdf_fuse_output, opt_onoff},
@@ -1816,7 +1817,7 @@ int asx_op_attention(asx_engine *e, const float *qkv_host, const float *gate_hos
   AttnArgs a{};
   const int64_t nseq = rof_attn_geometry(a, B, T, Fb, axis == 0);
   if (v == AV_AUTO) v = rof_attn_variant(e, a.len);
-  REQUIRE(v >= AV_ATTN2 && v <= AV_ATTN6H_QW2, "asx_op_attention: '%s' is not a Roformer attention variant", k_attn_variant_names[v]);
+  REQUIRE((v >= AV_ATTN2 && v <= AV_ATTN6H_QW2) || v == AV_ATTN6S || v == AV_ATTN6S_QW2, "asx_op_attention: '%s' is not a Roformer attention variant", k_attn_variant_names[v]);
   const int inner = heads * 64;
   DevBuf dqkv, dgate, dout;
   BufGuard g{{&dqkv, &dgate, &dout}};
@@ -3391,6 +3392,8 @@ int asx_counter(const asx_engine *e, const char *name, int64_t *out) {
   const std::string nm(name);
   if (nm == "tdf3_launches") *out = (int64_t)g_tdf3_launches.load();
   else if (nm == "tdf3h_launches") *out = (int64_t)g_tdf3h_launches.load();
+  else if (nm == "tdf3s_launches") *out = (int64_t)g_tdf3s_launches.load();
+  else if (nm == "attn6s_launches") *out = (int64_t)g_attn6s_launches.load();
   else if (nm == "attn6_launches") *out = (int64_t)g_attn6_launches.load();
   else if (nm == "attn6h_launches") *out = (int64_t)g_attn6h_launches.load();
   else if (nm == "tdf3_gather_launches") *out = (int64_t)g_tdf3_gather_launches.load();

@@ -20,12 +20,14 @@ enum AttnVariant {
   AV_MHA6H,        // mha6_kernel<dh / 16, 1, true>        (fp16 x 3)
   AV_MHA6H_WIDE,   // mha6_kernel<dh / 16, 2, true>
   AV_HD_LOCAL,     // hd_local_attn_kernel<dh>             (LocalState, narrow heads: dh 4, 8, 12, 24)
+  AV_ATTN6S,       // attention6_kernel<1, true, true>     (fp16 x 1: single product, reduced precision, opt-in)
+  AV_ATTN6S_QW2,   // attention6_kernel<2, true, true>
   AV_COUNT
 };
 
 static const char *const k_attn_variant_names[AV_COUNT] = {"auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h",
                                                            "attn6h_qw2", "mha", "mha_db", "mha6", "mha6_wide", "mha6h", "mha6h_wide",
-                                                           "hd_local"};
+                                                           "hd_local", "attn6s", "attn6s_qw2"};
 
 static int attn_variant_parse(const char *name, int *v) {
   for (int i = 0; i < AV_COUNT; ++i)
@@ -59,7 +61,7 @@ static int64_t rof_attn_geometry(AttnArgs &a, int B, int T, int Fb, bool time_ax
 
 // Fills a.nqt and launches `v` (one of AV_ATTN2 .. AV_ATTN6H_QW2) over nseq sequences.
 static int rof_attn_launch(asx_engine *e, int v, AttnArgs a, int64_t nseq, hipStream_t s) {
-  const int qw = (v == AV_ATTN2_QW2 || v == AV_ATTN6_QW2 || v == AV_ATTN6H_QW2) ? 2 : 1;
+  const int qw = (v == AV_ATTN2_QW2 || v == AV_ATTN6_QW2 || v == AV_ATTN6H_QW2 || v == AV_ATTN6S_QW2) ? 2 : 1;
   a.nqt = (a.len + 64 * qw - 1) / (64 * qw);
   const dim3 grid((unsigned)((int64_t)a.nqt * a.heads * nseq));   // 1-D, XCD-aware (kernels_rof.h)
   switch (v) {
@@ -70,13 +72,17 @@ static int rof_attn_launch(asx_engine *e, int v, AttnArgs a, int64_t nseq, hipSt
     case AV_ATTN6_QW2: hipLaunchKernelGGL(attention6_kernel<2>, grid, dim3(256), 0, s, a); break;
     case AV_ATTN6H: hipLaunchKernelGGL((attention6_kernel<1, true>), grid, dim3(256), 0, s, a); break;
     case AV_ATTN6H_QW2: hipLaunchKernelGGL((attention6_kernel<2, true>), grid, dim3(256), 0, s, a); break;
+    case AV_ATTN6S: hipLaunchKernelGGL((attention6_kernel<1, true, true>), grid, dim3(256), 0, s, a); break;
+    case AV_ATTN6S_QW2: hipLaunchKernelGGL((attention6_kernel<2, true, true>), grid, dim3(256), 0, s, a); break;
     default: set_err("attention variant '%s' is not a Roformer attention", k_attn_variant_names[v]); return ASX_ERR_INVALID;
   }
   if (v >= AV_ATTN6) {
-    const bool h3 = v == AV_ATTN6H || v == AV_ATTN6H_QW2;
+    const bool s1 = v == AV_ATTN6S || v == AV_ATTN6S_QW2;
+    const bool h3 = s1 || v == AV_ATTN6H || v == AV_ATTN6H_QW2;
     g_attn6_launches.fetch_add(1);
     if (h3) g_attn6h_launches.fetch_add(1);
-    e->prof_nprod = h3 ? 3 : 6;
+    if (s1) g_attn6s_launches.fetch_add(1);
+    e->prof_nprod = s1 ? 1 : (h3 ? 3 : 6);
   }
   return ASX_OK;
 }

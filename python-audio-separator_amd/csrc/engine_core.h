@@ -282,6 +282,10 @@ struct asx_engine {
   // bf16 x 6 form on finite data (profiles/r05_gemm_f16x3.txt, r05_attention_f16x3.txt, r05_wino6_f16x3.txt).  0: bf16 x 6 (exact
   // three-way split) everywhere.  ASX_GEMM_F16X3 or asx_set_option("gemm_f16x3", n).
   int gemm_f16x3 = 1;
+  // 1: where the fp16 x 3 form of the row GEMM (launch_tdf3, fp32 operands) and of the Roformer attention would run, run the SINGLE-PRODUCT
+  // form instead -- reduced precision, opt-in (kernels_gemm3.h: "fp16 x 1"; include/asx.h).  No effect unless gemm_bf16x6 > 0 and gemm_f16x3 > 0.
+  // asx_set_option("gemm_f16x1", n) only: no environment name.
+  int gemm_f16x1 = 0;
   // 3x3 TFC convs with at least this many input channels run Winograd F(2x2,3x3) on the bf16 pipe (conv_wino6_kernel, kernels_wino6.h)
   // when "winograd" is 3 and "gemm_bf16x6" is on; 0 = never.  Default 144: measured faster than conv_wino3_kernel from level 2 of the
   // HQ_3 net down, equal on level 1, slower on level 0 (profiles/r05_wino6_forms.txt).  ASX_WINO6 or asx_set_option("winograd_bf16x6", n).

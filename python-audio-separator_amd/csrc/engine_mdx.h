@@ -810,9 +810,11 @@ static void launch_tdf2(const TdfDmaArgs &a, hipStream_t s) {
 // launches of tdf3_kernel since the process started (tests assert that the path under test is the one that ran)
 static std::atomic<long long> g_tdf3_launches{0};
 static std::atomic<long long> g_tdf3h_launches{0};   // ... of which on the fp16 x 3 arithmetic (plain and GATHER mode)
+static std::atomic<long long> g_tdf3s_launches{0};   // ... of which on the single-product (fp16 x 1) arithmetic: counted by tdf3h_launches as well
 static std::atomic<long long> g_tdf3ps_launches{0};  // ... of which read x as a pair image (operands split by their producer)
 static std::atomic<long long> g_attn6_launches{0};   // launches of attention6_kernel (kernels_rof.h) / mha6_kernel (kernels_ht.h)
 static std::atomic<long long> g_attn6h_launches{0};  // ... of which on the fp16 x 3 arithmetic
+static std::atomic<long long> g_attn6s_launches{0};  // ... of which on the single-product (fp16 x 1) arithmetic: counted by attn6h_launches as well
 
 // The split image of a weight matrix is built on first use and cached PER ENGINE by (pointer, N, K, cin) (asx_engine::w3).  Every
 // entry point that uploads or frees weights of an engine flushes that engine's images (w3_flush) -- an address reused by another tensor
@@ -853,11 +855,14 @@ static const u32x4 *w3_image(asx_engine *e, const float *w, int N, int K, hipStr
   const int nst = cin > 0 ? (K / cin) * ((cin + 31) / 32) : 0;
   const int ntiles = (N + 15) / 16, nk = cin > 0 ? ((nst + 1) & ~1) : ((K + 63) / 64) * 2;   // an even number of 32-wide stages (zero padded)
   W3Entry en{w, N, K, cin, kind, nullptr};
-  const size_t bytes = kind == 1 ? (size_t)ntiles * nk * 2 * 1024 + (size_t)ntiles * 16 : (size_t)ntiles * nk * 3 * 1024;   // kind 1: + four exponents per tile
+  // kind 1 (fp16 x 3: h and l) / kind 2 (fp16 x 1: h only): + four exponents per tile
+  const size_t bytes = kind != 0 ? (size_t)ntiles * nk * (kind == 1 ? 2 : 1) * 1024 + (size_t)ntiles * 16 : (size_t)ntiles * nk * 3 * 1024;
   if (hipMalloc(&en.img, bytes) != hipSuccess) return nullptr;
   const int64_t total = (int64_t)ntiles * nk * 64;
-  if (kind == 1)
-    hipLaunchKernelGGL(w3h_split_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, w, reinterpret_cast<u32x4 *>(en.img), N, K, ntiles, cin, nst);
+  if (kind == 2)
+    hipLaunchKernelGGL(w3h_split_kernel<1>, dim3((unsigned)ntiles), dim3(256), 0, s, w, reinterpret_cast<u32x4 *>(en.img), N, K, ntiles, cin, nst);
+  else if (kind == 1)
+    hipLaunchKernelGGL(w3h_split_kernel<2>, dim3((unsigned)ntiles), dim3(256), 0, s, w, reinterpret_cast<u32x4 *>(en.img), N, K, ntiles, cin, nst);
   else
     hipLaunchKernelGGL(w3_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, reinterpret_cast<u32x4 *>(en.img), N, K,
                      total, cin, nst);
@@ -878,9 +883,10 @@ static bool tdf3_ok(const asx_engine *e, const TdfDmaArgs &d) {
          d.N > 64 && lda % 4 == 0 && ldy % 4 == 0 && ldr % 4 == 0 && a16(d.x) && a16(d.w) && a16(d.y) && (!d.res || a16(d.res)) &&
          (!d.bias || a16(d.bias)) && (uint64_t)16 * (uint64_t)ldy * 4 < (1ull << 31) && (uint64_t)16 * (uint64_t)ldr * 4 < (1ull << 31);
 }
-template <int NREP, int MREP, int ABL, bool H = false, bool PS = false>
+// S: the single-product form (kernels_gemm3.h; w3 is then the h-only image, kind 2)
+template <int NREP, int MREP, int ABL, bool H = false, bool PS = false, bool S = false>
 static void launch_tdf3_abl(const TdfDmaArgs &a0, const u32x4 *w3, hipStream_t s) {
-  constexpr int BM = 16 * MREP, BN = 64 * NREP, LDS_BYTES = H ? tdf3h_lds_bytes(BM) : 2 * 3 * BM * 64;
+  constexpr int BM = 16 * MREP, BN = 64 * NREP, LDS_BYTES = H ? tdf3h_lds_bytes(BM, S ? 1 : 2) : 2 * 3 * BM * 64;
   TdfDmaArgs a = a0;
   const int64_t nbm = (a.M + BM - 1) / BM;
   const int nbn = (a.N + BN - 1) / BN;
@@ -894,15 +900,17 @@ static void launch_tdf3_abl(const TdfDmaArgs &a0, const u32x4 *w3, hipStream_t s
   // x loads, splits and LDS stores per MFMA (kernels_gemm3.h, template parameter NW).  ASX_TDF3_NW8=0: A/B
   if constexpr (H && !PS && ABL == 0 && NREP == 3 && MREP == 8) {
     if (knobs().tdf3_nw8 && a.N == 384 && a.yexp == nullptr) {        // (a pair-image producer writes one exponent span per 192-column tile: the 4-wave form)
-      hipLaunchKernelGGL((tdf3_kernel<3, 8, 0, false, true, false, 8>), dim3((unsigned)nbm), dim3(512), LDS_BYTES, s, a, w3, RowGather{});
+      hipLaunchKernelGGL((tdf3_kernel<3, 8, 0, false, true, false, 8, false, S>), dim3((unsigned)nbm), dim3(512), LDS_BYTES, s, a, w3, RowGather{});
       g_tdf3_launches.fetch_add(1);
       g_tdf3h_launches.fetch_add(1);
+      if (S) g_tdf3s_launches.fetch_add(1);
       return;
     }
   }
-  hipLaunchKernelGGL((tdf3_kernel<NREP, MREP, ABL, false, H, PS>), dim3((unsigned)(nbm * nbn)), dim3(256), LDS_BYTES, s, a, w3, RowGather{});
+  hipLaunchKernelGGL((tdf3_kernel<NREP, MREP, ABL, false, H, PS, 4, false, S>), dim3((unsigned)(nbm * nbn)), dim3(256), LDS_BYTES, s, a, w3, RowGather{});
   g_tdf3_launches.fetch_add(1);
   if (H) g_tdf3h_launches.fetch_add(1);
+  if (S) g_tdf3s_launches.fetch_add(1);
   if (PS) g_tdf3ps_launches.fetch_add(1);
 }
 // GATHER mode (kernels_gemm3.h): stride-1 convolutions of the channels-last nets as implicit GEMMs on the same kernel
@@ -943,9 +951,15 @@ static bool launch_tdf3(asx_engine *e, const TdfDmaArgs &a, hipStream_t s) {
   // ASX_F16X3_N: a bisection aid, kept (tools/debug_rof_race.py found the rotary-epilogue anomaly with it)
   const int abl0 = knobs().tdf3_abl, only_n = knobs().f16x3_n;
   const bool h = e->gemm_f16x3 > 0 && abl0 == 0 && (only_n == 0 || (only_n > 0 ? a.N == only_n : a.N != -only_n));
-  const u32x4 *w3 = w3_image(e, a.w, a.N, a.K, s, 0, h ? 1 : 0);
+  // option "gemm_f16x1": one fp16 product instead of three, wherever the fp16 x 3 form would run on fp32 operands (pair images keep three)
+  const bool s1 = h && e->gemm_f16x1 > 0 && a.xexp == nullptr && a.yexp == nullptr;
+  const u32x4 *w3 = w3_image(e, a.w, a.N, a.K, s, 0, s1 ? 2 : (h ? 1 : 0));
   if (!w3) return false;                               // out of memory for the image: the caller falls back to the fp32 kernels
-  e->prof_nprod = h ? 3 : 6;
+  e->prof_nprod = s1 ? 1 : (h ? 3 : 6);
+  if (s1) {
+    launch_tdf3_abl<NREP, MREP, 0, true, false, true>(a, w3, s);
+    return true;
+  }
   if ((a.xexp != nullptr || a.yexp != nullptr) && !h) {
     // a pair image is only ever set up behind tdf3h_will_run(): reaching this line means the two disagree -- stop rather than multiply garbage
     fprintf(stderr, "asx: pair-image operands on a launch that is not on the fp16 x 3 row GEMM (N=%d K=%d)\n", a.N, a.K);

@@ -257,8 +257,9 @@ static int rof_attn_variant(const asx_engine *e, int len) {
   // bf16 x 6 form (kernels_rof.h: attention6_kernel) under the process-wide switch of the row GEMM; ASX_ATTN6=0: A/B
   if (k.attn6 && e->gemm_bf16x6 > 0) {
     const bool h3 = e->gemm_f16x3 > 0;           // fp16 x 3 arithmetic (kernels_rof.h: template parameter H)
-    if (k.attn6_qw >= 2 && len > 128) return h3 ? AV_ATTN6H_QW2 : AV_ATTN6_QW2;
-    return h3 ? AV_ATTN6H : AV_ATTN6;
+    const bool s1 = h3 && e->gemm_f16x1 > 0;     // single-product arithmetic (template parameter S), option "gemm_f16x1"
+    if (k.attn6_qw >= 2 && len > 128) return s1 ? AV_ATTN6S_QW2 : (h3 ? AV_ATTN6H_QW2 : AV_ATTN6_QW2);
+    return s1 ? AV_ATTN6S : (h3 ? AV_ATTN6H : AV_ATTN6);
   }
   if (k.attn_qw >= 2 && len > 64) return AV_ATTN2_QW2;   // (measured slower: 357 vs 328 ms)
   if (k.attn_db && len > 128) return AV_ATTN2_DB;   // several key tiles: one barrier per tile (double-buffered K / V)

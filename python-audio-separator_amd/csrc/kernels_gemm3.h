@@ -79,6 +79,19 @@ __device__ __forceinline__ void split3_oct(const f32x4 &a, const f32x4 &b, u32x4
 // power of two before the next stage's products arrive -- rare after a row's first stages, free when nothing changed (x 1.0).  The
 // epilogue multiplies every accumulator by 2^-(e_x[row] + e_w[column group]) (exact) and continues as the bf16 x 6 kernel does.  A row never
 // sees another row's magnitude: an Inf / NaN row poisons itself only, rows 2^100 apart in one tile keep their own precision.
+//
+// ---- fp16 x 1, the single-product form (template parameter S of tdf3_kernel and attention6_kernel; asx_set_option "gemm_f16x1", opt-in) ----
+// REDUCED PRECISION.  Operands are scaled by the SAME power-of-two block exponents as fp16 x 3 (x: one running exponent per row; W: one per group
+// of four output columns, the group's largest |w| in [2^14, 2^15)) and each scaled operand is rounded ONCE, round-to-nearest-even, to fp16:
+// h = RNE_f16(v 2^e).  There is no l part.  A product is wh xh on `v_mfma_f32_16x16x32_f16`; accumulation, exponent drops and rises and the
+// epilogue (bias, scale, shift, activation, residual, rotary) are the fp32 code of the fp16 x 3 form, expression for expression.  Consequences:
+//   * an element that stays in fp16's normal range under its block exponent -- every non-zero x within 2^-26 of its row's running maximum,
+//     every w within 2^-28 of its group's maximum -- enters as itself rounded to 11 significant bits, whatever the exponent
+//     (m, ex = frexp(v); ldexp(rint(m * 2048) / 2048, ex)); for such inputs the result is the float64 product of the rounded operands up to
+//     fp32 accumulation (tests/test_gpu_rowgemm_f16x1.py);
+//   * smaller elements carry an absolute error of at most 2^-25 in scaled units, below 2^-37 of the row maximum;
+//   * no overflow and no flush of a whole row, unlike a plain half() cast: Inf / NaN rows poison themselves only, as in fp16 x 3.
+// One third of the MFMAs, half of the split, half of the LDS and weight-image traffic of fp16 x 3.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
@@ -107,6 +120,15 @@ __device__ __forceinline__ void split2h_oct(const f32x4 &a, const f32x4 &b, int 
   split2h_pair(b.z, b.w, e, hh[3], ll[3]);
   h = (u32x4){hh[0], hh[1], hh[2], hh[3]};
   l = (u32x4){ll[0], ll[1], ll[2], ll[3]};
+}
+
+// single-product form: the scaled value rounded ONCE to fp16 (one v_cvt_pk_f16_f32 per pair after the ldexp), no l part
+__device__ __forceinline__ unsigned split1h_pair(float x0, float x1, int e) {
+  return cvt_pk_f16(__builtin_ldexpf(x0, e), __builtin_ldexpf(x1, e));
+}
+
+__device__ __forceinline__ void split1h_oct(const f32x4 &a, const f32x4 &b, int e, u32x4 &h) {
+  h = (u32x4){split1h_pair(a.x, a.y, e), split1h_pair(a.z, a.w, e), split1h_pair(b.x, b.y, e), split1h_pair(b.z, b.w, e)};
 }
 
 // largest finite |.| of eight floats (NaN never wins a v_max; Inf is masked by the caller's slow path)
@@ -212,8 +234,11 @@ __global__ __launch_bounds__(256) void w3_split_kernel(const float *__restrict__
 // [2^14, 2^15): an output channel never shares an exponent with more than three neighbours (weights with a folded normalisation can
 // differ by orders of magnitude from channel to channel).  The int32 exponents e[ntiles][4] follow the fragments (at img + ntiles *
 // nk * 128).  One workgroup per tile; a thread's items all belong to ONE row (lane & 15 is fixed by tid).
+// NPW = 1: the h-only image of the single-product form (half the bytes; same exponents, at img + ntiles * nk * 64).
+template <int NPW = 2>
 __global__ __launch_bounds__(256) void w3h_split_kernel(const float *__restrict__ w, u32x4 *__restrict__ img, int N, int K, int ntiles,
                                                         int cin = 0, int nst = 0) {
+  static_assert(NPW == 1 || NPW == 2, "fp16 parts per weight");
   const int nk = cin > 0 ? ((nst + 1) & ~1) : ((K + 63) >> 6) * 2;
   const int nt = blockIdx.x, tid = threadIdx.x;
   __shared__ float rowmax[256];
@@ -239,11 +264,11 @@ __global__ __launch_bounds__(256) void w3h_split_kernel(const float *__restrict_
     w3_fetch(w, N, K, cin, nst, nt, it >> 6, it & 63, a, b);
     u32x4 h, l;
     split2h_oct(a, b, e, h, l);
-    u32x4 *o = img + ((int64_t)(nt * nk + (it >> 6)) * 2) * 64 + (it & 63);
+    u32x4 *o = img + ((int64_t)(nt * nk + (it >> 6)) * NPW) * 64 + (it & 63);
     o[0] = h;
-    o[64] = l;
+    if constexpr (NPW == 2) o[64] = l;
   }
-  if (tid < 4) reinterpret_cast<int *>(img + (int64_t)ntiles * nk * 128)[nt * 4 + tid] = gexp[tid];
+  if (tid < 4) reinterpret_cast<int *>(img + (int64_t)ntiles * nk * (64 * NPW))[nt * 4 + tid] = gexp[tid];
 }
 
 template <int V>
@@ -270,7 +295,7 @@ struct RowGather {
 // buffered (a stage's rows are fetched a whole stage before their maximum is needed), 12 * BM + 16 more bytes of LDS: the exponent-drop table of either
 // stage parity, the rows' current exponents and, per stage parity, the last stage some row's exponent dropped at (de_tab[2][BM], ex_tab[BM], fl_tab[2]).
 // rmax[BM] (producer side of a pair image: the rows' largest |y| over the tile's columns) follows them.
-constexpr int tdf3h_lds_bytes(int BM) { return 2 * 2 * BM * 64 + 16 * BM + 16; }
+constexpr int tdf3h_lds_bytes(int BM, int parts = 2) { return 2 * parts * BM * 64 + 16 * BM + 16; }
 // PS (H only; instantiated by experimental builds and tools/proto_gemm3.hip -- measured round 6: the reader alone gains 3-17 %, the nets nothing,
 // profiles/NOTES.md): x is a PAIR IMAGE (kernels_net.h, TdfDmaArgs::xexp) -- split once by the kernel that produced it instead of by every column
 // tile of this GEMM: a chunk's two 16-byte loads are regrouped into its h and l parts (no arithmetic), brought from their span's exponent
@@ -303,15 +328,19 @@ struct TdfCgMap {
 };
 // (end of TdfCgMap)
 
-template <int NREP, int MREP, int ABL = 0, bool GATHER = false, bool H = false, bool PS = false, int NW = 4, bool CG = false>
+// S (H only; engine option "gemm_f16x1"): the SINGLE-PRODUCT form, "fp16 x 1" (header comment above) -- the H build with the l parts taken out:
+// one LDS image per stage buffer, one weight fragment per column tile and stage (the h-only image of w3h_split_kernel<1>), one MFMA per fragment
+// pair.  Exponent rule, tables, accumulator rescale and epilogue are the H code, line for line.
+template <int NREP, int MREP, int ABL = 0, bool GATHER = false, bool H = false, bool PS = false, int NW = 4, bool CG = false, bool S = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void tdf3_kernel(TdfDmaArgs a, const u32x4 *__restrict__ w3, RowGather gq) {
+  static_assert(!S || (H && !GATHER && !PS && !CG && ABL == 0), "single-product form: the plain fp16 row GEMM");
   static_assert(!PS || (H && !GATHER), "pair-image operands: fp16 x 3 arithmetic, plain row GEMM");
   static_assert(NW == 4 || (NW == 8 && MREP == 8 && !GATHER), "eight waves: 128-row tiles of the plain row GEMM");
   static_assert(!CG || (H && !GATHER && !PS && NW == 4 && NREP == 2 && MREP == TdfCgMap::MREP && ABL == 0), "channel-grouped tiles: 192 x 128, fp16 x 3");
   constexpr int NT = 64 * NW;                         // threads
   constexpr int BM = 16 * MREP, BN = 16 * NREP * NW;
   constexpr int XC = BM * 4 / NT;                     // 8-float chunks per thread and stage (BM * 4 chunks / NT threads)
-  constexpr int NP = H ? 2 : 3;                       // parts per operand
+  constexpr int NP = S ? 1 : (H ? 2 : 3);             // parts per operand
   constexpr int PART = BM * 64;                       // bytes of one part image
   constexpr int BUFB = NP * PART;                     // bytes of one stage buffer
   static_assert(MREP % 4 == 0 && XC >= 1, "tile shape");
@@ -509,10 +538,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void tdf3_kernel(TdfDmaAr
       if (e_new != e_old) fl_tab[buf] = ks_of;         // every writer of a stage writes the same value
     }
     char *dst = lds + buf * BUFB;
-    u32x4 h, l;
-    split2h_oct(xr[i][0], xr[i][1], e_new, h, l);
-    *reinterpret_cast<u32x4 *>(dst + xw[i]) = h;
-    *reinterpret_cast<u32x4 *>(dst + PART + xw[i]) = l;
+    if constexpr (S) {
+      u32x4 h;
+      split1h_oct(xr[i][0], xr[i][1], e_new, h);
+      *reinterpret_cast<u32x4 *>(dst + xw[i]) = h;
+    } else {
+      u32x4 h, l;
+      split2h_oct(xr[i][0], xr[i][1], e_new, h, l);
+      *reinterpret_cast<u32x4 *>(dst + xw[i]) = h;
+      *reinterpret_cast<u32x4 *>(dst + PART + xw[i]) = l;
+    }
   };
   // PS: regroup, rescale to the row's exponent, store
   auto split_chunk_ps = [&](int buf, int i) {
@@ -681,14 +716,15 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void tdf3_kernel(TdfDmaAr
       }
     }
     const char *xs = lds + P * BUFB + xf_off;
-    f16x8 xf[2][2];
+    constexpr int NPH = S ? 1 : 2;
+    f16x8 xf[2][NPH];
 #pragma unroll
-    for (int p = 0; p < 2; ++p) xf[0][p] = *reinterpret_cast<const f16x8 *>(xs + p * PART);
+    for (int p = 0; p < NPH; ++p) xf[0][p] = *reinterpret_cast<const f16x8 *>(xs + p * PART);
 #pragma unroll
     for (int m = 0; m < MREP; ++m) {
       if (m + 1 < MREP) {
 #pragma unroll
-        for (int p = 0; p < 2; ++p) xf[(m + 1) & 1][p] = *reinterpret_cast<const f16x8 *>(xs + p * PART + (m + 1) * 1024);
+        for (int p = 0; p < NPH; ++p) xf[(m + 1) & 1][p] = *reinterpret_cast<const f16x8 *>(xs + p * PART + (m + 1) * 1024);
       }
       __builtin_amdgcn_sched_barrier(0);
       const bool has_split = MODE < 2 && !(ABL & 1) && (m >= 1) && ((m - 1) % 3 == 0) && ((m - 1) / 3 < XC);
@@ -696,12 +732,15 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void tdf3_kernel(TdfDmaAr
         if constexpr (PS) split_chunk_ps(P ^ 1, (m - 1) / 3);
         else split_chunk_h(P ^ 1, (m - 1) / 3, ks + 1);
       }
-      const f16x8 xh = xf[m & 1][0], xl = xf[m & 1][1];
+      const f16x8 xh = xf[m & 1][0];
       // smallest terms first; the NREP column tiles of one product are independent accumulators
+      if constexpr (!S) {
+        const f16x8 xl = xf[m & 1][NPH - 1];
 #pragma unroll
-      for (int n = 0; n < NREP; ++n) acc[n][m] = ASX_MFMA_F16(__builtin_bit_cast(f16x8, wr[P][n][1]), xh, acc[n][m]);
+        for (int n = 0; n < NREP; ++n) acc[n][m] = ASX_MFMA_F16(__builtin_bit_cast(f16x8, wr[P][n][NP - 1]), xh, acc[n][m]);
 #pragma unroll
-      for (int n = 0; n < NREP; ++n) acc[n][m] = ASX_MFMA_F16(__builtin_bit_cast(f16x8, wr[P][n][0]), xl, acc[n][m]);
+        for (int n = 0; n < NREP; ++n) acc[n][m] = ASX_MFMA_F16(__builtin_bit_cast(f16x8, wr[P][n][0]), xl, acc[n][m]);
+      }
 #pragma unroll
       for (int n = 0; n < NREP; ++n) acc[n][m] = ASX_MFMA_F16(__builtin_bit_cast(f16x8, wr[P][n][0]), xh, acc[n][m]);
       if (m + 1 < MREP && (ABL & 32)) {                // the next row group's accumulators, behind this group's MFMAs
@@ -711,11 +750,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void tdf3_kernel(TdfDmaAr
 #ifndef ASX_G3_NOSGB
       if (has_split) {
 #pragma unroll
-        for (int g = 0; g < 3 * NREP; ++g) {
+        for (int g = 0; g < (S ? 1 : 3) * NREP; ++g) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
-          __builtin_amdgcn_sched_group_barrier(0x002, PS ? 2 : 5, 0);   // five VALU (two with pair-image operands)
+          __builtin_amdgcn_sched_group_barrier(0x002, S ? 10 : (PS ? 2 : 5), 0);   // five VALU (two with pair-image operands; the single-product form has a third of the MFMAs to hide its shorter split behind)
         }
-        __builtin_amdgcn_sched_group_barrier(0x200, PS ? 2 : 4, 0);     // the chunk's ds_writes (two parts, two table entries)
+        __builtin_amdgcn_sched_group_barrier(0x200, S ? 3 : (PS ? 2 : 4), 0);     // the chunk's ds_writes (two parts, two table entries)
       }
 #endif
       __builtin_amdgcn_sched_barrier(0);
@@ -735,7 +774,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void tdf3_kernel(TdfDmaAr
       stage_h(IntC<0>{}, IntC<1>{}, ks);
       stage_h(IntC<1>{}, IntC<2>{}, ks + 1);
       // back to the operands' own scale: 2^-(e_x[row] + e_w[this lane's four columns]), exact
-      const int *wexp = reinterpret_cast<const int *>(w3 + (int64_t)ntiles * nk * 128);
+      const int *wexp = reinterpret_cast<const int *>(w3 + (int64_t)ntiles * nk * (64 * NP));
       int ex[MREP];
       read_tab(ex_tab, ex);                            // written before the last barrier (the last split is in stage nk - 2)
 #pragma unroll

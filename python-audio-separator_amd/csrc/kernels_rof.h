@@ -492,9 +492,14 @@ __global__ __launch_bounds__(256, (QW == 1 && !DB) ? 3 : 2) void attention2_kern
 // 2^-(e_k + e_q) rides on the logit scale), a running one per tile for V (it only drops, with two bits of headroom; the drop rides on the
 // online-softmax correction the O accumulators are multiplied by anyway), none for P (probabilities are in [0, 1]: absolute error 2^-25).
 // The tile maxima cross the workgroup through eight LDS floats written in front of the barrier that already separates two tiles.
-template <int QW, bool H = false>
+// S (H only; engine option "gemm_f16x1", variants attn6s / attn6s_qw2): the SINGLE-PRODUCT form, "fp16 x 1" of kernels_gemm3.h -- reduced precision,
+// opt-in.  Q, K, V and the probabilities P handed to the PV product are scaled by the exponents of the H form (P: 2^14 behind the running maximum of
+// its key tile) and rounded ONCE to fp16; there are no l parts: one image per operand (16 KB of LDS), one MFMA per fragment pair.  Logits, running
+// maximum, exp, sums and the rescale between key tiles are the fp32 code of the H form.
+template <int QW, bool H = false, bool S = false>
 __global__ __launch_bounds__(256, (QW == 1 ? 3 : 2)) void attention6_kernel(AttnArgs a) {
-  constexpr int NP = H ? 2 : 3;                        // parts per operand
+  static_assert(!S || H, "single-product form: fp16 operands");
+  constexpr int NP = S ? 1 : (H ? 2 : 3);              // parts per operand
   constexpr int PARTB = 64 * 128;                      // bytes of one part image (64 rows x 64 16-bit values)
   __shared__ __attribute__((aligned(16))) char lds6[2 * NP * PARTB];
   __shared__ __attribute__((aligned(16))) float tile_mx[8];   // H: per-wave largest |K|, |V| of the tile about to be staged
@@ -538,7 +543,8 @@ __global__ __launch_bounds__(256, (QW == 1 ? 3 : 2)) void attention6_kernel(Attn
     }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      if constexpr (H) split2h_oct(qv[ks][0], qv[ks][1], eq[g], qf[g][ks][0], qf[g][ks][1]);
+      if constexpr (S) split1h_oct(qv[ks][0], qv[ks][1], eq[g], qf[g][ks][0]);
+      else if constexpr (H) split2h_oct(qv[ks][0], qv[ks][1], eq[g], qf[g][ks][0], qf[g][ks][1]);
       else split3_oct(qv[ks][0], qv[ks][1], qf[g][ks][0], qf[g][ks][1], qf[g][ks][NP - 1]);
     }
   }
@@ -602,7 +608,10 @@ __global__ __launch_bounds__(256, (QW == 1 ? 3 : 2)) void attention6_kernel(Attn
     for (int j = 0; j < 4; ++j) {
       const int row = 4 * kb + j;
       unsigned hh[2], mm[2], ll[2];
-      if constexpr (H) {
+      if constexpr (S) {
+        hh[0] = split1h_pair(kreg[j].x, kreg[j].y, ek);
+        hh[1] = split1h_pair(kreg[j].z, kreg[j].w, ek);
+      } else if constexpr (H) {
         split2h_pair(kreg[j].x, kreg[j].y, ek, hh[0], ll[0]);
         split2h_pair(kreg[j].z, kreg[j].w, ek, hh[1], ll[1]);
       } else {
@@ -612,13 +621,16 @@ __global__ __launch_bounds__(256, (QW == 1 ? 3 : 2)) void attention6_kernel(Attn
       char *d = Kp + row * 128 + ((((c4 >> 1) ^ ((row >> 1) & 7)) << 4) | ((c4 & 1) << 3));
       *reinterpret_cast<uint2 *>(d) = make_uint2(hh[0], hh[1]);
       if constexpr (!H) *reinterpret_cast<uint2 *>(d + PARTB) = make_uint2(mm[0], mm[1]);
-      *reinterpret_cast<uint2 *>(d + (NP - 1) * PARTB) = make_uint2(ll[0], ll[1]);
+      if constexpr (!S) *reinterpret_cast<uint2 *>(d + (NP - 1) * PARTB) = make_uint2(ll[0], ll[1]);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = 4 * c4 + i;
       unsigned hh[2], mm[2], ll[2];
-      if constexpr (H) {
+      if constexpr (S) {
+        hh[0] = split1h_pair(vreg[0][i], vreg[1][i], ev_run);
+        hh[1] = split1h_pair(vreg[2][i], vreg[3][i], ev_run);
+      } else if constexpr (H) {
         split2h_pair(vreg[0][i], vreg[1][i], ev_run, hh[0], ll[0]);
         split2h_pair(vreg[2][i], vreg[3][i], ev_run, hh[1], ll[1]);
       } else {
@@ -628,7 +640,7 @@ __global__ __launch_bounds__(256, (QW == 1 ? 3 : 2)) void attention6_kernel(Attn
       char *d = Vp + row * 128 + (((vslot ^ (((row >> 1) ^ (row >> 3)) & 7)) << 4) | (vhalf << 3));   // V^T swizzle: see the fragment read
       *reinterpret_cast<uint2 *>(d) = make_uint2(hh[0], hh[1]);
       if constexpr (!H) *reinterpret_cast<uint2 *>(d + PARTB) = make_uint2(mm[0], mm[1]);
-      *reinterpret_cast<uint2 *>(d + (NP - 1) * PARTB) = make_uint2(ll[0], ll[1]);
+      if constexpr (!S) *reinterpret_cast<uint2 *>(d + (NP - 1) * PARTB) = make_uint2(ll[0], ll[1]);
     }
   };
   // fragment reads: row 16 t + li, logical slot s -> physical s ^ ((li >> 1) & 7)
@@ -652,7 +664,12 @@ __global__ __launch_bounds__(256, (QW == 1 ? 3 : 2)) void attention6_kernel(Attn
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const char *kp = Kp + mt * 2048 + frow + (((ks * 4 + lk) ^ fsw) << 4);
-        if constexpr (H) {
+        if constexpr (S) {
+          const f16x8 kh = *reinterpret_cast<const f16x8 *>(kp);
+#pragma unroll
+          for (int g = 0; g < QW; ++g) st[g][mt] = ASX_MFMA_F16(kh, __builtin_bit_cast(f16x8, qf[g][ks][0]), st[g][mt]);
+          continue;
+        } else if constexpr (H) {
           const f16x8 kh = *reinterpret_cast<const f16x8 *>(kp), kl = *reinterpret_cast<const f16x8 *>(kp + PARTB);
 #pragma unroll
           for (int g = 0; g < QW; ++g) {
@@ -719,7 +736,23 @@ __global__ __launch_bounds__(256, (QW == 1 ? 3 : 2)) void attention6_kernel(Attn
     // ---- O^T[d, query] += V^T[d, key] P^T[key, query], 32 keys per k step (a V fragment serves every query group) ----
 #pragma unroll
     for (int kp = 0; kp < 2; ++kp) {
-      if constexpr (H) {
+      if constexpr (S) {
+        f16x8 p_h[QW];
+#pragma unroll
+        for (int g = 0; g < QW; ++g) {
+          u32x4 ph;
+          split1h_oct(st[g][2 * kp], st[g][2 * kp + 1], 14, ph);      // x 2^14 as in the H form: rounded once, relative to the tile's running maximum
+          p_h[g] = __builtin_bit_cast(f16x8, ph);
+        }
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const char *vp = Vp + dt * 2048 + frow + (((kp * 4 + lk) ^ (fsw ^ ((2 * dt + (li >> 3)) & 7))) << 4);
+          const f16x8 vh = *reinterpret_cast<const f16x8 *>(vp);
+#pragma unroll
+          for (int g = 0; g < QW; ++g) acc_o[g][dt] = ASX_MFMA_F16(vh, p_h[g], acc_o[g][dt]);
+        }
+        continue;
+      } else if constexpr (H) {
         f16x8 p_h[QW], p_l[QW];
 #pragma unroll
         for (int g = 0; g < QW; ++g) {

@@ -128,6 +128,7 @@ struct EngineKnobs {
 #endif
   int gemm_bf16x6 = knob::num("ASX_GEMM_BF16X6", 1);              // "gemm_bf16x6"
   int gemm_f16x3 = knob::num("ASX_GEMM_F16X3", 1);                // "gemm_f16x3"
+  int gemm_f16x1 = 0;                                             // "gemm_f16x1": an option only (no environment name: tests/test_host_knobs.py pins their set), off unless a caller asks
   int wino6 = knob::clamped("ASX_WINO6", 144, 0);                 // "winograd_bf16x6"
   int conv3h = knob::clamped("ASX_CONV3H", 144, 0);               // "conv_direct_f16x3"
   int conv_fuse_input = 1;                                        // "conv_fuse_input": an option only -- tests/test_host_knobs.py pins the set of environment names this header reads

@@ -290,7 +290,7 @@ SYMBOLS = ["asx_abi_version", "asx_last_error", "asx_device_count", "asx_engine_
 
 # the attention variants of asx_op_attention / asx_op_mha, in the order of their `resolved` index (include/asx.h)
 ATTN_VARIANTS = ("auto", "attn2", "attn2_qw2", "attn2_db", "attn6", "attn6_qw2", "attn6h", "attn6h_qw2", "mha", "mha_db", "mha6",
-                 "mha6_wide", "mha6h", "mha6h_wide", "hd_local")
+                 "mha6_wide", "mha6h", "mha6h_wide", "hd_local", "attn6s", "attn6s_qw2")
 
 
 GCONV_VARIANTS = ("auto", "gg", "halo", "gather")   # asx_op_gconv: `variant`, and resolved[0] as an index (0: nothing ran)

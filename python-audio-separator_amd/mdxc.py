@@ -96,6 +96,9 @@ class MDXCDemixer:
         self.overlap = arch_config.get("overlap", 8)
         self.batch_size = arch_config.get("batch_size", 1)
         self.pitch_shift = arch_config.get("pitch_shift", 0)
+        # ``common_config["asx_autocast"]`` (common_separator.py): "off" | "fp16" | "follow"; the separator that builds this demixer has validated it
+        self.asx_autocast = common_config.get("asx_autocast") or "off"
+        self.last_arithmetic = None             # "fp16x3" | "fp16x1" after an engine call of a Roformer model
         if self.pitch_shift != 0:
             from .vr import reference_wav_resolution
             if reference_wav_resolution() != "sinc_fastest":
@@ -184,6 +187,19 @@ class MDXCDemixer:
         else:
             self.engine.load_v3(self.v3, state_dict)
 
+    def _set_arithmetic(self):
+        """Before every engine call: the engine option "gemm_f16x1" as ``asx_autocast`` asks for THIS call -- set both ways, so that a
+        "follow" instance is back on the fp32-grade kernels outside the autocast context.  "off" never touches the option."""
+        if not self.is_roformer:
+            return
+        if self.asx_autocast == "off":
+            self.last_arithmetic = "fp16x3"
+            return
+        from .common_separator import CommonSeparator
+        on = CommonSeparator._autocast_active(self.asx_autocast)
+        self.engine.set_option("gemm_f16x1", 1 if on else 0)
+        self.last_arithmetic = "fp16x1" if on else "fp16x3"
+
     @staticmethod
     def _checked(mix):
         mix = np.asarray(mix, dtype=np.float32)
@@ -217,6 +233,7 @@ class MDXCDemixer:
         of all mixes share the net passes.  Returns the list of what ``demix(mix)`` returns, bit for bit.  With ``pitch_shift`` it
         is a loop of ``demix`` on host arrays; the pooled round trip is ``demix_many_dev``."""
         mixes = [self._checked(m) for m in mixes]
+        self._set_arithmetic()
         if self.pitch_shift != 0:
             return [self._demix_pitched(m) for m in mixes]
         if self.is_roformer:
@@ -233,6 +250,7 @@ class MDXCDemixer:
         import torch
         if not mixes_d:
             return []
+        self._set_arithmetic()
         st = torch.cuda.current_stream(mixes_d[0].device).cuda_stream
         if self.is_roformer:
             n_out = int(self.engine.rof_cfg.n_out)
@@ -304,6 +322,7 @@ class MDXCDemixer:
     def demix(self, mix: np.ndarray):
         """mdxc_separator.py:257-468 for TFC-TDF models: dict of stems, or the primary array."""
         mix = self._checked(mix)
+        self._set_arithmetic()
         if self.pitch_shift != 0:
             return self._demix_pitched(mix)
         if self.is_roformer:

@@ -159,7 +159,7 @@ static double run_shape(const Shape &sh, int abl, int reps) {
   a.tile_map = g_map;
 
   const int64_t total = (int64_t)ntiles * nk * 64;
-  if (g_h) hipLaunchKernelGGL(w3h_split_kernel, dim3((unsigned)ntiles), dim3(256), 0, 0, dw, dw3, N, K, ntiles);
+  if (g_h) hipLaunchKernelGGL(w3h_split_kernel<2>, dim3((unsigned)ntiles), dim3(256), 0, 0, dw, dw3, N, K, ntiles);
   else hipLaunchKernelGGL(w3_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, dw, dw3, N, K, total);
   CK(hipDeviceSynchronize());
 
@@ -332,7 +332,7 @@ static void run_chain(const char *name, int64_t M, int F, int F8, int C, int T, 
   auto image = [&](const float *dw, int N, int K, u32x4 *&img) {
     const int ntiles = (N + 15) / 16, nk = ((K + 63) / 64) * 2;
     CK(hipMalloc(&img, (size_t)ntiles * nk * 2 * 1024 + (size_t)ntiles * 16));
-    hipLaunchKernelGGL(w3h_split_kernel, dim3((unsigned)ntiles), dim3(256), 0, 0, dw, img, N, K, ntiles);
+    hipLaunchKernelGGL(w3h_split_kernel<2>, dim3((unsigned)ntiles), dim3(256), 0, 0, dw, img, N, K, ntiles);
   };
   image(dw1, F8, F, dw31);
   image(dw2, F, F8, dw32);
@@ -485,7 +485,7 @@ static void run_cg(const char *name, int B, int T, int N, int K, int reps) {
   CK(hipMemset(dout, 0xff, (size_t)B * 4 * T * N * 4));
   const int ntiles = (N + 15) / 16, nk = ((K + 63) / 64) * 2;
   CK(hipMalloc(&dw3, (size_t)ntiles * nk * 2 * 1024 + (size_t)ntiles * 16));
-  hipLaunchKernelGGL(w3h_split_kernel, dim3((unsigned)ntiles), dim3(256), 0, 0, dw, dw3, N, K, ntiles);
+  hipLaunchKernelGGL(w3h_split_kernel<2>, dim3((unsigned)ntiles), dim3(256), 0, 0, dw, dw3, N, K, ntiles);
   CK(hipDeviceSynchronize());
   TdfDmaArgs a{};
   a.x = dx; a.w = dw; a.scale = dsc; a.shift = dsh; a.res = dr; a.y = dy; a.M = M; a.N = N; a.K = K; a.C = C; a.T = T; a.relu = 1;
